@@ -167,6 +167,32 @@ def committed_traffic(precision: int):
                f"{j.get('commit', '?')} on these kernel sources ({j.get('src_sha16')})")
 
 
+DUMP_LIMIT = 64 << 20  # bytes written by --dump-outputs, all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each tensor of `arrays` as <path>/<name>.npy (float64 stays float64, everything else float32).
+    Past DUMP_LIMIT bytes in all, every tensor keeps the same fraction of its samples (leading dimension), picked by a
+    seeded permutation so that two runs keep the same rows.  Returns {name: {"shape", "rows"}} for the JSON line, with
+    rows = the kept sample indices, or "all"."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    budget = DUMP_LIMIT - 1024 * len(arrays)  # room for the .npy headers
+    info = {}
+    for name, v in arrays.items():
+        rows = "all"
+        if total > budget:
+            n = v.shape[0]
+            keep = max(1, n * budget // total)
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v, rows = v[idx], idx.tolist()
+        np.save(os.path.join(path, name + ".npy"), v.contiguous().numpy())
+        info[name] = {"shape": list(v.shape), "rows": rows}
+    return info
+
+
 def time_block(fn, iters=20):
     for _ in range(3):
         fn()
@@ -400,13 +426,14 @@ def dry_run(a, world, rank) -> None:
     final = dmod.all_gather_ragged(x, B * world)
     assert final.shape[0] == B * world and torch.equal(final[:, 0, 0], torch.arange(B * world, dtype=torch.float32))
     if rank == 0:
+        extra = {"dump_outputs": dump_outputs(a.dump_outputs, {"sample": final})} if a.dump_outputs else {}
         print(json.dumps({"metric": "denoising-steps/sec (B=32, T=196, 263-d, 8 experts)", "value": a.steps / dt * world * (B / 32.0),
                           "unit": "denoising-steps/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
                           "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                           "dtype": "none", "data": "synthetic", "dry_run": True,
                           "config": {"workload": "dry run: stand-in step on the CPU, gloo ranks (launcher rehearsal)",
-                                     "global_batch": B * world, "parallelism": f"batch-shard x{world}, weights replicated"}}),
-              flush=True)
+                                     "global_batch": B * world, "parallelism": f"batch-shard x{world}, weights replicated"},
+                          **extra}), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
@@ -456,7 +483,7 @@ def other_config_line(cfg_name, sampler, schedule, a, dev, steps=8, warmup=2, ba
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="small", choices=list(CONFIGS))
     ap.add_argument("--precision", type=int, default=1, choices=[1, 2, 3, 4, 5],
@@ -481,7 +508,12 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true", help="skip the configs[2] / configs[3] timings (big model) of the N = 1 line")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / timing-protocol rehearsal on the CPU: gloo ranks, a stand-in step, no GPU and no model")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (sample = x_{t-1}, pred_xstart) of every "
+                         "rank's samples as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: this process only LAUNCHES (it never touches a GPU); the ranks are N fresh
@@ -557,6 +589,8 @@ def main():
     # the path's single collective: gather the motion tensor of every shard (RCCL over xGMI)
     final = dmod.all_gather_ragged(r.xx[:B].clone(), B * world)
     assert final.shape[0] == B * world and bool(torch.isfinite(final).all())
+    # the last timed step's results, taken before the probes below step the sampler further
+    outputs = {"sample": final, "pred_xstart": dmod.all_gather_ragged(r.x0.clone(), B * world)} if a.dump_outputs else None
 
     if rank == 0:
         _, flop_fwd, flop_moe = CONFIGS[a.config]
@@ -664,6 +698,8 @@ def main():
                 line["configs"]["configs[4] (per GPU)"] = c4
         if world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(host, inputs, a.schedule, a.cfg_scale)
+        if outputs is not None:
+            line["dump_outputs"] = dump_outputs(a.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -59,3 +59,42 @@ def test_committed_traffic_is_reported_only_for_the_sources_it_was_measured_on(m
     assert j is None and "stale" in note
     j, note = bench.committed_traffic(2)
     assert j is None and "no counter profile" in note
+
+
+def test_dump_outputs_writes_every_rank_s_last_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the gathered result of the last timed step as DIR/<name>.npy (float32) and names it
+    in the JSON line; the stand-in step of --dry-run leaves sample row i equal to i, so the file shows the gather order."""
+    import numpy as np
+    for world in (1, 2):
+        d = tmp_path / f"w{world}"
+        r = _run(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--dry-run", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        y = np.load(d / "sample.npy")
+        assert y.dtype == np.float32 and y.shape == (32 * world, 4, 3)
+        assert np.array_equal(y[:, 0, 0], np.arange(32 * world, dtype=np.float32))
+        assert j["dump_outputs"] == {"sample": {"shape": [32 * world, 4, 3], "rows": "all"}}
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_byte_limit(tmp_path, monkeypatch):
+    """Past the limit every array keeps the same seeded choice of samples, and the files together stay within it."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 64 << 10)
+    x = torch.arange(100 * 200, dtype=torch.float32).reshape(100, 200)
+    a = {"sample": x, "pred_xstart": -x.double()}  # 240 kB
+    i1 = bench.dump_outputs(str(tmp_path / "a"), a)
+    i2 = bench.dump_outputs(str(tmp_path / "b"), a)
+    assert i1 == i2 and i1["sample"]["rows"] == i1["pred_xstart"]["rows"]
+    rows = i1["sample"]["rows"]
+    assert 0 < len(rows) < 100 and rows == sorted(set(rows))
+    s, p = np.load(tmp_path / "a" / "sample.npy"), np.load(tmp_path / "a" / "pred_xstart.npy")
+    assert s.dtype == np.float32 and p.dtype == np.float64
+    assert np.array_equal(s[:, 0], np.array(rows, dtype=np.float32) * 200) and np.array_equal(p, -s.astype(np.float64))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 10
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0", "--dry-run"])
+    assert r.returncode != 0 and "--steps" in r.stderr
