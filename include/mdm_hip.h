@@ -108,7 +108,8 @@ typedef struct MdmGemmDesc {
   const float* hn_b;
   uint16_t* C16_lo;
   int32_t hn_l2_tiles;
-  /* fp32-grade kernel: the result as MDM_OP_X2_ROW rows (row stride 2 * ldc 16-bit elements; N % 32 == 0), beside or instead of C */
+  /* fp32-grade kernel: the result as MDM_OP_X2_ROW rows (row stride 2 * ldc 16-bit elements; N % 32 == 0, ldc % 4 == 0), beside or
+   * instead of C.  Must be 16-byte aligned (each lane stores 16 bytes): otherwise mdm_gemm returns MDM_ERR_UNSUPPORTED */
   uint16_t* Cx2;
   /* optional fragment stream of W (mdm_gemm_stream1_pack, format h16): a plain Linear on 16-bit rows (precision 1 / 2, no batch /
    * groups / gather, act NONE or GELU, N % 256 == K % 256 == 0) then runs on the streamed-weight kernel (csrc/gemm_stream.hip);

@@ -380,7 +380,7 @@ bool gemm_x3_dma_eligible(const GemmArgs& a) {
   const bool planes_ok = a.C16 && a.C16_lo && !a.C && a.N % 128 == 0 && (a.ldc % 4) == 0 && (!a.R1 || (a.ldr1 & 3) == 0) &&
                          (!a.R2 || (a.ldr2 & 3) == 0) && ((((uintptr_t)a.C16) | ((uintptr_t)a.C16_lo)) & 7) == 0;
   if (a.C16_lo && !planes_ok) return false;
-  if (a.Cx2 && ((a.N % 32) || (a.ldc % 4) || (((uintptr_t)a.Cx2) & 7) || (a.R1 && (a.ldr1 & 3)) || (a.R2 && (a.ldr2 & 3)) ||
+  if (a.Cx2 && ((a.N % 32) || (a.ldc % 4) || (((uintptr_t)a.Cx2) & 15) || (a.R1 && (a.ldr1 & 3)) || (a.R2 && (a.ldr2 & 3)) ||
                 a.act == ACT_HEADNORM || a.act == ACT_HEADSOFTMAX))
     return false;
   if (a.act == ACT_HEADNORM)

@@ -73,6 +73,12 @@ __device__ __forceinline__ void store_x2_4(uint16_t* row, int k, float a, float 
 // The same when the lanes l and l ^ 1 hold the column groups k and k ^ 4 of ONE row (row kernels, GEMM epilogues): the pair trades
 // halves through a quad-permute (a VALU move) so that the even lane stores the 8 hi values and the odd lane the 8 lo values of their
 // 8 columns as ONE 16-byte store each (two 8-byte stores per lane move the same bytes in twice the store instructions).
+// Preconditions, which no device check enforces (the product build has no device asserts):
+//   * both lanes of a pair are active and call it for the same row: the DPP move reads the partner with old = 0, so a lone lane
+//     stores zeros in place of its partner's half.  Callers guard whole rows and whole column groups -- with N % 32 == 0 a pair's
+//     8 columns are all in range or all out;
+//   * row + x2_col(k & ~7) is 16-byte aligned: the row base (the launch's destination, checked with & 15 by the host-side
+//     eligibility of every GEMM that writes Cx2) and an even row stride (2 * ldc elements with ldc % 4 == 0).
 __device__ __forceinline__ void store_x2_4p(uint16_t* row, int k, float a, float b, float c, float d) {
   uint32_t h0, h1, l0, l1;
   split_bf16(a, b, h0, l0);

@@ -97,7 +97,8 @@ struct Row {
   }
   // MDM_OP_X2_ROW row (include/mdm_hip.h): bf16 hi / lo halves per block of 32 columns, the pre-split operand of the fp32-grade GEMM
   __device__ __forceinline__ void store_x2(uint16_t* __restrict__ p, int D, int lane) const {
-    static_assert(VEC, "x2 rows exist for the vector widths only");
+    // (destination: a workspace buffer the library carves itself, never a C-ABI caller's pointer)
+    static_assert(VEC && NE % 4 == 0, "x2 rows exist for the vector widths only: every lane active, lane pairs hold k and k ^ 4");
 #pragma unroll
     for (int c = 0; c < NE / 4; ++c) store_x2_4p(p, 4 * (lane + 64 * c), e[4 * c + 0], e[4 * c + 1], e[4 * c + 2], e[4 * c + 3]);
   }

@@ -326,6 +326,8 @@ __global__ __launch_bounds__(256) void moe_gate16_kernel(const float* __restrict
           } else if constexpr (HNF == 0) {
             *(f32x4*)((float*)p.hn + ((int64_t)br * M + rc) * D + k) = h;
           } else if constexpr (HNF == 4) {  // x2 rows (MDM_OP_X2_ROW): what the fp32-grade expert GEMM reads without re-splitting
+            // (p.hn is a workspace buffer the library carves itself; all 16 lanes of a row store, past-the-end rows repeat row M - 1)
+            static_assert(D % 32 == 0, "lane pairs of store_x2_4p hold k and k ^ 4 of one 32-column block");
             store_x2_4p((uint16_t*)p.hn + ((int64_t)br * M + rc) * 2 * D, k, h[0], h[1], h[2], h[3]);
           }
         } else if (ok && p.hn_bf16 != 3) {

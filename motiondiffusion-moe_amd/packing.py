@@ -24,9 +24,10 @@ _ALWAYS_X3_LAYER = ("ca_k", "ca_v", "sd_k", "sd_v")
 _MLP_LAYER = ("w1", "w2", "sd_f1", "sd_f2")  # the MFMA-bound GEMMs: expert MLPs and the 4x FFN
 
 
-def format_class(precision: int) -> str:
-    """Packed models are shared between precisions that read the same planes."""
-    return {L.PREC_BF16: "bf16", L.PREC_X3: "bf16", L.PREC_F16: "f16", L.PREC_MIXED: "mixed", L.PREC_FP8: "f8"}[precision]
+def pair_key(name: str) -> str:
+    """PackedModel.wstream1 key of matrix `name`'s (hi, lo) pair stream: never the key of a 16-bit fragment stream (those are the
+    plain kernel_layout() names), so the two formats of MdmPacked.ws cannot be confused."""
+    return "x3:" + name
 
 
 def weight_format(name: str, precision: int, head_dim: int) -> str:
@@ -142,14 +143,15 @@ def _style(out, sd, dst, src):
 
 
 class PackedModel:
-    """Device-resident packed weights + the ctypes ``MdmModel`` that points at them."""
+    """Device-resident packed weights + the ctypes ``MdmModel`` that points at them, for ONE precision: the weight streams it
+    builds (and the ``MdmPacked.ws`` pointers of the model struct) are in the formats that precision's kernels read."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], cfg: dict, eph, proj, device, with_lo: bool = True,
                  counters: Dict[str, torch.Tensor] = None, precision: int = L.PREC_X3):
         from .ops import PackedWeight  # HIP pack kernel
 
         self.cfg = dict(cfg)
-        self.format_class = format_class(precision)
+        self.precision = precision
         head_dim = cfg["latent_dim"] // cfg["num_heads"]
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -218,13 +220,18 @@ class PackedModel:
                         if ws is not None:
                             self.wstream[st + "out3"] = ws
             # fragment streams of the plain per-layer Linears for the streamed-weight GEMM (csrc/gemm_stream.hip): the 16-bit modes of the
-            # big model, whose D x D launches are latency chains on the tile kernel; MDM_GEMM_STREAM=0 keeps the tile kernel (A/B runs)
+            # big model, whose D x D launches are latency chains on the tile kernel; MDM_GEMM_STREAM=0 keeps the tile kernel (A/B runs).
+            # Not the expert matrices: only linear() hands MdmPacked.ws to a 16-bit launch, and the expert GEMMs of those modes take the
+            # fused MLP (self.wstream) or the tile kernel.  self.wstream1 holds every MdmPacked.ws: these under the matrix name, the pair
+            # streams below under pair_key(name)
             self.wstream1 = {}
             if (os.environ.get("MDM_GEMM_STREAM", "1") != "0" and D == 1024
                     and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_FP8)):
                 from .ops import gemm_stream1_pack
                 for kk, t in lay.items():
                     if not kk.startswith("W:L") or t.dim() != 2 or t.shape[1] not in (512, 1024) or t.shape[0] % 256:
+                        continue
+                    if kk.rsplit(".", 1)[1] in ("w1", "w2"):
                         continue
                     fmt = weight_format(kk[2:], precision, head_dim)
                     if fmt not in ("f16", "bf16", "bf16x2"):
@@ -243,7 +250,7 @@ class PackedModel:
                             continue
                         ws = gemm_stream3x_pack(lay["W:" + name].to(dev).reshape(*shape))
                         if ws is not None:
-                            self.wstream1[name] = ws
+                            self.wstream1[pair_key(name)] = ws
             self.layers = (L.Layer * (2 * L_))()
             for li, (pre, tag) in enumerate(layer_tags(L_)):
                 self._fill_layer(self.layers[li], f"L{li}.", pre, counters)
@@ -267,8 +274,11 @@ class PackedModel:
         w = self.W[name]
         p = L.Packed()
         p.hi, p.lo, p.ld = w.hi.data_ptr(), (w.lo.data_ptr() if w.lo is not None else 0), w.Kp
-        if name in getattr(self, "wstream1", {}):
-            p.ws = self.wstream1[name].data_ptr()
+        # MdmPacked.ws: a 16-bit fragment stream (plain Linears of the 16-bit modes) or a (hi, lo) pair stream (expert matrices of
+        # the fp32-grade mode); the two loops above never fill both for one matrix
+        ws = self.wstream1.get(name, self.wstream1.get(pair_key(name)))
+        if ws is not None:
+            p.ws = ws.data_ptr()
         return p
 
     def _style(self, st: L.Style, pre: str):

@@ -26,7 +26,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .layout import BUFFER_LEAVES, resolve_dims, state_dict_layout
-from .packing import PackedModel, format_class
+from .packing import PackedModel
 from .synth import ephemeral_names, projection_names
 
 
@@ -74,7 +74,7 @@ class MotionTransformer(nn.Module):
         self.text_encoder_fn = text_encoder
         self._eph: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None
         self._proj: Optional[Dict[str, torch.Tensor]] = None
-        self._packed: Dict[str, PackedModel] = {}  # per weight-format class (packing.format_class)
+        self._packed: Dict[int, PackedModel] = {}  # per precision (pack())
         self._text_cache = None
         self._ws: Optional[torch.Tensor] = None
         self._uncond: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
@@ -124,7 +124,8 @@ class MotionTransformer(nn.Module):
         self.invalidate()
 
     def invalidate(self):
-        """Forget packed weights / caches (call after mutating parameters in place)."""
+        """Forget packed weights / caches (call after mutating parameters in place).  Also frees the packs of every precision the
+        module has run at: switching ``precision`` on a live module keeps one pack per precision until this is called."""
         self._packed = {}
         self._text_cache = None
         self._time_table = None
@@ -248,6 +249,10 @@ class MotionTransformer(nn.Module):
     # HIP path
     # ------------------------------------------------------------------------------------------------
     def pack(self) -> PackedModel:
+        """The packed weights for the current ``precision``, built on first use.  The cache is keyed by precision, not shared
+        between precisions that read the same planes: each pack's weight streams (MdmPacked.ws and friends) are in the format
+        its own precision's kernels read, so a module switched between precisions computes what a fresh one would.  The cost
+        is one pack per precision used, held until invalidate()."""
         if self.device.type != "cuda":
             raise L.MdmError("MotionTransformer runs on hand-written HIP kernels only: move it to a GPU "
                              "(no CPU/eager fallback exists)")
@@ -255,13 +260,13 @@ class MotionTransformer(nn.Module):
             self.draw_ephemerals()
         if self._proj is None:
             self.draw_projections()
-        cls = format_class(self.precision)
-        if cls not in self._packed:
+        prec = self.precision
+        if prec not in self._packed:
             sd = {k: v.detach() for k, v in self.state_dict().items()}
-            self._packed[cls] = PackedModel(sd, self.kernel_cfg(), self._eph, self._proj, self.device,
+            self._packed[prec] = PackedModel(sd, self.kernel_cfg(), self._eph, self._proj, self.device,
                                             with_lo=True, counters=self.moe_buffers(), precision=self.precision)
             self._text_cache = None
-        return self._packed[cls]
+        return self._packed[prec]
 
     def workspace_bytes(self, B: int, T: int, N: int) -> int:
         pm = self.pack()

@@ -441,6 +441,49 @@ def test_x3_gemm_on_pre_split_rows_is_bit_identical(M, N, K, grouped):
     assert torch.equal(outs[0], outs[1])
 
 
+@pytest.mark.parametrize("M,N,K,grouped", [(300, 1024, 512, False), (515, 512, 1024, True)])
+def test_x3_gemm_pre_split_output_at_8_byte_offset(M, N, K, grouped):
+    """MdmGemmDesc.Cx2 takes 16-byte stores (csrc/mdm_common.h store_x2_4p), and include/mdm_hip.h documents that a Cx2 that is not
+    16-byte aligned is refused with MDM_ERR_UNSUPPORTED: a Cx2 8 bytes into a 16-byte-aligned allocation must be refused before
+    anything is written, dense and grouped with a row gather (the expert GEMM's form), while the aligned run beside it leaves
+    exactly split_bf16 of C in Cx2."""
+    L, ops = _mods()
+    G = 3 if grouped else 1
+    x = _rand(M, K, seed=21)
+    w = _rand(G, N, K, seed=22) * K ** -0.5
+    b = _rand(G * N, seed=23)
+    pw = ops.PackedWeight(w if grouped else w[0])
+    sizes = [200, 0, M - 200] if grouped else [M]
+    goff = torch.tensor([0] + list(torch.tensor(sizes).cumsum(0)), dtype=torch.int32, device="cuda")
+    gather = torch.randint(0, M, (M,), generator=torch.Generator(device="cpu").manual_seed(24), dtype=torch.int32).cuda()
+
+    def desc(c, cx2_ptr):
+        d = ops.gemm_desc(3)
+        d.A = ops.f32_operand(x, K)
+        d.W = pw.operand()
+        d.M, d.N, d.K = M, N, K
+        d.C, d.Cx2, d.ldc, d.act, d.bias = c.data_ptr(), cx2_ptr, N, L.ACT_GELU, b.data_ptr()
+        if grouped:
+            d.A.gather = gather.data_ptr()
+            d.goff, d.ngroups, d.W.bs1, d.bias_bs = goff.data_ptr(), G, N * pw.Kp, N
+        return d
+
+    c, cx2 = torch.zeros(M, N, device="cuda"), torch.zeros(M, 2 * N, dtype=torch.bfloat16, device="cuda")
+    ops.run_gemm(desc(c, cx2.data_ptr()))
+    hi = c.to(torch.bfloat16)
+    lo = (c - hi.float()).to(torch.bfloat16)
+    want = torch.stack([hi.reshape(M, N // 32, 32), lo.reshape(M, N // 32, 32)], 2).reshape(M, 2 * N)
+    assert c.abs().max() > 0 and torch.equal(cx2.view(torch.int16), want.view(torch.int16))
+    # the same launch with Cx2 at +8 bytes (the allocation holds 8 spare elements: even a launch would stay inside it)
+    raw = torch.zeros(M * 2 * N + 8, dtype=torch.bfloat16, device="cuda")
+    assert raw.data_ptr() % 16 == 0
+    c_off = torch.zeros(M, N, device="cuda")
+    with pytest.raises(L.MdmError, match="MDM_ERR_UNSUPPORTED"):
+        ops.run_gemm(desc(c_off, raw.data_ptr() + 8))
+    torch.cuda.synchronize()
+    assert not c_off.any() and not raw.any()
+
+
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 @pytest.mark.parametrize("M,N,K,act", [(12544, 1024, 1024, 1), (6272, 1024, 1024, 0), (3136, 1024, 1024, 0), (1568, 1024, 1024, 1),
                                        (1000, 1024, 1024, 0), (50, 512, 1024, 1), (1, 256, 512, 0), (12544, 512, 512, 0),
