@@ -364,6 +364,20 @@ int mdm_ddim_step(const float* x, const float* eps, const float* noise, int64_t 
                   const int32_t* t_dev, int32_t t_imm, float eta, int32_t clip_denoised, float* x_out, float* x0_out,
                   void* stream);
 
+/* Few-step samplers on a respaced schedule (csrc/solver.hip).  t = *t_dev when non-NULL else t_imm, an index into the
+ * SPACED schedule of `steps` entries.
+ * dst[r] = map[clamp(t, 0, steps-1)] for r < n: the original timestep of the spaced step, for the denoiser.
+ * Guided update: x0_c = tab[0][t]*x - tab[1][t]*eps_c and x0_u likewise from eps_u, each clamped to [-1,1] when
+ * clip_denoised; x0 = x0_u + cfg_scale*(x0_c - x0_u) (eps_u NULL = unguided, x0 = x0_c); then
+ * x_out = cx*x + c0*x0 + c1*x0_prev + cn*noise and x0_out = x0, with {cx, c0, c1, cn} = coef[t][0..3] (fp32 [steps][4]).
+ * x0_prev NULL or c1 == 0: no x0_prev term and no read; noise NULL: no noise term; x0_out may be NULL.  x_out may be x
+ * and x0_out may be x0_prev (in place).  Guided DDIM at any eta and DPM-Solver++(2M) differ only in coef. */
+int mdm_fill_timesteps_mapped(int64_t* dst, int64_t n, const int32_t* t_dev, const int64_t* map, int32_t steps,
+                              void* stream);
+int mdm_guided_update(const float* x, const float* eps_c, const float* eps_u, const float* x0_prev, const float* noise,
+                      int64_t n, const float* tab, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
+                      float cfg_scale, int32_t clip_denoised, float* x_out, float* x0_out, void* stream);
+
 /* Counter-based gaussian noise (Philox4x32-10 + Box-Muller, csrc/noise.hip): out[s, e] for s < nsamples, e < per_sample is
  * a function of (seed, sample0 + s, stream, e) only, where stream = *stream_dev when non-NULL (the device-resident timestep
  * of a captured step) else stream_imm (MDM_NOISE_STREAM_XT for the initial x_T).  Replaces th.randn(*shape) /

@@ -2,14 +2,19 @@
 
 Same constructor arguments (``args.device``, ``args.diffusion_steps``, ``args.is_train``, optional ``cfg_scale``),
 same ``generate(caption, m_lens, dim_pose, batch_size)`` -> list of (T, dim_pose) tensors, same checkpoint dict keys
-(``encoder``, ``ep``, ``total_it``, ``opt_encoder``).  The training loop (forward/backward/update/train) is out of
+(``encoder``, ``ep``, ``total_it``, ``opt_encoder``).  The generate methods also take ``sampler`` ("ddpm" | "ddim" |
+"dpmpp2m"), ``sample_steps`` and ``eta``: few-step guided sampling of the same model on a respaced schedule; the defaults
+run the reference's guided DDPM over every step.  The training loop (forward/backward/update/train) is out of
 scope for this build and raises.
 """
 from __future__ import annotations
 
 import torch
 
-from .diffusion import GaussianDiffusion, LossType, ModelMeanType, ModelVarType, get_named_beta_schedule
+from .diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType, SpacedDiffusion, get_named_beta_schedule,
+                        space_timesteps)
+
+SAMPLERS = ("ddpm", "ddim", "dpmpp2m")
 
 
 class DDPMTrainer(object):
@@ -18,9 +23,11 @@ class DDPMTrainer(object):
         self.device = args.device
         self.encoder = encoder
         self.diffusion_steps = args.diffusion_steps
-        betas = get_named_beta_schedule("linear", self.diffusion_steps)
-        self.diffusion = GaussianDiffusion(betas=betas, model_mean_type=ModelMeanType.EPSILON,
-                                           model_var_type=ModelVarType.FIXED_SMALL, loss_type=LossType.MSE)
+        self._diffusion_kw = dict(betas=get_named_beta_schedule("linear", self.diffusion_steps),
+                                  model_mean_type=ModelMeanType.EPSILON, model_var_type=ModelVarType.FIXED_SMALL,
+                                  loss_type=LossType.MSE)
+        self.diffusion = GaussianDiffusion(**self._diffusion_kw)
+        self._spaced = {}  # (sampler, steps) -> SpacedDiffusion
         self.sampler_name = "uniform"
         self.to(self.device)
         self.cfg_scale = getattr(args, "cfg_scale", 7.5)
@@ -37,24 +44,55 @@ class DDPMTrainer(object):
     def eval_mode(self):
         self._model().eval()
 
+    def sampling_diffusion(self, sampler: str = "ddpm", sample_steps=None) -> GaussianDiffusion:
+        """The diffusion a generate call samples with: the trainer's own schedule when ``sample_steps`` is None or the
+        whole schedule, else a SpacedDiffusion of ``sample_steps`` steps (stride-spaced "ddimN" when an integer stride
+        gives exactly that many, evenly spaced over the whole schedule otherwise), cached per (sampler, steps)."""
+        if sampler not in SAMPLERS:
+            raise ValueError(f"sampler must be one of {SAMPLERS}, not {sampler!r}")
+        n = self.diffusion_steps if sample_steps is None else int(sample_steps)
+        if not 1 <= n <= self.diffusion_steps:
+            raise ValueError(f"sample_steps must lie in [1, {self.diffusion_steps}]")
+        if n == self.diffusion_steps:
+            return self.diffusion
+        if (sampler, n) not in self._spaced:
+            try:
+                use = space_timesteps(self.diffusion_steps, f"ddim{n}")
+            except ValueError:
+                use = space_timesteps(self.diffusion_steps, [n])
+            self._spaced[(sampler, n)] = SpacedDiffusion(use, **self._diffusion_kw)
+        return self._spaced[(sampler, n)]
+
+    def _sample(self, m, shape, sampler, sample_steps, eta, **kw):
+        if eta != 0.0 and sampler != "ddim":
+            raise ValueError("eta applies to the ddim sampler only")
+        d = self.sampling_diffusion(sampler, sample_steps)
+        if sampler == "ddpm":
+            return d.p_sample_loop_with_cfg(m, shape, cfg_scale=self.cfg_scale, **kw)
+        if sampler == "ddim":
+            return d.ddim_sample_loop_with_cfg(m, shape, cfg_scale=self.cfg_scale, eta=eta, **kw)
+        return d.dpm_solver_sample_loop_with_cfg(m, shape, cfg_scale=self.cfg_scale, order=2, **kw)
+
     @torch.no_grad()
     def generate_batch(self, caption, m_lens, dim_pose, *, noise=None, step_noise=None, progress=True, seed=None,
-                       sample_offset=0):
+                       sample_offset=0, sampler="ddpm", sample_steps=None, eta=0.0):
         m = self._model()
         xf_proj, xf_out = m.encode_text(caption, self.device)
         m_lens = torch.as_tensor(m_lens)
         T = min(int(m_lens.max()), m.num_frames)
         B = len(caption)
-        return self.diffusion.p_sample_loop_with_cfg(
-            m, (B, T, dim_pose), clip_denoised=False, progress=progress, noise=noise, step_noise=step_noise,
-            model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": m_lens, "text": caption},
-            cfg_scale=self.cfg_scale, seed=seed, sample_offset=sample_offset)
+        return self._sample(
+            m, (B, T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress, noise=noise,
+            step_noise=step_noise, model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": m_lens, "text": caption},
+            seed=seed, sample_offset=sample_offset)
 
     @torch.no_grad()
-    def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None):
+    def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None, sampler="ddpm",
+                 sample_steps=None, eta=0.0):
         """``seed``: sample i's noise is then a function of (seed, i) only (counter-based device generator), so the result
         does not depend on ``batch_size``; without it the torch generator is used, as in the reference.
-        ``noises``: optional list with one ``(x_T, [step noise, ...])`` pair per batch, replacing the draws (parity tests)."""
+        ``noises``: optional list with one ``(x_T, [step noise, ...])`` pair per batch, replacing the draws (parity tests).
+        ``sampler`` / ``sample_steps`` / ``eta``: see ``sampling_diffusion``; e.g. ``sampler="dpmpp2m", sample_steps=20``."""
         N = len(caption)
         self.eval_mode()
         all_output = []
@@ -63,14 +101,15 @@ class DDPMTrainer(object):
             end = min(cur + batch_size, N)
             x_T, step_noise = noises[cur // batch_size] if noises is not None else (None, None)
             out = self.generate_batch(caption[cur:end], m_lens[cur:end], dim_pose, progress=progress, seed=seed,
-                                      sample_offset=cur, noise=x_T, step_noise=step_noise)
+                                      sample_offset=cur, noise=x_T, step_noise=step_noise, sampler=sampler,
+                                      sample_steps=sample_steps, eta=eta)
             all_output.extend(out[i] for i in range(out.shape[0]))
             cur += batch_size
         return all_output
 
     @torch.no_grad()
     def generate_bucketed(self, caption, m_lens, dim_pose, batch_size=32, *, unit_length=4, seed=None, group=None,
-                          progress=False):
+                          progress=False, sampler="ddpm", sample_steps=None, eta=0.0):
         """Evaluation-scale variant of ``generate``: same inputs and the same kind of result (a
         list of per-sample ``(T_batch, dim_pose)`` tensors in the caller's order, valid up to each sample's length),
         but batches hold samples of similar length (less padded work) and, under ``torch.distributed``, are dealt over
@@ -87,21 +126,21 @@ class DDPMTrainer(object):
             cap = [caption[i] for i in idx.tolist()]
             ln = lens[idx].clamp(max=T).to(self.device)
             xf_proj, xf_out = m.encode_text(cap, self.device)
-            return self.diffusion.p_sample_loop_with_cfg(
-                m, (len(cap), T, dim_pose), clip_denoised=False, progress=progress,
-                model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": ln, "text": cap}, cfg_scale=self.cfg_scale,
+            return self._sample(
+                m, (len(cap), T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress,
+                model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": ln, "text": cap},
                 seed=seed, sample_offset=idx)  # noise keyed on each row's index in the CALLER's list: == generate(seed=)
 
         return D.run_plan(plan, run_bucket, len(caption), m.num_frames, dim_pose, self.device, group)
 
     @torch.no_grad()
     def generate_joints(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, joints_num=22, sigma=1.0,
-                        bucketed=False, **kw):
+                        bucketed=False, sampler="ddpm", sample_steps=None, eta=0.0, **kw):
         """``generate`` followed by the reference's post-processing (tools/visualization.py:21-27,89) on the device:
         list of ``(m_len, joints_num, 3)`` joint positions, temporally smoothed with a gaussian of width ``sigma``."""
         from .postprocess import motion_to_joints
         gen = self.generate_bucketed if bucketed else self.generate
-        motions = gen(caption, m_lens, dim_pose, batch_size, **kw)
+        motions = gen(caption, m_lens, dim_pose, batch_size, sampler=sampler, sample_steps=sample_steps, eta=eta, **kw)
         lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
         x = torch.zeros((len(motions), max(mo.shape[0] for mo in motions), dim_pose), device=motions[0].device)
         for i, mo in enumerate(motions):

@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Time one whole generation at the configs[1] shape (small, 8 experts, B=32, T=196, guided, 1000-step schedule) through
+DDPMTrainer.generate for the samplers it offers: guided DDPM over all 1000 steps, guided DDIM in 50 and 20 steps and
+DPM-Solver++(2M) in 20 steps, at precision 1 (bf16) and 3 (fp32-grade).
+
+A generation is the whole call: text embedding lookup, the warm-up step and graph capture of the loop, every replay, the
+copy-out.  Each is timed with a host clock between two device synchronisations, after one untimed generation of the same
+shape.  The two DDIM lengths split the time into a per-step part and a fixed part: step = (t50 - t20) / 30, fixed =
+t20 - 20 step.  Prints one JSON line per (precision, sampler) and a table.
+
+    timeout -k 10 900 python tools/sample_time.py [--reps 2] [--precisions 1,3]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+SAMPLERS = (("ddpm", None, 1000), ("ddim", 50, 50), ("ddim", 20, 20), ("dpmpp2m", 20, 20))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=2, help="timed generations per sampler (the median is reported)")
+    ap.add_argument("--precisions", default="1,3")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--frames", type=int, default=196)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sample_time.py measures the GPU sampler: no GPU found")
+    bench = importlib.import_module("bench")
+    Tr = importlib.import_module("motiondiffusion-moe_amd.trainer")
+    dev = torch.device("cuda:0")
+    B, T = a.batch, a.frames
+    m, (_, length, xf_proj, xf_out), _ = bench.build_model("small", dev, 1, B, T, 28)
+    length[0] = T  # the batch runs at T frames
+    m.text_encoder_fn = lambda text, device: (xf_proj[:len(text)].to(device), xf_out[:len(text)].to(device))
+    import types
+    tr = Tr.DDPMTrainer(types.SimpleNamespace(device=dev, diffusion_steps=1000, is_train=False, cfg_scale=7.5), m)
+    caps = [f"caption {i}" for i in range(B)]
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        res = {}
+        for sampler, steps, n in SAMPLERS:
+            def gen():
+                return tr.generate(caps, length, 263, batch_size=B, seed=0, sampler=sampler, sample_steps=steps)
+            out = gen()  # warm-up: code objects, packs, caches
+            assert all(torch.isfinite(o).all() for o in out)
+            ts = []
+            for _ in range(a.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                gen()
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter() - t0)
+            ms = sorted(ts)[len(ts) // 2] * 1e3
+            name = {"ddpm": "DDPM", "ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+            res[name] = ms
+            line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, ms_per_generation=round(ms, 2),
+                        ms_per_step=round(ms / n, 3), reps_ms=[round(t * 1e3, 2) for t in ts])
+            rows.append(line)
+            print(json.dumps(line), flush=True)
+        step = (res["DDIM-50"] - res["DDIM-20"]) / 30
+        fixed = res["DDIM-20"] - 20 * step
+        line = dict(precision=prec, guided_ddim_step_ms=round(step, 3), fixed_ms_per_generation=round(fixed, 2),
+                    fixed_share_at_20_steps=round(fixed / res["DPM-Solver++(2M)-20"], 3))
+        rows.append(line)
+        print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}, guided (cfg 7.5), 1000-step schedule; {torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'sampler':>22} {'ms/generation':>14} {'ms/step':>9}")
+    for r in rows:
+        if "sampler" in r:
+            print(f"{r['precision']:>9} {r['sampler']:>22} {r['ms_per_generation']:>14.1f} {r['ms_per_step']:>9.3f}")
+        else:
+            print(f"{r['precision']:>9} {'(per step | fixed)':>22} {r['fixed_ms_per_generation']:>14.1f} "
+                  f"{r['guided_ddim_step_ms']:>9.3f}")
+
+
+if __name__ == "__main__":
+    main()
