@@ -377,6 +377,13 @@ int mdm_fill_timesteps_mapped(int64_t* dst, int64_t n, const int32_t* t_dev, con
 int mdm_guided_update(const float* x, const float* eps_c, const float* eps_u, const float* x0_prev, const float* noise,
                       int64_t n, const float* tab, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
                       float cfg_scale, int32_t clip_denoised, float* x_out, float* x0_out, void* stream);
+/* Motion editing: mdm_guided_update with the guided x0 replaced by (1 - mask)*x0 + mask*known before the update, so
+ * x_out uses that x0 and x0_out receives it.  known (normalised motion, never clamped) and mask (in [0, 1]) are dense [n];
+ * NULL is an argument error.  mask = 0 gives exactly the x0 of mdm_guided_update, mask = 1 exactly known. */
+int mdm_guided_update_inpaint(const float* x, const float* eps_c, const float* eps_u, const float* x0_prev,
+                              const float* noise, const float* known, const float* mask, int64_t n, const float* tab,
+                              const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, float cfg_scale,
+                              int32_t clip_denoised, float* x_out, float* x0_out, void* stream);
 
 /* Counter-based gaussian noise (Philox4x32-10 + Box-Muller, csrc/noise.hip): out[s, e] for s < nsamples, e < per_sample is
  * a function of (seed, sample0 + s, stream, e) only, where stream = *stream_dev when non-NULL (the device-resident timestep

@@ -5,6 +5,8 @@
 // Both read the step counter from device memory, so one captured hipGraph serves the whole loop.  The per-step
 // coefficients {cx, c0, c1, cn} are tabulated on the host in f64 and rounded to f32 (GaussianDiffusion.solver_coefficients):
 // guided DDIM at any eta and DPM-Solver++(2M) share this one kernel and differ only in the table.
+// Motion editing (mdm_guided_update_inpaint) replaces the guided x0 by (1 - m)*x0 + m*k before the update, with the known
+// motion k and the mask m dense [n]: two more reads per element, in a second instantiation of the same kernel.
 #include "kernels.h"
 
 namespace mdm {
@@ -18,12 +20,14 @@ __global__ void fill_mapped_kernel(int64_t* __restrict__ dst, int64_t n, const i
 
 // x / x_out and x0_prev / x0_out may be the same buffers (in-place update): each element is read before it is written,
 // by the same thread, so those four carry no __restrict__.  VEC: every pointer 16-byte aligned -> dwordx4 loads / stores
-// on whole quads; the last quad of an n that is not a multiple of 4 is done element by element.
-template <bool VEC>
+// on whole quads; the last quad of an n that is not a multiple of 4 is done element by element.  EDIT: known / mask are
+// read and the guided x0 is replaced on the masked entries (known is data: never clamped); without it they are not touched.
+template <bool VEC, bool EDIT>
 __global__ void __launch_bounds__(256) guided_update_kernel(
     const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u, const float* x0_prev,
-    const float* __restrict__ noise, int64_t n, const float* __restrict__ tab, const float* __restrict__ coef, int ts,
-    const int* __restrict__ t_ptr, int t_imm, float cfg_scale, int clip, float* x_out, float* x0_out) {
+    const float* __restrict__ noise, const float* __restrict__ known, const float* __restrict__ mask, int64_t n,
+    const float* __restrict__ tab, const float* __restrict__ coef, int ts, const int* __restrict__ t_ptr, int t_imm,
+    float cfg_scale, int clip, float* x_out, float* x0_out) {
   int t = t_ptr ? *t_ptr : t_imm;
   t = min(max(t, 0), ts - 1);
   const float a = tab[TAB_SQRT_RECIP * ts + t], b = tab[TAB_SQRT_RECIPM1 * ts + t];
@@ -31,7 +35,7 @@ __global__ void __launch_bounds__(256) guided_update_kernel(
   const float c1 = x0_prev ? coef[4 * t + 2] : 0.f, cn = noise ? coef[4 * t + 3] : 0.f;
   // c1 == 0 (first and last DPM-Solver++ steps, every DDIM step) skips the x0_prev read: its buffer may hold anything then
   const bool use_prev = c1 != 0.f, use_noise = cn != 0.f;
-  auto one = [&](float xv, float ec, float eu, float xp, float nz, float& xo) {
+  auto one = [&](float xv, float ec, float eu, float xp, float nz, float kv, float mv, float& xo) {
     float x0 = a * xv - b * ec;
     if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
     if (eps_u) {  // classifier-free guidance on pred_xstart (gaussian_diffusion.py:1075-1091)
@@ -39,6 +43,8 @@ __global__ void __launch_bounds__(256) guided_update_kernel(
       if (clip) x0u = fminf(fmaxf(x0u, -1.f), 1.f);
       x0 = x0u + cfg_scale * (x0 - x0u);
     }
+    // m = 0 gives x0 and m = 1 gives k exactly (finite operands), with or without fma contraction
+    if (EDIT) x0 = (1.f - mv) * x0 + mv * kv;
     float y = cx * xv + c0 * x0;
     if (use_prev) y += c1 * xp;
     if (use_noise) y += cn * nz;
@@ -54,11 +60,12 @@ __global__ void __launch_bounds__(256) guided_update_kernel(
       const f32x4 eu = eps_u ? *(const f32x4*)(eps_u + i) : z;
       const f32x4 xp = use_prev ? *(const f32x4*)(x0_prev + i) : z;
       const f32x4 nz = use_noise ? *(const f32x4*)(noise + i) : z;
+      const f32x4 kv = EDIT ? *(const f32x4*)(known + i) : z, mv = EDIT ? *(const f32x4*)(mask + i) : z;
       f32x4 xo, x0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float o;
-        x0[k] = one(xv[k], ec[k], eu[k], xp[k], nz[k], o);
+        x0[k] = one(xv[k], ec[k], eu[k], xp[k], nz[k], kv[k], mv[k], o);
         xo[k] = o;
       }
       *(f32x4*)(x_out + i) = xo;
@@ -67,7 +74,7 @@ __global__ void __launch_bounds__(256) guided_update_kernel(
       for (int64_t j = i; j < i + 4 && j < n; ++j) {
         float o;
         const float x0 = one(x[j], eps_c[j], eps_u ? eps_u[j] : 0.f, use_prev ? x0_prev[j] : 0.f,
-                             use_noise ? noise[j] : 0.f, o);
+                             use_noise ? noise[j] : 0.f, EDIT ? known[j] : 0.f, EDIT ? mask[j] : 0.f, o);
         x_out[j] = o;
         if (x0_out) x0_out[j] = x0;
       }
@@ -76,6 +83,31 @@ __global__ void __launch_bounds__(256) guided_update_kernel(
 }
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+template <bool EDIT>
+int launch_guided_update(const float* x, const float* eps_c, const float* eps_u, const float* x0_prev, const float* noise,
+                         const float* known, const float* mask, int64_t n, const float* tab, const float* coef,
+                         int32_t steps, const int32_t* t_dev, int32_t t_imm, float cfg_scale, int32_t clip_denoised,
+                         float* x_out, float* x0_out, void* stream) {
+  if (!x || !eps_c || !tab || !coef || !x_out || n < 0 || steps <= 0) return MDM_ERR_ARG;
+  if (EDIT && (!known || !mask)) return MDM_ERR_ARG;
+  if (!t_dev && (t_imm < 0 || t_imm >= steps)) return MDM_ERR_ARG;
+  if (n == 0) return MDM_OK;
+  const bool vec = aligned16(x) && aligned16(eps_c) && aligned16(eps_u) && aligned16(x0_prev) && aligned16(noise) &&
+                   aligned16(known) && aligned16(mask) && aligned16(x_out) && aligned16(x0_out);  // (NULL is aligned)
+  const int64_t blocks = (((n + 3) >> 2) + 255) / 256;
+  const dim3 grid((unsigned)(blocks > 2048 ? 2048 : blocks));
+  if (vec)
+    hipLaunchKernelGGL((guided_update_kernel<true, EDIT>), grid, dim3(256), 0, (hipStream_t)stream, x, eps_c, eps_u,
+                       x0_prev, noise, known, mask, n, tab, coef, steps, t_dev, t_imm, cfg_scale, clip_denoised, x_out,
+                       x0_out);
+  else
+    hipLaunchKernelGGL((guided_update_kernel<false, EDIT>), grid, dim3(256), 0, (hipStream_t)stream, x, eps_c, eps_u,
+                       x0_prev, noise, known, mask, n, tab, coef, steps, t_dev, t_imm, cfg_scale, clip_denoised, x_out,
+                       x0_out);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
 
 }  // namespace
 }  // namespace mdm
@@ -95,21 +127,16 @@ int mdm_fill_timesteps_mapped(int64_t* dst, int64_t n, const int32_t* t_dev, con
 int mdm_guided_update(const float* x, const float* eps_c, const float* eps_u, const float* x0_prev, const float* noise,
                       int64_t n, const float* tab, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
                       float cfg_scale, int32_t clip_denoised, float* x_out, float* x0_out, void* stream) {
-  if (!x || !eps_c || !tab || !coef || !x_out || n < 0 || steps <= 0) return MDM_ERR_ARG;
-  if (!t_dev && (t_imm < 0 || t_imm >= steps)) return MDM_ERR_ARG;
-  if (n == 0) return MDM_OK;
-  const bool vec = mdm::aligned16(x) && mdm::aligned16(eps_c) && mdm::aligned16(eps_u) && mdm::aligned16(x0_prev) &&
-                   mdm::aligned16(noise) && mdm::aligned16(x_out) && mdm::aligned16(x0_out);  // (NULL is aligned)
-  const int64_t blocks = (((n + 3) >> 2) + 255) / 256;
-  const dim3 grid((unsigned)(blocks > 2048 ? 2048 : blocks));
-  if (vec)
-    hipLaunchKernelGGL(mdm::guided_update_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, eps_c, eps_u, x0_prev,
-                       noise, n, tab, coef, steps, t_dev, t_imm, cfg_scale, clip_denoised, x_out, x0_out);
-  else
-    hipLaunchKernelGGL(mdm::guided_update_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, eps_c, eps_u, x0_prev,
-                       noise, n, tab, coef, steps, t_dev, t_imm, cfg_scale, clip_denoised, x_out, x0_out);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  return mdm::launch_guided_update<false>(x, eps_c, eps_u, x0_prev, noise, nullptr, nullptr, n, tab, coef, steps, t_dev,
+                                          t_imm, cfg_scale, clip_denoised, x_out, x0_out, stream);
+}
+
+int mdm_guided_update_inpaint(const float* x, const float* eps_c, const float* eps_u, const float* x0_prev,
+                              const float* noise, const float* known, const float* mask, int64_t n, const float* tab,
+                              const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, float cfg_scale,
+                              int32_t clip_denoised, float* x_out, float* x0_out, void* stream) {
+  return mdm::launch_guided_update<true>(x, eps_c, eps_u, x0_prev, noise, known, mask, n, tab, coef, steps, t_dev, t_imm,
+                                         cfg_scale, clip_denoised, x_out, x0_out, stream);
 }
 
 }  // extern "C"

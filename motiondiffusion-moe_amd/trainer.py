@@ -4,7 +4,8 @@ Same constructor arguments (``args.device``, ``args.diffusion_steps``, ``args.is
 same ``generate(caption, m_lens, dim_pose, batch_size)`` -> list of (T, dim_pose) tensors, same checkpoint dict keys
 (``encoder``, ``ep``, ``total_it``, ``opt_encoder``).  The generate methods also take ``sampler`` ("ddpm" | "ddim" |
 "dpmpp2m"), ``sample_steps`` and ``eta``: few-step guided sampling of the same model on a respaced schedule; the defaults
-run the reference's guided DDPM over every step.  The training loop (forward/backward/update/train) is out of
+run the reference's guided DDPM over every step.  ``edit_motion`` / ``edit_mask`` turn any of them into motion editing
+(prefix completion, in-betweening, body-part regeneration; masks from ``motion_edit``).  The training loop (forward/backward/update/train) is out of
 scope for this build and raises.
 """
 from __future__ import annotations
@@ -63,6 +64,24 @@ class DDPMTrainer(object):
             self._spaced[(sampler, n)] = SpacedDiffusion(use, **self._diffusion_kw)
         return self._spaced[(sampler, n)]
 
+    @staticmethod
+    def _edit_kwargs(edit_motion, edit_mask, rows, T, dim_pose):
+        """``inpaint_motion`` / ``inpaint_mask`` model kwargs of one batch: rows ``rows`` and the first T frames of
+        ``edit_motion`` (N, T_max, dim_pose) and of ``edit_mask`` broadcast to its shape; {} when neither is given."""
+        if edit_motion is None and edit_mask is None:
+            return {}
+        if edit_motion is None or edit_mask is None:
+            raise ValueError("edit_motion and edit_mask go together: give both or neither")
+        k = torch.as_tensor(edit_motion)
+        if k.dim() != 3 or k.shape[2] != dim_pose or k.shape[1] < T:
+            raise ValueError(f"edit_motion of shape {tuple(k.shape)} must be (N, T_max >= {T}, {dim_pose})")
+        try:
+            msk = torch.broadcast_to(torch.as_tensor(edit_mask), k.shape)
+        except RuntimeError:
+            raise ValueError(f"edit_mask of shape {tuple(torch.as_tensor(edit_mask).shape)} does not broadcast to "
+                             f"{tuple(k.shape)}") from None
+        return {"inpaint_motion": k[rows, :T], "inpaint_mask": msk[rows, :T]}
+
     def _sample(self, m, shape, sampler, sample_steps, eta, **kw):
         if eta != 0.0 and sampler != "ddim":
             raise ValueError("eta applies to the ddim sampler only")
@@ -75,26 +94,36 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_batch(self, caption, m_lens, dim_pose, *, noise=None, step_noise=None, progress=True, seed=None,
-                       sample_offset=0, sampler="ddpm", sample_steps=None, eta=0.0):
+                       sample_offset=0, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None):
+        """``edit_motion`` (B, T_max, dim_pose), normalised, and ``edit_mask`` broadcastable to it, values in [0, 1]: the
+        batch's first T frames of both are kept where the mask is 1 (exactly, for a binary mask) and generated elsewhere."""
         m = self._model()
-        xf_proj, xf_out = m.encode_text(caption, self.device)
         m_lens = torch.as_tensor(m_lens)
         T = min(int(m_lens.max()), m.num_frames)
         B = len(caption)
+        edit = self._edit_kwargs(edit_motion, edit_mask, slice(0, B), T, dim_pose)
+        xf_proj, xf_out = m.encode_text(caption, self.device)
         return self._sample(
             m, (B, T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress, noise=noise,
-            step_noise=step_noise, model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": m_lens, "text": caption},
+            step_noise=step_noise,
+            model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": m_lens, "text": caption, **edit},
             seed=seed, sample_offset=sample_offset)
 
     @torch.no_grad()
     def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None, sampler="ddpm",
-                 sample_steps=None, eta=0.0):
+                 sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None):
         """``seed``: sample i's noise is then a function of (seed, i) only (counter-based device generator), so the result
         does not depend on ``batch_size``; without it the torch generator is used, as in the reference.
         ``noises``: optional list with one ``(x_T, [step noise, ...])`` pair per batch, replacing the draws (parity tests).
-        ``sampler`` / ``sample_steps`` / ``eta``: see ``sampling_diffusion``; e.g. ``sampler="dpmpp2m", sample_steps=20``."""
+        ``sampler`` / ``sample_steps`` / ``eta``: see ``sampling_diffusion``; e.g. ``sampler="dpmpp2m", sample_steps=20``.
+        ``edit_motion`` (N, T_max, dim_pose) and ``edit_mask`` (broadcastable to it): motion editing, see ``generate_batch``;
+        each batch takes its samples' rows."""
         N = len(caption)
         self.eval_mode()
+        if edit_motion is not None and edit_mask is not None:
+            edit_motion = torch.as_tensor(edit_motion)
+            edit_mask = self._edit_kwargs(edit_motion, edit_mask, slice(None), edit_motion.shape[1],
+                                          dim_pose)["inpaint_mask"]
         all_output = []
         cur = 0
         while cur < N:
@@ -102,20 +131,23 @@ class DDPMTrainer(object):
             x_T, step_noise = noises[cur // batch_size] if noises is not None else (None, None)
             out = self.generate_batch(caption[cur:end], m_lens[cur:end], dim_pose, progress=progress, seed=seed,
                                       sample_offset=cur, noise=x_T, step_noise=step_noise, sampler=sampler,
-                                      sample_steps=sample_steps, eta=eta)
+                                      sample_steps=sample_steps, eta=eta,
+                                      edit_motion=None if edit_motion is None else edit_motion[cur:end],
+                                      edit_mask=None if edit_mask is None else edit_mask[cur:end])
             all_output.extend(out[i] for i in range(out.shape[0]))
             cur += batch_size
         return all_output
 
     @torch.no_grad()
     def generate_bucketed(self, caption, m_lens, dim_pose, batch_size=32, *, unit_length=4, seed=None, group=None,
-                          progress=False, sampler="ddpm", sample_steps=None, eta=0.0):
+                          progress=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None):
         """Evaluation-scale variant of ``generate``: same inputs and the same kind of result (a
         list of per-sample ``(T_batch, dim_pose)`` tensors in the caller's order, valid up to each sample's length),
         but batches hold samples of similar length (less padded work) and, under ``torch.distributed``, are dealt over
         the ranks with one all_gather at the end.  With ``seed`` every sample's noise is a function of (seed, its index in
         ``caption``) only -- the same as ``generate(..., seed=)`` -- so on each sample's valid frames the two give identical
-        results whatever the bucketing (tests/test_sampler_gpu.py)."""
+        results whatever the bucketing (tests/test_sampler_gpu.py).  ``edit_motion`` / ``edit_mask``: as in ``generate``;
+        each bucket takes its samples' rows and its first T frames."""
         from . import dist as D
         m = self._model()
         self.eval_mode()
@@ -125,22 +157,25 @@ class DDPMTrainer(object):
         def run_bucket(k, idx, T):
             cap = [caption[i] for i in idx.tolist()]
             ln = lens[idx].clamp(max=T).to(self.device)
+            edit = self._edit_kwargs(edit_motion, edit_mask, idx, T, dim_pose)
             xf_proj, xf_out = m.encode_text(cap, self.device)
             return self._sample(
                 m, (len(cap), T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress,
-                model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": ln, "text": cap},
+                model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": ln, "text": cap, **edit},
                 seed=seed, sample_offset=idx)  # noise keyed on each row's index in the CALLER's list: == generate(seed=)
 
         return D.run_plan(plan, run_bucket, len(caption), m.num_frames, dim_pose, self.device, group)
 
     @torch.no_grad()
     def generate_joints(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, joints_num=22, sigma=1.0,
-                        bucketed=False, sampler="ddpm", sample_steps=None, eta=0.0, **kw):
+                        bucketed=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, **kw):
         """``generate`` followed by the reference's post-processing (tools/visualization.py:21-27,89) on the device:
-        list of ``(m_len, joints_num, 3)`` joint positions, temporally smoothed with a gaussian of width ``sigma``."""
+        list of ``(m_len, joints_num, 3)`` joint positions, temporally smoothed with a gaussian of width ``sigma``.
+        ``edit_motion`` / ``edit_mask``: motion editing in normalised feature space, as in ``generate``."""
         from .postprocess import motion_to_joints
         gen = self.generate_bucketed if bucketed else self.generate
-        motions = gen(caption, m_lens, dim_pose, batch_size, sampler=sampler, sample_steps=sample_steps, eta=eta, **kw)
+        motions = gen(caption, m_lens, dim_pose, batch_size, sampler=sampler, sample_steps=sample_steps, eta=eta,
+                      edit_motion=edit_motion, edit_mask=edit_mask, **kw)
         lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
         x = torch.zeros((len(motions), max(mo.shape[0] for mo in motions), dim_pose), device=motions[0].device)
         for i, mo in enumerate(motions):

@@ -9,6 +9,12 @@ shape.  The two DDIM lengths split the time into a per-step part and a fixed par
 t20 - 20 step.  Prints one JSON line per (precision, sampler) and a table.
 
     timeout -k 10 900 python tools/sample_time.py [--reps 2] [--precisions 1,3]
+
+``--edit prefix:N`` or ``--edit inbetween:H,T`` measures motion editing instead: every sampler runs the same generation
+without and with that frame mask (``edit_motion``/``edit_mask``), alternating, ``--reps`` pairs after one untimed pair, and
+reports both medians and the per-pair difference (median, min, max; per generation and per step).
+
+    timeout -k 10 900 python tools/sample_time.py --edit prefix:40 --reps 5 --precisions 1
 """
 import argparse
 import importlib
@@ -31,6 +37,7 @@ def main():
     ap.add_argument("--precisions", default="1,3")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=196)
+    ap.add_argument("--edit", default=None, help="prefix:N | inbetween:H,T: time editing against plain generation")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_time.py measures the GPU sampler: no GPU found")
@@ -44,6 +51,8 @@ def main():
     import types
     tr = Tr.DDPMTrainer(types.SimpleNamespace(device=dev, diffusion_steps=1000, is_train=False, cfg_scale=7.5), m)
     caps = [f"caption {i}" for i in range(B)]
+    if a.edit:
+        return edit_main(a, tr, m, caps, length, B, T)
     rows = []
     for prec in [int(p) for p in a.precisions.split(",")]:
         m.precision = prec
@@ -82,6 +91,57 @@ def main():
         else:
             print(f"{r['precision']:>9} {'(per step | fixed)':>22} {r['fixed_ms_per_generation']:>14.1f} "
                   f"{r['guided_ddim_step_ms']:>9.3f}")
+
+
+def edit_mask(spec, T):
+    E = importlib.import_module("motiondiffusion-moe_amd.motion_edit")
+    kind, _, arg = spec.partition(":")
+    if kind == "prefix":
+        return E.prefix_mask(T, int(arg))
+    if kind == "inbetween":
+        head, tail = (int(v) for v in arg.split(","))
+        return E.inbetween_mask(T, head, tail)
+    raise SystemExit(f"--edit must be prefix:N or inbetween:H,T, not {spec!r}")
+
+
+def edit_main(a, tr, m, caps, length, B, T):
+    dev = torch.device("cuda:0")
+    mask = edit_mask(a.edit, T)
+    known = torch.rand((B, T, 263), generator=torch.Generator().manual_seed(0)).to(dev) * 2 - 1
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for sampler, steps, n in SAMPLERS:
+            def gen(edit):
+                extra = dict(edit_motion=known, edit_mask=mask) if edit else {}
+                return tr.generate(caps, length, 263, batch_size=B, seed=0, sampler=sampler, sample_steps=steps, **extra)
+            for edit in (False, True):  # warm-up
+                assert all(torch.isfinite(o).all() for o in gen(edit))
+            ts = {False: [], True: []}
+            for _ in range(a.reps):
+                for edit in (False, True):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    gen(edit)
+                    torch.cuda.synchronize()
+                    ts[edit].append((time.perf_counter() - t0) * 1e3)
+            med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+            diff = sorted(e - p for p, e in zip(ts[False], ts[True]))
+            name = {"ddpm": "DDPM", "ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+            line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, edit=a.edit, plain_ms=round(med[False], 2),
+                        edit_ms=round(med[True], 2), diff_ms_median=round(diff[len(diff) // 2], 2),
+                        diff_ms_min=round(diff[0], 2), diff_ms_max=round(diff[-1], 2),
+                        diff_us_per_step=round(diff[len(diff) // 2] / n * 1e3, 1),
+                        plain_reps_ms=[round(t, 2) for t in ts[False]], edit_reps_ms=[round(t, 2) for t in ts[True]])
+            rows.append(line)
+            print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}, guided (cfg 7.5), edit {a.edit}; {torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'sampler':>22} {'plain ms':>9} {'edit ms':>9} {'diff ms (min..max)':>22} {'us/step':>8}")
+    for r in rows:
+        spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
+        print(f"{r['precision']:>9} {r['sampler']:>22} {r['plain_ms']:>9.1f} {r['edit_ms']:>9.1f} {spread:>22} "
+              f"{r['diff_us_per_step']:>8.1f}")
 
 
 if __name__ == "__main__":
