@@ -384,6 +384,17 @@ int mdm_guided_update_inpaint(const float* x, const float* eps_c, const float* e
                               const float* noise, const float* known, const float* mask, int64_t n, const float* tab,
                               const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, float cfg_scale,
                               int32_t clip_denoised, float* x_out, float* x0_out, void* stream);
+/* Composed guidance: nconds = K prompts per sample.  eps is [(K + 1) * n]: the K condition blocks in order, then the
+ * unconditional block; weights is [K * n], condition-major (block k = w_k).  With x0_k and x0_u as in mdm_guided_update
+ * (each clamped when clip_denoised): x0 = x0_u + cfg_scale * sum_k w_k (x0_k - x0_u), then, when known and mask are both
+ * set, x0 = (1 - mask)*x0 + mask*known, then x_out = cx*x + c0*x0 + c1*x0_prev + cn*noise and x0_out = x0 as above.
+ * K = 1 with weights 1 equals mdm_guided_update (known / mask NULL) and mdm_guided_update_inpaint bit for bit.
+ * MDM_ERR_ARG: K outside [1, MDM_COMPOSE_MAX_K], only one of known / mask, or the checks of mdm_guided_update. */
+enum { MDM_COMPOSE_MAX_K = 8 };
+int mdm_composed_update(const float* x, const float* eps, int32_t nconds, const float* weights, const float* x0_prev,
+                        const float* noise, const float* known, const float* mask, int64_t n, const float* tab,
+                        const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, float cfg_scale,
+                        int32_t clip_denoised, float* x_out, float* x0_out, void* stream);
 
 /* Counter-based gaussian noise (Philox4x32-10 + Box-Muller, csrc/noise.hip): out[s, e] for s < nsamples, e < per_sample is
  * a function of (seed, sample0 + s, stream, e) only, where stream = *stream_dev when non-NULL (the device-resident timestep

@@ -22,6 +22,11 @@ Motion editing: ``model_kwargs`` may carry ``inpaint_motion`` (a known normalise
 ``inpaint_mask`` (in [0, 1], broadcastable to it).  Every loop and single step then replaces the guided x0 of each step by
 ``(1 - m) x0 + m k`` before its update (prefix completion, in-betweening, body-part regeneration); the update of every sampler
 goes through the same fused kernel (``mdm_guided_update_inpaint``), DDPM with the ``"ddpm"`` coefficient table.
+
+Composed guidance: ``model_kwargs`` may carry K prompts per sample (``compose_xf_proj`` / ``compose_xf_out`` or
+``compose_text``) and weight maps ``compose_weights``; every guided loop then runs (K + 1)B rows through the forward and
+combines ``x0 = x0_u + s * sum_k w_k (x0_k - x0_u)`` in one fused kernel (``mdm_composed_update``):
+time-varied and body-part control, negative prompts.
 """
 from __future__ import annotations
 
@@ -469,7 +474,8 @@ class SpacedDiffusion(GaussianDiffusion):
 
 
 # runner modes: "ddpm" / "ddim" unguided (B rows); "cfg" guided DDPM, "cfg_ddim" guided DDIM, "cfg_dpmpp" guided
-# DPM-Solver++ ([cond | uncond] = 2B rows); the last two share the fused update of csrc/solver.hip
+# DPM-Solver++ ([cond | uncond] = 2B rows, (K + 1)B with K composed prompts); the last two share the fused update of
+# csrc/solver.hip
 _GUIDED = ("cfg", "cfg_ddim", "cfg_dpmpp")
 _COEF_KIND = {"cfg_ddim": "ddim", "cfg_dpmpp": "dpmpp"}
 # motion editing: every mode's update through the masked fused kernel, with these coefficient tables
@@ -506,6 +512,62 @@ def check_inpaint_kwargs(kw, shape):
     return known, mask
 
 
+def check_compose_kwargs(kw, shape, mode=None):
+    """The composition inputs of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when no ``compose_*`` key is
+    given, else a dict with ``weights`` broadcast to (B, K, T, F) (a view), ``K``, and either ``xf_proj`` (B, K, Dt) and
+    ``xf_out`` (B, K, N, Dt) or ``text`` (B lists of K captions, for ``model.encode_text``).  Every input leads with B, so
+    dist.shard_kwargs slices them.  The weights lead with (B, K) and are aligned on those dims: (B, K) is per sample and
+    prompt, (B, K, T) per frame, (B, K, 1, F) per feature column.
+    Raises ValueError for weights without prompts or prompts without weights, both embeddings and captions, one embedding
+    without the other, shape or broadcast errors, K differing between samples or above MDM_COMPOSE_MAX_K, non-finite
+    weights, ``xf_proj`` / ``xf_out`` given as well, and (with ``mode``) a mode without guidance.  Host logic."""
+    w, cp, co, ct = (kw.get(k) for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text"))
+    if w is None and cp is None and co is None and ct is None:
+        return None
+    if mode is not None and mode not in _GUIDED:
+        raise ValueError(f"composed prompts need classifier-free guidance; mode {mode!r} has none")
+    if kw.get("xf_proj") is not None or kw.get("xf_out") is not None:
+        raise ValueError("xf_proj / xf_out and compose_* are exclusive: the prompts of a composed sample are compose_*")
+    if w is None:
+        raise ValueError("compose_weights is required with composed prompts")
+    if ct is not None and (cp is not None or co is not None):
+        raise ValueError("give compose_text or compose_xf_proj / compose_xf_out, not both")
+    if ct is None and (cp is None or co is None):
+        raise ValueError("composed prompts need compose_text or both compose_xf_proj and compose_xf_out")
+    B, T, F_ = (int(v) for v in shape)
+    if ct is not None:
+        if isinstance(ct, str) or len(ct) != B:
+            raise ValueError(f"compose_text must hold {B} sequences of captions, one per sample")
+        for seq in ct:
+            if isinstance(seq, str) or not all(isinstance(c, str) for c in seq):
+                raise ValueError("each entry of compose_text must be a sequence of caption strings")
+        ks = {len(seq) for seq in ct}
+        if len(ks) != 1:
+            raise ValueError(f"every sample must have the same number of prompts, not {sorted(ks)}")
+        K = ks.pop()
+        ct = [list(seq) for seq in ct]
+    else:
+        cp, co = torch.as_tensor(cp), torch.as_tensor(co)
+        if cp.dim() != 3 or co.dim() != 4 or cp.shape[0] != B or co.shape[0] != B or cp.shape[1] != co.shape[1]:
+            raise ValueError(f"compose_xf_proj {tuple(cp.shape)} / compose_xf_out {tuple(co.shape)} must be (B={B}, K, Dt) "
+                             "and (B, K, N, Dt)")
+        K = int(cp.shape[1])
+    if not 1 <= K <= L.COMPOSE_MAX_K:
+        raise ValueError(f"{K} prompts per sample: the composed update takes 1 to {L.COMPOSE_MAX_K}")
+    w = torch.as_tensor(w)
+    if not w.is_floating_point():
+        raise ValueError("compose_weights must be floating point")
+    if w.dim() < 2 or w.dim() > 4 or tuple(w.shape[:2]) != (B, K):
+        raise ValueError(f"compose_weights of shape {tuple(w.shape)} must lead with (B, K) = {(B, K)} and have at most 4 dims")
+    try:
+        w = w.reshape(tuple(w.shape) + (1,) * (4 - w.dim())).expand(B, K, T, F_)
+    except RuntimeError:
+        raise ValueError(f"compose_weights of shape {tuple(w.shape)} does not broadcast to {(B, K, T, F_)}") from None
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("compose_weights has non-finite values")
+    return {"weights": w, "K": K, "xf_proj": cp, "xf_out": co, "text": ct}
+
+
 class _StepRunner:
     """Static buffers + (optionally) one captured hipGraph for a whole denoising step."""
 
@@ -531,31 +593,45 @@ class _StepRunner:
         length = torch.as_tensor(length).to(self.dev, torch.int32)
         if getattr(model, "ephemeral_mode", "frozen") == "resample":
             self.use_graph = False  # fresh random projections are drawn on the host before every forward
-        xp, xo = kw.get("xf_proj"), kw.get("xf_out")
-        if xp is None or xo is None:
-            xp, xo = model.encode_text(kw["text"], self.dev)
+        # composed guidance: K prompts per sample, laid out condition-major (row k*B + b = prompt k of sample b)
+        comp = check_compose_kwargs(kw, shape, mode)
+        self.K = 1 if comp is None else comp["K"]
+        if comp is not None:
+            K = self.K
+            if comp["text"] is not None:  # B*K captions in one encoder call, sample-major, then (B, K, ...)
+                xp, xo = model.encode_text([c for seq in comp["text"] for c in seq], self.dev)
+                xp, xo = xp.reshape(B, K, *xp.shape[1:]), xo.reshape(B, K, *xo.shape[1:])
+            else:
+                xp, xo = comp["xf_proj"], comp["xf_out"]
+            xp, xo = xp.transpose(0, 1).flatten(0, 1), xo.transpose(0, 1).flatten(0, 1)
+        else:
+            xp, xo = kw.get("xf_proj"), kw.get("xf_out")
+            if xp is None or xo is None:
+                xp, xo = model.encode_text(kw["text"], self.dev)
         xp, xo = xp.to(self.dev, torch.float32), xo.to(self.dev, torch.float32)
-        if mode in _GUIDED:  # cond rows then uncond rows of the same samples, one forward of 2B rows
+        if mode in _GUIDED:  # cond rows then uncond rows of the same samples, one forward of (K + 1)B rows
             up, uo = kw.get("xf_proj_uncond"), kw.get("xf_out_uncond")
             if up is None or uo is None:
                 up, uo = model.uncond_embedding(B, self.dev)
             up, uo = up.to(self.dev, torch.float32), uo.to(self.dev, torch.float32)
-            self.len2 = torch.cat([length, length], 0)
-            self.R = 2 * B
+            self.len2 = torch.cat([length] * (self.K + 1), 0)
+            self.R = (self.K + 1) * B
             # A real tokenizer gives the empty caption fewer tokens than the captions (N = 8 + 2 vs 8 + longest caption,
             # text_encoder.py:25-43) and the reference's cross-attention has no text mask, so the shorter side must NOT
             # see padding.  Default: the shorter half is padded with zero rows and the text cache carries a per-row token
             # count (MdmTextCache.ntok) under which those rows have weight exactly 0 in both cross-attentions -- still ONE
             # forward of 2B rows.  model.ragged_text = "split": two B-row forwards with their own text caches instead.
+            # (Composed: the K prompt groups share one token count, so the same holds with (K + 1) groups of B rows.)
             ragged = uo.shape[1] != xo.shape[1]
             self.split_halves = ragged and (getattr(model, "ragged_text", "mask") == "split" or not hasattr(model, "prepare_text"))
             if self.split_halves:
                 self.xp, self.xo = None, None
-                self.halves = [(xp.contiguous(), xo.contiguous()), (up.contiguous(), uo.contiguous())]
+                self.halves = [(xp[k * B:(k + 1) * B].contiguous(), xo[k * B:(k + 1) * B].contiguous())
+                               for k in range(self.K)] + [(up.contiguous(), uo.contiguous())]
             else:
                 if ragged:
                     nmax = max(xo.shape[1], uo.shape[1])
-                    self.ntok = [xo.shape[1]] * B + [uo.shape[1]] * B
+                    self.ntok = [xo.shape[1]] * (self.K * B) + [uo.shape[1]] * B
                     xo = torch.nn.functional.pad(xo, (0, 0, 0, nmax - xo.shape[1]))
                     uo = torch.nn.functional.pad(uo, (0, 0, 0, nmax - uo.shape[1]))
                 self.xp = torch.cat([xp, up], 0).contiguous()
@@ -579,9 +655,14 @@ class _StepRunner:
             self.mask = torch.empty_like(self.noise)
             self.known.copy_(edit[0])
             self.mask.copy_(edit[1])
-        # few-step modes (and every mode when editing): per-step coefficients of the fused update; self.x0 doubles as
-        # x0_prev (updated in place)
-        kind = _EDIT_COEF_KIND[mode] if self.known is not None else _COEF_KIND.get(mode)
+        # composed guidance: the weights, dense f32 [K, n] (condition-major like the eps rows), owned by the runner
+        self.cw = None
+        if comp is not None:
+            self.cw = torch.empty((self.K, B, T, Fe), dtype=torch.float32, device=self.dev)
+            self.cw.copy_(comp["weights"].transpose(0, 1))
+        # few-step modes (and every mode when editing or composing): per-step coefficients of the fused update; self.x0
+        # doubles as x0_prev (updated in place)
+        kind = _EDIT_COEF_KIND[mode] if self.known is not None or self.cw is not None else _COEF_KIND.get(mode)
         self.coef = diff._device_coef(kind, eta, order, self.dev) if kind is not None else None
         self.graph = None
         # time-embedding chain tabulated per timestep + text half of the gated fusion: once per loop, not per step
@@ -630,7 +711,9 @@ class _StepRunner:
         if use_noise and self.philox is not None:  # step noise = f(seed, global sample, t, element); t read on the device
             self._philox_fill(self.noise, C.c_void_p(self.t_dev.data_ptr()), 0, s)
         x = self.xx[:B]
-        if self.R == 2 * B:
+        if self.K > 1:  # x_t into every prompt group and the unconditional one
+            self.xx[B:].view(self.K, B, self.T, self.Fe).copy_(x.unsqueeze(0).expand(self.K, -1, -1, -1))
+        elif self.R == 2 * B:
             self.xx[B:].copy_(x)
         if self.tmap is not None:
             L.check(lib.mdm_fill_timesteps_mapped(C.c_void_p(self.ts.data_ptr()), C.c_int64(self.R),
@@ -662,7 +745,17 @@ class _StepRunner:
             self.model(self.xx, self.ts, self.len2, xf_proj=self.xp, xf_out=self.xo, out=self.eps)
         noise = C.c_void_p(self.noise.data_ptr() if use_noise else 0)
         steps = C.c_int32(self.d.num_timesteps)
-        if self.known is not None:
+        if self.cw is not None:
+            x0 = C.c_void_p(self.x0.data_ptr())
+            edit = self.known is not None
+            L.check(lib.mdm_composed_update(
+                C.c_void_p(x.data_ptr()), C.c_void_p(self.eps.data_ptr()), C.c_int32(self.K),
+                C.c_void_p(self.cw.data_ptr()), x0 if self.mode == "cfg_dpmpp" else C.c_void_p(0), noise,
+                C.c_void_p(self.known.data_ptr() if edit else 0), C.c_void_p(self.mask.data_ptr() if edit else 0),
+                C.c_int64(n), C.c_void_p(self.tab.data_ptr()), C.c_void_p(self.coef.data_ptr()), steps,
+                C.c_void_p(self.t_dev.data_ptr()), C.c_int32(0), C.c_float(self.cfg_scale), C.c_int32(int(self.clip)),
+                C.c_void_p(x.data_ptr()), x0, s), "mdm_composed_update")
+        elif self.known is not None:
             x0 = C.c_void_p(self.x0.data_ptr())
             eps_u = C.c_void_p(self.eps[B:].data_ptr() if self.mode in _GUIDED else 0)
             L.check(lib.mdm_guided_update_inpaint(

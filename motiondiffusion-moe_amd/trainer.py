@@ -5,7 +5,9 @@ same ``generate(caption, m_lens, dim_pose, batch_size)`` -> list of (T, dim_pose
 (``encoder``, ``ep``, ``total_it``, ``opt_encoder``).  The generate methods also take ``sampler`` ("ddpm" | "ddim" |
 "dpmpp2m"), ``sample_steps`` and ``eta``: few-step guided sampling of the same model on a respaced schedule; the defaults
 run the reference's guided DDPM over every step.  ``edit_motion`` / ``edit_mask`` turn any of them into motion editing
-(prefix completion, in-betweening, body-part regeneration; masks from ``motion_edit``).  The training loop (forward/backward/update/train) is out of
+(prefix completion, in-betweening, body-part regeneration; masks from ``motion_edit``).  ``prompt_weights`` with K
+captions per sample composes them under per-prompt weight maps (time-varied and body-part control, negative prompts;
+weights from ``motion_compose``).  The training loop (forward/backward/update/train) is out of
 scope for this build and raises.
 """
 from __future__ import annotations
@@ -82,6 +84,42 @@ class DDPMTrainer(object):
                              f"{tuple(k.shape)}") from None
         return {"inpaint_motion": k[rows, :T], "inpaint_mask": msk[rows, :T]}
 
+    @staticmethod
+    def _compose_weights(caption, prompt_weights, dim_pose):
+        """Check a composed call: every ``caption[i]`` a sequence of the same K strings; returns ``prompt_weights`` as a
+        float32 tensor broadcast to (N, K, T_w, dim_pose) (T_w = its frame dim, 1 when it has none; a view)."""
+        N = len(caption)
+        for c in caption:
+            if isinstance(c, str) or not all(isinstance(v, str) for v in c):
+                raise ValueError("with prompt_weights every caption must be a sequence of K strings")
+        ks = {len(c) for c in caption}
+        if len(ks) != 1:
+            raise ValueError(f"every sample must have the same number of prompts, not {sorted(ks)}")
+        K = ks.pop()
+        w = torch.as_tensor(prompt_weights, dtype=torch.float32)
+        if w.dim() > 4:
+            raise ValueError(f"prompt_weights of shape {tuple(w.shape)} has more dims than (N, K, T, dim_pose)")
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("prompt_weights has non-finite values")
+        w = w.reshape(tuple(w.shape) + (1,) * (4 - w.dim()))
+        try:
+            return w.expand(N, K, w.shape[2], dim_pose)
+        except RuntimeError:
+            raise ValueError(f"prompt_weights of shape {tuple(w.shape)} does not broadcast to (N={N}, K={K}, T, "
+                             f"{dim_pose})") from None
+
+    @staticmethod
+    def _text_kwargs(m, caption, weights, rows, T, device):
+        """Text model kwargs of one batch: the captions' embeddings, or with ``weights`` (from _compose_weights) the
+        composed prompts and the rows ``rows`` / first T frames of the weights."""
+        if weights is None:
+            xf_proj, xf_out = m.encode_text(caption, device)
+            return {"xf_proj": xf_proj, "xf_out": xf_out, "text": caption}
+        if weights.shape[2] != 1 and weights.shape[2] < T:
+            raise ValueError(f"prompt_weights has {weights.shape[2]} frames, the batch {T}")
+        w = weights[rows]
+        return {"compose_text": [list(c) for c in caption], "compose_weights": w[:, :, :T] if w.shape[2] != 1 else w}
+
     def _sample(self, m, shape, sampler, sample_steps, eta, **kw):
         if eta != 0.0 and sampler != "ddim":
             raise ValueError("eta applies to the ddim sampler only")
@@ -94,32 +132,38 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_batch(self, caption, m_lens, dim_pose, *, noise=None, step_noise=None, progress=True, seed=None,
-                       sample_offset=0, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None):
+                       sample_offset=0, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
+                       prompt_weights=None):
         """``edit_motion`` (B, T_max, dim_pose), normalised, and ``edit_mask`` broadcastable to it, values in [0, 1]: the
-        batch's first T frames of both are kept where the mask is 1 (exactly, for a binary mask) and generated elsewhere."""
+        batch's first T frames of both are kept where the mask is 1 (exactly, for a binary mask) and generated elsewhere.
+        ``prompt_weights`` (B, K, ...) broadcastable to (B, K, T_max, dim_pose): ``caption[i]`` is then a sequence of K
+        captions, composed on every step under these weights."""
         m = self._model()
         m_lens = torch.as_tensor(m_lens)
         T = min(int(m_lens.max()), m.num_frames)
         B = len(caption)
+        w = None if prompt_weights is None else self._compose_weights(caption, prompt_weights, dim_pose)
         edit = self._edit_kwargs(edit_motion, edit_mask, slice(0, B), T, dim_pose)
-        xf_proj, xf_out = m.encode_text(caption, self.device)
+        text = self._text_kwargs(m, caption, w, slice(0, B), T, self.device)
         return self._sample(
             m, (B, T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress, noise=noise,
-            step_noise=step_noise,
-            model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": m_lens, "text": caption, **edit},
-            seed=seed, sample_offset=sample_offset)
+            step_noise=step_noise, model_kwargs={**text, "length": m_lens, **edit}, seed=seed,
+            sample_offset=sample_offset)
 
     @torch.no_grad()
     def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None, sampler="ddpm",
-                 sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None):
+                 sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, prompt_weights=None):
         """``seed``: sample i's noise is then a function of (seed, i) only (counter-based device generator), so the result
         does not depend on ``batch_size``; without it the torch generator is used, as in the reference.
         ``noises``: optional list with one ``(x_T, [step noise, ...])`` pair per batch, replacing the draws (parity tests).
         ``sampler`` / ``sample_steps`` / ``eta``: see ``sampling_diffusion``; e.g. ``sampler="dpmpp2m", sample_steps=20``.
         ``edit_motion`` (N, T_max, dim_pose) and ``edit_mask`` (broadcastable to it): motion editing, see ``generate_batch``;
-        each batch takes its samples' rows."""
+        each batch takes its samples' rows.  ``prompt_weights`` (N, K, ...): composed prompts, see ``generate_batch``; each
+        batch takes its samples' rows."""
         N = len(caption)
         self.eval_mode()
+        if prompt_weights is not None:
+            prompt_weights = self._compose_weights(caption, prompt_weights, dim_pose)
         if edit_motion is not None and edit_mask is not None:
             edit_motion = torch.as_tensor(edit_motion)
             edit_mask = self._edit_kwargs(edit_motion, edit_mask, slice(None), edit_motion.shape[1],
@@ -133,24 +177,27 @@ class DDPMTrainer(object):
                                       sample_offset=cur, noise=x_T, step_noise=step_noise, sampler=sampler,
                                       sample_steps=sample_steps, eta=eta,
                                       edit_motion=None if edit_motion is None else edit_motion[cur:end],
-                                      edit_mask=None if edit_mask is None else edit_mask[cur:end])
+                                      edit_mask=None if edit_mask is None else edit_mask[cur:end],
+                                      prompt_weights=None if prompt_weights is None else prompt_weights[cur:end])
             all_output.extend(out[i] for i in range(out.shape[0]))
             cur += batch_size
         return all_output
 
     @torch.no_grad()
     def generate_bucketed(self, caption, m_lens, dim_pose, batch_size=32, *, unit_length=4, seed=None, group=None,
-                          progress=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None):
+                          progress=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
+                          prompt_weights=None):
         """Evaluation-scale variant of ``generate``: same inputs and the same kind of result (a
         list of per-sample ``(T_batch, dim_pose)`` tensors in the caller's order, valid up to each sample's length),
         but batches hold samples of similar length (less padded work) and, under ``torch.distributed``, are dealt over
         the ranks with one all_gather at the end.  With ``seed`` every sample's noise is a function of (seed, its index in
         ``caption``) only -- the same as ``generate(..., seed=)`` -- so on each sample's valid frames the two give identical
         results whatever the bucketing (tests/test_sampler_gpu.py).  ``edit_motion`` / ``edit_mask``: as in ``generate``;
-        each bucket takes its samples' rows and its first T frames."""
+        each bucket takes its samples' rows and its first T frames; so does ``prompt_weights``."""
         from . import dist as D
         m = self._model()
         self.eval_mode()
+        w = None if prompt_weights is None else self._compose_weights(caption, prompt_weights, dim_pose)
         lens = torch.as_tensor(m_lens).flatten().long().cpu()
         plan = D.plan_buckets(lens, batch_size, m.num_frames, unit_length)
 
@@ -158,24 +205,26 @@ class DDPMTrainer(object):
             cap = [caption[i] for i in idx.tolist()]
             ln = lens[idx].clamp(max=T).to(self.device)
             edit = self._edit_kwargs(edit_motion, edit_mask, idx, T, dim_pose)
-            xf_proj, xf_out = m.encode_text(cap, self.device)
+            text = self._text_kwargs(m, cap, w, idx, T, self.device)
             return self._sample(
                 m, (len(cap), T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress,
-                model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": ln, "text": cap, **edit},
+                model_kwargs={**text, "length": ln, **edit},
                 seed=seed, sample_offset=idx)  # noise keyed on each row's index in the CALLER's list: == generate(seed=)
 
         return D.run_plan(plan, run_bucket, len(caption), m.num_frames, dim_pose, self.device, group)
 
     @torch.no_grad()
     def generate_joints(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, joints_num=22, sigma=1.0,
-                        bucketed=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, **kw):
+                        bucketed=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
+                        prompt_weights=None, **kw):
         """``generate`` followed by the reference's post-processing (tools/visualization.py:21-27,89) on the device:
         list of ``(m_len, joints_num, 3)`` joint positions, temporally smoothed with a gaussian of width ``sigma``.
-        ``edit_motion`` / ``edit_mask``: motion editing in normalised feature space, as in ``generate``."""
+        ``edit_motion`` / ``edit_mask``: motion editing in normalised feature space, as in ``generate``;
+        ``prompt_weights``: composed prompts, as in ``generate``."""
         from .postprocess import motion_to_joints
         gen = self.generate_bucketed if bucketed else self.generate
         motions = gen(caption, m_lens, dim_pose, batch_size, sampler=sampler, sample_steps=sample_steps, eta=eta,
-                      edit_motion=edit_motion, edit_mask=edit_mask, **kw)
+                      edit_motion=edit_motion, edit_mask=edit_mask, prompt_weights=prompt_weights, **kw)
         lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
         x = torch.zeros((len(motions), max(mo.shape[0] for mo in motions), dim_pose), device=motions[0].device)
         for i, mo in enumerate(motions):

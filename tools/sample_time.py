@@ -15,6 +15,11 @@ without and with that frame mask (``edit_motion``/``edit_mask``), alternating, `
 reports both medians and the per-pair difference (median, min, max; per generation and per step).
 
     timeout -k 10 900 python tools/sample_time.py --edit prefix:40 --reps 5 --precisions 1
+
+``--compose K`` measures composed guidance instead: DDIM-50 and DPM-Solver++(2M)-20 generations with K prompts per sample
+(a timeline split, ``prompt_weights``) against the same plain generations, alternating, as for ``--edit``; K may be a list.
+
+    timeout -k 10 900 python tools/sample_time.py --compose 2,3 --reps 5 --precisions 1
 """
 import argparse
 import importlib
@@ -38,6 +43,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=196)
     ap.add_argument("--edit", default=None, help="prefix:N | inbetween:H,T: time editing against plain generation")
+    ap.add_argument("--compose", default=None, help="K[,K...]: time K-prompt composed generation against plain")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_time.py measures the GPU sampler: no GPU found")
@@ -53,6 +59,8 @@ def main():
     caps = [f"caption {i}" for i in range(B)]
     if a.edit:
         return edit_main(a, tr, m, caps, length, B, T)
+    if a.compose:
+        return compose_main(a, tr, m, caps, length, B, T)
     rows = []
     for prec in [int(p) for p in a.precisions.split(",")]:
         m.precision = prec
@@ -142,6 +150,49 @@ def edit_main(a, tr, m, caps, length, B, T):
         spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
         print(f"{r['precision']:>9} {r['sampler']:>22} {r['plain_ms']:>9.1f} {r['edit_ms']:>9.1f} {spread:>22} "
               f"{r['diff_us_per_step']:>8.1f}")
+
+
+def compose_main(a, tr, m, caps, length, B, T):
+    MC = importlib.import_module("motiondiffusion-moe_amd.motion_compose")
+    xp_all, xo_all = m.text_encoder_fn(caps, torch.device("cuda:0"))  # one embedding per caption, looked up by name
+    row = {c: i for i, c in enumerate(caps)}
+    m.text_encoder_fn = lambda text, device: (xp_all[[row[c] for c in text]].to(device),
+                                              xo_all[[row[c] for c in text]].to(device))
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for K in [int(k) for k in a.compose.split(",")]:
+            w = MC.timeline_weights(T, [T * (k + 1) // K for k in range(K - 1)], blend=10)[None]
+            kcaps = [tuple(caps[(i + k) % B] for k in range(K)) for i in range(B)]
+            for sampler, steps, n in (("ddim", 50, 50), ("dpmpp2m", 20, 20)):
+                def gen(comp):
+                    if comp:
+                        return tr.generate(kcaps, length, 263, batch_size=B, seed=0, sampler=sampler, sample_steps=steps,
+                                           prompt_weights=w)
+                    return tr.generate(caps, length, 263, batch_size=B, seed=0, sampler=sampler, sample_steps=steps)
+                for comp in (False, True):  # warm-up
+                    assert all(torch.isfinite(o).all() for o in gen(comp))
+                ts = {False: [], True: []}
+                for _ in range(a.reps):
+                    for comp in (False, True):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        gen(comp)
+                        torch.cuda.synchronize()
+                        ts[comp].append((time.perf_counter() - t0) * 1e3)
+                med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+                name = {"ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+                line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, K=K, plain_ms=round(med[False], 2),
+                            compose_ms=round(med[True], 2), ratio=round(med[True] / med[False], 3),
+                            plain_reps_ms=[round(t, 2) for t in ts[False]], compose_reps_ms=[round(t, 2) for t in ts[True]])
+                rows.append(line)
+                print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}, guided (cfg 7.5), composed prompts; {torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'K':>2} {'sampler':>22} {'plain ms':>9} {'composed ms':>12} {'ratio':>6} {'(K+1)/2':>8}")
+    for r in rows:
+        print(f"{r['precision']:>9} {r['K']:>2} {r['sampler']:>22} {r['plain_ms']:>9.1f} {r['compose_ms']:>12.1f} "
+              f"{r['ratio']:>6.2f} {(r['K'] + 1) / 2:>8.1f}")
 
 
 if __name__ == "__main__":
