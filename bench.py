@@ -3,10 +3,15 @@
 model_size=small, 8 experts, B=32 per GPU, T=196, 263-d, 1000-step schedule, bf16 MFMA).
 
     python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = the whole hot path over one batch: cond+uncond rows (2B) through the denoiser, guidance on pred_xstart,
 posterior update, noise.  Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+--full also measures everything else after the timed steps: the MoE block and the dominant kernel alone and live
+(roofline), the per-mode table (parity_mode, modes), the other BASELINE configs (configs) and the CPU oracle (cpu_baseline).
 """
 import argparse
 import importlib
@@ -490,7 +495,11 @@ def main():
                     help="1 = bf16 MFMA (default: the format BASELINE configs[1] names), 2 = fp16 MFMA (same speed, 8x smaller error), "
                          "3 = bf16x3 fp32-grade (the only mode inside the 1e-3 parity bound: always reported beside the headline as "
                          "parity_mode), 4 = mixed (bf16x3 + fp16 expert/FFN GEMMs)")
-    ap.add_argument("--no-modes", action="store_true", help="skip the per-mode timing / error table")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the MoE block and the dominant "
+                         "kernel alone and inside real steps (roofline), the per-mode table, the other BASELINE configs and the "
+                         "CPU baseline (each leg can be skipped with its --no-* option)")
+    ap.add_argument("--no-modes", action="store_true", help="with --full: skip the per-mode timing / error table")
     ap.add_argument("--sampler", default="cfg", choices=["cfg", "ddim"],
                     help="cfg = guided DDPM step (2 forwards batched; configs[1], [2]); ddim = DDIM step (1 forward; configs[3])")
     ap.add_argument("--batch", type=int, default=32, help="samples per GPU")
@@ -501,11 +510,12 @@ def main():
                          "0 = the same count")
     ap.add_argument("--schedule", type=int, default=1000)
     ap.add_argument("--cfg-scale", type=float, default=7.5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle's timing")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--streams", type=int, default=1, help="concurrent HIP streams the step's rows are split over")
     ap.add_argument("--variant", type=int, default=0, help="kernel-selection knob for same-box A/B runs (mdm_set_gemm_variant)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the configs[2] / configs[3] timings (big model) of the N = 1 line")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="with --full: skip the configs[2] / configs[3] / configs[4] timings (big model) of the N = 1 line")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / timing-protocol rehearsal on the CPU: gloo ranks, a stand-in step, no GPU and no model")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -601,14 +611,17 @@ def main():
         steps_per_s = a.steps / dt
         value = steps_per_s * world * (B / 32.0)
         achieved = flop_step / (dt / a.steps)
-        rows_b = (2 if a.sampler == "cfg" else 1) * B
-        moe_dt, moe_flop = moe_block_rate(m, rows_b, T, a.precision)
-        dom = expert_mlp_rate(m, rows_b, T)
-        done[0] = 0
-        r.t_dev.fill_(a.schedule - 1)
-        live = probe_dominant_kernel(r, m) if not r.chunks else None  # single-stream steps only
-        # (the per-mode table is a single-GPU report: a scaling run keeps rank 0 no longer than the other ranks)
-        modes = None if (a.no_modes or world > 1 or a.sampler != "cfg" or a.config != "small") else mode_table(a, m, inputs, host, diff, kw, dev, a.precision, ms)
+        moe = dom = live = modes = None
+        if a.full:  # measurements of their own, after the timed steps: none of them feeds `value`
+            rows_b = (2 if a.sampler == "cfg" else 1) * B
+            moe = moe_block_rate(m, rows_b, T, a.precision)
+            dom = expert_mlp_rate(m, rows_b, T)
+            done[0] = 0
+            r.t_dev.fill_(a.schedule - 1)
+            live = probe_dominant_kernel(r, m) if not r.chunks else None  # single-stream steps only
+            # (the per-mode table is a single-GPU report: a scaling run keeps rank 0 no longer than the other ranks)
+            if not (a.no_modes or world > 1 or a.sampler != "cfg" or a.config != "small"):
+                modes = mode_table(a, m, inputs, host, diff, kw, dev, a.precision, ms)
         # fabric bytes per step from the committed rocprofv3 --pmc passes -- only for this exact workload AND these kernel sources
         pmc_j, traffic_note = (None, "the committed counter profiles are of the default workload (small, B=32, T=196, CFG)")
         if (a.config, B, T, a.sampler) == ("small", 32, 196, "cfg"):
@@ -635,11 +648,13 @@ def main():
                          "traffic_note": traffic_note,
                          "what": "whole step: algorithmic FLOP of 2 forwards / wall time per step",
                          "whole_step": {"achieved": round(achieved / 1e12, 2), "frac": round(achieved / PEAK[a.precision], 4),
-                                        "traffic": traffic},
-                         "moe_ffn_block": {"achieved": round(moe_flop / moe_dt / 1e12, 2), "us": round(moe_dt * 1e6, 1),
-                                           "frac": round(moe_flop / moe_dt / PEAK[a.precision], 4),
-                                           "rows": 2 * B * T, "timed_with": "HIP events on the launch stream"}},
+                                        "traffic": traffic}},
         }
+        if moe is not None:
+            moe_dt, moe_flop = moe
+            line["roofline"]["moe_ffn_block"] = {"achieved": round(moe_flop / moe_dt / 1e12, 2), "us": round(moe_dt * 1e6, 1),
+                                                 "frac": round(moe_flop / moe_dt / PEAK[a.precision], 4),
+                                                 "rows": 2 * B * T, "timed_with": "HIP events on the launch stream"}
         if dom is not None:
             line["roofline"]["dominant_kernel_alone"] = {
                 "name": "fused_mlp_stream_kernel (expert W1-GELU-W2, csrc/mlp_stream.hip)", "achieved": round(dom[1] / dom[0] / 1e12, 2),
@@ -683,7 +698,7 @@ def main():
                                           f"{line['parity_mode']['steps_per_s']} steps/s (parity_mode)")
         elif a.precision == 3:
             line["config"]["mode"] = "precision 3 (fp32-grade, the parity mode)"
-        if world == 1 and not a.no_other_configs and (a.config, a.sampler) == ("small", "cfg"):
+        if a.full and world == 1 and not a.no_other_configs and (a.config, a.sampler) == ("small", "cfg"):
             # the other single-GPU configs of BASELINE.json, measured in this process so that the driver's record carries them
             del r
             torch.cuda.empty_cache()
@@ -696,7 +711,7 @@ def main():
                               "of the routing decisions differ with free routing (fp16 beside it: 2.0e-3, 1.4 %; "
                               "tests/test_fp8_gpu.py); a throughput figure, not a usable-accuracy mode")
                 line["configs"]["configs[4] (per GPU)"] = c4
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(host, inputs, a.schedule, a.cfg_scale)
         if outputs is not None:
             line["dump_outputs"] = dump_outputs(a.dump_outputs, outputs)

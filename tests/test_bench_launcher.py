@@ -33,6 +33,13 @@ def test_single_rank_dry_run_needs_no_launcher():
     assert j["n_gpus"] == 1
 
 
+def test_full_is_an_option_of_every_run():
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "0", "--dry-run", "--full"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1
+    assert "--full" in _run(["--help"]).stdout
+
+
 def test_mismatched_world_size_is_refused():
     r = _run(["--gpus", "2", "--dry-run"], env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
