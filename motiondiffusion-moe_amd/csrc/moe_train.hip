@@ -310,18 +310,24 @@ __global__ __launch_bounds__(256) void gate_ln_bwd_kernel(const float* __restric
       const int i1 = top_idx[(int64_t)br * 2 * M + 2 * row], i2 = top_idx[(int64_t)br * 2 * M + 2 * row + 1];
       const int r1 = pos4[row * 4 + 2 * br], r2 = pos4[row * 4 + 2 * br + 1];
       const float dp1 = dp[r1], dp2 = dp[r2];
-      float c = 0.f;
+      // softmax backward dl_e = p_e (dp_e - c), c = p1 dp1 + p2 dp2 (only the top-2 have a dp).  For a routed expert the
+      // bracket is written dp1 (1 - p1) - p2 dp2 with 1 - p1 summed from the other probabilities: as p1 -> 1 the difference
+      // dp1 - c cancels down to the fp32 rounding of c and the gradient, proportional to 1 - p1, would lose its digits
+      float p1 = 0.f, p2 = 0.f, q1 = 0.f, q2 = 0.f;  // q = 1 - p of the two routed experts
       for (int e = 0; e < E; ++e) {
         logit[e] /= den;  // probabilities
-        c += logit[e] * ((e == i1 ? dp1 : 0.f) + (e == i2 ? dp2 : 0.f));
+        p1 = e == i1 ? logit[e] : p1, p2 = e == i2 ? logit[e] : p2;
+        q1 += e == i1 ? 0.f : logit[e], q2 += e == i2 ? 0.f : logit[e];
       }
+      const float c = p1 * dp1 + p2 * dp2;
+      const float g1 = dp1 * q1 - p2 * dp2, g2 = dp2 * q2 - p1 * dp1;  // dp1 - c, dp2 - c
       Row<NE, VEC> dh, t2;
       dh.load(dxg + (int64_t)r1 * D, D, lane);
       t2.load(dxg + (int64_t)r2 * D, D, lane);
 #pragma unroll
       for (int j = 0; j < NE; ++j) dh.e[j] += t2.e[j];
       for (int e = 0; e < E; ++e) {
-        const float dl = logit[e] * ((e == i1 ? dp1 : 0.f) + (e == i2 ? dp2 : 0.f) - c);
+        const float dl = logit[e] * (e == i1 ? g1 : (e == i2 ? g2 : -c));
         if (lane == 0) dlogits[((int64_t)br * M + row) * E + e] = dl;
         Row<NE, VEC> g;
         g.load(gwb + (int64_t)e * D, D, lane);

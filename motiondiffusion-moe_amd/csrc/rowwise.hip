@@ -877,7 +877,9 @@ int moe_route(const float* x, int64_t M, int D, int E, const MoeGateParams& p, i
   if (M <= 0) return MDM_OK;
   if (E < 2 || E > 16 || !x || !p.hn || !p.hist || !p.uimp || !p.top_idx || !p.top_val) return MDM_ERR_ARG;
   int nparts = 0;
-  if (D % 64 == 0 && D <= 1024) {
+  // the LDS-staged router exists for D / 64 in {1, 2, 4, 8, 16}; every other width (768, 320, 1000, ...) takes the row kernel
+  const int nv = D % 64 == 0 ? D / 64 : 0;
+  if (nv == 1 || nv == 2 || nv == 4 || nv == 8 || nv == 16) {
     const int smem = 2 * E * D * 4 + 4 * D * 4 + 3 * 32 * 4;  // gate matrices, LayerNorm vectors, counters
     int64_t nb = (M + 15) / 16;
     const int grid = (int)(nb > 512 ? 512 : nb);  // measured end to end: 256 blocks -2 %, 1024 blocks -0.5 %

@@ -77,7 +77,8 @@ def test_block_gradients_match_autograd(D, F, E, Te, De, B, S):
     assert max(errs.values()) < 2e-3, errs
 
 
-@pytest.mark.parametrize("D,F,E,Te,De,B,S,p", [(256, 320, 4, 128, 256, 2, 19, 0.1), (512, 1024, 8, 2048, 512, 2, 24, 0.1), (256, 128, 3, 96, 64, 1, 9, 0.5)])
+@pytest.mark.parametrize("D,F,E,Te,De,B,S,p", [(256, 320, 4, 128, 256, 2, 19, 0.1), (512, 1024, 8, 2048, 512, 2, 24, 0.1), (256, 128, 3, 96, 64, 1, 9, 0.5),
+                                                (1024, 2048, 8, 4096, 4096, 2, 24, 0.1)])
 def test_training_mode_dropout_matches_the_oracle_with_the_same_masks(D, F, E, Te, De, B, S, p):
     """Dropout on each branch's output (multi_branch.py:57) and after the SiLU of the stylization block (stylization.py:16):
     the counter-based masks are restated in numpy (oracle/moe_train_ref.dropout_masks) and applied to the oracle's forward;
