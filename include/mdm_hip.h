@@ -525,6 +525,38 @@ int mdm_route_dump(int32_t* buf, int64_t capacity);
 int mdm_sd_fold_passes(int32_t D, int32_t H, int32_t N);
 int mdm_probe_read(float* us, int32_t* rows, int32_t cap);
 
+/* ---- Text-motion evaluator (csrc/evaluator.hip): the reference's datasets1/evaluator_models.py (MovementConvEncoder :79-99,
+ * TextEncoderBiGRUCo :311-350, MotionEncoderBiGRUCo :353-386), EvaluatorModelWrapper (datasets1/evaluator.py:418-503) and the
+ * formulas of utils/metrics.py.  Every Linear / Conv1d of the three networks runs on mdm_gemm (precision 3); these are the rest. */
+
+/* Bidirectional single-layer GRU over packed sequences (nn.GRU(bidirectional=True) on pack_padded_sequence, evaluator_models.py
+ * :344-346 / :380-382), returning the final states out [B][2H] = [forward | backward].
+ *   gx    [B][T][2][3H]  x W_ih^T + b_ih of each direction (gate rows r, z, n as in PyTorch); b_hh is added here
+ *   w_hh  [2][3H][H], b_hh [2][3H]  weight_hh_l0 / _reverse, bias_hh_l0 / _reverse
+ *   h0    [2][H]         the learned initial state (`hidden`, broadcast over the batch)
+ *   lens_dev / lens_host the same int32 lengths [B] on the device and on the host: any order (no enforce_sorted), each in [1, T]
+ *   ws    mdm_gru_bidir_workspace_bytes(B, H) bytes (two state buffers)
+ * One launch per step (max(lens) launches), both directions per launch.  MDM_ERR_ARG: null pointers, a length outside [1, T],
+ * a short workspace, w_hh / h0 / ws not 16-byte aligned (checked before any launch); MDM_ERR_UNSUPPORTED: H % 16 != 0 or H > 1024. */
+int64_t mdm_gru_bidir_workspace_bytes(int32_t B, int32_t H);
+int mdm_gru_bidir(const float* gx, const float* w_hh, const float* b_hh, const float* h0, const int32_t* lens_dev,
+                  const int32_t* lens_host, int32_t B, int32_t T, int32_t H, float* out, float* ws, int64_t ws_bytes, void* stream);
+/* Row copy of the movement encoder (Conv1d k4 s2 p1 as a GEMM, evaluator_models.py:82-99):
+ * dst [B][T + 2 pad][Cp] = act(src row (b T + t), first C columns), zero columns [C, Cp) and zero pad frames at each end;
+ * act = LeakyReLU(0.2) when leaky != 0.  With pad = 0 and Cp = C the copy may be in place (dst == src, ld_src == C). */
+int mdm_eval_pad_rows(const float* src, int64_t ld_src, int32_t B, int32_t T, int32_t C, int32_t Cp, int32_t pad, int32_t leaky,
+                      float* dst, void* stream);
+/* y[M][N] = LeakyReLU_0.2(LayerNorm(x; w, b, eps)): the middle of the encoders' output_net (evaluator_models.py:320-325, 360-365) */
+int mdm_eval_ln_leaky(const float* x, int32_t M, int32_t N, const float* w, const float* b, float eps, float* y, void* stream);
+/* Matching of B text / motion embedding pairs [B][D] (tools/evaluation.py:163-176, utils/metrics.py:6-46):
+ * dist [B][B] = euclidean distances (optional, may be NULL), rank[i] = #{j : d_ij < d_ii} (R-precision top-k counts the
+ * rows with rank < k), diag[i] = d_ii (the matching score sums it).  One launch.  MDM_ERR_UNSUPPORTED when (D + B) * 4 > 64 KiB. */
+int mdm_eval_matching(const float* text, const float* motion, int32_t B, int32_t D, float* dist, int32_t* rank, float* diag,
+                      void* stream);
+/* Column means of x [N][D] (fp64 sums) and the centred rows xc = x - mean (utils/metrics.py:60-70; the covariance is then
+ * xc^T xc / (N - 1) on mdm_gemm with F32_KSTRIDE operands). */
+int mdm_eval_center(const float* x, int32_t N, int32_t D, float* mean, float* xc, void* stream);
+
 const char* mdm_version(void);
 
 #ifdef __cplusplus

@@ -214,6 +214,48 @@ class DDPMTrainer(object):
         return D.run_plan(plan, run_bucket, len(caption), m.num_frames, dim_pose, self.device, group)
 
     @torch.no_grad()
+    def generate_for_evaluation(self, caption, m_lens, dim_pose, *, mm_num_samples=0, mm_num_repeats=1, unit_length=4,
+                                max_motion_length=196, dataset_name="t2m", seed=None, batch_size=32, sampler="ddpm",
+                                sample_steps=None, eta=0.0, group=None):
+        """The generation half of the reference's ``EvaluationDataset`` (datasets1/evaluator.py:16-121) on
+        ``generate_bucketed``: lengths snapped to ``max(m // unit * unit, min_mov_length * unit)`` (min_mov_length 10 for
+        t2m, 6 for KIT) and capped at ``max_motion_length``; ``mm_num_samples`` captions, drawn with
+        ``RandomState(seed).choice(N, mm_num_samples, replace=False)`` and sorted, are generated ``mm_num_repeats`` times.
+        Frames at or past each length are zero, as the reference's dataset pads them.  Returns a dict:
+          motions (N, max_motion_length, dim_pose) and m_lens (N,): the first generation of every caption
+          mm_idxs (P,), mm_motions (P, mm_num_repeats, max_motion_length, dim_pose), mm_lens (P, mm_num_repeats)."""
+        import numpy as np
+        N = len(caption)
+        if mm_num_samples and not mm_num_samples < N:
+            raise ValueError("mm_num_samples must be smaller than the number of captions (evaluator.py:19)")
+        min_mov = 10 if dataset_name == "t2m" else 6
+        lens = torch.as_tensor(m_lens).flatten().long().cpu()
+        lens = torch.clamp(torch.clamp(lens // unit_length * unit_length, min=min_mov * unit_length), max=max_motion_length)
+        mm_idxs = np.sort(np.random.RandomState(seed).choice(N, mm_num_samples, replace=False)) if mm_num_samples else \
+            np.zeros(0, dtype=np.int64)
+        mm_set = set(mm_idxs.tolist())
+        all_cap, all_len, first = [], [], []
+        for i in range(N):
+            first.append(len(all_cap))
+            for _ in range(mm_num_repeats if i in mm_set else 1):
+                all_cap.append(caption[i])
+                all_len.append(int(lens[i]))
+        gen = self.generate_bucketed(all_cap, torch.tensor(all_len), dim_pose, batch_size, unit_length=unit_length, seed=seed,
+                                     group=group, sampler=sampler, sample_steps=sample_steps, eta=eta)
+        allm = torch.zeros((len(all_cap), max_motion_length, dim_pose), dtype=torch.float32, device=gen[0].device)
+        for k, (mo, n) in enumerate(zip(gen, all_len)):
+            n = min(n, mo.shape[0])
+            allm[k, :n] = mo[:n]  # frames at or past the length stay zero
+        sel = torch.tensor(first, dtype=torch.long, device=allm.device)
+        out = {"motions": allm.index_select(0, sel), "m_lens": lens.clone(), "mm_idxs": mm_idxs}
+        rows = [first[i] + r for i in mm_idxs.tolist() for r in range(mm_num_repeats)]
+        P = len(mm_idxs)
+        out["mm_motions"] = allm[torch.tensor(rows, dtype=torch.long, device=allm.device)].reshape(
+            P, mm_num_repeats, max_motion_length, dim_pose) if P else allm[:0].reshape(0, mm_num_repeats, max_motion_length, dim_pose)
+        out["mm_lens"] = lens[torch.as_tensor(mm_idxs, dtype=torch.long)].reshape(P, 1).repeat(1, mm_num_repeats)
+        return out
+
+    @torch.no_grad()
     def generate_joints(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, joints_num=22, sigma=1.0,
                         bucketed=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
                         prompt_weights=None, **kw):
