@@ -481,32 +481,33 @@ int mdm_xattn_gate(const float* gate, const float* adaptive_gate, int32_t D, flo
 int mdm_fill_i64(int64_t* dst, int64_t n, const int32_t* src_dev, void* stream);
 int mdm_add_i32(int32_t* dst, int32_t delta, void* stream);
 
-/* Kernel-selection knob for same-box A/B runs and tests (0 = default; process-global, not thread-safe, never part of the data
- * path).  Values: 1 / 2 force the 128- / 64-row tile of the 16-bit GEMM, 6 / 7 force / forbid its 256 x 256 tile, 28 two-stage
- * ring in the 64-row tile; 21 expert MLP as two GEMMs instead of the fused kernel, 34 the LDS-staged fused kernel (csrc/mlp.hip)
- * instead of the streamed-weight one (csrc/mlp_stream.hip); 32 / 33 the Performer proj_out pair / the 4x FFN pair as two GEMMs; 30 stylization input and
- * its Linear as two launches, 29 that kernel on 64-row tiles, 35 the Performer tail as its own launches instead of inside the proj_out
- * pair's launch, 50 the Performer's q | k | v projection as its own GEMM launch instead of inside the attention core's, 51 the same for
- * the query of the linear cross-attention; 22 unfolded text cross-attention, 24 folded at any pass count;
- * 23 generic head_dim-256 paths; 25 fp32 instead of 16-bit intermediates; 26 / 27 router with compile-time / run-time expert
- * count wherever both exist; 31 input embedding in the mode's own precision; 36 fp32-grade Linears on the register-staged
- * kernel, 37-39 ring depths of the LDS-DMA fp32-grade kernel; fp32-grade fusions: 52 attention chain / 56 cross-attention chains as
- * separate launches, 58 the fused stylization on 64-row tiles, 60 stylization input and its Linear as two launches, 61 the
- * LayerNorms / block tails behind it as their own launches, 62 fp32 rows instead of pre-split rows between the bf16x3 GEMMs;
- * streamed-weight GEMM (MdmGemmDesc.w_stream): 63 never, 68 wherever eligible, 64-67 the same with a forced tile shape (112 x 512,
- * 64 x 512, 64 x 256, 32 x 256); its bf16x3 form (pre-split rows x a pair stream): 69 never, 70 wherever eligible.
- * 41-49 and 74-77 (timing-only knock-outs and the stamped build of the fused expert MLP, knock-outs of the fused stylization
- * launch: outputs are WRONG under them) exist only in the
- * diagnostic library (-DMDM_DIAG: `python motiondiffusion-moe_amd/build.py --diag` -> libmdm_hip_diag.so, used by tools/mlp_ko.py
- * and tools/mlp_stamps.py); libmdm_hip.so returns MDM_ERR_ARG for them and leaves the knob unchanged. */
+/* Kernel-selection knob (mdm_set_gemm_variant): the reference path that a test holds another path against.  0 = default;
+ * process-global, not thread-safe, never part of the data path.  The numbers are part of the ABI (tests and bench.py --variant
+ * pass them); every other value is refused with MDM_ERR_ARG and leaves the knob unchanged. */
+enum MdmVariant {
+  MDM_VAR_DEFAULT = 0,
+  MDM_VAR_GEMM_256 = 6,          /* the 256 x 256 tile of the 16-bit GEMM wherever it is eligible */
+  MDM_VAR_SD_UNFOLDED = 22,      /* text cross-attention unfolded (attention-core kernel) */
+  MDM_VAR_GENERIC_DH256 = 23,    /* the generic (GEMM-composed) head_dim-256 paths */
+  MDM_VAR_SD_FOLD_ANY = 24,      /* text cross-attention folded at any pass count */
+  MDM_VAR_ROUTER_CONST_E = 26,   /* router with compile-time expert count wherever it exists */
+  MDM_VAR_ROUTER_RUNTIME_E = 27, /* router with run-time expert count everywhere */
+  MDM_VAR_MLP_LDS = 34,          /* fused expert MLP on the LDS-staged kernel (csrc/mlp.hip), not the streamed-weight one */
+  MDM_VAR_TAIL_SPLIT = 35,       /* the Performer tail as its own launches, not inside the proj_out pair's launch */
+  MDM_VAR_X3_REG = 36,           /* fp32-grade Linears on the register-staged kernel */
+  MDM_VAR_QKV_SPLIT = 50,        /* the Performer's q | k | v projection as its own GEMM launch */
+  MDM_VAR_XQ_SPLIT = 51,         /* the query of the linear cross-attention as its own GEMM launch */
+  MDM_VAR_X3_ATTN_CHAIN = 52,    /* fp32-grade: the attention chain as separate launches */
+  MDM_VAR_X3_XATTN_CHAIN = 56,   /* fp32-grade: the cross-attention chains as separate launches */
+  MDM_VAR_X3_STYLE_SPLIT = 60,   /* fp32-grade: stylization input and its Linear as two launches */
+  MDM_VAR_X3_TAILS_SPLIT = 61,   /* fp32-grade: the LayerNorms / block tails behind the stylization as their own launches */
+  MDM_VAR_X3_F32_ROWS = 62,      /* fp32-grade: fp32 rows instead of pre-split rows between the bf16x3 GEMMs */
+  MDM_VAR_STREAM_NEVER = 63,     /* streamed-weight GEMM (MdmGemmDesc.w_stream): never */
+  MDM_VAR_STREAM_ALWAYS = 68,    /*   wherever it is eligible */
+  MDM_VAR_STREAM3_NEVER = 69,    /* its bf16x3 form (pre-split rows x a pair stream): never */
+  MDM_VAR_STREAM3_ALWAYS = 70    /*   wherever it is eligible */
+};
 int mdm_set_gemm_variant(int variant);
-/* 1 in the diagnostic library, 0 in the product library */
-int mdm_diag_build(void);
-/* diagnostic library only (MDM_ERR_UNSUPPORTED otherwise): the eight 64-bit device counters that the stamped build of the fused
- * expert MLP (knob 49) adds its per-phase cycle sums to; NULL detaches them (knob 49 is then refused with MDM_ERR_ARG). */
-int mdm_diag_mlp_counters(uint64_t* dev_counters8);
-/* diagnostic: s_memtime stamps of block 0 of the last bf16 GEMM launched with feat_S == -77 (host copy, synchronises) */
-int mdm_debug_stamps(uint64_t* out16);
 
 /* Measurement probe for bench.py: while enabled, every launch of the dominant kernel (the fused expert MLP inside
  * mdm_denoiser_forward / mdm_block_forward) is bracketed by a pair of HIP events recorded on the launch stream (do not

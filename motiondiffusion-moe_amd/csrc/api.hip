@@ -36,43 +36,39 @@ __global__ void pack_f16_kernel(const float* __restrict__ src, int64_t ld_src, i
 }  // namespace mdm
 
 namespace mdm {
-extern int g_bf16_variant;
-int debug_stamps(unsigned long long* out);
-#ifdef MDM_DIAG
-extern unsigned long long* g_diag_counters;
-#endif
+int g_variant = MDM_VAR_DEFAULT;
 }
 
 extern "C" {
 
-int mdm_debug_stamps(uint64_t* out16) { return mdm::debug_stamps((unsigned long long*)out16); }
-
 int mdm_set_gemm_variant(int v) {
-#ifndef MDM_DIAG
-  // 41..49: knock-outs / stamped builds of the fused expert MLP whose outputs are wrong by construction.  They exist only in
-  // the diagnostic library (-DMDM_DIAG, `build.py --diag`); the product library refuses the knob instead of computing garbage.
-  if ((v >= 41 && v <= 49) || (v >= 74 && v <= 77)) return MDM_ERR_ARG;  // (74..77: knock-outs of the fused stylization launch)
-#endif
-  mdm::g_bf16_variant = v;
-  return MDM_OK;
-}
-
-int mdm_diag_build(void) {
-#ifdef MDM_DIAG
-  return 1;
-#else
-  return 0;
-#endif
-}
-
-int mdm_diag_mlp_counters(uint64_t* dev_counters8) {
-#ifdef MDM_DIAG
-  mdm::g_diag_counters = (unsigned long long*)dev_counters8;
-  return MDM_OK;
-#else
-  (void)dev_counters8;
-  return MDM_ERR_UNSUPPORTED;
-#endif
+  switch (v) {
+    case MDM_VAR_DEFAULT:
+    case MDM_VAR_GEMM_256:
+    case MDM_VAR_SD_UNFOLDED:
+    case MDM_VAR_GENERIC_DH256:
+    case MDM_VAR_SD_FOLD_ANY:
+    case MDM_VAR_ROUTER_CONST_E:
+    case MDM_VAR_ROUTER_RUNTIME_E:
+    case MDM_VAR_MLP_LDS:
+    case MDM_VAR_TAIL_SPLIT:
+    case MDM_VAR_X3_REG:
+    case MDM_VAR_QKV_SPLIT:
+    case MDM_VAR_XQ_SPLIT:
+    case MDM_VAR_X3_ATTN_CHAIN:
+    case MDM_VAR_X3_XATTN_CHAIN:
+    case MDM_VAR_X3_STYLE_SPLIT:
+    case MDM_VAR_X3_TAILS_SPLIT:
+    case MDM_VAR_X3_F32_ROWS:
+    case MDM_VAR_STREAM_NEVER:
+    case MDM_VAR_STREAM_ALWAYS:
+    case MDM_VAR_STREAM3_NEVER:
+    case MDM_VAR_STREAM3_ALWAYS:
+      mdm::g_variant = v;
+      return MDM_OK;
+    default:
+      return MDM_ERR_ARG;
+  }
 }
 
 const char* mdm_version(void) { return "mdm_hip 0.1 (gfx950)"; }

@@ -7,7 +7,6 @@
 
 namespace mdm {
 
-extern int g_bf16_variant;
 
 namespace {
 
@@ -373,9 +372,9 @@ int gemm(const GemmArgs& a_in, hipStream_t stream) {
   }
   if (a.K <= 0 || !a.A.p || !a.W.p || (!a.C && !a.C16 && !a.Cx2)) return MDM_ERR_ARG;
   if (a.A.kind == OP_BF16_ROW) {
-    // a Linear that carries a weight stream: streamed-weight kernel (gemm_stream.hip); knob 63: the tile kernel as before
-    // (knob 68: wherever it is eligible, not only where it was measured faster)
-    if (a.w_stream && g_bf16_variant != 63 && (g_bf16_variant >= 64 && g_bf16_variant <= 68 ? gemm_stream1_eligible(a) : gemm_stream1_wanted(a)))
+    // a Linear that carries a weight stream: streamed-weight kernel (gemm_stream.hip) where it measured faster
+    if (a.w_stream && g_variant != MDM_VAR_STREAM_NEVER &&
+        (g_variant == MDM_VAR_STREAM_ALWAYS ? gemm_stream1_eligible(a) : gemm_stream1_wanted(a)))
       return gemm_stream1(a, stream);
     return gemm_bf16(a, stream);  // bf16 activations: throughput kernel (gemm2.hip)
   }
@@ -388,12 +387,12 @@ int gemm(const GemmArgs& a_in, hipStream_t stream) {
   if (a.A.kind == OP_BF16_ROW) return MDM_ERR_UNSUPPORTED;
   if (a.goff && (a.batch != 1 || a.ngroups <= 0)) return MDM_ERR_ARG;
   if (a.kgoff && (a.goff || a.A.kind != OP_F32_KSTRIDE || a.W.kind != OP_F32_KSTRIDE)) return MDM_ERR_ARG;
-  // pre-split rows x a (hi, lo) pair stream: streamed-weight bf16x3 kernel (gemm_stream3.hip) where it measured faster; knob 69: the
-  // tile kernel as before, 70: the streamed kernel wherever it is eligible
-  if (a.w_stream && a.A.kind == OP_X2_ROW && g_bf16_variant != 69 && (g_bf16_variant == 70 ? gemm_stream3x_eligible(a) : gemm_stream3x_wanted(a)))
+  // pre-split rows x a (hi, lo) pair stream: streamed-weight bf16x3 kernel (gemm_stream3.hip) where it measured faster
+  if (a.w_stream && a.A.kind == OP_X2_ROW && g_variant != MDM_VAR_STREAM3_NEVER &&
+      (g_variant == MDM_VAR_STREAM3_ALWAYS ? gemm_stream3x_eligible(a) : gemm_stream3x_wanted(a)))
     return gemm_stream3x(a, stream);
-  // plain Linears of the fp32-grade mode: LDS-DMA staged bf16x3 kernel (gemm3.hip); knob 36 keeps the register-staged one
-  if ((g_bf16_variant != 36 || a.act == ACT_HEADNORM || a.act == ACT_HEADSOFTMAX || a.C16_lo || a.Cx2 || a.A.kind == OP_X2_ROW) &&
+  // plain Linears of the fp32-grade mode: LDS-DMA staged bf16x3 kernel (gemm3.hip); MDM_VAR_X3_REG keeps the register-staged one
+  if ((g_variant != MDM_VAR_X3_REG || a.act == ACT_HEADNORM || a.act == ACT_HEADSOFTMAX || a.C16_lo || a.Cx2 || a.A.kind == OP_X2_ROW) &&
       gemm_x3_dma_eligible(a))
     return gemm_x3_dma(a, stream);
   if (a.C16_lo || a.Cx2 || a.A.kind == OP_X2_ROW) return MDM_ERR_UNSUPPORTED;  // pre-split rows / plane outputs exist on that kernel only

@@ -19,16 +19,6 @@ __device__ __forceinline__ void glds16(const void* g, uint8_t* l) {
                                    (__attribute__((address_space(3))) void*)l, 16, 0, 0);
 }
 
-__device__ unsigned long long g_stamps[16];
-#define MDM_STAMP(i)                                                             \
-  do {                                                                       \
-    if (dbg) {                                                               \
-      unsigned long long t__;                                                \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory"); \
-      if (threadIdx.x == 0) g_stamps[i] = t__;                               \
-    }                                                                        \
-  } while (0)
-
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -63,8 +53,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const GemmArgs g) {
   constexpr int CPR = ROWB / 16;           // 16-B chunks per row
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
-  const bool dbg = (g.feat_S == -77) && blockIdx.x == 0;
-  MDM_STAMP(0);
 
   const int ntn = (g.N + BN - 1) / BN;
   const int tile = xcd_remap(blockIdx.x, gridDim.x);
@@ -128,11 +116,9 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const GemmArgs g) {
   // the first K tiles go out BEFORE anything else touches the memory pipeline: the epilogue constants below are not
   // needed for ~20 K cycles, the tiles are needed at once
   const int nk = g.K / BK;
-  MDM_STAMP(1);
 #pragma unroll
   for (int s = 0; s < NSTAGE - 1; ++s)
     if (s < nk) stage(s, s);
-  MDM_STAMP(2);
 
   // column / row constants of this lane's outputs, fetched before the K loop (they ride in 40 registers)
   float* __restrict__ C = g.C ? g.C + offC : nullptr;
@@ -198,7 +184,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const GemmArgs g) {
       wait_vm<0>();
     }
     __builtin_amdgcn_s_barrier();
-    if (kt == 0) MDM_STAMP(3);
     if (kt + NSTAGE - 1 < nk) stage(kt + NSTAGE - 1, (kt + NSTAGE - 1) % NSTAGE);
     const uint8_t* sa = smem + (kt % NSTAGE) * STAGE_B;
     const uint8_t* sw = sa + TILE_A;
@@ -223,7 +208,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const GemmArgs g) {
     }
   }
 
-  MDM_STAMP(4);
   // Epilogue in two passes through the (now idle) LDS ring:
   //  1. registers -> LDS: bias, activation, scales applied; D tile (j,i) lane holds n = nb + 4*(lane>>4) + r for
   //     m = mb + (lane & 15) -> one 16-B write, 16-B chunks of a row XOR-swizzled by the row index;
@@ -249,7 +233,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const GemmArgs g) {
     }
   }
   __syncthreads();  // every wave is done with the last K tile
-  MDM_STAMP(6);
   float* stg = (float*)smem;  // [BM][128] fp32
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
@@ -279,7 +262,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const GemmArgs g) {
     }
   }
   __syncthreads();
-  MDM_STAMP(7);
   if (fast) {
     // all staged rows out of LDS first (their reads need no row test): behind the per-row `continue` every read was its own block,
     // `R w S | S |` sixteen times -- one exposed LDS latency per row
@@ -316,21 +298,11 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(const GemmArgs g) {
       }
     }
   }
-  MDM_STAMP(8);
-  if (dbg) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    MDM_STAMP(5);
-  }
 }
 
 }  // namespace
 
-int debug_stamps(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 16) == hipSuccess ? MDM_OK : MDM_ERR_LAUNCH;
-}
-
-int g_big_min_tiles = 352;
-int g_bf16_variant = 0;  // tuning knob (mdm_set_gemm_variant): 0 = default
+constexpr int BIG_MIN_TILES = 352;  // 256 x 256 tiles at K >= 2048 from this many tiles on
 
 bool gemm_bf16_eligible(const GemmArgs& a) {
   return a.precision == 1 && a.A.kind == OP_BF16_ROW && a.W.kind == OP_BF16_ROW && a.K > 0 && (a.K % 64) == 0 &&
@@ -377,21 +349,18 @@ int gemm_bf16(const GemmArgs& a, hipStream_t stream) {
   if (!a.C && !a.C16) return MDM_ERR_ARG;
   // long-K, many-tile launches: 256x256 tiles halve the L2->LDS bytes per FLOP (1090 vs 865 TFLOP/s at 8192^3), but
   // with one workgroup per CU their prologue / 4-slab epilogue is not hidden: measured slower than the 128^2 tiles at
-  // K = 512 / 1024 (e.g. 50176x1024x512: 142 vs 128 us), so they are used for K >= 2048 only (variant 6 forces, 7 forbids)
-  if (g_bf16_variant != 7 && g_bf16_variant != 1 && g_bf16_variant != 2 && gemm_bf16_256_eligible(a)) {
+  // K = 512 / 1024 (e.g. 50176x1024x512: 142 vs 128 us), so they are used for K >= 2048 only (MDM_VAR_GEMM_256 forces them)
+  if (gemm_bf16_256_eligible(a)) {
     const int64_t t256 = (int64_t)((a.M + 255) / 256 + (a.goff ? a.ngroups : 0)) * (a.N / 256);
-    if (g_bf16_variant == 6 || (a.K >= 2048 && t256 >= g_big_min_tiles)) return gemm_bf16_256(a, stream);
+    if (g_variant == MDM_VAR_GEMM_256 || (a.K >= 2048 && t256 >= BIG_MIN_TILES)) return gemm_bf16_256(a, stream);
   }
   // few 128x128 tiles => the launch is a latency chain on <= 2 blocks per CU: halve the tile height so that every
-  // CU holds 3+ independent blocks (variant 1 / 2 force the 128- / 64-row tile for benchmarking).  The 64-row tile runs a
-  // 3-stage ring (72 KiB: still two blocks per CU; K tiles arrive two steps ahead): 5.90 -> 5.79 ms per step; for the
-  // 128-row tile a third stage costs the second resident block, and 32-wide K tiles in 3- / 4-deep rings change nothing
+  // CU holds 3+ independent blocks.  The 64-row tile runs a 3-stage ring (72 KiB: still two blocks per CU; K tiles arrive two
+  // steps ahead): 5.90 -> 5.79 ms per step against a 2-stage ring; for the 128-row tile a third stage costs the second resident
+  // block, and 32-wide K tiles in 3- / 4-deep rings change nothing
   const int64_t tiles128 = (int64_t)((a.M + 127) / 128) * ((a.N + BN - 1) / BN) * a.batch;
-  bool small = !a.goff && (tiles128 <= 256 || a.M <= 64);
-  if (g_bf16_variant == 1) small = false;
-  if (g_bf16_variant == 2) small = true;
-  if (small && g_bf16_variant != 28) return launch_bf16<64, 64, 3>(a, stream);  // 3-stage ring: still 2 blocks/CU, tiles arrive 2 ahead (knob 28: 2-stage)
-  return small ? launch_bf16<64, 64, 2>(a, stream) : launch_bf16<128, 64, 2>(a, stream);
+  const bool small = !a.goff && (tiles128 <= 256 || a.M <= 64);
+  return small ? launch_bf16<64, 64, 3>(a, stream) : launch_bf16<128, 64, 2>(a, stream);
 }
 
 }  // namespace mdm

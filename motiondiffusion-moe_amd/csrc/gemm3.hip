@@ -369,7 +369,6 @@ int launch3(const GemmArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-extern int g_bf16_variant;
 
 bool gemm_x3_dma_eligible(const GemmArgs& a) {
   const bool base = a.precision == 3 && (a.A.kind == OP_F32_ROW || a.A.kind == OP_X2_ROW) && a.W.kind == OP_BF16_ROW && a.W.p_lo && a.batch == 1 && a.A.rpg == 0 &&
@@ -394,9 +393,6 @@ int gemm_x3_dma(const GemmArgs& a, hipStream_t stream) {
   if (!a.C && !a.C16 && !a.Cx2) return MDM_ERR_ARG;
   const int64_t tiles128 = (int64_t)((a.M + 127) / 128) * ((a.N + 127) / 128);
   const bool small = !a.goff && (tiles128 <= 256 || a.M <= 64);
-  if (g_bf16_variant == 37) return launch3<128, 128, 3>(a, stream);  // A/B knobs: ring depth at the 128-row tile
-  if (g_bf16_variant == 38) return launch3<128, 128, 4>(a, stream);
-  if (g_bf16_variant == 39) return launch3<64, 128, 3>(a, stream);
   return small ? launch3<64, 128, 3>(a, stream) : launch3<128, 128, 2>(a, stream);
 }
 

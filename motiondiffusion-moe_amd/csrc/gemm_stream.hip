@@ -322,7 +322,6 @@ int launch_gs_k(const GsArgs& g, int act, int rt, int nj, hipStream_t s) {
 
 }  // namespace
 
-extern int g_bf16_variant;
 
 int64_t gemm_stream1_elems(int N, int K) {
   return (N > 0 && K > 0 && N % 256 == 0 && K % 256 == 0) ? (int64_t)(N / 16) * (K / 32 + GS_SKEW) * 512 + GS_PAD : 0;
@@ -386,12 +385,6 @@ int gemm_stream1(const GemmArgs& a, hipStream_t stream) {
   g.R1 = a.R1, g.ldr1 = a.ldr1, g.R2 = a.R2, g.ldr2 = a.ldr2, g.C = a.C, g.C16 = a.C16, g.ldc = a.ldc;
   int rt, nj;
   gemm_stream1_shape(a.M, a.N, rt, nj);
-  // A/B knobs 64..67 force a tile shape
-  if (g_bf16_variant == 64) rt = 7, nj = 4;
-  if (g_bf16_variant == 65) rt = 4, nj = 4;
-  if (g_bf16_variant == 66) rt = 4, nj = 2;
-  if (g_bf16_variant == 67) rt = 2, nj = 2;
-  if (a.N % (128 * nj)) nj = 2;
   return a.h16 == MDM_H16_F16 ? launch_gs_k<HF>(g, a.act, rt, nj, stream) : launch_gs_k<HB>(g, a.act, rt, nj, stream);
 }
 

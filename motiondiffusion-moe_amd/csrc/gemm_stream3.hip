@@ -325,7 +325,6 @@ int launch_g3(const G3Args& g, int act, int tiles, hipStream_t s) {
 
 }  // namespace
 
-extern int g_bf16_variant;
 
 int64_t gemm_stream3x_group_elems(int N, int K) {
   return (N > 0 && K > 0 && N % 512 == 0 && K % 128 == 0) ? (int64_t)(N / 16) * (K / 32 + G3_SKEW) * 1024 : 0;

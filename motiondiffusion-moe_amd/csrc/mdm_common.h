@@ -8,6 +8,9 @@ namespace mdm {
 
 // status codes: include/mdm_hip.h (MDM_OK, MDM_ERR_*)
 
+// kernel-selection knob: one of MdmVariant (include/mdm_hip.h), set by mdm_set_gemm_variant (api.hip)
+extern int g_variant;
+
 #define MDM_RETURN_IF_LAUNCH_FAILED()                 \
   do {                                                \
     hipError_t e__ = hipGetLastError();               \

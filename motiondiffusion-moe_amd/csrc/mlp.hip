@@ -265,12 +265,11 @@ bool fused_mlp_supported(const MdmMlpDesc& a) {
   return true;
 }
 
-extern int g_bf16_variant;
 
 int fused_mlp(const MdmMlpDesc& a, hipStream_t stream) {
-  // streamed-weight kernel (csrc/mlp_stream.hip) whenever the caller packed a weight stream and the shape fits; knob 34
-  // keeps this kernel for A/B runs
-  if (g_bf16_variant != 34 && fused_mlp_stream_supported(a)) return fused_mlp_stream(a, stream);
+  // streamed-weight kernel (csrc/mlp_stream.hip) whenever the caller packed a weight stream and the shape fits; MDM_VAR_MLP_LDS
+  // keeps this kernel
+  if (g_variant != MDM_VAR_MLP_LDS && fused_mlp_stream_supported(a)) return fused_mlp_stream(a, stream);
   if (!a.X || !a.w1 || !a.w2 || (!a.C && !a.C16)) return MDM_ERR_ARG;
   MdmMlpDesc plain = a;
   plain.wstream = nullptr;

@@ -18,7 +18,7 @@
 //   * the order of a chunk is  phase 1 (c) -> phase 2, second half of chunk c - 1 -> GELU half 0 -> publish -> phase 2, first
 //     half of chunk c -> GELU half 1 -> publish.  The GELU is x * sigmoid(q(x)) on SCALAR fp32 instructions (beside MFMAs a
 //     packed-fp32 instruction costs several plain ones; this file is compiled with -fno-slp-vectorize).  Interleaving its
-//     pieces with the phase-2 MFMAs of the same wave (knob 48) measured 1.5 % slower than back to back, storing the 16-bit
+//     pieces with the phase-2 MFMAs of the same wave measured 1.5 % slower than back to back, storing the 16-bit
 //     outputs straight from the accumulators 3 % slower than staging full rows through LDS, requesting the next tile's X rows
 //     between the two halves of the epilogue 4 % slower (the wait moves, it does not shrink): all three tried and dropped.
 //   * every { MFMAs of one A fragment, 1 fragment read } is pinned by a scheduling barrier, the A fragments go
@@ -86,7 +86,7 @@ __device__ __forceinline__ bool find_tile(const MdmMlpDesc& g, const int* gtab, 
 
 // Epilogue shared by both forms: EPT row tiles at a time staged as fp32 [16 EPT][DOUT] in LDS (all of it is free by then),
 // written as full rows with the row scale, the residuals and the optional 16-bit copy.
-template <typename HT, int RT, int NJ, int SMEM, int KO>
+template <typename HT, int RT, int NJ, int SMEM>
 __device__ __forceinline__ void store_tile(const MdmMlpDesc& g, f32x4 (&y)[RT][NJ], uint8_t* smem, int row0, int row_end, int tid,
                                            int wn, int frow, int fq) {
   constexpr int DOUT = NJ * 128;
@@ -115,7 +115,6 @@ __device__ __forceinline__ void store_tile(const MdmMlpDesc& g, f32x4 (&y)[RT][N
       const int ml = tid / TPR + RPS * k, m = row0 + ml;
       if (ml >= RT * 16 || m >= row_end) continue;
       const uint4 v = *(const uint4*)(smem + ml * ROWB + ((cl ^ (ml & (CH - 1))) << 4));
-      if (KO == 6 && v.x != 0x12345678u) continue;
       *(uint4*)(g.C16 + (int64_t)m * g.ldc + cl * 8) = v;
     }
     return;
@@ -189,32 +188,11 @@ __device__ __forceinline__ void store_tile(const MdmMlpDesc& g, f32x4 (&y)[RT][N
         else q = *(const f32x4*)(R2 + (int64_t)m * g.ldr2 + n);
         v[0] += q[0], v[1] += q[1], v[2] += q[2], v[3] += q[3];
       }
-      if (KO == 6 && v[0] != 123.456f) continue;
       if (g.C) *(f32x4*)(g.C + (int64_t)m * g.ldc + n) = v;
       if (g.C16) *(uint2*)(g.C16 + (int64_t)m * g.ldc + n) = make_uint2(HT::pack(v[0], v[1]), HT::pack(v[2], v[3]));
     }
   }
 }
-
-// Diagnostic build KO == 9 (-DMDM_DIAG library only, knob 49, tools/mlp_stamps.py): wave 0 of every workgroup sums s_memtime
-// differences per phase and adds them to the eight 64-bit counters handed over through mdm_diag_mlp_counters() (a buffer of
-// their own: no output or residual pointer is reused for them; the launch is refused while none is set).
-// Read the SHARES of this build, not its run time.
-__device__ __forceinline__ unsigned long long stamp_now() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define XSTAMP(k)                                  \
-  do {                                             \
-    if constexpr (KO == 9) {                       \
-      const unsigned long long n__ = stamp_now();  \
-      acc[k] += n__ - last;                        \
-      last = n__;                                  \
-    }                                              \
-  } while (0)
 
 template <int RT, int DIN, int NJ = 4, bool TAIL = false>
 struct XGeo {
@@ -405,17 +383,12 @@ __device__ __forceinline__ void pair_tail(const PairTail& st, f32x4 (&y)[RT][4],
   }
 }
 
-// KO: 0 = the real kernel, 10 = the real kernel + the Performer tail.  Every other value exists only in the diagnostic library
-// (built with -DMDM_DIAG by `python motiondiffusion-moe_amd/build.py --diag`; the shipped libmdm_hip.so neither instantiates them
-// nor accepts their knobs): timing-only knock-outs for tools/mlp_ko.py whose results are wrong -- 1 no GELU arithmetic, 2 no
-// weight refills, 4 no phase-1 MFMAs, 5 no phase-2 MFMAs, 6 no output stores -- and A/B arms: 7 = the erf-form GELU of the
-// LDS-staged kernel, 8 = GELU pieces interleaved with the phase-2 MFMAs of the same wave, 9 = stamped build
-template <typename HT, int RT, int NJ, int DIN, int KO>
+// TAIL: 0 = the fused pair alone, 1 = the pair + the Performer tail (post-norm, stylization, out_layers.2, residual) behind it
+template <typename HT, int RT, int NJ, int DIN, int TAIL>
 __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDesc g, const int tile_h, const PairTail st) {
   typedef typename HT::frag_t frag_t;
-  constexpr bool TAIL = KO == 10;  // the Performer tail (post-norm, stylization, out_layers.2, residual) behind the pair
   static_assert(!TAIL || (NJ == 4 && DIN == 512 && RT <= 4), "the tail is written for D = 512 rows");
-  typedef XGeo<RT, DIN, NJ, TAIL> G;
+  typedef XGeo<RT, DIN, NJ, TAIL != 0> G;
   constexpr int NKO = DIN / 128, NLINE = DIN / 64;
   constexpr int NA = 4, PD = NA - 1;  // A-fragment ring: NA registers, PD fragments ahead of the MFMAs
   // weight ring: fragments in flight per wave, 16 where the accumulators leave room.  The 32-row form runs one workgroup per CU
@@ -423,9 +396,7 @@ __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDes
   // ring as well: what bounds these short-tile launches is how many weight bytes a CU has in flight
   constexpr int NR = (RT <= 4 && NJ == 4 && DIN % 256 == 0) ? 16 : 8;
   constexpr int NF = 4 * RT;          // A fragments per unrolled body (4 K steps x RT row tiles)
-  constexpr bool ILV = KO == 8;  // knob 48: GELU pieces interleaved with phase-2 MFMAs (measured 1.5 % SLOWER than back to back)
   static_assert(NF % NA == 0, "the ring must close over the unrolled body");
-  static_assert(NF >= 4 * RT, "one GELU pair piece per fragment: 2 RT pairs x 2 pieces");
   extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
   uint8_t* const ximg = smem;
   uint8_t* const hid = smem + G::XIMG_B;
@@ -436,8 +407,6 @@ __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDes
     lds_barrier();
   }
 
-  unsigned long long acc[8] = {}, last = 0;
-  if constexpr (KO == 9) last = stamp_now();
   // Persistent over tiles: workgroup b takes tiles remap(b), remap(b) + grid, ...; round k hands an XCD a contiguous range of
   // tiles (~1 group: its weights stay in that XCD's L2).
   for (int mt = xcd_remap(blockIdx.x, gridDim.x);; mt += gridDim.x) {
@@ -449,7 +418,6 @@ __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDes
     const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
     int row0, row_end, grp;
     if (!find_tile(g, gtab, tile_h, lane, mt, row0, row_end, grp)) break;
-    XSTAMP(0);
 
     const int nchunk = g.F / FC;
     constexpr int fpc = (DIN / 32) * 2 + 8 * NJ;
@@ -501,17 +469,13 @@ __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDes
       }
     }
     lds_barrier();
-    XSTAMP(1);
 
     f32x4 h[RT][2];
     uint2 pk[RT];  // the GELU'd half that is about to be published, packed
-    // One half of phase 2 (K = the 128 hidden units of the image) with the GELU of the h[.][GJ] accumulators into pk[]
-    // interleaved (GJ < 0: none).  hb: byte offset of (row fr, K step 0) in the half image.
-    auto phase2 = [&](auto hf_c, auto gj_c, int hb) __attribute__((always_inline)) {
-      constexpr int HF = decltype(hf_c)::value, GJ = decltype(gj_c)::value;
+    // One half of phase 2 (K = the 128 hidden units of the image).  hb: byte offset of (row fr, K step 0) in the half image.
+    auto phase2 = [&](auto hf_c, int hb) __attribute__((always_inline)) {
+      constexpr int HF = decltype(hf_c)::value;
       frag_t A[NA];
-      f32x2 ge = {0.f, 0.f};
-      uint32_t plo = 0;
 #pragma unroll
       for (int k = 0; k < PD; ++k) A[k % NA] = *(const frag_t*)(hid + (hb ^ (64 * (k / RT))) + (k % RT) * 4096);
 #pragma unroll
@@ -520,51 +484,32 @@ __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDes
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           const int slot = ((4 * HF + sq) * NJ + j) & (NR - 1);
-          if constexpr (KO == 5) {
-            asm volatile("" ::"v"(A[k % NA]), "v"(R[slot]));
-          } else {
-            y[i][j] = HT::mfma16(R[slot], A[k % NA], y[i][j]);
-          }
+          y[i][j] = HT::mfma16(R[slot], A[k % NA], y[i][j]);
         }
         if (k + PD < NF) A[(k + PD) % NA] = *(const frag_t*)(hid + (hb ^ (64 * ((k + PD) / RT))) + ((k + PD) % RT) * 4096);
-        if constexpr (GJ >= 0 && ILV) {
-          // fragment k carries piece k & 1 of value pair k >> 1: pair p = elements 2 (p & 1), 2 (p & 1) + 1 of h[p >> 1][GJ]
-          const int p = k >> 1, ig = p >> 1, e0 = 2 * (p & 1);
-          const f32x2 v = {h[ig][GJ][e0], h[ig][GJ][e0 + 1]};
-          if ((k & 1) == 0) {
-            ge = KO == 1 ? v : gelu_part_a(v);
-          } else {
-            const f32x2 gv = KO == 1 ? v : gelu_part_b(v, ge);
-            const uint32_t w = HT::pack(gv[0], gv[1]);
-            if ((p & 1) == 0) plo = w;
-            else pk[ig] = make_uint2(plo, w);
-          }
-        }
         if (i == RT - 1) {
 #pragma unroll
           for (int j = 0; j < NJ; ++j) {
             const int slot = ((4 * HF + sq) * NJ + j) & (NR - 1);
-            if constexpr (KO != 2) R[slot] = ldg<frag_t>(wp + slot * 1024);
+            R[slot] = ldg<frag_t>(wp + slot * 1024);
             if (slot == NR - 1) wp += NR * 1024;
           }
         }
         pin();
       }
     };
-    // GELU of h[.][GJ] -> pk[] on its own (first chunk: there is no phase 2 to hide it under; knobs 7 / 8: always)
+    // GELU of h[.][GJ] -> pk[]
     auto gelu_alone = [&](auto gj_c) __attribute__((always_inline)) {
       constexpr int GJ = decltype(gj_c)::value;
 #pragma unroll
       for (int i = 0; i < RT; ++i) {
         f32x2 g01 = {h[i][GJ][0], h[i][GJ][1]}, g23 = {h[i][GJ][2], h[i][GJ][3]};
-        if constexpr (KO == 7) g01 = gelu_erf2(g01), g23 = gelu_erf2(g23);
-        else if constexpr (KO != 1) g01 = gelu_part_b(g01, gelu_part_a(g01)), g23 = gelu_part_b(g23, gelu_part_a(g23));
+        g01 = gelu_part_b(g01, gelu_part_a(g01)), g23 = gelu_part_b(g23, gelu_part_a(g23));
         pk[i] = make_uint2(HT::pack(g01[0], g01[1]), HT::pack(g23[0], g23[1]));
       }
     };
     typedef std::integral_constant<int, 0> I0;
     typedef std::integral_constant<int, 1> I1;
-    typedef std::integral_constant<int, -1> IN;
 
     // phase 1 of one chunk (no barrier): h[rows x 32 units of this wave] = X . W1 chunk^T + b1
     auto phase1 = [&](int chunk, int ln) __attribute__((always_inline)) {
@@ -593,19 +538,13 @@ __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDes
 #pragma unroll
           for (int k = 0; k < NF; ++k) {
             const int u = k / RT, i = k % RT, s0 = 8 * kb + 2 * u;
-            if constexpr (KO == 4) {
-              asm volatile("" ::"v"(A[k % NA]), "v"(R[s0]), "v"(R[s0 + 1]));
-            } else {
-              h[i][0] = HT::mfma16(R[s0], A[k % NA], h[i][0]);
-              h[i][1] = HT::mfma16(R[s0 + 1], A[k % NA], h[i][1]);
-            }
+            h[i][0] = HT::mfma16(R[s0], A[k % NA], h[i][0]);
+            h[i][1] = HT::mfma16(R[s0 + 1], A[k % NA], h[i][1]);
             const int kp = k + PD, up = (kp % NF) / RT, ip = kp % RT;
             A[kp % NA] = *(const frag_t*)(ximg + (xb ^ (64 * up)) + (kp < NF ? kc : kn) * 256 + ip * 16 * G::XROW_B);
             if (i == RT - 1) {
-              if constexpr (KO != 2) {
-                R[s0] = ldg<frag_t>(wp + s0 * 1024);
-                R[s0 + 1] = ldg<frag_t>(wp + (s0 + 1) * 1024);
-              }
+              R[s0] = ldg<frag_t>(wp + s0 * 1024);
+              R[s0 + 1] = ldg<frag_t>(wp + (s0 + 1) * 1024);
             }
             pin();
           }
@@ -636,69 +575,36 @@ __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDes
     {
       const int ln = olane();
       phase1(0, ln);
-      XSTAMP(2);
       gelu_alone(I0());
-      XSTAMP(3);
       publish(ln);
-      XSTAMP(4);
-      if constexpr (ILV) {
-        phase2(I0(), I1(), hbase(ln));
-      } else {
-        phase2(I0(), IN(), hbase(ln));
-        gelu_alone(I1());
-      }
-      XSTAMP(5);
+      phase2(I0(), hbase(ln));
+      gelu_alone(I1());
       publish(ln);
-      XSTAMP(4);
     }
 #pragma unroll 1
     for (int chunk = 1; chunk < nchunk; ++chunk) {
       const int ln = olane();
       phase1(chunk, ln);
-      XSTAMP(2);
-      // the second half of the PREVIOUS chunk's phase 2 (published before this chunk's phase 1) with the GELU of this chunk's
-      // half 0 under it
-      if constexpr (ILV) {
-        phase2(I1(), I0(), hbase(ln));
-      } else {
-        phase2(I1(), IN(), hbase(ln));
-        gelu_alone(I0());
-      }
-      XSTAMP(5);
+      // the second half of the PREVIOUS chunk's phase 2 (published before this chunk's phase 1), then the GELU of this chunk's
+      // half 0
+      phase2(I1(), hbase(ln));
+      gelu_alone(I0());
       publish(ln);
-      XSTAMP(4);
-      if constexpr (ILV) {
-        phase2(I0(), I1(), hbase(ln));
-      } else {
-        phase2(I0(), IN(), hbase(ln));
-        gelu_alone(I1());
-      }
-      XSTAMP(5);
+      phase2(I0(), hbase(ln));
+      gelu_alone(I1());
       publish(ln);
-      XSTAMP(4);
     }
-    phase2(I1(), IN(), hbase(olane()));  // the last chunk's second half
-    XSTAMP(5);
+    phase2(I1(), hbase(olane()));  // the last chunk's second half
 
     // the epilogue derives its addresses from an opaque thread id of its own (see above)
     int te = threadIdx.x;
     asm volatile("" : "+v"(te));
     if constexpr (TAIL) {
       pair_tail<HT, RT, NR>(st, y, R, smem, row0, row_end, te, wn);
-    } else if constexpr (KO == 9) {
-      store_tile<HT, RT, NJ, G::SMEM, KO>(g, y, smem, row0, row_end, te, wn, te & 15, (te & 63) >> 4);
-      XSTAMP(6);
-      if (te == 0) atomicAdd((unsigned long long*)st.out + 7, 1ull);  // st.out: the diagnostic counters (launcher below)
     } else {
-      store_tile<HT, RT, NJ, G::SMEM, KO>(g, y, smem, row0, row_end, te, wn, te & 15, (te & 63) >> 4);
+      store_tile<HT, RT, NJ, G::SMEM>(g, y, smem, row0, row_end, te, wn, te & 15, (te & 63) >> 4);
     }
     lds_barrier();  // the staging reads of this tile are done before the next tile's X rows land in the same LDS
-  }
-  if constexpr (KO == 9) {
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int q = 0; q < 7; ++q) atomicAdd((unsigned long long*)st.out + q, acc[q]);
-    }
   }
 }
 
@@ -804,18 +710,13 @@ int mlp_stream_tile_h(int64_t M, int rt_max) {
   return (int)h;
 }
 
-extern int g_bf16_variant;
-#ifdef MDM_DIAG
-unsigned long long* g_diag_counters = nullptr;  // mdm_diag_mlp_counters(): eight 64-bit device counters of the stamped build
-#endif
-
-template <int RT, int DIN, int KO, int NJ = 4>
+template <int RT, int DIN, int TAIL, int NJ = 4>
 static int launch_stream(const MdmMlpDesc& a, int th, hipStream_t stream, const PairTail& tail = PairTail()) {
-  constexpr int smem = XGeo<RT, DIN, NJ, KO == 10>::SMEM + 512;  // + the group-offset table
+  constexpr int smem = XGeo<RT, DIN, NJ, TAIL != 0>::SMEM + 512;  // + the group-offset table
   static DevOnce attr;
   if (smem > 65536 && !attr) {
-    if (hipFuncSetAttribute((const void*)fused_mlp_stream_kernel<HB, RT, NJ, DIN, KO>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess ||
-        hipFuncSetAttribute((const void*)fused_mlp_stream_kernel<HF, RT, NJ, DIN, KO>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)fused_mlp_stream_kernel<HB, RT, NJ, DIN, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess ||
+        hipFuncSetAttribute((const void*)fused_mlp_stream_kernel<HF, RT, NJ, DIN, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
       return MDM_ERR_LAUNCH;
     attr = true;
   }
@@ -824,9 +725,9 @@ static int launch_stream(const MdmMlpDesc& a, int th, hipStream_t stream, const 
   const int res = device_cus();
   const int grid = tiles < res ? tiles : res;
   if (a.h16 == MDM_H16_F16) {
-    hipLaunchKernelGGL((fused_mlp_stream_kernel<HF, RT, NJ, DIN, KO>), dim3(grid), dim3(NT), smem, stream, a, th, tail);
+    hipLaunchKernelGGL((fused_mlp_stream_kernel<HF, RT, NJ, DIN, TAIL>), dim3(grid), dim3(NT), smem, stream, a, th, tail);
   } else {
-    hipLaunchKernelGGL((fused_mlp_stream_kernel<HB, RT, NJ, DIN, KO>), dim3(grid), dim3(NT), smem, stream, a, th, tail);
+    hipLaunchKernelGGL((fused_mlp_stream_kernel<HB, RT, NJ, DIN, TAIL>), dim3(grid), dim3(NT), smem, stream, a, th, tail);
   }
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
@@ -851,27 +752,6 @@ int fused_mlp_stream(const MdmMlpDesc& a, hipStream_t stream) {
   }
   if (a.Din == 128) return launch_by_height<128>(a, stream);
   if (a.Din == 256) return launch_by_height<256>(a, stream);
-#ifdef MDM_DIAG
-  const int th = mlp_stream_tile_h(a.M, 7);
-  if (th > 64) {
-    switch (g_bf16_variant) {  // knobs 41..49: knock-out / diagnostic builds for tools/mlp_ko.py, tools/mlp_stamps.py (timing only)
-      case 41: return launch_stream<7, 512, 1>(a, th, stream);
-      case 42: return launch_stream<7, 512, 2>(a, th, stream);
-      case 44: return launch_stream<7, 512, 4>(a, th, stream);
-      case 45: return launch_stream<7, 512, 5>(a, th, stream);
-      case 46: return launch_stream<7, 512, 6>(a, th, stream);
-      case 47: return launch_stream<7, 512, 7>(a, th, stream);
-      case 48: return launch_stream<7, 512, 8>(a, th, stream);
-      case 49: {
-        if (!g_diag_counters) return MDM_ERR_ARG;  // mdm_diag_mlp_counters() first: the stamps need a buffer of their own
-        PairTail t = PairTail();
-        t.out = (float*)g_diag_counters;
-        return launch_stream<7, 512, 9>(a, th, stream, t);
-      }
-      default: break;
-    }
-  }
-#endif
   return launch_by_height<512>(a, stream);
 }
 
@@ -887,8 +767,8 @@ int fused_pair_style(const MdmMlpDesc& a, const PairTail& t, hipStream_t stream)
       ((uintptr_t)t.ws & 15) || (t.skip && (!t.lw || !t.lb)) || (t.l2w && (!t.l2b || !t.ln16 || !t.skip)))
     return MDM_ERR_ARG;
   const int th = mlp_stream_tile_h(a.M, 4);  // the tail stages fp32 rows: 64-row tiles at most
-  if (th <= 32) return launch_stream<2, 512, 10>(a, th, stream, t);
-  return launch_stream<4, 512, 10>(a, th, stream, t);
+  if (th <= 32) return launch_stream<2, 512, 1>(a, th, stream, t);
+  return launch_stream<4, 512, 1>(a, th, stream, t);
 }
 
 }  // namespace mdm

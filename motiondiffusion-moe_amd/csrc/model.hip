@@ -5,7 +5,6 @@
 #include "kernels.h"
 
 namespace mdm {
-extern int g_bf16_variant;
 namespace {
 
 #define MDM_TRY(expr)            \
@@ -97,7 +96,8 @@ struct Ctx {
   bool mix;         // precision 4: fp32-grade flow, but expert MLPs + the 4x FFN run as ONE fp16 pass on 16-bit operands
   bool fp8;         // precision 5: as 2, expert GEMMs on e4m3 operands (csrc/gemm8.hip)
   bool x2;          // fp32-grade GEMM chains: a tensor whose only consumer is a bf16x3 GEMM is written PRE-SPLIT by its producer
-                    // (MDM_OP_X2_ROW rows: same bytes as fp32) -- the GEMM then does not re-split every fragment in its K loop (knob 62: off)
+                    // (MDM_OP_X2_ROW rows: same bytes as fp32) -- the GEMM then does not re-split every fragment in its K loop
+                    // (MDM_VAR_X3_F32_ROWS: off)
   int B, S, N;      // batch, frames at this scale, text tokens
   const int32_t* ntok = nullptr;  // per-sample text token counts [B] (MdmTextCache.ntok), or null: all N
   int64_t M;        // B*S
@@ -114,8 +114,8 @@ bool use_bf16_acts(const MdmModel* m, int precision) {
 // precision (include/mdm_hip.h: MDM_PREC_*) -> how this run computes; false = unsupported combination
 bool set_precision(Ctx& c, const MdmModel* m, int precision) {
   c.mix = false, c.bf = false, c.fp8 = false, c.h16 = MDM_H16_BF16;
-  // (knob 36 puts the fp32-grade Linears on the register-staged kernel, which reads fp32 rows only)
-  c.x2 = (precision == MDM_PREC_X3 || precision == MDM_PREC_MIXED) && g_bf16_variant != 62 && g_bf16_variant != 36 &&
+  // (MDM_VAR_X3_REG puts the fp32-grade Linears on the register-staged kernel, which reads fp32 rows only)
+  c.x2 = (precision == MDM_PREC_X3 || precision == MDM_PREC_MIXED) && g_variant != MDM_VAR_X3_F32_ROWS && g_variant != MDM_VAR_X3_REG &&
          (m->D == 256 || m->D == 512 || m->D == 1024) && m->F % 32 == 0;
   switch (precision) {
     case MDM_PREC_FP8:  // the fp16 throughput mode with fp8 expert GEMMs (K = D and K = F must be multiples of 128)
@@ -199,12 +199,12 @@ int style_apply(const Ctx& c, const MdmStyle& st, const float* src, const float*
                 const float* sc, float* tmp, const float* resid, float out_scale, const float* colscale, float* out,
                 uint16_t* out16 = nullptr, bool src_bf16 = false, const StyleTail3* t3 = nullptr, bool* t3_done = nullptr) {
   const int D = c.m->D;
-  if (c.bf && st.out_ws && g_bf16_variant != 30 && style_gemm_supported(D, c.M))  // one launch (csrc/style_gemm.hip); knob 30: two
+  if (c.bf && st.out_ws && style_gemm_supported(D, c.M))  // one launch (csrc/style_gemm.hip)
     return style_gemm(src, src_bf16 ? c.h16 : 0, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws, st.out_b, resid,
                       out_scale, colscale, out, out16, c.h16, c.s);
-  // fp32-grade modes: the same fusion on bf16x3 products (csrc/style_gemm.hip style_gemm3; knob 60: two launches)
-  if (!c.bf && c.prec == 3 && !src_bf16 && !out16 && st.out_ws3 && g_bf16_variant != 60 && style_gemm_supported(D, c.M)) {
-    const bool tail = t3 && g_bf16_variant != 61;  // knob 61: the LayerNorms behind it as their own launches
+  // fp32-grade modes: the same fusion on bf16x3 products (csrc/style_gemm.hip style_gemm3; MDM_VAR_X3_STYLE_SPLIT: two launches)
+  if (!c.bf && c.prec == 3 && !src_bf16 && !out16 && st.out_ws3 && g_variant != MDM_VAR_X3_STYLE_SPLIT && style_gemm_supported(D, c.M)) {
+    const bool tail = t3 && g_variant != MDM_VAR_X3_TAILS_SPLIT;  // else the LayerNorms behind it as their own launches
     if (t3_done) *t3_done = tail;
     return style_gemm3(src, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws3, st.out_b, resid, out_scale, colscale, out,
                        tail ? *t3 : StyleTail3(), c.s);
@@ -240,12 +240,10 @@ MdmMlpDesc proj_pair_desc(const Ctx& c, const MdmPerformer& p) {
   f.r1_scale = 1.f, f.C16 = (uint16_t*)c.w.t4, f.ldc = D, f.h16 = c.h16;  // in place: a tile's rows are in LDS before its stores
   return f;
 }
-// whether performer() runs that pair (knob 32: two GEMMs) / the pair AND the Performer's tail (knob 35: the tail as its own launches)
-bool proj_pair_fused(const Ctx& c, const MdmPerformer& p) {
-  return c.bf && g_bf16_variant != 25 && p.proj_ws && g_bf16_variant != 32;
-}
+// whether performer() runs that pair / the pair AND the Performer's tail (MDM_VAR_TAIL_SPLIT: the tail as its own launches)
+bool proj_pair_fused(const Ctx& c, const MdmPerformer& p) { return c.bf && p.proj_ws; }
 bool performer_tail_fused(const Ctx& c, const MdmPerformer& p) {
-  return proj_pair_fused(c, p) && p.style.out_ws && g_bf16_variant != 35 && g_bf16_variant != 30 &&
+  return proj_pair_fused(c, p) && p.style.out_ws && g_variant != MDM_VAR_TAIL_SPLIT &&
          fused_pair_style_supported(proj_pair_desc(c, p));
 }
 
@@ -254,17 +252,18 @@ int performer(const Ctx& c, const MdmPerformer& p, const float* x, Act xn, const
   const MdmModel& m = *c.m;
   const int D = m.D, H = m.H, dh = D / H, mf = dh;  // m = min(dh, 256) = dh for dh <= 256
   const Work& w = c.w;
-  const bool fused256 = c.bf && g_bf16_variant != 23 && perf_attn256_supported(dh, c.S) &&
+  const bool fused256 = c.bf && g_variant != MDM_VAR_GENERIC_DH256 && perf_attn256_supported(dh, c.S) &&
                         perf_attn256_scratch_bytes(c.B, H, c.S) <= c.M * 2 * D * (int64_t)sizeof(float);
   const bool fused = fused256 || (c.bf && perf_attn_supported(dh, c.S));
   // head_dim 128, 16-bit modes: the q | k | v projection inside the attention core's launch (csrc/perf_attn.hip phase 0: one
   // workgroup per (batch, head) multiplies its sample's rows with its head's 384 weight rows; k and v never leave the CU).
-  // Knob 50: the projection as its own GEMM launch.
-  const bool qkv_in = fused && !fused256 && xn.bf && g_bf16_variant != 50 && perf_attn_qkv_supported(dh, c.S, H);
+  // MDM_VAR_QKV_SPLIT: the projection as its own GEMM launch.
+  const bool qkv_in = fused && !fused256 && xn.bf && g_variant != MDM_VAR_QKV_SPLIT && perf_attn_qkv_supported(dh, c.S, H);
   // fp32-grade modes, head_dim 128: the projection's epilogue applies LN(dh) / L2 and writes bf16 hi | lo planes, ONE launch
-  // (csrc/perf_attn3.hip) does features -> KV state -> num / den -> LN on bf16x3 products.  Knob 52: the five-launch chain.
-  const bool fused3 = !c.bf && c.prec == 3 && !xn.bf && g_bf16_variant != 52 && perf_attn3_supported(dh, c.S) && D % 32 == 0 &&
-                      p.qkv.lo && p.feat.lo && (c.M * 3 * D) % 8 == 0;
+  // (csrc/perf_attn3.hip) does features -> KV state -> num / den -> LN on bf16x3 products.  MDM_VAR_X3_ATTN_CHAIN: the five-launch
+  // chain.
+  const bool fused3 = !c.bf && c.prec == 3 && !xn.bf && g_variant != MDM_VAR_X3_ATTN_CHAIN && perf_attn3_supported(dh, c.S) &&
+                      D % 32 == 0 && p.qkv.lo && p.feat.lo && (c.M * 3 * D) % 8 == 0;
   if (fused3) {
     uint16_t* const xh = (uint16_t*)w.qkv;
     uint16_t* const xl = xh + c.M * 3 * D;  // the two 16-bit planes fill the fp32 [M, 3 D] buffer exactly
@@ -342,12 +341,12 @@ int performer(const Ctx& c, const MdmPerformer& p, const float* x, Act xn, const
     MDM_TRY(den_ln(w.t2, w.phi, c.M, H, dh, p.hn_w, p.hn_b, w.t4, fmt16(c), c.s));
   }
   // proj_out: Linear -> GELU -> Linear                             (:121-126,165)
-  const bool t16 = c.bf && g_bf16_variant != 25;  // the projection's output feeds a LayerNorm only: bf16 in throughput mode
+  const bool t16 = c.bf;  // the projection's output feeds a LayerNorm only: bf16 in throughput mode
   bool pair = false;
   if (proj_pair_fused(c, p)) {  // one launch, hidden layer on chip (csrc/mlp_stream.hip)
     const MdmMlpDesc f = proj_pair_desc(c, p);
     // ... and the tail (post_norm, stylization, out_layers.2, residual, the next block's LayerNorm) in the same launch: the
-    // pair's rows never leave the CU (knob 35: the tail as its own launch)
+    // pair's rows never leave the CU (MDM_VAR_TAIL_SPLIT: the tail as its own launch)
     if (performer_tail_fused(c, p)) {
       PairTail t = {};
       t.pw = p.post_w, t.pb = p.post_b, t.sw = p.style.norm_w, t.sb = p.style.norm_b, t.sc = sc, t.S = c.S;
@@ -400,9 +399,10 @@ int dual_block(const Ctx& c, const MdmLayer& l, const float* x, const uint16_t* 
   // launch ends with out = post_norm(skip + 0.1 * global_out) and the next block's pre-norm -- no D x D GEMM waiting behind the
   // attention chain, no LayerNorm launch behind that.
   const bool tails = performer_tail_fused(c, l.local) && performer_tail_fused(c, l.global);
-  // fp32-grade modes: the same re-ordering with the tails inside the stylization launches (style_gemm3): knobs 60 / 61 undo it
-  const bool tails3 = !c.bf && c.prec == 3 && g_bf16_variant != 60 && g_bf16_variant != 61 && l.local.style.out_ws3 &&
-                      l.global.style.out_ws3 && style_gemm_supported(D, c.M);
+  // fp32-grade modes: the same re-ordering with the tails inside the stylization launches (style_gemm3): MDM_VAR_X3_STYLE_SPLIT /
+  // MDM_VAR_X3_TAILS_SPLIT undo it
+  const bool tails3 = !c.bf && c.prec == 3 && g_variant != MDM_VAR_X3_STYLE_SPLIT && g_variant != MDM_VAR_X3_TAILS_SPLIT &&
+                      l.local.style.out_ws3 && l.global.style.out_ws3 && style_gemm_supported(D, c.M);
   float* const skipbuf = w.f1;
   if (tails || tails3) {
     LinOpts o;
@@ -449,14 +449,14 @@ int cross_block(const Ctx& c, const MdmLayer& l, const float* at, const float* x
   const int D = m.D, H = m.H, dh = D / H;
   const Work& w = c.w;
   if (!pre_normed) MDM_TRY(ln_chain(x, c.M, D, l.ca_norm_w, l.ca_norm_b, w.t2, (!c.bf && c.x2) ? 4 : fmt16(c), nullptr, nullptr, nullptr, 0, c.s));
-  const bool fused = c.bf && lin_xattn_supported(dh) && !(dh == 256 && g_bf16_variant == 23);  // knob 23: big-width generic paths
-  bool x16o = false;
-  // head_dim 128: the query projection inside the attention launch (csrc/xattn.hip lin_xattn_q; knob 51: its own GEMM launch)
-  const bool q_in = fused && g_bf16_variant != 51 && D == 512 && lin_xattn_q_supported(dh, c.S, H);
+  const bool fused = c.bf && lin_xattn_supported(dh) && !(dh == 256 && g_variant == MDM_VAR_GENERIC_DH256);
+  // head_dim 128: the query projection inside the attention launch (csrc/xattn.hip lin_xattn_q; MDM_VAR_XQ_SPLIT: its own GEMM launch)
+  const bool q_in = fused && g_variant != MDM_VAR_XQ_SPLIT && D == 512 && lin_xattn_q_supported(dh, c.S, H);
   // fp32-grade modes, head_dim 128: the head_dim softmax is the query projection's epilogue (bf16 hi | lo planes), the product with
-  // A[b, h] one launch on bf16x3 MFMAs (csrc/xattn3.hip).  Knob 56: the chain (GEMM, head_softmax, batched contraction).
-  const bool fused3 = !c.bf && c.prec == 3 && g_bf16_variant != 56 && xattn3_supported(dh, 1) && l.ca_q.lo && D % 32 == 0 &&
-                      (c.M * D) % 8 == 0;
+  // A[b, h] one launch on bf16x3 MFMAs (csrc/xattn3.hip).  MDM_VAR_X3_XATTN_CHAIN: the chain (GEMM, head_softmax, batched
+  // contraction).
+  const bool fused3 = !c.bf && c.prec == 3 && g_variant != MDM_VAR_X3_XATTN_CHAIN && xattn3_supported(dh, 1) && l.ca_q.lo &&
+                      D % 32 == 0 && (c.M * D) % 8 == 0;
   if (fused3) {
     uint16_t* const qh = (uint16_t*)w.t3;
     uint16_t* const ql = qh + c.M * D;  // the two planes fill the fp32 [M, D] buffer exactly
@@ -472,13 +472,12 @@ int cross_block(const Ctx& c, const MdmLayer& l, const float* at, const float* x
     return style_apply(c, l.ca_style, w.t4, nullptr, nullptr, nullptr, sc, w.t2, x, 1.f, l.ca_gvec, out, nullptr, false);
   }
   if (!q_in) MDM_TRY(linear(c, act_x2(c, w.t2), c.M, D, l.ca_q, l.ca_q_b, D, fused ? nullptr : w.t3, fused ? (uint16_t*)w.t3 : nullptr));
+  // the fused forms' output is consumed by the stylization LayerNorm only: 16-bit
   if (q_in) {
-    x16o = g_bf16_variant != 25;
-    MDM_TRY(lin_xattn_q((const uint16_t*)w.t2, l.ca_q.hi, (int)l.ca_q.ld, l.ca_q_b, at, c.B, c.S, H, dh, x16o ? nullptr : w.t4,
-                        x16o ? (uint16_t*)w.t4 : nullptr, c.h16, c.s));
+    MDM_TRY(lin_xattn_q((const uint16_t*)w.t2, l.ca_q.hi, (int)l.ca_q.ld, l.ca_q_b, at, c.B, c.S, H, dh, nullptr, (uint16_t*)w.t4,
+                        c.h16, c.s));
   } else if (fused) {
-    x16o = g_bf16_variant != 25;  // consumed by the stylization LayerNorm only: bf16
-    MDM_TRY(lin_xattn(w.t3, c.h16, at, c.B, c.S, H, dh, x16o ? nullptr : w.t4, x16o ? (uint16_t*)w.t4 : nullptr, c.h16, c.s));  // (:248,253)
+    MDM_TRY(lin_xattn(w.t3, c.h16, at, c.B, c.S, H, dh, nullptr, (uint16_t*)w.t4, c.h16, c.s));  // (:248,253)
   } else {
     MDM_TRY(head_softmax(w.t3, c.M * H, dh, c.s));  // softmax over head_dim (:248)
     {
@@ -493,7 +492,7 @@ int cross_block(const Ctx& c, const MdmLayer& l, const float* at, const float* x
       MDM_TRY(gemm(g, c.s));
     }
   }
-  return style_apply(c, l.ca_style, w.t4, nullptr, nullptr, nullptr, sc, w.t2, x, 1.f, l.ca_gvec, out, nullptr, x16o);
+  return style_apply(c, l.ca_style, w.t4, nullptr, nullptr, nullptr, sc, w.t2, x, 1.f, l.ca_gvec, out, nullptr, fused);
 }
 
 // MoEMultiBranchFFN (multi_branch.py:52-61) with SwitchMoELayer top-2 routing (switch_moe.py:44-111)
@@ -553,9 +552,9 @@ int moe_block(const Ctx& c, const MdmLayer& l, const float* x, const float* sc, 
     }
     return style_apply(c, l.ffn_style, w.y2, nullptr, nullptr, w.pos4, sc, w.t2, x, 1.f, nullptr, out, out16, true);
   }
-  if (h && g_bf16_variant != 21 && fused_mlp_supported(f)) {  // variant 21: two-GEMM chain, for A/B runs
+  if (h && fused_mlp_supported(f)) {
     // throughput mode: both expert GEMMs in one kernel, hidden activations stay in LDS (switch_moe.py:19-25,104-109)
-    const bool y16 = c.bf && g_bf16_variant != 25;  // expert outputs stored in 16 bits (what autocast does to a Linear); knob 25 / mixed mode: fp32
+    const bool y16 = c.bf;  // expert outputs stored in 16 bits (what autocast does to a Linear); mixed mode: fp32
     if (y16) f.C = nullptr, f.C16 = (uint16_t*)w.y2;
     const bool pr = g_probe.on && g_probe.n < PROBE_MAX;
     if (pr && hipEventRecord(g_probe.a[g_probe.n], c.s) != hipSuccess) return MDM_ERR_LAUNCH;
@@ -617,12 +616,12 @@ int moe_block(const Ctx& c, const MdmLayer& l, const float* x, const float* sc, 
 
 // Passes the folded text cross-attention (csrc/sdfold.hip) takes, 0 = use the GEMM chain.  Measured end to end (configs[1],
 // ms per step, folded / chain): N = 28: 6.09 / 6.28, N = 40: 6.16 / 6.27, N = 64: 6.21 / 6.29 (two passes), N = 85: 6.40 / 6.31
-// (four passes: each pass re-streams the x tile and restarts the K' pipeline) -- so the fold is taken up to two passes; knob 24
-// forces it at any supported N (tests).
+// (four passes: each pass re-streams the x tile and restarts the K' pipeline) -- so the fold is taken up to two passes;
+// MDM_VAR_SD_FOLD_ANY forces it at any supported N (tests).
 int sd_fold_policy(int D, int H, int N) {
   if (!sd_fold_supported(D, H, N)) return 0;
   const int np = sd_fold_passes(H, N);
-  return (np <= 2 || g_bf16_variant == 24) ? np : 0;
+  return (np <= 2 || g_variant == MDM_VAR_SD_FOLD_ANY) ? np : 0;
 }
 
 // MemoryEfficientCrossAttentionBlock (fast_attention.py:301-330); out must not alias x
@@ -637,15 +636,15 @@ int sdcross_block(const Ctx& c, const MdmLayer& l, const float* kc, const float*
   const MdmModel& m = *c.m;
   const int D = m.D, H = m.H, dh = D / H, N = c.N;
   const Work& w = c.w;
-  if (c.bf && fold.kfold && g_bf16_variant != 22 && sd_fold_policy(D, H, N) > 0) {
+  if (c.bf && fold.kfold && g_variant != MDM_VAR_SD_UNFOLDED && sd_fold_policy(D, H, N) > 0) {
     // throughput mode: query GEMM + attention core + output GEMM + LayerNorm in one launch (csrc/sdfold.hip)
     MDM_TRY(sd_fold(x16, fold.kfold, fold.cb, fold.vfold, l.sd_out_b, l.sd_ln_w, l.sd_ln_b, c.B, c.S, D, H, N, w.t3,
                     (uint16_t*)w.t4, c.h16, c.s));
-    // the 4x FFN pair in one launch (knob 33: two GEMMs) at the full time scale only: at the half scale of the bench batch
+    // the 4x FFN pair in one launch at the full time scale only: at the half scale of the bench batch
     // (6272 rows -> 32-row tiles, every workgroup streams the pair's 4 MB for 32 rows) it measures slower than the two GEMMs
     // (78 vs 66 us; 100 vs 120 us at 12544 rows).  The choice is made on the FRAME count of the scale, never on the batch: a
     // sample's result must not depend on the batch it travels in (shard invariance, cond | uncond batching)
-    if (l.sd_ffn_ws && g_bf16_variant != 33 && c.S >= 128) {
+    if (l.sd_ffn_ws && c.S >= 128) {
       MdmMlpDesc f = {};
       f.X = (const uint16_t*)w.t4, f.ldx = D, f.M = (int)c.M, f.Din = D, f.F = 4 * D, f.Dout = D;
       f.b1 = l.sd_f1_b, f.b2 = l.sd_f2_b, f.wstream = l.sd_ffn_ws, f.wstream_gs = 8 * (int64_t)D * D;
@@ -662,8 +661,8 @@ int sdcross_block(const Ctx& c, const MdmLayer& l, const float* kc, const float*
   }
   // fp32-grade modes, head_dim 128: the query projection leaves as bf16 hi | lo planes, scores / softmax / PV are one launch on
   // bf16x3 MFMAs (csrc/xattn3.hip).  Knob 56: the chain (two batched contractions around a row softmax).
-  const bool fused3 = !c.bf && c.prec == 3 && g_bf16_variant != 56 && xattn3_supported(dh, N) && l.sd_q.lo && D % 32 == 0 &&
-                      (c.M * D) % 8 == 0;
+  const bool fused3 = !c.bf && c.prec == 3 && g_variant != MDM_VAR_X3_XATTN_CHAIN && xattn3_supported(dh, N) && l.sd_q.lo &&
+                      D % 32 == 0 && (c.M * D) % 8 == 0;
   if (fused3) {
     uint16_t* const qh = (uint16_t*)w.t1;
     uint16_t* const ql = qh + c.M * D;
@@ -678,12 +677,12 @@ int sdcross_block(const Ctx& c, const MdmLayer& l, const float* kc, const float*
   } else {
     LinOpts o;
     o.alpha = 1.f / sqrtf((float)dh);
-    const bool fz = c.bf && xattn_supported(dh, N) && !(dh == 256 && g_bf16_variant == 23);
+    const bool fz = c.bf && xattn_supported(dh, N) && !(dh == 256 && g_variant == MDM_VAR_GENERIC_DH256);
     MDM_TRY(linear(c, c.bf ? act_bf16(x16) : act_f32(x), c.M, D, l.sd_q, l.sd_q_b, D, fz ? nullptr : w.t1,
                    fz ? (uint16_t*)w.t1 : nullptr, o));
   }
   if (fused3) {
-  } else if (c.bf && xattn_supported(dh, N) && !(dh == 256 && g_bf16_variant == 23)) {
+  } else if (c.bf && xattn_supported(dh, N) && !(dh == 256 && g_variant == MDM_VAR_GENERIC_DH256)) {
     MDM_TRY(sd_attn(w.t1, c.h16, kc, vc, c.B, c.S, H, dh, N, (uint16_t*)w.t2, nullptr, c.h16, c.s, c.ntok));  // scores, softmax, PV fused
   } else {
     {
@@ -1015,10 +1014,10 @@ int mdm_denoiser_forward(const MdmModel* m, const MdmTextCache* tc, const float*
     o.R1 = m->seq_emb, o.r1_mod = T;
     // the root of the residual stream (and of the U's skip connection): always the bf16x3 arithmetic -- 3.4 GFLOP, K = 263.
     // Measured at B = 32 / T = 196 / L = 4, fp16 mode, free routing: 1679 -> 596 of 75264 routing decisions differ from the
-    // fp32-grade run, median frame error 4.7e-3 -> 1.8e-3 (tools/mode_compare.py; knob 31 restores the single bf16 pass).
+    // fp32-grade run, median frame error 4.7e-3 -> 1.8e-3 (tools/mode_compare.py).
     // The same treatment of down / up / the stem GEMMs bought another 14 % for +0.2 ms per step: not taken.
     Ctx cj = c;
-    if (g_bf16_variant != 31) cj.prec = 3;
+    cj.prec = 3;
     MDM_TRY(linear(cj, act_f32(x), Mfull, m->feats, m->joint, m->joint_b, D, w.h0, c.bf ? w.h016 : nullptr, o));
   }
   // Conv1d(k=2,s=2) == Linear over pairs of frames                  (:332-337)

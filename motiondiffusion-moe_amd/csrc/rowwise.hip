@@ -5,7 +5,6 @@
 #include "row.h"
 
 namespace mdm {
-extern int g_bf16_variant;
 namespace {
 
 // ---- LN chain: y1 = LN1(x), y2 = LN2(y1) --------------------------------------------------------
@@ -831,11 +830,12 @@ int style_in(const float* x, int64_t M, int D, int S, const float* pw, const flo
 // The router with compile-time expert count and hn format (D = 512 / 1024, E = 8 / 16, 16-bit hn rows): bit-identical to the
 // run-time version (tests/test_blocks_gpu.py) and 2 % of a step faster at both model sizes (5.85 -> 5.74 and 15.59 -> 15.27 ms,
 // alternating runs on one box).  Default for E = 8 at D = 512 and D = 1024 (the combinations the bit-equality tests cover:
-// tests/test_blocks_gpu.py, tests/test_bigsize_gpu.py); knob 26 takes it wherever it exists, knob 27 never.
+// tests/test_blocks_gpu.py, tests/test_bigsize_gpu.py); MDM_VAR_ROUTER_CONST_E takes it wherever it exists, MDM_VAR_ROUTER_RUNTIME_E
+// never.
 bool gate16_const_wanted(int nv, int E) {
-  if (g_bf16_variant == 27) return false;
+  if (g_variant == MDM_VAR_ROUTER_RUNTIME_E) return false;
   // E = 16 (BASELINE configs[4]) as well: 6.65 -> 6.50 ms per step at its per-GPU shape (big, B = 8), same-box A/B of knobs 0 / 26
-  return g_bf16_variant == 26 || ((nv == 8 || nv == 16) && (E == 8 || E == 16));
+  return g_variant == MDM_VAR_ROUTER_CONST_E || ((nv == 8 || nv == 16) && (E == 8 || E == 16));
 }
 template <int NV, int EX, int HNF, bool FAST = true>
 bool launch_gate16_const(int grid, int smem, hipStream_t s, const float* x, int64_t M, int D, int E, const MoeGateParams& p) {

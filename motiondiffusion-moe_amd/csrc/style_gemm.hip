@@ -56,9 +56,6 @@ struct StyleGemmArgs {
   float skip_scale;
   const float *l2w, *l2b;
   int ln_x2;  // ln_out as pre-split rows (MDM_OP_X2_ROW) for the GEMM that reads it, instead of fp32
-#ifdef MDM_DIAG
-  int ko;  // diagnostic library only (knobs 74..77, tools/style_ko.sh): 1 no row phase, 2 no K loop, 3 no output stores, 4 no weight refills
-#endif
 };
 
 template <typename HT, bool SRC16, int SG_RT>
@@ -80,9 +77,6 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
   for (int f = 0; f < 8; ++f) R[f] = *(const frag_t*)(wp + f * 1024);
 
   // ---- row phase (csrc/rowwise.hip style_in_rows, one wave per row) ------------------------------------------------------
-#ifdef MDM_DIAG
-  if (g.ko != 1)
-#endif
   {
     R8 pww, pbb, sww, sbb;
     if (g.pw) pww.load(g.pw, D, lane), pbb.load(g.pb, D, lane);
@@ -156,12 +150,6 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
     frag_t A[2][SG_RT];
 #pragma unroll
     for (int i = 0; i < SG_RT; ++i) A[0][i] = *(const frag_t*)(smem + xb + i * 16384);
-#ifdef MDM_DIAG
-    const int ksteps = g.ko == 2 ? 0 : 16;
-    const bool refill = g.ko != 4;
-#pragma unroll 1
-    for (int s0 = 0; s0 < ksteps; s0 += 16)
-#endif
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
       if (s + 1 < 16) {
@@ -173,9 +161,6 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
         const int slot = (s * SG_NJ + j) & (NR - 1);
 #pragma unroll
         for (int i = 0; i < SG_RT; ++i) y[i][j] = HT::mfma16(R[slot], A[s & 1][i], y[i][j]);
-#ifdef MDM_DIAG
-        if (refill)
-#endif
         R[slot] = *(const frag_t*)(wp + slot * 1024);  // the last NR refills read (and discard) the next wave's / the padding
         if (slot == NR - 1) wp += NR * 1024;
       }
@@ -222,9 +207,6 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
     if (m >= g.M) continue;
     f32x4 v = *(const f32x4*)(stg + ml * D + ((cl ^ (ml & 31)) << 2));
     if (g.resid) v[0] += q[k][0], v[1] += q[k][1], v[2] += q[k][2], v[3] += q[k][3];
-#ifdef MDM_DIAG
-    if (g.ko == 3 && v[0] != 12345.678f) continue;
-#endif
     *(f32x4*)(g.out + m * D + n) = v;
     if (g.out16) *(uint2*)(g.out16 + m * D + n) = make_uint2(HT::pack(v[0], v[1]), HT::pack(v[2], v[3]));
   }
@@ -462,7 +444,6 @@ int gemm_stream_pack(const float* w, int N, int K, int h16, uint16_t* out, hipSt
 
 bool style_gemm_supported(int D, int64_t M) { return D == SG_D && M > 0 && M / 32 < (1ll << 30); }
 
-extern int g_bf16_variant;
 
 template <int RT>
 static int launch_style_gemm(const StyleGemmArgs& g, bool src16, int h16, hipStream_t s) {
@@ -498,12 +479,8 @@ int style_gemm(const void* src, int src_fmt, int64_t M, int D, int S, const floa
   StyleGemmArgs g = {};
   g.src = src, g.M = M, g.S = S, g.pw = pw, g.pb = pb, g.sw = sw, g.sb = sb, g.sc = sc, g.pos4 = pos4, g.ws = ws, g.bias = bias;
   g.resid = resid, g.out_scale = out_scale, g.colscale = colscale, g.out = out, g.out16 = out16;
-#ifdef MDM_DIAG
-  g.ko = (g_bf16_variant >= 74 && g_bf16_variant <= 77) ? g_bf16_variant - 73 : 0;
-#endif
-  // knob 29: 64-row tiles (one workgroup per CU, half the weight bytes per row) -- measured 1 % of a step SLOWER than two
-  // co-resident 32-row workgroups per CU at 12544 rows; a row's arithmetic does not depend on the tile height
-  if (g_bf16_variant == 29) return launch_style_gemm<4>(g, src_fmt != 0, h16, s);
+  // 64-row tiles (one workgroup per CU, half the weight bytes per row) measured 1 % of a step SLOWER than two co-resident 32-row
+  // workgroups per CU at 12544 rows; a row's arithmetic does not depend on the tile height
   return launch_style_gemm<2>(g, src_fmt != 0, h16, s);
 }
 
@@ -533,7 +510,7 @@ static int launch_style_gemm3(const StyleGemmArgs& g, hipStream_t s) {
 }
 
 // fp32 source rows, fp32 output; ws3 = the (hi, lo) pair stream of mdm_gemm_stream3_pack.  32-row tiles (two workgroups per CU) at
-// every size: 64-row tiles (one per CU, half the weight bytes per row; knob 58) measured 1 % of a step slower at the full time scale
+// every size: 64-row tiles (one per CU, half the weight bytes per row) measured 1 % of a step slower at the full time scale
 // (10.18 vs 10.06 ms) -- as in the 16-bit form, a second resident workgroup hides more than the halved stream saves.  A row's
 // arithmetic does not depend on the tile height.
 int style_gemm3(const float* src, int64_t M, int D, int S, const float* pw, const float* pb, const float* sw, const float* sb,
@@ -548,7 +525,6 @@ int style_gemm3(const float* src, int64_t M, int D, int S, const float* pw, cons
   g.src = src, g.M = M, g.S = S, g.pw = pw, g.pb = pb, g.sw = sw, g.sb = sb, g.sc = sc, g.pos4 = pos4, g.ws = ws3, g.bias = bias;
   g.resid = resid, g.out_scale = out_scale, g.colscale = colscale, g.out = out;
   g.lw = t.lw, g.lb = t.lb, g.ln_out = t.ln_out, g.skip = t.skip, g.skip_scale = t.skip_scale, g.l2w = t.l2w, g.l2b = t.l2b, g.ln_x2 = t.ln_x2;
-  if (g_bf16_variant == 58) return launch_style_gemm3<4>(g, s);  // A/B knob: 64-row tiles
   return launch_style_gemm3<2>(g, s);
 }
 

@@ -170,12 +170,10 @@ class PackedModel:
                     self.V[k[2:]] = t
             D, L_ = cfg["latent_dim"], cfg["num_layers"]
             # weight streams of the expert MLPs for the streamed-weight fused kernel (csrc/mlp_stream.hip): the 16-bit
-            # modes at the shapes it takes; MDM_MLP_STREAM=0 keeps the LDS-staged kernel (A/B runs)
+            # modes at the shapes it takes
             self.wstream = {}
             E2, F_ = 2 * cfg["moe_num_experts"], cfg["ff_size"]
-            import os
-            if (os.environ.get("MDM_MLP_STREAM", "1") != "0" and D in (512, 1024) and F_ % 256 == 0
-                    and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_MIXED)):
+            if D in (512, 1024) and F_ % 256 == 0 and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_MIXED):
                 from .ops import mlp_stream_pack
                 for li in range(2 * L_):
                     k = f"L{li}."
@@ -185,7 +183,7 @@ class PackedModel:
                                                       lay["W:" + k + "w2"].to(dev).reshape(E2, D, F_), dt)
             # ... and of the dense Linear-GELU-Linear pairs (Performer output projection, 4x FFN of the text cross-attention),
             # throughput modes only (their activations are 16-bit there); the mixed mode runs the FFN pair in fp16 as well
-            if os.environ.get("MDM_MLP_STREAM", "1") != "0" and D == 512 and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_MIXED):
+            if D == 512 and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_MIXED):
                 from .ops import mlp_stream_pack
                 for li in range(2 * L_):
                     k = f"L{li}."
@@ -209,7 +207,7 @@ class PackedModel:
                                 self.wstream[st + "out"] = ws
             # ... and its (hi, lo) pair streams for the fp32-grade form (csrc/style_gemm.hip style_gemm3): every format class whose
             # stylization Linears are packed as bf16 hi + lo planes (fp32-grade and mixed runs)
-            if os.environ.get("MDM_MLP_STREAM", "1") != "0" and D == 512 and with_lo:
+            if D == 512 and with_lo:
                 from .ops import gemm_stream3_pack
                 for li in range(2 * L_):
                     k = f"L{li}."
@@ -220,13 +218,12 @@ class PackedModel:
                         if ws is not None:
                             self.wstream[st + "out3"] = ws
             # fragment streams of the plain per-layer Linears for the streamed-weight GEMM (csrc/gemm_stream.hip): the 16-bit modes of the
-            # big model, whose D x D launches are latency chains on the tile kernel; MDM_GEMM_STREAM=0 keeps the tile kernel (A/B runs).
+            # big model, whose D x D launches are latency chains on the tile kernel.
             # Not the expert matrices: only linear() hands MdmPacked.ws to a 16-bit launch, and the expert GEMMs of those modes take the
             # fused MLP (self.wstream) or the tile kernel.  self.wstream1 holds every MdmPacked.ws: these under the matrix name, the pair
             # streams below under pair_key(name)
             self.wstream1 = {}
-            if (os.environ.get("MDM_GEMM_STREAM", "1") != "0" and D == 1024
-                    and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_FP8)):
+            if D == 1024 and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_FP8):
                 from .ops import gemm_stream1_pack
                 for kk, t in lay.items():
                     if not kk.startswith("W:L") or t.dim() != 2 or t.shape[1] not in (512, 1024) or t.shape[0] % 256:
@@ -241,7 +238,7 @@ class PackedModel:
                         self.wstream1[kk[2:]] = ws
             # (hi, lo) fragment-pair streams of the expert matrices for the streamed-weight bf16x3 GEMM (csrc/gemm_stream3.hip): the
             # fp32-grade mode, whose expert GEMM pair is 45 % of its step on the tile kernel
-            if os.environ.get("MDM_GEMM_STREAM", "1") != "0" and with_lo and precision == L.PREC_X3 and D % 128 == 0 and F_ % 128 == 0:
+            if with_lo and precision == L.PREC_X3 and D % 128 == 0 and F_ % 128 == 0:
                 from .ops import gemm_stream3x_pack
                 for li in range(2 * L_):
                     k = f"L{li}."

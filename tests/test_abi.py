@@ -53,22 +53,30 @@ def test_argument_validation_without_gpu():
     assert lib.mdm_cfg_posterior_step(None, None, None, None, C.c_int64(0), None, 0, None, 0, C.c_float(1.0), 0, None, None, None) == 1
 
 
-def test_product_library_refuses_the_diagnostic_knobs():
-    """the knock-out / stamped builds of the fused expert MLP (knobs 41..49, outputs wrong by construction) live
-    in the diagnostic library only (-DMDM_DIAG).  libmdm_hip.so returns MDM_ERR_ARG for them, leaves the knob where it was and
-    has no counter hook; every other documented knob is still accepted."""
+def _variants():
+    """The values of enum MdmVariant in include/mdm_hip.h."""
+    src = open(os.path.join(ROOT, "include", "mdm_hip.h")).read()
+    body = re.sub(r"/\*.*?\*/", "", re.search(r"enum MdmVariant \{(.*?)\};", src, flags=re.S).group(1), flags=re.S)
+    return {int(v) for v in re.findall(r"MDM_VAR_\w+\s*=\s*(\d+)", body)}
+
+
+def test_gemm_variant_accepts_exactly_the_enum():
+    """mdm_set_gemm_variant accepts the values of enum MdmVariant (the reference paths the tests hold other paths against) and
+    returns MDM_ERR_ARG for every other value.  The library has no diagnostic entry points, and its fused-MLP object holds only the
+    plain (0) and the Performer-tail (1) instantiations."""
     import subprocess
     L = pkg("_lib")
     lib = L.lib()
-    assert lib.mdm_diag_build() == 0
-    assert lib.mdm_set_gemm_variant(34) == 0
-    for v in list(range(41, 50)) + list(range(74, 78)):  # (74..77: knock-outs of the fused stylization launch)
-        assert lib.mdm_set_gemm_variant(v) == 1, v  # MDM_ERR_ARG
+    known = _variants()
+    assert known == {0, 6, 22, 23, 24, 26, 27, 34, 35, 36, 50, 51, 52, 56, 60, 61, 62, 63, 68, 69, 70}
+    for v in range(1, 128):
+        assert lib.mdm_set_gemm_variant(v) == (0 if v in known else 1), v  # MDM_OK / MDM_ERR_ARG
     assert lib.mdm_set_gemm_variant(0) == 0
-    assert lib.mdm_diag_mlp_counters(None) == 3  # MDM_ERR_UNSUPPORTED
-    # the product object holds no knock-out instantiation: template arguments <format, RT, NJ, DIN, KO> with KO in {0, 10} only
+    for name in ("mdm_diag_build", "mdm_diag_mlp_counters", "mdm_debug_stamps"):
+        assert not hasattr(lib, name), name
+    # template arguments <format, RT, NJ, DIN, TAIL>
     obj = os.path.join(ROOT, "motiondiffusion-moe_amd", "csrc", "build", "mlp_stream.o")
     if os.path.exists(obj):
         syms = subprocess.run(["nm", "-C", obj], capture_output=True, text=True).stdout
-        kos = set(re.findall(r"fused_mlp_stream_kernel<[^,]+, \d+, \d+, \d+, (\d+)>", syms))
-        assert kos and kos <= {"0", "10"}, kos
+        tails = set(re.findall(r"fused_mlp_stream_kernel<[^,]+, \d+, \d+, \d+, (\d+)>", syms))
+        assert tails == {"0", "1"}, tails

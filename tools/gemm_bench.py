@@ -29,9 +29,7 @@ if __name__ == "__main__":
     for (M, N, K) in shapes[:4]:
         us, tf = bench(M, N, K, 1, act=1)
         print(f"  M={M:6d} N={N:5d} K={K:5d}: {us:8.1f} us {tf:7.1f} TF")
-    for v, name in [(1, "BK64 x2"), (2, "BK64 x3"), (3, "BK32 x3"), (4, "BK32 x4"), (5, "BK64 x4")]:
-        L.lib().mdm_set_gemm_variant(v)
-        print(f"bf16 glds kernel variant {v} ({name}):")
-        for (M, N, K) in shapes:
-            us, tf = bench(M, N, K, 1, act=1, a16=True)
-            print(f"  M={M:6d} N={N:5d} K={K:5d}: {us:8.1f} us {tf:7.1f} TF")
+    print("bf16 glds kernel:")
+    for (M, N, K) in shapes:
+        us, tf = bench(M, N, K, 1, act=1, a16=True)
+        print(f"  M={M:6d} N={N:5d} K={K:5d}: {us:8.1f} us {tf:7.1f} TF")

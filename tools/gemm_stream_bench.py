@@ -1,5 +1,5 @@
-"""Streamed-weight GEMM (csrc/gemm_stream.hip) against the 128 x 128 tile kernel (knob 63) at the big model's shapes, interleaved in one
-process: 16-bit rows, fp32 + 16-bit outputs, bias + residual epilogue; knobs 64..67 force the tile shape (rows x columns)."""
+"""Streamed-weight GEMM (csrc/gemm_stream.hip) against the 128 x 128 tile kernel (MDM_VAR_STREAM_NEVER) at the big model's shapes,
+interleaved in one process: 16-bit rows, fp32 + 16-bit outputs, bias + residual epilogue."""
 import importlib
 import os
 import sys
@@ -16,7 +16,7 @@ def main():
     light = len(sys.argv) > 1 and sys.argv[1] == "light"  # 16-bit output only, no residual: the launch without its fp32 epilogue traffic
     shapes = [(12544, 1024, 1024), (6272, 1024, 1024), (3136, 1024, 1024), (1568, 1024, 1024), (12544, 3072, 1024), (12544, 4096, 1024),
               (6272, 3072, 1024), (12544, 512, 512), (6272, 512, 512)]
-    variants = [(63, "tile kernel"), (68, "streamed (auto shape)"), (64, "112 x 512"), (65, "64 x 512"), (66, "64 x 256"), (67, "32 x 256")]
+    variants = [(63, "tile kernel"), (68, "streamed (auto shape)")]
     for M, N, K in shapes:
         torch.manual_seed(0)
         x = torch.randn(M, K, device=dev).to(torch.bfloat16)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Precision modes against the fp32-grade mode (bf16x3) on the bench workload, HIP vs HIP: error, routing decisions that
-differ, optional kernel-selection knobs.   python tools/mode_compare.py [--variants 0,31,...] [--modes 4,2,1]"""
+differ, optional kernel-selection knobs.   python tools/mode_compare.py [--variants 0,62,...] [--modes 4,2,1]"""
 import argparse
 import ctypes as C
 import importlib
