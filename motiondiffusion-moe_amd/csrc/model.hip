@@ -23,6 +23,15 @@ struct Probe {
   bool made = false;
 };
 Probe g_probe;
+// the probe's bracket around the launches it times (nothing while it is off or full)
+bool probe_armed() { return g_probe.on && g_probe.n < PROBE_MAX; }
+int probe_begin(hipStream_t s) { return probe_armed() && hipEventRecord(g_probe.a[g_probe.n], s) != hipSuccess ? MDM_ERR_LAUNCH : MDM_OK; }
+int probe_end(hipStream_t s, int rows) {
+  if (!probe_armed()) return MDM_OK;
+  if (hipEventRecord(g_probe.b[g_probe.n], s) != hipSuccess) return MDM_ERR_LAUNCH;
+  g_probe.rows[g_probe.n++] = rows;
+  return MDM_OK;
+}
 int32_t* g_route_dump = nullptr;  // mdm_route_dump: where the router's top-2 indices of every layer are copied (tests)
 int64_t g_route_cap = 0;           // its capacity in int32 elements: a forward that would write past it is refused
 
@@ -137,8 +146,14 @@ inline GemmArgs gd(const Ctx& c) {  // GEMM descriptor defaults of this run
   g.h16 = c.h16;
   return g;
 }
-inline int fmt16(const Ctx& c) { return c.bf ? c.h16 : 0; }             // format code of a mode-typed tensor (0 = fp32)
-inline int fmt_mlp(const Ctx& c) { return (c.bf || c.mix) ? c.h16 : 0; }  // ... of the expert-MLP / FFN operands
+// the mode combinations the choosers and block bodies below ask about
+inline bool x3_flow(const Ctx& c) { return !c.bf && c.prec == 3; }  // fp32-grade flow: fp32 activations, bf16x3 GEMMs
+inline bool x2_rows(const Ctx& c) { return !c.bf && c.x2; }         // ... its GEMM-only tensors written as pre-split rows
+inline bool mlp16(const Ctx& c) { return c.bf || c.mix; }           // expert-MLP / 4x FFN operands in 16 bits
+inline bool mlp_x2(const Ctx& c) { return x2_rows(c) && !c.mix; }   // ... else pre-split (x2 implies D % 64 == 0)
+inline int fmt16(const Ctx& c) { return c.bf ? c.h16 : 0; }            // format code of a mode-typed tensor (0 = fp32)
+inline int fmt_xn(const Ctx& c) { return x2_rows(c) ? 4 : fmt16(c); }  // ... of the pre-normed rows a projection reads (4 = pre-split)
+inline int fmt_mlp(const Ctx& c) { return mlp_x2(c) ? 4 : mlp16(c) ? c.h16 : 0; }  // ... of the expert-MLP / FFN input rows
 
 // a tensor that is fp32 in the fp32-grade mode and bf16 in the throughput mode, living in a float-sized buffer
 struct Act {
@@ -147,10 +162,9 @@ struct Act {
   bool x2 = false;  // pre-split rows (MDM_OP_X2_ROW) in an fp32-sized buffer
 };
 inline Act act_of(const Ctx& c, float* buf) { return Act{buf, c.bf}; }
-inline Act act_x2(const Ctx& c, float* buf) { return Act{buf, c.bf, !c.bf && c.x2}; }  // a tensor its producer wrote in the mode's GEMM-input form
+inline Act act_x2(const Ctx& c, float* buf) { return Act{buf, c.bf, x2_rows(c)}; }  // a tensor its producer wrote in the mode's GEMM-input form
 inline Act act_f32(const float* buf) { return Act{(void*)buf, false}; }
 inline Act act_bf16(const uint16_t* buf) { return Act{(void*)buf, true}; }
-inline Act act_h16(const void* buf) { return Act{(void*)buf, true}; }
 
 struct LinOpts {
   int act = ACT_NONE;
@@ -192,44 +206,67 @@ int linear_to_act(const Ctx& c, Act A, int64_t M, int K, const MdmPacked& W, con
   return linear(c, A, M, K, W, bias, N, c.bf ? nullptr : buf, c.bf ? (uint16_t*)buf : nullptr, o);
 }
 
-// out = resid + out_scale * colscale * Lin(SiLU(LN(a)(1+scale)+shift)) with a = [post-processed] src
-// t3 / t3_done: fp32-grade modes only -- what the fused launch may do with the finished rows (csrc/gemm.h StyleTail3); *t3_done says
-// whether it did (false: the caller runs those LayerNorms itself)
-int style_apply(const Ctx& c, const MdmStyle& st, const float* src, const float* pw, const float* pb, const int* pos4,
-                const float* sc, float* tmp, const float* resid, float out_scale, const float* colscale, float* out,
-                uint16_t* out16 = nullptr, bool src_bf16 = false, const StyleTail3* t3 = nullptr, bool* t3_done = nullptr) {
-  const int D = c.m->D;
-  if (c.bf && st.out_ws && style_gemm_supported(D, c.M))  // one launch (csrc/style_gemm.hip)
-    return style_gemm(src, src_bf16 ? c.h16 : 0, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws, st.out_b, resid,
-                      out_scale, colscale, out, out16, c.h16, c.s);
-  // fp32-grade modes: the same fusion on bf16x3 products (csrc/style_gemm.hip style_gemm3; MDM_VAR_X3_STYLE_SPLIT: two launches)
-  if (!c.bf && c.prec == 3 && !src_bf16 && !out16 && st.out_ws3 && g_variant != MDM_VAR_X3_STYLE_SPLIT && style_gemm_supported(D, c.M)) {
-    const bool tail = t3 && g_variant != MDM_VAR_X3_TAILS_SPLIT;  // else the LayerNorms behind it as their own launches
-    if (t3_done) *t3_done = tail;
-    return style_gemm3(src, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws3, st.out_b, resid, out_scale, colscale, out,
-                       tail ? *t3 : StyleTail3(), c.s);
-  }
-  MDM_TRY(style_in(src, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, src_bf16 ? c.h16 : 0, tmp, fmt16(c), c.s));
-  LinOpts o;
-  o.out_scale = out_scale, o.R1 = resid, o.colscale = colscale;
-  return linear(c, act_of(c, tmp), c.M, D, st.out, st.out_b, D, out, out16, o);
+// one contraction per (sample b, head h) of the generic attention chains: A and W are read at b * bs1 + h * bs2 (heads()),
+// C is written at b * c_bs1 + h * c_bs2
+inline Operand heads(Operand o, int64_t bs1, int64_t bs2) { o.bs1 = bs1, o.bs2 = bs2; return o; }
+GemmArgs per_head(const Ctx& c, Operand A, Operand W, int M, int N, int K, int64_t ldc, int64_t c_bs1, int64_t c_bs2) {
+  GemmArgs g = gd(c);
+  g.A = A, g.W = W;
+  g.M = M, g.N = N, g.K = K;
+  g.batch = c.B * c.m->H, g.nb2 = c.m->H;
+  g.ldc = ldc, g.c_bs1 = c_bs1, g.c_bs2 = c_bs2;
+  return g;
 }
 
-// PerformerSelfAttention (fast_attention.py:137-179): xn = pre_norm(x) already computed; out = x + 0.1*style(...)
-// What the fused tail (csrc/mlp_stream.hip pair_tail) may do beyond the Performer itself when it runs (*done says whether it did):
-//   skip == NULL: ln16 = LN(out; lw, lb)                          (the pre-norm of the block that follows)
-//   skip != NULL: out  = LN(skip + skip_scale * r; lw, lb) with r the Performer's own output, which is not written;
-//                 ln16 = LN(out; l2w, l2b) when l2w is set         (the tail of DualSelfAttentionBlock, fast_attention.py:219-225)
-struct PerfTail {
-  const float *lw = nullptr, *lb = nullptr;
-  uint16_t* ln16 = nullptr;
-  float* ln32 = nullptr;  // the fp32-grade modes' form of ln16 (fp32 rows; csrc/style_gemm.hip style_gemm3)
-  bool ln_x2 = false;     // ... as pre-split rows for the GEMM that reads them
-  const float* skip = nullptr;
-  float skip_scale = 0.f;
-  const float *l2w = nullptr, *l2b = nullptr;
-  bool* done = nullptr;
-};
+// the input of an fp32-grade attention core: A W^T + bias (K = D) as bf16 hi | lo planes of [M, N] each; the caller adds the
+// epilogue (ACT_HEADNORM, ACT_HEADSOFTMAX, alpha)
+GemmArgs planes_gemm(const Ctx& c, Act A, const MdmPacked& W, const float* bias, int N, uint16_t* hi, uint16_t* lo) {
+  const int K = c.m->D;
+  GemmArgs g = gd(c);
+  g.A = op_f32((const float*)A.p, K);
+  if (A.x2) g.A.kind = OP_X2_ROW;
+  g.W = packed(W);
+  g.M = (int)c.M, g.N = N, g.K = K;
+  g.bias = bias;
+  g.C16 = hi, g.C16_lo = lo, g.ldc = N;
+  return g;
+}
+
+// Stylization: one launch (csrc/style_gemm.hip) / the same on bf16x3 products, with the caller's tail when it asks for one
+// (MDM_VAR_X3_TAILS_SPLIT: without) / style_in and the Linear as two launches (MDM_VAR_X3_STYLE_SPLIT in the fp32-grade modes)
+enum class StylePath { FUSED16, FUSED3, FUSED3_TAIL, SPLIT };
+StylePath style_path(const Ctx& c, const MdmStyle& st, bool src16, bool out16, bool tail) {
+  const int D = c.m->D;
+  if (c.bf && st.out_ws && style_gemm_supported(D, c.M)) return StylePath::FUSED16;
+  if (x3_flow(c) && !src16 && !out16 && st.out_ws3 && g_variant != MDM_VAR_X3_STYLE_SPLIT && style_gemm_supported(D, c.M))
+    return tail && g_variant != MDM_VAR_X3_TAILS_SPLIT ? StylePath::FUSED3_TAIL : StylePath::FUSED3;
+  return StylePath::SPLIT;
+}
+
+// out = resid + out_scale * colscale * Lin(SiLU(LN(a)(1+scale)+shift)) with a = [post-processed] src
+// t3: fp32-grade modes only -- what the fused launch does with the finished rows (csrc/gemm.h StyleTail3) where style_path()
+// says FUSED3_TAIL (elsewhere the caller runs those LayerNorms itself)
+int style_apply(const Ctx& c, const MdmStyle& st, const float* src, const float* pw, const float* pb, const int* pos4,
+                const float* sc, float* tmp, const float* resid, float out_scale, const float* colscale, float* out,
+                uint16_t* out16 = nullptr, bool src_bf16 = false, const StyleTail3* t3 = nullptr) {
+  const int D = c.m->D;
+  const StylePath path = style_path(c, st, src_bf16, out16 != nullptr, t3 != nullptr);
+  switch (path) {
+    case StylePath::FUSED16:
+      return style_gemm(src, src_bf16 ? c.h16 : 0, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws, st.out_b, resid,
+                        out_scale, colscale, out, out16, c.h16, c.s);
+    case StylePath::FUSED3:
+    case StylePath::FUSED3_TAIL:
+      return style_gemm3(src, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws3, st.out_b, resid, out_scale, colscale, out,
+                         path == StylePath::FUSED3_TAIL ? *t3 : StyleTail3(), c.s);
+    case StylePath::SPLIT: {
+      MDM_TRY(style_in(src, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, src_bf16 ? c.h16 : 0, tmp, fmt16(c), c.s));
+      LinOpts o;
+      o.out_scale = out_scale, o.R1 = resid, o.colscale = colscale;
+      return linear(c, act_of(c, tmp), c.M, D, st.out, st.out_b, D, out, out16, o);
+    }
+  }
+}
 
 // the proj_out pair (fast_attention.py:121-126) as one launch of the streamed-weight kernel, in place on t4
 MdmMlpDesc proj_pair_desc(const Ctx& c, const MdmPerformer& p) {
@@ -240,67 +277,77 @@ MdmMlpDesc proj_pair_desc(const Ctx& c, const MdmPerformer& p) {
   f.r1_scale = 1.f, f.C16 = (uint16_t*)c.w.t4, f.ldc = D, f.h16 = c.h16;  // in place: a tile's rows are in LDS before its stores
   return f;
 }
-// whether performer() runs that pair / the pair AND the Performer's tail (MDM_VAR_TAIL_SPLIT: the tail as its own launches)
-bool proj_pair_fused(const Ctx& c, const MdmPerformer& p) { return c.bf && p.proj_ws; }
-bool performer_tail_fused(const Ctx& c, const MdmPerformer& p) {
-  return proj_pair_fused(c, p) && p.style.out_ws && g_variant != MDM_VAR_TAIL_SPLIT &&
-         fused_pair_style_supported(proj_pair_desc(c, p));
+// Performer proj_out: pair + the Performer's tail in one launch, the pair's rows never leave the CU (MDM_VAR_TAIL_SPLIT: not) /
+// the pair in one launch, hidden layer on chip (csrc/mlp_stream.hip) / the two Linears on pre-split rows / the two Linears
+enum class ProjPath { PAIR_TAIL, PAIR, LINEARS_X2, LINEARS };
+ProjPath proj_path(const Ctx& c, const MdmPerformer& p) {
+  if (c.bf && p.proj_ws) {
+    const MdmMlpDesc f = proj_pair_desc(c, p);
+    if (p.style.out_ws && g_variant != MDM_VAR_TAIL_SPLIT && fused_pair_style_supported(f)) return ProjPath::PAIR_TAIL;
+    if (fused_mlp_stream_supported(f)) return ProjPath::PAIR;
+  }
+  return x2_rows(c) ? ProjPath::LINEARS_X2 : ProjPath::LINEARS;
 }
 
+// Performer attention core with its q | k | v projection.  CORE3 (fp32-grade, head_dim 128): the projection's epilogue applies
+// LN(dh) / L2 into bf16 hi | lo planes, ONE launch (csrc/perf_attn3.hip) does the rest on bf16x3 products (MDM_VAR_X3_ATTN_CHAIN:
+// CHAIN).  CORE256 (16-bit, head_dim 256): the core in two launches.  CORE16_QKV (16-bit, head_dim 128): the projection inside
+// the core's launch, k and v never leave the CU (MDM_VAR_QKV_SPLIT: CORE16).  CORE16: LN/L2 -> feature maps -> KV state ->
+// num/den -> LN in ONE kernel per (batch, head).  CHAIN: five launches (MDM_VAR_GENERIC_DH256 at head_dim 256).
+enum class PerfCore { CORE3, CORE256, CORE16_QKV, CORE16, CHAIN };
+PerfCore perf_core_path(const Ctx& c, const MdmPerformer& p, bool xn16) {
+  const int D = c.m->D, H = c.m->H, dh = D / H;
+  if (c.bf && g_variant != MDM_VAR_GENERIC_DH256 && perf_attn256_supported(dh, c.S) &&
+      perf_attn256_scratch_bytes(c.B, H, c.S) <= c.M * 2 * D * (int64_t)sizeof(float))
+    return PerfCore::CORE256;
+  if (c.bf && perf_attn_supported(dh, c.S))
+    return xn16 && g_variant != MDM_VAR_QKV_SPLIT && perf_attn_qkv_supported(dh, c.S, H) ? PerfCore::CORE16_QKV : PerfCore::CORE16;
+  if (x3_flow(c) && !xn16 && g_variant != MDM_VAR_X3_ATTN_CHAIN && perf_attn3_supported(dh, c.S) && D % 32 == 0 && p.qkv.lo &&
+      p.feat.lo && (c.M * 3 * D) % 8 == 0)
+    return PerfCore::CORE3;
+  return PerfCore::CHAIN;
+}
+
+// PerformerSelfAttention (fast_attention.py:137-179): xn = pre_norm(x) already computed; out = x + 0.1*style(...)
+// pt: the caller's LayerNorms / block tail behind it (csrc/gemm.h StyleTail3) where proj_path() / style_path() say they run; the
+// 16-bit modes' pair_tail (csrc/mlp_stream.hip) writes ln_out as 16-bit rows
 int performer(const Ctx& c, const MdmPerformer& p, const float* x, Act xn, const float* sc, float* out,
-              const PerfTail& pt = PerfTail()) {
+              const StyleTail3& pt = StyleTail3()) {
   const MdmModel& m = *c.m;
   const int D = m.D, H = m.H, dh = D / H, mf = dh;  // m = min(dh, 256) = dh for dh <= 256
   const Work& w = c.w;
-  const bool fused256 = c.bf && g_variant != MDM_VAR_GENERIC_DH256 && perf_attn256_supported(dh, c.S) &&
-                        perf_attn256_scratch_bytes(c.B, H, c.S) <= c.M * 2 * D * (int64_t)sizeof(float);
-  const bool fused = fused256 || (c.bf && perf_attn_supported(dh, c.S));
-  // head_dim 128, 16-bit modes: the q | k | v projection inside the attention core's launch (csrc/perf_attn.hip phase 0: one
-  // workgroup per (batch, head) multiplies its sample's rows with its head's 384 weight rows; k and v never leave the CU).
-  // MDM_VAR_QKV_SPLIT: the projection as its own GEMM launch.
-  const bool qkv_in = fused && !fused256 && xn.bf && g_variant != MDM_VAR_QKV_SPLIT && perf_attn_qkv_supported(dh, c.S, H);
-  // fp32-grade modes, head_dim 128: the projection's epilogue applies LN(dh) / L2 and writes bf16 hi | lo planes, ONE launch
-  // (csrc/perf_attn3.hip) does features -> KV state -> num / den -> LN on bf16x3 products.  MDM_VAR_X3_ATTN_CHAIN: the five-launch
-  // chain.
-  const bool fused3 = !c.bf && c.prec == 3 && !xn.bf && g_variant != MDM_VAR_X3_ATTN_CHAIN && perf_attn3_supported(dh, c.S) &&
-                      D % 32 == 0 && p.qkv.lo && p.feat.lo && (c.M * 3 * D) % 8 == 0;
-  if (fused3) {
-    uint16_t* const xh = (uint16_t*)w.qkv;
-    uint16_t* const xl = xh + c.M * 3 * D;  // the two 16-bit planes fill the fp32 [M, 3 D] buffer exactly
-    GemmArgs g = gd(c);
-    g.A = op_f32((const float*)xn.p, D);
-    if (xn.x2) g.A.kind = OP_X2_ROW;
-    g.W = packed(p.qkv);
-    g.M = (int)c.M, g.N = 3 * D, g.K = D;
-    g.bias = p.qkv_b, g.alpha = 0.1f;
-    g.act = ACT_HEADNORM, g.hn_w = p.hn_w, g.hn_b = p.hn_b, g.hn_l2_tiles = 2 * H;
-    g.C16 = xh, g.C16_lo = xl, g.ldc = 3 * D;
-    MDM_TRY(gemm(g, c.s));
-    MDM_TRY(perf_attn3(xh, xl, p.feat.hi, p.feat.lo, (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, dh, w.t4, c.x2 ? 1 : 0, c.s));
-  }
-  const bool t4x2 = fused3 && c.x2;  // the attention rows (t4) and the projection's hidden rows (t2) travel pre-split
-  // q|k|v = 0.1 * (xn W^T + b)                                   (:145-157); bf16 when the fused attention core reads it
-  if (!qkv_in && !fused3) {
-    LinOpts o;
-    o.alpha = 0.1f;
-    MDM_TRY(linear(c, xn, c.M, D, p.qkv, p.qkv_b, 3 * D, fused ? nullptr : w.qkv, fused ? (uint16_t*)w.qkv : nullptr, o));
-  }
-  if (fused3) {
-  } else if (qkv_in) {
-    MDM_TRY(perf_attn_qkv((const uint16_t*)xn.p, p.qkv.hi, (int)p.qkv.ld, p.qkv_b, 0.1f, (uint16_t*)w.qkv, c.h16, p.feat.hi,
-                          (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, dh, (uint16_t*)w.t4, c.s));
-  } else if (fused256) {
-    // the same at head_dim 256 (big model) in two launches: feature maps (P^T resident), then KV state + num + LN per
-    // (batch, head); qphi / kphi^T / den pass through w.phi (L2 / MALL resident)
-    MDM_TRY(perf_attn256(w.qkv, c.h16, p.feat.hi, (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, (uint16_t*)w.t4, w.phi, c.s));
-  } else if (fused) {
-    // throughput mode: LN/L2 -> feature maps -> KV state -> num/den -> LN in ONE kernel per (batch, head)  (:44-90)
-    MDM_TRY(perf_attn(w.qkv, c.h16, p.feat.hi, (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, dh, (uint16_t*)w.t4, c.s));
-  } else {
-    // shared LN over head_dim, L2 normalise q,k                     (:44-55)
-    MDM_TRY(head_norm(w.qkv, c.M, H, dh, p.hn_w, p.hn_b, c.s));
-    // feature maps 0.1*exp(clamp(z P)), keys masked past length     (:58-74): rows = (token, slot<2H)
-    {
+  LinOpts qo;  // q|k|v = 0.1 * (xn W^T + b)                     (:145-157); 16-bit when a fused attention core reads it
+  qo.alpha = 0.1f;
+  Act att = act_of(c, w.t4);  // the attention rows as the core leaves them in t4
+  switch (perf_core_path(c, p, xn.bf)) {
+    case PerfCore::CORE3: {
+      uint16_t* const xh = (uint16_t*)w.qkv;
+      uint16_t* const xl = xh + c.M * 3 * D;  // the two 16-bit planes fill the fp32 [M, 3 D] buffer exactly
+      GemmArgs g = planes_gemm(c, xn, p.qkv, p.qkv_b, 3 * D, xh, xl);
+      g.alpha = 0.1f, g.act = ACT_HEADNORM, g.hn_w = p.hn_w, g.hn_b = p.hn_b, g.hn_l2_tiles = 2 * H;
+      MDM_TRY(gemm(g, c.s));
+      MDM_TRY(perf_attn3(xh, xl, p.feat.hi, p.feat.lo, (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, dh, w.t4, c.x2 ? 1 : 0, c.s));
+      att.x2 = c.x2;  // the attention rows (t4) and the projection's hidden rows (t2) travel pre-split
+      break;
+    }
+    case PerfCore::CORE256:  // feature maps (P^T resident), then KV state + num + LN per (batch, head); qphi / kphi^T / den
+                             // pass through w.phi (L2 / MALL resident)
+      MDM_TRY(linear(c, xn, c.M, D, p.qkv, p.qkv_b, 3 * D, nullptr, (uint16_t*)w.qkv, qo));
+      MDM_TRY(perf_attn256(w.qkv, c.h16, p.feat.hi, (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, (uint16_t*)w.t4, w.phi, c.s));
+      break;
+    case PerfCore::CORE16_QKV:
+      MDM_TRY(perf_attn_qkv((const uint16_t*)xn.p, p.qkv.hi, (int)p.qkv.ld, p.qkv_b, 0.1f, (uint16_t*)w.qkv, c.h16, p.feat.hi,
+                            (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, dh, (uint16_t*)w.t4, c.s));
+      break;
+    case PerfCore::CORE16:  // (:44-90)
+      MDM_TRY(linear(c, xn, c.M, D, p.qkv, p.qkv_b, 3 * D, nullptr, (uint16_t*)w.qkv, qo));
+      MDM_TRY(perf_attn(w.qkv, c.h16, p.feat.hi, (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, dh, (uint16_t*)w.t4, c.s));
+      break;
+    case PerfCore::CHAIN: {
+      MDM_TRY(linear(c, xn, c.M, D, p.qkv, p.qkv_b, 3 * D, w.qkv, nullptr, qo));
+      // shared LN over head_dim, L2 normalise q,k                     (:44-55)
+      MDM_TRY(head_norm(w.qkv, c.M, H, dh, p.hn_w, p.hn_b, c.s));
+      // feature maps 0.1*exp(clamp(z P)), keys masked past length     (:58-74): rows = (token, slot<2H)
       GemmArgs g = gd(c);
       g.A = op_f32(w.qkv, dh);
       g.A.rpg = 2 * H, g.A.gstride = 3 * D;
@@ -310,80 +357,66 @@ int performer(const Ctx& c, const MdmPerformer& p, const float* x, Act xn, const
       g.act = ACT_FEAT;
       g.feat_len = c.len, g.feat_S = c.S, g.feat_rpt = 2 * H, g.feat_kslot = H;
       MDM_TRY(gemm(g, c.s));
+      // KV^T[b,h] (dh x m) = 0.1 * sum_t v[t] (x) kphi[t]              (:77)
+      GemmArgs kv = per_head(c, heads(op_f32_kstride(w.qkv + 2 * D, 3 * D), (int64_t)c.S * 3 * D, dh),
+                             heads(op_f32_kstride(w.phi + H * mf, 2 * H * mf), (int64_t)c.S * 2 * H * mf, mf), dh, mf, c.S, mf,
+                             (int64_t)H * dh * mf, (int64_t)dh * mf);
+      kv.C = w.kvt, kv.out_scale = 0.1f;
+      MDM_TRY(gemm(kv, c.s));
+      // num = 0.1 * qphi KV                                            (:78) -> t2 (M, D) merged heads
+      GemmArgs num = per_head(c, heads(op_f32(w.phi, 2 * H * mf), (int64_t)c.S * 2 * H * mf, mf),
+                              heads(op_f32(w.kvt, mf), (int64_t)H * dh * mf, (int64_t)dh * mf), c.S, dh, mf, D, (int64_t)c.S * D, dh);
+      num.C = w.t2, num.out_scale = 0.1f;
+      MDM_TRY(gemm(num, c.s));
+      // same-t denominator, divide, LN over head_dim                   (:81-90) -> t4
+      MDM_TRY(den_ln(w.t2, w.phi, c.M, H, dh, p.hn_w, p.hn_b, w.t4, fmt16(c), c.s));
+      break;
     }
-    // KV^T[b,h] (dh x m) = 0.1 * sum_t v[t] (x) kphi[t]              (:77)
-    {
-      GemmArgs g = gd(c);
-      g.A = op_f32_kstride(w.qkv + 2 * D, 3 * D);
-      g.A.bs1 = (int64_t)c.S * 3 * D, g.A.bs2 = dh;
-      g.W = op_f32_kstride(w.phi + H * mf, 2 * H * mf);
-      g.W.bs1 = (int64_t)c.S * 2 * H * mf, g.W.bs2 = mf;
-      g.M = dh, g.N = mf, g.K = c.S;
-      g.batch = c.B * H, g.nb2 = H;
-      g.C = w.kvt, g.ldc = mf, g.c_bs1 = (int64_t)H * dh * mf, g.c_bs2 = (int64_t)dh * mf;
-      g.out_scale = 0.1f;
-      MDM_TRY(gemm(g, c.s));
-    }
-    // num = 0.1 * qphi KV                                            (:78) -> t2 (M, D) merged heads
-    {
-      GemmArgs g = gd(c);
-      g.A = op_f32(w.phi, 2 * H * mf);
-      g.A.bs1 = (int64_t)c.S * 2 * H * mf, g.A.bs2 = mf;
-      g.W = op_f32(w.kvt, mf);
-      g.W.bs1 = (int64_t)H * dh * mf, g.W.bs2 = (int64_t)dh * mf;
-      g.M = c.S, g.N = dh, g.K = mf;
-      g.batch = c.B * H, g.nb2 = H;
-      g.C = w.t2, g.ldc = D, g.c_bs1 = (int64_t)c.S * D, g.c_bs2 = dh;
-      g.out_scale = 0.1f;
-      MDM_TRY(gemm(g, c.s));
-    }
-    // same-t denominator, divide, LN over head_dim                   (:81-90) -> t4
-    MDM_TRY(den_ln(w.t2, w.phi, c.M, H, dh, p.hn_w, p.hn_b, w.t4, fmt16(c), c.s));
   }
-  // proj_out: Linear -> GELU -> Linear                             (:121-126,165)
-  const bool t16 = c.bf;  // the projection's output feeds a LayerNorm only: bf16 in throughput mode
-  bool pair = false;
-  if (proj_pair_fused(c, p)) {  // one launch, hidden layer on chip (csrc/mlp_stream.hip)
-    const MdmMlpDesc f = proj_pair_desc(c, p);
-    // ... and the tail (post_norm, stylization, out_layers.2, residual, the next block's LayerNorm) in the same launch: the
-    // pair's rows never leave the CU (MDM_VAR_TAIL_SPLIT: the tail as its own launch)
-    if (performer_tail_fused(c, p)) {
+  // proj_out: Linear -> GELU -> Linear                             (:121-126,165); its output feeds a LayerNorm only: 16 bits in
+  // the 16-bit modes
+  switch (proj_path(c, p)) {
+    case ProjPath::PAIR_TAIL: {
       PairTail t = {};
       t.pw = p.post_w, t.pb = p.post_b, t.sw = p.style.norm_w, t.sb = p.style.norm_b, t.sc = sc, t.S = c.S;
       t.ws = p.style.out_ws, t.bias = p.style.out_b, t.resid = x, t.out_scale = 0.1f, t.out = out;
-      t.lw = pt.lw, t.lb = pt.lb, t.ln16 = pt.ln16, t.skip = pt.skip, t.skip_scale = pt.skip_scale, t.l2w = pt.l2w, t.l2b = pt.l2b;
-      MDM_TRY(fused_pair_style(f, t, c.s));
-      if (pt.done) *pt.done = true;
-      return MDM_OK;
+      t.lw = pt.lw, t.lb = pt.lb, t.ln16 = (uint16_t*)pt.ln_out, t.skip = pt.skip, t.skip_scale = pt.skip_scale, t.l2w = pt.l2w, t.l2b = pt.l2b;
+      return fused_pair_style(proj_pair_desc(c, p), t, c.s);
     }
-    if (fused_mlp_stream_supported(f)) {
-      MDM_TRY(fused_mlp_stream(f, c.s));
-      pair = true;
+    case ProjPath::PAIR:
+      MDM_TRY(fused_mlp_stream(proj_pair_desc(c, p), c.s));
+      break;
+    case ProjPath::LINEARS_X2: {
+      LinOpts o;
+      o.act = ACT_GELU, o.outx2 = (uint16_t*)w.t2;
+      MDM_TRY(linear(c, att, c.M, D, p.proj0, p.proj0_b, D, nullptr, nullptr, o));
+      MDM_TRY(linear(c, Act{w.t2, false, true}, c.M, D, p.proj3, p.proj3_b, D, w.t4, nullptr));
+      break;
     }
-  }
-  if (!pair && !c.bf && c.x2) {
-    LinOpts o;
-    o.act = ACT_GELU, o.outx2 = (uint16_t*)w.t2;
-    MDM_TRY(linear(c, Act{w.t4, false, t4x2}, c.M, D, p.proj0, p.proj0_b, D, nullptr, nullptr, o));
-    MDM_TRY(linear(c, Act{w.t2, false, true}, c.M, D, p.proj3, p.proj3_b, D, w.t4, nullptr));
-  } else if (!pair) {
-    LinOpts o;
-    o.act = ACT_GELU;
-    MDM_TRY(linear_to_act(c, act_of(c, w.t4), c.M, D, p.proj0, p.proj0_b, D, w.t2, o));
-    MDM_TRY(linear(c, act_of(c, w.t2), c.M, D, p.proj3, p.proj3_b, D, t16 ? nullptr : w.t4, t16 ? (uint16_t*)w.t4 : nullptr));
+    case ProjPath::LINEARS: {
+      LinOpts o;
+      o.act = ACT_GELU;
+      MDM_TRY(linear_to_act(c, att, c.M, D, p.proj0, p.proj0_b, D, w.t2, o));
+      MDM_TRY(linear_to_act(c, act_of(c, w.t2), c.M, D, p.proj3, p.proj3_b, D, w.t4));
+      break;
+    }
   }
   // post_norm, normalize * sqrt(D), stylization, y = x + 0.1 * style (:169-178); fp32-grade modes: the caller's LayerNorms / block
-  // tail behind it in the same launch when it asks for them (pt.ln32 / pt.skip)
-  if (!c.bf && (pt.ln32 || pt.skip)) {
-    StyleTail3 t3;
-    t3.lw = pt.lw, t3.lb = pt.lb, t3.ln_out = pt.ln32, t3.skip = pt.skip, t3.skip_scale = pt.skip_scale, t3.l2w = pt.l2w, t3.l2b = pt.l2b;
-    t3.ln_x2 = pt.ln_x2;
-    bool did = false;
-    MDM_TRY(style_apply(c, p.style, w.t4, p.post_w, p.post_b, nullptr, sc, w.t2, x, 0.1f, nullptr, out, nullptr, t16, &t3, &did));
-    if (pt.done) *pt.done = did;
-    return MDM_OK;
-  }
-  return style_apply(c, p.style, w.t4, p.post_w, p.post_b, nullptr, sc, w.t2, x, 0.1f, nullptr, out, nullptr, t16);
+  // tail behind it in the same launch when it asks for them (pt.ln_out / pt.skip)
+  const bool tail3 = !c.bf && (pt.ln_out || pt.skip);
+  return style_apply(c, p.style, w.t4, p.post_w, p.post_b, nullptr, sc, w.t2, x, 0.1f, nullptr, out, nullptr, c.bf,
+                     tail3 ? &pt : nullptr);
+}
+
+// DualSelfAttentionBlock's tail inside its Performers' launches: T16 where both Performers end in the pair + tail launch
+// (16-bit modes, D = 512), T3 where both stylizations take a tail (fp32-grade modes: style_gemm3); NONE: its own launches
+enum class DualTail { NONE, T16, T3 };
+DualTail dual_tail_path(const Ctx& c, const MdmLayer& l) {
+  if (proj_path(c, l.local) == ProjPath::PAIR_TAIL && proj_path(c, l.global) == ProjPath::PAIR_TAIL) return DualTail::T16;
+  if (style_path(c, l.local.style, false, false, true) == StylePath::FUSED3_TAIL &&
+      style_path(c, l.global.style, false, false, true) == StylePath::FUSED3_TAIL)
+    return DualTail::T3;
+  return DualTail::NONE;
 }
 
 // DualSelfAttentionBlock (fast_attention.py:208-226): x -> out.  Uses t1..t5.  x16: bf16 shadow of x (throughput mode)
@@ -394,52 +427,57 @@ int dual_block(const Ctx& c, const MdmLayer& l, const float* x, const uint16_t* 
   const int D = c.m->D;
   const Work& w = c.w;
   const int64_t scs = (int64_t)c.B * 2 * D;
-  // With the Performers' tails fused into their projection launches (16-bit modes, D = 512) the block's own tail goes there too:
-  // skip = GELU(Lin(x)) is computed FIRST (into the FFN's hidden buffer, free during this block), and the second Performer's
-  // launch ends with out = post_norm(skip + 0.1 * global_out) and the next block's pre-norm -- no D x D GEMM waiting behind the
-  // attention chain, no LayerNorm launch behind that.
-  const bool tails = performer_tail_fused(c, l.local) && performer_tail_fused(c, l.global);
-  // fp32-grade modes: the same re-ordering with the tails inside the stylization launches (style_gemm3): MDM_VAR_X3_STYLE_SPLIT /
-  // MDM_VAR_X3_TAILS_SPLIT undo it
-  const bool tails3 = !c.bf && c.prec == 3 && g_variant != MDM_VAR_X3_STYLE_SPLIT && g_variant != MDM_VAR_X3_TAILS_SPLIT &&
-                      l.local.style.out_ws3 && l.global.style.out_ws3 && style_gemm_supported(D, c.M);
-  float* const skipbuf = w.f1;
-  if (tails || tails3) {
-    LinOpts o;
-    o.act = ACT_GELU;
-    MDM_TRY(linear(c, tails ? act_bf16(x16) : act_f32(x), c.M, D, l.skip, l.skip_b, D, skipbuf, nullptr, o));
+  const int xnf = fmt_xn(c);  // format of the pre-normed rows the q | k | v projections read
+  const Act xa = c.bf ? act_bf16(x16) : act_f32(x);
+  LinOpts so;  // skip = GELU(Lin(x))                                (:219-225)
+  so.act = ACT_GELU;
+  switch (dual_tail_path(c, l)) {
+    case DualTail::T16:
+    case DualTail::T3: {
+      // skip is computed FIRST (into the FFN's hidden buffer, free during this block), and the second Performer's launch ends
+      // with out = post_norm(skip + 0.1 * global_out) and the next block's pre-norm -- no D x D GEMM waiting behind the
+      // attention chain, no LayerNorm launch behind that
+      MDM_TRY(linear(c, xa, c.M, D, l.skip, l.skip_b, D, w.f1, nullptr, so));
+      // h = pre_norm(x) -> t1 ; local.pre_norm(h) -> t3
+      MDM_TRY(ln_chain(x, c.M, D, l.dual_pre_w, l.dual_pre_b, w.t1, 0, l.local.pre_w, l.local.pre_b, w.t3, xnf, c.s));
+      StyleTail3 pt;  // local_out -> t5, global.pre_norm(local_out) -> t3 (t3 is dead by then)
+      pt.lw = l.global.pre_w, pt.lb = l.global.pre_b, pt.ln_out = w.t3, pt.ln_x2 = c.x2;
+      MDM_TRY(performer(c, l.local, w.t1, act_x2(c, w.t3), sc4 + 0 * scs, w.t5, pt));
+      StyleTail3 bt;
+      bt.skip = w.f1, bt.skip_scale = 0.1f, bt.lw = l.dual_post_w, bt.lb = l.dual_post_b;
+      if (next_w) bt.l2w = next_w, bt.l2b = next_b, bt.ln_out = w.t2, bt.ln_x2 = c.x2;
+      return performer(c, l.global, w.t5, act_x2(c, w.t3), sc4 + 1 * scs, out, bt);
+    }
+    case DualTail::NONE: {
+      MDM_TRY(ln_chain(x, c.M, D, l.dual_pre_w, l.dual_pre_b, w.t1, 0, l.local.pre_w, l.local.pre_b, w.t3, xnf, c.s));
+      // local_out -> t5; a local Performer that ends in the pair + tail launch also leaves global.pre_norm(local_out) in t3
+      const bool normed = proj_path(c, l.local) == ProjPath::PAIR_TAIL;
+      StyleTail3 pt;
+      if (normed) pt.lw = l.global.pre_w, pt.lb = l.global.pre_b, pt.ln_out = w.t3;
+      MDM_TRY(performer(c, l.local, w.t1, act_x2(c, w.t3), sc4 + 0 * scs, w.t5, pt));
+      if (!normed) MDM_TRY(ln_chain(w.t5, c.M, D, l.global.pre_w, l.global.pre_b, w.t3, xnf, nullptr, nullptr, nullptr, 0, c.s));
+      MDM_TRY(performer(c, l.global, w.t5, act_x2(c, w.t3), sc4 + 1 * scs, w.t1));  // global_out -> t1
+      // out = post_norm(skip + 0.1 * global); fp32 on purpose: this sum is the block's output before its final LayerNorm
+      // (storing it as bf16 measured +60 % block error for 0.01 ms per step)
+      so.R1 = w.t1, so.r1_scale = 0.1f;
+      MDM_TRY(linear(c, xa, c.M, D, l.skip, l.skip_b, D, w.t3, nullptr, so));
+      return ln_chain(w.t3, c.M, D, l.dual_post_w, l.dual_post_b, out, 0, next_w, next_b, next_w ? w.t2 : nullptr, xnf, c.s);
+    }
   }
-  // h = pre_norm(x) -> t1 ; local.pre_norm(h) -> t3
-  const int xnf = (!c.bf && c.x2) ? 4 : fmt16(c);  // format of the pre-normed rows the q | k | v projections read (4 = pre-split rows)
-  MDM_TRY(ln_chain(x, c.M, D, l.dual_pre_w, l.dual_pre_b, w.t1, 0, l.local.pre_w, l.local.pre_b, w.t3, xnf, c.s));
-  bool normed = false;  // local_out -> t5; the fused tail also leaves global.pre_norm(local_out) in t3 (t3 is dead by then)
-  {
-    PerfTail pt;
-    if (c.bf) pt.lw = l.global.pre_w, pt.lb = l.global.pre_b, pt.ln16 = (uint16_t*)w.t3, pt.done = &normed;
-    if (tails3) pt.lw = l.global.pre_w, pt.lb = l.global.pre_b, pt.ln32 = w.t3, pt.ln_x2 = c.x2, pt.done = &normed;
-    MDM_TRY(performer(c, l.local, w.t1, act_x2(c, w.t3), sc4 + 0 * scs, w.t5, pt));
-  }
-  if (!normed) MDM_TRY(ln_chain(w.t5, c.M, D, l.global.pre_w, l.global.pre_b, w.t3, xnf, nullptr, nullptr, nullptr, 0, c.s));
-  if ((tails || tails3) && normed) {
-    bool done = false;
-    PerfTail pt;
-    pt.skip = skipbuf, pt.skip_scale = 0.1f, pt.lw = l.dual_post_w, pt.lb = l.dual_post_b, pt.done = &done;
-    if (next_w && tails) pt.l2w = next_w, pt.l2b = next_b, pt.ln16 = (uint16_t*)w.t2;
-    if (next_w && tails3) pt.l2w = next_w, pt.l2b = next_b, pt.ln32 = w.t2, pt.ln_x2 = c.x2;
-    MDM_TRY(performer(c, l.global, w.t5, act_x2(c, w.t3), sc4 + 1 * scs, out, pt));
-    if (done) return MDM_OK;
-    return MDM_ERR_LAUNCH;  // (unreachable: performer_tail_fused said the tail runs)
-  }
-  MDM_TRY(performer(c, l.global, w.t5, act_x2(c, w.t3), sc4 + 1 * scs, w.t1));  // global_out -> t1
-  // skip = GELU(Lin(x)); out = post_norm(skip + 0.1 * global)      (:219-225)
-  {
-    LinOpts o;
-    o.act = ACT_GELU, o.R1 = w.t1, o.r1_scale = 0.1f;
-    // fp32 on purpose: this sum is the block's output before its final LayerNorm (storing it as bf16 measured +60 % block
-    // error for 0.01 ms per step)
-    MDM_TRY(linear(c, c.bf ? act_bf16(x16) : act_f32(x), c.M, D, l.skip, l.skip_b, D, w.t3, nullptr, o));
-  }
-  return ln_chain(w.t3, c.M, D, l.dual_post_w, l.dual_post_b, out, 0, next_w, next_b, next_w ? w.t2 : nullptr, xnf, c.s);
+}
+
+// Linear cross-attention.  CORE3 (fp32-grade, head_dim 128): the head_dim softmax is the query projection's epilogue (bf16 hi |
+// lo planes), the product with A[b, h] one launch on bf16x3 MFMAs (MDM_VAR_X3_XATTN_CHAIN: CHAIN).  CORE_Q (16-bit, head_dim
+// 128): the query projection inside the core's launch (MDM_VAR_XQ_SPLIT: CORE).  CORE: projection, 16-bit core
+// (MDM_VAR_GENERIC_DH256 at head_dim 256: CHAIN).  CHAIN: GEMM, head_softmax, batched contraction.
+enum class XattnPath { CORE3, CORE_Q, CORE, CHAIN };
+XattnPath lin_xattn_path(const Ctx& c, const MdmLayer& l) {
+  const int D = c.m->D, H = c.m->H, dh = D / H;
+  if (c.bf && lin_xattn_supported(dh) && !(dh == 256 && g_variant == MDM_VAR_GENERIC_DH256))
+    return g_variant != MDM_VAR_XQ_SPLIT && D == 512 && lin_xattn_q_supported(dh, c.S, H) ? XattnPath::CORE_Q : XattnPath::CORE;
+  if (x3_flow(c) && g_variant != MDM_VAR_X3_XATTN_CHAIN && xattn3_supported(dh, 1) && l.ca_q.lo && D % 32 == 0 && (c.M * D) % 8 == 0)
+    return XattnPath::CORE3;
+  return XattnPath::CHAIN;
 }
 
 // GatedCrossAttention (fast_attention.py:242-272): out = x + sigmoid(gate)*sigmoid(adaptive)*style(softmax(q) A)
@@ -448,51 +486,71 @@ int cross_block(const Ctx& c, const MdmLayer& l, const float* at, const float* x
   const MdmModel& m = *c.m;
   const int D = m.D, H = m.H, dh = D / H;
   const Work& w = c.w;
-  if (!pre_normed) MDM_TRY(ln_chain(x, c.M, D, l.ca_norm_w, l.ca_norm_b, w.t2, (!c.bf && c.x2) ? 4 : fmt16(c), nullptr, nullptr, nullptr, 0, c.s));
-  const bool fused = c.bf && lin_xattn_supported(dh) && !(dh == 256 && g_variant == MDM_VAR_GENERIC_DH256);
-  // head_dim 128: the query projection inside the attention launch (csrc/xattn.hip lin_xattn_q; MDM_VAR_XQ_SPLIT: its own GEMM launch)
-  const bool q_in = fused && g_variant != MDM_VAR_XQ_SPLIT && D == 512 && lin_xattn_q_supported(dh, c.S, H);
-  // fp32-grade modes, head_dim 128: the head_dim softmax is the query projection's epilogue (bf16 hi | lo planes), the product with
-  // A[b, h] one launch on bf16x3 MFMAs (csrc/xattn3.hip).  MDM_VAR_X3_XATTN_CHAIN: the chain (GEMM, head_softmax, batched
-  // contraction).
-  const bool fused3 = !c.bf && c.prec == 3 && g_variant != MDM_VAR_X3_XATTN_CHAIN && xattn3_supported(dh, 1) && l.ca_q.lo &&
-                      D % 32 == 0 && (c.M * D) % 8 == 0;
-  if (fused3) {
-    uint16_t* const qh = (uint16_t*)w.t3;
-    uint16_t* const ql = qh + c.M * D;  // the two planes fill the fp32 [M, D] buffer exactly
-    GemmArgs g = gd(c);
-    g.A = op_f32(w.t2, D);
-    if (c.x2) g.A.kind = OP_X2_ROW;
-    g.W = packed(l.ca_q);
-    g.M = (int)c.M, g.N = D, g.K = D;
-    g.bias = l.ca_q_b, g.act = ACT_HEADSOFTMAX;
-    g.C16 = qh, g.C16_lo = ql, g.ldc = D;
-    MDM_TRY(gemm(g, c.s));
-    MDM_TRY(lin_xattn3(qh, ql, at, c.B, c.S, H, dh, w.t4, c.s));
-    return style_apply(c, l.ca_style, w.t4, nullptr, nullptr, nullptr, sc, w.t2, x, 1.f, l.ca_gvec, out, nullptr, false);
-  }
-  if (!q_in) MDM_TRY(linear(c, act_x2(c, w.t2), c.M, D, l.ca_q, l.ca_q_b, D, fused ? nullptr : w.t3, fused ? (uint16_t*)w.t3 : nullptr));
-  // the fused forms' output is consumed by the stylization LayerNorm only: 16-bit
-  if (q_in) {
-    MDM_TRY(lin_xattn_q((const uint16_t*)w.t2, l.ca_q.hi, (int)l.ca_q.ld, l.ca_q_b, at, c.B, c.S, H, dh, nullptr, (uint16_t*)w.t4,
-                        c.h16, c.s));
-  } else if (fused) {
-    MDM_TRY(lin_xattn(w.t3, c.h16, at, c.B, c.S, H, dh, nullptr, (uint16_t*)w.t4, c.h16, c.s));  // (:248,253)
-  } else {
-    MDM_TRY(head_softmax(w.t3, c.M * H, dh, c.s));  // softmax over head_dim (:248)
-    {
-      GemmArgs g = gd(c);  // y[b,s,h,:] = q[b,s,h,:] A[b,h]  (:253), W = A^T rows
-      g.A = op_f32(w.t3, D);
-      g.A.bs1 = (int64_t)c.S * D, g.A.bs2 = dh;
-      g.W = op_f32(at, dh);
-      g.W.bs1 = (int64_t)H * dh * dh, g.W.bs2 = (int64_t)dh * dh;
-      g.M = c.S, g.N = dh, g.K = dh;
-      g.batch = c.B * H, g.nb2 = H;
-      g.C = w.t4, g.ldc = D, g.c_bs1 = (int64_t)c.S * D, g.c_bs2 = dh;
+  if (!pre_normed) MDM_TRY(ln_chain(x, c.M, D, l.ca_norm_w, l.ca_norm_b, w.t2, fmt_xn(c), nullptr, nullptr, nullptr, 0, c.s));
+  bool y16 = false;  // the core's output (t4) is 16-bit: it is consumed by the stylization LayerNorm only
+  switch (lin_xattn_path(c, l)) {
+    case XattnPath::CORE3: {
+      uint16_t* const qh = (uint16_t*)w.t3;
+      uint16_t* const ql = qh + c.M * D;  // the two planes fill the fp32 [M, D] buffer exactly
+      GemmArgs g = planes_gemm(c, act_x2(c, w.t2), l.ca_q, l.ca_q_b, D, qh, ql);
+      g.act = ACT_HEADSOFTMAX;
       MDM_TRY(gemm(g, c.s));
+      MDM_TRY(lin_xattn3(qh, ql, at, c.B, c.S, H, dh, w.t4, c.s));
+      break;
+    }
+    case XattnPath::CORE_Q:
+      MDM_TRY(lin_xattn_q((const uint16_t*)w.t2, l.ca_q.hi, (int)l.ca_q.ld, l.ca_q_b, at, c.B, c.S, H, dh, nullptr, (uint16_t*)w.t4,
+                          c.h16, c.s));
+      y16 = true;
+      break;
+    case XattnPath::CORE:
+      MDM_TRY(linear(c, act_x2(c, w.t2), c.M, D, l.ca_q, l.ca_q_b, D, nullptr, (uint16_t*)w.t3));
+      MDM_TRY(lin_xattn(w.t3, c.h16, at, c.B, c.S, H, dh, nullptr, (uint16_t*)w.t4, c.h16, c.s));  // (:248,253)
+      y16 = true;
+      break;
+    case XattnPath::CHAIN: {
+      MDM_TRY(linear(c, act_x2(c, w.t2), c.M, D, l.ca_q, l.ca_q_b, D, w.t3, nullptr));
+      MDM_TRY(head_softmax(w.t3, c.M * H, dh, c.s));  // softmax over head_dim (:248)
+      // y[b,s,h,:] = q[b,s,h,:] A[b,h]  (:253), W = A^T rows
+      GemmArgs g = per_head(c, heads(op_f32(w.t3, D), (int64_t)c.S * D, dh), heads(op_f32(at, dh), (int64_t)H * dh * dh, (int64_t)dh * dh),
+                            c.S, dh, dh, D, (int64_t)c.S * D, dh);
+      g.C = w.t4;
+      MDM_TRY(gemm(g, c.s));
+      break;
     }
   }
-  return style_apply(c, l.ca_style, w.t4, nullptr, nullptr, nullptr, sc, w.t2, x, 1.f, l.ca_gvec, out, nullptr, fused);
+  return style_apply(c, l.ca_style, w.t4, nullptr, nullptr, nullptr, sc, w.t2, x, 1.f, l.ca_gvec, out, nullptr, y16);
+}
+
+// one grouped expert GEMM: rows of A [., K] in the mode's expert-operand form (e4m3, 16-bit, pre-split or fp32 rows) times
+// W_e^T + b_e, per expert's rows (w.goff); the caller adds the rest of the epilogue and the output
+GemmArgs expert_gemm(const Ctx& c, const void* A, int K, const MdmPacked& W, const float* bias, int N) {
+  GemmArgs g = gd(c);
+  if (c.fp8) {  // W's channel scales live in its lo plane (packing)
+    g.A.p = A, g.A.ld = K, g.A.kind = MDM_OP_FP8_ROW;
+    g.W.p = W.hi, g.W.ld = W.ld, g.W.kind = MDM_OP_FP8_ROW, g.w_scale = (const float*)W.lo;
+  } else if (mlp16(c)) {
+    g.A.p = A, g.A.ld = K, g.A.kind = OP_BF16_ROW, g.precision = 1;
+    g.W = packed(W);
+  } else {
+    g.A = op_f32((const float*)A, K);
+    if (mlp_x2(c)) g.A.kind = OP_X2_ROW;
+    g.W = packed(W);
+  }
+  g.W.bs1 = (int64_t)N * W.ld;
+  g.goff = c.w.goff, g.ngroups = 2 * c.m->E;
+  g.M = (int)(4 * c.M), g.N = N, g.K = K;
+  g.bias = bias, g.bias_bs = N;
+  g.ldc = N;
+  // pre-split rows and a fragment pair stream of W: the streamed-weight bf16x3 kernel (csrc/gemm_stream3.hip)
+  if (mlp_x2(c) && W.ws) g.w_stream = W.ws, g.w_stream_gs = gemm_stream3x_group_elems(N, K);
+  return g;
+}
+// MoE experts: e4m3 operands (precision 5) / both expert GEMMs in one launch (f) on 16-bit operands / two grouped GEMMs
+enum class MoePath { FP8, FUSED, GROUPED };
+MoePath moe_path(const Ctx& c, const MdmMlpDesc& f) {
+  if (c.fp8) return MoePath::FP8;
+  return mlp16(c) && fused_mlp_supported(f) ? MoePath::FUSED : MoePath::GROUPED;
 }
 
 // MoEMultiBranchFFN (multi_branch.py:52-61) with SwitchMoELayer top-2 routing (switch_moe.py:44-111)
@@ -507,8 +565,7 @@ int moe_block(const Ctx& c, const MdmLayer& l, const float* x, const float* sc, 
     p.gate_w[b] = l.gate_w[b], p.gate_b[b] = l.gate_b[b];
     p.usage[b] = l.usage[b], p.importance[b] = l.importance[b];
   }
-  const bool hx2 = !c.bf && !c.mix && c.x2 && D % 64 == 0;  // fp32-grade experts: LN rows and hidden rows pre-split for the two GEMMs
-  p.hn = w.hn, p.hn_bf16 = c.fp8 ? 3 : (hx2 ? 4 : fmt_mlp(c)), p.hn_scale = w.hn_scale, p.top_idx = w.top_idx, p.top_val = w.top_val, p.hist = w.hist, p.uimp = w.uimp, p.forced_idx = forced;
+  p.hn = w.hn, p.hn_bf16 = c.fp8 ? 3 : fmt_mlp(c), p.hn_scale = w.hn_scale, p.top_idx = w.top_idx, p.top_val = w.top_val, p.hist = w.hist, p.uimp = w.uimp, p.forced_idx = forced;
   MDM_TRY(moe_route(x, c.M, D, E, p, w.goff, w.cursor, w.perm, w.rowscale, w.pos4, c.s));
   if (route_out && hipMemcpyAsync(route_out, w.top_idx, 4 * c.M * sizeof(int32_t), hipMemcpyDeviceToDevice, c.s) != hipSuccess)
     return MDM_ERR_LAUNCH;
@@ -522,96 +579,42 @@ int moe_block(const Ctx& c, const MdmLayer& l, const float* x, const float* sc, 
   f.C = w.y2, f.ldc = D;
   f.h16 = c.h16;
   f.wstream = l.wstream, f.wstream_gs = l.wstream_gs;
-  const bool h = c.bf || c.mix;  // 16-bit expert operands
-  if (c.fp8) {
-    // fp8 experts (switch_moe.py:19-25,104-109 on e4m3 operands): hidden = e4m3(8 * GELU(dequant(X8 W1_8^T) + b1)), then
-    // y2 = prob * (dequant(hidden8 W2_8^T) / 8 + b2).  Row scales come from the router kernel, channel scales from packing.
-    const float HS = 8.f;  // static hidden scale: GELU outputs of O(1) land in e4m3's normal range [2^-6, 448]
-    {
-      GemmArgs g8 = gd(c);
-      g8.A.p = w.hn, g8.A.ld = D, g8.A.kind = MDM_OP_FP8_ROW, g8.A.gather = w.perm;
-      g8.W.p = l.w1.hi, g8.W.ld = l.w1.ld, g8.W.kind = MDM_OP_FP8_ROW, g8.W.bs1 = (int64_t)F * l.w1.ld;
-      g8.a_scale = w.hn_scale, g8.w_scale = (const float*)l.w1.lo;
-      g8.goff = w.goff, g8.ngroups = 2 * E;
-      g8.M = (int)(4 * c.M), g8.N = F, g8.K = D;
-      g8.bias = l.b1, g8.bias_bs = F, g8.act = ACT_GELU;
-      g8.C8 = (uint8_t*)w.hid, g8.c8_scale = HS, g8.ldc = F;
-      MDM_TRY(gemm(g8, c.s));
+  switch (moe_path(c, f)) {
+    case MoePath::FP8: {
+      // fp8 experts (switch_moe.py:19-25,104-109 on e4m3 operands): hidden = e4m3(8 * GELU(dequant(X8 W1_8^T) + b1)), then
+      // y2 = prob * (dequant(hidden8 W2_8^T) / 8 + b2).  Row scales come from the router kernel, channel scales from packing.
+      const float HS = 8.f;  // static hidden scale: GELU outputs of O(1) land in e4m3's normal range [2^-6, 448]
+      GemmArgs g1 = expert_gemm(c, w.hn, D, l.w1, l.b1, F);
+      g1.A.gather = w.perm, g1.a_scale = w.hn_scale, g1.act = ACT_GELU, g1.C8 = (uint8_t*)w.hid, g1.c8_scale = HS;
+      MDM_TRY(gemm(g1, c.s));
+      GemmArgs g2 = expert_gemm(c, w.hid, F, l.w2, l.b2, D);
+      g2.a_scale_u = 1.f / HS, g2.rowscale = w.rowscale, g2.C16 = (uint16_t*)w.y2;
+      MDM_TRY(gemm(g2, c.s));
+      return style_apply(c, l.ffn_style, w.y2, nullptr, nullptr, w.pos4, sc, w.t2, x, 1.f, nullptr, out, out16, true);
     }
-    {
-      GemmArgs g8 = gd(c);
-      g8.A.p = w.hid, g8.A.ld = F, g8.A.kind = MDM_OP_FP8_ROW;
-      g8.W.p = l.w2.hi, g8.W.ld = l.w2.ld, g8.W.kind = MDM_OP_FP8_ROW, g8.W.bs1 = (int64_t)D * l.w2.ld;
-      g8.a_scale_u = 1.f / HS, g8.w_scale = (const float*)l.w2.lo;
-      g8.goff = w.goff, g8.ngroups = 2 * E;
-      g8.M = (int)(4 * c.M), g8.N = D, g8.K = F;
-      g8.bias = l.b2, g8.bias_bs = D;
-      g8.rowscale = w.rowscale;
-      g8.C16 = (uint16_t*)w.y2, g8.ldc = D;
-      MDM_TRY(gemm(g8, c.s));
+    case MoePath::FUSED: {  // hidden activations stay in LDS (switch_moe.py:19-25,104-109)
+      if (c.bf) f.C = nullptr, f.C16 = (uint16_t*)w.y2;  // expert outputs stored in 16 bits (what autocast does to a Linear); mixed mode: fp32
+      MDM_TRY(probe_begin(c.s));
+      MDM_TRY(fused_mlp(f, c.s));
+      MDM_TRY(probe_end(c.s, f.M));
+      return style_apply(c, l.ffn_style, w.y2, nullptr, nullptr, w.pos4, sc, w.t2, x, 1.f, nullptr, out, out16, c.bf);
     }
-    return style_apply(c, l.ffn_style, w.y2, nullptr, nullptr, w.pos4, sc, w.t2, x, 1.f, nullptr, out, out16, true);
-  }
-  if (h && fused_mlp_supported(f)) {
-    // throughput mode: both expert GEMMs in one kernel, hidden activations stay in LDS (switch_moe.py:19-25,104-109)
-    const bool y16 = c.bf;  // expert outputs stored in 16 bits (what autocast does to a Linear); mixed mode: fp32
-    if (y16) f.C = nullptr, f.C16 = (uint16_t*)w.y2;
-    const bool pr = g_probe.on && g_probe.n < PROBE_MAX;
-    if (pr && hipEventRecord(g_probe.a[g_probe.n], c.s) != hipSuccess) return MDM_ERR_LAUNCH;
-    MDM_TRY(fused_mlp(f, c.s));
-    if (pr) {
-      if (hipEventRecord(g_probe.b[g_probe.n], c.s) != hipSuccess) return MDM_ERR_LAUNCH;
-      g_probe.rows[g_probe.n++] = f.M;
+    case MoePath::GROUPED: {  // bracketed for the measurement probe like the fused kernel
+      MDM_TRY(probe_begin(c.s));
+      GemmArgs g1 = expert_gemm(c, w.hn, D, l.w1, l.b1, F);  // hidden = GELU(LN_b(x)[routed rows] W1_e^T + b1_e)
+      g1.A.gather = w.perm, g1.act = ACT_GELU;
+      if (mlp16(c)) g1.C16 = (uint16_t*)w.hid;
+      else if (mlp_x2(c)) g1.Cx2 = (uint16_t*)w.hid;
+      else g1.C = w.hid;
+      MDM_TRY(gemm(g1, c.s));
+      GemmArgs g2 = expert_gemm(c, w.hid, F, l.w2, l.b2, D);  // y2[pos] = prob[pos] * (hidden W2_e^T + b2_e)      (switch_moe.py:108-109)
+      g2.rowscale = w.rowscale, g2.C = w.y2;  // fp32: the four routed rows of a token are summed in the stylization kernel
+      MDM_TRY(gemm(g2, c.s));
+      MDM_TRY(probe_end(c.s, (int)(4 * c.M)));
+      // mean of the two branches (each the sum of its two routed rows), stylization, residual
+      return style_apply(c, l.ffn_style, w.y2, nullptr, nullptr, w.pos4, sc, w.t2, x, 1.f, nullptr, out, out16, false);
     }
-    return style_apply(c, l.ffn_style, w.y2, nullptr, nullptr, w.pos4, sc, w.t2, x, 1.f, nullptr, out, out16, y16);
   }
-  // measurement probe of the fp32-grade modes: the expert MLP as its two grouped GEMMs, bracketed like the fused kernel above
-  const bool pr2 = g_probe.on && g_probe.n < PROBE_MAX;
-  if (pr2 && hipEventRecord(g_probe.a[g_probe.n], c.s) != hipSuccess) return MDM_ERR_LAUNCH;
-  {
-    GemmArgs g = gd(c);  // hidden = GELU(LN_b(x)[routed rows] W1_e^T + b1_e)
-    if (h) {
-      g.A.p = w.hn, g.A.ld = D, g.A.kind = OP_BF16_ROW, g.precision = 1;
-    } else {
-      g.A = op_f32(w.hn, D);
-      if (hx2) g.A.kind = OP_X2_ROW;
-    }
-    g.A.gather = w.perm;
-    g.W = packed(l.w1);
-    g.W.bs1 = (int64_t)F * l.w1.ld;
-    g.goff = w.goff, g.ngroups = 2 * E;
-    g.M = (int)(4 * c.M), g.N = F, g.K = D;
-    g.bias = l.b1, g.bias_bs = F;
-    g.act = ACT_GELU;
-    g.C = (h || hx2) ? nullptr : w.hid, g.C16 = h ? (uint16_t*)w.hid : nullptr, g.ldc = F;
-    if (hx2) g.Cx2 = (uint16_t*)w.hid;
-    if (hx2 && l.w1.ws) g.w_stream = l.w1.ws, g.w_stream_gs = gemm_stream3x_group_elems(F, D);  // streamed-weight bf16x3 kernel (csrc/gemm_stream3.hip)
-    MDM_TRY(gemm(g, c.s));
-  }
-  {
-    GemmArgs g = gd(c);  // y2[pos] = prob[pos] * (hidden W2_e^T + b2_e)      (switch_moe.py:108-109)
-    if (h) {
-      g.A.p = w.hid, g.A.ld = F, g.A.kind = OP_BF16_ROW, g.precision = 1;
-    } else {
-      g.A = op_f32(w.hid, F);
-      if (hx2) g.A.kind = OP_X2_ROW;
-    }
-    g.W = packed(l.w2);
-    g.W.bs1 = (int64_t)D * l.w2.ld;
-    g.goff = w.goff, g.ngroups = 2 * E;
-    g.M = (int)(4 * c.M), g.N = D, g.K = F;
-    g.bias = l.b2, g.bias_bs = D;
-    g.rowscale = w.rowscale;
-    g.C = w.y2, g.ldc = D;  // fp32: the four routed rows of a token are summed in the stylization kernel
-    if (hx2 && l.w2.ws) g.w_stream = l.w2.ws, g.w_stream_gs = gemm_stream3x_group_elems(D, F);
-    MDM_TRY(gemm(g, c.s));
-  }
-  if (pr2) {
-    if (hipEventRecord(g_probe.b[g_probe.n], c.s) != hipSuccess) return MDM_ERR_LAUNCH;
-    g_probe.rows[g_probe.n++] = f.M;
-  }
-  // mean of the two branches (each the sum of its two routed rows), stylization, residual
-  return style_apply(c, l.ffn_style, w.y2, nullptr, nullptr, w.pos4, sc, w.t2, x, 1.f, nullptr, out, out16, false);
 }
 
 // Passes the folded text cross-attention (csrc/sdfold.hip) takes, 0 = use the GEMM chain.  Measured end to end (configs[1],
@@ -631,99 +634,94 @@ struct SdFold {  // folded text side of one layer (MdmTextCache.sd_kfold / sd_cb
   const uint16_t* vfold = nullptr;
 };
 
+// Text cross-attention.  FOLD_PAIR / FOLD (16-bit): query GEMM + attention core + output GEMM + LayerNorm in one launch
+// (csrc/sdfold.hip), then the 4x FFN pair in one launch (f) / as two GEMMs.  The pair at the full time scale only: at the half
+// scale of the bench batch (6272 rows -> 32-row tiles, every workgroup streams the pair's 4 MB for 32 rows) it measures slower
+// than the two GEMMs (78 vs 66 us; 100 vs 120 us at 12544 rows).  The choice is made on the FRAME count of the scale, never on
+// the batch: a sample's result must not depend on the batch it travels in (shard invariance, cond | uncond batching).
+// CORE3 (fp32-grade, head_dim 128): query as bf16 hi | lo planes, scores / softmax / PV one launch on bf16x3 MFMAs
+// (MDM_VAR_X3_XATTN_CHAIN: CHAIN).  CORE (16-bit): scores, softmax, PV in one launch (MDM_VAR_GENERIC_DH256 at head_dim 256:
+// CHAIN).  CHAIN: two batched contractions around a row softmax.
+enum class SdPath { FOLD_PAIR, FOLD, CORE3, CORE, CHAIN };
+SdPath sd_path(const Ctx& c, const MdmLayer& l, const SdFold& fold, const MdmMlpDesc& f) {
+  const int D = c.m->D, H = c.m->H, dh = D / H, N = c.N;
+  if (c.bf && fold.kfold && g_variant != MDM_VAR_SD_UNFOLDED && sd_fold_policy(D, H, N) > 0)
+    return l.sd_ffn_ws && c.S >= 128 && fused_mlp_stream_supported(f) ? SdPath::FOLD_PAIR : SdPath::FOLD;
+  if (x3_flow(c) && g_variant != MDM_VAR_X3_XATTN_CHAIN && xattn3_supported(dh, N) && l.sd_q.lo && D % 32 == 0 && (c.M * D) % 8 == 0)
+    return SdPath::CORE3;
+  if (c.bf && xattn_supported(dh, N) && !(dh == 256 && g_variant == MDM_VAR_GENERIC_DH256)) return SdPath::CORE;
+  return SdPath::CHAIN;
+}
+
+// the 4x FFN (LayerNorm rows in t4 -> Linear -> GELU -> Linear) as two GEMMs: out = x + (o + ffn(o)), o in t3.  16-bit operands
+// in the throughput AND the mixed mode; in the fp32-grade mode the hidden rows are written pre-split for the GEMM that reads them
+int sd_ffn(const Ctx& c, const MdmLayer& l, const float* x, float* out, uint16_t* out16) {
+  const int D = c.m->D;
+  const Work& w = c.w;
+  const bool h = mlp16(c), x2 = mlp_x2(c);
+  LinOpts o1;
+  o1.act = ACT_GELU;
+  if (x2) o1.outx2 = (uint16_t*)w.f1;
+  MDM_TRY(linear(c, Act{w.t4, h, x2}, c.M, D, l.sd_f1, l.sd_f1_b, 4 * D, (h || x2) ? nullptr : w.f1, h ? (uint16_t*)w.f1 : nullptr, o1));
+  LinOpts o;
+  o.R1 = x, o.R2 = w.t3;
+  return linear(c, Act{w.f1, h, x2}, c.M, 4 * D, l.sd_f2, l.sd_f2_b, D, out, out16, o);
+}
+
 int sdcross_block(const Ctx& c, const MdmLayer& l, const float* kc, const float* vc, const float* x, const uint16_t* x16,
                   float* out, uint16_t* out16, const SdFold& fold = SdFold()) {
   const MdmModel& m = *c.m;
   const int D = m.D, H = m.H, dh = D / H, N = c.N;
   const Work& w = c.w;
-  if (c.bf && fold.kfold && g_variant != MDM_VAR_SD_UNFOLDED && sd_fold_policy(D, H, N) > 0) {
-    // throughput mode: query GEMM + attention core + output GEMM + LayerNorm in one launch (csrc/sdfold.hip)
-    MDM_TRY(sd_fold(x16, fold.kfold, fold.cb, fold.vfold, l.sd_out_b, l.sd_ln_w, l.sd_ln_b, c.B, c.S, D, H, N, w.t3,
-                    (uint16_t*)w.t4, c.h16, c.s));
-    // the 4x FFN pair in one launch at the full time scale only: at the half scale of the bench batch
-    // (6272 rows -> 32-row tiles, every workgroup streams the pair's 4 MB for 32 rows) it measures slower than the two GEMMs
-    // (78 vs 66 us; 100 vs 120 us at 12544 rows).  The choice is made on the FRAME count of the scale, never on the batch: a
-    // sample's result must not depend on the batch it travels in (shard invariance, cond | uncond batching)
-    if (l.sd_ffn_ws && c.S >= 128) {
-      MdmMlpDesc f = {};
-      f.X = (const uint16_t*)w.t4, f.ldx = D, f.M = (int)c.M, f.Din = D, f.F = 4 * D, f.Dout = D;
-      f.b1 = l.sd_f1_b, f.b2 = l.sd_f2_b, f.wstream = l.sd_ffn_ws, f.wstream_gs = 8 * (int64_t)D * D;
-      f.R1 = x, f.ldr1 = D, f.r1_scale = 1.f, f.R2 = w.t3, f.ldr2 = D;  // x + (o + ffn(o))
-      f.C = out, f.C16 = out16, f.ldc = D, f.h16 = c.h16;
-      if (fused_mlp_stream_supported(f)) return fused_mlp_stream(f, c.s);
-    }
-    LinOpts o1;
-    o1.act = ACT_GELU;
-    MDM_TRY(linear_to_act(c, act_of(c, w.t4), c.M, D, l.sd_f1, l.sd_f1_b, 4 * D, w.f1, o1));
-    LinOpts o;  // x + (o + ffn(o))
-    o.R1 = x, o.R2 = w.t3;
-    return linear(c, act_of(c, w.f1), c.M, 4 * D, l.sd_f2, l.sd_f2_b, D, out, out16, o);
-  }
-  // fp32-grade modes, head_dim 128: the query projection leaves as bf16 hi | lo planes, scores / softmax / PV are one launch on
-  // bf16x3 MFMAs (csrc/xattn3.hip).  Knob 56: the chain (two batched contractions around a row softmax).
-  const bool fused3 = !c.bf && c.prec == 3 && g_variant != MDM_VAR_X3_XATTN_CHAIN && xattn3_supported(dh, N) && l.sd_q.lo &&
-                      D % 32 == 0 && (c.M * D) % 8 == 0;
-  if (fused3) {
-    uint16_t* const qh = (uint16_t*)w.t1;
-    uint16_t* const ql = qh + c.M * D;
-    GemmArgs g = gd(c);
-    g.A = op_f32(x, D);
-    g.W = packed(l.sd_q);
-    g.M = (int)c.M, g.N = D, g.K = D;
-    g.bias = l.sd_q_b, g.alpha = 1.f / sqrtf((float)dh);
-    g.C16 = qh, g.C16_lo = ql, g.ldc = D;
-    MDM_TRY(gemm(g, c.s));
-    MDM_TRY(sd_attn3(qh, ql, kc, vc, c.ntok, c.B, c.S, H, dh, N, w.t2, c.x2 ? 1 : 0, c.s));
-  } else {
-    LinOpts o;
-    o.alpha = 1.f / sqrtf((float)dh);
-    const bool fz = c.bf && xattn_supported(dh, N) && !(dh == 256 && g_variant == MDM_VAR_GENERIC_DH256);
-    MDM_TRY(linear(c, c.bf ? act_bf16(x16) : act_f32(x), c.M, D, l.sd_q, l.sd_q_b, D, fz ? nullptr : w.t1,
-                   fz ? (uint16_t*)w.t1 : nullptr, o));
-  }
-  if (fused3) {
-  } else if (c.bf && xattn_supported(dh, N) && !(dh == 256 && g_variant == MDM_VAR_GENERIC_DH256)) {
-    MDM_TRY(sd_attn(w.t1, c.h16, kc, vc, c.B, c.S, H, dh, N, (uint16_t*)w.t2, nullptr, c.h16, c.s, c.ntok));  // scores, softmax, PV fused
-  } else {
-    {
-      GemmArgs g = gd(c);  // scores[b,h,s,n] = q . k
-      g.A = op_f32(w.t1, D);
-      g.A.bs1 = (int64_t)c.S * D, g.A.bs2 = dh;
-      g.W = op_f32(kc, D);
-      g.W.bs1 = (int64_t)N * D, g.W.bs2 = dh;
-      g.M = c.S, g.N = N, g.K = dh;
-      g.batch = c.B * H, g.nb2 = H;
-      g.C = w.scr, g.ldc = N, g.c_bs1 = (int64_t)H * c.S * N, g.c_bs2 = (int64_t)c.S * N;
+  MdmMlpDesc f = {};  // the FFN pair in one launch of the streamed-weight kernel: out = x + (o + ffn(o)), o in t3, LN(o) in t4
+  f.X = (const uint16_t*)w.t4, f.ldx = D, f.M = (int)c.M, f.Din = D, f.F = 4 * D, f.Dout = D;
+  f.b1 = l.sd_f1_b, f.b2 = l.sd_f2_b, f.wstream = l.sd_ffn_ws, f.wstream_gs = 8 * (int64_t)D * D;
+  f.R1 = x, f.ldr1 = D, f.r1_scale = 1.f, f.R2 = w.t3, f.ldr2 = D;
+  f.C = out, f.C16 = out16, f.ldc = D, f.h16 = c.h16;
+  const SdPath path = sd_path(c, l, fold, f);
+  const Act xa = c.bf ? act_bf16(x16) : act_f32(x);
+  LinOpts qo;  // q = (x Wq^T + b) / sqrt(dh)
+  qo.alpha = 1.f / sqrtf((float)dh);
+  Act att = act_of(c, w.t2);  // the attention rows as the core leaves them in t2
+  switch (path) {
+    case SdPath::FOLD_PAIR:
+    case SdPath::FOLD:
+      MDM_TRY(sd_fold(x16, fold.kfold, fold.cb, fold.vfold, l.sd_out_b, l.sd_ln_w, l.sd_ln_b, c.B, c.S, D, H, N, w.t3,
+                      (uint16_t*)w.t4, c.h16, c.s));
+      return path == SdPath::FOLD_PAIR ? fused_mlp_stream(f, c.s) : sd_ffn(c, l, x, out, out16);
+    case SdPath::CORE3: {
+      uint16_t* const qh = (uint16_t*)w.t1;
+      uint16_t* const ql = qh + c.M * D;
+      GemmArgs g = planes_gemm(c, act_f32(x), l.sd_q, l.sd_q_b, D, qh, ql);
+      g.alpha = qo.alpha;
       MDM_TRY(gemm(g, c.s));
+      MDM_TRY(sd_attn3(qh, ql, kc, vc, c.ntok, c.B, c.S, H, dh, N, w.t2, c.x2 ? 1 : 0, c.s));
+      att.x2 = c.x2;
+      break;
     }
-    MDM_TRY(row_softmax(w.scr, c.M * H, N, c.s, c.ntok, (int64_t)H * c.S));
-    {
-      GemmArgs g = gd(c);  // o[b,s,h,:] = p v
-      g.A = op_f32(w.scr, N);
-      g.A.bs1 = (int64_t)H * c.S * N, g.A.bs2 = (int64_t)c.S * N;
-      g.W = op_f32_kstride(vc, D);
-      g.W.bs1 = (int64_t)N * D, g.W.bs2 = dh;
-      g.M = c.S, g.N = dh, g.K = N;
-      g.batch = c.B * H, g.nb2 = H;
-      g.C = c.bf ? nullptr : w.t2, g.C16 = c.bf ? (uint16_t*)w.t2 : nullptr;
-      g.ldc = D, g.c_bs1 = (int64_t)c.S * D, g.c_bs2 = dh;
+    case SdPath::CORE:
+      MDM_TRY(linear(c, xa, c.M, D, l.sd_q, l.sd_q_b, D, nullptr, (uint16_t*)w.t1, qo));
+      MDM_TRY(sd_attn(w.t1, c.h16, kc, vc, c.B, c.S, H, dh, N, (uint16_t*)w.t2, nullptr, c.h16, c.s, c.ntok));
+      break;
+    case SdPath::CHAIN: {
+      MDM_TRY(linear(c, xa, c.M, D, l.sd_q, l.sd_q_b, D, w.t1, nullptr, qo));
+      // scores[b,h,s,n] = q . k
+      GemmArgs g = per_head(c, heads(op_f32(w.t1, D), (int64_t)c.S * D, dh), heads(op_f32(kc, D), (int64_t)N * D, dh), c.S, N, dh,
+                            N, (int64_t)H * c.S * N, (int64_t)c.S * N);
+      g.C = w.scr;
       MDM_TRY(gemm(g, c.s));
+      MDM_TRY(row_softmax(w.scr, c.M * H, N, c.s, c.ntok, (int64_t)H * c.S));
+      // o[b,s,h,:] = p v
+      GemmArgs pv = per_head(c, heads(op_f32(w.scr, N), (int64_t)H * c.S * N, (int64_t)c.S * N),
+                             heads(op_f32_kstride(vc, D), (int64_t)N * D, dh), c.S, dh, N, D, (int64_t)c.S * D, dh);
+      pv.C = c.bf ? nullptr : w.t2, pv.C16 = c.bf ? (uint16_t*)w.t2 : nullptr;
+      MDM_TRY(gemm(pv, c.s));
+      break;
     }
   }
-  MDM_TRY(linear(c, Act{w.t2, c.bf, fused3 && c.x2}, c.M, D, l.sd_out, l.sd_out_b, D, w.t3, nullptr));
-  // the 4x FFN (LayerNorm -> Linear -> GELU -> Linear): 16-bit operands in the throughput AND the mixed mode; in the fp32-grade
-  // mode the LayerNorm rows and the hidden rows are written pre-split for the GEMM that reads them
-  const bool h = c.bf || c.mix, fx2 = !h && c.x2;
-  MDM_TRY(ln_chain(w.t3, c.M, D, l.sd_ln_w, l.sd_ln_b, w.t4, fx2 ? 4 : fmt_mlp(c), nullptr, nullptr, nullptr, 0, c.s));
-  {
-    LinOpts o;
-    o.act = ACT_GELU;
-    if (fx2) o.outx2 = (uint16_t*)w.f1;
-    MDM_TRY(linear(c, Act{w.t4, h, fx2}, c.M, D, l.sd_f1, l.sd_f1_b, 4 * D, (h || fx2) ? nullptr : w.f1, h ? (uint16_t*)w.f1 : nullptr, o));
-  }
-  LinOpts o;  // x + (o + ffn(o))
-  o.R1 = x, o.R2 = w.t3;
-  return linear(c, Act{w.f1, h, fx2}, c.M, 4 * D, l.sd_f2, l.sd_f2_b, D, out, out16, o);
+  MDM_TRY(linear(c, att, c.M, D, l.sd_out, l.sd_out_b, D, w.t3, nullptr));
+  MDM_TRY(ln_chain(w.t3, c.M, D, l.sd_ln_w, l.sd_ln_b, w.t4, fmt_mlp(c), nullptr, nullptr, nullptr, 0, c.s));
+  return sd_ffn(c, l, x, out, out16);
 }
 
 const float* tc_at(const MdmModel& m, const MdmTextCache& tc, int layer) {
