@@ -429,6 +429,33 @@ int mdm_motion_postprocess(const float* motion, const int32_t* length, const flo
                            int32_t T, int32_t feats, int32_t joints, int32_t radius, const double* weights,
                            float* scratch, float* joints_out, void* stream);
 
+/* Joint-position control (csrc/motion_control.hip).  For sample b, with J = (F + 1) / 12 joints (F must be
+ * 12 J - 1: 263 -> 22, 251 -> 21), targets G and weights W dense fp32 (B, T, J, 3), W >= 0 and finite, mean / std fp32
+ * (B, F) (one row per sample), and P = recover_from_ric(x0 * std + mean) without temporal filter (as mdm_motion_postprocess
+ * computes it at radius 0):
+ *   L_b = sum_{t < length[b], j, c} W[t, j, c] (P[t, j, c] - G[t, j, c])^2
+ * (entries with W == 0 contribute nothing, whatever G holds).  Only the steerable columns, root 0..3 and ric 4 .. 3J, enter
+ * recover_from_ric; every other column, and every frame at or past length[b], has gradient exactly 0.
+ * mdm_joint_loss_grad: loss_out (B) and grad_out (B, T, F) = dL_b / dx0, with respect to the normalised features (so it
+ * carries the std factor).  mdm_joint_guidance: runs after a sampler step's update kernel, on the same stream and before the
+ * step counter moves; x0 is the (guided / composed / edited) x0 that update wrote, x its x_{t-1}.  It runs `iters`
+ * iterations x0' = x0' - scale * (1 - mask) * dL/dx0' (mask (B, T, F) in [0, 1], or NULL = 0) from x0' = x0, recomputing P
+ * each time, then with delta = x0' - x0 writes x0 = x0' and x = x + c0[t] * delta, c0[t] = coef[4 t + 1] (the runner's
+ * coefficient table, t = *t_dev when non-NULL else t_imm): every update is linear in x0, so this is the update run on x0'.
+ * Nothing is stored where delta == 0 (an all-zero W leaves x and x0 bit for bit, -0.0 included); nothing is re-clamped.
+ * T is limited by the LDS that holds the steerable columns: mdm_joint_control_max_frames(F) (205 at F = 263, 211 at 251;
+ * 0 for an F not of the form 12 J - 1).  MDM_ERR_ARG: a null pointer (mask excepted), a bad F, T < 1 or over that limit,
+ * B < 0, iters outside [1, MDM_CONTROL_MAX_ITERS], a non-finite scale, steps <= 0 or t_imm outside [0, steps) without t_dev. */
+enum { MDM_CONTROL_MAX_ITERS = 32 };
+int mdm_joint_control_max_frames(int32_t feats);
+int mdm_joint_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
+                        const float* weights, int32_t B, int32_t T, int32_t F, float* loss_out, float* grad_out,
+                        void* stream);
+int mdm_joint_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
+                       const float* targets, const float* weights, int32_t B, int32_t T, int32_t F, float scale,
+                       int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
+                       void* stream);
+
 /* ---- training step of the MoE feed-forward block --------------------------------------------
  * MoEMultiBranchFFN.forward (multi_branch.py:52-61) with both SwitchMoELayers (switch_moe.py:44-111) and the StylizationBlock
  * (stylization.py:20-31) in training mode, and its backward: what loss.backward() does for this block inside

@@ -1,0 +1,281 @@
+// Joint-position control: the weighted squared distance of recover_from_ric(x0 * std + mean) to target
+// joint positions, its gradient with respect to the normalised features, and the guidance that moves a step's x0 down it.
+//   P = recover_from_ric(x0 * std + mean)    forward exactly as motion_post_kernel (fp64 scans, same operation order)
+//   L = sum_{t < len, j, k} W (P - G)^2      dL/dP = 2 W (P - G), zero wherever W == 0 (G is then never read into it)
+// Backward, per sample:
+//   ric columns   (4 + 3(j-1) ..): rotated by the inverse root rotation of their own frame -> transpose of that rotation
+//   root height   (3):             P[t, 0, y] directly
+//   root XZ       (1, 2):          P[t, :, x|z] += px|pz[t], px[t] = sum_{s <= t} rot(ang[s]) v[s - 1, 1|2]
+//                                  -> suffix sums of dL/dpx, dL/dpz, then the transpose of the rotation of frame s
+//   heading       (0):             ang[t] = sum_{s < t} v[s, 0] -> strict suffix sum of dL/dang, which collects the chain
+//                                  through rot_y / cos / sin of the ric joints and of the root velocity of frame t
+// One workgroup per sample; the sample's 4 + 3(J-1) steerable columns live in LDS for all iterations, row stride padded odd
+// (no bank conflicts between frame threads).  Frame phases run one thread per frame (a thread walks its frame's J joints, so
+// per-frame sums need no atomics and the result is deterministic); the three scans run in one thread with fp64
+// accumulators.  No other column of the feature row enters recover_from_ric, so none is read or written.
+#include "kernels.h"
+
+#include <cmath>
+
+namespace mdm {
+namespace {
+
+constexpr int CTRL_THREADS = 256;
+constexpr int CTRL_LDS_BYTES = 64 * 1024;
+enum { CW, SW, RX, RZ, PX, PZ, GX, GZ, GA, GH, FR };  // fields of the per-frame record
+constexpr int CTRL_FRAME_BYTES = FR * 4 + 8;          // per frame: the record + the fp64 loss
+
+__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
+
+// motion_post.hip's rot_y with q = qy, w: the same operations in the same order (P agrees with mdm_motion_postprocess)
+__device__ __forceinline__ void rot_y(float w, float qy, float vx, float vz, float& ox, float& oz) {
+  const float uvx = mul(qy, vz), uvz = -mul(qy, vx);
+  const float uuvx = mul(qy, uvz), uuvz = -mul(qy, uvx);
+  ox = add(vx, mul(2.f, add(mul(w, uvx), uuvx)));
+  oz = add(vz, mul(2.f, add(mul(w, uvz), uuvz)));
+}
+
+// Partials of rot_y(w = cos a, qy = -sin a) in exact arithmetic:
+//   ox = a11 vx + a13 vz, oz = -a13 vx + a11 vz with a11 = 1 - 2 qy^2, a13 = 2 w qy
+//   dox/da = 2 (e vz + f vx), doz/da = 2 (f vz - e vx) with e = qy^2 - w^2, f = 2 qy w
+struct RotD {
+  double a11, a13, e, f;
+};
+__device__ __forceinline__ RotD rot_d(float cw, float sw) {
+  const double w = cw, q = -(double)sw;
+  return {1.0 - 2.0 * q * q, 2.0 * w * q, q * q - w * w, 2.0 * q * w};
+}
+
+// GUIDE = false: mdm_joint_loss_grad (one evaluation; loss_out and the dense gradient grad_out written).
+// GUIDE = true:  mdm_joint_guidance (iters steps of x0 -= scale (1 - m) grad in LDS, then x0 / x updated where delta != 0).
+template <bool GUIDE, bool MASK>
+__global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
+    float* x0, float* x, const float* __restrict__ mask, const int* __restrict__ len, const float* __restrict__ mean,
+    const float* __restrict__ sd, const float* __restrict__ targets, const float* __restrict__ weights, int T, int F,
+    int J, float scale, int iters, const float* __restrict__ coef, int steps, const int* __restrict__ t_ptr, int t_imm,
+    float* __restrict__ loss_out, float* __restrict__ grad_out) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int D = 3 * J + 1;               // steerable columns: root (4) + ric (3 (J - 1))
+  const int DS = D | 1;                  // odd LDS row stride
+  double* lossF = (double*)smem_raw;     // [T]
+  float* lsd = (float*)(lossF + T);      // [DS] std and mean of the steerable columns (in LDS: as scalar loads hoisted
+  float* lmean = lsd + DS;               //      out of the loops they would take scalar registers the kernel lacks)
+  float* xs = lmean + DS;                // [T][DS] the steerable columns of x0, normalised
+  // per-frame record fr[t * FR + k] (one LDS base for all of them):
+  //   CW, SW   cos / sin of the heading of frame t
+  //   RX, RZ   root velocity of frame t - 1 rotated by the heading of frame t
+  //   PX, PZ   root XZ; after the frame phase: dL/dv[t, 1], dL/dv[t, 2]
+  //   GX, GZ   sum_j dL/dP[t, j, x] and z
+  //   GA       dL/dang[t] of the ric joints; after the scan: dL/dv[t, 0]
+  //   GH       dL/dv[t, 3] (root height)
+  float* fr = xs + T * DS;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int n = len[b];
+  n = n < 0 ? 0 : (n > T ? T : n);
+  const int64_t row0 = (int64_t)b * T * F;
+  const float* tg = targets + (int64_t)b * T * J * 3;
+  const float* wt = weights + (int64_t)b * T * J * 3;
+  const float* mk = MASK ? mask + row0 : nullptr;
+  float c0 = 0.f;  // read before the iterations: keeps the table's pointers out of the loop's scalar registers
+  if (GUIDE) {
+    int ts = t_ptr ? *t_ptr : t_imm;
+    ts = min(max(ts, 0), steps - 1);
+    c0 = coef[4 * ts + 1];
+  }
+
+  if (!GUIDE) {  // every entry that cannot receive gradient: frames past the length and the columns past D
+    float* gb = grad_out + row0;
+    for (int64_t i = tid; i < (int64_t)T * F; i += CTRL_THREADS) {
+      const int t = (int)(i / F), c = (int)(i - (int64_t)t * F);
+      if (t >= n || c >= D) gb[i] = 0.f;
+    }
+  }
+  for (int i = tid; i < n * D; i += CTRL_THREADS) {
+    const int t = i / D, c = i - t * D;
+    xs[t * DS + c] = x0[row0 + (int64_t)t * F + c];
+  }
+  for (int c = tid; c < D; c += CTRL_THREADS) lsd[c] = sd[(int64_t)b * F + c], lmean[c] = mean[(int64_t)b * F + c];
+  __syncthreads();
+  auto val = [&](int t, int c) { return add(mul(xs[t * DS + c], lsd[c]), lmean[c]); };
+  // one gradient entry g (w.r.t. the normalised feature): written out, or the guidance step applied in LDS
+  auto emit = [&](int t, int c, float g) {
+    if (GUIDE) {
+      const float u = MASK ? (1.f - mk[(int64_t)t * F + c]) * g : g;
+      xs[t * DS + c] = xs[t * DS + c] - scale * u;
+    } else {
+      grad_out[row0 + (int64_t)t * F + c] = g;
+    }
+  };
+
+#pragma unroll 1
+  for (int it = 0; it < iters; ++it) {
+    // heading: exclusive prefix sum of the rotation velocity (motion_post_kernel order)
+    if (tid == 0) {
+      double acc = 0.0;
+      for (int t = 0; t < n; ++t) {
+        if (t > 0) acc += (double)val(t - 1, 0);
+        const float a = (float)acc;
+        fr[t * FR + CW] = cosf(a), fr[t * FR + SW] = sinf(a);
+      }
+    }
+    __syncthreads();
+    for (int t = tid; t < n; t += CTRL_THREADS) {
+      float vx = 0.f, vz = 0.f;
+      if (t > 0) vx = val(t - 1, 1), vz = val(t - 1, 2);
+      float ox, oz;
+      rot_y(fr[t * FR + CW], -fr[t * FR + SW], vx, vz, ox, oz);
+      fr[t * FR + RX] = ox, fr[t * FR + RZ] = oz;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double ax = 0.0, az = 0.0;
+      for (int t = 0; t < n; ++t) {
+        ax += (double)fr[t * FR + RX], az += (double)fr[t * FR + RZ];
+        fr[t * FR + PX] = (float)ax, fr[t * FR + PZ] = (float)az;
+      }
+    }
+    __syncthreads();
+    // frame phase: P, dL/dP, the ric columns' gradient (local to the frame) and the per-frame sums the scans need
+    for (int t = tid; t < n; t += CTRL_THREADS) {
+      const float c = fr[t * FR + CW], s = fr[t * FR + SW], qx = fr[t * FR + PX], qz = fr[t * FR + PZ];
+      const RotD r = rot_d(c, s);
+      const float* tgt = tg + (int64_t)t * J * 3;
+      const float* wgt = wt + (int64_t)t * J * 3;
+      double lsum = 0.0, sx = 0.0, sz = 0.0, sa = 0.0;
+      float g[3];
+      auto dl = [&](int k, float p) {  // dL/dP of one coordinate; W == 0 contributes nothing, whatever G holds
+        const float w = wgt[k];
+        if (w == 0.f) return 0.f;
+        const float d = p - tgt[k];
+        lsum += (double)w * (double)d * (double)d;
+        return 2.f * w * d;
+      };
+      {  // joint 0: root XZ and height
+        g[0] = dl(0, qx), g[1] = dl(1, val(t, 3)), g[2] = dl(2, qz);
+        sx += g[0], sz += g[2];
+        fr[t * FR + GH] = g[1];
+      }
+#pragma unroll 1
+      for (int j = 1; j < J; ++j) {
+        const int col = 4 + 3 * (j - 1);
+        const float vx = val(t, col), vy = val(t, col + 1), vz = val(t, col + 2);
+        float ox, oz;
+        rot_y(c, -s, vx, vz, ox, oz);
+        g[0] = dl(3 * j, add(ox, qx)), g[1] = dl(3 * j + 1, vy), g[2] = dl(3 * j + 2, add(oz, qz));
+        if (GUIDE && g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) continue;  // no step: the entries keep their bits
+        sx += g[0], sz += g[2];
+        sa += 2.0 * ((double)g[0] * (r.e * vz + r.f * vx) + (double)g[2] * (r.f * vz - r.e * vx));
+        const float gvx = (float)((double)g[0] * r.a11 - (double)g[2] * r.a13);
+        const float gvz = (float)((double)g[0] * r.a13 + (double)g[2] * r.a11);
+        emit(t, col, gvx * lsd[col]);
+        emit(t, col + 1, g[1] * lsd[col + 1]);
+        emit(t, col + 2, gvz * lsd[col + 2]);
+      }
+      lossF[t] = lsum;
+      fr[t * FR + GX] = (float)sx, fr[t * FR + GZ] = (float)sz, fr[t * FR + GA] = (float)sa;
+    }
+    __syncthreads();
+    // reverse scans (fp64): dL/drx[t] = sum_{u >= t} GX[u]; dL/dv[t, 0] = sum_{u > t} dL/dang[u].  Reads CW / SW /
+    // the root velocity columns (not yet updated); writes dL/dv[t-1, 1|2] into PX / PZ and dL/dv[t, 0] over GA.
+    if (tid == 0) {
+      double sx = 0.0, sz = 0.0, sang = 0.0, loss = 0.0;
+      if (n > 0) fr[(n - 1) * FR + PX] = 0.f, fr[(n - 1) * FR + PZ] = 0.f;
+      for (int t = n - 1; t >= 0; --t) {
+        sx += (double)fr[t * FR + GX], sz += (double)fr[t * FR + GZ];
+        double gat = (double)fr[t * FR + GA];
+        if (t > 0) {
+          const RotD r = rot_d(fr[t * FR + CW], fr[t * FR + SW]);
+          const double vx = (double)val(t - 1, 1), vz = (double)val(t - 1, 2);
+          gat += 2.0 * (sx * (r.e * vz + r.f * vx) + sz * (r.f * vz - r.e * vx));
+          fr[(t - 1) * FR + PX] = (float)(sx * r.a11 - sz * r.a13);
+          fr[(t - 1) * FR + PZ] = (float)(sx * r.a13 + sz * r.a11);
+        }
+        fr[t * FR + GA] = (float)sang;
+        sang += gat;
+      }
+      if (!GUIDE) {
+        for (int t = 0; t < n; ++t) loss += lossF[t];
+        loss_out[b] = (float)loss;
+      }
+    }
+    __syncthreads();
+    for (int t = tid; t < n; t += CTRL_THREADS) {
+      emit(t, 0, fr[t * FR + GA] * lsd[0]);
+      emit(t, 1, fr[t * FR + PX] * lsd[1]);
+      emit(t, 2, fr[t * FR + PZ] * lsd[2]);
+      emit(t, 3, fr[t * FR + GH] * lsd[3]);
+    }
+    __syncthreads();
+  }
+  if (GUIDE) {  // delta = x0' - x0: x0 <- x0', x <- x + c0[t] delta; nothing stored where delta == 0
+    for (int i = tid; i < n * D; i += CTRL_THREADS) {
+      const int t = i / D, c = i - t * D;
+      const int64_t e = row0 + (int64_t)t * F + c;
+      const float nv = xs[t * DS + c], ov = x0[e], dlt = nv - ov;
+      if (dlt != 0.f) {
+        x0[e] = nv;
+        x[e] = x[e] + c0 * dlt;
+      }
+    }
+  }
+}
+
+int control_joints(int F) { return (F + 1) % 12 == 0 && F >= 11 ? (F + 1) / 12 : 0; }
+
+size_t control_lds_bytes(int T, int J) {
+  const int DS = (3 * J + 1) | 1;
+  return (size_t)2 * DS * 4 + (size_t)T * ((size_t)DS * 4 + CTRL_FRAME_BYTES);
+}
+
+}  // namespace
+}  // namespace mdm
+
+extern "C" {
+
+int mdm_joint_control_max_frames(int32_t feats) {
+  const int J = mdm::control_joints(feats);
+  if (J == 0) return 0;
+  const size_t fixed = mdm::control_lds_bytes(0, J), frame = mdm::control_lds_bytes(1, J) - fixed;
+  return (int)((mdm::CTRL_LDS_BYTES - fixed) / frame);
+}
+
+int mdm_joint_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
+                        const float* weights, int32_t B, int32_t T, int32_t F, float* loss_out, float* grad_out,
+                        void* stream) {
+  if (!x0 || !length || !mean || !std || !targets || !weights || !loss_out || !grad_out) return MDM_ERR_ARG;
+  const int J = mdm::control_joints(F);
+  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_control_max_frames(F)) return MDM_ERR_ARG;
+  if (B == 0) return MDM_OK;
+  const size_t smem = mdm::control_lds_bytes(T, J);
+  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
+                     const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J, 0.f, 1,
+                     nullptr, 1, nullptr, 0, loss_out, grad_out);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_joint_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
+                       const float* targets, const float* weights, int32_t B, int32_t T, int32_t F, float scale,
+                       int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
+                       void* stream) {
+  if (!x || !x0 || !length || !mean || !std || !targets || !weights || !coef) return MDM_ERR_ARG;
+  const int J = mdm::control_joints(F);
+  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_control_max_frames(F)) return MDM_ERR_ARG;
+  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
+  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
+  if (B == 0) return MDM_OK;
+  const size_t smem = mdm::control_lds_bytes(T, J);
+  if (mask)
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
+                       x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev, t_imm,
+                       nullptr, nullptr);
+  else
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
+                       x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev,
+                       t_imm, nullptr, nullptr);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+}  // extern "C"

@@ -27,6 +27,11 @@ Composed guidance: ``model_kwargs`` may carry K prompts per sample (``compose_xf
 ``compose_text``) and weight maps ``compose_weights``; every guided loop then runs (K + 1)B rows through the forward and
 combines ``x0 = x0_u + s * sum_k w_k (x0_k - x0_u)`` in one fused kernel (``mdm_composed_update``):
 time-varied and body-part control, negative prompts.
+
+Joint-position control: ``model_kwargs`` may carry ``control_joints`` (B, T, J, 3) targets, ``control_weights``,
+``control_mean`` / ``control_std`` (B, F), ``control_scale`` and ``control_iters``; every loop and single step then moves
+its x0 down the gradient of the weighted squared distance of ``recover_from_ric(x0 * std + mean)`` to the targets after its
+update, and x_{t-1} with it (``mdm_joint_guidance``): trajectories, keyframes, end positions.
 """
 from __future__ import annotations
 
@@ -568,6 +573,66 @@ def check_compose_kwargs(kw, shape, mode=None):
     return {"weights": w, "K": K, "xf_proj": cp, "xf_out": co, "text": ct}
 
 
+def check_control_kwargs(kw, shape):
+    """The joint-control inputs of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when none of the ``control_*``
+    keys is given, else a dict with ``targets`` (B, T, J, 3), ``weights`` broadcast to it (a view), ``mean`` / ``std``
+    (B, F), ``scale`` (float, default 1) and ``iters`` (int, default 1).  Every tensor leads with B, so dist.shard_kwargs
+    slices them; the weights are aligned on that dim: (B,) per sample, (B, T) per frame, (B, T, J) per joint.
+    Raises ValueError when only some of the four tensors are given (or a scale / iters without them), for an F not of the
+    form 12 J - 1, a T over the kernels' LDS limit, shape or broadcast errors, non-finite targets, weights, mean or std,
+    negative weights, a zero std, a non-finite scale or iters outside [1, MDM_CONTROL_MAX_ITERS].  Host logic."""
+    from .motion_control import joints_for_feats, max_frames
+    names = ("control_joints", "control_weights", "control_mean", "control_std")
+    g, w, mean, std = (kw.get(k) for k in names)
+    given = [k for k, v in zip(names, (g, w, mean, std)) if v is not None]
+    extra = [k for k in ("control_scale", "control_iters") if kw.get(k) is not None]
+    if not given:
+        if extra:
+            raise ValueError(f"{' / '.join(extra)} given without control_joints / control_weights / control_mean / control_std")
+        return None
+    if len(given) != 4:
+        raise ValueError(f"joint control needs all of {', '.join(names)}; missing "
+                         f"{', '.join(k for k in names if k not in given)}")
+    B, T, F_ = (int(v) for v in shape)
+    J = joints_for_feats(F_)
+    if T > max_frames(F_):
+        raise ValueError(f"T = {T}: joint control takes at most {max_frames(F_)} frames at F = {F_}")
+    g, w, mean, std = (torch.as_tensor(v) for v in (g, w, mean, std))
+    for name, v in zip(names, (g, w, mean, std)):
+        if not v.is_floating_point():
+            raise ValueError(f"{name} must be floating point")
+    if tuple(g.shape) != (B, T, J, 3):
+        raise ValueError(f"control_joints has shape {tuple(g.shape)}, expected {(B, T, J, 3)}")
+    if w.dim() == 0 or w.dim() > 4 or w.shape[0] != B:
+        raise ValueError(f"control_weights of shape {tuple(w.shape)} must lead with the batch size {B}")
+    try:
+        w = w.reshape(tuple(w.shape) + (1,) * (4 - w.dim())).expand(B, T, J, 3)
+    except RuntimeError:
+        raise ValueError(f"control_weights of shape {tuple(w.shape)} does not broadcast to {(B, T, J, 3)}") from None
+    for name, v in (("control_mean", mean), ("control_std", std)):
+        if tuple(v.shape) != (B, F_):
+            raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(B, F_)} (one row per sample)")
+    if not bool(torch.isfinite(g).all()):
+        raise ValueError("control_joints has non-finite values")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("control_weights has non-finite values")
+    if not bool((w >= 0).all()):
+        raise ValueError("control_weights must be >= 0")
+    if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all())):
+        raise ValueError("control_mean / control_std have non-finite values")
+    if bool((std == 0).any()):
+        raise ValueError("control_std has zero entries")
+    scale = kw.get("control_scale")
+    scale = 1.0 if scale is None else float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("control_scale must be finite")
+    iters = kw.get("control_iters")
+    iters = 1 if iters is None else iters
+    if isinstance(iters, bool) or int(iters) != iters or not 1 <= int(iters) <= L.CONTROL_MAX_ITERS:
+        raise ValueError(f"control_iters must be an integer in [1, {L.CONTROL_MAX_ITERS}]")
+    return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters)}
+
+
 class _StepRunner:
     """Static buffers + (optionally) one captured hipGraph for a whole denoising step."""
 
@@ -660,9 +725,23 @@ class _StepRunner:
         if comp is not None:
             self.cw = torch.empty((self.K, B, T, Fe), dtype=torch.float32, device=self.dev)
             self.cw.copy_(comp["weights"].transpose(0, 1))
-        # few-step modes (and every mode when editing or composing): per-step coefficients of the fused update; self.x0
-        # doubles as x0_prev (updated in place)
-        kind = _EDIT_COEF_KIND[mode] if self.known is not None or self.cw is not None else _COEF_KIND.get(mode)
+        # joint control: targets, weights, mean / std and the lengths, dense f32 / int32 and owned by the runner
+        ctl = check_control_kwargs(kw, shape)
+        self.ctl = None
+        if ctl is not None:
+            J = ctl["targets"].shape[2]
+            self.ctl = dict(scale=ctl["scale"], iters=ctl["iters"],
+                            len=length.contiguous(),
+                            targets=torch.empty((B, T, J, 3), dtype=torch.float32, device=self.dev),
+                            weights=torch.empty((B, T, J, 3), dtype=torch.float32, device=self.dev),
+                            mean=torch.empty((B, Fe), dtype=torch.float32, device=self.dev),
+                            std=torch.empty((B, Fe), dtype=torch.float32, device=self.dev))
+            for k in ("targets", "weights", "mean", "std"):
+                self.ctl[k].copy_(ctl[k])
+        # few-step modes (and every mode when editing, composing or controlling): per-step coefficients of the fused update;
+        # self.x0 doubles as x0_prev (updated in place)
+        table = self.known is not None or self.cw is not None or self.ctl is not None
+        kind = _EDIT_COEF_KIND[mode] if table else _COEF_KIND.get(mode)
         self.coef = diff._device_coef(kind, eta, order, self.dev) if kind is not None else None
         self.graph = None
         # time-embedding chain tabulated per timestep + text half of the gated fusion: once per loop, not per step
@@ -767,8 +846,9 @@ class _StepRunner:
                 "mdm_guided_update_inpaint")
         elif self.coef is not None:
             x0 = C.c_void_p(self.x0.data_ptr())
+            eps_u = C.c_void_p(self.eps[B:].data_ptr() if self.mode in _GUIDED else 0)
             L.check(lib.mdm_guided_update(C.c_void_p(x.data_ptr()), C.c_void_p(self.eps.data_ptr()),
-                                          C.c_void_p(self.eps[B:].data_ptr()), x0 if self.mode == "cfg_dpmpp" else C.c_void_p(0),
+                                          eps_u, x0 if self.mode == "cfg_dpmpp" else C.c_void_p(0),
                                           noise, C.c_int64(n), C.c_void_p(self.tab.data_ptr()),
                                           C.c_void_p(self.coef.data_ptr()), steps, C.c_void_p(self.t_dev.data_ptr()),
                                           C.c_int32(0), C.c_float(self.cfg_scale), C.c_int32(int(self.clip)),
@@ -785,6 +865,14 @@ class _StepRunner:
                                                C.c_void_p(self.t_dev.data_ptr()), C.c_int32(0), C.c_float(self.cfg_scale),
                                                C.c_int32(int(self.clip)), C.c_void_p(x.data_ptr()),
                                                C.c_void_p(self.x0.data_ptr()), s), "mdm_cfg_posterior_step")
+        if self.ctl is not None:  # x0 and x_{t-1} moved down the joint-position loss, before the counter moves
+            c = self.ctl
+            L.check(lib.mdm_joint_guidance(
+                C.c_void_p(x.data_ptr()), C.c_void_p(self.x0.data_ptr()), C.c_void_p(L.ptr(self.mask)),
+                C.c_void_p(c["len"].data_ptr()), C.c_void_p(c["mean"].data_ptr()), C.c_void_p(c["std"].data_ptr()),
+                C.c_void_p(c["targets"].data_ptr()), C.c_void_p(c["weights"].data_ptr()), C.c_int32(B), C.c_int32(self.T),
+                C.c_int32(self.Fe), C.c_float(c["scale"]), C.c_int32(c["iters"]), C.c_void_p(self.coef.data_ptr()), steps,
+                C.c_void_p(self.t_dev.data_ptr()), C.c_int32(0), s), "mdm_joint_guidance")
         L.check(lib.mdm_add_i32(C.c_void_p(self.t_dev.data_ptr()), C.c_int32(-1), s))
 
     def _needs_noise(self) -> bool:

@@ -7,11 +7,13 @@ same ``generate(caption, m_lens, dim_pose, batch_size)`` -> list of (T, dim_pose
 run the reference's guided DDPM over every step.  ``edit_motion`` / ``edit_mask`` turn any of them into motion editing
 (prefix completion, in-betweening, body-part regeneration; masks from ``motion_edit``).  ``prompt_weights`` with K
 captions per sample composes them under per-prompt weight maps (time-varied and body-part control, negative prompts;
-weights from ``motion_compose``).  The training loop (forward/backward/update/train) is out of
+weights from ``motion_compose``).  ``control_joints`` / ``control_weights`` (with ``mean`` / ``std``) steer joint positions:
+trajectories, keyframes, end positions (targets from ``motion_control``).  The training loop (forward/backward/update/train) is out of
 scope for this build and raises.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType, SpacedDiffusion, get_named_beta_schedule,
@@ -85,6 +87,51 @@ class DDPMTrainer(object):
         return {"inpaint_motion": k[rows, :T], "inpaint_mask": msk[rows, :T]}
 
     @staticmethod
+    def _control(control_joints, control_weights, mean, std, dim_pose):
+        """Check a controlled call: ``control_joints`` (N, T_max, J, 3) and ``control_weights`` broadcast to it (aligned on
+        the leading dim like ``check_control_kwargs``; a view), ``mean`` / ``std`` as float32 (dim_pose,) tensors.  None when
+        neither control tensor is given."""
+        if control_joints is None and control_weights is None:
+            return None
+        if control_joints is None or control_weights is None:
+            raise ValueError("control_joints and control_weights go together: give both or neither")
+        if mean is None or std is None:
+            raise ValueError("joint control needs the dataset's mean and std (the targets are de-normalised positions)")
+        from .motion_control import joints_for_feats
+        J = joints_for_feats(dim_pose)
+        g = torch.as_tensor(control_joints, dtype=torch.float32)
+        if g.dim() != 4 or tuple(g.shape[2:]) != (J, 3):
+            raise ValueError(f"control_joints of shape {tuple(g.shape)} must be (N, T_max, {J}, 3)")
+        w = torch.as_tensor(control_weights, dtype=torch.float32)
+        if w.dim() == 0 or w.dim() > 4 or w.shape[0] != g.shape[0]:
+            raise ValueError(f"control_weights of shape {tuple(w.shape)} must lead with N = {g.shape[0]}")
+        try:
+            w = w.reshape(tuple(w.shape) + (1,) * (4 - w.dim())).expand(g.shape)
+        except RuntimeError:
+            raise ValueError(f"control_weights of shape {tuple(w.shape)} does not broadcast to {tuple(g.shape)}") from None
+        ms = []
+        for name, v in (("mean", mean), ("std", std)):
+            v = torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v), dtype=torch.float32).flatten()
+            if v.numel() != dim_pose:
+                raise ValueError(f"{name} must have {dim_pose} entries")
+            ms.append(v)
+        return {"joints": g, "weights": w, "mean": ms[0], "std": ms[1]}
+
+    @staticmethod
+    def _control_kwargs(ctl, scale, iters, rows, T, device):
+        """``control_*`` model kwargs of one batch: rows ``rows`` and the first T frames of the checked control (from
+        _control); {} without control."""
+        if ctl is None:
+            return {}
+        g = ctl["joints"][rows]
+        if g.shape[1] < T:
+            raise ValueError(f"control_joints has {g.shape[1]} frames, the batch {T}")
+        n = g.shape[0]
+        return {"control_joints": g[:, :T].to(device), "control_weights": ctl["weights"][rows][:, :T].to(device),
+                "control_mean": ctl["mean"].to(device).expand(n, -1), "control_std": ctl["std"].to(device).expand(n, -1),
+                "control_scale": scale, "control_iters": iters}
+
+    @staticmethod
     def _compose_weights(caption, prompt_weights, dim_pose):
         """Check a composed call: every ``caption[i]`` a sequence of the same K strings; returns ``prompt_weights`` as a
         float32 tensor broadcast to (N, K, T_w, dim_pose) (T_w = its frame dim, 1 when it has none; a view)."""
@@ -133,35 +180,45 @@ class DDPMTrainer(object):
     @torch.no_grad()
     def generate_batch(self, caption, m_lens, dim_pose, *, noise=None, step_noise=None, progress=True, seed=None,
                        sample_offset=0, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
-                       prompt_weights=None):
+                       prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
+                       control_iters=1, mean=None, std=None):
         """``edit_motion`` (B, T_max, dim_pose), normalised, and ``edit_mask`` broadcastable to it, values in [0, 1]: the
         batch's first T frames of both are kept where the mask is 1 (exactly, for a binary mask) and generated elsewhere.
         ``prompt_weights`` (B, K, ...) broadcastable to (B, K, T_max, dim_pose): ``caption[i]`` is then a sequence of K
-        captions, composed on every step under these weights."""
+        captions, composed on every step under these weights.
+        ``control_joints`` (B, T_max, J, 3) target joint positions and ``control_weights`` (B, ...) broadcastable to them, with
+        the dataset's ``mean`` / ``std`` (dim_pose,): every step's x0 is moved ``control_iters`` times down the gradient of
+        the weighted squared distance, scaled by ``control_scale`` (units in ``motion_control``)."""
         m = self._model()
         m_lens = torch.as_tensor(m_lens)
         T = min(int(m_lens.max()), m.num_frames)
         B = len(caption)
         w = None if prompt_weights is None else self._compose_weights(caption, prompt_weights, dim_pose)
         edit = self._edit_kwargs(edit_motion, edit_mask, slice(0, B), T, dim_pose)
+        ctl = self._control(control_joints, control_weights, mean, std, dim_pose)
+        ctl = self._control_kwargs(ctl, control_scale, control_iters, slice(0, B), T, self.device)
         text = self._text_kwargs(m, caption, w, slice(0, B), T, self.device)
         return self._sample(
             m, (B, T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress, noise=noise,
-            step_noise=step_noise, model_kwargs={**text, "length": m_lens, **edit}, seed=seed,
+            step_noise=step_noise, model_kwargs={**text, "length": m_lens, **edit, **ctl}, seed=seed,
             sample_offset=sample_offset)
 
     @torch.no_grad()
     def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None, sampler="ddpm",
-                 sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, prompt_weights=None):
+                 sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
+                 control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None):
         """``seed``: sample i's noise is then a function of (seed, i) only (counter-based device generator), so the result
         does not depend on ``batch_size``; without it the torch generator is used, as in the reference.
         ``noises``: optional list with one ``(x_T, [step noise, ...])`` pair per batch, replacing the draws (parity tests).
         ``sampler`` / ``sample_steps`` / ``eta``: see ``sampling_diffusion``; e.g. ``sampler="dpmpp2m", sample_steps=20``.
         ``edit_motion`` (N, T_max, dim_pose) and ``edit_mask`` (broadcastable to it): motion editing, see ``generate_batch``;
         each batch takes its samples' rows.  ``prompt_weights`` (N, K, ...): composed prompts, see ``generate_batch``; each
-        batch takes its samples' rows."""
+        batch takes its samples' rows.  ``control_joints`` (N, T_max, J, 3), ``control_weights``, ``control_scale``,
+        ``control_iters``, ``mean``, ``std``: joint-position control, see ``generate_batch``; each batch takes its samples'
+        rows."""
         N = len(caption)
         self.eval_mode()
+        ctl = self._control(control_joints, control_weights, mean, std, dim_pose)
         if prompt_weights is not None:
             prompt_weights = self._compose_weights(caption, prompt_weights, dim_pose)
         if edit_motion is not None and edit_mask is not None:
@@ -178,7 +235,11 @@ class DDPMTrainer(object):
                                       sample_steps=sample_steps, eta=eta,
                                       edit_motion=None if edit_motion is None else edit_motion[cur:end],
                                       edit_mask=None if edit_mask is None else edit_mask[cur:end],
-                                      prompt_weights=None if prompt_weights is None else prompt_weights[cur:end])
+                                      prompt_weights=None if prompt_weights is None else prompt_weights[cur:end],
+                                      control_joints=None if ctl is None else ctl["joints"][cur:end],
+                                      control_weights=None if ctl is None else ctl["weights"][cur:end],
+                                      control_scale=control_scale, control_iters=control_iters,
+                                      mean=None if ctl is None else ctl["mean"], std=None if ctl is None else ctl["std"])
             all_output.extend(out[i] for i in range(out.shape[0]))
             cur += batch_size
         return all_output
@@ -186,18 +247,20 @@ class DDPMTrainer(object):
     @torch.no_grad()
     def generate_bucketed(self, caption, m_lens, dim_pose, batch_size=32, *, unit_length=4, seed=None, group=None,
                           progress=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
-                          prompt_weights=None):
+                          prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
+                          control_iters=1, mean=None, std=None):
         """Evaluation-scale variant of ``generate``: same inputs and the same kind of result (a
         list of per-sample ``(T_batch, dim_pose)`` tensors in the caller's order, valid up to each sample's length),
         but batches hold samples of similar length (less padded work) and, under ``torch.distributed``, are dealt over
         the ranks with one all_gather at the end.  With ``seed`` every sample's noise is a function of (seed, its index in
         ``caption``) only -- the same as ``generate(..., seed=)`` -- so on each sample's valid frames the two give identical
         results whatever the bucketing (tests/test_sampler_gpu.py).  ``edit_motion`` / ``edit_mask``: as in ``generate``;
-        each bucket takes its samples' rows and its first T frames; so does ``prompt_weights``."""
+        each bucket takes its samples' rows and its first T frames; so do ``prompt_weights`` and the ``control_*`` tensors."""
         from . import dist as D
         m = self._model()
         self.eval_mode()
         w = None if prompt_weights is None else self._compose_weights(caption, prompt_weights, dim_pose)
+        ctl = self._control(control_joints, control_weights, mean, std, dim_pose)
         lens = torch.as_tensor(m_lens).flatten().long().cpu()
         plan = D.plan_buckets(lens, batch_size, m.num_frames, unit_length)
 
@@ -206,9 +269,10 @@ class DDPMTrainer(object):
             ln = lens[idx].clamp(max=T).to(self.device)
             edit = self._edit_kwargs(edit_motion, edit_mask, idx, T, dim_pose)
             text = self._text_kwargs(m, cap, w, idx, T, self.device)
+            ck = self._control_kwargs(ctl, control_scale, control_iters, idx, T, self.device)
             return self._sample(
                 m, (len(cap), T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress,
-                model_kwargs={**text, "length": ln, **edit},
+                model_kwargs={**text, "length": ln, **edit, **ck},
                 seed=seed, sample_offset=idx)  # noise keyed on each row's index in the CALLER's list: == generate(seed=)
 
         return D.run_plan(plan, run_bucket, len(caption), m.num_frames, dim_pose, self.device, group)
@@ -258,13 +322,18 @@ class DDPMTrainer(object):
     @torch.no_grad()
     def generate_joints(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, joints_num=22, sigma=1.0,
                         bucketed=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
-                        prompt_weights=None, **kw):
+                        prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
+                        control_iters=1, **kw):
         """``generate`` followed by the reference's post-processing (tools/visualization.py:21-27,89) on the device:
         list of ``(m_len, joints_num, 3)`` joint positions, temporally smoothed with a gaussian of width ``sigma``.
         ``edit_motion`` / ``edit_mask``: motion editing in normalised feature space, as in ``generate``;
-        ``prompt_weights``: composed prompts, as in ``generate``."""
+        ``prompt_weights``: composed prompts, as in ``generate``; ``control_joints`` / ``control_weights`` /
+        ``control_scale`` / ``control_iters``: joint-position control under this call's ``mean`` / ``std``."""
         from .postprocess import motion_to_joints
         gen = self.generate_bucketed if bucketed else self.generate
+        if control_joints is not None or control_weights is not None:
+            kw = dict(kw, control_joints=control_joints, control_weights=control_weights, control_scale=control_scale,
+                      control_iters=control_iters, mean=mean, std=std)
         motions = gen(caption, m_lens, dim_pose, batch_size, sampler=sampler, sample_steps=sample_steps, eta=eta,
                       edit_motion=edit_motion, edit_mask=edit_mask, prompt_weights=prompt_weights, **kw)
         lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]

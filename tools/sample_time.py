@@ -20,6 +20,12 @@ reports both medians and the per-pair difference (median, min, max; per generati
 (a timeline split, ``prompt_weights``) against the same plain generations, alternating, as for ``--edit``; K may be a list.
 
     timeout -k 10 900 python tools/sample_time.py --compose 2,3 --reps 5 --precisions 1
+
+``--control I`` measures joint-position control instead: DDIM-50 and DPM-Solver++(2M)-20 generations steered toward target
+heights of every joint on every frame (``control_joints``/``control_weights``, ``control_iters`` = I) against the same plain generations, alternating, as for
+``--edit``; I may be a list.
+
+    timeout -k 10 900 python tools/sample_time.py --control 1,5 --reps 5 --precisions 1
 """
 import argparse
 import importlib
@@ -44,6 +50,7 @@ def main():
     ap.add_argument("--frames", type=int, default=196)
     ap.add_argument("--edit", default=None, help="prefix:N | inbetween:H,T: time editing against plain generation")
     ap.add_argument("--compose", default=None, help="K[,K...]: time K-prompt composed generation against plain")
+    ap.add_argument("--control", default=None, help="I[,I...]: time joint control with I iterations against plain")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_time.py measures the GPU sampler: no GPU found")
@@ -61,6 +68,8 @@ def main():
         return edit_main(a, tr, m, caps, length, B, T)
     if a.compose:
         return compose_main(a, tr, m, caps, length, B, T)
+    if a.control:
+        return control_main(a, tr, m, caps, length, B, T)
     rows = []
     for prec in [int(p) for p in a.precisions.split(",")]:
         m.precision = prec
@@ -193,6 +202,52 @@ def compose_main(a, tr, m, caps, length, B, T):
     for r in rows:
         print(f"{r['precision']:>9} {r['K']:>2} {r['sampler']:>22} {r['plain_ms']:>9.1f} {r['compose_ms']:>12.1f} "
               f"{r['ratio']:>6.2f} {(r['K'] + 1) / 2:>8.1f}")
+
+
+def control_main(a, tr, m, caps, length, B, T):
+    # every joint's height on every frame: the densest weight map (every steerable column is written on every iteration),
+    # and a loss quadratic in x0, so the unclipped random-weight samples stay finite at any step size used here
+    tg, w = torch.zeros(B, T, 22, 3), torch.zeros(B, T, 22, 3)
+    tg[..., 1], w[..., 1] = 1.0, 1.0
+    mean, std = torch.zeros(263), torch.ones(263)
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for iters in [int(k) for k in a.control.split(",")]:
+            for sampler, steps, n in (("ddim", 50, 50), ("dpmpp2m", 20, 20)):
+                def gen(ctl):
+                    extra = dict(control_joints=tg, control_weights=w, control_scale=0.05, control_iters=iters,
+                                 mean=mean, std=std) if ctl else {}
+                    return tr.generate(caps, length, 263, batch_size=B, seed=0, sampler=sampler, sample_steps=steps,
+                                       **extra)
+                for ctl in (False, True):  # warm-up
+                    assert all(torch.isfinite(o).all() for o in gen(ctl))
+                ts = {False: [], True: []}
+                for _ in range(a.reps):
+                    for ctl in (False, True):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        gen(ctl)
+                        torch.cuda.synchronize()
+                        ts[ctl].append((time.perf_counter() - t0) * 1e3)
+                med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+                diff = sorted(c - p for p, c in zip(ts[False], ts[True]))
+                name = {"ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+                line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, control_iters=iters,
+                            plain_ms=round(med[False], 2), control_ms=round(med[True], 2),
+                            diff_ms_median=round(diff[len(diff) // 2], 2), diff_ms_min=round(diff[0], 2),
+                            diff_ms_max=round(diff[-1], 2), diff_us_per_step=round(diff[len(diff) // 2] / n * 1e3, 1),
+                            plain_reps_ms=[round(t, 2) for t in ts[False]], control_reps_ms=[round(t, 2) for t in ts[True]])
+                rows.append(line)
+                print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}, guided (cfg 7.5), joint control (every joint's height); {torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'iters':>5} {'sampler':>22} {'plain ms':>9} {'control ms':>11} {'diff ms (min..max)':>22} "
+          f"{'us/step':>8}")
+    for r in rows:
+        spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
+        print(f"{r['precision']:>9} {r['control_iters']:>5} {r['sampler']:>22} {r['plain_ms']:>9.1f} "
+              f"{r['control_ms']:>11.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
 
 
 if __name__ == "__main__":
