@@ -456,6 +456,18 @@ int mdm_joint_guidance(float* x, float* x0, const float* mask, const int32_t* le
                        int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
                        void* stream);
 
+/* ---- long-motion handshakes ---------------------------------------------------------------------
+ * In place over the shared canvas frames only.  For every group g < groups, shared frame c < nshared and feature j < F:
+ *   v = sum over entries e in [offsets[c], offsets[c+1]) of weights[e] * x[g*group_stride + rows[e]*F + j]
+ *   (fp32 fmaf chain in entry order, from 0), then x[... rows[e] ...] = v for every e.
+ * weights == NULL: copy mode; every entry receives entry offsets[c]'s value bit for bit.
+ * rows[e] = window_row * T + frame; the rows of all entries must be distinct (each element is owned by one thread) and in
+ * range: both are the caller's tables, not checked here.  No allocation, no host sync, graph-capturable.
+ * MDM_ERR_ARG on null x / offsets / rows with nshared > 0, F < 1, groups < 1, nshared < 0 or group_stride < 0;
+ * nshared == 0 is a no-op. */
+int mdm_handshake_blend(float* x, int32_t groups, int64_t group_stride, int32_t F, int32_t nshared,
+                        const int32_t* offsets, const int32_t* rows, const float* weights, void* stream);
+
 /* ---- training step of the MoE feed-forward block --------------------------------------------
  * MoEMultiBranchFFN.forward (multi_branch.py:52-61) with both SwitchMoELayers (switch_moe.py:44-111) and the StylizationBlock
  * (stylization.py:20-31) in training mode, and its backward: what loss.backward() does for this block inside

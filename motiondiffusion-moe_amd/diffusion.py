@@ -32,6 +32,12 @@ Joint-position control: ``model_kwargs`` may carry ``control_joints`` (B, T, J, 
 ``control_mean`` / ``control_std`` (B, F), ``control_scale`` and ``control_iters``; every loop and single step then moves
 its x0 down the gradient of the weighted squared distance of ``recover_from_ric(x0 * std + mean)`` to the targets after its
 update, and x_{t-1} with it (``mdm_joint_guidance``): trajectories, keyframes, end positions.
+
+Long motions: ``model_kwargs`` may carry handshake tables (``handshake_offsets``, ``handshake_rows``,
+``handshake_weights``, ``handshake_owner_rows``, from ``motion_long``) over the rows of overlapping windows of one long
+motion; every step then blends the eps rows of the shared canvas frames before its update and copies the step noise (and
+the loops' x_T) from each overlap's owner window (``mdm_handshake_blend``), so the overlaps stay bit for bit
+equal.
 """
 from __future__ import annotations
 
@@ -331,7 +337,7 @@ class GaussianDiffusion:
         r._prepare()
         if noise is None:
             noise = torch.randn((B, r.T, r.Fe), device=r.dev)
-        r.xx[:B].copy_(noise.to(r.dev, torch.float32))
+        r._start(noise)
         r.t_dev.fill_(self.num_timesteps - 1)
         for i in range(self.num_timesteps):
             if r._needs_noise():
@@ -633,6 +639,70 @@ def check_control_kwargs(kw, shape):
     return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters)}
 
 
+def check_handshake_kwargs(kw, shape):
+    """The long-motion tables of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when none of the ``handshake_*``
+    keys is given or the tables have no shared frame, else a dict of CPU tensors ``offsets`` (nshared + 1), ``rows`` and
+    ``owner_rows`` int32 and ``weights`` float32 (one per entry), and ``nshared``.  The entries of shared frame c are
+    ``[offsets[c], offsets[c + 1])``, each a batch row times T plus a frame.
+    Raises ValueError when only some of the four are given, for tables that are not 1-D or whose sizes disagree, offsets
+    that do not start at 0, decrease or do not end at the entry count, a frame of fewer than two entries, rows outside
+    [0, B T) or repeated, owner rows that are not a reordering of each frame's rows, and weights that are not finite or do
+    not sum to 1 per frame (within 1e-5).  Raises NotImplementedError together with composed prompts or joint control.
+    Host logic."""
+    names = ("handshake_offsets", "handshake_rows", "handshake_weights", "handshake_owner_rows")
+    vals = [kw.get(k) for k in names]
+    given = [k for k, v in zip(names, vals) if v is not None]
+    if not given:
+        return None
+    if len(given) != 4:
+        raise ValueError(f"long-motion handshakes need all of {', '.join(names)}; missing "
+                         f"{', '.join(k for k in names if k not in given)}")
+    if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
+        raise NotImplementedError("composed prompts over a long motion are not supported yet")
+    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std")):
+        raise NotImplementedError("joint control over a long motion is not supported yet: its targets would need canvas "
+                                  "coordinates")
+    B, T, _ = (int(v) for v in shape)
+    off, rows, w, own = (torch.as_tensor(v).detach().cpu() for v in vals)
+    for name, v in zip(names, (off, rows, w, own)):
+        if v.dim() != 1:
+            raise ValueError(f"{name} must be 1-D, not of shape {tuple(v.shape)}")
+    for name, v in ((names[0], off), (names[1], rows), (names[3], own)):
+        if v.is_floating_point() or v.is_complex() or v.dtype == torch.bool:
+            raise ValueError(f"{name} must be integer")
+    if not w.is_floating_point():
+        raise ValueError("handshake_weights must be floating point")
+    off, rows, own = off.to(torch.int64), rows.to(torch.int64), own.to(torch.int64)
+    ne = rows.numel()
+    if off.numel() < 1 or int(off[0]) != 0 or int(off[-1]) != ne:
+        raise ValueError(f"handshake_offsets must run from 0 to the entry count {ne}")
+    if w.numel() != ne or own.numel() != ne:
+        raise ValueError(f"handshake_weights ({w.numel()}) and handshake_owner_rows ({own.numel()}) need one value per "
+                         f"entry of handshake_rows ({ne})")
+    ns = off.numel() - 1
+    cnt = off[1:] - off[:-1]
+    if ns and int(cnt.min()) < 2:
+        raise ValueError("every shared frame needs at least two entries, and offsets must not decrease")
+    for name, v in ((names[1], rows), (names[3], own)):
+        if ne and (int(v.min()) < 0 or int(v.max()) >= B * T):
+            raise ValueError(f"{name} must lie in [0, B * T) = [0, {B * T})")
+        if torch.unique(v).numel() != ne:
+            raise ValueError(f"{name} repeats a row: every element must belong to one shared frame")
+    fid = torch.repeat_interleave(torch.arange(ns), cnt)
+    key = lambda v: torch.sort(fid * (B * T) + v).values  # noqa: E731
+    if ne and not torch.equal(key(rows), key(own)):
+        raise ValueError("handshake_owner_rows must list each shared frame's rows (owner first), as handshake_rows does")
+    w64 = w.double()
+    if not bool(torch.isfinite(w64).all()):
+        raise ValueError("handshake_weights has non-finite values")
+    if ns and float((torch.zeros(ns, dtype=torch.float64).index_add_(0, fid, w64) - 1).abs().max()) > 1e-5:
+        raise ValueError("handshake_weights must sum to 1 over each shared frame")
+    if ns == 0:
+        return None
+    return {"offsets": off.to(torch.int32), "rows": rows.to(torch.int32), "weights": w.to(torch.float32),
+            "owner_rows": own.to(torch.int32), "nshared": ns}
+
+
 class _StepRunner:
     """Static buffers + (optionally) one captured hipGraph for a whole denoising step."""
 
@@ -738,6 +808,12 @@ class _StepRunner:
                             std=torch.empty((B, Fe), dtype=torch.float32, device=self.dev))
             for k in ("targets", "weights", "mean", "std"):
                 self.ctl[k].copy_(ctl[k])
+        # long motions: the handshake tables of the overlapping windows, owned by the runner
+        hs = check_handshake_kwargs(kw, shape)
+        self.hs = None
+        if hs is not None:
+            self.hs = {k: hs[k].to(self.dev).contiguous() for k in ("offsets", "rows", "weights", "owner_rows")}
+            self.hs["nshared"] = hs["nshared"]
         # few-step modes (and every mode when editing, composing or controlling): per-step coefficients of the fused update;
         # self.x0 doubles as x0_prev (updated in place)
         table = self.known is not None or self.cw is not None or self.ctl is not None
@@ -789,6 +865,8 @@ class _StepRunner:
         B, n = self.B, self.n
         if use_noise and self.philox is not None:  # step noise = f(seed, global sample, t, element); t read on the device
             self._philox_fill(self.noise, C.c_void_p(self.t_dev.data_ptr()), 0, s)
+        if use_noise and self.hs is not None:  # the owner window's noise in every overlap (host-filled noise too)
+            self._handshake(self.noise, 1, False, s)
         x = self.xx[:B]
         if self.K > 1:  # x_t into every prompt group and the unconditional one
             self.xx[B:].view(self.K, B, self.T, self.Fe).copy_(x.unsqueeze(0).expand(self.K, -1, -1, -1))
@@ -822,6 +900,8 @@ class _StepRunner:
             self.model(self.xx, self.ts, self.len2, xf_proj=self.xp, xf_out=self.xo, out=self.eps, stem_cache=self.stem)
         else:
             self.model(self.xx, self.ts, self.len2, xf_proj=self.xp, xf_out=self.xo, out=self.eps)
+        if self.hs is not None:  # one eps per shared canvas frame, in every row group, before the update reads it
+            self._handshake(self.eps, self.R // B, True, s)
         noise = C.c_void_p(self.noise.data_ptr() if use_noise else 0)
         steps = C.c_int32(self.d.num_timesteps)
         if self.cw is not None:
@@ -874,6 +954,22 @@ class _StepRunner:
                 C.c_int32(self.Fe), C.c_float(c["scale"]), C.c_int32(c["iters"]), C.c_void_p(self.coef.data_ptr()), steps,
                 C.c_void_p(self.t_dev.data_ptr()), C.c_int32(0), s), "mdm_joint_guidance")
         L.check(lib.mdm_add_i32(C.c_void_p(self.t_dev.data_ptr()), C.c_int32(-1), s))
+
+    def _handshake(self, buf, groups, blend: bool, s):
+        """mdm_handshake_blend over ``groups`` consecutive groups of B rows of ``buf``: the weighted mean of the eps rows
+        (``blend``) or the owner's values (copy) written to every window row of each shared frame."""
+        h = self.hs
+        L.check(L.lib().mdm_handshake_blend(
+            C.c_void_p(buf.data_ptr()), C.c_int32(groups), C.c_int64(self.n), C.c_int32(self.Fe), C.c_int32(h["nshared"]),
+            C.c_void_p(h["offsets"].data_ptr()), C.c_void_p((h["rows"] if blend else h["owner_rows"]).data_ptr()),
+            C.c_void_p(h["weights"].data_ptr() if blend else 0), s), "mdm_handshake_blend")
+
+    def _start(self, x_T):
+        """x_T into the model input rows; with handshakes each overlap takes its owner window's values."""
+        self.xx[:self.B].copy_(x_T.to(self.dev, torch.float32))
+        if self.hs is not None:
+            with torch.cuda.device(self.dev):
+                self._handshake(self.xx, 1, False, C.c_void_p(L.stream_ptr()))
 
     def _needs_noise(self) -> bool:
         if self.mode == "cfg_dpmpp":
@@ -949,7 +1045,7 @@ class _StepRunner:
             self.graph = g
         if noise is None:
             noise = self.draw_xT(seed, sample_offset) if seed is not None else torch.randn((B, self.T, self.Fe), device=self.dev)
-        self.xx[:B].copy_(noise.to(self.dev, torch.float32))
+        self._start(noise)
         self.t_dev.fill_(d.num_timesteps - 1)
         it = range(d.num_timesteps)
         if progress:

@@ -1,0 +1,151 @@
+"""Long motions from overlapping windows: host tables for the handshake kernel (csrc/handshake.hip).
+
+A long motion is a script of segments ``(caption_i, length_i)``, each at most the model's ``num_frames``, and an overlap
+``h``.  Window i covers canvas frames ``[s_i, s_i + length_i)`` with ``s_0 = 0`` and ``s_{i+1} = s_i + length_i - h``; the
+canvas has ``sum(length_i) - (n - 1) h`` frames.  With ``0 <= h <= min(length_i) / 2`` no canvas frame is covered by more
+than two windows.  The windows are rows of one sampler batch, padded to a common T.
+
+Every canvas frame two windows cover is a "shared frame" of the tables: its entries are that frame's row in the left
+window, then in the right one (``rows[e] = window_row * T + frame``).  On every step the sampler writes the weighted mean of
+the two eps rows back into both (``weights``: a linear crossfade, the right window weighing ``(j + 1) / (h + 1)`` at overlap
+frame j, or ``"uniform"`` halves), and copies x_T and the step noise from the left ("owner") window into the right one.
+The overlap frames of neighbouring windows then stay bit for bit equal on every step, and the canvas is the windows' valid
+frames.  Host logic only: runs without a GPU.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+BLENDS = ("linear", "uniform")
+
+
+def _int(v, name: str) -> int:
+    if isinstance(v, bool) or int(v) != v:
+        raise ValueError(f"{name} must be an integer, not {v!r}")
+    return int(v)
+
+
+def plan_windows(lengths: Sequence[int], overlap: int, max_len: Optional[int] = None) -> Tuple[List[int], int]:
+    """Window starts and the canvas length of a script with these window ``lengths`` and ``overlap`` frames.
+    Raises ValueError for an empty script, a length below 1 or above ``max_len``, and an overlap below 0 or above half
+    the shortest window."""
+    lengths = [_int(n, "a window length") for n in lengths]
+    h = _int(overlap, "overlap")
+    if not lengths:
+        raise ValueError("a long motion needs at least one window")
+    if min(lengths) < 1:
+        raise ValueError(f"window lengths must be >= 1, not {min(lengths)}")
+    if max_len is not None and max(lengths) > max_len:
+        raise ValueError(f"window length {max(lengths)} exceeds the model's {max_len} frames")
+    if h < 0:
+        raise ValueError(f"overlap must be >= 0, not {h}")
+    if 2 * h > min(lengths):
+        raise ValueError(f"overlap {h} exceeds half the shortest window ({min(lengths)} frames): a frame would be covered "
+                         "by more than two windows")
+    starts = [0]
+    for n in lengths[:-1]:
+        starts.append(starts[-1] + n - h)
+    return starts, starts[-1] + lengths[-1]
+
+
+def _check_plan(starts, lengths, T, overlap):
+    starts, lengths = list(starts), list(lengths)
+    if len(starts) != len(lengths):
+        raise ValueError(f"{len(starts)} starts for {len(lengths)} windows")
+    want, _ = plan_windows(lengths, overlap)
+    if [int(s) for s in starts] != want:
+        raise ValueError(f"starts {starts} do not follow from lengths {lengths} and overlap {overlap}: {want}")
+    if _int(T, "T") < max(lengths):
+        raise ValueError(f"T = {T} is shorter than the longest window ({max(lengths)} frames)")
+    return want, [int(n) for n in lengths]
+
+
+def handshake_tables(starts, lengths, T: int, overlap: int, blend: str = "linear", first_row: int = 0) -> Dict:
+    """The tables of one long motion whose windows are batch rows ``first_row, first_row + 1, ...`` padded to T frames:
+    ``offsets`` int32 (nshared + 1), ``rows`` int32 (2 nshared; left window first), ``weights`` float32 like ``rows``
+    (``blend`` "linear" or "uniform"), and the owner table ``owner_rows`` (its first entry per frame, the left window, is
+    the source of the copy; its weights are None)."""
+    if blend not in BLENDS:
+        raise ValueError(f"blend must be one of {BLENDS}, not {blend!r}")
+    starts, lengths = _check_plan(starts, lengths, T, overlap)
+    h, n = int(overlap), len(lengths)
+    rows, weights = [], []
+    for i in range(n - 1):
+        left, right = first_row + i, first_row + i + 1
+        for j in range(h):
+            wr = (j + 1) / (h + 1) if blend == "linear" else 0.5
+            rows += [left * T + lengths[i] - h + j, right * T + j]
+            weights += [1.0 - wr, wr]
+    ns = (n - 1) * h
+    rows = np.asarray(rows, dtype=np.int32).reshape(-1)
+    return {"offsets": np.arange(0, 2 * ns + 1, 2, dtype=np.int32), "rows": rows,
+            "weights": np.asarray(weights, dtype=np.float32).reshape(-1), "owner_rows": rows.copy()}
+
+
+def merge_tables(tables: Sequence[Dict]) -> Dict:
+    """The tables of several long motions in one batch (each built with its own ``first_row``), concatenated."""
+    offsets, rows, weights, owner, base = [np.zeros(1, np.int32)], [], [], [], 0
+    for t in tables:
+        offsets.append(t["offsets"][1:] + base)
+        base += int(t["offsets"][-1])
+        rows.append(t["rows"]), weights.append(t["weights"]), owner.append(t["owner_rows"])
+    cat = lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dt)  # noqa: E731
+    return {"offsets": np.concatenate(offsets).astype(np.int32), "rows": cat(rows, np.int32),
+            "weights": cat(weights, np.float32), "owner_rows": cat(owner, np.int32)}
+
+
+def split_long(caption: str, total_frames: int, window: int, overlap: int) -> List[Tuple[str, int]]:
+    """A script for one caption over ``total_frames`` canvas frames: the fewest windows of at most ``window`` frames that
+    cover it with ``overlap`` shared frames between neighbours, lengths as even as possible (the longer ones first)."""
+    total, window, h = _int(total_frames, "total_frames"), _int(window, "window"), _int(overlap, "overlap")
+    if total < 1:
+        raise ValueError(f"total_frames must be >= 1, not {total}")
+    if window < 1 or h < 0 or 2 * h > window:
+        raise ValueError(f"need window >= 1 and 0 <= overlap <= window / 2, not window {window}, overlap {h}")
+    n = 1 if total <= window else math.ceil((total - h) / (window - h))
+    size, extra = divmod(total + (n - 1) * h, n)
+    lengths = [size + (1 if i < extra else 0) for i in range(n)]
+    plan_windows(lengths, h, window)  # the shortest window must still hold two overlaps
+    return [(caption, n_) for n_ in lengths]
+
+
+def _span(starts, lengths):
+    """Checked windows (starts, lengths) that tile a canvas from frame 0 without gaps, and its length."""
+    starts, lengths = [int(s) for s in starts], [int(n) for n in lengths]
+    if len(starts) != len(lengths) or not starts:
+        raise ValueError(f"{len(starts)} starts for {len(lengths)} windows")
+    if starts[0] != 0 or min(lengths) < 1 or any(not starts[i] < starts[i + 1] <= starts[i] + lengths[i]
+                                                 for i in range(len(starts) - 1)):
+        raise ValueError(f"windows at {starts} of {lengths} frames do not tile a canvas from frame 0")
+    return starts, lengths, starts[-1] + lengths[-1]
+
+
+def canvas_to_windows(canvas: torch.Tensor, starts, lengths, T: int) -> torch.Tensor:
+    """Gather a canvas (C, ...) into the window layout (n, T, ...); frames past each window's length are zero."""
+    starts, lengths, C = _span(starts, lengths)
+    canvas = torch.as_tensor(canvas)
+    if canvas.dim() < 1 or canvas.shape[0] != C:
+        raise ValueError(f"the canvas has {canvas.shape[0] if canvas.dim() else 0} frames, the windows cover {C}")
+    if max(lengths) > T:
+        raise ValueError(f"T = {T} is shorter than the longest window ({max(lengths)} frames)")
+    out = canvas.new_zeros((len(starts), T) + tuple(canvas.shape[1:]))
+    for i, (s, n) in enumerate(zip(starts, lengths)):
+        out[i, :n] = canvas[s:s + n]
+    return out
+
+
+def windows_to_canvas(windows: torch.Tensor, starts, lengths) -> torch.Tensor:
+    """Scatter windows (n, T, ...) onto their canvas (C, ...): each canvas frame taken from the first window covering it
+    (the owner; after a handshake sampler its right neighbour holds the same bits there)."""
+    starts, lengths, C = _span(starts, lengths)
+    if windows.dim() < 2 or windows.shape[0] != len(starts) or windows.shape[1] < max(lengths):
+        raise ValueError(f"windows of shape {tuple(windows.shape)} do not hold {len(starts)} windows of up to "
+                         f"{max(lengths)} frames")
+    out = windows.new_empty((C,) + tuple(windows.shape[2:]))
+    for i in reversed(range(len(starts))):
+        out[starts[i]:starts[i] + lengths[i]] = windows[i, :lengths[i]]
+    return out

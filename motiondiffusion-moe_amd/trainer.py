@@ -8,7 +8,9 @@ run the reference's guided DDPM over every step.  ``edit_motion`` / ``edit_mask`
 (prefix completion, in-betweening, body-part regeneration; masks from ``motion_edit``).  ``prompt_weights`` with K
 captions per sample composes them under per-prompt weight maps (time-varied and body-part control, negative prompts;
 weights from ``motion_compose``).  ``control_joints`` / ``control_weights`` (with ``mean`` / ``std``) steer joint positions:
-trajectories, keyframes, end positions (targets from ``motion_control``).  The training loop (forward/backward/update/train) is out of
+trajectories, keyframes, end positions (targets from ``motion_control``).  ``generate_long`` samples motions longer than
+the model's window from scripts of ``(caption, length)`` segments, overlapping windows tied together on every step
+(``motion_long``).  The training loop (forward/backward/update/train) is out of
 scope for this build and raises.
 """
 from __future__ import annotations
@@ -20,6 +22,7 @@ from .diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType
                         space_timesteps)
 
 SAMPLERS = ("ddpm", "ddim", "dpmpp2m")
+MAX_JOINTS_FRAMES = 3276  # frames of mdm_motion_postprocess: 5 T floats of LDS per workgroup, 64 KiB
 
 
 class DDPMTrainer(object):
@@ -341,6 +344,136 @@ class DDPMTrainer(object):
         for i, mo in enumerate(motions):
             x[i, :mo.shape[0]] = mo
         j = motion_to_joints(x, mean, std, torch.tensor(lens), joints_num, sigma)  # one launch for all samples
+        return [j[i, :n] for i, n in enumerate(lens)]
+
+    @torch.no_grad()
+    def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
+                      sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, noise=None, progress=False):
+        """Long motions: ``scripts`` is a list of long motions, each a list of ``(caption, length)``
+        segments of at most ``num_frames`` frames; neighbouring segments share ``overlap`` canvas frames, whose eps is
+        blended on every step (``blend`` "linear" crossfade or "uniform") while x_T and the step noise come from the left
+        window.  Returns one ``(canvas_len, dim_pose)`` tensor per motion, canvas_len = sum(length) - (n - 1) overlap.
+        ``batch_size`` counts windows; a motion's windows stay in one batch.  ``seed``: window k of the call (counting
+        the windows of all motions in order) is global sample k of the counter-based generator, so the result does not
+        depend on ``batch_size``.  ``edit_motion`` / ``edit_mask``: one (canvas_len, dim_pose) known motion per motion and
+        a mask broadcastable to it (or None entries), kept where the mask is 1, e.g. a prefix to continue.  ``noise``: one
+        (canvas_len, dim_pose) x_T per motion.  ``sampler`` / ``sample_steps`` / ``eta`` as in ``generate``."""
+        from . import motion_long as ML
+        m = self._model()
+        self.eval_mode()
+        plans = self._long_plans(scripts, overlap, m.num_frames)
+        N = len(plans)
+        per = {}
+        for name, v in (("edit_motion", edit_motion), ("edit_mask", edit_mask), ("noise", noise)):
+            if v is not None and len(v) != N:
+                raise ValueError(f"{name} must hold one entry per motion ({N}), not {len(v)}")
+            per[name] = [None] * N if v is None else list(v)
+        if (edit_motion is None) != (edit_mask is None):
+            raise ValueError("edit_motion and edit_mask go together: give both or neither")
+        for i, (km, mk) in enumerate(zip(per["edit_motion"], per["edit_mask"])):
+            if (km is None) != (mk is None):
+                raise ValueError(f"motion {i}: edit_motion and edit_mask go together")
+        if any(km is not None for km in per["edit_motion"]) and not all(km is not None for km in per["edit_motion"]):
+            raise ValueError("edit_motion must be given for every motion of the call or for none")
+        if any(x is not None for x in per["noise"]) and not all(x is not None for x in per["noise"]):
+            raise ValueError("noise must be given for every motion of the call or for none")
+        batches, cur, first = [], [], 0  # whole motions, at most batch_size windows each
+        for i, (caps, lens, starts, C) in enumerate(plans):
+            if len(lens) > batch_size:
+                raise ValueError(f"motion {i} has {len(lens)} windows, more than batch_size = {batch_size}")
+            if cur and sum(len(plans[j][1]) for j in cur) + len(lens) > batch_size:
+                batches.append(cur)
+                cur = []
+            cur.append(i)
+        if cur:
+            batches.append(cur)
+        out = [None] * N
+        for idx in batches:
+            caps = [c for i in idx for c in plans[i][0]]
+            lens = [n for i in idx for n in plans[i][1]]
+            T = max(lens) + max(lens) % 2  # the denoiser takes even T
+            tabs, row = [], 0
+            for i in idx:
+                tabs.append(ML.handshake_tables(plans[i][2], plans[i][1], T, overlap, blend, first_row=row))
+                row += len(plans[i][1])
+            tab = ML.merge_tables(tabs)
+            kw = {"handshake_offsets": torch.from_numpy(tab["offsets"]), "handshake_rows": torch.from_numpy(tab["rows"]),
+                  "handshake_weights": torch.from_numpy(tab["weights"]),
+                  "handshake_owner_rows": torch.from_numpy(tab["owner_rows"])}
+
+            def gather(v, what):
+                parts = []
+                for i in idx:
+                    _, ln, st, C = plans[i]
+                    x = torch.as_tensor(v[i], dtype=torch.float32)
+                    try:
+                        x = torch.broadcast_to(x, (C, dim_pose))
+                    except RuntimeError:
+                        raise ValueError(f"{what} of motion {i} has shape {tuple(x.shape)}, not broadcastable to its "
+                                         f"canvas {(C, dim_pose)}") from None
+                    parts.append(ML.canvas_to_windows(x, st, ln, T))
+                return torch.cat(parts).to(self.device)
+
+            if per["edit_motion"][idx[0]] is not None:
+                for i in idx:
+                    if tuple(torch.as_tensor(per["edit_motion"][i]).shape) != (plans[i][3], dim_pose):
+                        raise ValueError(f"edit_motion of motion {i} must be {(plans[i][3], dim_pose)}")
+                kw["inpaint_motion"] = gather(per["edit_motion"], "edit_motion")
+                kw["inpaint_mask"] = gather(per["edit_mask"], "edit_mask")
+            x_T = None
+            if per["noise"][idx[0]] is not None:
+                for i in idx:
+                    if tuple(torch.as_tensor(per["noise"][i]).shape) != (plans[i][3], dim_pose):
+                        raise ValueError(f"noise of motion {i} must be {(plans[i][3], dim_pose)}")
+                x_T = gather(per["noise"], "noise")
+            text = self._text_kwargs(m, caps, None, None, T, self.device)
+            res = self._sample(m, (len(caps), T, dim_pose), sampler, sample_steps, eta, clip_denoised=False,
+                               progress=progress, noise=x_T, model_kwargs={**text, "length": torch.tensor(lens), **kw},
+                               seed=seed, sample_offset=first)
+            first += len(caps)
+            row = 0
+            for i in idx:
+                n = len(plans[i][1])
+                out[i] = ML.windows_to_canvas(res[row:row + n], plans[i][2], plans[i][1])
+                row += n
+        return out
+
+    @staticmethod
+    def _long_plans(scripts, overlap, num_frames):
+        """Checked scripts: per motion (captions, lengths, window starts, canvas length)."""
+        from . import motion_long as ML
+        if isinstance(scripts, (str, bytes)) or len(scripts) == 0:
+            raise ValueError("scripts must be a non-empty list of long motions, each a list of (caption, length)")
+        plans = []
+        for i, sc in enumerate(scripts):
+            if isinstance(sc, (str, bytes)) or len(sc) == 0:
+                raise ValueError(f"motion {i}: a script is a non-empty list of (caption, length) segments")
+            caps, lens = [], []
+            for seg in sc:
+                if len(seg) != 2 or not isinstance(seg[0], str):
+                    raise ValueError(f"motion {i}: segment {seg!r} is not a (caption, length) pair")
+                caps.append(seg[0])
+                lens.append(seg[1])
+            starts, C = ML.plan_windows(lens, overlap, num_frames)
+            plans.append((caps, [int(n) for n in lens], starts, C))
+        return plans
+
+    @torch.no_grad()
+    def generate_long_joints(self, scripts, dim_pose, mean, std, *, joints_num=22, sigma=1.0, **kw):
+        """``generate_long`` followed by ``postprocess.motion_to_joints`` over each whole canvas (one continuous root
+        path): a list of ``(canvas_len, joints_num, 3)`` joint positions.  The post-processing kernel holds a canvas in
+        LDS: at most MAX_JOINTS_FRAMES frames."""
+        from .postprocess import motion_to_joints
+        plans = self._long_plans(scripts, kw.get("overlap", 20), self._model().num_frames)
+        longest = max(p[3] for p in plans)
+        if longest > MAX_JOINTS_FRAMES:
+            raise ValueError(f"a canvas of {longest} frames: joint recovery takes at most {MAX_JOINTS_FRAMES} frames")
+        motions = self.generate_long(scripts, dim_pose, **kw)
+        lens = [mo.shape[0] for mo in motions]
+        x = torch.zeros((len(motions), max(lens), dim_pose), device=motions[0].device)
+        for i, mo in enumerate(motions):
+            x[i, :mo.shape[0]] = mo
+        j = motion_to_joints(x, mean, std, torch.tensor(lens), joints_num, sigma)
         return [j[i, :n] for i, n in enumerate(lens)]
 
     def save(self, file_name, ep, total_it):

@@ -26,6 +26,12 @@ heights of every joint on every frame (``control_joints``/``control_weights``, `
 ``--edit``; I may be a list.
 
     timeout -k 10 900 python tools/sample_time.py --control 1,5 --reps 5 --precisions 1
+
+``--long H`` measures long-motion generation instead: the batch's windows as B / 4 long motions of four windows each,
+neighbours sharing H frames (``generate_long``, eps blended and noise copied on every step), against plain generations of
+the same B windows, DDIM-50 and DPM-Solver++(2M)-20, alternating, as for ``--edit``.
+
+    timeout -k 10 900 python tools/sample_time.py --long 20 --reps 5 --precisions 1
 """
 import argparse
 import importlib
@@ -51,6 +57,8 @@ def main():
     ap.add_argument("--edit", default=None, help="prefix:N | inbetween:H,T: time editing against plain generation")
     ap.add_argument("--compose", default=None, help="K[,K...]: time K-prompt composed generation against plain")
     ap.add_argument("--control", default=None, help="I[,I...]: time joint control with I iterations against plain")
+    ap.add_argument("--long", type=int, default=None, help="H: time long motions (4 windows each, H shared frames) "
+                    "against plain generation of the same windows")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_time.py measures the GPU sampler: no GPU found")
@@ -70,6 +78,8 @@ def main():
         return compose_main(a, tr, m, caps, length, B, T)
     if a.control:
         return control_main(a, tr, m, caps, length, B, T)
+    if a.long is not None:
+        return long_main(a, tr, m, caps, B, T)
     rows = []
     for prec in [int(p) for p in a.precisions.split(",")]:
         m.precision = prec
@@ -248,6 +258,53 @@ def control_main(a, tr, m, caps, length, B, T):
         spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
         print(f"{r['precision']:>9} {r['control_iters']:>5} {r['sampler']:>22} {r['plain_ms']:>9.1f} "
               f"{r['control_ms']:>11.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
+
+
+def long_main(a, tr, m, caps, B, T):
+    if B % 4:
+        raise SystemExit("--long needs a batch of whole 4-window motions")
+    h = a.long
+    scripts = [[(caps[4 * i + k], T) for k in range(4)] for i in range(B // 4)]
+    full = torch.full((B,), T)
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for sampler, steps, n in (("ddim", 50, 50), ("dpmpp2m", 20, 20)):
+            def gen(long):
+                if long:
+                    return tr.generate_long(scripts, 263, overlap=h, batch_size=B, seed=0, sampler=sampler,
+                                            sample_steps=steps)
+                return tr.generate(caps, full, 263, batch_size=B, seed=0, sampler=sampler, sample_steps=steps)
+            for long in (False, True):  # warm-up
+                assert all(torch.isfinite(o).all() for o in gen(long))
+            ts = {False: [], True: []}
+            for _ in range(a.reps):
+                for long in (False, True):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    gen(long)
+                    torch.cuda.synchronize()
+                    ts[long].append((time.perf_counter() - t0) * 1e3)
+            med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+            diff = sorted(c - p for p, c in zip(ts[False], ts[True]))
+            name = {"ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+            line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, overlap=h, motions=B // 4,
+                        canvas_frames=4 * T - 3 * h, plain_ms=round(med[False], 2), long_ms=round(med[True], 2),
+                        diff_ms_median=round(diff[len(diff) // 2], 2), diff_ms_min=round(diff[0], 2),
+                        diff_ms_max=round(diff[-1], 2), diff_us_per_step=round(diff[len(diff) // 2] / n * 1e3, 1),
+                        diff_share=round(diff[len(diff) // 2] / med[False], 4),
+                        plain_reps_ms=[round(t, 2) for t in ts[False]], long_reps_ms=[round(t, 2) for t in ts[True]])
+            rows.append(line)
+            print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}, guided (cfg 7.5), {B // 4} long motions of 4 windows, overlap {h}; "
+          f"{torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'sampler':>22} {'plain ms':>9} {'long ms':>9} {'diff ms (min..max)':>22} {'us/step':>8} "
+          f"{'share':>7}")
+    for r in rows:
+        spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
+        print(f"{r['precision']:>9} {r['sampler']:>22} {r['plain_ms']:>9.1f} {r['long_ms']:>9.1f} {spread:>22} "
+              f"{r['diff_us_per_step']:>8.1f} {r['diff_share']:>7.2%}")
 
 
 if __name__ == "__main__":
