@@ -1,0 +1,335 @@
+"""Host side of every conditioning input of the sampler: what a generate call is given besides captions and lengths.
+
+``expand_to`` is the one align-and-expand of a weight / mask tensor.  The ``check_*_kwargs`` functions validate the
+``model_kwargs`` of one sampler batch (motion editing, composed prompts, joint control, long-motion handshakes; DESIGN.md
+§11, §12, §14, §15) for ``diffusion._StepRunner``; ``diffusion`` imports them under the same names.  ``Conditioning``
+holds the checked conditioning of one public ``DDPMTrainer`` call and hands out each batch's share as ``model_kwargs``.
+Host logic only: runs on CPU tensors and never loads the HIP library.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+# runner modes with classifier-free guidance: [cond | uncond] = 2B rows, (K + 1)B with K composed prompts
+GUIDED = ("cfg", "cfg_ddim", "cfg_dpmpp")
+
+
+def expand_to(t, lead, shape, name, lead_msg="", fail_msg="{name} of shape {shape} does not broadcast to {target}"):
+    """``t`` expanded to ``shape`` (a view; nothing is copied; -1 keeps a dim).  With ``lead`` an int, ``t`` must have
+    at most ``len(shape)`` dims and lead with ``shape[:lead]``, and is aligned on its leading dims: padded with trailing
+    size-1 dims, so (B,) is per sample and (B, T) per frame.  ``lead=None``: ordinary trailing-aligned broadcasting.
+    Raises ValueError ``"{name} of shape ... {lead_msg}"`` for the leading dims and ``fail_msg`` (formatted with name, the
+    given shape, the padded shape and target) for a tensor that does not broadcast."""
+    t = torch.as_tensor(t)
+    shape, had = tuple(shape), tuple(t.shape)
+    if lead is not None:
+        if t.dim() < lead or t.dim() > len(shape) or had[:lead] != shape[:lead]:
+            raise ValueError(f"{name} of shape {had} {lead_msg}")
+        t = t.reshape(had + (1,) * (len(shape) - t.dim()))
+    try:
+        return t.expand(shape)
+    except RuntimeError:
+        raise ValueError(fail_msg.format(name=name, shape=had, padded=tuple(t.shape), target=shape)) from None
+
+
+def check_inpaint_kwargs(kw, shape):
+    """The editing inputs of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when neither ``inpaint_motion`` nor
+    ``inpaint_mask`` is given, else (known, mask) with ``mask`` broadcast to ``shape`` (a view; nothing is copied).
+    A mask of fewer dims than the sample is aligned on its leading (batch) dim: (B,) is per sample, (B, T) per frame.
+    Raises ValueError for one without the other, a motion not shaped ``shape``, a mask whose leading dim is not B or that
+    does not broadcast, values outside [0, 1] or non-finite values.  Host logic: runs on CPU tensors as well."""
+    known, mask = kw.get("inpaint_motion"), kw.get("inpaint_mask")
+    if known is None and mask is None:
+        return None
+    if known is None or mask is None:
+        raise ValueError("inpaint_motion and inpaint_mask go together: give both or neither")
+    known = torch.as_tensor(known)
+    shape = tuple(int(v) for v in shape)
+    if tuple(known.shape) != shape:
+        raise ValueError(f"inpaint_motion has shape {tuple(known.shape)}, the sample {shape}")
+    mask = expand_to(mask, 1, shape, "inpaint_mask", f"must lead with the batch size {shape[0]}")
+    if not (known.is_floating_point() and mask.is_floating_point()):
+        raise ValueError("inpaint_motion and inpaint_mask must be floating point")
+    if not bool(torch.isfinite(known).all()):
+        raise ValueError("inpaint_motion has non-finite values")
+    if not bool(((mask >= 0) & (mask <= 1)).all()):  # NaN fails both comparisons
+        raise ValueError("inpaint_mask values must lie in [0, 1]")
+    return known, mask
+
+
+def check_compose_kwargs(kw, shape, mode=None):
+    """The composition inputs of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when no ``compose_*`` key is
+    given, else a dict with ``weights`` broadcast to (B, K, T, F) (a view), ``K``, and either ``xf_proj`` (B, K, Dt) and
+    ``xf_out`` (B, K, N, Dt) or ``text`` (B lists of K captions, for ``model.encode_text``).  Every input leads with B, so
+    dist.shard_kwargs slices them.  The weights lead with (B, K) and are aligned on those dims: (B, K) is per sample and
+    prompt, (B, K, T) per frame, (B, K, 1, F) per feature column.
+    Raises ValueError for weights without prompts or prompts without weights, both embeddings and captions, one embedding
+    without the other, shape or broadcast errors, K differing between samples or above MDM_COMPOSE_MAX_K, non-finite
+    weights, ``xf_proj`` / ``xf_out`` given as well, and (with ``mode``) a mode without guidance.  Host logic."""
+    w, cp, co, ct = (kw.get(k) for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text"))
+    if w is None and cp is None and co is None and ct is None:
+        return None
+    if mode is not None and mode not in GUIDED:
+        raise ValueError(f"composed prompts need classifier-free guidance; mode {mode!r} has none")
+    if kw.get("xf_proj") is not None or kw.get("xf_out") is not None:
+        raise ValueError("xf_proj / xf_out and compose_* are exclusive: the prompts of a composed sample are compose_*")
+    if w is None:
+        raise ValueError("compose_weights is required with composed prompts")
+    if ct is not None and (cp is not None or co is not None):
+        raise ValueError("give compose_text or compose_xf_proj / compose_xf_out, not both")
+    if ct is None and (cp is None or co is None):
+        raise ValueError("composed prompts need compose_text or both compose_xf_proj and compose_xf_out")
+    B, T, F_ = (int(v) for v in shape)
+    if ct is not None:
+        if isinstance(ct, str) or len(ct) != B:
+            raise ValueError(f"compose_text must hold {B} sequences of captions, one per sample")
+        for seq in ct:
+            if isinstance(seq, str) or not all(isinstance(c, str) for c in seq):
+                raise ValueError("each entry of compose_text must be a sequence of caption strings")
+        ks = {len(seq) for seq in ct}
+        if len(ks) != 1:
+            raise ValueError(f"every sample must have the same number of prompts, not {sorted(ks)}")
+        K = ks.pop()
+        ct = [list(seq) for seq in ct]
+    else:
+        cp, co = torch.as_tensor(cp), torch.as_tensor(co)
+        if cp.dim() != 3 or co.dim() != 4 or cp.shape[0] != B or co.shape[0] != B or cp.shape[1] != co.shape[1]:
+            raise ValueError(f"compose_xf_proj {tuple(cp.shape)} / compose_xf_out {tuple(co.shape)} must be (B={B}, K, Dt) "
+                             "and (B, K, N, Dt)")
+        K = int(cp.shape[1])
+    if not 1 <= K <= L.COMPOSE_MAX_K:
+        raise ValueError(f"{K} prompts per sample: the composed update takes 1 to {L.COMPOSE_MAX_K}")
+    w = torch.as_tensor(w)
+    if not w.is_floating_point():
+        raise ValueError("compose_weights must be floating point")
+    w = expand_to(w, 2, (B, K, T, F_), "compose_weights", f"must lead with (B, K) = {(B, K)} and have at most 4 dims")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("compose_weights has non-finite values")
+    return {"weights": w, "K": K, "xf_proj": cp, "xf_out": co, "text": ct}
+
+
+def check_control_kwargs(kw, shape):
+    """The joint-control inputs of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when none of the ``control_*``
+    keys is given, else a dict with ``targets`` (B, T, J, 3), ``weights`` broadcast to it (a view), ``mean`` / ``std``
+    (B, F), ``scale`` (float, default 1) and ``iters`` (int, default 1).  Every tensor leads with B, so dist.shard_kwargs
+    slices them; the weights are aligned on that dim: (B,) per sample, (B, T) per frame, (B, T, J) per joint.
+    Raises ValueError when only some of the four tensors are given (or a scale / iters without them), for an F not of the
+    form 12 J - 1, a T over the kernels' LDS limit, shape or broadcast errors, non-finite targets, weights, mean or std,
+    negative weights, a zero std, a non-finite scale or iters outside [1, MDM_CONTROL_MAX_ITERS].  Host logic."""
+    from .motion_control import joints_for_feats, max_frames
+    names = ("control_joints", "control_weights", "control_mean", "control_std")
+    g, w, mean, std = (kw.get(k) for k in names)
+    given = [k for k, v in zip(names, (g, w, mean, std)) if v is not None]
+    extra = [k for k in ("control_scale", "control_iters") if kw.get(k) is not None]
+    if not given:
+        if extra:
+            raise ValueError(f"{' / '.join(extra)} given without control_joints / control_weights / control_mean / control_std")
+        return None
+    if len(given) != 4:
+        raise ValueError(f"joint control needs all of {', '.join(names)}; missing "
+                         f"{', '.join(k for k in names if k not in given)}")
+    B, T, F_ = (int(v) for v in shape)
+    J = joints_for_feats(F_)
+    if T > max_frames(F_):
+        raise ValueError(f"T = {T}: joint control takes at most {max_frames(F_)} frames at F = {F_}")
+    g, w, mean, std = (torch.as_tensor(v) for v in (g, w, mean, std))
+    for name, v in zip(names, (g, w, mean, std)):
+        if not v.is_floating_point():
+            raise ValueError(f"{name} must be floating point")
+    if tuple(g.shape) != (B, T, J, 3):
+        raise ValueError(f"control_joints has shape {tuple(g.shape)}, expected {(B, T, J, 3)}")
+    w = expand_to(w, 1, (B, T, J, 3), "control_weights", f"must lead with the batch size {B}")
+    for name, v in (("control_mean", mean), ("control_std", std)):
+        if tuple(v.shape) != (B, F_):
+            raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(B, F_)} (one row per sample)")
+    if not bool(torch.isfinite(g).all()):
+        raise ValueError("control_joints has non-finite values")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("control_weights has non-finite values")
+    if not bool((w >= 0).all()):
+        raise ValueError("control_weights must be >= 0")
+    if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all())):
+        raise ValueError("control_mean / control_std have non-finite values")
+    if bool((std == 0).any()):
+        raise ValueError("control_std has zero entries")
+    scale = kw.get("control_scale")
+    scale = 1.0 if scale is None else float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("control_scale must be finite")
+    iters = kw.get("control_iters")
+    iters = 1 if iters is None else iters
+    if isinstance(iters, bool) or int(iters) != iters or not 1 <= int(iters) <= L.CONTROL_MAX_ITERS:
+        raise ValueError(f"control_iters must be an integer in [1, {L.CONTROL_MAX_ITERS}]")
+    return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters)}
+
+
+def check_handshake_kwargs(kw, shape):
+    """The long-motion tables of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when none of the ``handshake_*``
+    keys is given or the tables have no shared frame, else a dict of CPU tensors ``offsets`` (nshared + 1), ``rows`` and
+    ``owner_rows`` int32 and ``weights`` float32 (one per entry), and ``nshared``.  The entries of shared frame c are
+    ``[offsets[c], offsets[c + 1])``, each a batch row times T plus a frame.
+    Raises ValueError when only some of the four are given, for tables that are not 1-D or whose sizes disagree, offsets
+    that do not start at 0, decrease or do not end at the entry count, a frame of fewer than two entries, rows outside
+    [0, B T) or repeated, owner rows that are not a reordering of each frame's rows, and weights that are not finite or do
+    not sum to 1 per frame (within 1e-5).  Raises NotImplementedError together with composed prompts or joint control.
+    Host logic."""
+    names = ("handshake_offsets", "handshake_rows", "handshake_weights", "handshake_owner_rows")
+    vals = [kw.get(k) for k in names]
+    given = [k for k, v in zip(names, vals) if v is not None]
+    if not given:
+        return None
+    if len(given) != 4:
+        raise ValueError(f"long-motion handshakes need all of {', '.join(names)}; missing "
+                         f"{', '.join(k for k in names if k not in given)}")
+    if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
+        raise NotImplementedError("composed prompts over a long motion are not supported yet")
+    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std")):
+        raise NotImplementedError("joint control over a long motion is not supported yet: its targets would need canvas "
+                                  "coordinates")
+    B, T, _ = (int(v) for v in shape)
+    off, rows, w, own = (torch.as_tensor(v).detach().cpu() for v in vals)
+    for name, v in zip(names, (off, rows, w, own)):
+        if v.dim() != 1:
+            raise ValueError(f"{name} must be 1-D, not of shape {tuple(v.shape)}")
+    for name, v in ((names[0], off), (names[1], rows), (names[3], own)):
+        if v.is_floating_point() or v.is_complex() or v.dtype == torch.bool:
+            raise ValueError(f"{name} must be integer")
+    if not w.is_floating_point():
+        raise ValueError("handshake_weights must be floating point")
+    off, rows, own = off.to(torch.int64), rows.to(torch.int64), own.to(torch.int64)
+    ne = rows.numel()
+    if off.numel() < 1 or int(off[0]) != 0 or int(off[-1]) != ne:
+        raise ValueError(f"handshake_offsets must run from 0 to the entry count {ne}")
+    if w.numel() != ne or own.numel() != ne:
+        raise ValueError(f"handshake_weights ({w.numel()}) and handshake_owner_rows ({own.numel()}) need one value per "
+                         f"entry of handshake_rows ({ne})")
+    ns = off.numel() - 1
+    cnt = off[1:] - off[:-1]
+    if ns and int(cnt.min()) < 2:
+        raise ValueError("every shared frame needs at least two entries, and offsets must not decrease")
+    for name, v in ((names[1], rows), (names[3], own)):
+        if ne and (int(v.min()) < 0 or int(v.max()) >= B * T):
+            raise ValueError(f"{name} must lie in [0, B * T) = [0, {B * T})")
+        if torch.unique(v).numel() != ne:
+            raise ValueError(f"{name} repeats a row: every element must belong to one shared frame")
+    fid = torch.repeat_interleave(torch.arange(ns), cnt)
+    key = lambda v: torch.sort(fid * (B * T) + v).values  # noqa: E731
+    if ne and not torch.equal(key(rows), key(own)):
+        raise ValueError("handshake_owner_rows must list each shared frame's rows (owner first), as handshake_rows does")
+    w64 = w.double()
+    if not bool(torch.isfinite(w64).all()):
+        raise ValueError("handshake_weights has non-finite values")
+    if ns and float((torch.zeros(ns, dtype=torch.float64).index_add_(0, fid, w64) - 1).abs().max()) > 1e-5:
+        raise ValueError("handshake_weights must sum to 1 over each shared frame")
+    if ns == 0:
+        return None
+    return {"offsets": off.to(torch.int32), "rows": rows.to(torch.int32), "weights": w.to(torch.float32),
+            "owner_rows": own.to(torch.int32), "nshared": ns}
+
+
+class Conditioning:
+    """The checked conditioning of one generate call over N samples: ``captions`` (N strings, or N sequences of K strings
+    with ``prompt_weights``), ``edit_motion`` (N, T_max, dim_pose) with ``edit_mask`` broadcast to it, ``prompt_weights``
+    broadcast to (N, K, T_w, dim_pose) (T_w its frame dim, 1 when it has none; ``weights``), ``control_joints``
+    (N, T_max, J, 3) with ``control_weights`` broadcast to them and ``mean`` / ``std`` as float32 (dim_pose,) (``control``,
+    None without).  What does not depend on a batch is checked here, once; ``kwargs`` hands out a batch's rows and frames
+    (views of these tensors) and checks that they cover its T."""
+
+    def __init__(self, captions, dim_pose, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
+                 control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None):
+        self.captions, self.dim_pose = captions, dim_pose
+        self.weights = None if prompt_weights is None else self._compose(captions, prompt_weights, dim_pose)
+        self.edit = None
+        if edit_motion is not None or edit_mask is not None:
+            if edit_motion is None or edit_mask is None:
+                raise ValueError("edit_motion and edit_mask go together: give both or neither")
+            k = torch.as_tensor(edit_motion)
+            self.edit = (k, expand_to(edit_mask, None, k.shape, "edit_mask"))
+        self.control = self._control(control_joints, control_weights, mean, std, dim_pose)
+        self.control_scale, self.control_iters = control_scale, control_iters
+
+    @staticmethod
+    def _compose(captions, prompt_weights, dim_pose):
+        N = len(captions)
+        for c in captions:
+            if isinstance(c, str) or not all(isinstance(v, str) for v in c):
+                raise ValueError("with prompt_weights every caption must be a sequence of K strings")
+        ks = {len(c) for c in captions}
+        if len(ks) != 1:
+            raise ValueError(f"every sample must have the same number of prompts, not {sorted(ks)}")
+        K = ks.pop()
+        w = expand_to(torch.as_tensor(prompt_weights, dtype=torch.float32), 0, (N, K, -1, dim_pose), "prompt_weights",
+                      "has more dims than (N, K, T, dim_pose)",
+                      f"{{name}} of shape {{padded}} does not broadcast to (N={N}, K={K}, T, {dim_pose})")
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("prompt_weights has non-finite values")
+        return w
+
+    @staticmethod
+    def _control(control_joints, control_weights, mean, std, dim_pose):
+        if control_joints is None and control_weights is None:
+            return None
+        if control_joints is None or control_weights is None:
+            raise ValueError("control_joints and control_weights go together: give both or neither")
+        if mean is None or std is None:
+            raise ValueError("joint control needs the dataset's mean and std (the targets are de-normalised positions)")
+        from .motion_control import joints_for_feats
+        J = joints_for_feats(dim_pose)
+        g = torch.as_tensor(control_joints, dtype=torch.float32)
+        if g.dim() != 4 or tuple(g.shape[2:]) != (J, 3):
+            raise ValueError(f"control_joints of shape {tuple(g.shape)} must be (N, T_max, {J}, 3)")
+        w = expand_to(torch.as_tensor(control_weights, dtype=torch.float32), 1, g.shape, "control_weights",
+                      f"must lead with N = {g.shape[0]}")
+        ms = []
+        for name, v in (("mean", mean), ("std", std)):
+            v = torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v), dtype=torch.float32).flatten()
+            if v.numel() != dim_pose:
+                raise ValueError(f"{name} must have {dim_pose} entries")
+            ms.append(v)
+        return {"joints": g, "weights": w, "mean": ms[0], "std": ms[1]}
+
+    def captions_of(self, rows):
+        """The captions of batch rows ``rows`` (a slice or an index tensor)."""
+        return self.captions[rows] if isinstance(rows, slice) else [self.captions[i] for i in rows.tolist()]
+
+    def edit_kwargs(self, rows, T):
+        """``inpaint_motion`` / ``inpaint_mask`` of rows ``rows``, their first T frames; {} without editing."""
+        if self.edit is None:
+            return {}
+        k, msk = self.edit
+        if k.dim() != 3 or k.shape[2] != self.dim_pose or k.shape[1] < T:
+            raise ValueError(f"edit_motion of shape {tuple(k.shape)} must be (N, T_max >= {T}, {self.dim_pose})")
+        return {"inpaint_motion": k[rows, :T], "inpaint_mask": msk[rows, :T]}
+
+    def text_kwargs(self, rows, T):
+        """The rows' captions as ``text`` (the sampler encodes them), or the composed prompts and their weights' rows and
+        first T frames."""
+        caps, w = self.captions_of(rows), self.weights
+        if w is None:
+            return {"text": caps}
+        if w.shape[2] != 1 and w.shape[2] < T:
+            raise ValueError(f"prompt_weights has {w.shape[2]} frames, the batch {T}")
+        w = w[rows]
+        return {"compose_text": [list(c) for c in caps], "compose_weights": w[:, :, :T] if w.shape[2] != 1 else w}
+
+    def control_kwargs(self, rows, T, device):
+        """``control_*`` of rows ``rows``, their first T frames, on ``device``; {} without control."""
+        if self.control is None:
+            return {}
+        c = self.control
+        g = c["joints"][rows]
+        if g.shape[1] < T:
+            raise ValueError(f"control_joints has {g.shape[1]} frames, the batch {T}")
+        n = g.shape[0]
+        return {"control_joints": g[:, :T].to(device), "control_weights": c["weights"][rows][:, :T].to(device),
+                "control_mean": c["mean"].to(device).expand(n, -1), "control_std": c["std"].to(device).expand(n, -1),
+                "control_scale": self.control_scale, "control_iters": self.control_iters}
+
+    def kwargs(self, rows, T, device):
+        """The ``model_kwargs`` entries of the batch of rows ``rows`` (a slice or an index tensor) at T frames."""
+        return {**self.text_kwargs(rows, T), **self.edit_kwargs(rows, T), **self.control_kwargs(rows, T, device)}

@@ -38,9 +38,12 @@ Long motions: ``model_kwargs`` may carry handshake tables (``handshake_offsets``
 motion; every step then blends the eps rows of the shared canvas frames before its update and copies the step noise (and
 the loops' x_T) from each overlap's owner window (``mdm_handshake_blend``), so the overlaps stay bit for bit
 equal.
+
+The host-side validation of these inputs (``check_*_kwargs``) lives in ``conditioning`` and keeps its names here.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import enum
 import math
@@ -50,6 +53,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .conditioning import GUIDED as _GUIDED  # the checks keep their names here as well (tests)
+from .conditioning import check_compose_kwargs, check_control_kwargs, check_handshake_kwargs, check_inpaint_kwargs
 
 
 class ModelMeanType(enum.Enum):
@@ -340,11 +345,7 @@ class GaussianDiffusion:
         r._start(noise)
         r.t_dev.fill_(self.num_timesteps - 1)
         for i in range(self.num_timesteps):
-            if r._needs_noise():
-                if step_noise is not None:
-                    r.noise.copy_(step_noise[i].to(r.dev, torch.float32))
-                else:
-                    r.noise.normal_()
+            r._host_noise(step_noise, i)
             r._step(r._needs_noise())
             yield {"sample": r.xx[:B].clone(), "pred_xstart": r.x0.clone()}
 
@@ -487,231 +488,20 @@ class SpacedDiffusion(GaussianDiffusion):
 # runner modes: "ddpm" / "ddim" unguided (B rows); "cfg" guided DDPM, "cfg_ddim" guided DDIM, "cfg_dpmpp" guided
 # DPM-Solver++ ([cond | uncond] = 2B rows, (K + 1)B with K composed prompts); the last two share the fused update of
 # csrc/solver.hip
-_GUIDED = ("cfg", "cfg_ddim", "cfg_dpmpp")
 _COEF_KIND = {"cfg_ddim": "ddim", "cfg_dpmpp": "dpmpp"}
 # motion editing: every mode's update through the masked fused kernel, with these coefficient tables
 _EDIT_COEF_KIND = {"cfg": "ddpm", "ddpm": "ddpm", "ddim": "ddim", "cfg_ddim": "ddim", "cfg_dpmpp": "dpmpp"}
 
 
-def check_inpaint_kwargs(kw, shape):
-    """The editing inputs of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when neither ``inpaint_motion`` nor
-    ``inpaint_mask`` is given, else (known, mask) with ``mask`` broadcast to ``shape`` (a view; nothing is copied).
-    A mask of fewer dims than the sample is aligned on its leading (batch) dim: (B,) is per sample, (B, T) per frame.
-    Raises ValueError for one without the other, a motion not shaped ``shape``, a mask whose leading dim is not B or that
-    does not broadcast, values outside [0, 1] or non-finite values.  Host logic: runs on CPU tensors as well."""
-    known, mask = kw.get("inpaint_motion"), kw.get("inpaint_mask")
-    if known is None and mask is None:
-        return None
-    if known is None or mask is None:
-        raise ValueError("inpaint_motion and inpaint_mask go together: give both or neither")
-    known, mask = torch.as_tensor(known), torch.as_tensor(mask)
-    shape = tuple(int(v) for v in shape)
-    if tuple(known.shape) != shape:
-        raise ValueError(f"inpaint_motion has shape {tuple(known.shape)}, the sample {shape}")
-    if mask.dim() == 0 or mask.dim() > len(shape) or mask.shape[0] != shape[0]:
-        raise ValueError(f"inpaint_mask of shape {tuple(mask.shape)} must lead with the batch size {shape[0]}")
-    try:
-        mask = mask.reshape(tuple(mask.shape) + (1,) * (len(shape) - mask.dim())).expand(shape)
-    except RuntimeError:
-        raise ValueError(f"inpaint_mask of shape {tuple(mask.shape)} does not broadcast to {shape}") from None
-    if not (known.is_floating_point() and mask.is_floating_point()):
-        raise ValueError("inpaint_motion and inpaint_mask must be floating point")
-    if not bool(torch.isfinite(known).all()):
-        raise ValueError("inpaint_motion has non-finite values")
-    if not bool(((mask >= 0) & (mask <= 1)).all()):  # NaN fails both comparisons
-        raise ValueError("inpaint_mask values must lie in [0, 1]")
-    return known, mask
-
-
-def check_compose_kwargs(kw, shape, mode=None):
-    """The composition inputs of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when no ``compose_*`` key is
-    given, else a dict with ``weights`` broadcast to (B, K, T, F) (a view), ``K``, and either ``xf_proj`` (B, K, Dt) and
-    ``xf_out`` (B, K, N, Dt) or ``text`` (B lists of K captions, for ``model.encode_text``).  Every input leads with B, so
-    dist.shard_kwargs slices them.  The weights lead with (B, K) and are aligned on those dims: (B, K) is per sample and
-    prompt, (B, K, T) per frame, (B, K, 1, F) per feature column.
-    Raises ValueError for weights without prompts or prompts without weights, both embeddings and captions, one embedding
-    without the other, shape or broadcast errors, K differing between samples or above MDM_COMPOSE_MAX_K, non-finite
-    weights, ``xf_proj`` / ``xf_out`` given as well, and (with ``mode``) a mode without guidance.  Host logic."""
-    w, cp, co, ct = (kw.get(k) for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text"))
-    if w is None and cp is None and co is None and ct is None:
-        return None
-    if mode is not None and mode not in _GUIDED:
-        raise ValueError(f"composed prompts need classifier-free guidance; mode {mode!r} has none")
-    if kw.get("xf_proj") is not None or kw.get("xf_out") is not None:
-        raise ValueError("xf_proj / xf_out and compose_* are exclusive: the prompts of a composed sample are compose_*")
-    if w is None:
-        raise ValueError("compose_weights is required with composed prompts")
-    if ct is not None and (cp is not None or co is not None):
-        raise ValueError("give compose_text or compose_xf_proj / compose_xf_out, not both")
-    if ct is None and (cp is None or co is None):
-        raise ValueError("composed prompts need compose_text or both compose_xf_proj and compose_xf_out")
-    B, T, F_ = (int(v) for v in shape)
-    if ct is not None:
-        if isinstance(ct, str) or len(ct) != B:
-            raise ValueError(f"compose_text must hold {B} sequences of captions, one per sample")
-        for seq in ct:
-            if isinstance(seq, str) or not all(isinstance(c, str) for c in seq):
-                raise ValueError("each entry of compose_text must be a sequence of caption strings")
-        ks = {len(seq) for seq in ct}
-        if len(ks) != 1:
-            raise ValueError(f"every sample must have the same number of prompts, not {sorted(ks)}")
-        K = ks.pop()
-        ct = [list(seq) for seq in ct]
-    else:
-        cp, co = torch.as_tensor(cp), torch.as_tensor(co)
-        if cp.dim() != 3 or co.dim() != 4 or cp.shape[0] != B or co.shape[0] != B or cp.shape[1] != co.shape[1]:
-            raise ValueError(f"compose_xf_proj {tuple(cp.shape)} / compose_xf_out {tuple(co.shape)} must be (B={B}, K, Dt) "
-                             "and (B, K, N, Dt)")
-        K = int(cp.shape[1])
-    if not 1 <= K <= L.COMPOSE_MAX_K:
-        raise ValueError(f"{K} prompts per sample: the composed update takes 1 to {L.COMPOSE_MAX_K}")
-    w = torch.as_tensor(w)
-    if not w.is_floating_point():
-        raise ValueError("compose_weights must be floating point")
-    if w.dim() < 2 or w.dim() > 4 or tuple(w.shape[:2]) != (B, K):
-        raise ValueError(f"compose_weights of shape {tuple(w.shape)} must lead with (B, K) = {(B, K)} and have at most 4 dims")
-    try:
-        w = w.reshape(tuple(w.shape) + (1,) * (4 - w.dim())).expand(B, K, T, F_)
-    except RuntimeError:
-        raise ValueError(f"compose_weights of shape {tuple(w.shape)} does not broadcast to {(B, K, T, F_)}") from None
-    if not bool(torch.isfinite(w).all()):
-        raise ValueError("compose_weights has non-finite values")
-    return {"weights": w, "K": K, "xf_proj": cp, "xf_out": co, "text": ct}
-
-
-def check_control_kwargs(kw, shape):
-    """The joint-control inputs of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when none of the ``control_*``
-    keys is given, else a dict with ``targets`` (B, T, J, 3), ``weights`` broadcast to it (a view), ``mean`` / ``std``
-    (B, F), ``scale`` (float, default 1) and ``iters`` (int, default 1).  Every tensor leads with B, so dist.shard_kwargs
-    slices them; the weights are aligned on that dim: (B,) per sample, (B, T) per frame, (B, T, J) per joint.
-    Raises ValueError when only some of the four tensors are given (or a scale / iters without them), for an F not of the
-    form 12 J - 1, a T over the kernels' LDS limit, shape or broadcast errors, non-finite targets, weights, mean or std,
-    negative weights, a zero std, a non-finite scale or iters outside [1, MDM_CONTROL_MAX_ITERS].  Host logic."""
-    from .motion_control import joints_for_feats, max_frames
-    names = ("control_joints", "control_weights", "control_mean", "control_std")
-    g, w, mean, std = (kw.get(k) for k in names)
-    given = [k for k, v in zip(names, (g, w, mean, std)) if v is not None]
-    extra = [k for k in ("control_scale", "control_iters") if kw.get(k) is not None]
-    if not given:
-        if extra:
-            raise ValueError(f"{' / '.join(extra)} given without control_joints / control_weights / control_mean / control_std")
-        return None
-    if len(given) != 4:
-        raise ValueError(f"joint control needs all of {', '.join(names)}; missing "
-                         f"{', '.join(k for k in names if k not in given)}")
-    B, T, F_ = (int(v) for v in shape)
-    J = joints_for_feats(F_)
-    if T > max_frames(F_):
-        raise ValueError(f"T = {T}: joint control takes at most {max_frames(F_)} frames at F = {F_}")
-    g, w, mean, std = (torch.as_tensor(v) for v in (g, w, mean, std))
-    for name, v in zip(names, (g, w, mean, std)):
-        if not v.is_floating_point():
-            raise ValueError(f"{name} must be floating point")
-    if tuple(g.shape) != (B, T, J, 3):
-        raise ValueError(f"control_joints has shape {tuple(g.shape)}, expected {(B, T, J, 3)}")
-    if w.dim() == 0 or w.dim() > 4 or w.shape[0] != B:
-        raise ValueError(f"control_weights of shape {tuple(w.shape)} must lead with the batch size {B}")
-    try:
-        w = w.reshape(tuple(w.shape) + (1,) * (4 - w.dim())).expand(B, T, J, 3)
-    except RuntimeError:
-        raise ValueError(f"control_weights of shape {tuple(w.shape)} does not broadcast to {(B, T, J, 3)}") from None
-    for name, v in (("control_mean", mean), ("control_std", std)):
-        if tuple(v.shape) != (B, F_):
-            raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(B, F_)} (one row per sample)")
-    if not bool(torch.isfinite(g).all()):
-        raise ValueError("control_joints has non-finite values")
-    if not bool(torch.isfinite(w).all()):
-        raise ValueError("control_weights has non-finite values")
-    if not bool((w >= 0).all()):
-        raise ValueError("control_weights must be >= 0")
-    if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all())):
-        raise ValueError("control_mean / control_std have non-finite values")
-    if bool((std == 0).any()):
-        raise ValueError("control_std has zero entries")
-    scale = kw.get("control_scale")
-    scale = 1.0 if scale is None else float(scale)
-    if not math.isfinite(scale):
-        raise ValueError("control_scale must be finite")
-    iters = kw.get("control_iters")
-    iters = 1 if iters is None else iters
-    if isinstance(iters, bool) or int(iters) != iters or not 1 <= int(iters) <= L.CONTROL_MAX_ITERS:
-        raise ValueError(f"control_iters must be an integer in [1, {L.CONTROL_MAX_ITERS}]")
-    return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters)}
-
-
-def check_handshake_kwargs(kw, shape):
-    """The long-motion tables of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when none of the ``handshake_*``
-    keys is given or the tables have no shared frame, else a dict of CPU tensors ``offsets`` (nshared + 1), ``rows`` and
-    ``owner_rows`` int32 and ``weights`` float32 (one per entry), and ``nshared``.  The entries of shared frame c are
-    ``[offsets[c], offsets[c + 1])``, each a batch row times T plus a frame.
-    Raises ValueError when only some of the four are given, for tables that are not 1-D or whose sizes disagree, offsets
-    that do not start at 0, decrease or do not end at the entry count, a frame of fewer than two entries, rows outside
-    [0, B T) or repeated, owner rows that are not a reordering of each frame's rows, and weights that are not finite or do
-    not sum to 1 per frame (within 1e-5).  Raises NotImplementedError together with composed prompts or joint control.
-    Host logic."""
-    names = ("handshake_offsets", "handshake_rows", "handshake_weights", "handshake_owner_rows")
-    vals = [kw.get(k) for k in names]
-    given = [k for k, v in zip(names, vals) if v is not None]
-    if not given:
-        return None
-    if len(given) != 4:
-        raise ValueError(f"long-motion handshakes need all of {', '.join(names)}; missing "
-                         f"{', '.join(k for k in names if k not in given)}")
-    if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
-        raise NotImplementedError("composed prompts over a long motion are not supported yet")
-    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std")):
-        raise NotImplementedError("joint control over a long motion is not supported yet: its targets would need canvas "
-                                  "coordinates")
-    B, T, _ = (int(v) for v in shape)
-    off, rows, w, own = (torch.as_tensor(v).detach().cpu() for v in vals)
-    for name, v in zip(names, (off, rows, w, own)):
-        if v.dim() != 1:
-            raise ValueError(f"{name} must be 1-D, not of shape {tuple(v.shape)}")
-    for name, v in ((names[0], off), (names[1], rows), (names[3], own)):
-        if v.is_floating_point() or v.is_complex() or v.dtype == torch.bool:
-            raise ValueError(f"{name} must be integer")
-    if not w.is_floating_point():
-        raise ValueError("handshake_weights must be floating point")
-    off, rows, own = off.to(torch.int64), rows.to(torch.int64), own.to(torch.int64)
-    ne = rows.numel()
-    if off.numel() < 1 or int(off[0]) != 0 or int(off[-1]) != ne:
-        raise ValueError(f"handshake_offsets must run from 0 to the entry count {ne}")
-    if w.numel() != ne or own.numel() != ne:
-        raise ValueError(f"handshake_weights ({w.numel()}) and handshake_owner_rows ({own.numel()}) need one value per "
-                         f"entry of handshake_rows ({ne})")
-    ns = off.numel() - 1
-    cnt = off[1:] - off[:-1]
-    if ns and int(cnt.min()) < 2:
-        raise ValueError("every shared frame needs at least two entries, and offsets must not decrease")
-    for name, v in ((names[1], rows), (names[3], own)):
-        if ne and (int(v.min()) < 0 or int(v.max()) >= B * T):
-            raise ValueError(f"{name} must lie in [0, B * T) = [0, {B * T})")
-        if torch.unique(v).numel() != ne:
-            raise ValueError(f"{name} repeats a row: every element must belong to one shared frame")
-    fid = torch.repeat_interleave(torch.arange(ns), cnt)
-    key = lambda v: torch.sort(fid * (B * T) + v).values  # noqa: E731
-    if ne and not torch.equal(key(rows), key(own)):
-        raise ValueError("handshake_owner_rows must list each shared frame's rows (owner first), as handshake_rows does")
-    w64 = w.double()
-    if not bool(torch.isfinite(w64).all()):
-        raise ValueError("handshake_weights has non-finite values")
-    if ns and float((torch.zeros(ns, dtype=torch.float64).index_add_(0, fid, w64) - 1).abs().max()) > 1e-5:
-        raise ValueError("handshake_weights must sum to 1 over each shared frame")
-    if ns == 0:
-        return None
-    return {"offsets": off.to(torch.int32), "rows": rows.to(torch.int32), "weights": w.to(torch.float32),
-            "owner_rows": own.to(torch.int32), "nshared": ns}
-
-
 class _StepRunner:
-    """Static buffers + (optionally) one captured hipGraph for a whole denoising step."""
+    """Static buffers + (optionally) one captured hipGraph for a whole denoising step.  Which forward and which update
+    entry a step launches follows from the mode and the ``model_kwargs``: both are decided once, at construction."""
 
     def __init__(self, diff: GaussianDiffusion, model, shape, kw, device, mode, cfg_scale, eta, clip, use_graph,
                  streams: int = 0, order: int = 2):
         self.d, self.model, self.mode = diff, model, mode
         self.philox = None  # (seed, global index of row 0): per-step noise from the counter-based device generator
-        self.ntok = None    # per-row text token counts when the cond / uncond captions tokenise to different lengths
-        self.tcache = None
+        self.graph = None
         self.nstreams = int(streams) if streams else int(getattr(model, "sampler_streams", 1))
         self.cfg_scale, self.eta, self.clip, self.use_graph = float(cfg_scale), float(eta), bool(clip), use_graph
         if device is None:
@@ -728,11 +518,29 @@ class _StepRunner:
         length = torch.as_tensor(length).to(self.dev, torch.int32)
         if getattr(model, "ephemeral_mode", "frozen") == "resample":
             self.use_graph = False  # fresh random projections are drawn on the host before every forward
-        # composed guidance: K prompts per sample, laid out condition-major (row k*B + b = prompt k of sample b)
         comp = check_compose_kwargs(kw, shape, mode)
         self.K = 1 if comp is None else comp["K"]
+        self._text_rows(kw, comp, length)
+        self.xx = torch.empty((self.R, T, Fe), dtype=torch.float32, device=self.dev)  # model input rows
+        self.eps = torch.empty_like(self.xx)
+        self.noise = torch.empty((B, T, Fe), dtype=torch.float32, device=self.dev)
+        self.x0 = torch.empty_like(self.noise)
+        self.t_dev = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.ts = torch.zeros(self.R, dtype=torch.int64, device=self.dev)
+        self.tab = diff._device_table(self.dev)
+        self.tmap = diff._device_map(self.dev)  # spaced schedule: the denoiser is given the original timesteps
+        self._conditioning_buffers(kw, comp, length, order)
+        self._forward = self._plan_forward()
+        self._update, self._guide = self._plan_update()
+
+    def _text_rows(self, kw, comp, length):
+        """The text embeddings of the R forward rows (``xp`` / ``xo``, or ``halves`` run one after the other) and their
+        lengths ``len2``.  Composed guidance lays K prompts per sample out condition-major (row k*B + b = prompt k of
+        sample b); a guided mode appends the unconditional rows of the same samples: one forward of (K + 1)B rows."""
+        model, B, K = self.model, self.B, self.K
+        self.ntok = None  # per-row text token counts when the cond / uncond captions tokenise to different lengths
+        self.halves = None
         if comp is not None:
-            K = self.K
             if comp["text"] is not None:  # B*K captions in one encoder call, sample-major, then (B, K, ...)
                 xp, xo = model.encode_text([c for seq in comp["text"] for c in seq], self.dev)
                 xp, xo = xp.reshape(B, K, *xp.shape[1:]), xo.reshape(B, K, *xo.shape[1:])
@@ -744,116 +552,153 @@ class _StepRunner:
             if xp is None or xo is None:
                 xp, xo = model.encode_text(kw["text"], self.dev)
         xp, xo = xp.to(self.dev, torch.float32), xo.to(self.dev, torch.float32)
-        if mode in _GUIDED:  # cond rows then uncond rows of the same samples, one forward of (K + 1)B rows
-            up, uo = kw.get("xf_proj_uncond"), kw.get("xf_out_uncond")
-            if up is None or uo is None:
-                up, uo = model.uncond_embedding(B, self.dev)
-            up, uo = up.to(self.dev, torch.float32), uo.to(self.dev, torch.float32)
-            self.len2 = torch.cat([length] * (self.K + 1), 0)
-            self.R = (self.K + 1) * B
-            # A real tokenizer gives the empty caption fewer tokens than the captions (N = 8 + 2 vs 8 + longest caption,
-            # text_encoder.py:25-43) and the reference's cross-attention has no text mask, so the shorter side must NOT
-            # see padding.  Default: the shorter half is padded with zero rows and the text cache carries a per-row token
-            # count (MdmTextCache.ntok) under which those rows have weight exactly 0 in both cross-attentions -- still ONE
-            # forward of 2B rows.  model.ragged_text = "split": two B-row forwards with their own text caches instead.
-            # (Composed: the K prompt groups share one token count, so the same holds with (K + 1) groups of B rows.)
-            ragged = uo.shape[1] != xo.shape[1]
-            self.split_halves = ragged and (getattr(model, "ragged_text", "mask") == "split" or not hasattr(model, "prepare_text"))
-            if self.split_halves:
-                self.xp, self.xo = None, None
-                self.halves = [(xp[k * B:(k + 1) * B].contiguous(), xo[k * B:(k + 1) * B].contiguous())
-                               for k in range(self.K)] + [(up.contiguous(), uo.contiguous())]
-            else:
-                if ragged:
-                    nmax = max(xo.shape[1], uo.shape[1])
-                    self.ntok = [xo.shape[1]] * (self.K * B) + [uo.shape[1]] * B
-                    xo = torch.nn.functional.pad(xo, (0, 0, 0, nmax - xo.shape[1]))
-                    uo = torch.nn.functional.pad(uo, (0, 0, 0, nmax - uo.shape[1]))
-                self.xp = torch.cat([xp, up], 0).contiguous()
-                self.xo = torch.cat([xo, uo], 0).contiguous()
-        else:
+        if self.mode not in _GUIDED:
             self.xp, self.xo, self.len2, self.R = xp.contiguous(), xo.contiguous(), length, B
-            self.split_halves = False
-        self.xx = torch.empty((self.R, T, Fe), dtype=torch.float32, device=self.dev)  # model input rows
-        self.eps = torch.empty_like(self.xx)
-        self.noise = torch.empty((B, T, Fe), dtype=torch.float32, device=self.dev)
-        self.x0 = torch.empty_like(self.noise)
-        self.t_dev = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self.ts = torch.zeros(self.R, dtype=torch.int64, device=self.dev)
-        self.tab = diff._device_table(self.dev)
-        self.tmap = diff._device_map(self.dev)  # spaced schedule: the denoiser is given the original timesteps
-        # motion editing: the known motion and the mask, dense f32 and owned by the runner, read by every (captured) step
+            return
+        up, uo = kw.get("xf_proj_uncond"), kw.get("xf_out_uncond")
+        if up is None or uo is None:
+            up, uo = model.uncond_embedding(B, self.dev)
+        up, uo = up.to(self.dev, torch.float32), uo.to(self.dev, torch.float32)
+        self.len2 = torch.cat([length] * (K + 1), 0)
+        self.R = (K + 1) * B
+        # A real tokenizer gives the empty caption fewer tokens than the captions (N = 8 + 2 vs 8 + longest caption,
+        # text_encoder.py:25-43) and the reference's cross-attention has no text mask, so the shorter side must NOT
+        # see padding.  Default: the shorter half is padded with zero rows and the text cache carries a per-row token
+        # count (MdmTextCache.ntok) under which those rows have weight exactly 0 in both cross-attentions -- still ONE
+        # forward of 2B rows.  model.ragged_text = "split": two B-row forwards with their own text caches instead.
+        # (Composed: the K prompt groups share one token count, so the same holds with (K + 1) groups of B rows.)
+        ragged = uo.shape[1] != xo.shape[1]
+        if ragged and (getattr(model, "ragged_text", "mask") == "split" or not hasattr(model, "prepare_text")):
+            if not hasattr(model, "prepare_text"):
+                raise ValueError("cond and uncond text embeddings have different token counts; this model cannot run "
+                                 "them as separate forwards")
+            self.xp, self.xo = None, None
+            self.halves = [(xp[k * B:(k + 1) * B].contiguous(), xo[k * B:(k + 1) * B].contiguous())
+                           for k in range(K)] + [(up.contiguous(), uo.contiguous())]
+            return
+        if ragged:
+            nmax = max(xo.shape[1], uo.shape[1])
+            self.ntok = [xo.shape[1]] * (K * B) + [uo.shape[1]] * B
+            xo = torch.nn.functional.pad(xo, (0, 0, 0, nmax - xo.shape[1]))
+            uo = torch.nn.functional.pad(uo, (0, 0, 0, nmax - uo.shape[1]))
+        self.xp = torch.cat([xp, up], 0).contiguous()
+        self.xo = torch.cat([xo, uo], 0).contiguous()
+
+    def _conditioning_buffers(self, kw, comp, length, order):
+        """Everything the (captured) steps read besides text: dense f32 / int32 device buffers owned by the runner."""
+        B, T, Fe, dev, shape = self.B, self.T, self.Fe, self.dev, (self.B, self.T, self.Fe)
+        f32 = lambda src, shp: torch.empty(shp, dtype=torch.float32, device=dev).copy_(src)  # noqa: E731
+        # motion editing: the known motion and the mask
         edit = check_inpaint_kwargs(kw, shape)
-        self.known = self.mask = None
-        if edit is not None:
-            self.known = torch.empty_like(self.noise)
-            self.mask = torch.empty_like(self.noise)
-            self.known.copy_(edit[0])
-            self.mask.copy_(edit[1])
-        # composed guidance: the weights, dense f32 [K, n] (condition-major like the eps rows), owned by the runner
-        self.cw = None
-        if comp is not None:
-            self.cw = torch.empty((self.K, B, T, Fe), dtype=torch.float32, device=self.dev)
-            self.cw.copy_(comp["weights"].transpose(0, 1))
-        # joint control: targets, weights, mean / std and the lengths, dense f32 / int32 and owned by the runner
+        self.known, self.mask = (None, None) if edit is None else (f32(edit[0], shape), f32(edit[1], shape))
+        # composed guidance: the weights [K, n], condition-major like the eps rows
+        self.cw = None if comp is None else f32(comp["weights"].transpose(0, 1), (self.K, B, T, Fe))
+        # joint control: targets, weights, mean / std and the lengths
         ctl = check_control_kwargs(kw, shape)
         self.ctl = None
         if ctl is not None:
             J = ctl["targets"].shape[2]
-            self.ctl = dict(scale=ctl["scale"], iters=ctl["iters"],
-                            len=length.contiguous(),
-                            targets=torch.empty((B, T, J, 3), dtype=torch.float32, device=self.dev),
-                            weights=torch.empty((B, T, J, 3), dtype=torch.float32, device=self.dev),
-                            mean=torch.empty((B, Fe), dtype=torch.float32, device=self.dev),
-                            std=torch.empty((B, Fe), dtype=torch.float32, device=self.dev))
-            for k in ("targets", "weights", "mean", "std"):
-                self.ctl[k].copy_(ctl[k])
-        # long motions: the handshake tables of the overlapping windows, owned by the runner
+            self.ctl = dict(scale=ctl["scale"], iters=ctl["iters"], len=length.contiguous(),
+                            targets=f32(ctl["targets"], (B, T, J, 3)), weights=f32(ctl["weights"], (B, T, J, 3)),
+                            mean=f32(ctl["mean"], (B, Fe)), std=f32(ctl["std"], (B, Fe)))
+        # long motions: the handshake tables of the overlapping windows
         hs = check_handshake_kwargs(kw, shape)
-        self.hs = None
-        if hs is not None:
-            self.hs = {k: hs[k].to(self.dev).contiguous() for k in ("offsets", "rows", "weights", "owner_rows")}
-            self.hs["nshared"] = hs["nshared"]
+        self.hs = None if hs is None else {k: v.to(dev).contiguous() if torch.is_tensor(v) else v for k, v in hs.items()}
         # few-step modes (and every mode when editing, composing or controlling): per-step coefficients of the fused update;
         # self.x0 doubles as x0_prev (updated in place)
         table = self.known is not None or self.cw is not None or self.ctl is not None
-        kind = _EDIT_COEF_KIND[mode] if table else _COEF_KIND.get(mode)
-        self.coef = diff._device_coef(kind, eta, order, self.dev) if kind is not None else None
-        self.graph = None
-        # time-embedding chain tabulated per timestep + text half of the gated fusion: once per loop, not per step
+        kind = _EDIT_COEF_KIND[self.mode] if table else _COEF_KIND.get(self.mode)
+        self.coef = self.d._device_coef(kind, self.eta, order, dev) if kind is not None else None
+
+    def _plan_forward(self):
+        """The forward of a step: sets ``stem`` (time-embedding chain tabulated per timestep + text half of the gated
+        fusion: once per loop, not per step), ``chunks`` and ``side`` and returns the function that writes ``eps``."""
+        model, B, T = self.model, self.B, self.T
+        # over the MODEL's schedule: the cache's gather clamps t into [0, steps), a spaced length would silently cut it
+        steps = self.d.model_timesteps
         frozen = getattr(model, "ephemeral_mode", "frozen") == "frozen"
         can_cache = hasattr(model, "stem_cache") and frozen
-        # over the MODEL's schedule: the cache's gather clamps t into [0, steps), a spaced length would silently cut it
-        self.stem = model.stem_cache(diff.model_timesteps, self.xp) if can_cache and not self.split_halves else None
+        self.stem = model.stem_cache(steps, self.xp) if can_cache and self.halves is None else None
         # Samples never interact, so the R rows of a step can be cut into independent chunks whose forwards run
         # CONCURRENTLY on separate HIP streams (forked/joined inside the captured graph): most launches of a forward are
         # latency-bound, and two chains in flight overlap each other's prologues, DMA round trips and tails.
-        self.chunks = None
-        self.side = []
-        if self.split_halves:
-            if not hasattr(model, "prepare_text"):
-                raise ValueError("cond and uncond text embeddings have different token counts; this model cannot run "
-                                 "them as separate forwards")
-            self.chunks = []
-            for c, (xp_c, xo_c) in enumerate(self.halves):  # same stream, one after the other
-                sl = slice(c * B, (c + 1) * B)
-                self.chunks.append(dict(
-                    sl=sl, xp=xp_c, xo=xo_c, len=self.len2[sl].contiguous(), tc=model.prepare_text(xo_c, private=True),
-                    stem=model.stem_cache(diff.model_timesteps, xp_c) if can_cache else None,
-                    ws=model.new_workspace(B, T, xo_c.shape[1]), stream=0))
+        self.chunks, self.side, self.tcache = None, [], None
+
+        def chunk(sl, xp_c, xo_c, stream, ntok=None):
+            return dict(sl=sl, xp=xp_c, xo=xo_c, len=self.len2[sl].contiguous(), stream=stream,
+                        tc=model.prepare_text(xo_c, private=True, ntok=ntok),
+                        stem=model.stem_cache(steps, xp_c) if can_cache else None,
+                        ws=model.new_workspace(sl.stop - sl.start, T, xo_c.shape[1]))
+
+        if self.halves is not None:  # same stream, one after the other
+            self.chunks = [chunk(slice(c * B, (c + 1) * B), xp_c, xo_c, 0) for c, (xp_c, xo_c) in enumerate(self.halves)]
         elif self.nstreams > 1 and frozen and hasattr(model, "new_workspace") and self.R % self.nstreams == 0:
             n = self.R // self.nstreams
             self.side = [torch.cuda.Stream(device=self.dev) for _ in range(self.nstreams - 1)]
-            self.chunks = []
-            for c in range(self.nstreams):
-                sl = slice(c * n, (c + 1) * n)
-                xo_c = self.xo[sl].contiguous()
-                xp_c = self.xp[sl].contiguous()
-                self.chunks.append(dict(
-                    sl=sl, xp=xp_c, xo=xo_c, len=self.len2[sl].contiguous(),
-                    tc=model.prepare_text(xo_c, private=True, ntok=self.ntok[sl] if self.ntok else None),
-                    stem=model.stem_cache(diff.model_timesteps, xp_c),
-                    ws=model.new_workspace(n, T, xo_c.shape[1]), stream=c))
+            cuts = [slice(c * n, (c + 1) * n) for c in range(self.nstreams)]
+            self.chunks = [chunk(sl, self.xp[sl].contiguous(), self.xo[sl].contiguous(), c, self.ntok[sl] if self.ntok else None)
+                           for c, sl in enumerate(cuts)]
+        # plain functions, not bound methods: a bound method kept on the runner is a reference cycle, and the runner must
+        # be freed with its captured graph when its loop returns -- a graph destroyed by a later garbage collection, while
+        # another runner is capturing, aborts the process
+        if self.chunks is not None:
+            return _StepRunner._forward_chunks
+        if self.ntok is not None:
+            return _StepRunner._forward_ragged
+        self._stem_kw = {} if self.stem is None else {"stem_cache": self.stem}
+        return _StepRunner._forward_whole
+
+    def _forward_whole(self):
+        self.model(self.xx, self.ts, self.len2, xf_proj=self.xp, xf_out=self.xo, out=self.eps, **self._stem_kw)
+
+    def _forward_chunks(self):
+        main = torch.cuda.current_stream()
+        for ch in self.chunks:
+            st = main if ch["stream"] == 0 else self.side[ch["stream"] - 1]
+            if st is not main:
+                st.wait_stream(main)  # fork: x_t rows and the timestep vector are ready
+            with torch.cuda.stream(st):
+                self.model(self.xx[ch["sl"]], self.ts[ch["sl"]], ch["len"], xf_proj=ch["xp"], xf_out=ch["xo"],
+                           out=self.eps[ch["sl"]], stem_cache=ch["stem"], text_cache=ch["tc"], workspace=ch["ws"])
+        for st in self.side:
+            main.wait_stream(st)  # join before the guidance / posterior update
+
+    def _forward_ragged(self):
+        """Ragged captions in one forward: a private text cache with per-row token counts.  It stays lazy, built on the
+        first step: it needs the module's packed weights."""
+        if self.tcache is None:
+            self.tcache = self.model.prepare_text(self.xo, private=True, ntok=self.ntok)
+        # text_tokens as well: should the module's packed weights have been rebuilt since the cache was made, forward()
+        # rebuilds the text side -- with these counts, not with the zero-padded rows taken for real tokens
+        self.model(self.xx, self.ts, self.len2, xf_proj=self.xp, xf_out=self.xo, out=self.eps, stem_cache=self.stem,
+                   text_cache=self.tcache, text_tokens=self.ntok)
+
+    def _plan_update(self):
+        """The update of a step, ``(entry name, arguments before the noise pointer, arguments after it)``, and the
+        arguments of mdm_joint_guidance (None without control).  Every pointer belongs to a buffer the runner owns for its
+        lifetime; the noise pointer and the stream are the launch's.  Plain "cfg" / "ddpm" keep mdm_cfg_posterior_step and
+        plain "ddim" mdm_ddim_step; with a coefficient table the three fused entries share their head and tail."""
+        p, i32 = (lambda t: C.c_void_p(L.ptr(t))), C.c_int32
+        x, eps, x0 = p(self.xx), p(self.eps), p(self.x0)  # x_t is rows [0, B) of xx, updated in place
+        eps_u = p(self.eps[self.B:] if self.mode in _GUIDED else None)
+        clock = (i32(self.d.num_timesteps), p(self.t_dev), i32(0))  # steps, the device timestep, no immediate one
+        out = (i32(int(self.clip)), x, x0)
+        guide = None
+        if self.ctl is not None:
+            c = self.ctl
+            guide = (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"]),
+                     i32(self.B), i32(self.T), i32(self.Fe), C.c_float(c["scale"]), i32(c["iters"]), p(self.coef)) + clock
+        if self.coef is None and self.mode == "ddim":
+            return ("mdm_ddim_step", (x, eps), (C.c_int64(self.n), p(self.tab)) + clock + (C.c_float(self.eta),) + out), guide
+        tail = clock + (C.c_float(self.cfg_scale),) + out
+        if self.coef is None:
+            return ("mdm_cfg_posterior_step", (x, eps, eps_u), (C.c_int64(self.n), p(self.tab)) + tail), guide
+        head = (i32(self.K), p(self.cw)) if self.cw is not None else (eps_u,)
+        head = (x, eps) + head + (x0 if self.mode == "cfg_dpmpp" else p(None),)  # x0_prev: the two-step solver only
+        edit = (p(self.known), p(self.mask)) if self.cw is not None or self.known is not None else ()
+        name = ("mdm_composed_update" if self.cw is not None else
+                "mdm_guided_update_inpaint" if self.known is not None else "mdm_guided_update")
+        return (name, head, edit + (C.c_int64(self.n), p(self.tab), p(self.coef)) + tail), guide
 
     # one step on the current stream: reads self.xx[:B] (x_t), writes x_{t-1} back into it
     def _step(self, use_noise: bool):
@@ -862,9 +707,9 @@ class _StepRunner:
 
     def _step_on_device(self, use_noise: bool):
         lib, s = L.lib(), C.c_void_p(L.stream_ptr())
-        B, n = self.B, self.n
+        B, t_dev = self.B, C.c_void_p(self.t_dev.data_ptr())
         if use_noise and self.philox is not None:  # step noise = f(seed, global sample, t, element); t read on the device
-            self._philox_fill(self.noise, C.c_void_p(self.t_dev.data_ptr()), 0, s)
+            self._philox_fill(self.noise, t_dev, 0, s)
         if use_noise and self.hs is not None:  # the owner window's noise in every overlap (host-filled noise too)
             self._handshake(self.noise, 1, False, s)
         x = self.xx[:B]
@@ -872,88 +717,20 @@ class _StepRunner:
             self.xx[B:].view(self.K, B, self.T, self.Fe).copy_(x.unsqueeze(0).expand(self.K, -1, -1, -1))
         elif self.R == 2 * B:
             self.xx[B:].copy_(x)
+        ts, R = C.c_void_p(self.ts.data_ptr()), C.c_int64(self.R)
         if self.tmap is not None:
-            L.check(lib.mdm_fill_timesteps_mapped(C.c_void_p(self.ts.data_ptr()), C.c_int64(self.R),
-                                                  C.c_void_p(self.t_dev.data_ptr()), C.c_void_p(self.tmap.data_ptr()),
+            L.check(lib.mdm_fill_timesteps_mapped(ts, R, t_dev, C.c_void_p(self.tmap.data_ptr()),
                                                   C.c_int32(self.d.num_timesteps), s), "mdm_fill_timesteps_mapped")
         else:
-            L.check(lib.mdm_fill_i64(C.c_void_p(self.ts.data_ptr()), C.c_int64(self.R), C.c_void_p(self.t_dev.data_ptr()), s))
-        if self.chunks is not None:
-            main = torch.cuda.current_stream()
-            for i, ch in enumerate(self.chunks):
-                st = main if ch["stream"] == 0 else self.side[ch["stream"] - 1]
-                if st is not main:
-                    st.wait_stream(main)  # fork: x_t rows and the timestep vector are ready
-                with torch.cuda.stream(st):
-                    self.model(self.xx[ch["sl"]], self.ts[ch["sl"]], ch["len"], xf_proj=ch["xp"], xf_out=ch["xo"],
-                               out=self.eps[ch["sl"]], stem_cache=ch["stem"], text_cache=ch["tc"], workspace=ch["ws"])
-            for st in self.side:
-                main.wait_stream(st)  # join before the guidance / posterior update
-        elif self.ntok is not None:  # ragged captions: a private text cache with per-row token counts
-            if self.tcache is None:
-                self.tcache = self.model.prepare_text(self.xo, private=True, ntok=self.ntok)
-            # text_tokens as well: should the module's packed weights have been rebuilt since the cache was made, forward()
-            # rebuilds the text side -- with these counts, not with the zero-padded rows taken for real tokens
-            self.model(self.xx, self.ts, self.len2, xf_proj=self.xp, xf_out=self.xo, out=self.eps, stem_cache=self.stem,
-                       text_cache=self.tcache, text_tokens=self.ntok)
-        elif self.stem is not None:
-            self.model(self.xx, self.ts, self.len2, xf_proj=self.xp, xf_out=self.xo, out=self.eps, stem_cache=self.stem)
-        else:
-            self.model(self.xx, self.ts, self.len2, xf_proj=self.xp, xf_out=self.xo, out=self.eps)
+            L.check(lib.mdm_fill_i64(ts, R, t_dev, s))
+        self._forward(self)
         if self.hs is not None:  # one eps per shared canvas frame, in every row group, before the update reads it
             self._handshake(self.eps, self.R // B, True, s)
-        noise = C.c_void_p(self.noise.data_ptr() if use_noise else 0)
-        steps = C.c_int32(self.d.num_timesteps)
-        if self.cw is not None:
-            x0 = C.c_void_p(self.x0.data_ptr())
-            edit = self.known is not None
-            L.check(lib.mdm_composed_update(
-                C.c_void_p(x.data_ptr()), C.c_void_p(self.eps.data_ptr()), C.c_int32(self.K),
-                C.c_void_p(self.cw.data_ptr()), x0 if self.mode == "cfg_dpmpp" else C.c_void_p(0), noise,
-                C.c_void_p(self.known.data_ptr() if edit else 0), C.c_void_p(self.mask.data_ptr() if edit else 0),
-                C.c_int64(n), C.c_void_p(self.tab.data_ptr()), C.c_void_p(self.coef.data_ptr()), steps,
-                C.c_void_p(self.t_dev.data_ptr()), C.c_int32(0), C.c_float(self.cfg_scale), C.c_int32(int(self.clip)),
-                C.c_void_p(x.data_ptr()), x0, s), "mdm_composed_update")
-        elif self.known is not None:
-            x0 = C.c_void_p(self.x0.data_ptr())
-            eps_u = C.c_void_p(self.eps[B:].data_ptr() if self.mode in _GUIDED else 0)
-            L.check(lib.mdm_guided_update_inpaint(
-                C.c_void_p(x.data_ptr()), C.c_void_p(self.eps.data_ptr()), eps_u,
-                x0 if self.mode == "cfg_dpmpp" else C.c_void_p(0), noise, C.c_void_p(self.known.data_ptr()),
-                C.c_void_p(self.mask.data_ptr()), C.c_int64(n), C.c_void_p(self.tab.data_ptr()),
-                C.c_void_p(self.coef.data_ptr()), steps, C.c_void_p(self.t_dev.data_ptr()), C.c_int32(0),
-                C.c_float(self.cfg_scale), C.c_int32(int(self.clip)), C.c_void_p(x.data_ptr()), x0, s),
-                "mdm_guided_update_inpaint")
-        elif self.coef is not None:
-            x0 = C.c_void_p(self.x0.data_ptr())
-            eps_u = C.c_void_p(self.eps[B:].data_ptr() if self.mode in _GUIDED else 0)
-            L.check(lib.mdm_guided_update(C.c_void_p(x.data_ptr()), C.c_void_p(self.eps.data_ptr()),
-                                          eps_u, x0 if self.mode == "cfg_dpmpp" else C.c_void_p(0),
-                                          noise, C.c_int64(n), C.c_void_p(self.tab.data_ptr()),
-                                          C.c_void_p(self.coef.data_ptr()), steps, C.c_void_p(self.t_dev.data_ptr()),
-                                          C.c_int32(0), C.c_float(self.cfg_scale), C.c_int32(int(self.clip)),
-                                          C.c_void_p(x.data_ptr()), x0, s), "mdm_guided_update")
-        elif self.mode == "ddim":
-            L.check(lib.mdm_ddim_step(C.c_void_p(x.data_ptr()), C.c_void_p(self.eps.data_ptr()), noise, C.c_int64(n),
-                                      C.c_void_p(self.tab.data_ptr()), steps, C.c_void_p(self.t_dev.data_ptr()), C.c_int32(0),
-                                      C.c_float(self.eta), C.c_int32(int(self.clip)), C.c_void_p(x.data_ptr()),
-                                      C.c_void_p(self.x0.data_ptr()), s), "mdm_ddim_step")
-        else:
-            eps_u = self.eps[B:].data_ptr() if self.mode == "cfg" else 0
-            L.check(lib.mdm_cfg_posterior_step(C.c_void_p(x.data_ptr()), C.c_void_p(self.eps.data_ptr()), C.c_void_p(eps_u),
-                                               noise, C.c_int64(n), C.c_void_p(self.tab.data_ptr()), steps,
-                                               C.c_void_p(self.t_dev.data_ptr()), C.c_int32(0), C.c_float(self.cfg_scale),
-                                               C.c_int32(int(self.clip)), C.c_void_p(x.data_ptr()),
-                                               C.c_void_p(self.x0.data_ptr()), s), "mdm_cfg_posterior_step")
-        if self.ctl is not None:  # x0 and x_{t-1} moved down the joint-position loss, before the counter moves
-            c = self.ctl
-            L.check(lib.mdm_joint_guidance(
-                C.c_void_p(x.data_ptr()), C.c_void_p(self.x0.data_ptr()), C.c_void_p(L.ptr(self.mask)),
-                C.c_void_p(c["len"].data_ptr()), C.c_void_p(c["mean"].data_ptr()), C.c_void_p(c["std"].data_ptr()),
-                C.c_void_p(c["targets"].data_ptr()), C.c_void_p(c["weights"].data_ptr()), C.c_int32(B), C.c_int32(self.T),
-                C.c_int32(self.Fe), C.c_float(c["scale"]), C.c_int32(c["iters"]), C.c_void_p(self.coef.data_ptr()), steps,
-                C.c_void_p(self.t_dev.data_ptr()), C.c_int32(0), s), "mdm_joint_guidance")
-        L.check(lib.mdm_add_i32(C.c_void_p(self.t_dev.data_ptr()), C.c_int32(-1), s))
+        name, head, tail = self._update
+        L.check(getattr(lib, name)(*head, C.c_void_p(self.noise.data_ptr() if use_noise else 0), *tail, s), name)
+        if self._guide is not None:  # x0 and x_{t-1} moved down the joint-position loss, before the counter moves
+            L.check(lib.mdm_joint_guidance(*self._guide, s), "mdm_joint_guidance")
+        L.check(lib.mdm_add_i32(t_dev, C.c_int32(-1), s))
 
     def _handshake(self, buf, groups, blend: bool, s):
         """mdm_handshake_blend over ``groups`` consecutive groups of B rows of ``buf``: the weighted mean of the eps rows
@@ -976,18 +753,33 @@ class _StepRunner:
             return False
         return not (self.mode in ("ddim", "cfg_ddim") and self.eta == 0.0)
 
+    @contextlib.contextmanager
+    def _moe_counters_kept(self):
+        """The warm-up forward and the capture must not disturb the MoE counters the reference would show
+        (switch_moe.py:71-92): they are put back when the block ends."""
+        bufs = self.model.moe_buffers() if hasattr(self.model, "moe_buffers") else {}
+        saved = {k: v.clone() for k, v in bufs.items()}
+        yield
+        for k, v in saved.items():
+            self.model.moe_buffers()[k].copy_(v)
+
     def _prepare(self):
-        """Pack weights, build the text cache, size the workspace -- everything that allocates -- before capture.
-        The warm-up forward must not disturb the MoE counters the reference would show (switch_moe.py:71-92)."""
+        """Pack weights, build the text cache, size the workspace -- everything that allocates -- before capture."""
         with torch.cuda.device(self.dev):  # the synchronize below must be on the sampler's device as well
-            saved = {k: v.clone() for k, v in self.model.moe_buffers().items()} if hasattr(self.model, "moe_buffers") else {}
-            self.xx.zero_()
-            self.t_dev.fill_(self.d.num_timesteps - 1)
-            self.noise.zero_()
-            self._step(self._needs_noise())
-            for k, v in saved.items():
-                self.model.moe_buffers()[k].copy_(v)
+            with self._moe_counters_kept():
+                self.xx.zero_()
+                self.t_dev.fill_(self.d.num_timesteps - 1)
+                self.noise.zero_()
+                self._step(self._needs_noise())
             torch.cuda.current_stream().synchronize()
+
+    def _host_noise(self, step_noise, i):
+        """Step i's noise from ``step_noise`` or the torch generator, unless the step draws it on the device or uses none."""
+        if self._needs_noise() and self.philox is None:
+            if step_noise is not None:
+                self.noise.copy_(step_noise[i].to(self.dev, torch.float32))
+            else:
+                self.noise.normal_()
 
     def _philox_fill(self, out, stream_dev, stream_imm, s):
         """out[row] = noise(seed, global sample of that row, stream): rows are consecutive samples (first + row) or carry
@@ -1028,42 +820,32 @@ class _StepRunner:
         # current: captured on another device's stream the graph would be empty and every replay a no-op (the reference's
         # tools use torch.device('cuda:N') without set_device, tools/visualization.py:57)
         with torch.cuda.device(self.dev):
-            return self._run(noise, step_noise, progress, callback, seed, sample_offset)
-
-    def _run(self, noise, step_noise, progress, callback, seed, sample_offset):
-        d, B = self.d, self.B
-        if seed is not None and step_noise is None:
-            self.philox = (int(seed) & 0xFFFFFFFFFFFFFFFF, self._ids(sample_offset))
-        self._prepare()
-        if self.use_graph:
-            g = torch.cuda.CUDAGraph()
-            saved = {k: v.clone() for k, v in self.model.moe_buffers().items()}
-            with torch.cuda.graph(g):
-                self._step(self._needs_noise())
-            for k, v in saved.items():  # capture does not execute, but keep the invariant explicit
-                self.model.moe_buffers()[k].copy_(v)
-            self.graph = g
-        if noise is None:
-            noise = self.draw_xT(seed, sample_offset) if seed is not None else torch.randn((B, self.T, self.Fe), device=self.dev)
-        self._start(noise)
-        self.t_dev.fill_(d.num_timesteps - 1)
-        it = range(d.num_timesteps)
-        if progress:
-            from tqdm.auto import tqdm
-            it = tqdm(it, desc="Sampling")
-        for i in it:
-            if self._needs_noise() and self.philox is None:
-                if step_noise is not None:
-                    self.noise.copy_(step_noise[i].to(self.dev, torch.float32))
+            d, B = self.d, self.B
+            if seed is not None and step_noise is None:
+                self.philox = (int(seed) & 0xFFFFFFFFFFFFFFFF, self._ids(sample_offset))
+            self._prepare()
+            if self.use_graph:
+                g = torch.cuda.CUDAGraph()
+                with self._moe_counters_kept(), torch.cuda.graph(g):  # capture does not execute: the invariant kept explicit
+                    self._step(self._needs_noise())
+                self.graph = g
+            if noise is None:
+                noise = self.draw_xT(seed, sample_offset) if seed is not None else torch.randn((B, self.T, self.Fe), device=self.dev)
+            self._start(noise)
+            self.t_dev.fill_(d.num_timesteps - 1)
+            it = range(d.num_timesteps)
+            if progress:
+                from tqdm.auto import tqdm
+                it = tqdm(it, desc="Sampling")
+            for i in it:
+                self._host_noise(step_noise, i)
+                if self.graph is not None:
+                    self.graph.replay()
                 else:
-                    self.noise.normal_()
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self._step(self._needs_noise())
-            if callback is not None:
-                callback(i, d.num_timesteps - 1 - i, self.xx[:B])
-        return self.xx[:B].clone()
+                    self._step(self._needs_noise())
+                if callback is not None:
+                    callback(i, d.num_timesteps - 1 - i, self.xx[:B])
+            return self.xx[:B].clone()
 
     def single(self, x, t, noise):
         t = torch.as_tensor(t)

@@ -10,7 +10,8 @@ window, then in the right one (``rows[e] = window_row * T + frame``).  On every 
 the two eps rows back into both (``weights``: a linear crossfade, the right window weighing ``(j + 1) / (h + 1)`` at overlap
 frame j, or ``"uniform"`` halves), and copies x_T and the step noise from the left ("owner") window into the right one.
 The overlap frames of neighbouring windows then stay bit for bit equal on every step, and the canvas is the windows' valid
-frames.  Host logic only: runs without a GPU.
+frames.  ``script_plans``, ``plan_batches``, ``batch_tables`` and ``gather_canvases`` are the host half of
+``DDPMTrainer.generate_long``.  Host logic only: runs without a GPU.
 """
 from __future__ import annotations
 
@@ -19,6 +20,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from .conditioning import expand_to
 
 BLENDS = ("linear", "uniform")
 
@@ -96,6 +99,63 @@ def merge_tables(tables: Sequence[Dict]) -> Dict:
     cat = lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dt)  # noqa: E731
     return {"offsets": np.concatenate(offsets).astype(np.int32), "rows": cat(rows, np.int32),
             "weights": cat(weights, np.float32), "owner_rows": cat(owner, np.int32)}
+
+
+def script_plans(scripts, overlap, num_frames):
+    """Checked scripts: per motion (captions, lengths, window starts, canvas length)."""
+    if isinstance(scripts, (str, bytes)) or len(scripts) == 0:
+        raise ValueError("scripts must be a non-empty list of long motions, each a list of (caption, length)")
+    plans = []
+    for i, sc in enumerate(scripts):
+        if isinstance(sc, (str, bytes)) or len(sc) == 0:
+            raise ValueError(f"motion {i}: a script is a non-empty list of (caption, length) segments")
+        caps, lens = [], []
+        for seg in sc:
+            if len(seg) != 2 or not isinstance(seg[0], str):
+                raise ValueError(f"motion {i}: segment {seg!r} is not a (caption, length) pair")
+            caps.append(seg[0])
+            lens.append(seg[1])
+        starts, C = plan_windows(lens, overlap, num_frames)
+        plans.append((caps, [int(n) for n in lens], starts, C))
+    return plans
+
+
+def plan_batches(plans, batch_size: int) -> List[List[int]]:
+    """The motions of ``plans`` (from ``script_plans``) dealt into batches in order: whole motions, at most ``batch_size``
+    windows each.  Raises ValueError for a motion of more windows than that."""
+    batches, cur = [], []
+    for i, (_, lens, _, _) in enumerate(plans):
+        if len(lens) > batch_size:
+            raise ValueError(f"motion {i} has {len(lens)} windows, more than batch_size = {batch_size}")
+        if cur and sum(len(plans[j][1]) for j in cur) + len(lens) > batch_size:
+            batches.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def batch_tables(plans, idx, T: int, overlap: int, blend: str = "linear") -> Dict[str, torch.Tensor]:
+    """The ``handshake_*`` model kwargs of one batch: the tables of motions ``idx``, whose windows are consecutive batch
+    rows in that order padded to T frames, merged."""
+    tabs, row = [], 0
+    for i in idx:
+        tabs.append(handshake_tables(plans[i][2], plans[i][1], T, overlap, blend, first_row=row))
+        row += len(plans[i][1])
+    return {"handshake_" + k: torch.from_numpy(v) for k, v in merge_tables(tabs).items()}
+
+
+def gather_canvases(values, plans, idx, T: int, dim_pose: int, what: str) -> torch.Tensor:
+    """``values[i]``, broadcast to motion i's canvas (C_i, dim_pose), for the motions ``idx`` of a batch, gathered into
+    their window rows (sum of windows, T, dim_pose) as float32."""
+    parts = []
+    for i in idx:
+        _, lens, starts, C = plans[i]
+        x = expand_to(torch.as_tensor(values[i], dtype=torch.float32), None, (C, dim_pose), what,
+                      fail_msg=f"{{name}} of motion {i} has shape {{shape}}, not broadcastable to its canvas {{target}}")
+        parts.append(canvas_to_windows(x, starts, lens, T))
+    return torch.cat(parts)
 
 
 def split_long(caption: str, total_frames: int, window: int, overlap: int) -> List[Tuple[str, int]]:

@@ -10,14 +10,16 @@ captions per sample composes them under per-prompt weight maps (time-varied and 
 weights from ``motion_compose``).  ``control_joints`` / ``control_weights`` (with ``mean`` / ``std``) steer joint positions:
 trajectories, keyframes, end positions (targets from ``motion_control``).  ``generate_long`` samples motions longer than
 the model's window from scripts of ``(caption, length)`` segments, overlapping windows tied together on every step
-(``motion_long``).  The training loop (forward/backward/update/train) is out of
-scope for this build and raises.
+(``motion_long``).  Every generate method checks its conditioning once (``conditioning.Conditioning``) and
+samples each batch's rows through ``_sample_rows``.  The training loop (forward/backward/update/train) is out of scope for
+this build and raises.
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 
+from . import motion_long as ML
+from .conditioning import Conditioning
 from .diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType, SpacedDiffusion, get_named_beta_schedule,
                         space_timesteps)
 
@@ -71,114 +73,20 @@ class DDPMTrainer(object):
             self._spaced[(sampler, n)] = SpacedDiffusion(use, **self._diffusion_kw)
         return self._spaced[(sampler, n)]
 
-    @staticmethod
-    def _edit_kwargs(edit_motion, edit_mask, rows, T, dim_pose):
-        """``inpaint_motion`` / ``inpaint_mask`` model kwargs of one batch: rows ``rows`` and the first T frames of
-        ``edit_motion`` (N, T_max, dim_pose) and of ``edit_mask`` broadcast to its shape; {} when neither is given."""
-        if edit_motion is None and edit_mask is None:
-            return {}
-        if edit_motion is None or edit_mask is None:
-            raise ValueError("edit_motion and edit_mask go together: give both or neither")
-        k = torch.as_tensor(edit_motion)
-        if k.dim() != 3 or k.shape[2] != dim_pose or k.shape[1] < T:
-            raise ValueError(f"edit_motion of shape {tuple(k.shape)} must be (N, T_max >= {T}, {dim_pose})")
-        try:
-            msk = torch.broadcast_to(torch.as_tensor(edit_mask), k.shape)
-        except RuntimeError:
-            raise ValueError(f"edit_mask of shape {tuple(torch.as_tensor(edit_mask).shape)} does not broadcast to "
-                             f"{tuple(k.shape)}") from None
-        return {"inpaint_motion": k[rows, :T], "inpaint_mask": msk[rows, :T]}
-
-    @staticmethod
-    def _control(control_joints, control_weights, mean, std, dim_pose):
-        """Check a controlled call: ``control_joints`` (N, T_max, J, 3) and ``control_weights`` broadcast to it (aligned on
-        the leading dim like ``check_control_kwargs``; a view), ``mean`` / ``std`` as float32 (dim_pose,) tensors.  None when
-        neither control tensor is given."""
-        if control_joints is None and control_weights is None:
-            return None
-        if control_joints is None or control_weights is None:
-            raise ValueError("control_joints and control_weights go together: give both or neither")
-        if mean is None or std is None:
-            raise ValueError("joint control needs the dataset's mean and std (the targets are de-normalised positions)")
-        from .motion_control import joints_for_feats
-        J = joints_for_feats(dim_pose)
-        g = torch.as_tensor(control_joints, dtype=torch.float32)
-        if g.dim() != 4 or tuple(g.shape[2:]) != (J, 3):
-            raise ValueError(f"control_joints of shape {tuple(g.shape)} must be (N, T_max, {J}, 3)")
-        w = torch.as_tensor(control_weights, dtype=torch.float32)
-        if w.dim() == 0 or w.dim() > 4 or w.shape[0] != g.shape[0]:
-            raise ValueError(f"control_weights of shape {tuple(w.shape)} must lead with N = {g.shape[0]}")
-        try:
-            w = w.reshape(tuple(w.shape) + (1,) * (4 - w.dim())).expand(g.shape)
-        except RuntimeError:
-            raise ValueError(f"control_weights of shape {tuple(w.shape)} does not broadcast to {tuple(g.shape)}") from None
-        ms = []
-        for name, v in (("mean", mean), ("std", std)):
-            v = torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v), dtype=torch.float32).flatten()
-            if v.numel() != dim_pose:
-                raise ValueError(f"{name} must have {dim_pose} entries")
-            ms.append(v)
-        return {"joints": g, "weights": w, "mean": ms[0], "std": ms[1]}
-
-    @staticmethod
-    def _control_kwargs(ctl, scale, iters, rows, T, device):
-        """``control_*`` model kwargs of one batch: rows ``rows`` and the first T frames of the checked control (from
-        _control); {} without control."""
-        if ctl is None:
-            return {}
-        g = ctl["joints"][rows]
-        if g.shape[1] < T:
-            raise ValueError(f"control_joints has {g.shape[1]} frames, the batch {T}")
-        n = g.shape[0]
-        return {"control_joints": g[:, :T].to(device), "control_weights": ctl["weights"][rows][:, :T].to(device),
-                "control_mean": ctl["mean"].to(device).expand(n, -1), "control_std": ctl["std"].to(device).expand(n, -1),
-                "control_scale": scale, "control_iters": iters}
-
-    @staticmethod
-    def _compose_weights(caption, prompt_weights, dim_pose):
-        """Check a composed call: every ``caption[i]`` a sequence of the same K strings; returns ``prompt_weights`` as a
-        float32 tensor broadcast to (N, K, T_w, dim_pose) (T_w = its frame dim, 1 when it has none; a view)."""
-        N = len(caption)
-        for c in caption:
-            if isinstance(c, str) or not all(isinstance(v, str) for v in c):
-                raise ValueError("with prompt_weights every caption must be a sequence of K strings")
-        ks = {len(c) for c in caption}
-        if len(ks) != 1:
-            raise ValueError(f"every sample must have the same number of prompts, not {sorted(ks)}")
-        K = ks.pop()
-        w = torch.as_tensor(prompt_weights, dtype=torch.float32)
-        if w.dim() > 4:
-            raise ValueError(f"prompt_weights of shape {tuple(w.shape)} has more dims than (N, K, T, dim_pose)")
-        if not bool(torch.isfinite(w).all()):
-            raise ValueError("prompt_weights has non-finite values")
-        w = w.reshape(tuple(w.shape) + (1,) * (4 - w.dim()))
-        try:
-            return w.expand(N, K, w.shape[2], dim_pose)
-        except RuntimeError:
-            raise ValueError(f"prompt_weights of shape {tuple(w.shape)} does not broadcast to (N={N}, K={K}, T, "
-                             f"{dim_pose})") from None
-
-    @staticmethod
-    def _text_kwargs(m, caption, weights, rows, T, device):
-        """Text model kwargs of one batch: the captions' embeddings, or with ``weights`` (from _compose_weights) the
-        composed prompts and the rows ``rows`` / first T frames of the weights."""
-        if weights is None:
-            xf_proj, xf_out = m.encode_text(caption, device)
-            return {"xf_proj": xf_proj, "xf_out": xf_out, "text": caption}
-        if weights.shape[2] != 1 and weights.shape[2] < T:
-            raise ValueError(f"prompt_weights has {weights.shape[2]} frames, the batch {T}")
-        w = weights[rows]
-        return {"compose_text": [list(c) for c in caption], "compose_weights": w[:, :, :T] if w.shape[2] != 1 else w}
-
-    def _sample(self, m, shape, sampler, sample_steps, eta, **kw):
+    def _sample_rows(self, cond, rows, lengths, T, sampler, sample_steps, eta, extra=None, **kw):
+        """Sample the batch of rows ``rows`` (a slice or an index tensor) of the call ``cond`` conditions, at T frames,
+        with the call's sampler: ``model_kwargs`` are the rows' share of the conditioning, ``lengths`` and ``extra``."""
+        m, shape = self._model(), (len(cond.captions_of(rows)), T, cond.dim_pose)
+        kw = dict(kw, cfg_scale=self.cfg_scale, clip_denoised=False,
+                  model_kwargs={**cond.kwargs(rows, T, self.device), "length": lengths, **(extra or {})})
         if eta != 0.0 and sampler != "ddim":
             raise ValueError("eta applies to the ddim sampler only")
         d = self.sampling_diffusion(sampler, sample_steps)
         if sampler == "ddpm":
-            return d.p_sample_loop_with_cfg(m, shape, cfg_scale=self.cfg_scale, **kw)
+            return d.p_sample_loop_with_cfg(m, shape, **kw)
         if sampler == "ddim":
-            return d.ddim_sample_loop_with_cfg(m, shape, cfg_scale=self.cfg_scale, eta=eta, **kw)
-        return d.dpm_solver_sample_loop_with_cfg(m, shape, cfg_scale=self.cfg_scale, order=2, **kw)
+            return d.ddim_sample_loop_with_cfg(m, shape, eta=eta, **kw)
+        return d.dpm_solver_sample_loop_with_cfg(m, shape, order=2, **kw)
 
     @torch.no_grad()
     def generate_batch(self, caption, m_lens, dim_pose, *, noise=None, step_noise=None, progress=True, seed=None,
@@ -192,19 +100,12 @@ class DDPMTrainer(object):
         ``control_joints`` (B, T_max, J, 3) target joint positions and ``control_weights`` (B, ...) broadcastable to them, with
         the dataset's ``mean`` / ``std`` (dim_pose,): every step's x0 is moved ``control_iters`` times down the gradient of
         the weighted squared distance, scaled by ``control_scale`` (units in ``motion_control``)."""
-        m = self._model()
+        cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
+                            control_scale, control_iters, mean, std)
         m_lens = torch.as_tensor(m_lens)
-        T = min(int(m_lens.max()), m.num_frames)
-        B = len(caption)
-        w = None if prompt_weights is None else self._compose_weights(caption, prompt_weights, dim_pose)
-        edit = self._edit_kwargs(edit_motion, edit_mask, slice(0, B), T, dim_pose)
-        ctl = self._control(control_joints, control_weights, mean, std, dim_pose)
-        ctl = self._control_kwargs(ctl, control_scale, control_iters, slice(0, B), T, self.device)
-        text = self._text_kwargs(m, caption, w, slice(0, B), T, self.device)
-        return self._sample(
-            m, (B, T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress, noise=noise,
-            step_noise=step_noise, model_kwargs={**text, "length": m_lens, **edit, **ctl}, seed=seed,
-            sample_offset=sample_offset)
+        T = min(int(m_lens.max()), self._model().num_frames)
+        return self._sample_rows(cond, slice(0, len(caption)), m_lens, T, sampler, sample_steps, eta, progress=progress,
+                                 noise=noise, step_noise=step_noise, seed=seed, sample_offset=sample_offset)
 
     @torch.no_grad()
     def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None, sampler="ddpm",
@@ -221,30 +122,17 @@ class DDPMTrainer(object):
         rows."""
         N = len(caption)
         self.eval_mode()
-        ctl = self._control(control_joints, control_weights, mean, std, dim_pose)
-        if prompt_weights is not None:
-            prompt_weights = self._compose_weights(caption, prompt_weights, dim_pose)
-        if edit_motion is not None and edit_mask is not None:
-            edit_motion = torch.as_tensor(edit_motion)
-            edit_mask = self._edit_kwargs(edit_motion, edit_mask, slice(None), edit_motion.shape[1],
-                                          dim_pose)["inpaint_mask"]
+        cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
+                            control_scale, control_iters, mean, std)
         all_output = []
-        cur = 0
-        while cur < N:
+        for cur in range(0, N, batch_size):
             end = min(cur + batch_size, N)
             x_T, step_noise = noises[cur // batch_size] if noises is not None else (None, None)
-            out = self.generate_batch(caption[cur:end], m_lens[cur:end], dim_pose, progress=progress, seed=seed,
-                                      sample_offset=cur, noise=x_T, step_noise=step_noise, sampler=sampler,
-                                      sample_steps=sample_steps, eta=eta,
-                                      edit_motion=None if edit_motion is None else edit_motion[cur:end],
-                                      edit_mask=None if edit_mask is None else edit_mask[cur:end],
-                                      prompt_weights=None if prompt_weights is None else prompt_weights[cur:end],
-                                      control_joints=None if ctl is None else ctl["joints"][cur:end],
-                                      control_weights=None if ctl is None else ctl["weights"][cur:end],
-                                      control_scale=control_scale, control_iters=control_iters,
-                                      mean=None if ctl is None else ctl["mean"], std=None if ctl is None else ctl["std"])
+            lens = torch.as_tensor(m_lens[cur:end])
+            T = min(int(lens.max()), self._model().num_frames)
+            out = self._sample_rows(cond, slice(cur, end), lens, T, sampler, sample_steps, eta, progress=progress,
+                                    noise=x_T, step_noise=step_noise, seed=seed, sample_offset=cur)
             all_output.extend(out[i] for i in range(out.shape[0]))
-            cur += batch_size
         return all_output
 
     @torch.no_grad()
@@ -262,21 +150,14 @@ class DDPMTrainer(object):
         from . import dist as D
         m = self._model()
         self.eval_mode()
-        w = None if prompt_weights is None else self._compose_weights(caption, prompt_weights, dim_pose)
-        ctl = self._control(control_joints, control_weights, mean, std, dim_pose)
+        cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
+                            control_scale, control_iters, mean, std)
         lens = torch.as_tensor(m_lens).flatten().long().cpu()
         plan = D.plan_buckets(lens, batch_size, m.num_frames, unit_length)
 
-        def run_bucket(k, idx, T):
-            cap = [caption[i] for i in idx.tolist()]
-            ln = lens[idx].clamp(max=T).to(self.device)
-            edit = self._edit_kwargs(edit_motion, edit_mask, idx, T, dim_pose)
-            text = self._text_kwargs(m, cap, w, idx, T, self.device)
-            ck = self._control_kwargs(ctl, control_scale, control_iters, idx, T, self.device)
-            return self._sample(
-                m, (len(cap), T, dim_pose), sampler, sample_steps, eta, clip_denoised=False, progress=progress,
-                model_kwargs={**text, "length": ln, **edit, **ck},
-                seed=seed, sample_offset=idx)  # noise keyed on each row's index in the CALLER's list: == generate(seed=)
+        def run_bucket(k, idx, T):  # noise keyed on each row's index in the CALLER's list: == generate(seed=)
+            return self._sample_rows(cond, idx, lens[idx].clamp(max=T).to(self.device), T, sampler, sample_steps, eta,
+                                     progress=progress, seed=seed, sample_offset=idx)
 
         return D.run_plan(plan, run_bucket, len(caption), m.num_frames, dim_pose, self.device, group)
 
@@ -332,18 +213,22 @@ class DDPMTrainer(object):
         ``edit_motion`` / ``edit_mask``: motion editing in normalised feature space, as in ``generate``;
         ``prompt_weights``: composed prompts, as in ``generate``; ``control_joints`` / ``control_weights`` /
         ``control_scale`` / ``control_iters``: joint-position control under this call's ``mean`` / ``std``."""
-        from .postprocess import motion_to_joints
-        gen = self.generate_bucketed if bucketed else self.generate
-        if control_joints is not None or control_weights is not None:
-            kw = dict(kw, control_joints=control_joints, control_weights=control_weights, control_scale=control_scale,
-                      control_iters=control_iters, mean=mean, std=std)
+        gen = self.generate_bucketed if bucketed else self.generate  # mean / std go along: unused without control
         motions = gen(caption, m_lens, dim_pose, batch_size, sampler=sampler, sample_steps=sample_steps, eta=eta,
-                      edit_motion=edit_motion, edit_mask=edit_mask, prompt_weights=prompt_weights, **kw)
+                      edit_motion=edit_motion, edit_mask=edit_mask, prompt_weights=prompt_weights,
+                      control_joints=control_joints, control_weights=control_weights, control_scale=control_scale,
+                      control_iters=control_iters, mean=mean, std=std, **kw)
         lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
+        return self._to_joints(motions, lens, dim_pose, mean, std, joints_num, sigma)
+
+    @staticmethod
+    def _to_joints(motions, lens, dim_pose, mean, std, joints_num, sigma):
+        """``postprocess.motion_to_joints`` over the first ``lens[i]`` frames of every motion: one launch for all."""
+        from .postprocess import motion_to_joints
         x = torch.zeros((len(motions), max(mo.shape[0] for mo in motions), dim_pose), device=motions[0].device)
         for i, mo in enumerate(motions):
             x[i, :mo.shape[0]] = mo
-        j = motion_to_joints(x, mean, std, torch.tensor(lens), joints_num, sigma)  # one launch for all samples
+        j = motion_to_joints(x, mean, std, torch.tensor(lens), joints_num, sigma)
         return [j[i, :n] for i, n in enumerate(lens)]
 
     @torch.no_grad()
@@ -358,10 +243,9 @@ class DDPMTrainer(object):
         depend on ``batch_size``.  ``edit_motion`` / ``edit_mask``: one (canvas_len, dim_pose) known motion per motion and
         a mask broadcastable to it (or None entries), kept where the mask is 1, e.g. a prefix to continue.  ``noise``: one
         (canvas_len, dim_pose) x_T per motion.  ``sampler`` / ``sample_steps`` / ``eta`` as in ``generate``."""
-        from . import motion_long as ML
         m = self._model()
         self.eval_mode()
-        plans = self._long_plans(scripts, overlap, m.num_frames)
+        plans = ML.script_plans(scripts, overlap, m.num_frames)
         N = len(plans)
         per = {}
         for name, v in (("edit_motion", edit_motion), ("edit_mask", edit_mask), ("noise", noise)):
@@ -373,63 +257,27 @@ class DDPMTrainer(object):
         for i, (km, mk) in enumerate(zip(per["edit_motion"], per["edit_mask"])):
             if (km is None) != (mk is None):
                 raise ValueError(f"motion {i}: edit_motion and edit_mask go together")
-        if any(km is not None for km in per["edit_motion"]) and not all(km is not None for km in per["edit_motion"]):
-            raise ValueError("edit_motion must be given for every motion of the call or for none")
-        if any(x is not None for x in per["noise"]) and not all(x is not None for x in per["noise"]):
-            raise ValueError("noise must be given for every motion of the call or for none")
-        batches, cur, first = [], [], 0  # whole motions, at most batch_size windows each
-        for i, (caps, lens, starts, C) in enumerate(plans):
-            if len(lens) > batch_size:
-                raise ValueError(f"motion {i} has {len(lens)} windows, more than batch_size = {batch_size}")
-            if cur and sum(len(plans[j][1]) for j in cur) + len(lens) > batch_size:
-                batches.append(cur)
-                cur = []
-            cur.append(i)
-        if cur:
-            batches.append(cur)
-        out = [None] * N
-        for idx in batches:
+        for name in ("edit_motion", "noise"):
+            if any(x is not None for x in per[name]) and not all(x is not None for x in per[name]):
+                raise ValueError(f"{name} must be given for every motion of the call or for none")
+        out, first = [None] * N, 0
+        for idx in ML.plan_batches(plans, batch_size):
             caps = [c for i in idx for c in plans[i][0]]
             lens = [n for i in idx for n in plans[i][1]]
             T = max(lens) + max(lens) % 2  # the denoiser takes even T
-            tabs, row = [], 0
-            for i in idx:
-                tabs.append(ML.handshake_tables(plans[i][2], plans[i][1], T, overlap, blend, first_row=row))
-                row += len(plans[i][1])
-            tab = ML.merge_tables(tabs)
-            kw = {"handshake_offsets": torch.from_numpy(tab["offsets"]), "handshake_rows": torch.from_numpy(tab["rows"]),
-                  "handshake_weights": torch.from_numpy(tab["weights"]),
-                  "handshake_owner_rows": torch.from_numpy(tab["owner_rows"])}
-
-            def gather(v, what):
-                parts = []
+            kw = ML.batch_tables(plans, idx, T, overlap, blend)
+            rows = {}  # the per-motion canvases given, as window rows
+            for name in ("edit_motion", "edit_mask", "noise"):
+                if per[name][idx[0]] is None:
+                    continue
                 for i in idx:
-                    _, ln, st, C = plans[i]
-                    x = torch.as_tensor(v[i], dtype=torch.float32)
-                    try:
-                        x = torch.broadcast_to(x, (C, dim_pose))
-                    except RuntimeError:
-                        raise ValueError(f"{what} of motion {i} has shape {tuple(x.shape)}, not broadcastable to its "
-                                         f"canvas {(C, dim_pose)}") from None
-                    parts.append(ML.canvas_to_windows(x, st, ln, T))
-                return torch.cat(parts).to(self.device)
-
-            if per["edit_motion"][idx[0]] is not None:
-                for i in idx:
-                    if tuple(torch.as_tensor(per["edit_motion"][i]).shape) != (plans[i][3], dim_pose):
-                        raise ValueError(f"edit_motion of motion {i} must be {(plans[i][3], dim_pose)}")
-                kw["inpaint_motion"] = gather(per["edit_motion"], "edit_motion")
-                kw["inpaint_mask"] = gather(per["edit_mask"], "edit_mask")
-            x_T = None
-            if per["noise"][idx[0]] is not None:
-                for i in idx:
-                    if tuple(torch.as_tensor(per["noise"][i]).shape) != (plans[i][3], dim_pose):
-                        raise ValueError(f"noise of motion {i} must be {(plans[i][3], dim_pose)}")
-                x_T = gather(per["noise"], "noise")
-            text = self._text_kwargs(m, caps, None, None, T, self.device)
-            res = self._sample(m, (len(caps), T, dim_pose), sampler, sample_steps, eta, clip_denoised=False,
-                               progress=progress, noise=x_T, model_kwargs={**text, "length": torch.tensor(lens), **kw},
-                               seed=seed, sample_offset=first)
+                    if name != "edit_mask" and tuple(torch.as_tensor(per[name][i]).shape) != (plans[i][3], dim_pose):
+                        raise ValueError(f"{name} of motion {i} must be {(plans[i][3], dim_pose)}")
+                rows[name] = ML.gather_canvases(per[name], plans, idx, T, dim_pose, name).to(self.device)
+            if "edit_motion" in rows:
+                kw.update(inpaint_motion=rows["edit_motion"], inpaint_mask=rows["edit_mask"])
+            res = self._sample_rows(Conditioning(caps, dim_pose), slice(None), torch.tensor(lens), T, sampler, sample_steps,
+                                    eta, extra=kw, progress=progress, noise=rows.get("noise"), seed=seed, sample_offset=first)
             first += len(caps)
             row = 0
             for i in idx:
@@ -438,43 +286,17 @@ class DDPMTrainer(object):
                 row += n
         return out
 
-    @staticmethod
-    def _long_plans(scripts, overlap, num_frames):
-        """Checked scripts: per motion (captions, lengths, window starts, canvas length)."""
-        from . import motion_long as ML
-        if isinstance(scripts, (str, bytes)) or len(scripts) == 0:
-            raise ValueError("scripts must be a non-empty list of long motions, each a list of (caption, length)")
-        plans = []
-        for i, sc in enumerate(scripts):
-            if isinstance(sc, (str, bytes)) or len(sc) == 0:
-                raise ValueError(f"motion {i}: a script is a non-empty list of (caption, length) segments")
-            caps, lens = [], []
-            for seg in sc:
-                if len(seg) != 2 or not isinstance(seg[0], str):
-                    raise ValueError(f"motion {i}: segment {seg!r} is not a (caption, length) pair")
-                caps.append(seg[0])
-                lens.append(seg[1])
-            starts, C = ML.plan_windows(lens, overlap, num_frames)
-            plans.append((caps, [int(n) for n in lens], starts, C))
-        return plans
-
     @torch.no_grad()
     def generate_long_joints(self, scripts, dim_pose, mean, std, *, joints_num=22, sigma=1.0, **kw):
         """``generate_long`` followed by ``postprocess.motion_to_joints`` over each whole canvas (one continuous root
         path): a list of ``(canvas_len, joints_num, 3)`` joint positions.  The post-processing kernel holds a canvas in
         LDS: at most MAX_JOINTS_FRAMES frames."""
-        from .postprocess import motion_to_joints
-        plans = self._long_plans(scripts, kw.get("overlap", 20), self._model().num_frames)
+        plans = ML.script_plans(scripts, kw.get("overlap", 20), self._model().num_frames)
         longest = max(p[3] for p in plans)
         if longest > MAX_JOINTS_FRAMES:
             raise ValueError(f"a canvas of {longest} frames: joint recovery takes at most {MAX_JOINTS_FRAMES} frames")
         motions = self.generate_long(scripts, dim_pose, **kw)
-        lens = [mo.shape[0] for mo in motions]
-        x = torch.zeros((len(motions), max(lens), dim_pose), device=motions[0].device)
-        for i, mo in enumerate(motions):
-            x[i, :mo.shape[0]] = mo
-        j = motion_to_joints(x, mean, std, torch.tensor(lens), joints_num, sigma)
-        return [j[i, :n] for i, n in enumerate(lens)]
+        return self._to_joints(motions, [mo.shape[0] for mo in motions], dim_pose, mean, std, joints_num, sigma)
 
     def save(self, file_name, ep, total_it):
         state = {"opt_encoder": getattr(self, "opt_encoder_state", {}), "ep": ep, "total_it": total_it,

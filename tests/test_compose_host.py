@@ -123,20 +123,25 @@ def _cpu_trainer():
 
 
 def test_trainer_prompt_weight_checks():
-    Tr = pkg("trainer")
-    cw = Tr.DDPMTrainer._compose_weights
+    Cond = pkg("conditioning").Conditioning
+    cw = lambda caps, w, dim_pose: Cond(caps, dim_pose, prompt_weights=w).weights  # noqa: E731
     caps = [("a", "b"), ("c", "d"), ("e", "f")]
     assert cw(caps, 1, 263).shape == (3, 2, 1, 263)
     assert cw(caps, torch.ones(3, 2), 263).shape == (3, 2, 1, 263)
-    w = cw(caps, torch.rand(1, 2, 16, 1), 263)
+    cond = Cond(caps, 263, prompt_weights=torch.rand(1, 2, 16, 1))
+    w = cond.weights
     assert w.shape == (3, 2, 16, 263)
     assert cw(caps, torch.rand(1, 2, 1, 263), 263).shape == (3, 2, 1, 263)
-    kw = Tr.DDPMTrainer._text_kwargs(None, caps[1:], w, slice(1, 3), 10, "cpu")
+    kw = cond.text_kwargs(slice(1, 3), 10)
     assert kw["compose_text"] == [["c", "d"], ["e", "f"]] and torch.equal(kw["compose_weights"], w[1:3, :, :10])
-    kw = Tr.DDPMTrainer._text_kwargs(None, caps, cw(caps, 1, 263), torch.tensor([2, 0]), 10, "cpu")
+    kw = Cond(caps, 263, prompt_weights=1).text_kwargs(torch.tensor([2, 0]), 10)
     assert kw["compose_weights"].shape == (2, 2, 1, 263) and "xf_proj" not in kw
+    assert kw["compose_text"] == [["e", "f"], ["a", "b"]]
+    assert sorted(Cond(caps, 263, prompt_weights=1).kwargs(torch.tensor([2, 0]), 10, "cpu")) == sorted(kw)
     with pytest.raises(ValueError):  # the weights cover fewer frames than the batch
-        Tr.DDPMTrainer._text_kwargs(None, caps, w, slice(0, 3), 17, "cpu")
+        cond.text_kwargs(slice(0, 3), 17)
+    with pytest.raises(ValueError):
+        cond.kwargs(slice(0, 3), 17, "cpu")
     for bad_caps, bad_w in ((["a", "b", "c"], 1), ([("a", "b"), ("c",), ("d", "e")], 1), ([("a", 1)] * 3, 1),
                             (caps, torch.ones(3, 3)), (caps, torch.ones(2, 2)), (caps, torch.ones(3, 2, 16, 262)),
                             (caps, torch.ones(3, 2, 16, 263, 1)), (caps, torch.rand(2, 1, 263)), (caps, torch.full((3, 2), float("nan")))):

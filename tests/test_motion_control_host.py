@@ -217,23 +217,29 @@ def test_shard_kwargs_gives_each_rank_its_rows():
 
 # ---- trainer arguments --------------------------------------------------------------------------------------------------
 def test_trainer_control_arguments():
-    Tr = pkg("trainer").DDPMTrainer
+    Cond = pkg("conditioning").Conditioning
+    caps = ["a", "b", "c"]
     g = torch.zeros(3, 10, 22, 3)
     mean, std = np.zeros(263, np.float32), np.ones(263, np.float32)
-    assert Tr._control(None, None, None, None, 263) is None
-    c = Tr._control(g, torch.ones(3, 10), mean, std, 263)
+
+    def ctl(g, w, mean, std, dim_pose=263, **kw):
+        return Cond(caps, dim_pose, control_joints=g, control_weights=w, mean=mean, std=std, **kw)
+
+    assert ctl(None, None, None, None).control is None
+    assert ctl(None, None, mean, std).control is None and ctl(None, None, mean, std).control_kwargs(slice(0, 3), 6, "cpu") == {}
+    c = ctl(g, torch.ones(3, 10), mean, std).control
     assert c["weights"].shape == (3, 10, 22, 3) and c["mean"].shape == (263,)
-    kw = Tr._control_kwargs(c, 2.0, 4, slice(1, 3), 6, "cpu")
+    kw = ctl(g, torch.ones(3, 10), mean, std, control_scale=2.0, control_iters=4).control_kwargs(slice(1, 3), 6, "cpu")
     assert kw["control_joints"].shape == (2, 6, 22, 3) and kw["control_weights"].shape == (2, 6, 22, 3)
     assert kw["control_mean"].shape == (2, 263) and kw["control_scale"] == 2.0 and kw["control_iters"] == 4
-    kw = Tr._control_kwargs(c, 1.0, 1, torch.tensor([2, 0]), 10, "cpu")
-    assert kw["control_joints"].shape == (2, 10, 22, 3)
+    kw = ctl(g, torch.ones(3, 10), mean, std).kwargs(torch.tensor([2, 0]), 10, "cpu")
+    assert kw["control_joints"].shape == (2, 10, 22, 3) and kw["control_scale"] == 1.0 and kw["control_iters"] == 1
     with pytest.raises(ValueError):
-        Tr._control_kwargs(c, 1.0, 1, slice(0, 3), 11, "cpu")
+        ctl(g, torch.ones(3, 10), mean, std).control_kwargs(slice(0, 3), 11, "cpu")
     for args in ((g, None, mean, std), (None, torch.ones(3), mean, std), (g, torch.ones(3), None, std),
                  (g, torch.ones(3), mean, None), (torch.zeros(3, 10, 21, 3), torch.ones(3), mean, std),
                  (g, torch.ones(2), mean, std), (g, torch.ones(3, 10, 7), mean, std), (g, torch.ones(3), mean[:5], std)):
         with pytest.raises(ValueError):
-            Tr._control(*args, 263)
+            ctl(*args)
     with pytest.raises(ValueError):
-        Tr._control(torch.zeros(3, 10, 22, 3), torch.ones(3), np.zeros(262), np.ones(262), 262)
+        ctl(torch.zeros(3, 10, 22, 3), torch.ones(3), np.zeros(262), np.ones(262), 262)

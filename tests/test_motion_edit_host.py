@@ -148,20 +148,22 @@ def test_inpaint_kwargs_validation():
 
 
 def test_trainer_edit_kwargs_slice_rows_and_frames():
-    Tr = pkg("trainer")
+    Cond = pkg("conditioning").Conditioning
     E = pkg("motion_edit")
+    caps = ["a", "b", "c"]
     k = torch.arange(3 * 8 * 263, dtype=torch.float32).view(3, 8, 263)
-    assert Tr.DDPMTrainer._edit_kwargs(None, None, slice(0, 3), 8, 263) == {}
-    kw = Tr.DDPMTrainer._edit_kwargs(k, E.prefix_mask(8, 2), torch.tensor([2, 0]), 5, 263)
+    assert Cond(caps, 263).edit_kwargs(slice(0, 3), 8) == {}
+    assert Cond(caps, 263).kwargs(slice(0, 3), 8, "cpu") == {"text": caps}
+    kw = Cond(caps, 263, edit_motion=k, edit_mask=E.prefix_mask(8, 2)).edit_kwargs(torch.tensor([2, 0]), 5)
     assert torch.equal(kw["inpaint_motion"], k[[2, 0], :5])
     assert kw["inpaint_mask"].shape == (2, 5, 263) and kw["inpaint_mask"][:, :2].eq(1).all()
     assert kw["inpaint_mask"][:, 2:].eq(0).all()
-    kw = Tr.DDPMTrainer._edit_kwargs(k, E.joint_feature_mask(E.LOWER_BODY), slice(1, 3), 8, 263)
-    assert torch.equal(kw["inpaint_mask"][1, 7], E.joint_feature_mask(E.LOWER_BODY))
+    kw = Cond(caps, 263, edit_motion=k, edit_mask=E.joint_feature_mask(E.LOWER_BODY)).kwargs(slice(1, 3), 8, "cpu")
+    assert torch.equal(kw["inpaint_mask"][1, 7], E.joint_feature_mask(E.LOWER_BODY)) and kw["text"] == ["b", "c"]
     for bad in ((k, None), (None, torch.ones(8, 1)), (k[:, :4], torch.ones(4, 1)), (k[..., :262], torch.ones(1)),
                 (k, torch.ones(7, 1))):
         with pytest.raises(ValueError):
-            Tr.DDPMTrainer._edit_kwargs(*bad, slice(0, 3), 5, 263)
+            Cond(caps, 263, edit_motion=bad[0], edit_mask=bad[1]).edit_kwargs(slice(0, 3), 5)
 
 
 def test_inpaint_entry_rejects_bad_arguments_without_a_gpu():

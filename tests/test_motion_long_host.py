@@ -182,6 +182,63 @@ def test_check_handshake_kwargs():
         D.check_handshake_kwargs(_kw(), (2, 16, 263))                        # rows of a third window in a batch of two
 
 
+def test_plan_batches_keeps_motions_whole_and_in_order():
+    ML = _ml()
+    plans = ML.script_plans([[("a", 16)] * 2, [("b", 16)] * 3, [("c", 16)], [("d", 16)] * 2, [("e", 12)] * 4], 4, 16)
+    assert [len(p[1]) for p in plans] == [2, 3, 1, 2, 4] and plans[1][0] == ["b"] * 3 and plans[4][2:] == ([0, 8, 16, 24], 36)
+    assert ML.plan_batches(plans, 4) == [[0], [1, 2], [3], [4]]      # a motion that does not fit starts the next batch
+    assert ML.plan_batches(plans, 5) == [[0, 1], [2, 3], [4]]
+    assert ML.plan_batches(plans, 6) == [[0, 1, 2], [3, 4]]
+    assert ML.plan_batches(plans, 100) == [[0, 1, 2, 3, 4]]
+    assert ML.plan_batches(plans[:1], 2) == [[0]]
+    for bs in (4, 5, 6, 7, 12):  # every motion once, in order, never more windows than batch_size
+        got = ML.plan_batches(plans, bs)
+        assert [i for b in got for i in b] == [0, 1, 2, 3, 4]
+        assert all(sum(len(plans[i][1]) for i in b) <= bs for b in got)
+    with pytest.raises(ValueError, match="motion 4 has 4 windows, more than batch_size = 3"):
+        ML.plan_batches(plans, 3)
+
+
+def test_gather_canvases_against_canvas_to_windows():
+    ML = _ml()
+    plans = ML.script_plans([[("a", 6), ("b", 4)], [("c", 5)], [("d", 4), ("e", 4), ("f", 6)]], 2, 8)
+    assert [p[3] for p in plans] == [8, 5, 10]
+    canv = [torch.arange(8 * 3, dtype=torch.float64).view(8, 3), None, 100 + torch.arange(10 * 3, dtype=torch.float32).view(10, 3)]
+    got = ML.gather_canvases(canv, plans, [2, 0], 6, 3, "noise")
+    assert got.shape == (5, 6, 3) and got.dtype == torch.float32
+    want = torch.cat([ML.canvas_to_windows(canv[2], [0, 2, 4], [4, 4, 6], 6), ML.canvas_to_windows(canv[0].float(), [0, 4], [6, 4], 6)])
+    assert torch.equal(got, want)
+    # by hand: window 1 of motion 2 is canvas frames 2..5, then padding; window 1 of motion 0 is canvas frames 4..7
+    assert torch.equal(got[1, :4], canv[2][2:6]) and torch.equal(got[1, 4:], torch.zeros(2, 3))
+    assert torch.equal(got[4, :4], canv[0][4:8].float()) and torch.equal(got[4, 4:], torch.zeros(2, 3))
+    # values broadcast to the canvas: a (C, 1) frame mask, a (dim_pose,) feature mask
+    fm = torch.tensor([1.0, 1.0, 0.0, 0.0, 0.0])[:, None]
+    got = ML.gather_canvases([None, fm, None], plans, [1], 6, 3, "edit_mask")
+    assert got.shape == (1, 6, 3) and got[0, :, 1].tolist() == [1.0, 1.0, 0.0, 0.0, 0.0, 0.0]
+    assert torch.equal(ML.gather_canvases([None, torch.tensor([1.0, 0.0, 1.0]), None], plans, [1], 6, 3, "edit_mask")[0, :5],
+                       torch.tensor([1.0, 0.0, 1.0]).expand(5, 3))
+    with pytest.raises(ValueError, match=r"edit_mask of motion 1 has shape \(4, 1\), not broadcastable to its canvas \(5, 3\)"):
+        ML.gather_canvases([None, fm[:4], None], plans, [1], 6, 3, "edit_mask")
+
+
+@pytest.mark.parametrize("blend", ["linear", "uniform"])
+def test_batch_tables_of_two_motions_pass_the_sampler_check(blend):
+    ML = _ml()
+    D = pkg("diffusion")
+    plans = ML.script_plans([[("a", 16), ("b", 12), ("c", 16)], [("d", 10)], [("e", 14), ("f", 16)]], 4, 16)
+    kw = ML.batch_tables(plans, [0, 2], 16, 4, blend)
+    assert sorted(kw) == ["handshake_offsets", "handshake_owner_rows", "handshake_rows", "handshake_weights"]
+    hs = D.check_handshake_kwargs(kw, (5, 16, 263))
+    assert hs["nshared"] == 12 and hs["offsets"].tolist() == list(range(0, 25, 2))
+    # the second motion's windows are batch rows 3 and 4: frames 10..13 of row 3 meet frames 0..3 of row 4
+    assert hs["rows"][16:].tolist() == [3 * 16 + 10, 4 * 16, 3 * 16 + 11, 4 * 16 + 1, 3 * 16 + 12, 4 * 16 + 2, 3 * 16 + 13, 4 * 16 + 3]
+    one = ML.handshake_tables(plans[0][2], plans[0][1], 16, 4, blend)
+    assert hs["rows"][:16].tolist() == one["rows"].tolist() and hs["weights"][:16].tolist() == one["weights"].tolist()
+    with pytest.raises(ValueError):  # the same tables over a batch that lacks the last window's row
+        D.check_handshake_kwargs(kw, (4, 16, 263))
+    assert D.check_handshake_kwargs(ML.batch_tables(plans, [1], 10, 4, blend), (1, 10, 263)) is None  # one window: no overlap
+
+
 def test_compose_and_control_with_handshakes_are_not_implemented():
     D = pkg("diffusion")
     shape = (3, 16, 263)
