@@ -429,6 +429,35 @@ int mdm_motion_postprocess(const float* motion, const int32_t* length, const flo
                            int32_t T, int32_t feats, int32_t joints, int32_t radius, const double* weights,
                            float* scratch, float* joints_out, void* stream);
 
+/* Joints -> feature rows on the device (csrc/motion_features.hip): the inverse of mdm_motion_postprocess,
+ * restating utils/motion_process.py process_file / extract_features.  The skeleton is data: parent-ordered kinematic chains
+ * (chain c is chain_joints[chain_offsets[c] .. chain_offsets[c + 1]); it starts at joint 0 or at a joint an earlier chain
+ * reached), one axis direction per bone (raw_offsets, (joints, 3)), the face joints in the reference's list order
+ * (r_hip, l_hip, sdr_r, sdr_l), the four foot joints in contact-column order and the two leg joints whose bone lengths give
+ * the uniform skeleton's scale.  A host struct, checked before the launch (every index inside [0, joints)). */
+enum { MDM_SKEL_MAX_JOINTS = 32, MDM_SKEL_MAX_CHAINS = 8, MDM_SKEL_MAX_CHAIN_ENTRIES = 48 };
+typedef struct {
+  int32_t joints, nchains;
+  int32_t chain_offsets[MDM_SKEL_MAX_CHAINS + 1];
+  int32_t chain_joints[MDM_SKEL_MAX_CHAIN_ENTRIES];
+  float raw_offsets[MDM_SKEL_MAX_JOINTS * 3];
+  int32_t face[4], feet[4], legs[2];
+} MdmSkeleton;
+/* joints (B, T, J, 3) fp32, length (B) int32 or NULL (= T), mean / std (F = 12 J - 1) or both NULL (rows not normalised).
+ * features_out (B, T - 1, F): a clip of n frames gives n - 1 rows (the last frame only supplies velocities); rows at or past
+ * length[b] - 1 are zero.  canonicalize != 0: the clip is first put on the floor, frame 0's root XZ moved to the origin and
+ * frame 0 turned to face Z+; with target_offsets (J, 3) it is before that re-posed on those bone offsets (uniform_skeleton).
+ * The canonical positions go to positions_out (B, T, J, 3), which is then required (frames past the length zero).
+ * canonicalize == 0: the joints are taken as they are, positions_out is not touched and target_offsets must be NULL.
+ * weights[0..radius]: fp64 taps of the facing-direction filter (sigma 20: radius 80), as for mdm_motion_postprocess.
+ * feet_thre: squared displacement per frame under which a foot joint is in contact.
+ * MDM_ERR_ARG: a null pointer, T < 2, a malformed skeleton; MDM_ERR_UNSUPPORTED: T > mdm_motion_features_max_frames(). */
+int mdm_motion_features_max_frames(void);
+int mdm_motion_features(const float* joints, const int32_t* length, const float* mean, const float* std,
+                        const MdmSkeleton* skeleton, const float* target_offsets, int32_t B, int32_t T, double feet_thre,
+                        int32_t canonicalize, int32_t radius, const double* weights, float* positions_out,
+                        float* features_out, void* stream);
+
 /* Joint-position control (csrc/motion_control.hip).  For sample b, with J = (F + 1) / 12 joints (F must be
  * 12 J - 1: 263 -> 22, 251 -> 21), targets G and weights W dense fp32 (B, T, J, 3), W >= 0 and finite, mean / std fp32
  * (B, F) (one row per sample), and P = recover_from_ric(x0 * std + mean) without temporal filter (as mdm_motion_postprocess

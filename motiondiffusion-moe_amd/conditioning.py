@@ -232,24 +232,88 @@ def check_handshake_kwargs(kw, shape):
             "owner_rows": own.to(torch.int32), "nshared": ns}
 
 
+def edit_rows_from_joints(edit_joints, mean, std, dim_pose, device=None, to_motion=None):
+    """``edit_joints``, a list of N joint clips (n_i, J, 3) (or a padded (N, T, J, 3) tensor: every clip T frames), as the
+    known motion of an edit: (rows (N, max n_i - 1, dim_pose), normalised with ``mean`` / ``std`` and zero past each clip,
+    and the row counts n_i - 1).  One call of ``to_motion`` (default ``motion_features.joints_to_motion``, the HIP kernel;
+    tests inject a CPU function) on the clips moved to ``device``, canonicalised as the training data was: on the floor,
+    frame 0's root XZ at the origin and facing Z+.  Raises ValueError without mean / std or for a dim_pose that is neither
+    the HumanML3D nor the KIT width."""
+    if mean is None or std is None:
+        raise ValueError("edit_joints needs the dataset's mean and std (feature rows are normalised, joints are not)")
+    skeleton = {263: "t2m", 251: "kit"}.get(int(dim_pose))
+    if skeleton is None:
+        raise ValueError(f"edit_joints needs dim_pose 263 (HumanML3D) or 251 (KIT), not {dim_pose}")
+    if torch.is_tensor(edit_joints) or isinstance(edit_joints, np.ndarray):
+        edit_joints = list(torch.as_tensor(edit_joints))
+    clips = [torch.as_tensor(c) if device is None else torch.as_tensor(c).to(device) for c in edit_joints]
+    if to_motion is None:
+        from .motion_features import joints_to_motion as to_motion
+    rows = to_motion(clips, None, mean, std, skeleton=skeleton)
+    return rows, [int(c.shape[0]) - 1 for c in clips]
+
+
+def check_joint_edit_mask(mask, rows):
+    """``mask`` (N, T, F), expanded, against the row counts of the clips an edit was given as: a clip of n joint frames has
+    n - 1 feature rows, so a mask that keeps frame n - 1 or a later one asks for a row that does not exist."""
+    for i, n in enumerate(rows):
+        if bool((mask[i, n:] != 0).any()):
+            raise ValueError(f"edit_mask keeps a frame at or past {n} of sample {i}, whose clip of {n + 1} joint frames gives "
+                             f"{n} feature rows (the last frame only supplies velocities): the clip is one frame short")
+
+
+def joint_edit_mask_frames(mask, rows):
+    """The frames the mask of an ``edit_joints`` call covers: its frame dim, second to last as ``edit_mask`` broadcasts by
+    its trailing dims ((T, 1), (N, T, 1), (N, T, F)); 0 for a mask without one ((F,), (1, F)).  Raises ValueError for a mask
+    of more than 3 dims and for one that covers fewer frames than the longest clip has rows (``rows``)."""
+    m = torch.as_tensor(mask)
+    if m.dim() > 3:
+        raise ValueError(f"edit_mask of shape {tuple(m.shape)} has more dims than (N, T, dim_pose)")
+    T = int(m.shape[-2]) if m.dim() >= 2 and m.shape[-2] != 1 else 0
+    if T and T < rows:
+        raise ValueError(f"edit_mask covers {T} frames, the longest clip of edit_joints gives {rows} feature rows: give a "
+                         "mask over the whole motion, or shorter clips")
+    return T
+
+
+def pad_frames(x, T):
+    """``x`` (N, t, F) zero-padded along its frame dim to T frames (returned as it is when t >= T)."""
+    if x.shape[1] >= T:
+        return x
+    return torch.cat([x, x.new_zeros((x.shape[0], T - x.shape[1], x.shape[2]))], dim=1)
+
+
 class Conditioning:
     """The checked conditioning of one generate call over N samples: ``captions`` (N strings, or N sequences of K strings
     with ``prompt_weights``), ``edit_motion`` (N, T_max, dim_pose) with ``edit_mask`` broadcast to it, ``prompt_weights``
     broadcast to (N, K, T_w, dim_pose) (T_w its frame dim, 1 when it has none; ``weights``), ``control_joints``
     (N, T_max, J, 3) with ``control_weights`` broadcast to them and ``mean`` / ``std`` as float32 (dim_pose,) (``control``,
-    None without).  What does not depend on a batch is checked here, once; ``kwargs`` hands out a batch's rows and frames
+    None without).  ``edit_joints`` in place of ``edit_motion``: N joint clips (n_i, J, 3), turned into feature rows once
+    (``edit_rows_from_joints``) and zero-padded to the mask's frames.
+    What does not depend on a batch is checked here, once; ``kwargs`` hands out a batch's rows and frames
     (views of these tensors) and checks that they cover its T."""
 
     def __init__(self, captions, dim_pose, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
-                 control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None):
+                 control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,
+                 device=None, to_motion=None):
         self.captions, self.dim_pose = captions, dim_pose
         self.weights = None if prompt_weights is None else self._compose(captions, prompt_weights, dim_pose)
         self.edit = None
+        rows = None
+        if edit_joints is not None:
+            if edit_motion is not None:
+                raise ValueError("edit_joints and edit_motion are exclusive: the known motion is given as joints or as rows")
+            if edit_mask is None:
+                raise ValueError("edit_joints and edit_mask go together: give both or neither")
+            edit_motion, rows = edit_rows_from_joints(edit_joints, mean, std, dim_pose, device, to_motion)
+            edit_motion = pad_frames(edit_motion, joint_edit_mask_frames(edit_mask, edit_motion.shape[1]))
         if edit_motion is not None or edit_mask is not None:
             if edit_motion is None or edit_mask is None:
                 raise ValueError("edit_motion and edit_mask go together: give both or neither")
             k = torch.as_tensor(edit_motion)
             self.edit = (k, expand_to(edit_mask, None, k.shape, "edit_mask"))
+            if rows is not None:
+                check_joint_edit_mask(self.edit[1], rows)
         self.control = self._control(control_joints, control_weights, mean, std, dim_pose)
         self.control_scale, self.control_iters = control_scale, control_iters
 

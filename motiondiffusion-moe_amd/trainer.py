@@ -7,7 +7,9 @@ same ``generate(caption, m_lens, dim_pose, batch_size)`` -> list of (T, dim_pose
 run the reference's guided DDPM over every step.  ``edit_motion`` / ``edit_mask`` turn any of them into motion editing
 (prefix completion, in-betweening, body-part regeneration; masks from ``motion_edit``).  ``prompt_weights`` with K
 captions per sample composes them under per-prompt weight maps (time-varied and body-part control, negative prompts;
-weights from ``motion_compose``).  ``control_joints`` / ``control_weights`` (with ``mean`` / ``std``) steer joint positions:
+weights from ``motion_compose``).  ``edit_joints`` gives the known motion of an edit as joint positions, and
+``refeaturize`` makes all columns of generated rows describe the joints they show (``motion_features``).
+``control_joints`` / ``control_weights`` (with ``mean`` / ``std``) steer joint positions:
 trajectories, keyframes, end positions (targets from ``motion_control``).  ``generate_long`` samples motions longer than
 the model's window from scripts of ``(caption, length)`` segments, overlapping windows tied together on every step
 (``motion_long``).  Every generate method checks its conditioning once (``conditioning.Conditioning``) and
@@ -19,7 +21,7 @@ from __future__ import annotations
 import torch
 
 from . import motion_long as ML
-from .conditioning import Conditioning
+from .conditioning import Conditioning, check_joint_edit_mask, edit_rows_from_joints, expand_to, pad_frames
 from .diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType, SpacedDiffusion, get_named_beta_schedule,
                         space_timesteps)
 
@@ -92,16 +94,19 @@ class DDPMTrainer(object):
     def generate_batch(self, caption, m_lens, dim_pose, *, noise=None, step_noise=None, progress=True, seed=None,
                        sample_offset=0, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
                        prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
-                       control_iters=1, mean=None, std=None):
+                       control_iters=1, mean=None, std=None, edit_joints=None):
         """``edit_motion`` (B, T_max, dim_pose), normalised, and ``edit_mask`` broadcastable to it, values in [0, 1]: the
         batch's first T frames of both are kept where the mask is 1 (exactly, for a binary mask) and generated elsewhere.
         ``prompt_weights`` (B, K, ...) broadcastable to (B, K, T_max, dim_pose): ``caption[i]`` is then a sequence of K
         captions, composed on every step under these weights.
         ``control_joints`` (B, T_max, J, 3) target joint positions and ``control_weights`` (B, ...) broadcastable to them, with
         the dataset's ``mean`` / ``std`` (dim_pose,): every step's x0 is moved ``control_iters`` times down the gradient of
-        the weighted squared distance, scaled by ``control_scale`` (units in ``motion_control``)."""
+        the weighted squared distance, scaled by ``control_scale`` (units in ``motion_control``).
+        ``edit_joints``: B joint clips (n_i, J, 3) in place of ``edit_motion`` (needs ``mean`` / ``std``), turned into
+        feature rows once per call (``motion_features.joints_to_motion``); a clip of n frames gives n - 1
+        rows, so the mask may keep frames up to n - 2."""
         cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
-                            control_scale, control_iters, mean, std)
+                            control_scale, control_iters, mean, std, edit_joints, self.device)
         m_lens = torch.as_tensor(m_lens)
         T = min(int(m_lens.max()), self._model().num_frames)
         return self._sample_rows(cond, slice(0, len(caption)), m_lens, T, sampler, sample_steps, eta, progress=progress,
@@ -110,7 +115,7 @@ class DDPMTrainer(object):
     @torch.no_grad()
     def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None, sampler="ddpm",
                  sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
-                 control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None):
+                 control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None):
         """``seed``: sample i's noise is then a function of (seed, i) only (counter-based device generator), so the result
         does not depend on ``batch_size``; without it the torch generator is used, as in the reference.
         ``noises``: optional list with one ``(x_T, [step noise, ...])`` pair per batch, replacing the draws (parity tests).
@@ -119,11 +124,11 @@ class DDPMTrainer(object):
         each batch takes its samples' rows.  ``prompt_weights`` (N, K, ...): composed prompts, see ``generate_batch``; each
         batch takes its samples' rows.  ``control_joints`` (N, T_max, J, 3), ``control_weights``, ``control_scale``,
         ``control_iters``, ``mean``, ``std``: joint-position control, see ``generate_batch``; each batch takes its samples'
-        rows."""
+        rows.  ``edit_joints``: N joint clips in place of ``edit_motion``, see ``generate_batch``."""
         N = len(caption)
         self.eval_mode()
         cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
-                            control_scale, control_iters, mean, std)
+                            control_scale, control_iters, mean, std, edit_joints, self.device)
         all_output = []
         for cur in range(0, N, batch_size):
             end = min(cur + batch_size, N)
@@ -139,19 +144,20 @@ class DDPMTrainer(object):
     def generate_bucketed(self, caption, m_lens, dim_pose, batch_size=32, *, unit_length=4, seed=None, group=None,
                           progress=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
                           prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
-                          control_iters=1, mean=None, std=None):
+                          control_iters=1, mean=None, std=None, edit_joints=None):
         """Evaluation-scale variant of ``generate``: same inputs and the same kind of result (a
         list of per-sample ``(T_batch, dim_pose)`` tensors in the caller's order, valid up to each sample's length),
         but batches hold samples of similar length (less padded work) and, under ``torch.distributed``, are dealt over
         the ranks with one all_gather at the end.  With ``seed`` every sample's noise is a function of (seed, its index in
         ``caption``) only -- the same as ``generate(..., seed=)`` -- so on each sample's valid frames the two give identical
         results whatever the bucketing (tests/test_sampler_gpu.py).  ``edit_motion`` / ``edit_mask``: as in ``generate``;
-        each bucket takes its samples' rows and its first T frames; so do ``prompt_weights`` and the ``control_*`` tensors."""
+        each bucket takes its samples' rows and its first T frames; so do ``prompt_weights`` and the ``control_*`` tensors.
+        ``edit_joints``: joint clips in place of ``edit_motion``, as in ``generate``."""
         from . import dist as D
         m = self._model()
         self.eval_mode()
         cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
-                            control_scale, control_iters, mean, std)
+                            control_scale, control_iters, mean, std, edit_joints, self.device)
         lens = torch.as_tensor(m_lens).flatten().long().cpu()
         plan = D.plan_buckets(lens, batch_size, m.num_frames, unit_length)
 
@@ -164,14 +170,17 @@ class DDPMTrainer(object):
     @torch.no_grad()
     def generate_for_evaluation(self, caption, m_lens, dim_pose, *, mm_num_samples=0, mm_num_repeats=1, unit_length=4,
                                 max_motion_length=196, dataset_name="t2m", seed=None, batch_size=32, sampler="ddpm",
-                                sample_steps=None, eta=0.0, group=None):
+                                sample_steps=None, eta=0.0, group=None, consistent_features=False, mean=None, std=None):
         """The generation half of the reference's ``EvaluationDataset`` (datasets1/evaluator.py:16-121) on
         ``generate_bucketed``: lengths snapped to ``max(m // unit * unit, min_mov_length * unit)`` (min_mov_length 10 for
         t2m, 6 for KIT) and capped at ``max_motion_length``; ``mm_num_samples`` captions, drawn with
         ``RandomState(seed).choice(N, mm_num_samples, replace=False)`` and sorted, are generated ``mm_num_repeats`` times.
         Frames at or past each length are zero, as the reference's dataset pads them.  Returns a dict:
           motions (N, max_motion_length, dim_pose) and m_lens (N,): the first generation of every caption
-          mm_idxs (P,), mm_motions (P, mm_num_repeats, max_motion_length, dim_pose), mm_lens (P, mm_num_repeats)."""
+          mm_idxs (P,), mm_motions (P, mm_num_repeats, max_motion_length, dim_pose), mm_lens (P, mm_num_repeats).
+        ``consistent_features`` (with ``mean`` / ``std``): every generated motion goes through ``refeaturize`` before it is
+        padded, so all its columns describe the joints its root and position columns show; a motion of n frames then has
+        n - 1 rows, and ``m_lens`` / ``mm_lens`` count those.  Off by default: the result is then unchanged."""
         import numpy as np
         N = len(caption)
         if mm_num_samples and not mm_num_samples < N:
@@ -190,6 +199,12 @@ class DDPMTrainer(object):
                 all_len.append(int(lens[i]))
         gen = self.generate_bucketed(all_cap, torch.tensor(all_len), dim_pose, batch_size, unit_length=unit_length, seed=seed,
                                      group=group, sampler=sampler, sample_steps=sample_steps, eta=eta)
+        if consistent_features:
+            if mean is None or std is None:
+                raise ValueError("consistent_features needs the dataset's mean and std")
+            all_len = [min(n, mo.shape[0]) for mo, n in zip(gen, all_len)]
+            gen = self.refeaturize(gen, all_len, mean, std)
+            all_len, lens = [n - 1 for n in all_len], lens - 1
         allm = torch.zeros((len(all_cap), max_motion_length, dim_pose), dtype=torch.float32, device=gen[0].device)
         for k, (mo, n) in enumerate(zip(gen, all_len)):
             n = min(n, mo.shape[0])
@@ -204,6 +219,21 @@ class DDPMTrainer(object):
         return out
 
     @torch.no_grad()
+    def refeaturize(self, motions, m_lens, mean, std):
+        """``motion_features.refeaturize`` over the first ``m_lens[i]`` frames of every motion (normalised rows, as the
+        generate methods return them): a list of ``(m_len - 1, dim_pose)`` rows that show the same joints under
+        ``recover_from_ric`` and whose rot6d, velocity and foot-contact columns describe those joints.  One launch of each
+        kernel for all."""
+        from .motion_features import refeaturize
+        lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
+        dim_pose = motions[0].shape[-1]
+        x = torch.zeros((len(motions), max(lens), dim_pose), device=motions[0].device)
+        for i, (mo, n) in enumerate(zip(motions, lens)):
+            x[i, :n] = mo[:n]
+        rows = refeaturize(x, mean, std, torch.tensor(lens), skeleton={263: "t2m", 251: "kit"}[dim_pose])
+        return [rows[i, :n - 1] for i, n in enumerate(lens)]
+
+    @torch.no_grad()
     def generate_joints(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, joints_num=22, sigma=1.0,
                         bucketed=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
                         prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
@@ -212,7 +242,9 @@ class DDPMTrainer(object):
         list of ``(m_len, joints_num, 3)`` joint positions, temporally smoothed with a gaussian of width ``sigma``.
         ``edit_motion`` / ``edit_mask``: motion editing in normalised feature space, as in ``generate``;
         ``prompt_weights``: composed prompts, as in ``generate``; ``control_joints`` / ``control_weights`` /
-        ``control_scale`` / ``control_iters``: joint-position control under this call's ``mean`` / ``std``."""
+        ``control_scale`` / ``control_iters``: joint-position control under this call's ``mean`` / ``std``;
+        ``edit_joints`` (through ``**kw``): joint clips in place of ``edit_motion``, converted under the same ``mean`` /
+        ``std``."""
         gen = self.generate_bucketed if bucketed else self.generate  # mean / std go along: unused without control
         motions = gen(caption, m_lens, dim_pose, batch_size, sampler=sampler, sample_steps=sample_steps, eta=eta,
                       edit_motion=edit_motion, edit_mask=edit_mask, prompt_weights=prompt_weights,
@@ -233,7 +265,8 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
-                      sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, noise=None, progress=False):
+                      sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, noise=None, progress=False,
+                      edit_joints=None, mean=None, std=None):
         """Long motions: ``scripts`` is a list of long motions, each a list of ``(caption, length)``
         segments of at most ``num_frames`` frames; neighbouring segments share ``overlap`` canvas frames, whose eps is
         blended on every step (``blend`` "linear" crossfade or "uniform") while x_T and the step noise come from the left
@@ -242,11 +275,26 @@ class DDPMTrainer(object):
         the windows of all motions in order) is global sample k of the counter-based generator, so the result does not
         depend on ``batch_size``.  ``edit_motion`` / ``edit_mask``: one (canvas_len, dim_pose) known motion per motion and
         a mask broadcastable to it (or None entries), kept where the mask is 1, e.g. a prefix to continue.  ``noise``: one
-        (canvas_len, dim_pose) x_T per motion.  ``sampler`` / ``sample_steps`` / ``eta`` as in ``generate``."""
+        (canvas_len, dim_pose) x_T per motion.  ``sampler`` / ``sample_steps`` / ``eta`` as in ``generate``.
+        ``edit_joints`` (with ``mean`` / ``std``): one joint clip (n_i, J, 3) per motion in place of ``edit_motion``, e.g. the
+        joints ``generate_long_joints`` returned, to be continued: its n_i - 1 rows start the canvas, and every motion
+        needs its mask."""
         m = self._model()
         self.eval_mode()
         plans = ML.script_plans(scripts, overlap, m.num_frames)
         N = len(plans)
+        if edit_joints is not None:
+            if edit_motion is not None:
+                raise ValueError("edit_joints and edit_motion are exclusive: the known motion is given as joints or as rows")
+            if edit_mask is None or len(edit_joints) != N or len(edit_mask) != N or any(mk is None for mk in edit_mask):
+                raise ValueError(f"edit_joints needs one clip and one edit_mask per motion ({N})")
+            rows, nrows = edit_rows_from_joints(edit_joints, mean, std, dim_pose, self.device)
+            edit_motion = []
+            for i, n in enumerate(nrows):
+                if n > plans[i][3]:
+                    raise ValueError(f"motion {i}: a clip of {n} rows does not fit its canvas of {plans[i][3]} frames")
+                edit_motion.append(pad_frames(rows[i:i + 1, :n], plans[i][3])[0])
+                check_joint_edit_mask(expand_to(edit_mask[i], None, edit_motion[i].shape, "edit_mask")[None], [n])
         per = {}
         for name, v in (("edit_motion", edit_motion), ("edit_mask", edit_mask), ("noise", noise)):
             if v is not None and len(v) != N:
@@ -290,11 +338,14 @@ class DDPMTrainer(object):
     def generate_long_joints(self, scripts, dim_pose, mean, std, *, joints_num=22, sigma=1.0, **kw):
         """``generate_long`` followed by ``postprocess.motion_to_joints`` over each whole canvas (one continuous root
         path): a list of ``(canvas_len, joints_num, 3)`` joint positions.  The post-processing kernel holds a canvas in
-        LDS: at most MAX_JOINTS_FRAMES frames."""
+        LDS: at most MAX_JOINTS_FRAMES frames.  ``edit_joints`` / ``edit_mask`` (through ``**kw``): continue joint clips, as
+        in ``generate_long``, under this call's ``mean`` / ``std``."""
         plans = ML.script_plans(scripts, kw.get("overlap", 20), self._model().num_frames)
         longest = max(p[3] for p in plans)
         if longest > MAX_JOINTS_FRAMES:
             raise ValueError(f"a canvas of {longest} frames: joint recovery takes at most {MAX_JOINTS_FRAMES} frames")
+        if kw.get("edit_joints") is not None:  # joints in, joints out: the clips are converted under the same mean / std
+            kw = dict(kw, mean=mean, std=std)
         motions = self.generate_long(scripts, dim_pose, **kw)
         return self._to_joints(motions, [mo.shape[0] for mo in motions], dim_pose, mean, std, joints_num, sigma)
 
