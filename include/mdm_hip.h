@@ -48,7 +48,9 @@ enum { MDM_H16_BF16 = 1, MDM_H16_F16 = 2 };
  *      MFMA-bound GEMMs only (expert MLPs, the 4x FFN of the text cross-attention block)
  *   5  as 2, with the expert GEMMs on fp8 (e4m3) operands: activations quantised per row by the router kernel, weights per
  *      output channel at pack time, block-scaled MFMA with unit block scales (csrc/gemm8.hip); BASELINE configs[4]
- * The packed weights must be in the matching format (packing.py: weight_format). */
+ * The packed weights must be in the matching format (packing.py: weight_format).
+ * Widths: 2 and 4 need D and F in multiples of 64 (the k-tile of the 16-bit kernels), 5 in multiples of 128; a model-level entry
+ * point called with another shape returns MDM_ERR_UNSUPPORTED before any launch and writes nothing.  1 runs on fp32 rows there. */
 enum { MDM_PREC_BF16 = 1, MDM_PREC_F16 = 2, MDM_PREC_X3 = 3, MDM_PREC_MIXED = 4, MDM_PREC_FP8 = 5 };
 
 /* One GEMM operand: a [rows x K] matrix seen through a loader kind (see csrc/gemm.h). */
