@@ -33,6 +33,8 @@ int ln_chain(const float* x, int64_t M, int D, const float* w1, const float* b1,
 int style_in(const float* x, int64_t M, int D, int S, const float* pw, const float* pb, const float* sw,
              const float* sb, const float* sc, const int* pos4, int x_bf, void* out, int out_bf, hipStream_t s);
 int to_bf16(const float* src, int64_t n, uint16_t* dst, int h16, hipStream_t s);  // h16: MDM_H16_BF16 / MDM_H16_F16
+// an fp16 plane (n elements) as bf16 hi | lo planes of the same values: what a GEMM on fp32 rows reads of a weight packed in fp16
+int f16_to_bf16x2(const uint16_t* src, int64_t n, uint16_t* hi, uint16_t* lo, hipStream_t s);
 int moe_route(const float* x, int64_t M, int D, int E, const MoeGateParams& p, int* goff, int* cursor, int* perm,
               float* rowscale, int* pos4, hipStream_t s);
 int head_norm(float* qkv, int64_t M, int H, int dh, const float* w, const float* b, hipStream_t s);

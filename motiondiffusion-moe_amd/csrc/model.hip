@@ -348,10 +348,26 @@ int performer(const Ctx& c, const MdmPerformer& p, const float* x, Act xn, const
       // shared LN over head_dim, L2 normalise q,k                     (:44-55)
       MDM_TRY(head_norm(w.qkv, c.M, H, dh, p.hn_w, p.hn_b, c.s));
       // feature maps 0.1*exp(clamp(z P)), keys masked past length     (:58-74): rows = (token, slot<2H)
+      // a model packed for the fp16 modes holds P as ONE fp16 plane, which only the 16-bit-activation kernels read: the chain
+      // works on fp32 rows, so it re-splits that plane into bf16 hi | lo (exact; kvt is free until the KV GEMM) and runs its
+      // GEMMs as bf16x3 -- a single bf16 pass on these rows would be coarser than the fp16 mode it serves
+      const bool f16p = c.bf && c.h16 == MDM_H16_F16 && !p.feat.lo;
+      Operand P = packed(p.feat);
+      if (f16p) {
+        const int64_t pn = (int64_t)mf * p.feat.ld;
+        // cannot bind for a model the packer makes: an fp16 P exists at head_dim 128 / 256 only, where ld = dh (a multiple of 32)
+        // and mf = dh, so pn = dh * dh <= B * H * dh * dh
+        if (pn > (int64_t)c.B * H * dh * dh) return MDM_ERR_UNSUPPORTED;
+        uint16_t* const ph = (uint16_t*)w.kvt;
+        MDM_TRY(f16_to_bf16x2(p.feat.hi, pn, ph, ph + pn, c.s));
+        P = op_bf16(ph, ph + pn, p.feat.ld);
+      }
+      const int cprec = f16p ? 3 : c.prec;
       GemmArgs g = gd(c);
+      g.precision = cprec;
       g.A = op_f32(w.qkv, dh);
       g.A.rpg = 2 * H, g.A.gstride = 3 * D;
-      g.W = packed(p.feat);
+      g.W = P;
       g.M = (int)(c.M * 2 * H), g.N = mf, g.K = dh;
       g.C = w.phi, g.ldc = mf;
       g.act = ACT_FEAT;
@@ -361,12 +377,12 @@ int performer(const Ctx& c, const MdmPerformer& p, const float* x, Act xn, const
       GemmArgs kv = per_head(c, heads(op_f32_kstride(w.qkv + 2 * D, 3 * D), (int64_t)c.S * 3 * D, dh),
                              heads(op_f32_kstride(w.phi + H * mf, 2 * H * mf), (int64_t)c.S * 2 * H * mf, mf), dh, mf, c.S, mf,
                              (int64_t)H * dh * mf, (int64_t)dh * mf);
-      kv.C = w.kvt, kv.out_scale = 0.1f;
+      kv.C = w.kvt, kv.out_scale = 0.1f, kv.precision = cprec;
       MDM_TRY(gemm(kv, c.s));
       // num = 0.1 * qphi KV                                            (:78) -> t2 (M, D) merged heads
       GemmArgs num = per_head(c, heads(op_f32(w.phi, 2 * H * mf), (int64_t)c.S * 2 * H * mf, mf),
                               heads(op_f32(w.kvt, mf), (int64_t)H * dh * mf, (int64_t)dh * mf), c.S, dh, mf, D, (int64_t)c.S * D, dh);
-      num.C = w.t2, num.out_scale = 0.1f;
+      num.C = w.t2, num.out_scale = 0.1f, num.precision = cprec;
       MDM_TRY(gemm(num, c.s));
       // same-t denominator, divide, LN over head_dim                   (:81-90) -> t4
       MDM_TRY(den_ln(w.t2, w.phi, c.M, H, dh, p.hn_w, p.hn_b, w.t4, fmt16(c), c.s));

@@ -783,6 +783,16 @@ __global__ void to_bf16_kernel(const float* __restrict__ src, int64_t n4, uint16
   }
 }
 
+// exact: the 11 significand bits of an fp16 value fit bf16 hi (8) + lo = rn(x - hi)
+__global__ void f16_to_bf16x2_kernel(const uint32_t* __restrict__ src, int64_t n2, uint32_t* __restrict__ hi, uint32_t* __restrict__ lo) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t u = src[i];
+    uint32_t h, l;
+    split_bf16(f16_lo_f32(u), f16_hi_f32(u), h, l);
+    hi[i] = h, lo[i] = l;
+  }
+}
+
 __global__ void fill_i64_kernel(int64_t* dst, int64_t n, const int* src) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < n) dst[i] = (int64_t)*src;
@@ -1030,6 +1040,16 @@ int to_bf16(const float* src, int64_t n, uint16_t* dst, int h16, hipStream_t s) 
   if (n & 3) return MDM_ERR_ARG;
   int64_t blocks = (n / 4 + 255) / 256;
   hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, src, n / 4, dst, h16);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int f16_to_bf16x2(const uint16_t* src, int64_t n, uint16_t* hi, uint16_t* lo, hipStream_t s) {
+  if (n <= 0) return MDM_OK;
+  if ((n & 1) || ((((uintptr_t)src) | ((uintptr_t)hi) | ((uintptr_t)lo)) & 3)) return MDM_ERR_ARG;
+  int64_t blocks = (n / 2 + 255) / 256;
+  hipLaunchKernelGGL(f16_to_bf16x2_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, (const uint32_t*)src, n / 2,
+                     (uint32_t*)hi, (uint32_t*)lo);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 TOL = {3: 1e-3, 1: 3e-2, 2: 6e-3, 4: 1e-3}
 
 
-def _setup(B, S, N, precision):
+def _setup(B, S, N, precision, lengths=None):
     g, meta = load_golden("fwd_small_dims")
     m, (sd, eph, proj, mcfg) = build_module(meta, precision=precision)
     synth = pkg("synth")
@@ -25,7 +25,7 @@ def _setup(B, S, N, precision):
     h = synth.uniform_pm1((B, S, D), "blk.h", S) * 1.5
     emb = synth.uniform_pm1((B, D), "blk.emb", S)
     xf = synth.uniform_pm1((B, N, Dt), "blk.xf", N) * 1.7
-    length = torch.tensor([S, max(1, S - 13)][:B] + [S] * max(0, B - 2))
+    length = torch.tensor([S, max(1, S - 13)][:B] + [S] * max(0, B - 2)) if lengths is None else torch.tensor(list(lengths))
     pre = "decoder_blocks_low.0.module"
     sc = []
     for slot, sp in (("local_style", pre + ".dual_self_attn.local_attn.style_block"),
@@ -56,10 +56,15 @@ def _run_block(m, block, h, sc, length, xf, forced=None, ntok=None):
 
 
 @pytest.mark.parametrize("precision", [3, 1, 2, 4])
-@pytest.mark.parametrize("S,N", [(40, 6), (98, 28), (196, 85)])
-def test_blocks_match_oracle(S, N, precision):
+@pytest.mark.parametrize("S,N,lengths", [(40, 6, None), (98, 28, None), (196, 85, None), (98, 28, (98, 24)), (37, 6, (17, 5))],
+                         ids=["40-6", "98-28", "196-85", "98-28-lengths98.24", "37-6-lengths17.5"])
+def test_blocks_match_oracle(S, N, lengths, precision):
+    """lengths None: [S, S - 13].  On the short-length cases a core that ignores the key mask moves the dual block by 6.5e-3 and
+    1.0e-2 (tests/test_attention_probe_host.py::test_short_lengths_on_legacy_inputs): outside the fp32-grade and fp16 tolerances,
+    still inside the bf16 one -- the probe fixtures of tests/test_attention_selective_gpu.py see that mutant, and the finer
+    ones, in every mode."""
     B = 2
-    m, sd, eph, proj, h, emb, xf, length, sc, pre, (D, H, E) = _setup(B, S, N, precision)
+    m, sd, eph, proj, h, emb, xf, length, sc, pre, (D, H, E) = _setup(B, S, N, precision, lengths)
     L = pkg("_lib")
     mask = R.src_mask(S, length)
     with torch.no_grad():
