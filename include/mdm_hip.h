@@ -460,6 +460,26 @@ int mdm_motion_features(const float* joints, const int32_t* length, const float*
                         int32_t canonicalize, int32_t radius, const double* weights, float* positions_out,
                         float* features_out, void* stream);
 
+/* Joints from rotations (csrc/motion_fk.hip): recover_from_rot of utils/motion_process.py:384-398 on normalised
+ * rows.  motion (B, T, F) fp32 with F = 12 joints - 1 (263 t2m, 251 KIT), length (B) int32 or NULL (= T), mean / std (F):
+ * de-normalise, recover the root heading and XZ path exactly as mdm_motion_postprocess, turn the root quaternion and the rot6d
+ * columns 4 + 3 (J - 1) .. of joints 1 .. J - 1 into matrices (cont6d_to_matrix, no clamp and no epsilon: a zero-norm or
+ * parallel pair gives non-finite joints down that frame's chain) and accumulate them down the skeleton's chains, every chain
+ * from the ROOT matrix: R <- R M[c], joint[c] = R offset[c] + joint[previous].  offsets: (J, 3) shared by the batch
+ * (offsets_per_sample == 0), (B, J, 3) (!= 0), or NULL: each sample's own, bone length = mean over its valid frames of the
+ * bone's length on the recover_from_ric joints (summed in double in frame order) times the skeleton's raw_offsets axis.  The
+ * offsets used go to offsets_out (B, J, 3) when non-NULL.  joints_out (B, T, J, 3); rotations_out (B, T, J, 3, 3) or NULL:
+ * the accumulated global matrices, row-major, the root's at joint 0.  weights[0..radius]: temporal gaussian filter of the
+ * joints (never of the rotations) as for mdm_motion_postprocess.  Frames at or past length[b] are zero in every output and
+ * are never read.  scratch (B, T, J, 3) is needed when radius > 0 or offsets is NULL.  Of the skeleton, the chains and
+ * raw_offsets are used.  MDM_ERR_ARG: a null pointer, T < 1, F != 12 joints - 1, a malformed skeleton (the check of
+ * mdm_motion_features); MDM_ERR_UNSUPPORTED: T > mdm_motion_fk_max_frames() (20 bytes of LDS per frame). */
+int mdm_motion_fk_max_frames(void);
+int mdm_motion_fk(const float* motion, const int32_t* length, const float* mean, const float* std,
+                  const MdmSkeleton* skeleton, const float* offsets, int32_t offsets_per_sample, int32_t B, int32_t T,
+                  int32_t F, int32_t radius, const double* weights, float* scratch, float* joints_out,
+                  float* rotations_out, float* offsets_out, void* stream);
+
 /* Joint-position control (csrc/motion_control.hip).  For sample b, with J = (F + 1) / 12 joints (F must be
  * 12 J - 1: 263 -> 22, 251 -> 21), targets G and weights W dense fp32 (B, T, J, 3), W >= 0 and finite, mean / std fp32
  * (B, F) (one row per sample), and P = recover_from_ric(x0 * std + mean) without temporal filter (as mdm_motion_postprocess

@@ -99,6 +99,9 @@ int text_assemble(const float* pp, const float* ph, int B, int N0, int P, int Dt
 // motion_post.hip: 263-d HumanML3D rows -> (T, J, 3) joints, optional temporal gaussian filter (wts[0..radius])
 int motion_post(const float* x, const int* len, const float* mean, const float* sd, int B, int T, int feats, int J,
                 int radius, const double* wts, float* raw, float* out, hipStream_t s);
+// motion_features.hip: parent-ordered chains over J joints: every joint but the root is the child of exactly one link, a chain
+// starts at the root or at a joint an earlier link reached; parent[] (MDM_SKEL_MAX_JOINTS) filled.  Host side
+bool skeleton_ok(const MdmSkeleton& s, int* parent);
 // noise.hip: Philox4x32-10 + Box-Muller, keyed on (seed, global sample, stream, element)
 int philox_normal(float* out, int64_t per_sample, int nsamples, int64_t sample0, const int64_t* sample_ids, uint64_t seed,
                   const int* stream_dev, int stream_imm, hipStream_t s);

@@ -257,6 +257,8 @@ __global__ __launch_bounds__(MF_THREADS) void motion_features_kernel(
   for (int i = rows * F + tid; i < (T - 1) * F; i += MF_THREADS) ob[i] = 0.f;
 }
 
+}  // namespace
+
 // parent-ordered chains over J joints: every joint but the root is the child of exactly one link, a chain starts at the
 // root or at a joint an earlier link reached; parent[] filled
 bool skeleton_ok(const MdmSkeleton& s, int* parent) {
@@ -288,7 +290,6 @@ bool skeleton_ok(const MdmSkeleton& s, int* parent) {
   return true;
 }
 
-}  // namespace
 }  // namespace mdm
 
 extern "C" {

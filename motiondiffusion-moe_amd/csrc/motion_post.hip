@@ -11,22 +11,10 @@
 // contraction disabled, and the filter accumulates symmetric pairs in double like scipy's correlate1d: results agree with
 // the reference to the last bits of the libm sin/cos.  HBM-bound and tiny (B x T x 263 floats in, B x T x 66 out).
 #include "kernels.h"
+#include "motion_root.h"
 
 namespace mdm {
 namespace {
-
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
-
-// v rotated by the quaternion (w, 0, qy, 0): qrot with cross products written out (utils/quaternion.py:70-73)
-__device__ __forceinline__ void rot_y(float w, float qy, float vx, float vy, float vz, float& ox, float& oy, float& oz) {
-  const float uvx = mul(qy, vz), uvz = -mul(qy, vx);        // uv = cross(qvec, v), qvec = (0, qy, 0)
-  const float uuvx = mul(qy, uvz), uuvz = -mul(qy, uvx);    // uuv = cross(qvec, uv)
-  ox = add(vx, mul(2.f, add(mul(w, uvx), uuvx)));
-  oy = vy;                                                  // + 2 * (w * 0 + 0)
-  oz = add(vz, mul(2.f, add(mul(w, uvz), uuvz)));
-}
 
 __global__ __launch_bounds__(256) void motion_post_kernel(const float* __restrict__ x, const int* __restrict__ len,
                                                           const float* __restrict__ mean, const float* __restrict__ sd,
