@@ -480,6 +480,35 @@ int mdm_motion_fk(const float* motion, const int32_t* length, const float* mean,
                   int32_t F, int32_t radius, const double* weights, float* scratch, float* joints_out,
                   float* rotations_out, float* offsets_out, void* stream);
 
+/* Foot-skate clean-up (csrc/foot_skate.hip): pin planted feet with two-bone leg IK.  joints (B, T, J, 3) fp32,
+ * length (B) int32 or NULL (= T).  Four contact labels per frame, in the order of skeleton->feet (ankle, toe, ankle, toe):
+ * contact != NULL: label f of frame t of sample b is on iff contact[(b T + t) contact_stride + f] > contact_thre[f] (a host
+ * array of 4; a (B, T, 4) tensor has stride 4, the contact columns of normalised rows (B, T, F) are read in place with
+ * stride F from column F - 4 and thresholds (0.5 - mean) / std); contact == NULL: detected as mdm_motion_features has them,
+ * frame t < n - 1 on iff the fp32 squared displacement of the joint to frame t + 1 is < feet_thre, frame n - 1 repeating
+ * frame n - 2, none at n = 1.  A leg is hip, knee, ankle, toe: the last four entries of the chain that ends in feet[1] /
+ * feet[3], whose entry before is feet[0] / feet[2].  Per foot joint and maximal run of frames with the label on, the anchor
+ * is the joint's mean (X, Z) over the run (double, frame order, rounded once) and delta = anchor - p_xz inside the run; up
+ * to `blend` frames outside, delta = (wL dL + wR dR) / max(1, wL + wR) of the nearest contact frame within `blend` on
+ * either side, w = 1 - smoothstep(k / (blend + 1)).  The ankle goes to its target by two-bone IK with the hip fixed (reach
+ * clamped to [|l1 - l2| (1 + 1e-4) + 1e-6, (l1 + l2) (1 - 1e-4)], the knee kept in its bend plane), the toe is aimed from
+ * the new ankle at its own target on its own bone length.  Heights of the targets never change.  A (frame, leg) neither of
+ * whose two labels is on or within `blend` of a run, and every other joint, is copied bit for bit.  rotations_in
+ * (B, T, J, 3, 3), the layout of mdm_motion_fk's rotations_out, or NULL: rotations_out = Q R for knee, ankle and toe, Q the
+ * shortest arc from the old bone to the new one (R copied where the bone keeps every bit); all others copied.  slide_out
+ * (B, 2, 4) or NULL: per foot joint the mean |step in XZ| over the pairs of neighbouring frames that are both in contact,
+ * before [0] and after [1] (double, frame order; 0 without a pair); pairs_out (B, 4) int32 or NULL: the pair counts.
+ * scratch: (B, T, 4, 2) fp32.  Frames at or past length[b] are zero in every output and are never read.  Nothing is
+ * updated in place: joints_out != joints, rotations_out != rotations_in.
+ * MDM_ERR_ARG: a null required pointer (joints, skeleton, joints_out, scratch; contact_thre with contact), T < 1, blend < 0,
+ * contact_stride < 4, feet_thre not >= 0 when detecting, a malformed skeleton or leg, rotations_in without rotations_out or
+ * the reverse, an output that is its input; MDM_ERR_UNSUPPORTED: T > mdm_foot_skate_max_frames() (5 bytes of LDS per frame). */
+int mdm_foot_skate_max_frames(void);
+int mdm_foot_skate(const float* joints, const int32_t* length, const MdmSkeleton* skeleton, const float* contact,
+                   int64_t contact_stride, const float* contact_thre, double feet_thre, int32_t blend, int32_t B, int32_t T,
+                   const float* rotations_in, float* joints_out, float* rotations_out, float* slide_out, int32_t* pairs_out,
+                   float* scratch, void* stream);
+
 /* Joint-position control (csrc/motion_control.hip).  For sample b, with J = (F + 1) / 12 joints (F must be
  * 12 J - 1: 263 -> 22, 251 -> 21), targets G and weights W dense fp32 (B, T, J, 3), W >= 0 and finite, mean / std fp32
  * (B, F) (one row per sample), and P = recover_from_ric(x0 * std + mean) without temporal filter (as mdm_motion_postprocess

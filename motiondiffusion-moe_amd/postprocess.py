@@ -6,7 +6,10 @@ Host mirror of what the reference does on the CPU after sampling (tools/visualiz
 
 ``motion_to_joints_fk`` is the other way to joints: forward kinematics of the rows' rot6d columns on fixed
 bone offsets (``recover_from_rot``, utils/motion_process.py:384-398), in ``mdm_motion_fk`` (csrc/motion_fk.hip).  Bones are
-rigid by construction, and the per-joint global rotations come with it."""
+rigid by construction, and the per-joint global rotations come with it.
+
+``remove_foot_skate`` is the last stage: where a foot-contact label is on, the ankle is pinned to its mean
+position over the run by two-bone leg IK and the toe is aimed at its own, in ``mdm_foot_skate`` (csrc/foot_skate.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -161,3 +164,137 @@ def recover_from_rot(data: torch.Tensor, joints_num: int, offsets, *, skeleton=N
     Fe = x.shape[-1]
     j = motion_to_joints_fk(x, np.zeros(Fe, np.float32), np.ones(Fe, np.float32), None, offsets, skeleton=skeleton, sigma=0.0)
     return j.reshape(lead + tuple(j.shape[1:]))
+
+
+def foot_skate_max_frames() -> int:
+    """The longest motion ``mdm_foot_skate`` takes (5 bytes of LDS per frame); longer ones are MDM_ERR_UNSUPPORTED."""
+    return int(L.lib().mdm_foot_skate_max_frames())
+
+
+def leg_joints(sk):
+    """((hip, knee, ankle, toe), (hip, knee, ankle, toe)) of a skeleton: per pair of ``sk.feet`` (ankle, toe) the last four
+    entries of the chain that ends in the toe.  Raises ValueError where the skeleton has no such legs."""
+    legs = []
+    for ankle, toe in (sk.feet[0:2], sk.feet[2:4]):
+        found = [c for c in sk.chains if len(c) >= 4 and c[-1] == toe and c[-2] == ankle]
+        if not found:
+            raise ValueError(f"the skeleton has no chain of 4 or more joints that ends in ankle {ankle}, toe {toe}")
+        legs.append(tuple(int(j) for j in found[0][-4:]))
+    if any(a == b for a, b in zip(*legs)):
+        raise ValueError("the skeleton's two legs share a joint")
+    return tuple(legs)
+
+
+def check_foot_skate(joints, lengths, contacts, rotations, sk, blend=5, contact_thre=0.5, feet_thre=None):
+    """Argument checks of ``remove_foot_skate`` that need no device: -> (joints (B, T, J, 3), lengths (B,) int64 or None,
+    contact values ((B, T, 4), or the rows (B, T, F) whose last four columns they are) or None, their four thresholds as
+    float32 or None, feet_thre, rotations (B, T, J, 3, 3) or None).  Raises ValueError."""
+    J, F_ = sk.joints, sk.feats
+    leg_joints(sk)
+    x = torch.as_tensor(joints)
+    if x.dim() == 3:
+        x = x[None]
+    if x.dim() != 4 or tuple(x.shape[2:]) != (J, 3):
+        raise ValueError(f"joints of shape {tuple(x.shape)} must be (B, T, {J}, 3) for this skeleton")
+    B, T = x.shape[:2]
+    if T < 1:
+        raise ValueError("a motion needs at least 1 frame")
+    if int(blend) != blend or blend < 0:
+        raise ValueError("blend must be a whole number of frames >= 0")
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
+        if lengths.numel() != B:
+            raise ValueError(f"lengths must have {B} entries")
+        if B and (int(lengths.min()) < 1 or int(lengths.max()) > T):
+            raise ValueError(f"every length must lie in [1, {T}]")
+    feet_thre = sk.feet_thre if feet_thre is None else float(feet_thre)
+    if not feet_thre >= 0:
+        raise ValueError("feet_thre must be >= 0")
+    thre = None
+    if isinstance(contacts, (tuple, list)):
+        if len(contacts) != 3:
+            raise ValueError("contacts as a tuple is (motion, mean, std): the rows' own contact columns")
+        rows, mean, std = contacts
+        rows = torch.as_tensor(rows)
+        if rows.dim() == 2:
+            rows = rows[None]
+        if tuple(rows.shape) != (B, T, F_):
+            raise ValueError(f"contacts: motion of shape {tuple(rows.shape)} must be ({B}, {T}, {F_})")
+        mean, std = (torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v)).detach().to("cpu", torch.float64).flatten()
+                     for v in (mean, std))
+        if mean.numel() != F_ or std.numel() != F_:
+            raise ValueError(f"mean/std must have {F_} entries")
+        if not (bool(torch.isfinite(mean[-4:]).all()) and bool(torch.isfinite(std[-4:]).all()) and bool((std[-4:] > 0).all())):
+            raise ValueError("mean / std of the contact columns must be finite, std > 0")
+        thre = ((float(contact_thre) - mean[-4:]) / std[-4:]).to(torch.float32)  # fp64 on the host, rounded once
+        contacts = rows
+    elif contacts is not None:
+        contacts = torch.as_tensor(contacts)
+        if contacts.dim() == 2:
+            contacts = contacts[None]
+        if tuple(contacts.shape) != (B, T, 4):
+            raise ValueError(f"contacts of shape {tuple(contacts.shape)} must be ({B}, {T}, 4)")
+        thre = torch.full((4,), float(contact_thre), dtype=torch.float32)
+    if thre is not None and not bool(torch.isfinite(thre).all()):
+        raise ValueError("contact_thre must be finite")
+    if rotations is not None:
+        rotations = torch.as_tensor(rotations)
+        if rotations.dim() == 4:
+            rotations = rotations[None]
+        if tuple(rotations.shape) != (B, T, J, 3, 3):
+            raise ValueError(f"rotations of shape {tuple(rotations.shape)} must be ({B}, {T}, {J}, 3, 3)")
+    if T > foot_skate_max_frames():
+        raise ValueError(f"a motion of {T} frames: foot-skate clean-up takes at most {foot_skate_max_frames()} frames")
+    return x, lengths, contacts, thre, feet_thre, rotations
+
+
+@torch.no_grad()
+def remove_foot_skate(joints, lengths=None, contacts=None, *, skeleton="t2m", feet_thre=None, contact_thre=0.5, blend=5,
+                      rotations=None, return_slide=False):
+    """joints (B, T, J, 3) on a GPU -> joints whose planted feet stand still; frames >= lengths[b] are zero.
+    Where a foot joint's contact label is on, its ankle is moved in XZ to its mean position over that run of frames by
+    two-bone IK of the leg with the hip fixed, and the toe is aimed from the new ankle at its own pinned position (aimed, not
+    pinned: the toe keeps its bone length).  ``blend`` frames either side of a run the correction fades out.  Heights, the
+    hips and the rest of the body are untouched.  ``contacts``: None detects the labels from the joints (squared
+    displacement to the next frame under ``feet_thre``, default the skeleton's); a (B, T, 4) tensor of label values, on
+    where > ``contact_thre``; or ``(motion, mean, std)``: the last four columns of the normalised rows (B, T, F) that the
+    joints came from, read in place, on where the de-normalised value is > ``contact_thre``.  ``rotations`` (B, T, J, 3, 3)
+    global rotations (``motion_to_joints_fk(..., return_rotations=True)``) are turned with the bones and returned after the
+    joints.  ``return_slide``: also ``(slide (B, 2, 4), pairs (B, 4))``, per foot joint the mean XZ step between neighbouring
+    contact frames before [:, 0] and after [:, 1], and the number of such pairs.  A target out of the leg's reach is
+    approached as far as the leg goes."""
+    from .motion_features import _skeleton_struct, get_skeleton
+    sk = get_skeleton(skeleton)
+    x, lengths, cont, thre, feet_thre, rot = check_foot_skate(joints, lengths, contacts, rotations, sk, blend, contact_thre,
+                                                             feet_thre)
+    L.require_cuda(x, cont, rot)
+    dev = x.device
+    x = x.detach().to(torch.float32).contiguous()
+    B, T, J = x.shape[:3]
+    ln = None if lengths is None else lengths.to(dev, torch.int32).contiguous()
+    cptr, stride, thre_c = 0, 0, None
+    if cont is not None:
+        if cont.device != dev:
+            raise ValueError("contacts must be on the joints' device")
+        cont = cont.detach().to(torch.float32).contiguous()
+        stride = cont.shape[-1]
+        cptr = cont.data_ptr() + 4 * (stride - 4)  # a (B, T, 4) tensor, or the rows' last four columns in place
+        thre_c = (C.c_float * 4)(*[float(v) for v in thre])
+    if rot is not None:
+        if rot.device != dev:
+            raise ValueError("rotations must be on the joints' device")
+        rot = rot.detach().to(torch.float32).contiguous()
+    out = torch.empty_like(x)
+    rot_out = None if rot is None else torch.empty_like(rot)
+    scratch = torch.empty(B, T, 4, 2, device=dev)
+    slide = torch.empty(B, 2, 4, device=dev) if return_slide else None
+    pairs = torch.empty(B, 4, dtype=torch.int32, device=dev) if return_slide else None
+    s = _skeleton_struct(sk)
+    with torch.cuda.device(dev):
+        L.check(L.lib().mdm_foot_skate(
+            C.c_void_p(x.data_ptr()), C.c_void_p(L.ptr(ln)), C.byref(s), C.c_void_p(cptr), C.c_int64(stride), thre_c,
+            C.c_double(feet_thre), C.c_int32(int(blend)), C.c_int32(B), C.c_int32(T), C.c_void_p(L.ptr(rot)),
+            C.c_void_p(out.data_ptr()), C.c_void_p(L.ptr(rot_out)), C.c_void_p(L.ptr(slide)), C.c_void_p(L.ptr(pairs)),
+            C.c_void_p(scratch.data_ptr()), C.c_void_p(L.stream_ptr())), "mdm_foot_skate")
+    res = (out,) + ((rot_out,) if rot is not None else ()) + (((slide, pairs),) if return_slide else ())
+    return res if len(res) > 1 else out

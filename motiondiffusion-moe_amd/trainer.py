@@ -237,7 +237,7 @@ class DDPMTrainer(object):
     def generate_joints(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, joints_num=22, sigma=1.0,
                         bucketed=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
                         prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
-                        control_iters=1, from_rotations=False, offsets=None, **kw):
+                        control_iters=1, from_rotations=False, offsets=None, fix_feet=False, blend=5, **kw):
         """``generate`` followed by the reference's post-processing (tools/visualization.py:21-27,89) on the device:
         list of ``(m_len, joints_num, 3)`` joint positions, temporally smoothed with a gaussian of width ``sigma``.
         ``edit_motion`` / ``edit_mask``: motion editing in normalised feature space, as in ``generate``;
@@ -246,22 +246,29 @@ class DDPMTrainer(object):
         ``edit_joints`` (through ``**kw``): joint clips in place of ``edit_motion``, converted under the same ``mean`` /
         ``std``.  ``from_rotations``: joints by forward kinematics of the rot6d columns (``postprocess.motion_to_joints_fk``,
         DESIGN.md §17: rigid bones) on ``offsets`` (J, 3) or one (J, 3) per motion; None: every motion's own mean bone
-        lengths."""
+        lengths.  ``fix_feet``: foot-skate clean-up after the temporal filter (``postprocess.remove_foot_skate``, DESIGN.md
+        §18), the labels being the generated rows' own foot-contact columns; ``blend`` frames of fade either side of a contact."""
         gen = self.generate_bucketed if bucketed else self.generate  # mean / std go along: unused without control
         motions = gen(caption, m_lens, dim_pose, batch_size, sampler=sampler, sample_steps=sample_steps, eta=eta,
                       edit_motion=edit_motion, edit_mask=edit_mask, prompt_weights=prompt_weights,
                       control_joints=control_joints, control_weights=control_weights, control_scale=control_scale,
                       control_iters=control_iters, mean=mean, std=std, **kw)
         lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
-        return self._to_joints(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotations, offsets)
+        return self._to_joints(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotations, offsets,
+                               fix_feet=fix_feet, blend=blend)
 
     @staticmethod
     def _to_joints(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotations=False, offsets=None,
-                   return_rotations=False):
+                   return_rotations=False, fix_feet=False, blend=5):
         """``postprocess.motion_to_joints`` over the first ``lens[i]`` frames of every motion, or with ``from_rotations``
         ``postprocess.motion_to_joints_fk``: one launch for all.  ``return_rotations`` (forward kinematics only): a list of
-        (joints, rotations, offsets) per motion."""
-        from .postprocess import motion_to_joints, motion_to_joints_fk
+        (joints, rotations, offsets) per motion.  ``fix_feet``: ``postprocess.remove_foot_skate`` on the result, filtered
+        first (filtering afterwards would smear the pins), labels from the rows' contact columns read in place; rotations go
+        through it, so that joints and rotations still agree."""
+        from .postprocess import motion_to_joints, motion_to_joints_fk, remove_foot_skate
+        skel = {263: "t2m", 251: "kit"}.get(dim_pose)
+        if fix_feet and (skel is None or dim_pose != 12 * joints_num - 1):
+            raise ValueError(f"fix_feet needs dim_pose 263 (22 joints) or 251 (21), not {dim_pose} ({joints_num})")
         if (offsets is not None or return_rotations) and not from_rotations:
             raise ValueError("offsets and rotations belong to forward kinematics: pass from_rotations=True")
         x = torch.zeros((len(motions), max(mo.shape[0] for mo in motions), dim_pose), device=motions[0].device)
@@ -269,26 +276,33 @@ class DDPMTrainer(object):
             x[i, :mo.shape[0]] = mo
         if not from_rotations:
             j = motion_to_joints(x, mean, std, torch.tensor(lens), joints_num, sigma)
+            if fix_feet:
+                j = remove_foot_skate(j, torch.tensor(lens), (x, mean, std), skeleton=skel, blend=blend)
             return [j[i, :n] for i, n in enumerate(lens)]
         if dim_pose != 12 * joints_num - 1 or dim_pose not in (263, 251):
             raise ValueError(f"forward kinematics needs dim_pose 263 (22 joints) or 251 (21), not {dim_pose} ({joints_num})")
         if isinstance(offsets, (list, tuple)):
             offsets = torch.stack([torch.as_tensor(o).to("cpu", torch.float32) for o in offsets])
-        j, r, o = motion_to_joints_fk(x, mean, std, torch.tensor(lens), offsets, skeleton={263: "t2m", 251: "kit"}[dim_pose],
-                                      sigma=sigma, return_rotations=True, return_offsets=True)
+        j, r, o = motion_to_joints_fk(x, mean, std, torch.tensor(lens), offsets, skeleton=skel, sigma=sigma,
+                                      return_rotations=True, return_offsets=True)
+        if fix_feet:
+            j, r = remove_foot_skate(j, torch.tensor(lens), (x, mean, std), skeleton=skel, blend=blend, rotations=r)
         if return_rotations:
             return [(j[i, :n], r[i, :n], o[i]) for i, n in enumerate(lens)]
         return [j[i, :n] for i, n in enumerate(lens)]
 
     @torch.no_grad()
-    def generate_rotations(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, offsets=None, **kw):
+    def generate_rotations(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, offsets=None, fix_feet=False,
+                           blend=5, **kw):
         """``generate`` followed by forward kinematics (``postprocess.motion_to_joints_fk``): per sample
         ``(joints (m, J, 3), rotations (m, J, 3, 3), offsets (J, 3))``: the joints on rigid bones, unfiltered so that they
         agree with the rotations, the global rotation matrix of every joint (the root's at joint 0) and the bone offsets
-        used (``offsets``, or the sample's own mean bone lengths).  ``**kw`` as for ``generate``."""
+        used (``offsets``, or the sample's own mean bone lengths).  ``fix_feet`` / ``blend``: foot-skate clean-up as in
+        ``generate_joints``; the rotations of knees, ankles and toes turn with their bones.  ``**kw`` as for ``generate``."""
         motions = self.generate(caption, m_lens, dim_pose, batch_size, **kw)
         lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
-        return self._to_joints(motions, lens, dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True, offsets, True)
+        return self._to_joints(motions, lens, dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True, offsets, True,
+                               fix_feet=fix_feet, blend=blend)
 
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
@@ -363,12 +377,14 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_long_joints(self, scripts, dim_pose, mean, std, *, joints_num=22, sigma=1.0, from_rotations=False,
-                             offsets=None, **kw):
+                             offsets=None, fix_feet=False, feet_blend=5, **kw):
         """``generate_long`` followed by ``postprocess.motion_to_joints`` over each whole canvas (one continuous root
         path): a list of ``(canvas_len, joints_num, 3)`` joint positions.  The post-processing kernel holds a canvas in
         LDS: at most MAX_JOINTS_FRAMES frames.  ``edit_joints`` / ``edit_mask`` (through ``**kw``): continue joint clips, as
         in ``generate_long``, under this call's ``mean`` / ``std``.  ``from_rotations`` / ``offsets``: forward kinematics,
-        as in ``generate_joints`` (at most ``postprocess.fk_max_frames()`` frames)."""
+        as in ``generate_joints`` (at most ``postprocess.fk_max_frames()`` frames).  ``fix_feet`` / ``feet_blend``:
+        foot-skate clean-up over each whole canvas, as ``fix_feet`` / ``blend`` of ``generate_joints`` (``blend`` is
+        ``generate_long``'s here): a contact that spans an overlap is one run."""
         plans = ML.script_plans(scripts, kw.get("overlap", 20), self._model().num_frames)
         longest = max(p[3] for p in plans)
         most = MAX_JOINTS_FRAMES
@@ -381,7 +397,7 @@ class DDPMTrainer(object):
             kw = dict(kw, mean=mean, std=std)
         motions = self.generate_long(scripts, dim_pose, **kw)
         return self._to_joints(motions, [mo.shape[0] for mo in motions], dim_pose, mean, std, joints_num, sigma,
-                               from_rotations, offsets)
+                               from_rotations, offsets, fix_feet=fix_feet, blend=feet_blend)
 
     def save(self, file_name, ep, total_it):
         state = {"opt_encoder": getattr(self, "opt_encoder_state", {}), "ep": ep, "total_it": total_it,
