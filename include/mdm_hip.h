@@ -626,6 +626,9 @@ enum MdmVariant {
   MDM_VAR_STREAM3_NEVER = 69,    /* its bf16x3 form (pre-split rows x a pair stream): never */
   MDM_VAR_STREAM3_ALWAYS = 70    /*   wherever it is eligible */
 };
+/* One more value of the same knob, kept apart from the enum above, whose values (all below 128) are a closed set that
+ * tests/test_abi.py pins: the MoE router as its own three launches, not inside the stylization launch in front of the block. */
+enum MdmRouteVariant { MDM_VAR_ROUTE_LAUNCH = 171 };
 int mdm_set_gemm_variant(int variant);
 
 /* Measurement probe for bench.py: while enabled, every launch of the dominant kernel (the fused expert MLP inside
@@ -638,6 +641,11 @@ int mdm_probe_enable(int32_t enable);
  * capacity = int32 elements buf holds: a forward that needs more (2L * 4 * B * T) returns MDM_ERR_ARG instead of writing past it.
  * Used to count routing flips against the oracle; pass NULL to switch it off.  Process-global, not thread-safe. */
 int mdm_route_dump(int32_t* buf, int64_t capacity);
+/* Test aid: where, inside a workspace carved for (m, B, T, N), the LAST MoE block that ran left its routing.  Byte offsets:
+ * off[0] hn rows (2, M, D; the mode's expert-operand format), off[1] top_idx (2, M, 2) int32, off[2] top_val (2, M, 2) fp32,
+ * off[3] perm (4 M) int32, off[4] rowscale (4 M) fp32, off[5] pos4 (M, 4) int32, off[6] goff (2 E + 1) int32, off[7] cursor
+ * (2 E) int32; M = the rows of that block (B * T / 2 at the coarse scale). */
+int mdm_route_workspace(const MdmModel* m, int32_t B, int32_t T, int32_t N, int64_t* off);
 /* Number of passes (of <= 128 folded text columns, whole heads) the fused text cross-attention takes for H heads and N text
  * tokens, 0 when the folded path is not taken (D != 512, or more than two passes: N > 64 at H = 4, where the GEMM chain
  * measures faster).  Sizes the optional MdmTextCache buffers:

@@ -157,7 +157,7 @@ def lib():
 EXPORTS = ["mdm_version", "mdm_gemm", "mdm_fused_mlp", "mdm_mlp_stream_elems", "mdm_mlp_stream_pack", "mdm_gemm_stream_elems", "mdm_gemm_stream_pack", "mdm_gemm_stream3_elems", "mdm_gemm_stream3_pack", "mdm_gemm_stream1_elems", "mdm_gemm_stream1_pack", "mdm_gemm_stream3x_elems", "mdm_gemm_stream3x_group_elems", "mdm_gemm_stream3x_pack", "mdm_pack_bf16", "mdm_pack_f16", "mdm_pack_fp8", "mdm_workspace_bytes", "mdm_text_cache_build",
            "mdm_denoiser_forward", "mdm_stem_cache_build", "mdm_block_forward", "mdm_moe_ffn_forward", "mdm_dual_self_attn_forward", "mdm_linear_xattn_forward",
            "mdm_softmax_xattn_ffn_forward", "mdm_performer_attn_forward", "mdm_stylization_forward", "mdm_stem_embeddings",
-           "mdm_cfg_posterior_step", "mdm_ddim_step", "mdm_fill_timesteps_mapped", "mdm_guided_update", "mdm_guided_update_inpaint", "mdm_composed_update", "mdm_noise_normal", "mdm_noise_normal_ids", "mdm_text_head_workspace_bytes", "mdm_text_head_forward", "mdm_motion_postprocess", "mdm_motion_features_max_frames", "mdm_motion_features", "mdm_motion_fk_max_frames", "mdm_motion_fk", "mdm_foot_skate_max_frames", "mdm_foot_skate", "mdm_joint_control_max_frames", "mdm_joint_loss_grad", "mdm_joint_guidance", "mdm_handshake_blend", "mdm_xattn_gate", "mdm_fill_i64", "mdm_add_i32", "mdm_set_gemm_variant", "mdm_probe_enable", "mdm_probe_read", "mdm_route_dump",
+           "mdm_cfg_posterior_step", "mdm_ddim_step", "mdm_fill_timesteps_mapped", "mdm_guided_update", "mdm_guided_update_inpaint", "mdm_composed_update", "mdm_noise_normal", "mdm_noise_normal_ids", "mdm_text_head_workspace_bytes", "mdm_text_head_forward", "mdm_motion_postprocess", "mdm_motion_features_max_frames", "mdm_motion_features", "mdm_motion_fk_max_frames", "mdm_motion_fk", "mdm_foot_skate_max_frames", "mdm_foot_skate", "mdm_joint_control_max_frames", "mdm_joint_loss_grad", "mdm_joint_guidance", "mdm_handshake_blend", "mdm_xattn_gate", "mdm_fill_i64", "mdm_add_i32", "mdm_set_gemm_variant", "mdm_probe_enable", "mdm_probe_read", "mdm_route_dump", "mdm_route_workspace",
            "mdm_moe_train_workspace_bytes", "mdm_moe_ffn_train_forward", "mdm_moe_ffn_train_backward", "mdm_sumsq", "mdm_adam_step", "mdm_sd_fold_passes",
            "mdm_gru_bidir_workspace_bytes", "mdm_gru_bidir", "mdm_eval_pad_rows", "mdm_eval_ln_leaky", "mdm_eval_matching", "mdm_eval_center"]
 

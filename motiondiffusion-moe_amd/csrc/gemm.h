@@ -116,11 +116,22 @@ struct StyleTail3 {
   const float *l2w = nullptr, *l2b = nullptr;  // with skip: ln_out = LN(out; l2w, l2b)
   int ln_x2 = 0;                               // ln_out as MDM_OP_X2_ROW rows instead of fp32
 };
+// router descriptor of style_gemm: with it the launch also routes its finished rows for the MoE block behind it -- the work of the
+// gate launch of moe_route (hn rows, top_idx / top_val, per-workgroup partials in gate->hist / gate->uimp, style_gemm_route_parts(M)
+// of them) -- and zeroes the slab cursors; moe_route_folded (csrc/kernels.h) finishes the route
+struct MoeGateParams;
+struct StyleRoute {
+  const MoeGateParams* gate = nullptr;
+  int E = 0;
+  int* cursor = nullptr;  // [2 E]
+};
+bool style_gemm_route_supported(int D, int64_t M, int E, int hn_fmt, int h16);
+int64_t style_gemm_route_parts(int64_t M);
 int style_gemm3(const float* src, int64_t M, int D, int S, const float* pw, const float* pb, const float* sw, const float* sb,
                 const float* sc, const int* pos4, const uint16_t* ws3, const float* bias, const float* resid, float out_scale,
                 const float* colscale, float* out, const StyleTail3& t, hipStream_t s);
 int style_gemm(const void* src, int src_fmt, int64_t M, int D, int S, const float* pw, const float* pb, const float* sw, const float* sb,
                const float* sc, const int* pos4, const uint16_t* ws, const float* bias, const float* resid, float out_scale,
-               const float* colscale, float* out, uint16_t* out16, int h16, hipStream_t s);
+               const float* colscale, float* out, uint16_t* out16, int h16, hipStream_t s, const StyleRoute* route = nullptr);
 
 }  // namespace mdm

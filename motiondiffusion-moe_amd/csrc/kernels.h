@@ -37,6 +37,8 @@ int to_bf16(const float* src, int64_t n, uint16_t* dst, int h16, hipStream_t s);
 int f16_to_bf16x2(const uint16_t* src, int64_t n, uint16_t* hi, uint16_t* lo, hipStream_t s);
 int moe_route(const float* x, int64_t M, int D, int E, const MoeGateParams& p, int* goff, int* cursor, int* perm,
               float* rowscale, int* pos4, hipStream_t s);
+int moe_route_folded(int64_t M, int E, const MoeGateParams& p, int nparts, int* goff, int* cursor, int* perm, float* rowscale,
+                     int* pos4, hipStream_t s);
 int head_norm(float* qkv, int64_t M, int H, int dh, const float* w, const float* b, hipStream_t s);
 int den_ln(const float* num, const float* phi, int64_t M, int H, int dh, const float* w, const float* b, void* out,
            int out_bf, hipStream_t s);

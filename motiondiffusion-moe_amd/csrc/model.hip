@@ -248,13 +248,14 @@ StylePath style_path(const Ctx& c, const MdmStyle& st, bool src16, bool out16, b
 // says FUSED3_TAIL (elsewhere the caller runs those LayerNorms itself)
 int style_apply(const Ctx& c, const MdmStyle& st, const float* src, const float* pw, const float* pb, const int* pos4,
                 const float* sc, float* tmp, const float* resid, float out_scale, const float* colscale, float* out,
-                uint16_t* out16 = nullptr, bool src_bf16 = false, const StyleTail3* t3 = nullptr) {
+                uint16_t* out16 = nullptr, bool src_bf16 = false, const StyleTail3* t3 = nullptr, const StyleRoute* route = nullptr) {
   const int D = c.m->D;
   const StylePath path = style_path(c, st, src_bf16, out16 != nullptr, t3 != nullptr);
+  if (route && path != StylePath::FUSED16) return MDM_ERR_UNSUPPORTED;  // (route_path() asks for it on the one-launch form only)
   switch (path) {
     case StylePath::FUSED16:
       return style_gemm(src, src_bf16 ? c.h16 : 0, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws, st.out_b, resid,
-                        out_scale, colscale, out, out16, c.h16, c.s);
+                        out_scale, colscale, out, out16, c.h16, c.s, route);
     case StylePath::FUSED3:
     case StylePath::FUSED3_TAIL:
       return style_gemm3(src, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws3, st.out_b, resid, out_scale, colscale, out,
@@ -496,9 +497,37 @@ XattnPath lin_xattn_path(const Ctx& c, const MdmLayer& l) {
   return XattnPath::CHAIN;
 }
 
+// MoE router.  FOLDED (16-bit modes at D = 512, E = 8 / 16, hn rows in the mode's 16-bit format, inside decoder_layer): the gate
+// runs in the epilogue of the cross-attention stylization launch in front of the MoE block, on the rows that launch has just
+// finished, and the assign launch makes the slab offsets itself -- one router launch per layer instead of three, bit-identical
+// routing (MDM_VAR_ROUTE_LAUNCH: LAUNCH).  LAUNCH: gate, offsets and assign as three launches (moe_route); also whenever the
+// stylization grid would not fit the partial-counter buffers, and for a MoE block that runs alone.  The variants that pick the
+// gate KERNEL (MDM_VAR_ROUTER_CONST_E / _RUNTIME_E) keep the launch they are about.
+enum class RoutePath { FOLDED, LAUNCH };
+RoutePath route_path(const Ctx& c, const MdmLayer& l) {
+  if (g_variant == MDM_VAR_ROUTE_LAUNCH || g_variant == MDM_VAR_ROUTER_CONST_E || g_variant == MDM_VAR_ROUTER_RUNTIME_E) return RoutePath::LAUNCH;
+  if (c.bf && !c.fp8 && style_path(c, l.ca_style, true, false, false) == StylePath::FUSED16 &&
+      style_gemm_route_supported(c.m->D, c.M, c.m->E, fmt_mlp(c), c.h16))
+    return RoutePath::FOLDED;
+  return RoutePath::LAUNCH;
+}
+// the router's operands of one layer (forced: optional injected routing)
+MoeGateParams gate_params(const Ctx& c, const MdmLayer& l, const int* forced) {
+  const Work& w = c.w;
+  MoeGateParams p = {};
+  for (int b = 0; b < 2; ++b) {
+    p.ln_w[b] = l.moe_ln_w[b], p.ln_b[b] = l.moe_ln_b[b];
+    p.gate_w[b] = l.gate_w[b], p.gate_b[b] = l.gate_b[b];
+    p.usage[b] = l.usage[b], p.importance[b] = l.importance[b];
+  }
+  p.hn = w.hn, p.hn_bf16 = c.fp8 ? 3 : fmt_mlp(c), p.hn_scale = w.hn_scale, p.top_idx = w.top_idx, p.top_val = w.top_val, p.hist = w.hist, p.uimp = w.uimp, p.forced_idx = forced;
+  return p;
+}
+
 // GatedCrossAttention (fast_attention.py:242-272): out = x + sigmoid(gate)*sigmoid(adaptive)*style(softmax(q) A)
+// route: the stylization launch also routes `out` for the MoE block that follows (RoutePath::FOLDED)
 int cross_block(const Ctx& c, const MdmLayer& l, const float* at, const float* x, const float* sc, float* out,
-                bool pre_normed = false) {
+                bool pre_normed = false, const StyleRoute* route = nullptr) {
   const MdmModel& m = *c.m;
   const int D = m.D, H = m.H, dh = D / H;
   const Work& w = c.w;
@@ -535,7 +564,7 @@ int cross_block(const Ctx& c, const MdmLayer& l, const float* at, const float* x
       break;
     }
   }
-  return style_apply(c, l.ca_style, w.t4, nullptr, nullptr, nullptr, sc, w.t2, x, 1.f, l.ca_gvec, out, nullptr, y16);
+  return style_apply(c, l.ca_style, w.t4, nullptr, nullptr, nullptr, sc, w.t2, x, 1.f, l.ca_gvec, out, nullptr, y16, nullptr, route);
 }
 
 // one grouped expert GEMM: rows of A [., K] in the mode's expert-operand form (e4m3, 16-bit, pre-split or fp32 rows) times
@@ -570,19 +599,19 @@ MoePath moe_path(const Ctx& c, const MdmMlpDesc& f) {
 }
 
 // MoEMultiBranchFFN (multi_branch.py:52-61) with SwitchMoELayer top-2 routing (switch_moe.py:44-111)
+// rp == FOLDED: the launch that produced x has run the gate already (cross_block with a StyleRoute)
 int moe_block(const Ctx& c, const MdmLayer& l, const float* x, const float* sc, const int* forced, float* out,
-              uint16_t* out16, int32_t* route_out = nullptr) {
+              uint16_t* out16, int32_t* route_out = nullptr, RoutePath rp = RoutePath::LAUNCH) {
   const MdmModel& m = *c.m;
   const int D = m.D, F = m.F, E = m.E;
   const Work& w = c.w;
-  MoeGateParams p = {};
-  for (int b = 0; b < 2; ++b) {
-    p.ln_w[b] = l.moe_ln_w[b], p.ln_b[b] = l.moe_ln_b[b];
-    p.gate_w[b] = l.gate_w[b], p.gate_b[b] = l.gate_b[b];
-    p.usage[b] = l.usage[b], p.importance[b] = l.importance[b];
+  const MoeGateParams p = gate_params(c, l, forced);
+  switch (rp) {
+    case RoutePath::FOLDED:
+      MDM_TRY(moe_route_folded(c.M, E, p, (int)style_gemm_route_parts(c.M), w.goff, w.cursor, w.perm, w.rowscale, w.pos4, c.s));
+      break;
+    case RoutePath::LAUNCH: MDM_TRY(moe_route(x, c.M, D, E, p, w.goff, w.cursor, w.perm, w.rowscale, w.pos4, c.s)); break;
   }
-  p.hn = w.hn, p.hn_bf16 = c.fp8 ? 3 : fmt_mlp(c), p.hn_scale = w.hn_scale, p.top_idx = w.top_idx, p.top_val = w.top_val, p.hist = w.hist, p.uimp = w.uimp, p.forced_idx = forced;
-  MDM_TRY(moe_route(x, c.M, D, E, p, w.goff, w.cursor, w.perm, w.rowscale, w.pos4, c.s));
   if (route_out && hipMemcpyAsync(route_out, w.top_idx, 4 * c.M * sizeof(int32_t), hipMemcpyDeviceToDevice, c.s) != hipSuccess)
     return MDM_ERR_LAUNCH;
   MdmMlpDesc f = {};
@@ -776,9 +805,13 @@ int decoder_layer(const Ctx& c, int layer, const MdmTextCache& tc, float* x, uin
   if (!c.bf) x16 = y16 = nullptr;  // the 16-bit shadows of the residual stream are read by the 16-bit modes only: do not write them here
   MDM_TRY(dual_block(c, l, x, x16, sc4, y, l.ca_norm_w, l.ca_norm_b));
   MDM_TRY(dump(0, y));
-  MDM_TRY(cross_block(c, l, tc_at(m, tc, layer), y, sc4 + 2 * scs, x, true));
+  const RoutePath rp = route_path(c, l);
+  const MoeGateParams gp = gate_params(c, l, forced);
+  StyleRoute sr;
+  sr.gate = &gp, sr.E = m.E, sr.cursor = c.w.cursor;
+  MDM_TRY(cross_block(c, l, tc_at(m, tc, layer), y, sc4 + 2 * scs, x, true, rp == RoutePath::FOLDED ? &sr : nullptr));
   MDM_TRY(dump(1, x));
-  MDM_TRY(moe_block(c, l, x, sc4 + 3 * scs, forced, y, y16, route_out));
+  MDM_TRY(moe_block(c, l, x, sc4 + 3 * scs, forced, y, y16, route_out, rp));
   MDM_TRY(dump(2, y));
   MDM_TRY(sdcross_block(c, l, tc_k(m, tc, layer), tc_v(m, tc, layer), y, y16, x, x16, tc_fold(m, tc, layer)));
   return dump(3, x);
@@ -1208,6 +1241,15 @@ int mdm_motion_postprocess(const float* motion, const int32_t* length, const flo
 // passes of <= 128 folded text columns that sd_fold takes for (H heads, N text tokens); 0 = unsupported: sizes the
 // MdmTextCache.sd_kfold / sd_cb / sd_vfold buffers ([L2][B][passes][128][D], [L2][B][passes][128], [L2][B][passes][D][128])
 int mdm_sd_fold_passes(int32_t D, int32_t H, int32_t N) { return sd_fold_policy(D, H, N); }
+
+int mdm_route_workspace(const MdmModel* m, int32_t B, int32_t T, int32_t N, int64_t* off) {
+  if (check_model(m) != MDM_OK || B <= 0 || T <= 0 || !off) return MDM_ERR_ARG;
+  uint8_t* const base = (uint8_t*)4096;  // (never dereferenced: carve() only adds to it)
+  const Work w = carve(*m, B, T, N, base);
+  const void* p[8] = {w.hn, w.top_idx, w.top_val, w.perm, w.rowscale, w.pos4, w.goff, w.cursor};
+  for (int i = 0; i < 8; ++i) off[i] = (const uint8_t*)p[i] - base;
+  return MDM_OK;
+}
 
 int mdm_route_dump(int32_t* buf, int64_t capacity) {
   if (buf && capacity <= 0) return MDM_ERR_ARG;

@@ -2,6 +2,7 @@
 // normalisations of the Performer attention, softmaxes, MoE routing and the sampler update.
 // One wave (64 lanes) owns one row of D elements; everything stays in fp32.
 #include "kernels.h"
+#include "moe_gate_row.h"
 #include "row.h"
 
 namespace mdm {
@@ -289,135 +290,13 @@ __global__ __launch_bounds__(256) void moe_gate16_kernel(const float* __restrict
     const int64_t rc = ok ? row : M - 1;
     if constexpr (NV > 8) load_x(base, vn);  // D = 1024: a second row set in flight costs the second wave per SIMD
     f32x4 v[NV];
-    float s = 0.f;
 #pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      v[c] = vn[c];
-      s += v[c][0] + v[c][1] + v[c][2] + v[c][3];
-    }
+    for (int c = 0; c < NV; ++c) v[c] = vn[c];
+    const float s = gate16_row_sum(v);
     // next iteration's rows, in flight during this one's arithmetic
     if constexpr (NV <= 8)
       if (base + stride < M) load_x(base + stride, vn);
-    const float mean = group_sum<16>(s) / D;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      v[c] = (f32x4){v[c][0] - mean, v[c][1] - mean, v[c][2] - mean, v[c][3] - mean};
-      q += v[c][0] * v[c][0] + v[c][1] * v[c][1] + v[c][2] * v[c][2] + v[c][3] * v[c][3];
-    }
-    const float rstd = rsqrtf(group_sum<16>(q) / D + 1e-5f);
-#pragma unroll
-    for (int br = 0; br < 2; ++br) {
-      float logit[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) logit[e] = 0.f;
-      float amax = 0.f;  // fp8 rows: per-row scale from the largest |LN output|
-#pragma unroll
-      for (int c = 0; c < NV; ++c) {
-        const int k = 4 * (l16 + 16 * c);
-        const f32x4 w = *(const f32x4*)(lnw + br * D + k), b = *(const f32x4*)(lnb + br * D + k);
-        const f32x4 h = {v[c][0] * rstd * w[0] + b[0], v[c][1] * rstd * w[1] + b[1], v[c][2] * rstd * w[2] + b[2],
-                         v[c][3] * rstd * w[3] + b[3]};
-        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(h[0]), fabsf(h[1])), fmaxf(fabsf(h[2]), fabsf(h[3]))));
-        if constexpr (HNF >= 0) {
-          if constexpr (HNF == 1 || HNF == 2) {
-            *(uint2*)((uint16_t*)p.hn + ((int64_t)br * M + rc) * D + k) = make_uint2(pack_h16(HNF, h[0], h[1]), pack_h16(HNF, h[2], h[3]));
-          } else if constexpr (HNF == 0) {
-            *(f32x4*)((float*)p.hn + ((int64_t)br * M + rc) * D + k) = h;
-          } else if constexpr (HNF == 4) {  // x2 rows (MDM_OP_X2_ROW): what the fp32-grade expert GEMM reads without re-splitting
-            // (p.hn is a workspace buffer the library carves itself; all 16 lanes of a row store, past-the-end rows repeat row M - 1)
-            static_assert(D % 32 == 0, "lane pairs of store_x2_4p hold k and k ^ 4 of one 32-column block");
-            store_x2_4p((uint16_t*)p.hn + ((int64_t)br * M + rc) * 2 * D, k, h[0], h[1], h[2], h[3]);
-          }
-        } else if (ok && p.hn_bf16 != 3) {
-          if (p.hn_bf16 == 4) {
-            store_x2_4((uint16_t*)p.hn + ((int64_t)br * M + row) * 2 * D, k, h[0], h[1], h[2], h[3]);
-          } else if (p.hn_bf16 == 2) {  // (one uniform branch per chunk, not one per converted pair)
-            *(uint2*)((uint16_t*)p.hn + ((int64_t)br * M + row) * D + k) = make_uint2(pack_h16(2, h[0], h[1]), pack_h16(2, h[2], h[3]));
-          } else if (p.hn_bf16) {
-            *(uint2*)((uint16_t*)p.hn + ((int64_t)br * M + row) * D + k) = make_uint2(pack_h16(1, h[0], h[1]), pack_h16(1, h[2], h[3]));
-          } else {
-            *(f32x4*)((float*)p.hn + ((int64_t)br * M + row) * D + k) = h;
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-          if (e < E) {
-            const f32x4 g = *(const f32x4*)(gw + (br * E + e) * D + k);
-            if constexpr (FAST) {
-              // explicit FMA chain: written as a sum of products hipcc SLP-packs the four multiplies (v_pk_mul_f32) and adds
-              // the results one by one -- 1626 VALU instructions per token group where 1024 FMAs do
-              logit[e] = __builtin_fmaf(h[3], g[3], __builtin_fmaf(h[2], g[2], __builtin_fmaf(h[1], g[1], __builtin_fmaf(h[0], g[0], logit[e]))));
-            } else {
-              logit[e] += h[0] * g[0] + h[1] * g[1] + h[2] * g[2] + h[3] * g[3];
-            }
-          }
-        if constexpr (EX > 0 && HNF >= 0) __builtin_amdgcn_sched_barrier(0);
-      }
-      if (hnf == 3) {  // e4m3 rows, scale = amax / 448 (the LayerNorm output is recomputed: cheaper than keeping it)
-        amax = group_max<16>(amax);
-        const float scale = amax > 0.f ? amax * (1.f / 448.f) : 1.f, inv = 1.f / scale;
-#pragma unroll
-        for (int c = 0; c < NV; ++c) {
-          const int k = 4 * (l16 + 16 * c);
-          const f32x4 w = *(const f32x4*)(lnw + br * D + k), b = *(const f32x4*)(lnb + br * D + k);
-          uint32_t q = 0;
-          q = __builtin_amdgcn_cvt_pk_fp8_f32((v[c][0] * rstd * w[0] + b[0]) * inv, (v[c][1] * rstd * w[1] + b[1]) * inv, q, false);
-          q = __builtin_amdgcn_cvt_pk_fp8_f32((v[c][2] * rstd * w[2] + b[2]) * inv, (v[c][3] * rstd * w[3] + b[3]) * inv, q, true);
-          if (HNF >= 0 || ok) *(uint32_t*)((uint8_t*)p.hn + ((int64_t)br * M + (HNF >= 0 ? rc : row)) * D + k) = q;
-        }
-        if (ok && l16 == 0) p.hn_scale[(int64_t)br * M + row] = scale;
-      }
-      // top-2 is decided on the LOGITS (softmax is monotone; ties -> lowest index), the softmax denominator is built
-      // with one exp per lane (lane e owns expert e) instead of E exps in every lane
-      float mx = -INFINITY, mine = -INFINITY;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        if (e < E) {
-          logit[e] = group_sum<16>(logit[e]) + p.gate_b[br][e];
-          mx = fmaxf(mx, logit[e]);
-          mine = (l16 == e) ? logit[e] : mine;
-        }
-      }
-      const float den = group_sum<16>(l16 < E ? expf(mine - mx) : 0.f);
-      // top-2 is TOTAL (see moe_gate_kernel): NaN logits fail every `>`, the distinct in-range initial pair survives and the
-      // probabilities (hence the token's outputs) come out NaN instead of an out-of-range index
-      int i1 = 0, i2 = 1;
-      float l1 = -INFINITY, l2 = -INFINITY;
-      if (p.forced_idx) {
-        i1 = min(max(p.forced_idx[((int64_t)br * M + rc) * 2 + 0], 0), E - 1);
-        i2 = min(max(p.forced_idx[((int64_t)br * M + rc) * 2 + 1], 0), E - 1);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          l1 = e == i1 ? logit[e] : l1;
-          l2 = e == i2 ? logit[e] : l2;
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          if (e < E) {
-            if (logit[e] > l1) {
-              l2 = l1, i2 = i1;
-              l1 = logit[e], i1 = e;
-            } else if (logit[e] > l2) {
-              l2 = logit[e], i2 = e;
-            }
-          }
-        }
-        if (i2 == i1) i2 = i1 == 0 ? 1 : 0;  // only reachable with non-finite logits
-      }
-      const float v1 = expf(l1 - mx) / den, v2 = expf(l2 - mx) / den;
-      if (ok && l16 == 0) {
-        const int64_t o = ((int64_t)br * M + row) * 2;
-        p.top_idx[o] = i1, p.top_idx[o + 1] = i2;
-        p.top_val[o] = v1, p.top_val[o + 1] = v2;
-        atomicAdd(&s_hist[br * E + i1], 1);
-        atomicAdd(&s_hist[br * E + i2], 1);
-        atomicAdd(&s_usage[br * E + i1], 1.f);
-        atomicAdd(&s_imp[br * E + i1], v1);
-        atomicAdd(&s_imp[br * E + i2], v2);
-      }
-    }
+    gate16_row<NV, FAST, EX, HNF>(v, s, row, ok, rc, M, E, hnf, l16, gw, lnw, lnb, s_hist, s_usage, s_imp, p);
   }
   __syncthreads();
   if (threadIdx.x < 2 * E) {  // per-block partials, summed by moe_offsets_kernel: no global atomics at all
@@ -475,13 +354,103 @@ __global__ __launch_bounds__(1024) void moe_offsets_kernel(const int* __restrict
 
 // positions inside each expert's contiguous slab: rank within the block from an LDS counter, one global
 // atomic per (block, expert) to reserve the block's range.  Order within a slab is irrelevant (rows are independent).
+// OFFS (the folded route, moe_route_folded): there is no moe_offsets_kernel in front.  Every workgroup sums the nparts histogram
+// partials of the producing launch itself (<= 1024 x 2E ints, L2-resident, independent loads; integer sums, so every workgroup
+// gets the same offsets) and scans them in LDS.  The grid has ONE workgroup more than the assignment needs: that last one does the
+// bookkeeping and nothing else -- goff for the expert MLP, usage / importance partials folded into the module buffers (single
+// writer, fixed order) -- so its two extra passes over the partials run beside the others' assignment instead of in front of it.
+// The cursors were zeroed by workgroup 0 of the producing launch.  No workgroup waits for another.
+template <bool OFFS>
 __global__ __launch_bounds__(256) void moe_assign_kernel(const int* __restrict__ top_idx, const float* __restrict__ top_val,
-                                                         int64_t M, int E, const int* __restrict__ goff,
+                                                         int64_t M, int E, int* __restrict__ goff,
                                                          int* __restrict__ cursor, int* __restrict__ perm,
-                                                         float* __restrict__ rowscale, int* __restrict__ pos4) {
-  __shared__ int s_cnt[32], s_base[32];
+                                                         float* __restrict__ rowscale, int* __restrict__ pos4, int nparts,
+                                                         MoeGateParams p) {
+  __shared__ int s_cnt[32], s_base[32], s_goff[33];
+  if constexpr (OFFS) {
+    // column sums of the partials in three steps, every load of a thread requested before the first is used (one memory round
+    // trip): thread t sums rows t, t + 256, ... (a row = the 32 counters of one producing workgroup, 128 B), the 256 row sums go
+    // through an LDS tile, eight 32-row chunks are summed per counter, then the eight chunk sums.  The order is fixed, so the float
+    // sums of the bookkeeping workgroup are deterministic; the integer sums are the same in every workgroup.
+    __shared__ int tile[256][33];
+    __shared__ int chunk[8][33];
+    const int g = threadIdx.x & 31, c = threadIdx.x >> 5, G = 2 * E;
+    const bool book = blockIdx.x == gridDim.x - 1;
+    auto col_sums = [&](auto zero, const decltype(zero)* __restrict__ part, int ld) {  // -> chunk[0][g], as raw bits
+      typedef decltype(zero) T;
+      T acc[32];
+#pragma unroll
+      for (int j = 0; j < 32; ++j) acc[j] = zero;
+      for (int b0 = threadIdx.x; b0 < nparts; b0 += 512) {
+        const int b1 = b0 + 256;
+        uint4 r0[8], r1[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r0[j] = 4 * j < G ? *(const uint4*)(part + (int64_t)b0 * ld + 4 * j) : make_uint4(0, 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r1[j] = 4 * j < G && b1 < nparts ? *(const uint4*)(part + (int64_t)b1 * ld + 4 * j) : make_uint4(0, 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const uint32_t w0[4] = {r0[j].x, r0[j].y, r0[j].z, r0[j].w}, w1[4] = {r1[j].x, r1[j].y, r1[j].z, r1[j].w};
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            acc[4 * j + i] += __builtin_bit_cast(T, w0[i]);
+            acc[4 * j + i] += __builtin_bit_cast(T, w1[i]);  // (+ 0 past the end: exact for both types)
+          }
+        }
+      }
+      __syncthreads();  // (the tile's previous use is over)
+#pragma unroll
+      for (int j = 0; j < 32; ++j) tile[threadIdx.x][j] = __builtin_bit_cast(int, acc[j]);
+      __syncthreads();
+      T s = zero;
+      for (int i = 0; i < 32; ++i) s += __builtin_bit_cast(T, tile[32 * c + i][g]);
+      chunk[c][g] = __builtin_bit_cast(int, s);
+      __syncthreads();
+      if (threadIdx.x < 32) {
+        T t = zero;
+        for (int k = 0; k < 8; ++k) t += __builtin_bit_cast(T, chunk[k][g]);
+        chunk[0][g] = __builtin_bit_cast(int, t);
+      }
+      __syncthreads();
+    };
+    // (counters g >= 2 E of a row are never written by the producer: those in the last 16 bytes read are summed as they are, never used)
+    col_sums(0, p.hist, 32);
+    if (threadIdx.x < 32) s_cnt[g] = g < G ? chunk[0][g] : 0;  // (reset at the top of the loop below)
+    if (book) {  // single writer of the module buffers
+      float ut = 0.f, it = 0.f;
+      col_sums(0.f, p.uimp, 64);
+      if (threadIdx.x < G) ut = __int_as_float(chunk[0][g]);
+      col_sums(0.f, p.uimp + 32, 64);
+      if (threadIdx.x < G) {
+        it = __int_as_float(chunk[0][g]);
+        const int br = g / E, e = g - br * E;
+        if (p.usage[br]) {  // atomics: forwards of different batch chunks may run concurrently on separate streams
+          atomicAdd(&p.usage[br][e], ut);
+          atomicAdd(&p.importance[br][e], it);
+        }
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int s = 0;
+      for (int i = 0; i < G; ++i) {
+        s_goff[i] = s;
+        s += s_cnt[i];
+      }
+      s_goff[G] = s;
+    }
+    __syncthreads();
+    if (book) {
+      if (threadIdx.x <= G) goff[threadIdx.x] = s_goff[threadIdx.x];
+      return;
+    }
+  } else {
+    if (threadIdx.x <= 2 * E) s_goff[threadIdx.x] = goff[threadIdx.x];
+    __syncthreads();
+  }
   const int64_t total = 2 * M * 2;
-  for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base < total; base += (int64_t)gridDim.x * blockDim.x) {
+  const int64_t nwork = OFFS ? gridDim.x - 1 : gridDim.x;  // workgroups that assign
+  for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base < total; base += nwork * blockDim.x) {
     if (threadIdx.x < 32) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     const int64_t i = base + threadIdx.x;
@@ -499,7 +468,7 @@ __global__ __launch_bounds__(256) void moe_assign_kernel(const int* __restrict__
     if (threadIdx.x < 2 * E && s_cnt[threadIdx.x]) s_base[threadIdx.x] = atomicAdd(&cursor[threadIdx.x], s_cnt[threadIdx.x]);
     __syncthreads();
     if (g >= 0) {
-      const int pos = goff[g] + s_base[g] + rank;
+      const int pos = s_goff[g] + s_base[g] + rank;
       perm[pos] = (int)(br * M + tok);
       rowscale[pos] = top_val[i];
       pos4[tok * 4 + br * 2 + k] = pos;
@@ -930,8 +899,23 @@ int moe_route(const float* x, int64_t M, int D, int E, const MoeGateParams& p, i
   hipLaunchKernelGGL(moe_offsets_kernel, dim3(1), dim3(1024), 0, s, p.hist, p.uimp, nparts, E, goff, cursor, p);
   const int64_t total = 4 * M;
   int blocks = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(moe_assign_kernel, dim3(blocks > 1024 ? 1024 : blocks), dim3(256), 0, s, p.top_idx, p.top_val, M, E,
-                     goff, cursor, perm, rowscale, pos4);
+  hipLaunchKernelGGL(moe_assign_kernel<false>, dim3(blocks > 1024 ? 1024 : blocks), dim3(256), 0, s, p.top_idx, p.top_val, M, E,
+                     goff, cursor, perm, rowscale, pos4, nparts, p);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+// The rest of the route behind a stylization launch that ran the gate in its epilogue (style_gemm with a StyleRoute): that launch
+// left top_idx / top_val / hn, nparts per-workgroup partials in p.hist / p.uimp and zeroed cursors; ONE launch makes the offsets
+// and assigns the slab positions.
+int moe_route_folded(int64_t M, int E, const MoeGateParams& p, int nparts, int* goff, int* cursor, int* perm, float* rowscale,
+                     int* pos4, hipStream_t s) {
+  if (M <= 0) return MDM_OK;
+  if (E < 2 || E > 16 || nparts < 1 || nparts > 1024 || !p.hist || !p.uimp || !p.top_idx || !p.top_val) return MDM_ERR_ARG;
+  const int64_t total = 4 * M;
+  int blocks = (int)((total + 255) / 256);
+  hipLaunchKernelGGL(moe_assign_kernel<true>, dim3((blocks > 1024 ? 1024 : blocks) + 1), dim3(256), 0, s, p.top_idx, p.top_val, M, E,
+                     goff, cursor, perm, rowscale, pos4, nparts, p);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }

@@ -13,9 +13,17 @@
 //     registers from a packed fragment stream (mdm_gemm_stream_pack: per wave the 64 fragments of its columns in K order) through
 //     an 8-fragment ring, as in csrc/mlp_stream.hip.  With 32 rows a weight fragment feeds only two MFMAs, so the launch is bound
 //     by the 512 KiB of Wout every workgroup streams (98 / 196 MB per launch, L2-resident), not by the matrix pipe;
-//   * epilogue: staged as fp32 rows through LDS, full-row stores, residual read coalesced.
+//   * epilogue: staged as fp32 rows through LDS, full-row stores, residual read coalesced;
+//   * routing epilogue (RE > 0: the cross-attention position in front of the MoE block, when the caller passes a StyleRoute): the
+//     finished rows go back into the staging, every 16-lane group takes one row into registers (32 rows x 16 lanes = the
+//     workgroup), the staging -- dead from then on -- receives both branches' fp32 gate matrices and LayerNorm vectors, and the
+//     group runs the router's row body (csrc/moe_gate_row.h, the one moe_gate16_kernel<8, true, RE, FMT> runs) on its row: hn rows,
+//     top-2, and this workgroup's histogram / usage / importance partials at p.hist / p.uimp [blockIdx.x].  Workgroup 0 zeroes the
+//     slab cursors for moe_assign_kernel<true>.  The gate data REPLACES the staging: 64 KiB of LDS at E = 8 (as without the
+//     routing), 72.4 KiB at E = 16 -- two workgroups per CU either way.
 #include "gemm.h"
 #include "kernels.h"
+#include "moe_gate_row.h"
 #include "row.h"
 
 namespace mdm {
@@ -58,8 +66,18 @@ struct StyleGemmArgs {
   int ln_x2;  // ln_out as pre-split rows (MDM_OP_X2_ROW) for the GEMM that reads it, instead of fp32
 };
 
-template <typename HT, bool SRC16, int SG_RT>
-__global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel(const StyleGemmArgs g) {
+struct StyleRouteArgs {  // the routing epilogue's operands (unused where RE == 0)
+  MoeGateParams p;
+  int* cursor;
+};
+
+// LDS of one workgroup: the fp32 staging, or the router's image where that is larger (RE = 16)
+constexpr int sg_lds_bytes(int RT, int RE) {
+  return RE > 0 && gate16_lds_bytes(RE, SG_D) > 16 * RT * SG_D * 4 ? gate16_lds_bytes(RE, SG_D) : 16 * RT * SG_D * 4;
+}
+
+template <typename HT, bool SRC16, int SG_RT, int RE = 0>
+__global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel(const StyleGemmArgs g, const StyleRouteArgs rt) {
   constexpr int SG_ROWS = 16 * SG_RT, RPW = SG_ROWS / 8;  // rows per wave in the row phase
   typedef typename HT::frag_t frag_t;
   typedef Row<8, true> R8;
@@ -209,6 +227,63 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
     if (g.resid) v[0] += q[k][0], v[1] += q[k][1], v[2] += q[k][2], v[3] += q[k][3];
     *(f32x4*)(g.out + m * D + n) = v;
     if (g.out16) *(uint2*)(g.out16 + m * D + n) = make_uint2(HT::pack(v[0], v[1]), HT::pack(v[2], v[3]));
+    if constexpr (RE > 0) *(f32x4*)(stg + ml * D + ((cl ^ (ml & 31)) << 2)) = v;  // the finished row, for the router below
+  }
+
+  // ---- routing epilogue: the MoE gate on the finished rows (csrc/moe_gate_row.h) --------------------------------------------
+  if constexpr (RE > 0) {
+    static_assert(SG_ROWS * 16 == SG_NT, "one 16-lane group per row of the tile");
+    static_assert(2 * RE * D / 4 % (2 * SG_NT) == 0 && 4 * D / 4 == SG_NT, "staging loops below");
+    static_assert(sg_lds_bytes(SG_RT, RE) <= 80 * 1024, "two workgroups per CU");
+    constexpr int NV = D / 64, NG = 2 * RE * D / 4 / SG_NT;  // 16-B pieces of the gate matrices per thread
+    const MoeGateParams& p = rt.p;
+    // the thread index again, from the wave's number and the lane count: nothing of this epilogue is then live in the GEMM phase,
+    // which has no register to spare
+    const int tid = wn * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    // the gate matrices and LayerNorm vectors are requested now and parked in registers until the staging is free
+    // (E = 16: one branch's matrix now, the other's once the rows have left the staging -- 8 pieces beside the 8 of the row spill)
+    constexpr int NP = NG <= 4 ? NG : NG / 2;
+    f32x4 tg[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) tg[j] = *(const f32x4*)(p.gate_w[j / (NG / 2)] + 4 * (tid + SG_NT * (j % (NG / 2))));
+    const int lw = tid >> 7;  // ln_w[0] | ln_w[1] | ln_b[0] | ln_b[1], D / 4 pieces each
+    const f32x4 tl = *(const f32x4*)((lw < 2 ? p.ln_w[lw] : p.ln_b[lw - 2]) + 4 * (tid & 127));
+    sg_barrier();
+    const int l16 = tid & 15;
+    const int64_t row = row0 + (tid >> 4);
+    const bool ok = row < g.M;
+    const int64_t rc = ok ? row : g.M - 1;  // a past-the-end group takes row M - 1, as in moe_gate16_kernel
+    const int rl = (int)(rc - row0);
+    f32x4 v[NV];
+#pragma unroll
+    for (int c = 0; c < NV; ++c) v[c] = *(const f32x4*)(stg + rl * D + (((l16 + 16 * c) ^ (rl & 31)) << 2));
+    sg_barrier();  // every row is in registers: the staging becomes the router's image (layout of moe_gate16_kernel)
+    float* gw = (float*)smem;
+    float* lnw = gw + 2 * RE * D;
+    float* lnb = lnw + 2 * D;
+    int* s_hist = (int*)(lnb + 2 * D);
+    float* s_usage = (float*)(s_hist + 32);
+    float* s_imp = s_usage + 32;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) *(f32x4*)(gw + (j / (NG / 2)) * RE * D + 4 * (tid + SG_NT * (j % (NG / 2)))) = tg[j];
+    if constexpr (NP < NG) {
+#pragma unroll
+      for (int j = NP; j < NG; ++j) tg[j - NP] = *(const f32x4*)(p.gate_w[j / (NG / 2)] + 4 * (tid + SG_NT * (j % (NG / 2))));
+#pragma unroll
+      for (int j = NP; j < NG; ++j) *(f32x4*)(gw + (j / (NG / 2)) * RE * D + 4 * (tid + SG_NT * (j % (NG / 2)))) = tg[j - NP];
+    }
+    *(f32x4*)(lnw + 4 * tid) = tl;
+    if (tid < 32) s_hist[tid] = 0, s_usage[tid] = 0.f, s_imp[tid] = 0.f;
+    // the slab cursors of moe_assign_kernel<true>: the previous layer's assign launch has finished in stream order
+    if (blockIdx.x == 0 && tid < 2 * RE) rt.cursor[tid] = 0;
+    sg_barrier();
+    gate16_row<NV, true, RE, FMT, (RE > 8 ? 4 : 16)>(v, gate16_row_sum(v), row, ok, rc, g.M, RE, FMT, l16, gw, lnw, lnb, s_hist, s_usage, s_imp, p);
+    __syncthreads();
+    if (tid < 2 * RE) {  // per-workgroup partials, summed by moe_assign_kernel<true>
+      p.hist[blockIdx.x * 32 + tid] = s_hist[tid];
+      p.uimp[blockIdx.x * 64 + tid] = s_usage[tid];
+      p.uimp[blockIdx.x * 64 + 32 + tid] = s_imp[tid];
+    }
   }
 }
 
@@ -445,33 +520,41 @@ int gemm_stream_pack(const float* w, int N, int K, int h16, uint16_t* out, hipSt
 bool style_gemm_supported(int D, int64_t M) { return D == SG_D && M > 0 && M / 32 < (1ll << 30); }
 
 
-template <int RT>
-static int launch_style_gemm(const StyleGemmArgs& g, bool src16, int h16, hipStream_t s) {
-  constexpr int smem = 16 * RT * SG_D * 4;
+template <int RT, int RE = 0>
+static int launch_style_gemm(const StyleGemmArgs& g, const StyleRouteArgs& rt, bool src16, int h16, hipStream_t s) {
+  constexpr int smem = sg_lds_bytes(RT, RE);
   static DevOnce attr;
   if (!attr) {
-    const void* fns[4] = {(const void*)style_gemm_kernel<HB, true, RT>, (const void*)style_gemm_kernel<HB, false, RT>,
-                          (const void*)style_gemm_kernel<HF, true, RT>, (const void*)style_gemm_kernel<HF, false, RT>};
+    const void* fns[4] = {(const void*)style_gemm_kernel<HB, true, RT, RE>, (const void*)style_gemm_kernel<HB, false, RT, RE>,
+                          (const void*)style_gemm_kernel<HF, true, RT, RE>, (const void*)style_gemm_kernel<HF, false, RT, RE>};
     for (const void* fn : fns)
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return MDM_ERR_LAUNCH;
     attr = true;
   }
   const dim3 grid((unsigned)((g.M + 16 * RT - 1) / (16 * RT)));
   if (h16 == MDM_H16_F16) {
-    if (src16) hipLaunchKernelGGL((style_gemm_kernel<HF, true, RT>), grid, dim3(SG_NT), smem, s, g);
-    else hipLaunchKernelGGL((style_gemm_kernel<HF, false, RT>), grid, dim3(SG_NT), smem, s, g);
+    if (src16) hipLaunchKernelGGL((style_gemm_kernel<HF, true, RT, RE>), grid, dim3(SG_NT), smem, s, g, rt);
+    else hipLaunchKernelGGL((style_gemm_kernel<HF, false, RT, RE>), grid, dim3(SG_NT), smem, s, g, rt);
   } else {
-    if (src16) hipLaunchKernelGGL((style_gemm_kernel<HB, true, RT>), grid, dim3(SG_NT), smem, s, g);
-    else hipLaunchKernelGGL((style_gemm_kernel<HB, false, RT>), grid, dim3(SG_NT), smem, s, g);
+    if (src16) hipLaunchKernelGGL((style_gemm_kernel<HB, true, RT, RE>), grid, dim3(SG_NT), smem, s, g, rt);
+    else hipLaunchKernelGGL((style_gemm_kernel<HB, false, RT, RE>), grid, dim3(SG_NT), smem, s, g, rt);
   }
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
 
+// The routing epilogue exists for E = 8 / 16 with hn rows in the launch's own 16-bit format; its partials are indexed by workgroup,
+// so the grid has to fit the partial buffers ([1024][32] / [1024][64])
+bool style_gemm_route_supported(int D, int64_t M, int E, int hn_fmt, int h16) {
+  return style_gemm_supported(D, M) && (E == 8 || E == 16) && hn_fmt == h16 && (h16 == MDM_H16_BF16 || h16 == MDM_H16_F16) &&
+         style_gemm_route_parts(M) <= 1024;
+}
+int64_t style_gemm_route_parts(int64_t M) { return (M + 31) / 32; }
+
 // src_fmt: 0 = fp32 source rows, else the launch's 16-bit format (must equal h16)
 int style_gemm(const void* src, int src_fmt, int64_t M, int D, int S, const float* pw, const float* pb, const float* sw, const float* sb,
                const float* sc, const int* pos4, const uint16_t* ws, const float* bias, const float* resid, float out_scale,
-               const float* colscale, float* out, uint16_t* out16, int h16, hipStream_t s) {
+               const float* colscale, float* out, uint16_t* out16, int h16, hipStream_t s, const StyleRoute* route) {
   if (M <= 0) return MDM_OK;
   if (!style_gemm_supported(D, M)) return MDM_ERR_UNSUPPORTED;
   if (!src || !sw || !sb || !sc || !ws || !bias || !out || S <= 0 || (pw && !pb)) return MDM_ERR_ARG;
@@ -481,7 +564,20 @@ int style_gemm(const void* src, int src_fmt, int64_t M, int D, int S, const floa
   g.resid = resid, g.out_scale = out_scale, g.colscale = colscale, g.out = out, g.out16 = out16;
   // 64-row tiles (one workgroup per CU, half the weight bytes per row) measured 1 % of a step SLOWER than two co-resident 32-row
   // workgroups per CU at 12544 rows; a row's arithmetic does not depend on the tile height
-  return launch_style_gemm<2>(g, src_fmt != 0, h16, s);
+  StyleRouteArgs rt = {};
+  if (route) {
+    if (!route->gate || !route->cursor) return MDM_ERR_ARG;
+    const MoeGateParams& p = *route->gate;
+    if (!style_gemm_route_supported(D, M, route->E, p.hn_bf16, h16)) return MDM_ERR_UNSUPPORTED;
+    if (!p.hn || !p.hist || !p.uimp || !p.top_idx || !p.top_val) return MDM_ERR_ARG;
+    for (int b = 0; b < 2; ++b)
+      if (!p.ln_w[b] || !p.ln_b[b] || !p.gate_w[b] || !p.gate_b[b] || ((uintptr_t)p.gate_w[b] & 15) || ((uintptr_t)p.ln_w[b] & 15) ||
+          ((uintptr_t)p.ln_b[b] & 15))
+        return MDM_ERR_ARG;
+    rt.p = p, rt.cursor = route->cursor;
+    return route->E == 8 ? launch_style_gemm<2, 8>(g, rt, src_fmt != 0, h16, s) : launch_style_gemm<2, 16>(g, rt, src_fmt != 0, h16, s);
+  }
+  return launch_style_gemm<2>(g, rt, src_fmt != 0, h16, s);
 }
 
 // ---- fp32-grade form ---------------------------------------------------------------------------------------------------------
