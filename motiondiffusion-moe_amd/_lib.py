@@ -136,6 +136,87 @@ CONTROL_MAX_ITERS = 32  # MDM_CONTROL_MAX_ITERS: guidance iterations per step of
 TAB_ROWS = 7  # sqrt_recip_acp, sqrt_recipm1_acp, coef1, coef2, post_logvar_clipped, acp, acp_prev
 
 
+_P, _I32, _I64, _U64, _F32, _F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+
+# The prototypes of include/mdm_hip.h, name -> (restype, argtypes), held against the header by tests/test_abi.py.  Every pointer,
+# struct pointers and the `void* stream` included, is _P: it takes data_ptr() ints, byref(struct), ctypes arrays and None.
+PROTOTYPES = {
+    "mdm_version": (C.c_char_p, []),
+    "mdm_gemm": (_I32, [_P, _P]),
+    "mdm_fused_mlp": (_I32, [_P, _P]),
+    "mdm_mlp_stream_elems": (_I64, [_I32, _I32, _I32, _I32]),
+    "mdm_mlp_stream_pack": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "mdm_gemm_stream_elems": (_I64, [_I32, _I32]),
+    "mdm_gemm_stream_pack": (_I32, [_P, _I32, _I32, _I32, _P, _P]),
+    "mdm_gemm_stream1_elems": (_I64, [_I32, _I32]),
+    "mdm_gemm_stream3x_elems": (_I64, [_I32, _I32, _I32]),
+    "mdm_gemm_stream3x_group_elems": (_I64, [_I32, _I32]),
+    "mdm_gemm_stream3x_pack": (_I32, [_P, _I64, _I32, _I32, _I32, _P, _P]),
+    "mdm_gemm_stream1_pack": (_I32, [_P, _I64, _I32, _I32, _I32, _P, _P]),
+    "mdm_gemm_stream3_elems": (_I64, [_I32, _I32]),
+    "mdm_gemm_stream3_pack": (_I32, [_P, _I32, _I32, _P, _P]),
+    "mdm_pack_bf16": (_I32, [_P, _I64, _I64, _I64, _P, _P, _I64, _P]),
+    "mdm_pack_fp8": (_I32, [_P, _I64, _I64, _I64, _P, _I64, _P, _P]),
+    "mdm_pack_f16": (_I32, [_P, _I64, _I64, _I64, _P, _I64, _P]),
+    "mdm_stem_cache_build": (_I32, [_P, _I32, _P, _P, _I32, _P, _P, _I64, _I32, _P]),
+    "mdm_workspace_bytes": (_I64, [_P, _I32, _I32, _I32]),
+    "mdm_text_cache_build": (_I32, [_P, _P, _P, _P, _I64, _I32, _P]),
+    "mdm_denoiser_forward": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _I32, _P]),
+    "mdm_block_forward": (_I32, [_P, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _I64, _P, _I32, _P]),
+    "mdm_moe_ffn_forward": (_I32, [_P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64, _P, _I32, _P]),
+    "mdm_dual_self_attn_forward": (_I32, [_P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64, _I32, _P]),
+    "mdm_linear_xattn_forward": (_I32, [_P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _I64, _I32, _P]),
+    "mdm_softmax_xattn_ffn_forward": (_I32, [_P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _I64, _I32, _P]),
+    "mdm_performer_attn_forward": (_I32, [_P, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64, _I32, _P]),
+    "mdm_stylization_forward": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P]),
+    "mdm_stem_embeddings": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _I64, _I32, _P]),
+    "mdm_cfg_posterior_step": (_I32, [_P, _P, _P, _P, _I64, _P, _I32, _P, _I32, _F32, _I32, _P, _P, _P]),
+    "mdm_ddim_step": (_I32, [_P, _P, _P, _I64, _P, _I32, _P, _I32, _F32, _I32, _P, _P, _P]),
+    "mdm_fill_timesteps_mapped": (_I32, [_P, _I64, _P, _P, _I32, _P]),
+    "mdm_guided_update": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _I32, _F32, _I32, _P, _P, _P]),
+    "mdm_guided_update_inpaint": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _I32, _F32, _I32, _P, _P, _P]),
+    "mdm_composed_update": (_I32, [_P, _P, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _I32, _F32, _I32, _P, _P, _P]),
+    "mdm_noise_normal": (_I32, [_P, _I64, _I32, _I64, _U64, _P, _I32, _P]),
+    "mdm_noise_normal_ids": (_I32, [_P, _I64, _I32, _P, _U64, _P, _I32, _P]),
+    "mdm_text_head_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32]),
+    "mdm_text_head_forward": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I64, _I32, _P]),
+    "mdm_motion_postprocess": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "mdm_motion_features_max_frames": (_I32, []),
+    "mdm_motion_features": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _F64, _I32, _I32, _P, _P, _P, _P]),
+    "mdm_motion_fk_max_frames": (_I32, []),
+    "mdm_motion_fk": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "mdm_foot_skate_max_frames": (_I32, []),
+    "mdm_foot_skate": (_I32, [_P, _P, _P, _P, _I64, _P, _F64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "mdm_joint_control_max_frames": (_I32, [_I32]),
+    "mdm_joint_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "mdm_joint_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F32, _I32, _P, _I32, _P, _I32, _P]),
+    "mdm_handshake_blend": (_I32, [_P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "mdm_moe_train_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "mdm_moe_ffn_train_forward": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _F32, _U64, _P, _P, _P, _P,
+                                         _I64, _P]),
+    "mdm_moe_ffn_train_backward": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _F32, _U64, _P, _P, _P, _P, _P,
+                                          _I64, _P]),
+    "mdm_sumsq": (_I32, [_P, _I64, _P, _P]),
+    "mdm_adam_step": (_I32, [_P, _P, _P, _P, _I64, _F32, _F32, _F32, _F32, _I32, _P, _F32, _P]),
+    "mdm_xattn_gate": (_I32, [_P, _P, _I32, _P, _P]),
+    "mdm_fill_i64": (_I32, [_P, _I64, _P, _P]),
+    "mdm_add_i32": (_I32, [_P, _I32, _P]),
+    "mdm_set_gemm_variant": (_I32, [_I32]),
+    "mdm_probe_enable": (_I32, [_I32]),
+    "mdm_route_dump": (_I32, [_P, _I64]),
+    "mdm_route_workspace": (_I32, [_P, _I32, _I32, _I32, _P]),
+    "mdm_sd_fold_passes": (_I32, [_I32, _I32, _I32]),
+    "mdm_probe_read": (_I32, [_P, _P, _I32]),
+    "mdm_gru_bidir_workspace_bytes": (_I64, [_I32, _I32]),
+    "mdm_gru_bidir": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I64, _P]),
+    "mdm_eval_pad_rows": (_I32, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "mdm_eval_ln_leaky": (_I32, [_P, _I32, _I32, _P, _P, _F32, _P, _P]),
+    "mdm_eval_matching": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "mdm_eval_center": (_I32, [_P, _I32, _I32, _P, _P, _P]),
+}
+EXPORTS = list(PROTOTYPES)
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -143,23 +224,11 @@ def lib():
             raise MdmError(f"{LIB_PATH} not found: build it with `python motiondiffusion-moe_amd/build.py` "
                            "(hipcc, gfx950). There is no CPU/eager fallback for the denoising path.")
         L = C.CDLL(LIB_PATH)
-        L.mdm_version.restype = C.c_char_p
-        for name in EXPORTS:
-            if name in ("mdm_workspace_bytes", "mdm_text_head_workspace_bytes", "mdm_moe_train_workspace_bytes", "mdm_mlp_stream_elems", "mdm_gemm_stream_elems", "mdm_gemm_stream3_elems", "mdm_gemm_stream1_elems", "mdm_gemm_stream3x_elems", "mdm_gemm_stream3x_group_elems", "mdm_gru_bidir_workspace_bytes"):
-                getattr(L, name).restype = C.c_int64
-            elif name != "mdm_version":
-                getattr(L, name).restype = C.c_int
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
-
-
-# every symbol include/mdm_hip.h declares (checked by tests/test_abi.py)
-EXPORTS = ["mdm_version", "mdm_gemm", "mdm_fused_mlp", "mdm_mlp_stream_elems", "mdm_mlp_stream_pack", "mdm_gemm_stream_elems", "mdm_gemm_stream_pack", "mdm_gemm_stream3_elems", "mdm_gemm_stream3_pack", "mdm_gemm_stream1_elems", "mdm_gemm_stream1_pack", "mdm_gemm_stream3x_elems", "mdm_gemm_stream3x_group_elems", "mdm_gemm_stream3x_pack", "mdm_pack_bf16", "mdm_pack_f16", "mdm_pack_fp8", "mdm_workspace_bytes", "mdm_text_cache_build",
-           "mdm_denoiser_forward", "mdm_stem_cache_build", "mdm_block_forward", "mdm_moe_ffn_forward", "mdm_dual_self_attn_forward", "mdm_linear_xattn_forward",
-           "mdm_softmax_xattn_ffn_forward", "mdm_performer_attn_forward", "mdm_stylization_forward", "mdm_stem_embeddings",
-           "mdm_cfg_posterior_step", "mdm_ddim_step", "mdm_fill_timesteps_mapped", "mdm_guided_update", "mdm_guided_update_inpaint", "mdm_composed_update", "mdm_noise_normal", "mdm_noise_normal_ids", "mdm_text_head_workspace_bytes", "mdm_text_head_forward", "mdm_motion_postprocess", "mdm_motion_features_max_frames", "mdm_motion_features", "mdm_motion_fk_max_frames", "mdm_motion_fk", "mdm_foot_skate_max_frames", "mdm_foot_skate", "mdm_joint_control_max_frames", "mdm_joint_loss_grad", "mdm_joint_guidance", "mdm_handshake_blend", "mdm_xattn_gate", "mdm_fill_i64", "mdm_add_i32", "mdm_set_gemm_variant", "mdm_probe_enable", "mdm_probe_read", "mdm_route_dump", "mdm_route_workspace",
-           "mdm_moe_train_workspace_bytes", "mdm_moe_ffn_train_forward", "mdm_moe_ffn_train_backward", "mdm_sumsq", "mdm_adam_step", "mdm_sd_fold_passes",
-           "mdm_gru_bidir_workspace_bytes", "mdm_gru_bidir", "mdm_eval_pad_rows", "mdm_eval_ln_leaky", "mdm_eval_matching", "mdm_eval_center"]
 
 
 def check(status: int, what: str = "mdm call"):

@@ -44,7 +44,6 @@ The host-side validation of these inputs (``check_*_kwargs``) lives in ``conditi
 from __future__ import annotations
 
 import contextlib
-import ctypes as C
 import enum
 import math
 from typing import Callable, Optional
@@ -678,27 +677,27 @@ class _StepRunner:
         arguments of mdm_joint_guidance (None without control).  Every pointer belongs to a buffer the runner owns for its
         lifetime; the noise pointer and the stream are the launch's.  Plain "cfg" / "ddpm" keep mdm_cfg_posterior_step and
         plain "ddim" mdm_ddim_step; with a coefficient table the three fused entries share their head and tail."""
-        p, i32 = (lambda t: C.c_void_p(L.ptr(t))), C.c_int32
+        p = L.ptr
         x, eps, x0 = p(self.xx), p(self.eps), p(self.x0)  # x_t is rows [0, B) of xx, updated in place
         eps_u = p(self.eps[self.B:] if self.mode in _GUIDED else None)
-        clock = (i32(self.d.num_timesteps), p(self.t_dev), i32(0))  # steps, the device timestep, no immediate one
-        out = (i32(int(self.clip)), x, x0)
+        clock = (self.d.num_timesteps, p(self.t_dev), 0)  # steps, the device timestep, no immediate one
+        out = (int(self.clip), x, x0)
         guide = None
         if self.ctl is not None:
             c = self.ctl
-            guide = (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"]),
-                     i32(self.B), i32(self.T), i32(self.Fe), C.c_float(c["scale"]), i32(c["iters"]), p(self.coef)) + clock
+            guide = (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"]), self.B,
+                     self.T, self.Fe, c["scale"], c["iters"], p(self.coef)) + clock
         if self.coef is None and self.mode == "ddim":
-            return ("mdm_ddim_step", (x, eps), (C.c_int64(self.n), p(self.tab)) + clock + (C.c_float(self.eta),) + out), guide
-        tail = clock + (C.c_float(self.cfg_scale),) + out
+            return ("mdm_ddim_step", (x, eps), (self.n, p(self.tab)) + clock + (self.eta,) + out), guide
+        tail = clock + (self.cfg_scale,) + out
         if self.coef is None:
-            return ("mdm_cfg_posterior_step", (x, eps, eps_u), (C.c_int64(self.n), p(self.tab)) + tail), guide
-        head = (i32(self.K), p(self.cw)) if self.cw is not None else (eps_u,)
-        head = (x, eps) + head + (x0 if self.mode == "cfg_dpmpp" else p(None),)  # x0_prev: the two-step solver only
+            return ("mdm_cfg_posterior_step", (x, eps, eps_u), (self.n, p(self.tab)) + tail), guide
+        head = (self.K, p(self.cw)) if self.cw is not None else (eps_u,)
+        head = (x, eps) + head + (x0 if self.mode == "cfg_dpmpp" else 0,)  # x0_prev: the two-step solver only
         edit = (p(self.known), p(self.mask)) if self.cw is not None or self.known is not None else ()
         name = ("mdm_composed_update" if self.cw is not None else
                 "mdm_guided_update_inpaint" if self.known is not None else "mdm_guided_update")
-        return (name, head, edit + (C.c_int64(self.n), p(self.tab), p(self.coef)) + tail), guide
+        return (name, head, edit + (self.n, p(self.tab), p(self.coef)) + tail), guide
 
     # one step on the current stream: reads self.xx[:B] (x_t), writes x_{t-1} back into it
     def _step(self, use_noise: bool):
@@ -706,8 +705,8 @@ class _StepRunner:
             self._step_on_device(use_noise)
 
     def _step_on_device(self, use_noise: bool):
-        lib, s = L.lib(), C.c_void_p(L.stream_ptr())
-        B, t_dev = self.B, C.c_void_p(self.t_dev.data_ptr())
+        lib, s = L.lib(), L.stream_ptr()
+        B, t_dev = self.B, self.t_dev.data_ptr()
         if use_noise and self.philox is not None:  # step noise = f(seed, global sample, t, element); t read on the device
             self._philox_fill(self.noise, t_dev, 0, s)
         if use_noise and self.hs is not None:  # the owner window's noise in every overlap (host-filled noise too)
@@ -717,36 +716,36 @@ class _StepRunner:
             self.xx[B:].view(self.K, B, self.T, self.Fe).copy_(x.unsqueeze(0).expand(self.K, -1, -1, -1))
         elif self.R == 2 * B:
             self.xx[B:].copy_(x)
-        ts, R = C.c_void_p(self.ts.data_ptr()), C.c_int64(self.R)
+        ts, R = self.ts.data_ptr(), self.R
         if self.tmap is not None:
-            L.check(lib.mdm_fill_timesteps_mapped(ts, R, t_dev, C.c_void_p(self.tmap.data_ptr()),
-                                                  C.c_int32(self.d.num_timesteps), s), "mdm_fill_timesteps_mapped")
+            L.check(lib.mdm_fill_timesteps_mapped(ts, R, t_dev, self.tmap.data_ptr(), self.d.num_timesteps, s),
+                    "mdm_fill_timesteps_mapped")
         else:
             L.check(lib.mdm_fill_i64(ts, R, t_dev, s))
         self._forward(self)
         if self.hs is not None:  # one eps per shared canvas frame, in every row group, before the update reads it
             self._handshake(self.eps, self.R // B, True, s)
         name, head, tail = self._update
-        L.check(getattr(lib, name)(*head, C.c_void_p(self.noise.data_ptr() if use_noise else 0), *tail, s), name)
+        L.check(getattr(lib, name)(*head, self.noise.data_ptr() if use_noise else 0, *tail, s), name)
         if self._guide is not None:  # x0 and x_{t-1} moved down the joint-position loss, before the counter moves
             L.check(lib.mdm_joint_guidance(*self._guide, s), "mdm_joint_guidance")
-        L.check(lib.mdm_add_i32(t_dev, C.c_int32(-1), s))
+        L.check(lib.mdm_add_i32(t_dev, -1, s))
 
     def _handshake(self, buf, groups, blend: bool, s):
         """mdm_handshake_blend over ``groups`` consecutive groups of B rows of ``buf``: the weighted mean of the eps rows
         (``blend``) or the owner's values (copy) written to every window row of each shared frame."""
         h = self.hs
         L.check(L.lib().mdm_handshake_blend(
-            C.c_void_p(buf.data_ptr()), C.c_int32(groups), C.c_int64(self.n), C.c_int32(self.Fe), C.c_int32(h["nshared"]),
-            C.c_void_p(h["offsets"].data_ptr()), C.c_void_p((h["rows"] if blend else h["owner_rows"]).data_ptr()),
-            C.c_void_p(h["weights"].data_ptr() if blend else 0), s), "mdm_handshake_blend")
+            buf.data_ptr(), groups, self.n, self.Fe, h["nshared"], h["offsets"].data_ptr(),
+            (h["rows"] if blend else h["owner_rows"]).data_ptr(), h["weights"].data_ptr() if blend else 0, s),
+            "mdm_handshake_blend")
 
     def _start(self, x_T):
         """x_T into the model input rows; with handshakes each overlap takes its owner window's values."""
         self.xx[:self.B].copy_(x_T.to(self.dev, torch.float32))
         if self.hs is not None:
             with torch.cuda.device(self.dev):
-                self._handshake(self.xx, 1, False, C.c_void_p(L.stream_ptr()))
+                self._handshake(self.xx, 1, False, L.stream_ptr())
 
     def _needs_noise(self) -> bool:
         if self.mode == "cfg_dpmpp":
@@ -785,13 +784,12 @@ class _StepRunner:
         """out[row] = noise(seed, global sample of that row, stream): rows are consecutive samples (first + row) or carry
         explicit global indices (self.philox = (seed, int64 device tensor))."""
         seed, first = self.philox
-        lib, per = L.lib(), C.c_int64(self.T * self.Fe)
+        lib, per = L.lib(), self.T * self.Fe
         if torch.is_tensor(first):
-            L.check(lib.mdm_noise_normal_ids(C.c_void_p(out.data_ptr()), per, C.c_int32(self.B), C.c_void_p(first.data_ptr()),
-                                             C.c_uint64(seed), stream_dev, C.c_int32(stream_imm), s), "mdm_noise_normal_ids")
+            L.check(lib.mdm_noise_normal_ids(out.data_ptr(), per, self.B, first.data_ptr(), seed, stream_dev, stream_imm, s),
+                    "mdm_noise_normal_ids")
         else:
-            L.check(lib.mdm_noise_normal(C.c_void_p(out.data_ptr()), per, C.c_int32(self.B), C.c_int64(first),
-                                         C.c_uint64(seed), stream_dev, C.c_int32(stream_imm), s), "mdm_noise_normal")
+            L.check(lib.mdm_noise_normal(out.data_ptr(), per, self.B, first, seed, stream_dev, stream_imm, s), "mdm_noise_normal")
 
     def draw_xT(self, seed: int, first=0):
         """x_T for rows [first, first + B) of a global batch (or the rows whose global indices `first` lists): the
@@ -800,7 +798,7 @@ class _StepRunner:
         keep = self.philox
         self.philox = (int(seed) & 0xFFFFFFFFFFFFFFFF, self._ids(first))
         with torch.cuda.device(self.dev):
-            self._philox_fill(out, C.c_void_p(0), L.NOISE_STREAM_XT, C.c_void_p(L.stream_ptr()))
+            self._philox_fill(out, 0, L.NOISE_STREAM_XT, L.stream_ptr())
         self.philox = keep
         return out
 

@@ -4,7 +4,6 @@ the 512 x 512 matrix square root's trace on the host in fp64), Diversity and Mul
 diagonal of mdm_eval_matching on the drawn rows)."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import numpy as np
@@ -27,9 +26,8 @@ def _match(text: torch.Tensor, motion: torch.Tensor, with_dist: bool = False):
     rank = torch.empty(B, dtype=torch.int32, device=text.device)
     diag = torch.empty(B, dtype=torch.float32, device=text.device)
     dist = torch.empty(B, B, dtype=torch.float32, device=text.device) if with_dist else None
-    L.check(L.lib().mdm_eval_matching(C.c_void_p(text.data_ptr()), C.c_void_p(motion.data_ptr()), C.c_int32(B), C.c_int32(D),
-                                      C.c_void_p(L.ptr(dist)), C.c_void_p(rank.data_ptr()), C.c_void_p(diag.data_ptr()),
-                                      C.c_void_p(L.stream_ptr())), "mdm_eval_matching")
+    L.check(L.lib().mdm_eval_matching(text.data_ptr(), motion.data_ptr(), B, D, L.ptr(dist), rank.data_ptr(), diag.data_ptr(),
+                                      L.stream_ptr()), "mdm_eval_matching")
     return (rank, diag, dist) if with_dist else (rank, diag)
 
 
@@ -71,8 +69,7 @@ def activation_stats(emb):
     mean = torch.empty(D, dtype=torch.float32, device=x.device)
     xc = torch.empty_like(x)
     lib = L.lib()
-    L.check(lib.mdm_eval_center(C.c_void_p(x.data_ptr()), C.c_int32(N), C.c_int32(D), C.c_void_p(mean.data_ptr()),
-                                C.c_void_p(xc.data_ptr()), C.c_void_p(L.stream_ptr())), "mdm_eval_center")
+    L.check(lib.mdm_eval_center(x.data_ptr(), N, D, mean.data_ptr(), xc.data_ptr(), L.stream_ptr()), "mdm_eval_center")
     cov = torch.empty(D, D, dtype=torch.float32, device=x.device)
     d = gemm_desc(L.PREC_X3)  # cov[m, n] = sum_k xc[k, m] xc[k, n] / (N - 1): both operands read k-strided
     d.A = f32_operand(xc, D, L.OP_F32_KSTRIDE)

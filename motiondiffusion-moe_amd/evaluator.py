@@ -8,7 +8,6 @@ Their arithmetic runs on the library: every Linear and both k4 s2 p1 convolution
 csrc/evaluator.hip.  There is no eager fallback."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import numpy as np
@@ -83,16 +82,13 @@ class _BiGRUHead(_Packs):
         nbytes = lib.mdm_gru_bidir_workspace_bytes(B, H)
         ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
         last = torch.empty(B, 2 * H, dtype=torch.float32, device=x.device)
-        L.check(lib.mdm_gru_bidir(C.c_void_p(gx.data_ptr()), C.c_void_p(p["w_hh"].data_ptr()), C.c_void_p(p["b_hh"].data_ptr()),
-                                  C.c_void_p(p["h0"].data_ptr()), C.c_void_p(ld.data_ptr()),
-                                  lh.ctypes.data_as(C.POINTER(C.c_int32)), C.c_int32(B), C.c_int32(T), C.c_int32(H),
-                                  C.c_void_p(last.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_int64(nbytes),
-                                  C.c_void_p(L.stream_ptr())), "mdm_gru_bidir")
+        L.check(lib.mdm_gru_bidir(gx.data_ptr(), p["w_hh"].data_ptr(), p["b_hh"].data_ptr(), p["h0"].data_ptr(), ld.data_ptr(),
+                                  lh.ctypes.data, B, T, H, last.data_ptr(), ws.data_ptr(), nbytes,
+                                  L.stream_ptr()), "mdm_gru_bidir")
         y = linear(last, *p["o0"], precision=PREC)
         lw, lb, eps = p["ln"]
-        L.check(lib.mdm_eval_ln_leaky(C.c_void_p(y.data_ptr()), C.c_int32(B), C.c_int32(H), C.c_void_p(lw.data_ptr()),
-                                      C.c_void_p(lb.data_ptr()), C.c_float(eps), C.c_void_p(y.data_ptr()),
-                                      C.c_void_p(L.stream_ptr())), "mdm_eval_ln_leaky")
+        L.check(lib.mdm_eval_ln_leaky(y.data_ptr(), B, H, lw.data_ptr(), lb.data_ptr(), eps, y.data_ptr(), L.stream_ptr()),
+                "mdm_eval_ln_leaky")
         return linear(y, *p["o3"], precision=PREC)
 
 
@@ -131,9 +127,8 @@ class MovementConvEncoder(_Packs):
         w, bias, Cp = pk
         lib = L.lib()
         padded = torch.empty(B, T + 2, Cp, dtype=torch.float32, device=src.device)
-        L.check(lib.mdm_eval_pad_rows(C.c_void_p(src.data_ptr()), C.c_int64(ld_src), C.c_int32(B), C.c_int32(T), C.c_int32(Cin),
-                                      C.c_int32(Cp), C.c_int32(1), C.c_int32(int(leaky_in)), C.c_void_p(padded.data_ptr()),
-                                      C.c_void_p(L.stream_ptr())), "mdm_eval_pad_rows")
+        L.check(lib.mdm_eval_pad_rows(src.data_ptr(), ld_src, B, T, Cin, Cp, 1, int(leaky_in), padded.data_ptr(), L.stream_ptr()),
+                "mdm_eval_pad_rows")
         To = T // 2
         out = torch.empty(B * To, w.N, dtype=torch.float32, device=src.device)
         d = gemm_desc(PREC)
@@ -164,9 +159,8 @@ class MovementConvEncoder(_Packs):
         h2 = self._conv(h1, h1.shape[1], B, T1, h1.shape[1], p["c3"], True)  # LeakyReLU of conv 1 in the pad copy
         T2 = T1 // 2
         O = h2.shape[1]
-        L.check(L.lib().mdm_eval_pad_rows(C.c_void_p(h2.data_ptr()), C.c_int64(O), C.c_int32(B), C.c_int32(T2), C.c_int32(O),
-                                          C.c_int32(O), C.c_int32(0), C.c_int32(1), C.c_void_p(h2.data_ptr()),
-                                          C.c_void_p(L.stream_ptr())), "mdm_eval_pad_rows")  # LeakyReLU of conv 2, in place
+        L.check(L.lib().mdm_eval_pad_rows(h2.data_ptr(), O, B, T2, O, O, 0, 1, h2.data_ptr(), L.stream_ptr()),
+                "mdm_eval_pad_rows")  # LeakyReLU of conv 2, in place
         return linear(h2, *p["out"], precision=PREC).reshape(B, T2, -1)
 
     def forward(self, inputs):

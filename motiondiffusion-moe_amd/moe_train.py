@@ -145,11 +145,9 @@ class MoEFFNTrainer:
         mask_seed = (self.seed + self.step_count + rank * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
         with torch.cuda.device(self.device):
             L.check(L.lib().mdm_moe_ffn_train_forward(
-                C.byref(self.params.struct), self.D, self.F, self.E, self.Te, De, C.c_void_p(L.ptr(ew)), C.c_void_p(L.ptr(eb)),
-                C.c_void_p(x.data_ptr()), C.c_void_p(emb.data_ptr()), B, S, C.c_float(self.dropout), C.c_uint64(mask_seed),
-                C.c_void_p(out.data_ptr()),
-                C.c_void_p(self.lb_loss.data_ptr()), C.c_void_p(L.ptr(route_out)), C.c_void_p(ws.data_ptr()), C.c_int64(ws.numel()),
-                C.c_void_p(L.stream_ptr())), "mdm_moe_ffn_train_forward")
+                C.byref(self.params.struct), self.D, self.F, self.E, self.Te, De, L.ptr(ew), L.ptr(eb), x.data_ptr(),
+                emb.data_ptr(), B, S, self.dropout, mask_seed, out.data_ptr(), self.lb_loss.data_ptr(), L.ptr(route_out),
+                ws.data_ptr(), ws.numel(), L.stream_ptr()), "mdm_moe_ffn_train_forward")
         self._saved = (x, emb, ew, B, S, De, mask_seed)
         return out
 
@@ -166,11 +164,9 @@ class MoEFFNTrainer:
         dx, demb = torch.empty_like(x), torch.empty_like(emb)
         with torch.cuda.device(self.device):
             L.check(L.lib().mdm_moe_ffn_train_backward(
-                C.byref(self.params.struct), self.D, self.F, self.E, self.Te, De, C.c_void_p(L.ptr(ew)), C.c_void_p(x.data_ptr()),
-                C.c_void_p(emb.data_ptr()), B, S, C.c_float(self.dropout), C.c_uint64(mask_seed), C.c_void_p(dout.data_ptr()),
-                C.c_void_p(dx.data_ptr()),
-                C.c_void_p(demb.data_ptr()), C.byref(self.grads.struct), C.c_void_p(self._ws.data_ptr()),
-                C.c_int64(self._ws.numel()), C.c_void_p(L.stream_ptr())), "mdm_moe_ffn_train_backward")
+                C.byref(self.params.struct), self.D, self.F, self.E, self.Te, De, L.ptr(ew), x.data_ptr(), emb.data_ptr(), B, S,
+                self.dropout, mask_seed, dout.data_ptr(), dx.data_ptr(), demb.data_ptr(), C.byref(self.grads.struct),
+                self._ws.data_ptr(), self._ws.numel(), L.stream_ptr()), "mdm_moe_ffn_train_backward")
         self._saved = None
         return dx, demb
 
@@ -185,13 +181,10 @@ class MoEFFNTrainer:
         lib, n = L.lib(), self.params.flat.numel()
         with torch.cuda.device(self.device):
             sp = L.stream_ptr()
-            L.check(lib.mdm_sumsq(C.c_void_p(self.grads.flat.data_ptr()), C.c_int64(n), C.c_void_p(self._sumsq.data_ptr()),
-                                  C.c_void_p(sp)), "mdm_sumsq")
-            L.check(lib.mdm_adam_step(C.c_void_p(self.params.flat.data_ptr()), C.c_void_p(self.grads.flat.data_ptr()),
-                                      C.c_void_p(self.adam_m.data_ptr()), C.c_void_p(self.adam_v.data_ptr()), C.c_int64(n),
-                                      C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
-                                      C.c_int32(self.step_count), C.c_void_p(self._sumsq.data_ptr()), C.c_float(self.max_norm),
-                                      C.c_void_p(sp)), "mdm_adam_step")
+            L.check(lib.mdm_sumsq(self.grads.flat.data_ptr(), n, self._sumsq.data_ptr(), sp), "mdm_sumsq")
+            L.check(lib.mdm_adam_step(self.params.flat.data_ptr(), self.grads.flat.data_ptr(), self.adam_m.data_ptr(),
+                                      self.adam_v.data_ptr(), n, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count,
+                                      self._sumsq.data_ptr(), self.max_norm, sp), "mdm_adam_step")
 
     def grad_norm(self) -> float:
         return float(self._sumsq.sqrt().item())

@@ -15,7 +15,6 @@ denoiser.  J follows from the feature width F = 12J - 1 (263 -> 22, 251 -> 21).
 the loss and its gradient on the device (``mdm_joint_loss_grad``)."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Iterable, Sequence
 
 import numpy as np
@@ -130,7 +129,6 @@ def joint_loss_grad(x0: torch.Tensor, lengths, mean, std, targets, weights):
     grad = torch.empty_like(x)
     with torch.cuda.device(dev):
         L.check(L.lib().mdm_joint_loss_grad(
-            C.c_void_p(x.data_ptr()), C.c_void_p(ln.data_ptr()), C.c_void_p(mean_t.data_ptr()), C.c_void_p(std_t.data_ptr()),
-            C.c_void_p(tg.data_ptr()), C.c_void_p(w.data_ptr()), C.c_int32(B), C.c_int32(T), C.c_int32(F),
-            C.c_void_p(loss.data_ptr()), C.c_void_p(grad.data_ptr()), C.c_void_p(L.stream_ptr())), "mdm_joint_loss_grad")
+            x.data_ptr(), ln.data_ptr(), mean_t.data_ptr(), std_t.data_ptr(), tg.data_ptr(), w.data_ptr(), B, T, F, loss.data_ptr(),
+            grad.data_ptr(), L.stream_ptr()), "mdm_joint_loss_grad")
     return loss, grad

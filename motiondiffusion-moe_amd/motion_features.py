@@ -193,10 +193,8 @@ def joints_to_motion(joints, lengths=None, mean=None, std=None, *, skeleton="t2m
     s = _skeleton_struct(sk)
     with torch.cuda.device(dev):
         L.check(L.lib().mdm_motion_features(
-            C.c_void_p(x.data_ptr()), C.c_void_p(L.ptr(ln)), C.c_void_p(L.ptr(mean_t)), C.c_void_p(L.ptr(std_t)), C.byref(s),
-            C.c_void_p(L.ptr(tgt)), C.c_int32(B), C.c_int32(T), C.c_double(feet_thre), C.c_int32(1 if canonicalize else 0),
-            C.c_int32(len(w) - 1), C.c_void_p(w_t.data_ptr()), C.c_void_p(L.ptr(pos)), C.c_void_p(out.data_ptr()),
-            C.c_void_p(L.stream_ptr())), "mdm_motion_features")
+            x.data_ptr(), L.ptr(ln), L.ptr(mean_t), L.ptr(std_t), C.byref(s), L.ptr(tgt), B, T, feet_thre, 1 if canonicalize else 0,
+            len(w) - 1, w_t.data_ptr(), L.ptr(pos), out.data_ptr(), L.stream_ptr()), "mdm_motion_features")
     return (out, pos if canonicalize else x) if return_positions else out
 
 

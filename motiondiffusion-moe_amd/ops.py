@@ -32,9 +32,8 @@ class PackedWeight:
             self.hi = torch.empty((w2.shape[0], kp), dtype=torch.uint8, device=w.device)
             self.lo = torch.empty((w2.shape[0],), dtype=torch.float32, device=w.device)
             with torch.cuda.device(w.device):
-                L.check(L.lib().mdm_pack_fp8(C.c_void_p(w2.data_ptr()), C.c_int64(k), C.c_int64(w2.shape[0]), C.c_int64(k),
-                                             C.c_void_p(self.hi.data_ptr()), C.c_int64(kp), C.c_void_p(self.lo.data_ptr()),
-                                             C.c_void_p(L.stream_ptr())), "mdm_pack_fp8")
+                L.check(L.lib().mdm_pack_fp8(w2.data_ptr(), k, w2.shape[0], k, self.hi.data_ptr(), kp, self.lo.data_ptr(),
+                                             L.stream_ptr()), "mdm_pack_fp8")
             return
         w = w.detach().to(torch.float32)
         lead = w.shape[:-2]
@@ -46,13 +45,11 @@ class PackedWeight:
         self.lo = torch.empty_like(self.hi) if with_lo else None
         with torch.cuda.device(w.device):
             if fmt == "f16":
-                L.check(L.lib().mdm_pack_f16(C.c_void_p(w2.data_ptr()), C.c_int64(k), C.c_int64(w2.shape[0]), C.c_int64(k),
-                                             C.c_void_p(self.hi.data_ptr()), C.c_int64(kp), C.c_void_p(L.stream_ptr())),
+                L.check(L.lib().mdm_pack_f16(w2.data_ptr(), k, w2.shape[0], k, self.hi.data_ptr(), kp, L.stream_ptr()),
                         "mdm_pack_f16")
             else:
-                L.check(L.lib().mdm_pack_bf16(C.c_void_p(w2.data_ptr()), C.c_int64(k), C.c_int64(w2.shape[0]), C.c_int64(k),
-                                              C.c_void_p(self.hi.data_ptr()), C.c_void_p(L.ptr(self.lo)), C.c_int64(kp),
-                                              C.c_void_p(L.stream_ptr())), "mdm_pack_bf16")
+                L.check(L.lib().mdm_pack_bf16(w2.data_ptr(), k, w2.shape[0], k, self.hi.data_ptr(), L.ptr(self.lo), kp,
+                                              L.stream_ptr()), "mdm_pack_bf16")
         self.lead = tuple(lead)
 
     def operand(self, row_offset: int = 0) -> L.Operand:
@@ -81,7 +78,7 @@ def gemm_desc(precision: int) -> L.GemmDesc:
 
 
 def run_gemm(d: L.GemmDesc):
-    L.check(L.lib().mdm_gemm(C.byref(d), C.c_void_p(L.stream_ptr())), "mdm_gemm")
+    L.check(L.lib().mdm_gemm(C.byref(d), L.stream_ptr()), "mdm_gemm")
 
 
 def linear(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor] = None, *, act: int = L.ACT_NONE,
@@ -174,13 +171,12 @@ def mlp_stream_pack(w1: torch.Tensor, w2: torch.Tensor, dtype: torch.dtype) -> t
     assert w2.shape == (G, Dout, F) and dtype in (torch.float16, torch.bfloat16)
     w1 = w1.detach().to(torch.float32).contiguous()
     w2 = w2.detach().to(torch.float32).contiguous()
-    n = L.lib().mdm_mlp_stream_elems(C.c_int32(G), C.c_int32(F), C.c_int32(Din), C.c_int32(Dout))
+    n = L.lib().mdm_mlp_stream_elems(G, F, Din, Dout)
     out = torch.empty(n, dtype=dtype, device=w1.device)
     with torch.cuda.device(w1.device):
-        L.check(L.lib().mdm_mlp_stream_pack(C.c_void_p(w1.data_ptr()), C.c_void_p(w2.data_ptr()), C.c_int32(G), C.c_int32(F),
-                                            C.c_int32(Din), C.c_int32(Dout),
-                                            C.c_int32(L.H16_F16 if dtype == torch.float16 else L.H16_BF16),
-                                            C.c_void_p(out.data_ptr()), C.c_void_p(L.stream_ptr())), "mdm_mlp_stream_pack")
+        L.check(L.lib().mdm_mlp_stream_pack(w1.data_ptr(), w2.data_ptr(), G, F, Din, Dout,
+                                            L.H16_F16 if dtype == torch.float16 else L.H16_BF16, out.data_ptr(), L.stream_ptr()),
+                "mdm_mlp_stream_pack")
     return out
 
 
@@ -189,15 +185,14 @@ def gemm_stream_pack(w: torch.Tensor, dtype: torch.dtype) -> Optional[torch.Tens
     is not taken (N = K = 512 only)."""
     L.require_cuda(w)
     N, K = w.shape
-    n = L.lib().mdm_gemm_stream_elems(C.c_int32(N), C.c_int32(K))
+    n = L.lib().mdm_gemm_stream_elems(N, K)
     if n <= 0:
         return None
     w = w.detach().to(torch.float32).contiguous()
     out = torch.empty(n, dtype=dtype, device=w.device)
     with torch.cuda.device(w.device):
-        L.check(L.lib().mdm_gemm_stream_pack(C.c_void_p(w.data_ptr()), C.c_int32(N), C.c_int32(K),
-                                             C.c_int32(L.H16_F16 if dtype == torch.float16 else L.H16_BF16),
-                                             C.c_void_p(out.data_ptr()), C.c_void_p(L.stream_ptr())), "mdm_gemm_stream_pack")
+        L.check(L.lib().mdm_gemm_stream_pack(w.data_ptr(), N, K, L.H16_F16 if dtype == torch.float16 else L.H16_BF16,
+                                             out.data_ptr(), L.stream_ptr()), "mdm_gemm_stream_pack")
     return out
 
 
@@ -206,15 +201,14 @@ def gemm_stream1_pack(w: torch.Tensor, dtype: torch.dtype) -> Optional[torch.Ten
     MdmGemmDesc.w_stream / MdmPacked.ws); None when the shape is not covered (N % 256, K % 256)."""
     L.require_cuda(w)
     N, K = w.shape
-    n = L.lib().mdm_gemm_stream1_elems(C.c_int32(N), C.c_int32(K))
+    n = L.lib().mdm_gemm_stream1_elems(N, K)
     if n <= 0:
         return None
     w = w.detach().to(torch.float32).contiguous()
     out = torch.empty(n, dtype=dtype, device=w.device)
     with torch.cuda.device(w.device):
-        L.check(L.lib().mdm_gemm_stream1_pack(C.c_void_p(w.data_ptr()), C.c_int64(K), C.c_int32(N), C.c_int32(K),
-                                              C.c_int32(L.H16_F16 if dtype == torch.float16 else L.H16_BF16),
-                                              C.c_void_p(out.data_ptr()), C.c_void_p(L.stream_ptr())), "mdm_gemm_stream1_pack")
+        L.check(L.lib().mdm_gemm_stream1_pack(w.data_ptr(), K, N, K, L.H16_F16 if dtype == torch.float16 else L.H16_BF16,
+                                              out.data_ptr(), L.stream_ptr()), "mdm_gemm_stream1_pack")
     return out
 
 
@@ -224,14 +218,13 @@ def gemm_stream3x_pack(w: torch.Tensor) -> Optional[torch.Tensor]:
     L.require_cuda(w)
     w3 = w if w.dim() == 3 else w[None]
     G, N, K = w3.shape
-    n = L.lib().mdm_gemm_stream3x_elems(C.c_int32(G), C.c_int32(N), C.c_int32(K))
+    n = L.lib().mdm_gemm_stream3x_elems(G, N, K)
     if n <= 0:
         return None
     w3 = w3.detach().to(torch.float32).contiguous()
     out = torch.empty(n, dtype=torch.bfloat16, device=w.device)
     with torch.cuda.device(w.device):
-        L.check(L.lib().mdm_gemm_stream3x_pack(C.c_void_p(w3.data_ptr()), C.c_int64(K), C.c_int32(G), C.c_int32(N), C.c_int32(K),
-                                               C.c_void_p(out.data_ptr()), C.c_void_p(L.stream_ptr())), "mdm_gemm_stream3x_pack")
+        L.check(L.lib().mdm_gemm_stream3x_pack(w3.data_ptr(), K, G, N, K, out.data_ptr(), L.stream_ptr()), "mdm_gemm_stream3x_pack")
     return out
 
 
@@ -240,14 +233,13 @@ def gemm_stream3_pack(w: torch.Tensor) -> Optional[torch.Tensor]:
     (csrc/style_gemm.hip style_gemm3); None when the shape is not taken (N = K = 512 only)."""
     L.require_cuda(w)
     N, K = w.shape
-    n = L.lib().mdm_gemm_stream3_elems(C.c_int32(N), C.c_int32(K))
+    n = L.lib().mdm_gemm_stream3_elems(N, K)
     if n <= 0:
         return None
     w = w.detach().to(torch.float32).contiguous()
     out = torch.empty(n, dtype=torch.bfloat16, device=w.device)
     with torch.cuda.device(w.device):
-        L.check(L.lib().mdm_gemm_stream3_pack(C.c_void_p(w.data_ptr()), C.c_int32(N), C.c_int32(K), C.c_void_p(out.data_ptr()),
-                                              C.c_void_p(L.stream_ptr())), "mdm_gemm_stream3_pack")
+        L.check(L.lib().mdm_gemm_stream3_pack(w.data_ptr(), N, K, out.data_ptr(), L.stream_ptr()), "mdm_gemm_stream3_pack")
     return out
 
 
@@ -319,5 +311,5 @@ def fused_mlp(x16: torch.Tensor, w1: PackedWeight, b1: Optional[torch.Tensor], w
     if out16 is not None:
         assert out is None or out16.stride(0) == out.stride(0)
         d.C16, d.ldc = out16.data_ptr(), out16.stride(0)
-    L.check(L.lib().mdm_fused_mlp(C.byref(d), C.c_void_p(L.stream_ptr())), "mdm_fused_mlp")
+    L.check(L.lib().mdm_fused_mlp(C.byref(d), L.stream_ptr()), "mdm_fused_mlp")
     return out if out is not None else out16

@@ -310,9 +310,8 @@ class PackedModel:
             setattr(l, nm + "_b", V[k + nm + "_b"].data_ptr())
         l.sd_q_w32, l.sd_out_w32 = V[k + "sd_q_w32"].data_ptr(), V[k + "sd_out_w32"].data_ptr()
         gvec = torch.empty(D, dtype=torch.float32, device=V[k + "ca_gate"].device)
-        L.check(L.lib().mdm_xattn_gate(C.c_void_p(V[k + "ca_gate"].data_ptr()), C.c_void_p(V[k + "ca_adaptive"].data_ptr()),
-                                       C.c_int32(D), C.c_void_p(gvec.data_ptr()), C.c_void_p(L.stream_ptr())),
-                "mdm_xattn_gate")
+        L.check(L.lib().mdm_xattn_gate(V[k + "ca_gate"].data_ptr(), V[k + "ca_adaptive"].data_ptr(), D, gvec.data_ptr(),
+                                       L.stream_ptr()), "mdm_xattn_gate")
         V[k + "ca_gvec"] = gvec
         l.ca_gvec = gvec.data_ptr()
         self._style(l.ca_style, k + "ca_style.")

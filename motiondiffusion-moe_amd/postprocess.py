@@ -54,9 +54,8 @@ def motion_to_joints(motion: torch.Tensor, mean, std, lengths: Optional[torch.Te
     out = torch.empty_like(scratch)
     with torch.cuda.device(dev):
         L.check(L.lib().mdm_motion_postprocess(
-            C.c_void_p(x.data_ptr()), C.c_void_p(L.ptr(ln)), C.c_void_p(mean_t.data_ptr()), C.c_void_p(std_t.data_ptr()),
-            C.c_int32(B), C.c_int32(T), C.c_int32(Fe), C.c_int32(joints_num), C.c_int32(radius), C.c_void_p(w_t.data_ptr()),
-            C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(L.stream_ptr())), "mdm_motion_postprocess")
+            x.data_ptr(), L.ptr(ln), mean_t.data_ptr(), std_t.data_ptr(), B, T, Fe, joints_num, radius, w_t.data_ptr(),
+            scratch.data_ptr(), out.data_ptr(), L.stream_ptr()), "mdm_motion_postprocess")
     return out
 
 
@@ -140,11 +139,9 @@ def motion_to_joints_fk(motion: torch.Tensor, mean, std, lengths: Optional[torch
     s = _skeleton_struct(sk)
     with torch.cuda.device(dev):
         L.check(L.lib().mdm_motion_fk(
-            C.c_void_p(x.data_ptr()), C.c_void_p(L.ptr(ln)), C.c_void_p(mean_t.data_ptr()), C.c_void_p(std_t.data_ptr()),
-            C.byref(s), C.c_void_p(L.ptr(off_t)), C.c_int32(1 if off_t is not None and off_t.dim() == 3 else 0), C.c_int32(B),
-            C.c_int32(T), C.c_int32(Fe), C.c_int32(radius), C.c_void_p(w_t.data_ptr()), C.c_void_p(L.ptr(scratch)),
-            C.c_void_p(out.data_ptr()), C.c_void_p(L.ptr(rot)), C.c_void_p(L.ptr(used)), C.c_void_p(L.stream_ptr())),
-            "mdm_motion_fk")
+            x.data_ptr(), L.ptr(ln), mean_t.data_ptr(), std_t.data_ptr(), C.byref(s), L.ptr(off_t),
+            1 if off_t is not None and off_t.dim() == 3 else 0, B, T, Fe, radius, w_t.data_ptr(), L.ptr(scratch), out.data_ptr(),
+            L.ptr(rot), L.ptr(used), L.stream_ptr()), "mdm_motion_fk")
     res = (out,) + ((rot,) if return_rotations else ()) + ((used,) if return_offsets else ())
     return res if len(res) > 1 else out
 
@@ -292,9 +289,7 @@ def remove_foot_skate(joints, lengths=None, contacts=None, *, skeleton="t2m", fe
     s = _skeleton_struct(sk)
     with torch.cuda.device(dev):
         L.check(L.lib().mdm_foot_skate(
-            C.c_void_p(x.data_ptr()), C.c_void_p(L.ptr(ln)), C.byref(s), C.c_void_p(cptr), C.c_int64(stride), thre_c,
-            C.c_double(feet_thre), C.c_int32(int(blend)), C.c_int32(B), C.c_int32(T), C.c_void_p(L.ptr(rot)),
-            C.c_void_p(out.data_ptr()), C.c_void_p(L.ptr(rot_out)), C.c_void_p(L.ptr(slide)), C.c_void_p(L.ptr(pairs)),
-            C.c_void_p(scratch.data_ptr()), C.c_void_p(L.stream_ptr())), "mdm_foot_skate")
+            x.data_ptr(), L.ptr(ln), C.byref(s), cptr, stride, thre_c, feet_thre, int(blend), B, T, L.ptr(rot), out.data_ptr(),
+            L.ptr(rot_out), L.ptr(slide), L.ptr(pairs), scratch.data_ptr(), L.stream_ptr()), "mdm_foot_skate")
     res = (out,) + ((rot_out,) if rot is not None else ()) + (((slide, pairs),) if return_slide else ())
     return res if len(res) > 1 else out

@@ -270,7 +270,7 @@ class MotionTransformer(nn.Module):
 
     def workspace_bytes(self, B: int, T: int, N: int) -> int:
         pm = self.pack()
-        need = L.lib().mdm_workspace_bytes(C.byref(pm.model), C.c_int32(B), C.c_int32(T), C.c_int32(N))
+        need = L.lib().mdm_workspace_bytes(C.byref(pm.model), B, T, N)
         if need < 0:
             raise L.MdmError("unsupported model shape for the HIP path")
         return int(need)
@@ -330,9 +330,8 @@ class MotionTransformer(nn.Module):
             tc.sd_kfold, tc.sd_cb, tc.sd_vfold = (t.data_ptr() for t in fold)
         ws = self._workspace(B, 2, N)
         with torch.cuda.device(dev):  # launches go to the current stream OF THE MODEL'S DEVICE, whatever device is current
-            L.check(L.lib().mdm_text_cache_build(C.byref(pm.model), C.c_void_p(xf_out.data_ptr()), C.byref(tc),
-                                                 C.c_void_p(ws.data_ptr()), C.c_int64(ws.numel()), C.c_int32(self.precision),
-                                                 C.c_void_p(L.stream_ptr())), "mdm_text_cache_build")
+            L.check(L.lib().mdm_text_cache_build(C.byref(pm.model), xf_out.data_ptr(), C.byref(tc), ws.data_ptr(), ws.numel(),
+                                                 self.precision, L.stream_ptr()), "mdm_text_cache_build")
         cache = {"key": key, "tc": tc, "keep": (at, sk, sv, xf_out, nt_dev) + fold, "B": B, "N": N, "pm": pm}
         if not private:
             self._text_cache = cache
@@ -354,10 +353,9 @@ class MotionTransformer(nn.Module):
         gx = torch.empty((xp.shape[0], D), dtype=torch.float32, device=dev)
         ws = self._workspace(128, 2, 1)
         with torch.cuda.device(dev):
-            L.check(L.lib().mdm_stem_cache_build(C.byref(pm.model), C.c_int32(steps), C.c_void_p(table.data_ptr() if fill_table else 0),
-                                                 C.c_void_p(xp.data_ptr()), C.c_int32(xp.shape[0]), C.c_void_p(gx.data_ptr()),
-                                                 C.c_void_p(ws.data_ptr()), C.c_int64(ws.numel()), C.c_int32(self.precision),
-                                                 C.c_void_p(L.stream_ptr())), "mdm_stem_cache_build")
+            L.check(L.lib().mdm_stem_cache_build(C.byref(pm.model), steps, table.data_ptr() if fill_table else 0, xp.data_ptr(),
+                                                 xp.shape[0], gx.data_ptr(), ws.data_ptr(), ws.numel(), self.precision,
+                                                 L.stream_ptr()), "mdm_stem_cache_build")
         sc = L.StemCache()
         sc.time_table, sc.gx, sc.steps = table.data_ptr(), gx.data_ptr(), steps
         return {"sc": sc, "keep": (table, gx)}
@@ -406,11 +404,10 @@ class MotionTransformer(nn.Module):
         tr = torch.zeros((2 * self.num_layers, 4, B * T, self.latent_dim), dtype=torch.float32, device=dev) if trace else None
         with torch.cuda.device(dev):
             L.check(L.lib().mdm_denoiser_forward(
-                C.byref(pm.model), C.byref(tcache["tc"]), C.c_void_p(x.data_ptr()), C.c_void_p(ts.data_ptr()),
-                C.c_void_p(ln.data_ptr()), C.c_void_p(xp.data_ptr()), C.c_int32(B), C.c_int32(T), C.c_void_p(out.data_ptr()),
-                C.c_void_p(ws.data_ptr()), C.c_int64(ws.numel()), C.c_void_p(L.ptr(fr)), C.c_void_p(L.ptr(tr)),
-                C.byref(stem_cache["sc"]) if stem_cache is not None else None,
-                C.c_int32(self.precision), C.c_void_p(L.stream_ptr())), "mdm_denoiser_forward")
+                C.byref(pm.model), C.byref(tcache["tc"]), x.data_ptr(), ts.data_ptr(), ln.data_ptr(), xp.data_ptr(), B, T,
+                out.data_ptr(), ws.data_ptr(), ws.numel(), L.ptr(fr), L.ptr(tr),
+                C.byref(stem_cache["sc"]) if stem_cache is not None else None, self.precision, L.stream_ptr()),
+                "mdm_denoiser_forward")
         if trace:
             return out, tr
         return out

@@ -6,7 +6,6 @@ each step reads.  Writes one JSON object (stdout and --out).
 
     timeout -k 10 600 python tools/eval_bench.py [--reps 20] [--out eval_bench.json]"""
 import argparse
-import ctypes as C
 import importlib
 import json
 import os
@@ -71,10 +70,8 @@ def main():
     out = torch.empty(B, 2 * H, device="cuda")
 
     def gru():
-        L.check(lib.mdm_gru_bidir(C.c_void_p(gx.data_ptr()), C.c_void_p(pk["w_hh"].data_ptr()), C.c_void_p(pk["b_hh"].data_ptr()),
-                                  C.c_void_p(pk["h0"].data_ptr()), C.c_void_p(ld.data_ptr()), lh.ctypes.data_as(C.POINTER(C.c_int32)),
-                                  B, T, H, C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_int64(nb),
-                                  C.c_void_p(L.stream_ptr())), "mdm_gru_bidir")
+        L.check(lib.mdm_gru_bidir(gx.data_ptr(), pk["w_hh"].data_ptr(), pk["b_hh"].data_ptr(), pk["h0"].data_ptr(), ld.data_ptr(),
+                                  lh.ctypes.data, B, T, H, out.data_ptr(), ws.data_ptr(), nb, L.stream_ptr()), "mdm_gru_bidir")
 
     med, mn = _time(gru, args.reps)
     step_us = med * 1000 / T

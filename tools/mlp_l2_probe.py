@@ -36,7 +36,7 @@ def run(shared, gathered):
     d.w2, d.ldw2, d.b2 = pw2.hi.data_ptr(), pw2.Kp, b2.data_ptr()
     d.rowscale, d.r1_scale = rs.data_ptr(), 1.0
     d.C16, d.ldc = out16.data_ptr(), D
-    return lambda: L.check(L.lib().mdm_fused_mlp(C.byref(d), C.c_void_p(L.stream_ptr())))
+    return lambda: L.check(L.lib().mdm_fused_mlp(C.byref(d), L.stream_ptr()))
 
 
 for rnd in range(2):

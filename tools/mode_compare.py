@@ -2,7 +2,6 @@
 """Precision modes against the fp32-grade mode (bf16x3) on the bench workload, HIP vs HIP: error, routing decisions that
 differ, optional kernel-selection knobs.   python tools/mode_compare.py [--variants 0,62,...] [--modes 4,2,1]"""
 import argparse
-import ctypes as C
 import importlib
 import os
 import sys
@@ -18,10 +17,10 @@ def run(m, x, t, length, xf_proj, xf_out, L2):
     L = importlib.import_module("motiondiffusion-moe_amd._lib")
     B, T = x.shape[:2]
     dump = torch.full((L2, 2, B * T, 2), -1, dtype=torch.int32, device="cuda")
-    L.lib().mdm_route_dump(C.c_void_p(dump.data_ptr()))
+    L.lib().mdm_route_dump(dump.data_ptr(), dump.numel())
     y = m(x, t, length, xf_proj=xf_proj, xf_out=xf_out).clone()
     torch.cuda.synchronize()
-    L.lib().mdm_route_dump(C.c_void_p(0))
+    L.lib().mdm_route_dump(None, 0)
     return y, dump.sort(-1).values
 
 

@@ -1,7 +1,6 @@
 """The fp32-grade expert GEMMs on the streamed-weight bf16x3 kernel (csrc/gemm_stream3.hip) against the 128 x 128 tile kernel
 (knob 69), interleaved in one process: grouped (16 balanced groups), gathered pre-split rows, W1 + GELU -> pre-split rows and
 W2 * row scale -> fp32, at the full (50176 routed rows) and the half time scale."""
-import ctypes as C
 import importlib
 import os
 import sys
@@ -41,7 +40,7 @@ def main():
             d.W, d.w_stream = pw.operand(), ws.data_ptr()
             d.M, d.N, d.K, d.bias, d.bias_bs, d.act = M, N, K, b.data_ptr(), N, (L.ACT_GELU if act else L.ACT_NONE)
             d.goff, d.ngroups, d.W.bs1 = goff.data_ptr(), G, N * pw.Kp
-            d.w_stream_gs = L.lib().mdm_gemm_stream3x_group_elems(C.c_int32(N), C.c_int32(K))
+            d.w_stream_gs = L.lib().mdm_gemm_stream3x_group_elems(N, K)
             d.ldc = N
             if act:
                 d.Cx2 = ox2.data_ptr()

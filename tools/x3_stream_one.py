@@ -1,6 +1,5 @@
 """One expert-GEMM shape of the fp32-grade mode, 10 launches per kernel (for counter passes): the streamed-weight bf16x3 kernel
 (csrc/gemm_stream3.hip) and the tile kernel (knob 69) on the same operands.  python tools/x3_stream_one.py M N K gelu(0|1)"""
-import ctypes as C
 import importlib
 import os
 import sys
@@ -32,7 +31,7 @@ for v in (0, 69):
         d.W, d.w_stream = pw.operand(), ws.data_ptr()
         d.M, d.N, d.K, d.bias, d.bias_bs, d.act = M, N, K, b.data_ptr(), N, (L.ACT_GELU if act else L.ACT_NONE)
         d.goff, d.ngroups, d.W.bs1 = goff.data_ptr(), G, N * pw.Kp
-        d.w_stream_gs = L.lib().mdm_gemm_stream3x_group_elems(C.c_int32(N), C.c_int32(K))
+        d.w_stream_gs = L.lib().mdm_gemm_stream3x_group_elems(N, K)
         d.ldc = N
         if act:
             d.Cx2 = ox2.data_ptr()
