@@ -509,6 +509,27 @@ int mdm_foot_skate(const float* joints, const int32_t* length, const MdmSkeleton
                    const float* rotations_in, float* joints_out, float* rotations_out, float* slide_out, int32_t* pairs_out,
                    float* scratch, void* stream);
 
+/* Rig export (csrc/motion_rig.hip): global rotations -> the channels of a node tree, retimed.  joints
+ * (B, T, J, 3) and rotations (B, T, J, 3, 3) fp32 in the layout of mdm_motion_fk's outputs (R[c] orients the bone
+ * parent(c) -> c), length (B) int32 or NULL (= T).  The node tree is three host arrays of n_nodes <= 64 entries, parents before
+ * their nodes: parent[n] (the root's is -1, node 0 is the root) and carried[n], the joint whose R is the node's global rotation
+ * G, or -1: G = the parent node's G (the identity at a root that carries nothing).  Output frame k < length_out[b] (device,
+ * (B) int32, or NULL = T_out) lies at source time k den / num in integers: t0 = (k den) / num, frac = ((k den) % num) / num.  Per
+ * node the local rotation G[parent]^T G[node] (the root: its G) at t0 and t0 + 1 -> unit quaternions, w >= 0 -> the second
+ * flipped onto the first one's hemisphere -> slerp at frac (lerp where they nearly coincide) -> normalised -> matrix -> Euler
+ * angles a, b, c of L = R_axis0(a) R_axis1(b) R_axis2(c), axes 0 / 1 / 2 = X / Y / Z, a permutation; where cos b is within
+ * rounding of 0, c = 0 and a takes the rest.  channels_out (B, T_out, 3 + 3 n_nodes): scale * lerp(joint 0 at t0, t0 + 1; frac),
+ * then a, b, c in degrees per node, in node order.  quaternions_out (B, T_out, n_nodes, 4) or NULL: the local (w, x, y, z).
+ * Where frac == 0 frame t0 + 1 is not read and nothing is interpolated: at num == den the result is the frame's own rotation.
+ * Output frames at or past length_out[b], or whose t0 is at or past length[b], are zero; source frames at or past length[b]
+ * are never read.  Any T (no LDS).  MDM_ERR_ARG: a null pointer (length, length_out, quaternions_out excepted), T, J or T_out
+ * < 1, n_nodes outside [1, 64], a parent not smaller than its node, a carried joint outside [-1, J), axes that are no
+ * permutation, num or den < 1, (T_out - 1) den > (T - 1) num (the last output frame past the source). */
+int mdm_rig_channels(const float* joints, const float* rotations, const int32_t* length, int32_t B, int32_t T, int32_t J,
+                     int32_t n_nodes, const int32_t* parent, const int32_t* carried, int32_t axis0, int32_t axis1,
+                     int32_t axis2, float scale, int32_t num, int32_t den, int32_t T_out, const int32_t* length_out,
+                     float* channels_out, float* quaternions_out, void* stream);
+
 /* Joint-position control (csrc/motion_control.hip).  For sample b, with J = (F + 1) / 12 joints (F must be
  * 12 J - 1: 263 -> 22, 251 -> 21), targets G and weights W dense fp32 (B, T, J, 3), W >= 0 and finite, mean / std fp32
  * (B, F) (one row per sample), and P = recover_from_ric(x0 * std + mean) without temporal filter (as mdm_motion_postprocess

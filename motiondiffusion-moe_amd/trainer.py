@@ -12,7 +12,8 @@ weights from ``motion_compose``).  ``edit_joints`` gives the known motion of an 
 ``control_joints`` / ``control_weights`` (with ``mean`` / ``std``) steer joint positions:
 trajectories, keyframes, end positions (targets from ``motion_control``).  ``generate_long`` samples motions longer than
 the model's window from scripts of ``(caption, length)`` segments, overlapping windows tied together on every step
-(``motion_long``).  Every generate method checks its conditioning once (``conditioning.Conditioning``) and
+(``motion_long``).  ``generate_bvh`` / ``generate_long_bvh`` end in BVH text for a rig (``motion_rig``,
+DESIGN.md §19).  Every generate method checks its conditioning once (``conditioning.Conditioning``) and
 samples each batch's rows through ``_sample_rows``.  The training loop (forward/backward/update/train) is out of scope for
 this build and raises.
 """
@@ -304,6 +305,44 @@ class DDPMTrainer(object):
         return self._to_joints(motions, lens, dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True, offsets, True,
                                fix_feet=fix_feet, blend=blend)
 
+    @staticmethod
+    def _to_bvh(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, paths, fps, fps_out, euler, scale):
+        """Rows -> one BVH text per motion: ``_to_joints`` with rotations and no filter, one
+        ``motion_rig.rotations_to_rig`` over the padded batch, ``motion_rig.bvh_text`` per sample."""
+        from .motion_rig import bvh_text, retime_ratio, rig_of, rotations_to_rig
+        res = DDPMTrainer._to_joints(motions, lens, dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True, offsets, True,
+                                     fix_feet=fix_feet, blend=blend)
+        skel = {263: "t2m", 251: "kit"}[dim_pose]
+        rig = rig_of(skel)
+        j = torch.zeros((len(res), max(lens)) + tuple(res[0][0].shape[1:]), device=res[0][0].device)
+        r = torch.zeros(tuple(j.shape[:3]) + (3, 3), device=j.device)
+        for i, (ji, ri, _) in enumerate(res):
+            j[i, :lens[i]], r[i, :lens[i]] = ji, ri
+        chan, lens_out = rotations_to_rig(j, r, torch.tensor(lens), skeleton=skel, euler=euler, fps=fps, fps_out=fps_out,
+                                          scale=scale)
+        num, den, fps = retime_ratio(skel, fps, fps_out)
+        frame_time = den / (num * float(fps))
+        chan, texts = chan.cpu(), []
+        for i, (_, _, o) in enumerate(res):
+            texts.append(bvh_text(rig, o, chan[i], int(lens_out[i]), frame_time, euler=euler, scale=scale))
+            if paths is not None and paths[i] is not None:
+                with open(paths[i], "w") as f:
+                    f.write(texts[-1])
+        return texts
+
+    @torch.no_grad()
+    def generate_bvh(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, paths=None, fps=None, fps_out=None,
+                     euler="ZXY", scale=1.0, offsets=None, fix_feet=False, blend=5, **kw):
+        """``generate`` followed by forward kinematics and the rig export (``motion_rig``): one BVH text per
+        sample, written to ``paths[i]`` where given.  ``fps`` (default 20 at dim_pose 263, 12.5 at 251) / ``fps_out``: retimed
+        to the frame rate a tool works at; ``euler``: the channels' rotation order; ``scale``: of positions and offsets (100
+        for centimetres).  ``offsets`` / ``fix_feet`` / ``blend`` as in ``generate_rotations``, ``**kw`` as for ``generate``."""
+        if paths is not None and len(paths) != len(caption):
+            raise ValueError(f"paths must hold one entry per caption ({len(caption)}), or None")
+        motions = self.generate(caption, m_lens, dim_pose, batch_size, **kw)
+        lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
+        return self._to_bvh(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, paths, fps, fps_out, euler, scale)
+
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
                       sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, noise=None, progress=False,
@@ -398,6 +437,25 @@ class DDPMTrainer(object):
         motions = self.generate_long(scripts, dim_pose, **kw)
         return self._to_joints(motions, [mo.shape[0] for mo in motions], dim_pose, mean, std, joints_num, sigma,
                                from_rotations, offsets, fix_feet=fix_feet, blend=feet_blend)
+
+    @torch.no_grad()
+    def generate_long_bvh(self, scripts, dim_pose, mean, std, *, paths=None, fps=None, fps_out=None, euler="ZXY", scale=1.0,
+                          offsets=None, fix_feet=False, feet_blend=5, **kw):
+        """``generate_long`` followed by forward kinematics over each whole canvas and the rig export, as ``generate_bvh``:
+        one BVH text per motion (at most ``postprocess.fk_max_frames()`` canvas frames).  ``feet_blend`` is ``generate_bvh``'s
+        ``blend`` (``blend`` is ``generate_long``'s here); ``**kw`` as for ``generate_long``."""
+        from .postprocess import fk_max_frames
+        if paths is not None and len(paths) != len(scripts):
+            raise ValueError(f"paths must hold one entry per motion ({len(scripts)}), or None")
+        plans = ML.script_plans(scripts, kw.get("overlap", 20), self._model().num_frames)
+        longest = max(p[3] for p in plans)
+        if longest > fk_max_frames():
+            raise ValueError(f"a canvas of {longest} frames: forward kinematics takes at most {fk_max_frames()} frames")
+        if kw.get("edit_joints") is not None:
+            kw = dict(kw, mean=mean, std=std)
+        motions = self.generate_long(scripts, dim_pose, **kw)
+        return self._to_bvh(motions, [mo.shape[0] for mo in motions], dim_pose, mean, std, offsets, fix_feet, feet_blend, paths,
+                            fps, fps_out, euler, scale)
 
     def save(self, file_name, ep, total_it):
         state = {"opt_encoder": getattr(self, "opt_encoder_state", {}), "ep": ep, "total_it": total_it,
