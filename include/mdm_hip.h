@@ -530,6 +530,31 @@ int mdm_rig_channels(const float* joints, const float* rotations, const int32_t*
                      int32_t axis2, float scale, int32_t num, int32_t den, int32_t T_out, const int32_t* length_out,
                      float* channels_out, float* quaternions_out, void* stream);
 
+/* Rig import (csrc/motion_rig_import.hip): the channel values of a BVH file -> joint positions at picked
+ * nodes, retimed.  values (B, T, C) fp32 on the device: the MOTION rows, zero-padded to T frames; length (B) int32 or NULL (= T).
+ * The node tables are host arrays, parents before their nodes: parent[n] (n_nodes <= 128; the root's is -1, node 0 is the
+ * root), offsets (n_nodes, 3), rot_col / rot_axis (n_nodes, 3): the column and the axis (0 / 1 / 2 = X / Y / Z) of the node's
+ * rotation channels in the order the file lists them, column -1 where it has fewer than three; pos_col[3]: the columns of the
+ * root's X, Y, Z position, or -1; pick[n_pick] (n_pick <= 128): the nodes whose positions are wanted.  A node's local rotation
+ * is L = R_axis0(v0) R_axis1(v1) R_axis2(v2) over its channels, angles in degrees, held as a unit quaternion with w >= 0.
+ * Output frame k < length_out[b] (device, (B) int32, or NULL = T_out) lies at source time k den / num in integers, as in
+ * mdm_rig_channels: where frac == 0 one frame is read and nothing is interpolated, otherwise the local quaternions at t0 and
+ * t0 + 1 are slerped (the second flipped onto the first one's hemisphere, lerp where they nearly coincide) and the root's
+ * position is lerped.  Position of a picked node j: p = OFFSET[j]; for each ancestor a up to the root p = OFFSET[a] + L[a] p;
+ * at the root its position channels are added.  joints_out (B, T_out, n_pick, 3) = scale * basis * p, basis[9] a row-major
+ * 3 x 3 host matrix.  quaternions_out (B, T_out, n_nodes, 4) or NULL: the retimed local (w, x, y, z) of every node.  Output
+ * frames at or past length_out[b], or whose t0 is at or past length[b], are zero; source frames at or past length[b] are
+ * never read.  Any T (no LDS).  MDM_ERR_ARG, before any launch: a null pointer (length, length_out, quaternions_out
+ * excepted), T, T_out or C < 1, C > 32767, n_nodes or n_pick outside [1, 128], a parent not smaller than its node, a chain
+ * deeper than 128, a column outside [-1, C), an axis outside 0..2, a pick outside [0, n_nodes), num or den < 1,
+ * (T_out - 1) den > (T - 1) num (the last output frame past the source), quaternions_out not 16-byte aligned.
+ * MDM_ERR_UNSUPPORTED: B T_out (n_pick + n_nodes) or (T_out - 1) den at or beyond 2^31 (the kernel counts in 32 bits). */
+int mdm_rig_joints(const float* values, const int32_t* length, int32_t B, int32_t T, int32_t C, int32_t n_nodes,
+                   const int32_t* parent, const float* offsets, const int32_t* rot_col, const int32_t* rot_axis,
+                   const int32_t* pos_col, const int32_t* pick, int32_t n_pick, const float* basis, float scale, int32_t num,
+                   int32_t den, int32_t T_out, const int32_t* length_out, float* joints_out, float* quaternions_out,
+                   void* stream);
+
 /* Joint-position control (csrc/motion_control.hip).  For sample b, with J = (F + 1) / 12 joints (F must be
  * 12 J - 1: 263 -> 22, 251 -> 21), targets G and weights W dense fp32 (B, T, J, 3), W >= 0 and finite, mean / std fp32
  * (B, F) (one row per sample), and P = recover_from_ric(x0 * std + mean) without temporal filter (as mdm_motion_postprocess

@@ -253,6 +253,27 @@ def edit_rows_from_joints(edit_joints, mean, std, dim_pose, device=None, to_moti
     return rows, [int(c.shape[0]) - 1 for c in clips]
 
 
+def joint_clips_from_bvh(edit_bvh, bvh_options=None, edit_joints=None, edit_motion=None, device=None):
+    """``edit_bvh``, a list of N BVH texts, paths or parsed files, as the known motion of an edit: the joint clips that
+    ``motion_rig.bvh_to_joints`` reads from them at the model's frame rate, under ``bvh_options`` (its ``joint_map``,
+    ``scale``, ``up``, ``basis`` and ``fps_out``).  The one place where files become clips: from here on they are
+    ``edit_joints``.  Raises ValueError when the known motion is also given as joints or as rows, and for options without
+    files."""
+    if edit_bvh is None:
+        if bvh_options is not None:
+            raise ValueError("bvh_options goes with edit_bvh")
+        return edit_joints
+    if edit_joints is not None or edit_motion is not None:
+        raise ValueError("edit_bvh, edit_joints and edit_motion are exclusive: the known motion is given as files, as joints "
+                         "or as rows")
+    options = dict(bvh_options or {})
+    unknown = sorted(set(options) - {"joint_map", "scale", "up", "basis", "fps_out"})
+    if unknown:
+        raise ValueError(f"bvh_options takes joint_map, scale, up, basis and fps_out, not {unknown}")
+    from .motion_rig import bvh_to_joints
+    return bvh_to_joints(edit_bvh, device=device, **options)
+
+
 def check_joint_edit_mask(mask, rows):
     """``mask`` (N, T, F), expanded, against the row counts of the clips an edit was given as: a clip of n joint frames has
     n - 1 feature rows, so a mask that keeps frame n - 1 or a later one asks for a row that does not exist."""
@@ -289,14 +310,16 @@ class Conditioning:
     broadcast to (N, K, T_w, dim_pose) (T_w its frame dim, 1 when it has none; ``weights``), ``control_joints``
     (N, T_max, J, 3) with ``control_weights`` broadcast to them and ``mean`` / ``std`` as float32 (dim_pose,) (``control``,
     None without).  ``edit_joints`` in place of ``edit_motion``: N joint clips (n_i, J, 3), turned into feature rows once
-    (``edit_rows_from_joints``) and zero-padded to the mask's frames.
+    (``edit_rows_from_joints``) and zero-padded to the mask's frames.  ``edit_bvh`` (with ``bvh_options``) in place of
+    ``edit_joints``: N BVH files, read into joint clips first (``joint_clips_from_bvh``).
     What does not depend on a batch is checked here, once; ``kwargs`` hands out a batch's rows and frames
     (views of these tensors) and checks that they cover its T."""
 
     def __init__(self, captions, dim_pose, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
                  control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,
-                 device=None, to_motion=None):
+                 device=None, to_motion=None, edit_bvh=None, bvh_options=None):
         self.captions, self.dim_pose = captions, dim_pose
+        edit_joints = joint_clips_from_bvh(edit_bvh, bvh_options, edit_joints, edit_motion, device)
         self.weights = None if prompt_weights is None else self._compose(captions, prompt_weights, dim_pose)
         self.edit = None
         rows = None

@@ -7,10 +7,16 @@ global rotation" it gives a broken pose.  ``rig_of`` builds the node tree in whi
 every branching joint (the ``LHipJoint`` / ``LowerBack`` nodes of the CMU files), one per outgoing bone.  On that tree the
 existing rotations are a lossless animation, no IK fit.  The arithmetic (local rotations, quaternions, slerp retiming, Euler
 angles) is in ``mdm_rig_channels`` (csrc/motion_rig.hip); no eager fallback.  ``bvh_text`` / ``write_bvh`` are host code that
-prints numbers and does no arithmetic on the motion."""
+prints numbers and does no arithmetic on the motion.
+
+Rig import is the way back, for any hierarchy: ``parse_bvh`` / ``read_bvh`` (host, no arithmetic) ->
+``resolve_joint_map`` (which node stands for which joint: ``JOINT_MAPS``) -> ``bvh_to_joints``, whose arithmetic (local
+rotations from the channels, slerp retiming, the walk from a node up to the root) is in ``mdm_rig_joints``
+(csrc/motion_rig_import.hip); ``bvh_to_motion`` goes on to feature rows.  No eager fallback either."""
 from __future__ import annotations
 
 import ctypes as C
+import os
 from fractions import Fraction
 from types import SimpleNamespace
 
@@ -22,6 +28,7 @@ from . import _lib as L
 MAX_NODES = 64  # of mdm_rig_channels
 EULER_ORDERS = ("XYZ", "XZY", "YXZ", "YZX", "ZXY", "ZYX")
 DEFAULT_FPS = {"t2m": 20.0, "kit": 12.5}
+MAX_IMPORT_NODES = 128  # of mdm_rig_joints
 
 
 def rig_of(skeleton):
@@ -221,3 +228,413 @@ def write_bvh(path, rig, offsets, channels, n_frames, frame_time, **kw):
     with open(path, "w") as f:
         f.write(text)
     return text
+
+
+# ---- rig import ----
+
+_KEYWORDS = ("ROOT", "JOINT", "END", "{", "}", "OFFSET", "CHANNELS", "MOTION")
+_CHANNELS = {a.lower() + k: (a + k, i, k == "rotation") for i, a in enumerate("XYZ") for k in ("position", "rotation")}
+
+
+def parse_bvh(text):
+    """BVH text -> a namespace: ``names``, ``parent`` (node index, -1 at the root; parents come first), ``offsets`` (N, 3)
+    float64, ``channels`` (per node its channel names, spelled ``Xposition`` ... ``Zrotation``), ``end_sites`` {node: offset},
+    ``rot_col`` / ``rot_axis`` (N, 3) int32: per node the column of ``values`` and the axis (0 / 1 / 2) of each rotation
+    channel in the order the file lists them, column -1 (axis 0) where the node has fewer than three; ``pos_col`` (3,): the
+    columns of the root's X, Y, Z position, or -1; ``frames``, ``frame_time`` and ``values`` (frames, C) float32.  Host code
+    that reads numbers and does no arithmetic on the motion.
+
+    A node has 0 to 3 rotation channels, on any axes and in its own order.  Position channels on a node other than the root
+    count towards the column numbering and are otherwise ignored: the node's OFFSET is used and bones stay rigid (files that
+    write six channels per joint repeat the offset there).  An ``End Site`` owns no channels.  Any whitespace, CRLF line ends,
+    keywords in any letter case, names with ``:`` and a missing final newline are taken; the hierarchy is read token by token
+    (a CHANNELS list may wrap), a MOTION row is a line.  Raises ValueError, with the line number, for a second ROOT, a CHANNELS count that disagrees
+    with its list, an unknown channel name, more than 3 rotation channels on a node, a MOTION row of the wrong width, a row
+    count other than ``Frames:``, a number that does not parse or is not finite, ``Frame Time`` <= 0, more than
+    ``MAX_IMPORT_NODES`` nodes, and a hierarchy that does not parse."""
+    lines = text.splitlines()
+    toks = [(w, i + 1, k == len(ws) - 1) for i, ws in enumerate(ln.split() for ln in lines) for k, w in enumerate(ws)]
+    pos = 0
+
+    def bad(line, what):
+        return ValueError(f"BVH line {line}: {what}")
+
+    def take(what):
+        nonlocal pos
+        if pos >= len(toks):
+            raise bad(len(lines), f"the text ends where {what} is expected")
+        pos += 1
+        return toks[pos - 1]
+
+    def number(what, kind=float):
+        w, line, _ = take(what)
+        try:
+            v = kind(w)
+        except ValueError:
+            raise bad(line, f"{w!r} is not {what}") from None
+        if not np.isfinite(v):
+            raise bad(line, f"{what} {w!r} is not finite")
+        return v, line
+
+    w, line, _ = take("HIERARCHY")
+    if w.upper() != "HIERARCHY":
+        raise bad(line, f"HIERARCHY expected, not {w!r}")
+    names, parent, offsets, channels, ends, rot_col, rot_axis = [], [], [], [], {}, [], []
+    pos_col, stack, pending, width, listed = [-1, -1, -1], [], None, 0, set()
+    while True:
+        w, line, last = take("MOTION")
+        key = w.upper()
+        if key == "MOTION":
+            break
+        if key in ("ROOT", "JOINT"):
+            if key == "ROOT" and names:
+                raise bad(line, "a second ROOT")
+            if key == "JOINT" and not stack:
+                raise bad(line, "JOINT outside the ROOT")
+            if pending is not None or (stack and stack[-1] == "end"):
+                raise bad(line, f"{w!r} where a node cannot start")
+            if len(names) == MAX_IMPORT_NODES:
+                raise bad(line, f"more than {MAX_IMPORT_NODES} nodes")
+            names.append(take("a node's name")[0]), parent.append(stack[-1] if stack else -1), offsets.append(None)
+            channels.append([]), rot_col.append([-1, -1, -1]), rot_axis.append([0, 0, 0])
+            pending = len(names) - 1
+        elif key == "END":
+            if take("Site")[0].upper() != "SITE" or not stack or stack[-1] == "end" or pending is not None:
+                raise bad(line, "a misplaced End Site")
+            pending = "end"
+        elif key == "{":
+            if pending is None:
+                raise bad(line, "'{' without a node")
+            stack.append(pending)
+            pending = None
+        elif key == "}":
+            if not stack or pending is not None:
+                raise bad(line, "'}' without its '{'")
+            if stack[-1] != "end" and offsets[stack[-1]] is None:
+                raise bad(line, f"node {names[stack[-1]]!r} has no OFFSET")
+            stack.pop()
+        elif key == "OFFSET":
+            if not stack or pending is not None:
+                raise bad(line, "OFFSET outside a node")
+            v = np.array([number("an offset")[0] for _ in range(3)], np.float64)
+            if stack[-1] == "end":
+                ends[stack[-2]] = v
+            else:
+                offsets[stack[-1]] = v
+        elif key == "CHANNELS":
+            if not stack or stack[-1] == "end" or pending is not None or stack[-1] in listed:
+                raise bad(line, "CHANNELS outside a node, in an End Site or given twice")
+            node = stack[-1]
+            listed.add(node)
+            count = number("a channel count", int)[0]
+            while pos < len(toks) and (len(channels[node]) < count or toks[pos][0].lower() in _CHANNELS):
+                c = toks[pos][0]
+                if c.lower() not in _CHANNELS:  # the list is over before its count: a keyword, or a name that is no channel
+                    if c.upper() in _KEYWORDS:
+                        break
+                    raise bad(toks[pos][1], f"unknown channel {c!r}")
+                pos += 1
+                name, axis, turns = _CHANNELS[c.lower()]
+                if turns:
+                    k = sum(col >= 0 for col in rot_col[node])
+                    if k == 3:
+                        raise bad(line, f"more than 3 rotation channels on node {names[node]!r}")
+                    rot_col[node][k], rot_axis[node][k] = width, axis
+                elif node == 0:
+                    pos_col[axis] = width
+                channels[node].append(name)
+                width += 1
+            if len(channels[node]) != count:
+                raise bad(line, f"CHANNELS {count} lists {len(channels[node])} channels")
+        else:
+            raise bad(line, f"unexpected {w!r} in the hierarchy")
+    if stack or pending is not None or not names:
+        raise bad(line, "MOTION inside an open node" if names else "MOTION before a ROOT")
+    w, line, _ = take("Frames:")
+    if w.upper() != "FRAMES:":
+        raise bad(line, f"Frames: expected, not {w!r}")
+    frames, line = number("a frame count", int)
+    if frames < 0:
+        raise bad(line, "a negative frame count")
+    w, line, _ = take("Frame Time:")
+    if w.upper() != "FRAME" or take("Time:")[0].upper() != "TIME:":
+        raise bad(line, "Frame Time: expected")
+    frame_time, line = number("a frame time")
+    if not frame_time > 0:
+        raise bad(line, "Frame Time must be > 0")
+    values = np.zeros((frames, width), np.float32)
+    n = 0
+    for i in range(line, len(lines)):  # a row is a line
+        ws = lines[i].split()
+        if not ws:
+            continue
+        if n == frames:
+            raise bad(i + 1, f"more rows than Frames: {frames}")
+        try:
+            row = np.array(ws, dtype=np.float64)
+        except ValueError:
+            raise bad(i + 1, "a MOTION row holds something that is not a number") from None
+        if len(row) != width:
+            raise bad(i + 1, f"a MOTION row of {len(row)} numbers, the hierarchy has {width} channels")
+        if not np.isfinite(row).all():
+            raise bad(i + 1, "a MOTION row holds a number that is not finite")
+        values[n] = row
+        n += 1
+    if n != frames:
+        raise bad(len(lines), f"{n} MOTION rows, Frames: says {frames}")
+    return SimpleNamespace(names=names, parent=parent, offsets=np.stack(offsets), channels=channels, end_sites=ends,
+                           rot_col=np.array(rot_col, np.int32), rot_axis=np.array(rot_axis, np.int32),
+                           pos_col=np.array(pos_col, np.int32), frames=frames, frame_time=frame_time, values=values)
+
+
+def read_bvh(path):
+    """``parse_bvh`` of the file at ``path``."""
+    with open(path, newline="") as f:
+        return parse_bvh(f.read())
+
+
+def _cmu(side):
+    return [side + n for n in ("UpLeg", "Leg", "Foot", "ToeBase", "Shoulder", "Arm", "ForeArm", "Hand")]
+
+
+def _humanoid(spine):
+    """The 22 joints in ``SMPL_JOINTS`` order on the Left / Right naming that the CMU and the Mixamo files share."""
+    l, r = _cmu("Left"), _cmu("Right")
+    return ("Hips", l[0], r[0], spine[0], l[1], r[1], spine[1], l[2], r[2], spine[2], l[3], r[3], spine[3], l[4], r[4],
+            spine[4], l[5], r[5], l[6], r[6], l[7], r[7])
+
+
+def _smpl_names():
+    from .motion_edit import SMPL_JOINTS
+    return tuple(SMPL_JOINTS)
+
+
+# Per preset, the node at which each joint sits, in joint order: "smpl" and "kit" are the names ``rig_of`` gives its own export
+# (22 HumanML3D joints / 21 KIT joints); "cmu" and "mixamo" place the 22 HumanML3D joints on those files' nodes.  ``X/End`` is
+# the End Site of node X.  The CMU files have LowerBack, Neck and the Shoulder nodes at zero offset below Hips and Spine1 (as
+# ``rig_of`` has its helpers), so their spine has five distinct node positions for the six joints pelvis .. head: the preset
+# takes Spine, Spine1, Neck1, Head and Head's End Site, which leaves no bone of the skeleton without length (the collars, at
+# Spine1's position, hang off spine3 at Neck1).
+JOINT_MAPS = {
+    "smpl": _smpl_names(),
+    "kit": tuple(f"joint_{j:02d}" for j in range(21)),
+    "cmu": _humanoid(("Spine", "Spine1", "Neck1", "Head", "Head/End")),
+    "mixamo": _humanoid(("Spine", "Spine1", "Spine2", "Neck", "Head")),
+}
+
+
+def _bare(name):
+    return str(name).rsplit(":", 1)[-1].lower()
+
+
+def resolve_joint_map(bvh, joint_map=None):
+    """-> per joint the index of the node of ``bvh`` (``parse_bvh``'s namespace) it sits at; ``N + n`` stands for the End Site
+    of node n, named ``<node>/End``.  Names match without letter case and with anything up to the last ``:`` stripped
+    (``mixamorig:Hips`` is ``hips``); of nodes that then share a name the first counts.  ``joint_map``: None (the first preset
+    of ``JOINT_MAPS`` whose names are all present), a preset's name, a sequence of node names in joint order, or a dict from
+    joint index or HumanML3D joint name to node name that covers the joints 0 .. J - 1.  Raises ValueError listing the names
+    that the file lacks."""
+    at, N = {}, len(bvh.names)
+    for n, name in enumerate(bvh.names):
+        at.setdefault(_bare(name), n)
+    for n in getattr(bvh, "end_sites", {}):
+        at.setdefault(_bare(bvh.names[n]) + "/end", N + n)
+    if joint_map is None:
+        for wanted in JOINT_MAPS.values():
+            if all(_bare(w) in at for w in wanted):
+                return [at[_bare(w)] for w in wanted]
+        lacks = {k: [w for w in wanted if _bare(w) not in at] for k, wanted in JOINT_MAPS.items()}
+        raise ValueError("no preset of JOINT_MAPS fits the file's nodes: " + "; ".join(f"{k!r} lacks {v}" for k, v in lacks.items()))
+    if isinstance(joint_map, str):
+        if joint_map not in JOINT_MAPS:
+            raise ValueError(f"joint_map must be one of {sorted(JOINT_MAPS)}, a sequence or a dict, not {joint_map!r}")
+        wanted = JOINT_MAPS[joint_map]
+    elif isinstance(joint_map, dict):
+        smpl = {n: i for i, n in enumerate(JOINT_MAPS["smpl"])}
+        by_index = {}
+        for k, v in joint_map.items():
+            if isinstance(k, str) and k not in smpl:
+                raise ValueError(f"joint_map names the joint {k!r}: not one of {JOINT_MAPS['smpl']}")
+            by_index[smpl[k] if isinstance(k, str) else int(k)] = v
+        if sorted(by_index) != list(range(len(by_index))) or not by_index:
+            raise ValueError(f"joint_map must cover the joints 0 .. J - 1, not {sorted(by_index)}")
+        wanted = [by_index[j] for j in range(len(by_index))]
+    else:
+        wanted = list(joint_map)
+    missing = [w for w in wanted if _bare(w) not in at]
+    if missing or not wanted:
+        raise ValueError(f"the file has no node named {missing}" if missing else "joint_map names no joint")
+    return [at[_bare(w)] for w in wanted]
+
+
+def import_tables(bvh, pick):
+    """The node tables ``mdm_rig_joints`` takes for ``pick`` (``resolve_joint_map``'s indices): -> (parent, offsets, rot_col,
+    rot_axis, pick).  A picked End Site becomes a node of its own behind the file's N nodes: its parent the node it ends,
+    its OFFSET the End Site's, no channels.  Raises ValueError for an index that is neither, and beyond ``MAX_IMPORT_NODES``."""
+    N = len(bvh.names)
+    parent, offsets = list(bvh.parent), [np.asarray(o, np.float64) for o in bvh.offsets]
+    extra, out = {}, []
+    for p in pick:
+        p = int(p)
+        if not 0 <= p < 2 * N or (p >= N and p - N not in bvh.end_sites):
+            raise ValueError(f"pick {p}: not a node of the file (0 .. {N - 1}) or N + a node that has an End Site")
+        if p >= N and p not in extra:
+            extra[p] = len(parent)
+            parent.append(p - N), offsets.append(np.asarray(bvh.end_sites[p - N], np.float64))
+        out.append(extra.get(p, p))
+    if len(parent) > MAX_IMPORT_NODES or len(out) > MAX_IMPORT_NODES:
+        raise ValueError(f"{len(parent)} nodes and {len(out)} picked joints: at most {MAX_IMPORT_NODES} of each")
+    pad = len(parent) - N
+    rot_col = np.concatenate([np.asarray(bvh.rot_col, np.int32).reshape(N, 3), np.full((pad, 3), -1, np.int32)])
+    rot_axis = np.concatenate([np.asarray(bvh.rot_axis, np.int32).reshape(N, 3), np.zeros((pad, 3), np.int32)])
+    return np.asarray(parent, np.int32), np.stack(offsets), rot_col, rot_axis, np.asarray(out, np.int32)
+
+
+def zero_length_bones(bvh, pick, skeleton):
+    """The bones (parent joint, joint) of ``skeleton`` that have no length in any frame under ``pick``: both joints sit at the
+    same point of the rig, which a node at zero OFFSET shares with its parent.  ``joints_to_motion`` divides by a bone's
+    length."""
+    from .motion_features import get_skeleton
+    parent, offsets, _, _, at = import_tables(bvh, pick)
+
+    def point(n):  # the highest node that n always coincides with
+        while parent[n] >= 0 and not np.any(offsets[n]):
+            n = int(parent[n])
+        return n
+
+    return [(p, c) for c, p in enumerate(get_skeleton(skeleton).parents) if p >= 0 and point(at[p]) == point(at[c])]
+
+
+UP_BASIS = {"Y": ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)),
+            "Z": ((1.0, 0.0, 0.0), (0.0, 0.0, 1.0), (0.0, -1.0, 0.0))}  # Z-up right-handed -> Y-up: (x, y, z) -> (x, z, -y)
+
+
+def _as_bvh(source):
+    if isinstance(source, SimpleNamespace):
+        return source
+    if isinstance(source, os.PathLike) or (isinstance(source, str) and "\n" not in source and "\r" not in source
+                                           and not source.lstrip().upper().startswith("HIERARCHY")):
+        return read_bvh(source)
+    if isinstance(source, str):
+        return parse_bvh(source)
+    raise ValueError(f"a source must be BVH text, a path or parse_bvh's namespace, not {type(source).__name__}")
+
+
+def check_import(sources, joint_map=None, fps_out=20.0, scale=1.0, up="Y", basis=None):
+    """Argument checks of ``bvh_to_joints`` that need no device: -> (the parsed files, per file its picked nodes, its (num, den)
+    and its output length, the basis as a (3, 3) float32 array).  Raises ValueError, also where 22 or 21 joints are picked and
+    a bone of that skeleton has no length (``zero_length_bones``)."""
+    if isinstance(sources, (str, os.PathLike, SimpleNamespace)):
+        raise ValueError("sources is a list of texts, paths or parsed files")
+    files = [_as_bvh(s) for s in sources]
+    if not files:
+        raise ValueError("no sources given")
+    if not np.isfinite(float(scale)):
+        raise ValueError("scale must be finite")
+    if basis is None:
+        if up not in UP_BASIS:
+            raise ValueError(f"up must be one of {sorted(UP_BASIS)}, not {up!r}")
+        basis = UP_BASIS[up]
+    basis = np.asarray(basis.detach().cpu() if torch.is_tensor(basis) else basis, dtype=np.float32)
+    if basis.shape != (3, 3) or not np.isfinite(basis).all():
+        raise ValueError("basis must be a finite 3 x 3 matrix")
+    picks, ratios, lengths_out = [], [], []
+    for i, f in enumerate(files):
+        if f.frames < 1 or f.values.shape[1] < 1:
+            raise ValueError(f"source {i} has no {'frames' if f.frames < 1 else 'channels'}")
+        if len(f.names) > MAX_IMPORT_NODES:
+            raise ValueError(f"source {i} has {len(f.names)} nodes: at most {MAX_IMPORT_NODES}")
+        picks.append(resolve_joint_map(f, joint_map))
+        skeleton = {22: "t2m", 21: "kit"}.get(len(picks[-1]))  # the joint counts of the skeletons that feature rows are made for
+        flat = zero_length_bones(f, picks[-1], skeleton) if skeleton else []
+        if flat:
+            raise ValueError(f"source {i}: under this joint_map the {skeleton} bones {flat} (parent joint, joint) have no length, "
+                             f"the joints sit at one point of the rig ({[(f.names[picks[-1][a] % len(f.names)], f.names[picks[-1][b] % len(f.names)]) for a, b in flat]}): "
+                             "feature rows divide by a bone's length.  Give a joint_map that puts them at different nodes")
+        num, den, _ = retime_ratio(None, 1.0 / float(f.frame_time), fps_out)
+        ratios.append((num, den)), lengths_out.append((f.frames - 1) * num // den + 1)
+    return files, picks, ratios, lengths_out, basis
+
+
+@torch.no_grad()
+def rig_joints(values, lengths, bvh, pick, num=1, den=1, *, scale=1.0, basis=UP_BASIS["Y"], return_quaternions=False):
+    """One launch of ``mdm_rig_joints``: ``values`` (B, T, C) float32 on a GPU, the MOTION rows of B files that share the
+    tables of ``bvh`` (``parse_bvh``'s namespace), zero-padded to T frames, with ``lengths`` (B,) or None -> ``(joints
+    (B, T_out, len(pick), 3), lengths_out (B,) int64, quaternions (B, T_out, N, 4) or None)``, ``lengths_out = (length - 1)
+    num // den + 1`` and ``T_out`` its largest; frames at or past it are zero, values at or past a length are never read.
+    ``pick``: ``resolve_joint_map``'s indices (``import_tables`` makes a node of a picked End Site; the quaternions are those of
+    the file's own N nodes).  Raises ValueError where the launch has 2^31 work items or more."""
+    L.require_cuda(values)
+    if values.dim() != 3 or values.dtype != torch.float32:
+        raise ValueError(f"values must be float32 (B, T, C), not {values.dtype} {tuple(values.shape)}")
+    values = values.contiguous()
+    dev = values.device
+    B, T, width = values.shape
+    n = torch.full((B,), T, dtype=torch.int64) if lengths is None else torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
+    if n.numel() != B or (B and (int(n.min()) < 1 or int(n.max()) > T)):
+        raise ValueError(f"lengths must have {B} entries in [1, {T}]")
+    lengths_out = (n - 1) * num // den + 1
+    parent, offsets, rot_col, rot_axis, pick = import_tables(bvh, pick)
+    N, n_pick = len(parent), len(pick)
+    T_out = int(lengths_out.max()) if B else 1
+    if B * T_out * (n_pick + N) >= 2 ** 31 or (T_out - 1) * int(den) >= 2 ** 31:
+        raise ValueError(f"{B} files of up to {T_out} output frames at {num} / {den}: too long for one launch")
+    ln, ln_out = n.to(dev, torch.int32), lengths_out.to(dev, torch.int32)
+    out = torch.empty(B, T_out, n_pick, 3, device=dev)
+    quat = torch.empty(B, T_out, N, 4, device=dev) if return_quaternions else None
+    tables = [np.ascontiguousarray(a, dtype=t) for a, t in ((parent, np.int32), (offsets, np.float32), (rot_col, np.int32),
+              (rot_axis, np.int32), (bvh.pos_col, np.int32), (pick, np.int32), (basis, np.float32))]
+    with torch.cuda.device(dev):
+        L.check(L.lib().mdm_rig_joints(
+            values.data_ptr(), ln.data_ptr(), B, T, width, N, *(a.ctypes.data_as(C.c_void_p) for a in tables[:6]), n_pick,
+            tables[6].ctypes.data_as(C.c_void_p), float(scale), int(num), int(den), T_out, ln_out.data_ptr(), out.data_ptr(),
+            L.ptr(quat), L.stream_ptr()), "mdm_rig_joints")
+    return out, lengths_out, None if quat is None else quat[:, :, :len(bvh.names)]
+
+
+@torch.no_grad()
+def bvh_to_joints(sources, *, joint_map=None, fps_out=20.0, scale=1.0, up="Y", basis=None, return_quaternions=False,
+                  device=None):
+    """``sources``, a list of BVH texts, paths or ``parse_bvh`` namespaces -> a list of joint positions (n_i, J, 3) on the
+    GPU ``device`` (default the current one) at ``fps_out`` frames a second: the positions, by the file's own hierarchy,
+    channel orders and OFFSETs, of the nodes that ``resolve_joint_map(file, joint_map)`` picks, times ``scale`` (0.01 for
+    centimetres) and turned by ``basis`` (3 x 3; default by ``up``: "Y" as it is, "Z" the fixed turn of a Z-up right-handed
+    file onto Y-up), ``out = scale * basis @ p``.  The source rate is ``1 / frame_time``: with ``num / den`` of
+    ``retime_ratio`` output frame k lies at source frame k den / num, the local rotations slerped and the root lerped where
+    that is no whole frame, and ``n_i = (frames - 1) num // den + 1``; ``fps_out=None`` keeps the file's frames.  Files
+    whose tables and ratio agree share one launch of ``mdm_rig_joints``, padded and with their lengths.
+    ``return_quaternions``: ``(joints, quaternions)``, the second a list of the retimed local unit quaternions (n_i, N, 4)
+    of every node as (w, x, y, z), w >= 0.  No eager fallback: without a GPU this raises."""
+    files, picks, ratios, lengths_out, basis = check_import(sources, joint_map, fps_out, scale, up, basis)
+    dev = torch.device("cuda" if device is None else device)
+    groups = {}
+    for i, f in enumerate(files):  # files that one launch can take together
+        key = (tuple(f.parent), np.asarray(f.offsets, np.float32).tobytes(), f.rot_col.tobytes(), f.rot_axis.tobytes(),
+               f.pos_col.tobytes(), tuple(picks[i]), ratios[i], f.values.shape[1],
+               tuple((n, np.asarray(v, np.float32).tobytes()) for n, v in sorted(f.end_sites.items())))
+        groups.setdefault(key, []).append(i)
+    joints, quats = [None] * len(files), [None] * len(files)
+    for idx in groups.values():
+        host = np.zeros((len(idx), max(files[i].frames for i in idx), files[idx[0]].values.shape[1]), np.float32)
+        for b, i in enumerate(idx):
+            host[b, :files[i].frames] = files[i].values
+        out, _, quat = rig_joints(torch.from_numpy(host).to(dev), [files[i].frames for i in idx], files[idx[0]], picks[idx[0]],
+                                      *ratios[idx[0]], scale=scale, basis=basis, return_quaternions=return_quaternions)
+        for b, i in enumerate(idx):
+            joints[i] = out[b, :lengths_out[i]]
+            if return_quaternions:
+                quats[i] = quat[b, :lengths_out[i]]
+    return (joints, quats) if return_quaternions else joints
+
+
+@torch.no_grad()
+def bvh_to_motion(sources, mean, std, *, target_offsets=None, skeleton="t2m", **kw):
+    """``bvh_to_joints(sources, **kw)`` followed by ``motion_features.joints_to_motion`` with ``mean`` / ``std`` and, when
+    given, ``target_offsets`` (the retargeting of §16): -> (rows (B, max n_i - 1, F), normalised and zero past each clip, and
+    the row counts n_i - 1 as an int64 tensor).  A file of n_i frames at the output rate gives n_i - 1 rows."""
+    from .motion_features import joints_to_motion
+    if kw.get("return_quaternions"):
+        raise ValueError("bvh_to_motion returns rows: ask bvh_to_joints for the quaternions")
+    clips = bvh_to_joints(sources, **kw)
+    rows = joints_to_motion(clips, None, mean, std, skeleton=skeleton, target_offsets=target_offsets)
+    return rows, torch.tensor([int(c.shape[0]) - 1 for c in clips], dtype=torch.int64)

@@ -7,7 +7,8 @@ same ``generate(caption, m_lens, dim_pose, batch_size)`` -> list of (T, dim_pose
 run the reference's guided DDPM over every step.  ``edit_motion`` / ``edit_mask`` turn any of them into motion editing
 (prefix completion, in-betweening, body-part regeneration; masks from ``motion_edit``).  ``prompt_weights`` with K
 captions per sample composes them under per-prompt weight maps (time-varied and body-part control, negative prompts;
-weights from ``motion_compose``).  ``edit_joints`` gives the known motion of an edit as joint positions, and
+weights from ``motion_compose``).  ``edit_joints`` gives the known motion of an edit as joint positions, ``edit_bvh`` as
+BVH files from any rig (``motion_rig.bvh_to_joints``), and
 ``refeaturize`` makes all columns of generated rows describe the joints they show (``motion_features``).
 ``control_joints`` / ``control_weights`` (with ``mean`` / ``std``) steer joint positions:
 trajectories, keyframes, end positions (targets from ``motion_control``).  ``generate_long`` samples motions longer than
@@ -22,7 +23,8 @@ from __future__ import annotations
 import torch
 
 from . import motion_long as ML
-from .conditioning import Conditioning, check_joint_edit_mask, edit_rows_from_joints, expand_to, pad_frames
+from .conditioning import (Conditioning, check_joint_edit_mask, edit_rows_from_joints, expand_to, joint_clips_from_bvh,
+                           pad_frames)
 from .diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType, SpacedDiffusion, get_named_beta_schedule,
                         space_timesteps)
 
@@ -95,7 +97,7 @@ class DDPMTrainer(object):
     def generate_batch(self, caption, m_lens, dim_pose, *, noise=None, step_noise=None, progress=True, seed=None,
                        sample_offset=0, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
                        prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
-                       control_iters=1, mean=None, std=None, edit_joints=None):
+                       control_iters=1, mean=None, std=None, edit_joints=None, edit_bvh=None, bvh_options=None):
         """``edit_motion`` (B, T_max, dim_pose), normalised, and ``edit_mask`` broadcastable to it, values in [0, 1]: the
         batch's first T frames of both are kept where the mask is 1 (exactly, for a binary mask) and generated elsewhere.
         ``prompt_weights`` (B, K, ...) broadcastable to (B, K, T_max, dim_pose): ``caption[i]`` is then a sequence of K
@@ -105,9 +107,13 @@ class DDPMTrainer(object):
         the weighted squared distance, scaled by ``control_scale`` (units in ``motion_control``).
         ``edit_joints``: B joint clips (n_i, J, 3) in place of ``edit_motion`` (needs ``mean`` / ``std``), turned into
         feature rows once per call (``motion_features.joints_to_motion``); a clip of n frames gives n - 1
-        rows, so the mask may keep frames up to n - 2."""
+        rows, so the mask may keep frames up to n - 2.  ``edit_bvh``: B BVH texts, paths or parsed files in place of
+        ``edit_joints``, read at the model's frame rate by ``motion_rig.bvh_to_joints`` under
+        ``bvh_options`` (a dict of its ``joint_map`` / ``scale`` / ``up`` / ``basis`` / ``fps_out``) and from there on
+        treated as ``edit_joints``; exclusive with ``edit_joints`` and ``edit_motion``."""
         cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
-                            control_scale, control_iters, mean, std, edit_joints, self.device)
+                            control_scale, control_iters, mean, std, edit_joints, self.device, edit_bvh=edit_bvh,
+                            bvh_options=bvh_options)
         m_lens = torch.as_tensor(m_lens)
         T = min(int(m_lens.max()), self._model().num_frames)
         return self._sample_rows(cond, slice(0, len(caption)), m_lens, T, sampler, sample_steps, eta, progress=progress,
@@ -116,7 +122,8 @@ class DDPMTrainer(object):
     @torch.no_grad()
     def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None, sampler="ddpm",
                  sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
-                 control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None):
+                 control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,
+                 edit_bvh=None, bvh_options=None):
         """``seed``: sample i's noise is then a function of (seed, i) only (counter-based device generator), so the result
         does not depend on ``batch_size``; without it the torch generator is used, as in the reference.
         ``noises``: optional list with one ``(x_T, [step noise, ...])`` pair per batch, replacing the draws (parity tests).
@@ -125,11 +132,13 @@ class DDPMTrainer(object):
         each batch takes its samples' rows.  ``prompt_weights`` (N, K, ...): composed prompts, see ``generate_batch``; each
         batch takes its samples' rows.  ``control_joints`` (N, T_max, J, 3), ``control_weights``, ``control_scale``,
         ``control_iters``, ``mean``, ``std``: joint-position control, see ``generate_batch``; each batch takes its samples'
-        rows.  ``edit_joints``: N joint clips in place of ``edit_motion``, see ``generate_batch``."""
+        rows.  ``edit_joints``: N joint clips in place of ``edit_motion``, see ``generate_batch``; ``edit_bvh`` /
+        ``bvh_options``: N BVH files in place of those, see ``generate_batch``."""
         N = len(caption)
         self.eval_mode()
         cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
-                            control_scale, control_iters, mean, std, edit_joints, self.device)
+                            control_scale, control_iters, mean, std, edit_joints, self.device, edit_bvh=edit_bvh,
+                            bvh_options=bvh_options)
         all_output = []
         for cur in range(0, N, batch_size):
             end = min(cur + batch_size, N)
@@ -145,7 +154,7 @@ class DDPMTrainer(object):
     def generate_bucketed(self, caption, m_lens, dim_pose, batch_size=32, *, unit_length=4, seed=None, group=None,
                           progress=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
                           prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
-                          control_iters=1, mean=None, std=None, edit_joints=None):
+                          control_iters=1, mean=None, std=None, edit_joints=None, edit_bvh=None, bvh_options=None):
         """Evaluation-scale variant of ``generate``: same inputs and the same kind of result (a
         list of per-sample ``(T_batch, dim_pose)`` tensors in the caller's order, valid up to each sample's length),
         but batches hold samples of similar length (less padded work) and, under ``torch.distributed``, are dealt over
@@ -153,12 +162,13 @@ class DDPMTrainer(object):
         ``caption``) only -- the same as ``generate(..., seed=)`` -- so on each sample's valid frames the two give identical
         results whatever the bucketing (tests/test_sampler_gpu.py).  ``edit_motion`` / ``edit_mask``: as in ``generate``;
         each bucket takes its samples' rows and its first T frames; so do ``prompt_weights`` and the ``control_*`` tensors.
-        ``edit_joints``: joint clips in place of ``edit_motion``, as in ``generate``."""
+        ``edit_joints``: joint clips in place of ``edit_motion``, as in ``generate``; so are ``edit_bvh`` / ``bvh_options``."""
         from . import dist as D
         m = self._model()
         self.eval_mode()
         cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
-                            control_scale, control_iters, mean, std, edit_joints, self.device)
+                            control_scale, control_iters, mean, std, edit_joints, self.device, edit_bvh=edit_bvh,
+                            bvh_options=bvh_options)
         lens = torch.as_tensor(m_lens).flatten().long().cpu()
         plan = D.plan_buckets(lens, batch_size, m.num_frames, unit_length)
 
@@ -300,7 +310,7 @@ class DDPMTrainer(object):
         agree with the rotations, the global rotation matrix of every joint (the root's at joint 0) and the bone offsets
         used (``offsets``, or the sample's own mean bone lengths).  ``fix_feet`` / ``blend``: foot-skate clean-up as in
         ``generate_joints``; the rotations of knees, ankles and toes turn with their bones.  ``**kw`` as for ``generate``."""
-        motions = self.generate(caption, m_lens, dim_pose, batch_size, **kw)
+        motions = self.generate(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)  # unused without an edit or control
         lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
         return self._to_joints(motions, lens, dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True, offsets, True,
                                fix_feet=fix_feet, blend=blend)
@@ -336,17 +346,19 @@ class DDPMTrainer(object):
         """``generate`` followed by forward kinematics and the rig export (``motion_rig``): one BVH text per
         sample, written to ``paths[i]`` where given.  ``fps`` (default 20 at dim_pose 263, 12.5 at 251) / ``fps_out``: retimed
         to the frame rate a tool works at; ``euler``: the channels' rotation order; ``scale``: of positions and offsets (100
-        for centimetres).  ``offsets`` / ``fix_feet`` / ``blend`` as in ``generate_rotations``, ``**kw`` as for ``generate``."""
+        for centimetres).  ``offsets`` / ``fix_feet`` / ``blend`` as in ``generate_rotations``, ``**kw`` as for ``generate``:
+        with ``edit_bvh=`` / ``edit_mask=`` a file from a rig is continued and written back as one (converted under this
+        call's ``mean`` / ``std``)."""
         if paths is not None and len(paths) != len(caption):
             raise ValueError(f"paths must hold one entry per caption ({len(caption)}), or None")
-        motions = self.generate(caption, m_lens, dim_pose, batch_size, **kw)
+        motions = self.generate(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)  # unused without an edit or control
         lens = [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
         return self._to_bvh(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, paths, fps, fps_out, euler, scale)
 
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
                       sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, noise=None, progress=False,
-                      edit_joints=None, mean=None, std=None):
+                      edit_joints=None, mean=None, std=None, edit_bvh=None, bvh_options=None):
         """Long motions: ``scripts`` is a list of long motions, each a list of ``(caption, length)``
         segments of at most ``num_frames`` frames; neighbouring segments share ``overlap`` canvas frames, whose eps is
         blended on every step (``blend`` "linear" crossfade or "uniform") while x_T and the step noise come from the left
@@ -358,11 +370,14 @@ class DDPMTrainer(object):
         (canvas_len, dim_pose) x_T per motion.  ``sampler`` / ``sample_steps`` / ``eta`` as in ``generate``.
         ``edit_joints`` (with ``mean`` / ``std``): one joint clip (n_i, J, 3) per motion in place of ``edit_motion``, e.g. the
         joints ``generate_long_joints`` returned, to be continued: its n_i - 1 rows start the canvas, and every motion
-        needs its mask."""
+        needs its mask.  ``edit_bvh`` / ``bvh_options``: one BVH file per motion in place of ``edit_joints``, as in
+        ``generate``."""
         m = self._model()
         self.eval_mode()
         plans = ML.script_plans(scripts, overlap, m.num_frames)
         N = len(plans)
+        if edit_bvh is not None or bvh_options is not None:
+            edit_joints = joint_clips_from_bvh(edit_bvh, bvh_options, edit_joints, edit_motion, self.device)
         if edit_joints is not None:
             if edit_motion is not None:
                 raise ValueError("edit_joints and edit_motion are exclusive: the known motion is given as joints or as rows")
@@ -432,7 +447,7 @@ class DDPMTrainer(object):
             most = fk_max_frames()
         if longest > most:
             raise ValueError(f"a canvas of {longest} frames: joint recovery takes at most {most} frames")
-        if kw.get("edit_joints") is not None:  # joints in, joints out: the clips are converted under the same mean / std
+        if kw.get("edit_joints") is not None or kw.get("edit_bvh") is not None:  # converted under the same mean / std
             kw = dict(kw, mean=mean, std=std)
         motions = self.generate_long(scripts, dim_pose, **kw)
         return self._to_joints(motions, [mo.shape[0] for mo in motions], dim_pose, mean, std, joints_num, sigma,
@@ -451,7 +466,7 @@ class DDPMTrainer(object):
         longest = max(p[3] for p in plans)
         if longest > fk_max_frames():
             raise ValueError(f"a canvas of {longest} frames: forward kinematics takes at most {fk_max_frames()} frames")
-        if kw.get("edit_joints") is not None:
+        if kw.get("edit_joints") is not None or kw.get("edit_bvh") is not None:
             kw = dict(kw, mean=mean, std=std)
         motions = self.generate_long(scripts, dim_pose, **kw)
         return self._to_bvh(motions, [mo.shape[0] for mo in motions], dim_pose, mean, std, offsets, fix_feet, feet_blend, paths,
