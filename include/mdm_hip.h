@@ -555,6 +555,28 @@ int mdm_rig_joints(const float* values, const int32_t* length, int32_t B, int32_
                    int32_t den, int32_t T_out, const int32_t* length_out, float* joints_out, float* quaternions_out,
                    void* stream);
 
+/* Motion preview (csrc/motion_render.hip): joints -> image frames.  joints (B, T, J, 3) fp32, length (B) int32 or
+ * NULL (= T); of the skeleton the chains are used (group 2 + c draws the links of chain c) and J must be its joint count.
+ * The image is defined in DESIGN.md §21: the scene of the reference's plot_3d_motion (floor rectangle from the clip's extent,
+ * root trajectory up to the frame before, the chains) relative to the frame's root, a look-at pinhole camera, capsules and a
+ * floor polygon with a one-pixel coverage ramp, groups composited once each in fp32, uint8 = floor(255 c + 0.5).
+ * camera[8]: elevation and azimuth in degrees, distance, vertical field of view in degrees, target x, y, z, near plane.
+ * style[3 + 5 (2 + nchains)]: the background's r, g, b, then r, g, b, alpha, full width in points (of a figure 720 points
+ * high) of the floor (width unused), the trajectory and every chain, colours in [0, 1].  mode 0: out (B, NF, H, W, 3) uint8;
+ * mode 1: out (B, NF, H, W) uint8, indices into the 6 x 7 x 6 colour cube (r6 42 + g7 6 + b6 of the 8-bit colour).
+ * frames: device int32 [n_frames], the frame index behind each of the NF = n_frames output frames, or NULL: NF = T, all frames
+ * in order (n_frames is not read).  An output frame whose index is outside [0, length[b]) is all zero; source frames at or
+ * past length[b] are never read.  scratch: mdm_motion_render_scratch_floats(B, T) floats (8 + 2 T per sample: the clip's
+ * extent and its root path).  Any T (the trajectory goes through LDS in chunks).  Two launches, stream-ordered, no allocation.
+ * MDM_ERR_ARG, before the device is touched: a null pointer (length, frames excepted), B < 0, T < 1, H or W < 4, W % 4 != 0, a
+ * mode other than 0 / 1, frames with n_frames < 1, out not 4-byte aligned, a malformed skeleton, J != skeleton->joints, a
+ * non-finite camera or style value, |elevation| >= 89.9, distance, near or field of view <= 0, field of view >= 180,
+ * near >= distance, a negative width.  MDM_ERR_UNSUPPORTED: B or NF above 65535 (grid dimensions). */
+int64_t mdm_motion_render_scratch_floats(int32_t B, int32_t T);
+int mdm_motion_render(const float* joints, const int32_t* length, const MdmSkeleton* skeleton, int32_t B, int32_t T, int32_t J,
+                      int32_t H, int32_t W, const float* camera, const float* style, int32_t mode, const int32_t* frames,
+                      int32_t n_frames, uint8_t* out, float* scratch, void* stream);
+
 /* Joint-position control (csrc/motion_control.hip).  For sample b, with J = (F + 1) / 12 joints (F must be
  * 12 J - 1: 263 -> 22, 251 -> 21), targets G and weights W dense fp32 (B, T, J, 3), W >= 0 and finite, mean / std fp32
  * (B, F) (one row per sample), and P = recover_from_ric(x0 * std + mean) without temporal filter (as mdm_motion_postprocess

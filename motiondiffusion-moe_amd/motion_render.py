@@ -1,0 +1,274 @@
+"""Motion preview on the device: joints -> image frames, contact sheets and GIF files.
+
+Host side of ``mdm_motion_render`` (csrc/motion_render.hip).  The scene is the one the reference's ``plot_3d_motion``
+(utils/plot_script.py) prepares: a floor rectangle from the clip's extent, the root's trajectory up to the frame before, and the
+skeleton's five kinematic chains in red, blue, black, red, blue, all relative to the frame's root.  The rasteriser is this
+project's own and is defined in DESIGN.md §21 (a look-at pinhole camera, capsules with a one-pixel coverage ramp), not
+matplotlib's: two implementations of that definition agree to a grey level.  All pixels are made in the kernel; no eager
+fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import io
+from dataclasses import dataclass, replace
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+RED, BLUE, BLACK = (1.0, 0.0, 0.0), (0.0, 0.0, 1.0), (0.0, 0.0, 0.0)
+STYLE = dict(background=(1.0, 1.0, 1.0),
+             floor_color=(0.5, 0.5, 0.5), floor_alpha=0.5,
+             trajectory_color=BLUE, trajectory_alpha=1.0, trajectory_width=1.0,
+             chain_colors=(RED, BLUE, BLACK, RED, BLUE), chain_alpha=1.0, chain_width=4.0)  # widths: points of a 720-point figure
+MAX_ELEV = 89.9
+
+
+@dataclass(frozen=True)
+class Camera:
+    """Look-at pinhole camera: eye = target + dist (cos e sin a, sin e, cos e cos a), angles and ``fov`` (vertical) in degrees.
+    The defaults look at the figure from its front and above, as the reference's axes do; they are a choice."""
+    elev: float = 30.0
+    azim: float = 0.0
+    dist: float = 5.0
+    fov: float = 40.0
+    target: Tuple[float, float, float] = (0.0, 0.9, 0.0)
+    near: float = 0.1
+
+    def block(self):
+        """The eight floats of ``mdm_motion_render``'s camera argument, checked."""
+        v = [float(self.elev), float(self.azim), float(self.dist), float(self.fov)] + [float(x) for x in self.target] + [float(self.near)]
+        if len(v) != 8 or not all(np.isfinite(v)):
+            raise ValueError("camera values must be finite, target three of them")
+        if abs(self.elev) >= MAX_ELEV:
+            raise ValueError(f"|elev| must be below {MAX_ELEV} degrees (the camera's up is the world's)")
+        if not (self.dist > 0 and 0 < self.near < self.dist and 0 < self.fov < 180):
+            raise ValueError("camera needs dist > 0, 0 < near < dist and 0 < fov < 180")
+        return (C.c_float * 8)(*v)
+
+
+def as_camera(camera) -> Camera:
+    if camera is None:
+        return Camera()
+    if isinstance(camera, Camera):
+        return camera
+    if isinstance(camera, dict):
+        return replace(Camera(), **{k: (tuple(v) if k == "target" else v) for k, v in camera.items()})
+    raise ValueError("camera must be a Camera, a dict of its fields, or None")
+
+
+def _palette() -> np.ndarray:
+    r, g, b = np.meshgrid(np.arange(6), np.arange(7), np.arange(6), indexing="ij")
+    return np.stack([r * 51, (g * 255 + 3) // 6, b * 51], -1).reshape(252, 3).astype(np.uint8)
+
+
+PALETTE = _palette()  # entry r6 42 + g7 6 + b6 of the 6 x 7 x 6 colour cube
+
+
+def palette_index(rgb):
+    """8-bit colours (..., 3), a tensor or an array -> the cube's index (...) uint8: ``r6 = (r8 5 + 127) // 255``,
+    ``g7 = (g8 6 + 127) // 255``, ``b6 = (b8 5 + 127) // 255``, ``index = r6 42 + g7 6 + b6``, all in integers."""
+    if torch.is_tensor(rgb):
+        v = rgb.to(torch.int32)
+        idx = (torch.div(v[..., 0] * 5 + 127, 255, rounding_mode="floor") * 42
+               + torch.div(v[..., 1] * 6 + 127, 255, rounding_mode="floor") * 6 + torch.div(v[..., 2] * 5 + 127, 255, rounding_mode="floor"))
+        return idx.to(torch.uint8)
+    v = np.asarray(rgb).astype(np.int32)
+    return (((v[..., 0] * 5 + 127) // 255) * 42 + ((v[..., 1] * 6 + 127) // 255) * 6 + (v[..., 2] * 5 + 127) // 255).astype(np.uint8)
+
+
+def style_block(nchains: int, **style):
+    """The floats of ``mdm_motion_render``'s style argument from the keyword arguments of ``render_motion`` (``STYLE`` holds
+    the names and defaults): background, then colour, alpha and width of the floor, the trajectory and every chain.
+    ``chain_alpha`` / ``chain_width``: one value or one per chain; ``chain_colors``: one colour per chain, repeated in turn
+    where the skeleton has more chains."""
+    unknown = set(style) - set(STYLE)
+    if unknown:
+        raise ValueError(f"unknown style arguments {sorted(unknown)}: the style is {sorted(STYLE)}")
+    st = dict(STYLE, **style)
+
+    def rgb(v, what):
+        v = [float(x) for x in v]
+        if len(v) != 3 or not all(0.0 <= x <= 1.0 for x in v):
+            raise ValueError(f"{what} must be three values in [0, 1]")
+        return v
+
+    def per_chain(v, what):
+        v = np.broadcast_to(np.asarray(v, np.float64), (nchains,)) if np.ndim(v) == 0 or len(v) == nchains else None
+        if v is None or not np.isfinite(v).all() or (v < 0).any():
+            raise ValueError(f"{what} must be one non-negative value, or one per chain ({nchains})")
+        return [float(x) for x in v]
+
+    colors = [rgb(c, "a chain colour") for c in st["chain_colors"]]
+    if not colors:
+        raise ValueError("chain_colors is empty")
+    alphas, widths = per_chain(st["chain_alpha"], "chain_alpha"), per_chain(st["chain_width"], "chain_width")
+    for name in ("floor_alpha", "trajectory_alpha", "trajectory_width"):
+        if not (np.isfinite(st[name]) and st[name] >= 0):
+            raise ValueError(f"{name} must be finite and >= 0")
+    if max(alphas + [st["floor_alpha"], st["trajectory_alpha"]]) > 1:
+        raise ValueError("an alpha must lie in [0, 1]")
+    v = rgb(st["background"], "background")
+    v += rgb(st["floor_color"], "floor_color") + [float(st["floor_alpha"]), 0.0]
+    v += rgb(st["trajectory_color"], "trajectory_color") + [float(st["trajectory_alpha"]), float(st["trajectory_width"])]
+    for c in range(nchains):
+        v += colors[c % len(colors)] + [alphas[c], widths[c]]
+    return (C.c_float * len(v))(*v)
+
+
+def frame_indices(frames, T: int):
+    """``frames`` of ``render_motion`` -> the list of frame indices: None (all), an int stride, a slice, or indices."""
+    if frames is None:
+        return None
+    if isinstance(frames, slice):
+        idx = list(range(T))[frames]
+    elif isinstance(frames, (int, np.integer)):
+        if frames < 1:
+            raise ValueError("a frame stride must be >= 1")
+        idx = list(range(0, T, int(frames)))
+    else:
+        idx = [int(i) for i in (frames.tolist() if hasattr(frames, "tolist") else frames)]
+        idx = [i + T if i < 0 else i for i in idx]
+    if not idx or min(idx) < 0 or max(idx) >= T:
+        raise ValueError(f"frames must pick at least one frame inside [0, {T})")
+    return idx
+
+
+def _skeleton_for(skeleton, J):
+    from .motion_features import get_skeleton
+    if skeleton is None:
+        if J not in (22, 21):
+            raise ValueError(f"{J} joints: pass skeleton= (22 joints default to \"t2m\", 21 to \"kit\")")
+        skeleton = {22: "t2m", 21: "kit"}[J]
+    sk = get_skeleton(skeleton)
+    if sk.joints != J:
+        raise ValueError(f"the skeleton has {sk.joints} joints, the motion {J}")
+    return sk
+
+
+@torch.no_grad()
+def render_motion(joints, lengths=None, skeleton=None, size=(480, 480), camera=None, palette=False, frames=None, **style):
+    """joints (B, T, J, 3) on a GPU (or one clip (T, J, 3)) -> frames (B, T, H, W, 3) uint8 on the device, ``size`` = (H, W),
+    W a multiple of 4; with ``palette=True`` (B, T, H, W) uint8 indices into ``PALETTE`` (the same picture: ``palette_index``
+    of the RGB frames, a third of the bytes, ready for a GIF).  Frames at or past ``lengths[b]`` are zero and are never read.
+    ``skeleton`` defaults by J (22: "t2m", 21: "kit").  ``camera``: a ``Camera`` or a dict of its fields.  ``frames``: a
+    slice, an int stride or a list of frame indices: only those frames are drawn (the output's T is their count) while the
+    scene's extent and the trajectory still come from all frames, which keeps a long motion's output small.  ``**style``:
+    colours in [0, 1], alphas and widths in points, see ``STYLE``."""
+    from .motion_features import _skeleton_struct
+    x = torch.as_tensor(joints)
+    if x.dim() == 3:
+        x = x[None]
+    if x.dim() != 4 or x.shape[-1] != 3:
+        raise ValueError(f"joints of shape {tuple(x.shape)} must be (B, T, J, 3)")
+    B, T, J = x.shape[:3]
+    if T < 1:
+        raise ValueError("a motion needs at least one frame")
+    sk = _skeleton_for(skeleton, J)
+    H, W = (int(v) for v in size)
+    if H < 4 or W < 4 or W % 4:
+        raise ValueError(f"size (H, W) = {(H, W)}: both at least 4 and W a multiple of 4 (a thread stores 4 pixels)")
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
+        if lengths.numel() != B or (B and (int(lengths.min()) < 1 or int(lengths.max()) > T)):
+            raise ValueError(f"lengths must hold {B} entries in [1, {T}]")
+    cam = as_camera(camera).block()
+    st = style_block(len(sk.chains), **style)
+    idx = frame_indices(frames, T)
+    L.require_cuda(x)
+    dev = x.device
+    x = x.detach().to(torch.float32).contiguous()
+    ln = None if lengths is None else lengths.to(dev, torch.int32).contiguous()
+    fr = None if idx is None else torch.tensor(idx, dtype=torch.int32, device=dev)
+    NF = T if idx is None else len(idx)
+    if B > 65535 or NF > 65535:
+        raise ValueError("at most 65535 samples and 65535 frames per call")
+    out = torch.empty((B, NF, H, W) + (() if palette else (3,)), dtype=torch.uint8, device=dev)
+    lib = L.lib()
+    scratch = torch.empty(max(1, int(lib.mdm_motion_render_scratch_floats(B, T))), dtype=torch.float32, device=dev)
+    s = _skeleton_struct(sk)
+    with torch.cuda.device(dev):
+        L.check(lib.mdm_motion_render(x.data_ptr(), L.ptr(ln), C.byref(s), B, T, J, H, W, cam, st, 1 if palette else 0, L.ptr(fr),
+                                      NF, out.data_ptr(), scratch.data_ptr(), L.stream_ptr()), "mdm_motion_render")
+    return out
+
+
+def contact_sheet(frames_or_joints, cols: Optional[int] = None, every: int = 1, **render_kw):
+    """Every ``every``-th frame of each sample side by side, ``cols`` to a row (default: all in one row): frames
+    (B, T, H, W, 3) or palette indices (B, T, H, W) -> (B, rows H, cols W[, 3]); cells past the last frame are white.  A float
+    tensor is taken as joints (B, T, J, 3) and rendered first with ``render_kw``.  Plain reshaping of ``render_motion``'s output."""
+    x = torch.as_tensor(frames_or_joints)
+    if x.dtype != torch.uint8:
+        x = render_motion(x, frames=slice(None, None, every), **render_kw)
+    else:
+        if render_kw:
+            raise ValueError("rendered frames take no rendering arguments")
+        x = x[:, ::every]
+    if x.dim() not in (4, 5) or every < 1:
+        raise ValueError("frames must be (B, T, H, W, 3) or (B, T, H, W), every >= 1")
+    B, n, H, W = x.shape[:4]
+    cols = n if cols is None else int(cols)
+    if cols < 1:
+        raise ValueError("cols must be >= 1")
+    rows = -(-n // cols)
+    tail = tuple(x.shape[4:])
+    white = 255 if tail else int(palette_index(np.array([255, 255, 255])))
+    cells = torch.full((B, rows * cols, H, W) + tail, white, dtype=torch.uint8, device=x.device)
+    cells[:, :n] = x
+    cells = cells.reshape((B, rows, cols, H, W) + tail)
+    order = (0, 1, 3, 2, 4) + ((5,) if tail else ())
+    return cells.permute(*order).reshape((B, rows * H, cols * W) + tail)
+
+
+def gif_duration_ms(fps: float) -> int:
+    """A GIF's frame delay is a whole number of centiseconds: ``10 round(100 / fps)`` ms, at least 10 (20 fps -> 50 ms,
+    12.5 fps -> 80 ms, 30 fps -> 30 ms instead of 33.3)."""
+    if not fps > 0:
+        raise ValueError("fps must be > 0")
+    return 10 * max(1, int(round(100.0 / float(fps))))
+
+
+def write_gif(indices, path, fps: float, lengths=None):
+    """Palette frames -> an animated GIF that loops.  indices: (T, H, W) uint8 of one clip with ``path`` a file name or a
+    binary file object, or (B, T, H, W) with one path per clip; ``lengths``: frames to write of each clip (default all).
+    The frames go to PIL in its "P" mode with ``PALETTE``: nothing is quantised on the host.  The frame delay is rounded to
+    whole centiseconds (``gif_duration_ms``).  PIL stores a frame that repeats the one before as a longer delay of that one.
+    Returns ``path``."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError("write_gif needs PIL (the pillow package), which is not installed; the frames themselves, "
+                          "render_motion(..., palette=True) and PALETTE, need nothing") from e
+    x = indices.detach().cpu().numpy() if torch.is_tensor(indices) else np.asarray(indices)
+    if x.dtype != np.uint8 or x.ndim not in (3, 4):
+        raise ValueError("indices must be uint8 palette frames (T, H, W) or (B, T, H, W): render_motion(..., palette=True)")
+    if x.ndim == 4:
+        if isinstance(path, (str, bytes)) or len(path) != len(x):
+            raise ValueError(f"a batch of {len(x)} clips needs as many paths")
+        ns = [x.shape[1]] * len(x) if lengths is None else [int(n) for n in torch.as_tensor(lengths).flatten().tolist()]
+        if len(ns) != len(x):
+            raise ValueError(f"lengths must hold {len(x)} entries")
+        return [write_gif(x[b], path[b], fps, ns[b]) for b in range(len(x))]
+    n = x.shape[0] if lengths is None else int(torch.as_tensor(lengths).flatten()[0])
+    if n < 1 or n > x.shape[0]:
+        raise ValueError(f"{n} frames of a clip of {x.shape[0]}")
+    if int(x[:n].max()) >= len(PALETTE):
+        raise ValueError("an index outside the palette")
+    pal = PALETTE.tobytes() + bytes(3 * (256 - len(PALETTE)))
+    ims = []
+    for t in range(n):
+        im = Image.fromarray(x[t], "P")
+        im.putpalette(pal)
+        ims.append(im)
+    ims[0].save(path, format="GIF", save_all=True, append_images=ims[1:], duration=gif_duration_ms(fps), loop=0, optimize=False)
+    return path
+
+
+def gif_bytes(indices, fps: float, length=None) -> bytes:
+    """``write_gif`` of one clip into memory."""
+    buf = io.BytesIO()
+    write_gif(indices, buf, fps, length)
+    return buf.getvalue()

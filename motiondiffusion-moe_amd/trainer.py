@@ -472,6 +472,59 @@ class DDPMTrainer(object):
         return self._to_bvh(motions, [mo.shape[0] for mo in motions], dim_pose, mean, std, offsets, fix_feet, feet_blend, paths,
                             fps, fps_out, euler, scale)
 
+    @staticmethod
+    def _to_frames(joints, size, camera, palette, style):
+        """``motion_render.render_motion`` over a list of (n_i, J, 3) joint clips, one launch for all: a list of
+        ``(n_i, H, W, 3)`` uint8 frames, or ``(n_i, H, W)`` palette indices."""
+        from .motion_features import pad_clips
+        from .motion_render import render_motion
+        x, lens = pad_clips(joints, joints[0].shape[1])
+        frames = render_motion(x, lens, size=size, camera=camera, palette=palette, **(style or {}))
+        return [frames[i, :n] for i, n in enumerate(lens.tolist())]
+
+    @staticmethod
+    def _to_gifs(frames, dim_pose, paths, fps):
+        from .motion_render import gif_bytes, write_gif
+        from .motion_rig import DEFAULT_FPS
+        if fps is None:
+            fps = DEFAULT_FPS.get({263: "t2m", 251: "kit"}.get(dim_pose), DEFAULT_FPS["t2m"])
+        if paths is None:
+            return [gif_bytes(f, fps) for f in frames]
+        return [gif_bytes(f, fps) if p is None else write_gif(f, p, fps) for f, p in zip(frames, paths)]
+
+    @torch.no_grad()
+    def generate_frames(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, size=(480, 480), camera=None,
+                        palette=False, style=None, **kw):
+        """``generate_joints`` followed by the motion preview (``motion_render.render_motion``) on the device:
+        a list of ``(m_len, H, W, 3)`` uint8 frames, ``size`` = (H, W); with ``palette`` ``(m_len, H, W)`` indices into
+        ``motion_render.PALETTE``.  ``camera``: a ``motion_render.Camera`` or a dict of its fields; ``style``: a dict of
+        ``render_motion``'s colour and width arguments.  ``**kw`` goes to ``generate_joints`` untouched: ``from_rotations``,
+        ``fix_feet``, the sampler, edit and control arguments."""
+        joints = self.generate_joints(caption, m_lens, dim_pose, mean, std, batch_size, **kw)
+        return self._to_frames(joints, size, camera, palette, style)
+
+    @torch.no_grad()
+    def generate_gif(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, paths=None, fps=None, size=(480, 480),
+                     camera=None, style=None, **kw):
+        """``generate_frames`` in palette mode followed by ``motion_render.write_gif``: one animated GIF per caption, as
+        bytes, or written to ``paths[i]`` where given (the path is then returned in its place).  ``fps`` defaults to
+        ``motion_rig.DEFAULT_FPS`` (20 at dim_pose 263, 12.5 at 251); a GIF's frame delay is whole centiseconds."""
+        if paths is not None and len(paths) != len(caption):
+            raise ValueError(f"paths must hold one entry per caption ({len(caption)}), or None")
+        frames = self.generate_frames(caption, m_lens, dim_pose, mean, std, batch_size, size=size, camera=camera, palette=True,
+                                      style=style, **kw)
+        return self._to_gifs(frames, dim_pose, paths, fps)
+
+    @torch.no_grad()
+    def generate_long_gif(self, scripts, dim_pose, mean, std, *, paths=None, fps=None, size=(480, 480), camera=None,
+                          style=None, **kw):
+        """``generate_long_joints`` followed by the motion preview and ``write_gif``, as ``generate_gif``: one GIF per long
+        motion.  ``**kw`` goes to ``generate_long_joints`` untouched."""
+        if paths is not None and len(paths) != len(scripts):
+            raise ValueError(f"paths must hold one entry per motion ({len(scripts)}), or None")
+        joints = self.generate_long_joints(scripts, dim_pose, mean, std, **kw)
+        return self._to_gifs(self._to_frames(joints, size, camera, True, style), dim_pose, paths, fps)
+
     def save(self, file_name, ep, total_it):
         state = {"opt_encoder": getattr(self, "opt_encoder_state", {}), "ep": ep, "total_it": total_it,
                  "encoder": self._model().state_dict()}
