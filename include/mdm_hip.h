@@ -409,6 +409,14 @@ int mdm_noise_normal(float* out, int64_t per_sample, int32_t nsamples, int64_t s
  * not consecutive samples (trainer.generate_bucketed) */
 int mdm_noise_normal_ids(float* out, int64_t per_sample, int32_t nsamples, const int64_t* sample_ids, uint64_t seed,
                          const int32_t* stream_dev, int32_t stream_imm, void* stream);
+/* Forward diffusion of a given motion to an intermediate level of the schedule, the start of a partial sampling loop
+ * (csrc/noise.hip): out[r, e] = a * x_start[r, e] + s * n[r, e] for r < nsamples, e < per_sample.
+ * n is read from noise when it is non-NULL; otherwise it is drawn in registers and equals what mdm_noise_normal (sample_ids
+ * NULL: global sample sample0 + r) or mdm_noise_normal_ids (global sample sample_ids[r]) writes under seed on the
+ * MDM_NOISE_STREAM_XT stream.  a = sqrt(abar) and s = sqrt(1 - abar) of the level, evaluated in f64 on the host and rounded
+ * once.  out may be x_start.  MDM_ERR_ARG: NULL x_start or out, a negative size or sample0, a or s not finite. */
+int mdm_diffuse_start(const float* x_start, const float* noise, float* out, int64_t per_sample, int32_t nsamples,
+                      int64_t sample0, const int64_t* sample_ids, uint64_t seed, float a, float s, void* stream);
 
 /* Text projection head of the reference's EnhancedTextEncoder (text_encoder.py:13-18,31-43), applied to the
  * last_hidden_state of any text encoder (the DeBERTa weights themselves are third-party and stay outside this library):

@@ -178,6 +178,7 @@ PROTOTYPES = {
     "mdm_composed_update": (_I32, [_P, _P, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _I32, _F32, _I32, _P, _P, _P]),
     "mdm_noise_normal": (_I32, [_P, _I64, _I32, _I64, _U64, _P, _I32, _P]),
     "mdm_noise_normal_ids": (_I32, [_P, _I64, _I32, _P, _U64, _P, _I32, _P]),
+    "mdm_diffuse_start": (_I32, [_P, _P, _P, _I64, _I32, _I64, _P, _U64, _F32, _F32, _P]),
     "mdm_text_head_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32]),
     "mdm_text_head_forward": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I64, _I32, _P]),
     "mdm_motion_postprocess": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),

@@ -1,7 +1,8 @@
 """Host side of every conditioning input of the sampler: what a generate call is given besides captions and lengths.
 
-``expand_to`` is the one align-and-expand of a weight / mask tensor.  The ``check_*_kwargs`` functions validate the
-``model_kwargs`` of one sampler batch (motion editing, composed prompts, joint control, long-motion handshakes; DESIGN.md
+``expand_to`` is the one align-and-expand of a weight / mask tensor.  ``strength_steps`` and ``init_rows_from`` are the host
+side of motion-to-motion generation (a given motion as the start of a partial loop).  The
+``check_*_kwargs`` functions validate the ``model_kwargs`` of one sampler batch (motion editing, composed prompts, joint control, long-motion handshakes; DESIGN.md
 §11, §12, §14, §15) for ``diffusion._StepRunner``; ``diffusion`` imports them under the same names.  ``Conditioning``
 holds the checked conditioning of one public ``DDPMTrainer`` call and hands out each batch's share as ``model_kwargs``.
 Host logic only: runs on CPU tensors and never loads the HIP library.
@@ -297,6 +298,53 @@ def joint_edit_mask_frames(mask, rows):
     return T
 
 
+def strength_steps(strength, num_steps) -> int:
+    """The steps a motion-to-motion call runs of a sampler of ``num_steps`` steps: ``round(strength * num_steps)``, halves
+    up.  All of them is the plain loop (the given motion is ignored), none returns the given motion, and n of them start
+    at step n - 1.  Raises ValueError for a strength outside [0, 1] (NaN included)."""
+    v = float(strength)
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"strength must lie in [0, 1], not {strength}")
+    return min(int(math.floor(v * int(num_steps) + 0.5)), int(num_steps))
+
+
+class LatentStep(int):
+    """The step of a spaced schedule at which inverted latents stand, with the step count of that schedule
+    (``sample_steps``): ``DDPMTrainer.invert`` returns one, and ``generate(latents=, latent_step=)`` holds it against its
+    own sampler."""
+
+    def __new__(cls, step, sample_steps):
+        self = super().__new__(cls, step)
+        self.sample_steps = int(sample_steps)
+        return self
+
+
+def init_rows_from(init_motion, init_joints, init_bvh, bvh_options, mean, std, dim_pose, device=None, to_motion=None):
+    """The motion a motion-to-motion call starts from, given as normalised rows ``init_motion`` (N, T_max, dim_pose), as N
+    joint clips ``init_joints`` or as N BVH files ``init_bvh`` (the paths of the edit inputs: ``joint_clips_from_bvh``, then
+    ``edit_rows_from_joints`` under ``mean`` / ``std``): (rows (N, T, dim_pose), the row count of every sample).  Raises
+    ValueError for more than one of the three, joints or files without mean / std, rows of another shape, and rows that are
+    not finite."""
+    given = [k for k, v in (("init_motion", init_motion), ("init_joints", init_joints), ("init_bvh", init_bvh)) if v is not None]
+    if len(given) != 1:
+        raise ValueError("init_motion, init_joints and init_bvh are exclusive: the motion to start from is given as rows, as "
+                         f"joints or as files, not as {' and '.join(given) or 'none of them'}")
+    if init_motion is None:
+        if mean is None or std is None:
+            raise ValueError(f"{given[0]} needs the dataset's mean and std (feature rows are normalised, joints are not)")
+        if init_bvh is not None:
+            init_joints = joint_clips_from_bvh(init_bvh, bvh_options, device=device)
+        x, have = edit_rows_from_joints(init_joints, mean, std, dim_pose, device, to_motion)
+    else:
+        x = torch.as_tensor(init_motion)
+        if x.dim() != 3 or x.shape[2] != dim_pose or not x.is_floating_point():
+            raise ValueError(f"init_motion of shape {tuple(x.shape)} must be floating point (N, T_max, {dim_pose})")
+        have = [int(x.shape[1])] * int(x.shape[0])
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError(f"{given[0]} has non-finite values")
+    return x, have
+
+
 def pad_frames(x, T):
     """``x`` (N, t, F) zero-padded along its frame dim to T frames (returned as it is when t >= T)."""
     if x.shape[1] >= T:
@@ -312,13 +360,44 @@ class Conditioning:
     None without).  ``edit_joints`` in place of ``edit_motion``: N joint clips (n_i, J, 3), turned into feature rows once
     (``edit_rows_from_joints``) and zero-padded to the mask's frames.  ``edit_bvh`` (with ``bvh_options``) in place of
     ``edit_joints``: N BVH files, read into joint clips first (``joint_clips_from_bvh``).
+    ``init_motion`` / ``init_joints`` / ``init_bvh`` with ``strength``: the motion every sample starts from
+    (``init_rows_from``) and the share of the sampler's steps to run (``strength_steps``); ``latents`` with ``latent_step``
+    in their place: x at that step, e.g. from ``DDPMTrainer.invert``, to continue from.  ``start_kwargs`` hands out a
+    batch's share of either.
     What does not depend on a batch is checked here, once; ``kwargs`` hands out a batch's rows and frames
     (views of these tensors) and checks that they cover its T."""
 
     def __init__(self, captions, dim_pose, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
                  control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,
-                 device=None, to_motion=None, edit_bvh=None, bvh_options=None):
+                 device=None, to_motion=None, edit_bvh=None, bvh_options=None, init_motion=None, init_joints=None,
+                 init_bvh=None, strength=None, latents=None, latent_step=None):
         self.captions, self.dim_pose = captions, dim_pose
+        self.init, self.strength, self.latents, self.latent_step = None, None, None, None
+        if init_motion is not None or init_joints is not None or init_bvh is not None:
+            if latents is not None:
+                raise ValueError("latents and init_motion / init_joints / init_bvh are exclusive")
+            if strength is None:
+                raise ValueError("a motion to start from needs strength, the share of the sampler's steps to run")
+            strength_steps(strength, 1)
+            self.init = init_rows_from(init_motion, init_joints, init_bvh, bvh_options, mean, std, dim_pose, device, to_motion)
+            if self.init[0].shape[0] != len(captions):
+                raise ValueError(f"{self.init[0].shape[0]} motions to start from for {len(captions)} captions")
+            self.strength = float(strength)
+        elif strength is not None:
+            raise ValueError("strength goes with init_motion, init_joints or init_bvh")
+        if (latents is None) != (latent_step is None):
+            raise ValueError("latents and latent_step go together: give both or neither")
+        if latents is not None:
+            if not torch.is_tensor(latents):
+                lat = [torch.as_tensor(v) for v in latents]
+                latents = torch.stack([pad_frames(v[None], max(u.shape[0] for u in lat))[0] for v in lat])
+            if latents.dim() != 3 or latents.shape[0] != len(captions) or latents.shape[2] != dim_pose:
+                raise ValueError(f"latents of shape {tuple(latents.shape)} must be (N = {len(captions)}, T, {dim_pose})")
+            if not bool(torch.isfinite(latents).all()):
+                raise ValueError("latents has non-finite values")
+            self.latents, self.latent_step = latents, latent_step
+        if init_bvh is not None and edit_bvh is None:
+            bvh_options = None  # they were the init files'
         edit_joints = joint_clips_from_bvh(edit_bvh, bvh_options, edit_joints, edit_motion, device)
         self.weights = None if prompt_weights is None else self._compose(captions, prompt_weights, dim_pose)
         self.edit = None
@@ -416,6 +495,39 @@ class Conditioning:
         return {"control_joints": g[:, :T].to(device), "control_weights": c["weights"][rows][:, :T].to(device),
                 "control_mean": c["mean"].to(device).expand(n, -1), "control_std": c["std"].to(device).expand(n, -1),
                 "control_scale": self.control_scale, "control_iters": self.control_iters}
+
+    def start_kwargs(self, rows, T, lengths, num_steps, sampler, device):
+        """Where the loop of the batch of rows ``rows`` at T frames starts, for a sampler of ``num_steps`` steps:
+        ``(loop arguments, result)``.  ({}, None): the plain loop (nothing given, or a strength that runs every step).
+        ``init_motion`` and ``start_step``: the rows' motions, their first T frames, and the step ``strength_steps`` maps the
+        strength to.  ({}, the motions): a strength that runs no step.  ``noise`` and ``start_step``: the rows' latents.
+        Raises ValueError for a motion with fewer rows than its sample's length, latents of fewer than T frames, latents
+        with a sampler other than "ddim", and a ``latent_step`` outside the schedule or from another step count."""
+        if self.latents is not None:
+            ls = self.latent_step
+            if sampler != "ddim":
+                raise ValueError(f'latents continue a DDIM inversion: they need sampler="ddim", not {sampler!r}')
+            if getattr(ls, "sample_steps", num_steps) != num_steps or not 0 <= int(ls) < num_steps:
+                raise ValueError(f"latent_step {int(ls)} (of {getattr(ls, 'sample_steps', '?')} steps) does not belong to this "
+                                 f"call's {num_steps}-step schedule: give the sample_steps of the inversion")
+            if self.latents.shape[1] < T:
+                raise ValueError(f"latents has {self.latents.shape[1]} frames, the batch {T}")
+            return {"noise": self.latents[rows][:, :T].to(device), "start_step": int(ls)}, None
+        if self.init is None:
+            return {}, None
+        n_run = strength_steps(self.strength, num_steps)
+        if n_run == num_steps:
+            return {}, None
+        x, have = self.init
+        ids = list(range(x.shape[0]))[rows] if isinstance(rows, slice) else rows.tolist()
+        for i, n in zip(ids, torch.as_tensor(lengths).flatten().tolist()):
+            if have[i] < min(int(n), T):
+                raise ValueError(f"sample {i}: a motion of {have[i]} rows to start from is shorter than its length "
+                                 f"{min(int(n), T)}")
+        x = pad_frames(x[rows], T)[:, :T].to(device, torch.float32)
+        if n_run == 0:
+            return {}, x.clone()
+        return {"init_motion": x, "start_step": n_run - 1}, None
 
     def kwargs(self, rows, T, device):
         """The ``model_kwargs`` entries of the batch of rows ``rows`` (a slice or an index tensor) at T frames."""

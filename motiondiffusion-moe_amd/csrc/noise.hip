@@ -6,14 +6,14 @@
 // The stream id is the timestep t of the step that consumes the noise (read from device memory, so one captured hipGraph
 // serves the whole loop) or MDM_NOISE_STREAM_XT for the initial x_T.
 // oracle/philox_ref.py restates the generator in numpy; tests compare bit patterns of the uniforms and the normals to 1e-6.
+// mdm_diffuse_start is the forward diffusion of a given motion to an intermediate level, out = a*x_start + s*n, in one launch:
+// n is drawn in registers on the x_T stream (the values mdm_noise_normal would write) or read from a given buffer, so a
+// sample's start is a function of (seed, global sample index) only, whatever the batch split.
 #include "kernels.h"
 #include "philox.h"
 
 namespace mdm {
 namespace {
-
-// u in (0, 1]: (bits + 1) * 2^-32 evaluated exactly in fp32 steps that the numpy oracle repeats
-__device__ __forceinline__ float u01(uint32_t b) { return ((float)(b >> 8) + 1.0f) * (1.0f / 16777216.0f); }
 
 __global__ void philox_normal_kernel(float* __restrict__ out, int64_t per_sample, int nsamples, int64_t sample0,
                                      const int64_t* __restrict__ sample_ids, uint64_t seed,
@@ -24,23 +24,52 @@ __global__ void philox_normal_kernel(float* __restrict__ out, int64_t per_sample
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t s = i / quads, qd = i - s * quads;
     const uint64_t gs = sample_ids ? (uint64_t)sample_ids[s] : (uint64_t)(sample0 + s);
-    uint32_t c[4] = {(uint32_t)qd, (uint32_t)gs, (uint32_t)(gs >> 32), stream};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     float z[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {  // Box-Muller on (u1, u2) = (c[2h], c[2h+1])
-      const float u1 = u01(c[2 * h]), u2 = u01(c[2 * h + 1]);
-      const float r = sqrtf(-2.0f * logf(u1));
-      float sn, cs;
-      sincosf(6.283185307179586f * u2, &sn, &cs);
-      z[2 * h] = r * cs, z[2 * h + 1] = r * sn;
-    }
+    philox_normal4(qd, gs, stream, seed, z);
     float* o = out + s * per_sample + 4 * qd;
     const int64_t left = per_sample - 4 * qd;
     if (left >= 4 && ((((uintptr_t)o) & 15) == 0)) {
       *(f32x4*)o = (f32x4){z[0], z[1], z[2], z[3]};
     } else {
       for (int k = 0; k < 4 && k < left; ++k) o[k] = z[k];
+    }
+  }
+}
+
+// One thread per quad of one sample, the quads of philox_normal_kernel.  out may be x_start (each element is read before it
+// is written, by the same thread: no __restrict__ on the two).  VEC: every base pointer 16-byte aligned -> dwordx4 loads and
+// stores on the whole quads of every row that starts on a 16-byte boundary; rows that do not (per_sample % 4 != 0) and each
+// row's last partial quad go element by element.  a*x + s*n is written out as fma(a, x, s*n): one rounding per product and sum,
+// the same in both forms.
+template <bool VEC>
+__global__ void __launch_bounds__(256) diffuse_start_kernel(const float* x_start, const float* __restrict__ noise, float* out,
+                                                            int64_t per_sample, int nsamples, int64_t sample0,
+                                                            const int64_t* __restrict__ sample_ids, uint64_t seed, float a,
+                                                            float s) {
+  const int64_t quads = (per_sample + 3) >> 2;
+  const int64_t total = quads * nsamples;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / quads, qd = i - r * quads;
+    const int64_t at = r * per_sample + 4 * qd, left = per_sample - 4 * qd;
+    const bool whole = left >= 4;
+    float z[4];
+    if (!noise) {
+      const uint64_t gs = sample_ids ? (uint64_t)sample_ids[r] : (uint64_t)(sample0 + r);
+      philox_normal4(qd, gs, (uint32_t)MDM_NOISE_STREAM_XT, seed, z);
+    }
+    if (VEC && whole && (at & 3) == 0) {
+      const f32x4 xv = *(const f32x4*)(x_start + at);
+      f32x4 nz;
+      if (noise) nz = *(const f32x4*)(noise + at);
+      else nz = (f32x4){z[0], z[1], z[2], z[3]};
+      f32x4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = fmaf(a, xv[k], s * nz[k]);
+      *(f32x4*)(out + at) = o;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)  // unrolled: z stays in registers
+        if (k < left) out[at + k] = fmaf(a, x_start[at + k], s * (noise ? noise[at + k] : z[k]));
     }
   }
 }
@@ -71,4 +100,25 @@ extern "C" int mdm_noise_normal_ids(float* out, int64_t per_sample, int32_t nsam
                                     const int32_t* stream_dev, int32_t stream_imm, void* stream) {
   if (!sample_ids) return MDM_ERR_ARG;
   return mdm::philox_normal(out, per_sample, nsamples, 0, sample_ids, seed, stream_dev, stream_imm, (hipStream_t)stream);
+}
+
+// out[r, e] = a * x_start[r, e] + s * n[r, e]: n from `noise` when given, else the x_T-stream draw of global sample
+// sample_ids[r] (when given) or sample0 + r
+extern "C" int mdm_diffuse_start(const float* x_start, const float* noise, float* out, int64_t per_sample, int32_t nsamples,
+                                 int64_t sample0, const int64_t* sample_ids, uint64_t seed, float a, float s, void* stream) {
+  if (!x_start || !out || per_sample < 0 || nsamples < 0 || sample0 < 0) return MDM_ERR_ARG;
+  if (!std::isfinite(a) || !std::isfinite(s)) return MDM_ERR_ARG;
+  if (per_sample == 0 || nsamples == 0) return MDM_OK;
+  const int64_t total = ((per_sample + 3) >> 2) * nsamples;
+  const int64_t blocks = (total + 255) / 256;
+  const dim3 grid((unsigned)(blocks > 2048 ? 2048 : blocks));
+  const bool vec = ((((uintptr_t)x_start) | ((uintptr_t)noise) | ((uintptr_t)out)) & 15) == 0;  // (NULL is aligned)
+  if (vec)
+    hipLaunchKernelGGL(mdm::diffuse_start_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x_start, noise, out, per_sample,
+                       nsamples, sample0, sample_ids, seed, a, s);
+  else
+    hipLaunchKernelGGL(mdm::diffuse_start_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x_start, noise, out,
+                       per_sample, nsamples, sample0, sample_ids, seed, a, s);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
 }

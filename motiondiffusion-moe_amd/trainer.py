@@ -14,8 +14,10 @@ BVH files from any rig (``motion_rig.bvh_to_joints``), and
 trajectories, keyframes, end positions (targets from ``motion_control``).  ``generate_long`` samples motions longer than
 the model's window from scripts of ``(caption, length)`` segments, overlapping windows tied together on every step
 (``motion_long``).  ``generate_bvh`` / ``generate_long_bvh`` end in BVH text for a rig (``motion_rig``,
-DESIGN.md §19).  Every generate method checks its conditioning once (``conditioning.Conditioning``) and
-samples each batch's rows through ``_sample_rows``.  The training loop (forward/backward/update/train) is out of scope for
+DESIGN.md §19).  ``init_motion`` / ``init_joints`` / ``init_bvh`` with ``strength`` start from a given motion instead of
+from noise: the motion is noised part of the way and only the remaining steps run; ``invert`` runs DDIM inversion and
+``generate(latents=, latent_step=)`` continues from its result.  Every generate method checks its
+conditioning once (``conditioning.Conditioning``) and samples each batch's rows through ``_sample_rows``.  The training loop (forward/backward/update/train) is out of scope for
 this build and raises.
 """
 from __future__ import annotations
@@ -23,8 +25,8 @@ from __future__ import annotations
 import torch
 
 from . import motion_long as ML
-from .conditioning import (Conditioning, check_joint_edit_mask, edit_rows_from_joints, expand_to, joint_clips_from_bvh,
-                           pad_frames)
+from .conditioning import (Conditioning, LatentStep, check_joint_edit_mask, edit_rows_from_joints, expand_to,
+                           joint_clips_from_bvh, pad_frames, strength_steps)
 from .diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType, SpacedDiffusion, get_named_beta_schedule,
                         space_timesteps)
 
@@ -87,6 +89,12 @@ class DDPMTrainer(object):
         if eta != 0.0 and sampler != "ddim":
             raise ValueError("eta applies to the ddim sampler only")
         d = self.sampling_diffusion(sampler, sample_steps)
+        start, done = cond.start_kwargs(rows, T, lengths, d.num_timesteps, sampler, self.device)
+        if done is not None:  # a strength that runs no step: the given motion
+            return done
+        if "noise" in start and kw.get("noise") is not None:
+            raise ValueError("latents are the start of the loop: noise / noises cannot be given as well")
+        kw.update(start)
         if sampler == "ddpm":
             return d.p_sample_loop_with_cfg(m, shape, **kw)
         if sampler == "ddim":
@@ -97,7 +105,8 @@ class DDPMTrainer(object):
     def generate_batch(self, caption, m_lens, dim_pose, *, noise=None, step_noise=None, progress=True, seed=None,
                        sample_offset=0, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
                        prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
-                       control_iters=1, mean=None, std=None, edit_joints=None, edit_bvh=None, bvh_options=None):
+                       control_iters=1, mean=None, std=None, edit_joints=None, edit_bvh=None, bvh_options=None,
+                       init_motion=None, init_joints=None, init_bvh=None, strength=None, latents=None, latent_step=None):
         """``edit_motion`` (B, T_max, dim_pose), normalised, and ``edit_mask`` broadcastable to it, values in [0, 1]: the
         batch's first T frames of both are kept where the mask is 1 (exactly, for a binary mask) and generated elsewhere.
         ``prompt_weights`` (B, K, ...) broadcastable to (B, K, T_max, dim_pose): ``caption[i]`` is then a sequence of K
@@ -110,10 +119,20 @@ class DDPMTrainer(object):
         rows, so the mask may keep frames up to n - 2.  ``edit_bvh``: B BVH texts, paths or parsed files in place of
         ``edit_joints``, read at the model's frame rate by ``motion_rig.bvh_to_joints`` under
         ``bvh_options`` (a dict of its ``joint_map`` / ``scale`` / ``up`` / ``basis`` / ``fps_out``) and from there on
-        treated as ``edit_joints``; exclusive with ``edit_joints`` and ``edit_motion``."""
+        treated as ``edit_joints``; exclusive with ``edit_joints`` and ``edit_motion``.
+        ``init_motion`` (B, T_max, dim_pose), normalised, with ``strength`` in [0, 1]: motion-to-motion.
+        The motion is noised to an intermediate level of the chosen sampler's schedule and ``round(strength * steps)``
+        steps run from there under the caption: 1 is the plain call (the motion is ignored), 0 returns the motion, values
+        in between stay the closer to it the smaller they are.  ``init_joints`` (B joint clips, needs ``mean`` / ``std``) or
+        ``init_bvh`` (B files, read under ``bvh_options``) in place of ``init_motion``, converted as ``edit_joints`` /
+        ``edit_bvh`` are; a clip must cover its sample's length.  It composes with the edit, prompt and control inputs,
+        which act on every step that runs.  ``latents`` (B, T, dim_pose) with ``latent_step``: x at that step of this
+        call's schedule, as ``invert`` returns them, to continue from; needs ``sampler="ddim"`` and the ``sample_steps``
+        of the inversion."""
         cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
                             control_scale, control_iters, mean, std, edit_joints, self.device, edit_bvh=edit_bvh,
-                            bvh_options=bvh_options)
+                            bvh_options=bvh_options, init_motion=init_motion, init_joints=init_joints, init_bvh=init_bvh,
+                            strength=strength, latents=latents, latent_step=latent_step)
         m_lens = torch.as_tensor(m_lens)
         T = min(int(m_lens.max()), self._model().num_frames)
         return self._sample_rows(cond, slice(0, len(caption)), m_lens, T, sampler, sample_steps, eta, progress=progress,
@@ -123,7 +142,8 @@ class DDPMTrainer(object):
     def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None, sampler="ddpm",
                  sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
                  control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,
-                 edit_bvh=None, bvh_options=None):
+                 edit_bvh=None, bvh_options=None, init_motion=None, init_joints=None, init_bvh=None, strength=None,
+                 latents=None, latent_step=None):
         """``seed``: sample i's noise is then a function of (seed, i) only (counter-based device generator), so the result
         does not depend on ``batch_size``; without it the torch generator is used, as in the reference.
         ``noises``: optional list with one ``(x_T, [step noise, ...])`` pair per batch, replacing the draws (parity tests).
@@ -133,12 +153,16 @@ class DDPMTrainer(object):
         batch takes its samples' rows.  ``control_joints`` (N, T_max, J, 3), ``control_weights``, ``control_scale``,
         ``control_iters``, ``mean``, ``std``: joint-position control, see ``generate_batch``; each batch takes its samples'
         rows.  ``edit_joints``: N joint clips in place of ``edit_motion``, see ``generate_batch``; ``edit_bvh`` /
-        ``bvh_options``: N BVH files in place of those, see ``generate_batch``."""
+        ``bvh_options``: N BVH files in place of those, see ``generate_batch``.  ``init_motion`` (N, T_max, dim_pose) /
+        ``init_joints`` / ``init_bvh`` with ``strength``: start from a given motion, see ``generate_batch``; each batch takes
+        its samples' rows and its first T frames, and with ``seed`` the noise mixed into sample i is a function of (seed, i).
+        ``latents`` (N, T, dim_pose, or a list of (T_i, dim_pose)) with ``latent_step``: continue from ``invert``'s result."""
         N = len(caption)
         self.eval_mode()
         cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
                             control_scale, control_iters, mean, std, edit_joints, self.device, edit_bvh=edit_bvh,
-                            bvh_options=bvh_options)
+                            bvh_options=bvh_options, init_motion=init_motion, init_joints=init_joints, init_bvh=init_bvh,
+                            strength=strength, latents=latents, latent_step=latent_step)
         all_output = []
         for cur in range(0, N, batch_size):
             end = min(cur + batch_size, N)
@@ -154,7 +178,8 @@ class DDPMTrainer(object):
     def generate_bucketed(self, caption, m_lens, dim_pose, batch_size=32, *, unit_length=4, seed=None, group=None,
                           progress=False, sampler="ddpm", sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None,
                           prompt_weights=None, control_joints=None, control_weights=None, control_scale=1.0,
-                          control_iters=1, mean=None, std=None, edit_joints=None, edit_bvh=None, bvh_options=None):
+                          control_iters=1, mean=None, std=None, edit_joints=None, edit_bvh=None, bvh_options=None,
+                          init_motion=None, init_joints=None, init_bvh=None, strength=None):
         """Evaluation-scale variant of ``generate``: same inputs and the same kind of result (a
         list of per-sample ``(T_batch, dim_pose)`` tensors in the caller's order, valid up to each sample's length),
         but batches hold samples of similar length (less padded work) and, under ``torch.distributed``, are dealt over
@@ -162,13 +187,16 @@ class DDPMTrainer(object):
         ``caption``) only -- the same as ``generate(..., seed=)`` -- so on each sample's valid frames the two give identical
         results whatever the bucketing (tests/test_sampler_gpu.py).  ``edit_motion`` / ``edit_mask``: as in ``generate``;
         each bucket takes its samples' rows and its first T frames; so do ``prompt_weights`` and the ``control_*`` tensors.
-        ``edit_joints``: joint clips in place of ``edit_motion``, as in ``generate``; so are ``edit_bvh`` / ``bvh_options``."""
+        ``edit_joints``: joint clips in place of ``edit_motion``, as in ``generate``; so are ``edit_bvh`` / ``bvh_options``.
+        ``init_motion`` / ``init_joints`` / ``init_bvh`` with ``strength``: as in ``generate``, each bucket taking its
+        samples' rows and its first T frames."""
         from . import dist as D
         m = self._model()
         self.eval_mode()
         cond = Conditioning(caption, dim_pose, edit_motion, edit_mask, prompt_weights, control_joints, control_weights,
                             control_scale, control_iters, mean, std, edit_joints, self.device, edit_bvh=edit_bvh,
-                            bvh_options=bvh_options)
+                            bvh_options=bvh_options, init_motion=init_motion, init_joints=init_joints, init_bvh=init_bvh,
+                            strength=strength)
         lens = torch.as_tensor(m_lens).flatten().long().cpu()
         plan = D.plan_buckets(lens, batch_size, m.num_frames, unit_length)
 
@@ -177,6 +205,40 @@ class DDPMTrainer(object):
                                      progress=progress, seed=seed, sample_offset=idx)
 
         return D.run_plan(plan, run_bucket, len(caption), m.num_frames, dim_pose, self.device, group)
+
+    @torch.no_grad()
+    def invert(self, caption, motions, m_lens, dim_pose, *, sample_steps=50, to_strength=1.0, cfg_scale=1.0, batch_size=8,
+               progress=False):
+        """DDIM inversion of given motions under their captions (``ddim_invert_loop``): ``motions`` is
+        (N, T_max, dim_pose) or a list of (T_i, dim_pose), normalised, each covering its ``m_lens`` entry.  Runs upwards on
+        the ``sample_steps``-step DDIM schedule to the step a ``strength=to_strength`` call would start at,
+        ``round(to_strength * sample_steps) - 1``, at ``cfg_scale`` (1.0: the caption alone, the scale at which a
+        regeneration under the same caption retraces the inversion).  Returns ``(latents, latent_step)``: a list of
+        (T_batch, dim_pose) tensors and the step they stand at, for ``generate(..., sampler="ddim", sample_steps=,
+        latents=, latent_step=)``."""
+        N = len(caption)
+        self.eval_mode()
+        d = self.sampling_diffusion("ddim", sample_steps)
+        n_run = strength_steps(to_strength, d.num_timesteps)
+        if n_run < 1:
+            raise ValueError("to_strength maps to no step: nothing to invert to")
+        if not torch.is_tensor(motions):
+            clips = [torch.as_tensor(v) for v in motions]
+            motions = torch.stack([pad_frames(v[None], max(u.shape[0] for u in clips))[0] for v in clips])
+        if motions.dim() != 3 or motions.shape[0] != N or motions.shape[2] != dim_pose:
+            raise ValueError(f"motions of shape {tuple(motions.shape)} must be (N = {N}, T_max, {dim_pose})")
+        out = []
+        for cur in range(0, N, batch_size):
+            end = min(cur + batch_size, N)
+            lens = torch.as_tensor(m_lens[cur:end])
+            T = min(int(lens.max()), self._model().num_frames)
+            if motions.shape[1] < T:
+                raise ValueError(f"motions has {motions.shape[1]} frames, the batch {T}")
+            x = d.ddim_invert_loop(self._model(), motions[cur:end, :T].to(self.device, torch.float32),
+                                   {"text": caption[cur:end], "length": lens}, to_step=n_run - 1, cfg_scale=cfg_scale,
+                                   progress=progress)
+            out.extend(x[i] for i in range(x.shape[0]))
+        return out, LatentStep(n_run - 1, d.num_timesteps)
 
     @torch.no_grad()
     def generate_for_evaluation(self, caption, m_lens, dim_pose, *, mm_num_samples=0, mm_num_repeats=1, unit_length=4,
@@ -358,7 +420,8 @@ class DDPMTrainer(object):
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
                       sample_steps=None, eta=0.0, edit_motion=None, edit_mask=None, noise=None, progress=False,
-                      edit_joints=None, mean=None, std=None, edit_bvh=None, bvh_options=None):
+                      edit_joints=None, mean=None, std=None, edit_bvh=None, bvh_options=None, init_motion=None,
+                      strength=None):
         """Long motions: ``scripts`` is a list of long motions, each a list of ``(caption, length)``
         segments of at most ``num_frames`` frames; neighbouring segments share ``overlap`` canvas frames, whose eps is
         blended on every step (``blend`` "linear" crossfade or "uniform") while x_T and the step noise come from the left
@@ -371,7 +434,9 @@ class DDPMTrainer(object):
         ``edit_joints`` (with ``mean`` / ``std``): one joint clip (n_i, J, 3) per motion in place of ``edit_motion``, e.g. the
         joints ``generate_long_joints`` returned, to be continued: its n_i - 1 rows start the canvas, and every motion
         needs its mask.  ``edit_bvh`` / ``bvh_options``: one BVH file per motion in place of ``edit_joints``, as in
-        ``generate``."""
+        ``generate``.  ``init_motion`` with ``strength``: one (canvas_len, dim_pose) motion per long motion to start from, as
+        in ``generate``: each window takes its frames of the canvas, and an overlap starts from its owner
+        window's noised values."""
         m = self._model()
         self.eval_mode()
         plans = ML.script_plans(scripts, overlap, m.num_frames)
@@ -391,7 +456,9 @@ class DDPMTrainer(object):
                 edit_motion.append(pad_frames(rows[i:i + 1, :n], plans[i][3])[0])
                 check_joint_edit_mask(expand_to(edit_mask[i], None, edit_motion[i].shape, "edit_mask")[None], [n])
         per = {}
-        for name, v in (("edit_motion", edit_motion), ("edit_mask", edit_mask), ("noise", noise)):
+        if (init_motion is None) != (strength is None):
+            raise ValueError("init_motion and strength go together: give both or neither")
+        for name, v in (("edit_motion", edit_motion), ("edit_mask", edit_mask), ("noise", noise), ("init_motion", init_motion)):
             if v is not None and len(v) != N:
                 raise ValueError(f"{name} must hold one entry per motion ({N}), not {len(v)}")
             per[name] = [None] * N if v is None else list(v)
@@ -400,7 +467,7 @@ class DDPMTrainer(object):
         for i, (km, mk) in enumerate(zip(per["edit_motion"], per["edit_mask"])):
             if (km is None) != (mk is None):
                 raise ValueError(f"motion {i}: edit_motion and edit_mask go together")
-        for name in ("edit_motion", "noise"):
+        for name in ("edit_motion", "noise", "init_motion"):
             if any(x is not None for x in per[name]) and not all(x is not None for x in per[name]):
                 raise ValueError(f"{name} must be given for every motion of the call or for none")
         out, first = [None] * N, 0
@@ -410,7 +477,7 @@ class DDPMTrainer(object):
             T = max(lens) + max(lens) % 2  # the denoiser takes even T
             kw = ML.batch_tables(plans, idx, T, overlap, blend)
             rows = {}  # the per-motion canvases given, as window rows
-            for name in ("edit_motion", "edit_mask", "noise"):
+            for name in ("edit_motion", "edit_mask", "noise", "init_motion"):
                 if per[name][idx[0]] is None:
                     continue
                 for i in idx:
@@ -419,8 +486,9 @@ class DDPMTrainer(object):
                 rows[name] = ML.gather_canvases(per[name], plans, idx, T, dim_pose, name).to(self.device)
             if "edit_motion" in rows:
                 kw.update(inpaint_motion=rows["edit_motion"], inpaint_mask=rows["edit_mask"])
-            res = self._sample_rows(Conditioning(caps, dim_pose), slice(None), torch.tensor(lens), T, sampler, sample_steps,
-                                    eta, extra=kw, progress=progress, noise=rows.get("noise"), seed=seed, sample_offset=first)
+            cond = Conditioning(caps, dim_pose, init_motion=rows.get("init_motion"), strength=strength)
+            res = self._sample_rows(cond, slice(None), torch.tensor(lens), T, sampler, sample_steps, eta, extra=kw,
+                                    progress=progress, noise=rows.get("noise"), seed=seed, sample_offset=first)
             first += len(caps)
             row = 0
             for i in idx:
