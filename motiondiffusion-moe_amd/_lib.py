@@ -5,6 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -254,3 +255,29 @@ def require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
             raise MdmError("mdm HIP path needs tensors on a GPU device (no CPU fallback)")
+
+
+def check_lengths(lengths, B: int, T: int, least: int = 1, why: str = "", message=None):
+    """``lengths`` as (B,) int64 on the CPU, every entry in [least, T].  Raises ValueError ``"lengths must have {B} entries"``
+    and ``"every length must lie in [{least}, {T}]{why}"``, or ``message`` for either."""
+    lengths = torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
+    if lengths.numel() != B:
+        raise ValueError(message or f"lengths must have {B} entries")
+    if B and (int(lengths.min()) < least or int(lengths.max()) > T):
+        raise ValueError(message or f"every length must lie in [{least}, {T}]{why}")
+    return lengths
+
+
+def mean_std(mean, std, F: int, dtype=torch.float32, values: bool = True):
+    """A dataset's ``mean`` / ``std`` (tensors, arrays or sequences) as flat CPU tensors of ``dtype`` with F entries each.
+    ``values``: also finite, and std without zeros.  Raises ValueError."""
+    mean, std = (torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v)).detach().to("cpu", dtype).flatten()
+                 for v in (mean, std))
+    if mean.numel() != F or std.numel() != F:
+        raise ValueError(f"mean/std must have {F} entries")
+    if values:
+        if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all())):
+            raise ValueError("mean / std have non-finite values")
+        if bool((std == 0).any()):
+            raise ValueError("std has zero entries")
+    return mean, std

@@ -242,15 +242,14 @@ def edit_rows_from_joints(edit_joints, mean, std, dim_pose, device=None, to_moti
     the HumanML3D nor the KIT width."""
     if mean is None or std is None:
         raise ValueError("edit_joints needs the dataset's mean and std (feature rows are normalised, joints are not)")
-    skeleton = {263: "t2m", 251: "kit"}.get(int(dim_pose))
+    from .motion_features import joints_to_motion, skeleton_for_feats
+    skeleton = skeleton_for_feats(dim_pose)
     if skeleton is None:
         raise ValueError(f"edit_joints needs dim_pose 263 (HumanML3D) or 251 (KIT), not {dim_pose}")
     if torch.is_tensor(edit_joints) or isinstance(edit_joints, np.ndarray):
         edit_joints = list(torch.as_tensor(edit_joints))
     clips = [torch.as_tensor(c) if device is None else torch.as_tensor(c).to(device) for c in edit_joints]
-    if to_motion is None:
-        from .motion_features import joints_to_motion as to_motion
-    rows = to_motion(clips, None, mean, std, skeleton=skeleton)
+    rows = (to_motion or joints_to_motion)(clips, None, mean, std, skeleton=skeleton)
     return rows, [int(c.shape[0]) - 1 for c in clips]
 
 
@@ -353,19 +352,35 @@ def pad_frames(x, T):
 
 
 class Conditioning:
-    """The checked conditioning of one generate call over N samples: ``captions`` (N strings, or N sequences of K strings
-    with ``prompt_weights``), ``edit_motion`` (N, T_max, dim_pose) with ``edit_mask`` broadcast to it, ``prompt_weights``
-    broadcast to (N, K, T_w, dim_pose) (T_w its frame dim, 1 when it has none; ``weights``), ``control_joints``
-    (N, T_max, J, 3) with ``control_weights`` broadcast to them and ``mean`` / ``std`` as float32 (dim_pose,) (``control``,
-    None without).  ``edit_joints`` in place of ``edit_motion``: N joint clips (n_i, J, 3), turned into feature rows once
-    (``edit_rows_from_joints``) and zero-padded to the mask's frames.  ``edit_bvh`` (with ``bvh_options``) in place of
-    ``edit_joints``: N BVH files, read into joint clips first (``joint_clips_from_bvh``).
-    ``init_motion`` / ``init_joints`` / ``init_bvh`` with ``strength``: the motion every sample starts from
-    (``init_rows_from``) and the share of the sampler's steps to run (``strength_steps``); ``latents`` with ``latent_step``
-    in their place: x at that step, e.g. from ``DDPMTrainer.invert``, to continue from.  ``start_kwargs`` hands out a
-    batch's share of either.
-    What does not depend on a batch is checked here, once; ``kwargs`` hands out a batch's rows and frames
-    (views of these tensors) and checks that they cover its T."""
+    """The checked conditioning of one generate call over N samples, and the one description of the conditioning keywords of
+    ``DDPMTrainer.generate_batch`` (N = its B) / ``generate`` / ``generate_bucketed``, which pass theirs on as
+    ``**conditioning``.  Tensors cover the call, T_max frames; what does not depend on a batch is checked here, once, and
+    ``kwargs`` / ``start_kwargs`` hand out a batch's rows and first T frames (views) and check that they cover its T.
+    ``captions``: N strings, or with ``prompt_weights`` N sequences of K strings.
+    ``edit_motion`` (N, T_max, dim_pose), normalised, and ``edit_mask`` broadcastable to it, values in [0, 1]: motion editing;
+    both are kept where the mask is 1 (exactly, for a binary mask) and generated elsewhere (``edit``).
+    ``prompt_weights`` (N, K, ...) broadcastable to (N, K, T_max, dim_pose): ``captions[i]`` is then a sequence of K captions,
+    composed on every step under these weights; kept as (N, K, T_w, dim_pose), T_w 1 without a frame dim
+    (``weights``).
+    ``control_joints`` (N, T_max, J, 3) target joint positions and ``control_weights`` (N, ...) broadcastable to them, with the
+    dataset's ``mean`` / ``std`` (dim_pose,), kept as float32: every step's x0 is moved ``control_iters`` times down the gradient
+    of the weighted squared distance, scaled by ``control_scale`` (units in ``motion_control``; ``control``).
+    ``edit_joints``: N joint clips (n_i, J, 3) in place of ``edit_motion`` (needs ``mean`` / ``std``), turned into feature rows
+    once per call (``edit_rows_from_joints``: ``motion_features.joints_to_motion``) and zero-padded to the mask's
+    frames; a clip of n frames gives n - 1 rows, so the mask may keep frames up to n - 2.
+    ``edit_bvh``: N BVH texts, paths or parsed files in place of ``edit_joints``, read into clips first (``joint_clips_from_bvh``)
+    at the model's frame rate by ``motion_rig.bvh_to_joints`` under ``bvh_options`` (a dict of its ``joint_map`` /
+    ``scale`` / ``up`` / ``basis`` / ``fps_out``), from there on treated as ``edit_joints``; exclusive with it and ``edit_motion``.
+    ``init_motion`` (N, T_max, dim_pose), normalised, with ``strength`` in [0, 1]: motion-to-motion (DESIGN.md §22;
+    ``init_rows_from``, ``strength_steps``).  The motion is noised to an intermediate level of the chosen sampler's schedule and
+    ``round(strength * steps)`` steps run from there under the caption: 1 is the plain call (the motion is ignored), 0 returns
+    the motion, values in between stay the closer to it the smaller they are; with the call's ``seed`` the noise mixed into
+    sample i is a function of (seed, i).  ``init_joints`` (N joint clips, needs ``mean`` / ``std``) or ``init_bvh`` (N files, read
+    under ``bvh_options``) in place of ``init_motion``, converted as ``edit_joints`` / ``edit_bvh`` are; a clip must cover its
+    sample's length.  It composes with the edit, prompt and control inputs, which act on every step that runs.
+    ``latents`` (N, T, dim_pose, or a list of (T_i, dim_pose)) with ``latent_step`` in their place: x at that step of this call's
+    schedule, as ``DDPMTrainer.invert`` returns them, to continue from; needs ``sampler="ddim"`` and the inversion's
+    ``sample_steps``.  ``device``: where clips and files are converted; ``to_motion``: see ``edit_rows_from_joints``."""
 
     def __init__(self, captions, dim_pose, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
                  control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,

@@ -74,6 +74,13 @@ def _kit():
 SKELETONS = {"t2m": _t2m(), "kit": _kit()}
 
 
+def skeleton_for_feats(dim_pose, strict=False):
+    """The name in ``SKELETONS`` of the skeleton whose feature rows are ``dim_pose`` wide (263: "t2m", 251: "kit"); for
+    another width None, or with ``strict`` the KeyError of a lookup."""
+    names = {sk.feats: name for name, sk in SKELETONS.items()}
+    return names[int(dim_pose)] if strict else names.get(int(dim_pose))
+
+
 def get_skeleton(skeleton):
     if isinstance(skeleton, str):
         if skeleton not in SKELETONS:
@@ -135,11 +142,7 @@ def check_joints(joints, lengths, mean, std, sk, target_offsets=None):
     if T < 2:
         raise ValueError("a clip needs at least 2 frames: n frames give n - 1 rows")
     if lengths is not None:
-        lengths = torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
-        if lengths.numel() != B:
-            raise ValueError(f"lengths must have {B} entries")
-        if int(lengths.min()) < 2 or int(lengths.max()) > T:
-            raise ValueError(f"every length must lie in [2, {T}]: n frames give n - 1 rows")
+        lengths = L.check_lengths(lengths, B, T, 2, ": n frames give n - 1 rows")
     joints = joints.to(torch.float32)
     bad = ~torch.isfinite(joints)
     if lengths is not None:  # frames past a clip's length are never read
@@ -149,14 +152,7 @@ def check_joints(joints, lengths, mean, std, sk, target_offsets=None):
     if (mean is None) != (std is None):
         raise ValueError("mean and std go together: give both or neither")
     if mean is not None:
-        mean, std = (torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v)).detach().to("cpu", torch.float32).flatten()
-                     for v in (mean, std))
-        if mean.numel() != F_ or std.numel() != F_:
-            raise ValueError(f"mean/std must have {F_} entries")
-        if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all())):
-            raise ValueError("mean / std have non-finite values")
-        if bool((std == 0).any()):
-            raise ValueError("std has zero entries")
+        mean, std = L.mean_std(mean, std, F_)
     if target_offsets is not None:
         target_offsets = torch.as_tensor(target_offsets).detach().to("cpu", torch.float32)
         if tuple(target_offsets.shape) != (J, 3) or not bool(torch.isfinite(target_offsets).all()):

@@ -10,8 +10,8 @@ window, then in the right one (``rows[e] = window_row * T + frame``).  On every 
 the two eps rows back into both (``weights``: a linear crossfade, the right window weighing ``(j + 1) / (h + 1)`` at overlap
 frame j, or ``"uniform"`` halves), and copies x_T and the step noise from the left ("owner") window into the right one.
 The overlap frames of neighbouring windows then stay bit for bit equal on every step, and the canvas is the windows' valid
-frames.  ``script_plans``, ``plan_batches``, ``batch_tables`` and ``gather_canvases`` are the host half of
-``DDPMTrainer.generate_long``.  Host logic only: runs without a GPU.
+frames.  ``script_plans``, ``canvas_conditioning``, ``plan_batches``, ``batch_tables`` and ``gather_canvases`` are the host
+half of ``DDPMTrainer.generate_long``.  Host logic only: runs without a GPU.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .conditioning import expand_to
+from .conditioning import check_joint_edit_mask, edit_rows_from_joints, expand_to, joint_clips_from_bvh, pad_frames
 
 BLENDS = ("linear", "uniform")
 
@@ -156,6 +156,59 @@ def gather_canvases(values, plans, idx, T: int, dim_pose: int, what: str) -> tor
                       fail_msg=f"{{name}} of motion {i} has shape {{shape}}, not broadcastable to its canvas {{target}}")
         parts.append(canvas_to_windows(x, starts, lens, T))
     return torch.cat(parts)
+
+
+def canvas_conditioning(plans, dim_pose, *, edit_motion=None, edit_mask=None, noise=None, init_motion=None, strength=None,
+                        edit_joints=None, mean=None, std=None, edit_bvh=None, bvh_options=None, device=None, to_motion=None):
+    """The per-motion inputs of ``DDPMTrainer.generate_long`` (described there), one entry per motion of ``plans`` each, checked
+    once for the call; joint clips and files become rows that start their canvas (``to_motion``: as in
+    ``conditioning.edit_rows_from_joints``).  Returns ``window_rows(idx, T)``: for the batch of motions ``idx`` at T frames a
+    dict of the inputs given, gathered into the batch's window rows on ``device``; it raises ValueError for a canvas of
+    another shape.  Raises ValueError for inputs that exclude each other, lack their partner, have not one entry per motion or
+    are given for some motions only, and for a clip longer than its canvas or cut short by its mask."""
+    N = len(plans)
+    if edit_bvh is not None or bvh_options is not None:
+        edit_joints = joint_clips_from_bvh(edit_bvh, bvh_options, edit_joints, edit_motion, device)
+    if edit_joints is not None:
+        if edit_motion is not None:
+            raise ValueError("edit_joints and edit_motion are exclusive: the known motion is given as joints or as rows")
+        if edit_mask is None or len(edit_joints) != N or len(edit_mask) != N or any(mk is None for mk in edit_mask):
+            raise ValueError(f"edit_joints needs one clip and one edit_mask per motion ({N})")
+        rows, nrows = edit_rows_from_joints(edit_joints, mean, std, dim_pose, device, to_motion)
+        edit_motion = []
+        for i, n in enumerate(nrows):
+            if n > plans[i][3]:
+                raise ValueError(f"motion {i}: a clip of {n} rows does not fit its canvas of {plans[i][3]} frames")
+            edit_motion.append(pad_frames(rows[i:i + 1, :n], plans[i][3])[0])
+            check_joint_edit_mask(expand_to(edit_mask[i], None, edit_motion[i].shape, "edit_mask")[None], [n])
+    per = {}
+    if (init_motion is None) != (strength is None):
+        raise ValueError("init_motion and strength go together: give both or neither")
+    for name, v in (("edit_motion", edit_motion), ("edit_mask", edit_mask), ("noise", noise), ("init_motion", init_motion)):
+        if v is not None and len(v) != N:
+            raise ValueError(f"{name} must hold one entry per motion ({N}), not {len(v)}")
+        per[name] = [None] * N if v is None else list(v)
+    if (edit_motion is None) != (edit_mask is None):
+        raise ValueError("edit_motion and edit_mask go together: give both or neither")
+    for i, (km, mk) in enumerate(zip(per["edit_motion"], per["edit_mask"])):
+        if (km is None) != (mk is None):
+            raise ValueError(f"motion {i}: edit_motion and edit_mask go together")
+    for name in ("edit_motion", "noise", "init_motion"):
+        if any(x is not None for x in per[name]) and not all(x is not None for x in per[name]):
+            raise ValueError(f"{name} must be given for every motion of the call or for none")
+
+    def window_rows(idx, T):
+        rows = {}
+        for name, values in per.items():
+            if values[idx[0]] is None:
+                continue
+            for i in idx:
+                if name != "edit_mask" and tuple(torch.as_tensor(values[i]).shape) != (plans[i][3], dim_pose):
+                    raise ValueError(f"{name} of motion {i} must be {(plans[i][3], dim_pose)}")
+            rows[name] = gather_canvases(values, plans, idx, T, dim_pose, name).to(device)
+        return rows
+
+    return window_rows
 
 
 def split_long(caption: str, total_frames: int, window: int, overlap: int) -> List[Tuple[str, int]]:

@@ -1,0 +1,108 @@
+"""The output chain of generated motions: rows -> joints -> rotations -> BVH, and joints -> frames -> GIF; what the output
+methods of ``DDPMTrainer`` run on the motions ``generate``, ``generate_bucketed`` or ``generate_long`` returned.  ``joints_batch``
+keeps the zero-padded batch the kernels work on: ``to_joints`` slices it per motion, ``to_bvh`` hands it on as it is.
+"""
+from __future__ import annotations
+
+import torch
+from torch.nn.utils.rnn import pad_sequence
+
+from .motion_features import pad_clips, skeleton_for_feats
+from .motion_render import gif_bytes, render_motion, write_gif
+from .motion_rig import DEFAULT_FPS, bvh_text, retime_ratio, rig_of, rotations_to_rig
+from .postprocess import fk_max_frames, motion_to_joints, motion_to_joints_fk, remove_foot_skate
+
+MAX_JOINTS_FRAMES = 3276  # frames of mdm_motion_postprocess: 5 T floats of LDS per workgroup, 64 KiB
+
+
+def valid_lengths(motions, m_lens=None):
+    """Every generated motion's ``m_lens`` entry, at most the frames it has; without ``m_lens`` all it has."""
+    if m_lens is None:
+        return [mo.shape[0] for mo in motions]
+    return [min(int(n), mo.shape[0]) for n, mo in zip(torch.as_tensor(m_lens).flatten().tolist(), motions)]
+
+
+def check_paths(paths, n, what):
+    if paths is not None and len(paths) != n:
+        raise ValueError(f"paths must hold one entry per {what} ({n}), or None")
+
+
+def canvas_frame_limit(forward_kinematics=False):
+    """The longest canvas the long variants take: with forward kinematics (``from_rotations``, BVH) ``fk_max_frames()``."""
+    return fk_max_frames() if forward_kinematics else MAX_JOINTS_FRAMES
+
+
+def joints_batch(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotations=False, offsets=None,
+                 return_rotations=False, fix_feet=False, blend=5):
+    """``postprocess.motion_to_joints`` over the first ``lens[i]`` frames of every motion, or with ``from_rotations``
+    ``postprocess.motion_to_joints_fk``: one launch for all.  -> (joints (B, T, J, 3), rotations (B, T, J, 3, 3), offsets
+    (B, J, 3), lens), zero past each length; rotations and offsets are None without forward kinematics.  ``fix_feet``:
+    ``postprocess.remove_foot_skate`` on the result, filtered first (filtering afterwards would smear the pins), labels from
+    the rows' contact columns read in place; rotations go through it, so that joints and rotations still agree."""
+    skel = skeleton_for_feats(dim_pose)
+    if fix_feet and (skel is None or dim_pose != 12 * joints_num - 1):
+        raise ValueError(f"fix_feet needs dim_pose 263 (22 joints) or 251 (21), not {dim_pose} ({joints_num})")
+    if (offsets is not None or return_rotations) and not from_rotations:
+        raise ValueError("offsets and rotations belong to forward kinematics: pass from_rotations=True")
+    x = pad_sequence(list(motions), batch_first=True)  # (B, longest, dim_pose), zero past each motion
+    if not from_rotations:
+        j = motion_to_joints(x, mean, std, torch.tensor(lens), joints_num, sigma)
+        if fix_feet:
+            j = remove_foot_skate(j, torch.tensor(lens), (x, mean, std), skeleton=skel, blend=blend)
+        return j, None, None, lens
+    if dim_pose != 12 * joints_num - 1 or dim_pose not in (263, 251):
+        raise ValueError(f"forward kinematics needs dim_pose 263 (22 joints) or 251 (21), not {dim_pose} ({joints_num})")
+    if isinstance(offsets, (list, tuple)):
+        offsets = torch.stack([torch.as_tensor(o).to("cpu", torch.float32) for o in offsets])
+    j, r, o = motion_to_joints_fk(x, mean, std, torch.tensor(lens), offsets, skeleton=skel, sigma=sigma,
+                                  return_rotations=True, return_offsets=True)
+    if fix_feet:
+        j, r = remove_foot_skate(j, torch.tensor(lens), (x, mean, std), skeleton=skel, blend=blend, rotations=r)
+    return j, r, o, lens
+
+
+def to_joints(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotations=False, offsets=None,
+              return_rotations=False, fix_feet=False, blend=5):
+    """``joints_batch`` as a list per motion: joints (lens[i], J, 3), or with ``return_rotations`` (joints, rotations, offsets)."""
+    j, r, o, lens = joints_batch(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotations, offsets,
+                                 return_rotations, fix_feet, blend)
+    if return_rotations:
+        return [(j[i, :n], r[i, :n], o[i]) for i, n in enumerate(lens)]
+    return [j[i, :n] for i, n in enumerate(lens)]
+
+
+def to_bvh(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, paths, fps, fps_out, euler, scale):
+    """Rows -> one BVH text per motion: ``joints_batch`` with rotations and no filter, one
+    ``motion_rig.rotations_to_rig`` over the padded batch, ``motion_rig.bvh_text`` per sample."""
+    j, r, o, lens = joints_batch(motions, lens, dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True, offsets, True,
+                                 fix_feet=fix_feet, blend=blend)
+    skel = skeleton_for_feats(dim_pose)
+    rig = rig_of(skel)
+    chan, lens_out = rotations_to_rig(j[:, :max(lens)], r[:, :max(lens)], torch.tensor(lens), skeleton=skel, euler=euler,
+                                      fps=fps, fps_out=fps_out, scale=scale)
+    num, den, fps = retime_ratio(skel, fps, fps_out)
+    frame_time = den / (num * float(fps))
+    chan, texts = chan.cpu(), []
+    for i in range(len(lens)):
+        texts.append(bvh_text(rig, o[i], chan[i], int(lens_out[i]), frame_time, euler=euler, scale=scale))
+        if paths is not None and paths[i] is not None:
+            with open(paths[i], "w") as f:
+                f.write(texts[-1])
+    return texts
+
+
+def to_frames(joints, size, camera, palette, style):
+    """``motion_render.render_motion`` over a list of (n_i, J, 3) joint clips, one launch for all: a list of
+    ``(n_i, H, W, 3)`` uint8 frames, or ``(n_i, H, W)`` palette indices."""
+    x, lens = pad_clips(joints, joints[0].shape[1])
+    frames = render_motion(x, lens, size=size, camera=camera, palette=palette, **(style or {}))
+    return [frames[i, :n] for i, n in enumerate(lens.tolist())]
+
+
+def to_gifs(frames, dim_pose, paths, fps):
+    """One GIF per clip of palette frames: bytes, or ``paths[i]`` where given and written; ``fps`` defaults by ``dim_pose``."""
+    if fps is None:
+        fps = DEFAULT_FPS.get(skeleton_for_feats(dim_pose), DEFAULT_FPS["t2m"])
+    if paths is None:
+        return [gif_bytes(f, fps) for f in frames]
+    return [gif_bytes(f, fps) if p is None else write_gif(f, p, fps) for f, p in zip(frames, paths)]

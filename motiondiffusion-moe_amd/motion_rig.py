@@ -121,11 +121,7 @@ def check_rig(joints, rotations, lengths, skeleton, euler="ZXY", fps=None, fps_o
         raise ValueError("scale must be finite")
     num, den, _ = retime_ratio(skeleton, fps, fps_out)
     if lengths is not None:
-        lengths = torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
-        if lengths.numel() != B:
-            raise ValueError(f"lengths must have {B} entries")
-        if B and (int(lengths.min()) < 1 or int(lengths.max()) > T):
-            raise ValueError(f"every length must lie in [1, {T}]")
+        lengths = L.check_lengths(lengths, B, T)
     n = torch.full((B,), T, dtype=torch.int64) if lengths is None else lengths
     lengths_out = (n - 1) * num // den + 1
     if B and int(lengths_out.max()) * (3 + 3 * rig.n_nodes) >= 2 ** 31:
@@ -570,9 +566,8 @@ def rig_joints(values, lengths, bvh, pick, num=1, den=1, *, scale=1.0, basis=UP_
     values = values.contiguous()
     dev = values.device
     B, T, width = values.shape
-    n = torch.full((B,), T, dtype=torch.int64) if lengths is None else torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
-    if n.numel() != B or (B and (int(n.min()) < 1 or int(n.max()) > T)):
-        raise ValueError(f"lengths must have {B} entries in [1, {T}]")
+    n = torch.full((B,), T, dtype=torch.int64) if lengths is None else \
+        L.check_lengths(lengths, B, T, message=f"lengths must have {B} entries in [1, {T}]")
     lengths_out = (n - 1) * num // den + 1
     parent, offsets, rot_col, rot_axis, pick = import_tables(bvh, pick)
     N, n_pick = len(parent), len(pick)

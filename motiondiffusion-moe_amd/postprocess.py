@@ -42,10 +42,7 @@ def motion_to_joints(motion: torch.Tensor, mean, std, lengths: Optional[torch.Te
     if x.dim() == 2:
         x = x[None]
     B, T, Fe = x.shape
-    mean_t = torch.as_tensor(np.asarray(mean), dtype=torch.float32).to(dev).contiguous()
-    std_t = torch.as_tensor(np.asarray(std), dtype=torch.float32).to(dev).contiguous()
-    if mean_t.numel() != Fe or std_t.numel() != Fe:
-        raise ValueError(f"mean/std must have {Fe} entries")
+    mean_t, std_t = (v.to(dev) for v in L.mean_std(mean, std, Fe, values=False))
     w = gaussian_taps(sigma)
     radius = len(w) - 1
     w_t = torch.from_numpy(w).to(dev)
@@ -85,20 +82,9 @@ def check_fk(motion, mean, std, lengths, offsets, sk):
     B, T = x.shape[:2]
     if T < 1:
         raise ValueError("a motion needs at least 1 frame")
-    mean, std = (torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v)).detach().to("cpu", torch.float32).flatten()
-                 for v in (mean, std))
-    if mean.numel() != F_ or std.numel() != F_:
-        raise ValueError(f"mean/std must have {F_} entries")
-    if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all())):
-        raise ValueError("mean / std have non-finite values")
-    if bool((std == 0).any()):
-        raise ValueError("std has zero entries")
+    mean, std = L.mean_std(mean, std, F_)
     if lengths is not None:
-        lengths = torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
-        if lengths.numel() != B:
-            raise ValueError(f"lengths must have {B} entries")
-        if B and (int(lengths.min()) < 1 or int(lengths.max()) > T):
-            raise ValueError(f"every length must lie in [1, {T}]")
+        lengths = L.check_lengths(lengths, B, T)
     if offsets is not None:
         offsets = torch.as_tensor(offsets).detach().to("cpu", torch.float32)
         if tuple(offsets.shape) not in ((J, 3), (B, J, 3)) or not bool(torch.isfinite(offsets).all()):
@@ -199,11 +185,7 @@ def check_foot_skate(joints, lengths, contacts, rotations, sk, blend=5, contact_
     if int(blend) != blend or blend < 0:
         raise ValueError("blend must be a whole number of frames >= 0")
     if lengths is not None:
-        lengths = torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
-        if lengths.numel() != B:
-            raise ValueError(f"lengths must have {B} entries")
-        if B and (int(lengths.min()) < 1 or int(lengths.max()) > T):
-            raise ValueError(f"every length must lie in [1, {T}]")
+        lengths = L.check_lengths(lengths, B, T)
     feet_thre = sk.feet_thre if feet_thre is None else float(feet_thre)
     if not feet_thre >= 0:
         raise ValueError("feet_thre must be >= 0")
@@ -217,10 +199,7 @@ def check_foot_skate(joints, lengths, contacts, rotations, sk, blend=5, contact_
             rows = rows[None]
         if tuple(rows.shape) != (B, T, F_):
             raise ValueError(f"contacts: motion of shape {tuple(rows.shape)} must be ({B}, {T}, {F_})")
-        mean, std = (torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v)).detach().to("cpu", torch.float64).flatten()
-                     for v in (mean, std))
-        if mean.numel() != F_ or std.numel() != F_:
-            raise ValueError(f"mean/std must have {F_} entries")
+        mean, std = L.mean_std(mean, std, F_, torch.float64, values=False)  # only the contact columns are read
         if not (bool(torch.isfinite(mean[-4:]).all()) and bool(torch.isfinite(std[-4:]).all()) and bool((std[-4:] > 0).all())):
             raise ValueError("mean / std of the contact columns must be finite, std > 0")
         thre = ((float(contact_thre) - mean[-4:]) / std[-4:]).to(torch.float32)  # fp64 on the host, rounded once

@@ -132,11 +132,11 @@ def test_argument_checks_need_no_device():
         P.recover_from_rot(good, 22, torch.zeros(22, 3), skeleton="kit")
     with pytest.raises(L.MdmError):
         P.recover_from_rot(good, 22, torch.zeros(22, 3))
-    Tr = pkg("trainer").DDPMTrainer
+    MO = pkg("motion_outputs")
     with pytest.raises(ValueError, match="from_rotations"):
-        Tr._to_joints([good[0]], [6], 263, mean, std, 22, 1.0, offsets=torch.zeros(22, 3))
+        MO.to_joints([good[0]], [6], 263, mean, std, 22, 1.0, offsets=torch.zeros(22, 3))
     with pytest.raises(ValueError, match="dim_pose"):
-        Tr._to_joints([torch.zeros(6, 100)], [6], 100, mean, std, 22, 1.0, from_rotations=True)
+        MO.to_joints([torch.zeros(6, 100)], [6], 100, mean, std, 22, 1.0, from_rotations=True)
 
 
 def test_entry_point_checks_and_frame_limit():
