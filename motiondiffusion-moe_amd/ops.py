@@ -13,44 +13,33 @@ from . import _lib as L
 class PackedWeight:
     """16-bit planes of an fp32 [N, K] weight, K zero-padded to a multiple of 32.
     fmt "bf16x2": bf16 hi + lo planes (`lo` = rn(w - hi), the bf16x3 fp32-grade mode; `hi` alone serves a single bf16 pass);
-    "bf16": hi plane only; "f16": one IEEE fp16 plane in `hi` (single fp16 pass, include/mdm_hip.h MDM_H16_F16)."""
+    "bf16": hi plane only; "f16": one IEEE fp16 plane in `hi` (single fp16 pass, include/mdm_hip.h MDM_H16_F16);
+    "f8": e4m3 bytes (K padded to 128) in `hi`, per-row fp32 scales (amax / 448) in `lo` (csrc/gemm8.hip)."""
+
+    # fmt -> (K pad multiple, dtype of `hi`, pack entry)
+    _FORMATS = {"bf16x2": (32, torch.bfloat16, "mdm_pack_bf16"), "bf16": (32, torch.bfloat16, "mdm_pack_bf16"),
+                "f16": (32, torch.float16, "mdm_pack_f16"), "f8": (128, torch.uint8, "mdm_pack_fp8")}
 
     def __init__(self, w: torch.Tensor, with_lo: bool = True, fmt: Optional[str] = None):
         L.require_cuda(w)
         fmt = fmt or ("bf16x2" if with_lo else "bf16")
-        if fmt not in ("bf16x2", "bf16", "f16", "f8"):
+        if fmt not in self._FORMATS:
             raise ValueError(f"unknown packed weight format {fmt!r}")
         self.fmt = fmt
-        with_lo = fmt == "bf16x2"
-        if fmt == "f8":  # e4m3 bytes (K padded to 128) in `hi`, per-row fp32 scales (amax / 448) in `lo`: csrc/gemm8.hip
-            w = w.detach().to(torch.float32)
-            self.lead = tuple(w.shape[:-2])
-            n, k = w.shape[-2], w.shape[-1]
-            w2 = w.reshape(-1, k).contiguous()
-            kp = (k + 127) // 128 * 128
-            self.N, self.K, self.Kp = n, k, kp
-            self.hi = torch.empty((w2.shape[0], kp), dtype=torch.uint8, device=w.device)
-            self.lo = torch.empty((w2.shape[0],), dtype=torch.float32, device=w.device)
-            with torch.cuda.device(w.device):
-                L.check(L.lib().mdm_pack_fp8(w2.data_ptr(), k, w2.shape[0], k, self.hi.data_ptr(), kp, self.lo.data_ptr(),
-                                             L.stream_ptr()), "mdm_pack_fp8")
-            return
+        pad, hi_dtype, entry = self._FORMATS[fmt]
         w = w.detach().to(torch.float32)
-        lead = w.shape[:-2]
+        self.lead = tuple(w.shape[:-2])
         n, k = w.shape[-2], w.shape[-1]
         w2 = w.reshape(-1, k).contiguous()
-        kp = (k + 31) // 32 * 32
+        rows, kp = w2.shape[0], (k + pad - 1) // pad * pad
         self.N, self.K, self.Kp = n, k, kp
-        self.hi = torch.empty((w2.shape[0], kp), dtype=torch.float16 if fmt == "f16" else torch.bfloat16, device=w.device)
-        self.lo = torch.empty_like(self.hi) if with_lo else None
+        self.hi = torch.empty((rows, kp), dtype=hi_dtype, device=w.device)
+        self.lo = (torch.empty((rows,), dtype=torch.float32, device=w.device) if fmt == "f8" else
+                   torch.empty_like(self.hi) if fmt == "bf16x2" else None)
+        planes = {"mdm_pack_bf16": (self.hi.data_ptr(), L.ptr(self.lo), kp), "mdm_pack_f16": (self.hi.data_ptr(), kp),
+                  "mdm_pack_fp8": (self.hi.data_ptr(), kp, L.ptr(self.lo))}[entry]
         with torch.cuda.device(w.device):
-            if fmt == "f16":
-                L.check(L.lib().mdm_pack_f16(w2.data_ptr(), k, w2.shape[0], k, self.hi.data_ptr(), kp, L.stream_ptr()),
-                        "mdm_pack_f16")
-            else:
-                L.check(L.lib().mdm_pack_bf16(w2.data_ptr(), k, w2.shape[0], k, self.hi.data_ptr(), L.ptr(self.lo), kp,
-                                              L.stream_ptr()), "mdm_pack_bf16")
-        self.lead = tuple(lead)
+            L.check(getattr(L.lib(), entry)(w2.data_ptr(), k, rows, k, *planes, L.stream_ptr()), entry)
 
     def operand(self, row_offset: int = 0) -> L.Operand:
         o = L.Operand()
@@ -159,88 +148,85 @@ def gemm_fp8(a8: torch.Tensor, a_scale: Optional[torch.Tensor], w: PackedWeight,
     return out if out is not None else out8
 
 
-def mlp_stream_pack(w1: torch.Tensor, w2: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """Weight stream of the streamed-weight fused MLP (csrc/mlp_stream.hip, include/mdm_hip.h mdm_mlp_stream_pack):
-    fp32 w1 (G, F, Din) / w2 (G, Dout, F) (or without the group axis) -> one 16-bit buffer holding, per (group, wave), the
-    1-KiB MFMA fragments of both layers in the order the wave consumes them (+ 16 KiB of tail padding)."""
-    L.require_cuda(w1, w2)
-    if w1.dim() == 2:
-        w1, w2 = w1[None], w2[None]
-    G, F, Din = w1.shape
-    Dout = w2.shape[1]
-    assert w2.shape == (G, Dout, F) and dtype in (torch.float16, torch.bfloat16)
-    w1 = w1.detach().to(torch.float32).contiguous()
-    w2 = w2.detach().to(torch.float32).contiguous()
-    n = L.lib().mdm_mlp_stream_elems(G, F, Din, Dout)
-    out = torch.empty(n, dtype=dtype, device=w1.device)
-    with torch.cuda.device(w1.device):
-        L.check(L.lib().mdm_mlp_stream_pack(w1.data_ptr(), w2.data_ptr(), G, F, Din, Dout,
-                                            L.H16_F16 if dtype == torch.float16 else L.H16_BF16, out.data_ptr(), L.stream_ptr()),
-                "mdm_mlp_stream_pack")
+# The five weight-stream formats: kind -> (entry stem of `<stem>_elems` / `<stem>_pack`, arguments of the size
+# query, arguments of the packer between its matrices and (out, stream)).  The matrices are [G, N, K] (a 2-D one is G = 1);
+# N2 = rows of the second matrix of an MLP pair, h16 = MDM_H16_* of the stream (kinds without it are bf16 (hi, lo) pairs), a K in
+# the packer's list is the source's row stride.
+_STREAM_ABI = {
+    "mlp": ("mdm_mlp_stream", "G N K N2", "G N K N2 h16"),      # fused MLP, csrc/mlp_stream.hip
+    "style": ("mdm_gemm_stream", "N K", "N K h16"),             # stylization, 16-bit, csrc/style_gemm.hip
+    "style3": ("mdm_gemm_stream3", "N K", "N K"),               # stylization, (hi, lo) pairs, csrc/style_gemm.hip style_gemm3
+    "frag": ("mdm_gemm_stream1", "N K", "K N K h16"),           # plain Linear, csrc/gemm_stream.hip
+    "expert3": ("mdm_gemm_stream3x", "G N K", "K G N K"),       # expert (hi, lo) pairs, csrc/gemm_stream3.hip
+}
+
+
+def _stream_dims(kind: str, shapes) -> dict:
+    shapes = [(1,) * (3 - len(s)) + tuple(s) for s in shapes]
+    (G, N, K), last = shapes[0], shapes[-1]
+    if len(shapes) != (2 if kind == "mlp" else 1) or (kind == "mlp" and (last[0], last[2]) != (G, N)):  # w2 is [G, Dout, F]
+        raise ValueError(f"{kind} stream: unexpected matrix shapes {shapes}")
+    if G != 1 and "G" not in _STREAM_ABI[kind][1]:
+        raise ValueError(f"{kind} stream takes one [N, K] matrix")
+    return dict(G=G, N=N, K=K, N2=last[1])
+
+
+def stream_elems(kind: str, *shapes) -> int:
+    """Elements of the `kind` stream of matrices of these shapes ([G, N, K] or [N, K]); <= 0: the library takes no such shape.
+    A host-only query."""
+    d = _stream_dims(kind, shapes)
+    stem, query, _ = _STREAM_ABI[kind]
+    return getattr(L.lib(), stem + "_elems")(*(d[a] for a in query.split()))
+
+
+def pack_stream(kind: str, *mats: torch.Tensor, dtype: Optional[torch.dtype] = None) -> Optional[torch.Tensor]:
+    """fp32 matrices -> the weight stream of `kind`: the same values in the MFMA fragment order its consumer reads.  `dtype`
+    (float16 / bfloat16) for the 16-bit kinds; the pair kinds are bf16.  None when the library takes no such shape (the size
+    query of the fused-MLP kind is positive for every shape: its packer refuses instead, which raises)."""
+    L.require_cuda(*mats)
+    stem, _, order = _STREAM_ABI[kind]
+    if "h16" not in order:
+        dtype = dtype or torch.bfloat16
+    assert dtype in ((torch.float16, torch.bfloat16) if "h16" in order else (torch.bfloat16,)), (kind, dtype)
+    d = _stream_dims(kind, [m.shape for m in mats])
+    d["h16"] = L.H16_F16 if dtype == torch.float16 else L.H16_BF16
+    n = stream_elems(kind, *(m.shape for m in mats))
+    if n <= 0:
+        return None
+    mats = [m.detach().to(torch.float32).contiguous() for m in mats]
+    out = torch.empty(n, dtype=dtype, device=mats[0].device)
+    with torch.cuda.device(out.device):
+        L.check(getattr(L.lib(), stem + "_pack")(*(m.data_ptr() for m in mats), *(d[a] for a in order.split()), out.data_ptr(),
+                                                 L.stream_ptr()), stem + "_pack")
     return out
+
+
+def mlp_stream_pack(w1: torch.Tensor, w2: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """fp32 w1 (G, F, Din) / w2 (G, Dout, F) (or without the group axis) -> one 16-bit buffer holding, per (group, wave), the
+    1-KiB MFMA fragments of both layers in the order the wave consumes them (+ 16 KiB of tail padding)."""
+    return pack_stream("mlp", w1, w2, dtype=dtype)
 
 
 def gemm_stream_pack(w: torch.Tensor, dtype: torch.dtype) -> Optional[torch.Tensor]:
-    """Weight stream of one fp32 Linear [N, K] for the fused stylization kernel (csrc/style_gemm.hip); None when the shape
-    is not taken (N = K = 512 only)."""
-    L.require_cuda(w)
-    N, K = w.shape
-    n = L.lib().mdm_gemm_stream_elems(N, K)
-    if n <= 0:
-        return None
-    w = w.detach().to(torch.float32).contiguous()
-    out = torch.empty(n, dtype=dtype, device=w.device)
-    with torch.cuda.device(w.device):
-        L.check(L.lib().mdm_gemm_stream_pack(w.data_ptr(), N, K, L.H16_F16 if dtype == torch.float16 else L.H16_BF16,
-                                             out.data_ptr(), L.stream_ptr()), "mdm_gemm_stream_pack")
-    return out
+    """One fp32 Linear [N, K] for the fused stylization kernel; None when the shape is not taken (N = K = 512 only)."""
+    return pack_stream("style", w, dtype=dtype)
 
 
 def gemm_stream1_pack(w: torch.Tensor, dtype: torch.dtype) -> Optional[torch.Tensor]:
-    """Fragment stream of one fp32 Linear [N, K] for the streamed-weight GEMM of the 16-bit modes (csrc/gemm_stream.hip;
-    MdmGemmDesc.w_stream / MdmPacked.ws); None when the shape is not covered (N % 256, K % 256)."""
-    L.require_cuda(w)
-    N, K = w.shape
-    n = L.lib().mdm_gemm_stream1_elems(N, K)
-    if n <= 0:
-        return None
-    w = w.detach().to(torch.float32).contiguous()
-    out = torch.empty(n, dtype=dtype, device=w.device)
-    with torch.cuda.device(w.device):
-        L.check(L.lib().mdm_gemm_stream1_pack(w.data_ptr(), K, N, K, L.H16_F16 if dtype == torch.float16 else L.H16_BF16,
-                                              out.data_ptr(), L.stream_ptr()), "mdm_gemm_stream1_pack")
-    return out
+    """One fp32 Linear [N, K] for the streamed-weight GEMM of the 16-bit modes (MdmGemmDesc.w_stream / MdmPacked.ws); None when
+    the shape is not covered (N % 256, K % 256)."""
+    return pack_stream("frag", w, dtype=dtype)
 
 
 def gemm_stream3x_pack(w: torch.Tensor) -> Optional[torch.Tensor]:
-    """(bf16 hi, lo) fragment-pair stream of G stacked fp32 Linears [G, N, K] (or one [N, K]) for the streamed-weight bf16x3 GEMM
-    (csrc/gemm_stream3.hip; MdmGemmDesc.w_stream with pre-split activation rows); None when the shape is not covered."""
-    L.require_cuda(w)
-    w3 = w if w.dim() == 3 else w[None]
-    G, N, K = w3.shape
-    n = L.lib().mdm_gemm_stream3x_elems(G, N, K)
-    if n <= 0:
-        return None
-    w3 = w3.detach().to(torch.float32).contiguous()
-    out = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-    with torch.cuda.device(w.device):
-        L.check(L.lib().mdm_gemm_stream3x_pack(w3.data_ptr(), K, G, N, K, out.data_ptr(), L.stream_ptr()), "mdm_gemm_stream3x_pack")
-    return out
+    """G stacked fp32 Linears [G, N, K] (or one [N, K]) for the streamed-weight bf16x3 GEMM (MdmGemmDesc.w_stream with pre-split
+    activation rows); None when the shape is not covered."""
+    return pack_stream("expert3", w)
 
 
 def gemm_stream3_pack(w: torch.Tensor) -> Optional[torch.Tensor]:
-    """(bf16 hi, lo) fragment-pair stream of one fp32 Linear [N, K] for the fp32-grade form of the fused stylization kernel
-    (csrc/style_gemm.hip style_gemm3); None when the shape is not taken (N = K = 512 only)."""
-    L.require_cuda(w)
-    N, K = w.shape
-    n = L.lib().mdm_gemm_stream3_elems(N, K)
-    if n <= 0:
-        return None
-    w = w.detach().to(torch.float32).contiguous()
-    out = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-    with torch.cuda.device(w.device):
-        L.check(L.lib().mdm_gemm_stream3_pack(w.data_ptr(), N, K, out.data_ptr(), L.stream_ptr()), "mdm_gemm_stream3_pack")
-    return out
+    """One fp32 Linear [N, K] for the fp32-grade form of the fused stylization kernel; None when the shape is not taken."""
+    return pack_stream("style3", w)
 
 
 def mlp_stream_pack_reference(w1: torch.Tensor, w2: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:

@@ -1,13 +1,15 @@
 """Weight packing: reference ``state_dict`` layout -> kernel layouts -> ``MdmModel`` (include/mdm_hip.h).
 
-Two stages so the layout logic is checkable without a GPU:
+Three stages so the layout logic and the choice of weight streams are checkable without a GPU:
   * ``kernel_layout(sd, cfg, eph, proj)``: pure tensor reshapes/concats (fp32, any device);
-  * ``PackedModel(...)``: uploads, splits every matrix into bf16 hi/lo planes with the HIP pack kernel and
-    fills the ctypes structs.  Runs once per (weights, captured randomness), never on the hot path.
+  * ``stream_plan(cfg, precision)``: which matrices are also packed as weight streams, and for which struct field (pure);
+  * ``PackedModel(...)``: uploads, splits every matrix into 16-bit planes with the HIP pack kernels, packs the planned streams
+    and fills the ctypes structs.  Runs once per (weights, captured randomness, precision), never on the hot path.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from typing import Dict, List, Tuple
 
 import torch
@@ -22,12 +24,6 @@ STYLE_SLOTS = ("local_style", "global_style", "cross_style", "ffn_style")
 _ALWAYS_X3 = ("tmlp0", "tmlp2", "te0", "te2", "tproj", "gf_time", "gf_text", "text_proj", "joint")
 _ALWAYS_X3_LAYER = ("ca_k", "ca_v", "sd_k", "sd_v")
 _MLP_LAYER = ("w1", "w2", "sd_f1", "sd_f2")  # the MFMA-bound GEMMs: expert MLPs and the 4x FFN
-
-
-def pair_key(name: str) -> str:
-    """PackedModel.wstream1 key of matrix `name`'s (hi, lo) pair stream: never the key of a 16-bit fragment stream (those are the
-    plain kernel_layout() names), so the two formats of MdmPacked.ws cannot be confused."""
-    return "x3:" + name
 
 
 def weight_format(name: str, precision: int, head_dim: int) -> str:
@@ -142,13 +138,90 @@ def _style(out, sd, dst, src):
     out["W:" + dst + "out"], out["V:" + dst + "out_b"] = sd[src + ".out_layers.2.weight"], sd[src + ".out_layers.2.bias"]
 
 
+# Weight streams: a matrix (or Linear-GELU-Linear pair) re-ordered into the MFMA fragment order ONE kernel consumes (DESIGN.md
+# section 5).  kind -> consumer: "mlp" csrc/mlp_stream.hip, "style" / "style3" csrc/style_gemm.hip (16-bit / (hi, lo) pairs), "frag"
+# csrc/gemm_stream.hip, "expert3" csrc/gemm_stream3.hip ((hi, lo) pairs); ops.pack_stream() packs each.
+STREAM_KINDS = ("mlp", "style", "style3", "frag", "expert3")
+_PAIR_KINDS = ("style3", "expert3")  # bf16 (hi, lo) fragment pairs: only of matrices whose planes are bf16x2
+
+# Where a stream's pointer goes: the struct (packed / style / performer / layer = MdmPacked / MdmStyle / MdmPerformer / MdmLayer),
+# the kernel_layout() prefix of that struct (for MdmPacked: the matrix name) and the field.
+Slot = namedtuple("Slot", "struct owner field")
+# One stream: `sources` are kernel_layout() matrix names, `shape` the [G, N, K] view of each that the packer is given, `h16` the
+# 16-bit format ("f16" / "bf16").
+Stream = namedtuple("Stream", "key kind sources shape h16 slot")
+
+
+def _layer_shapes(cfg: dict) -> Dict[str, Tuple[int, int, int]]:
+    """[G, N, K] views of kernel_layout()'s per-layer matrices by leaf name, in its order (experts: G = 2E stacked Linears)."""
+    D, F_, Dt, E2 = cfg["latent_dim"], cfg["ff_size"], cfg["text_latent_dim"], 2 * cfg["moe_num_experts"]
+    dh = D // cfg["num_heads"]
+    out = {}
+    for w in ("local.", "global."):
+        out.update({w + "qkv": (1, 3 * D, D), w + "feat": (1, min(dh, 256), dh), w + "proj0": (1, D, D), w + "proj3": (1, D, D),
+                    w + "style.out": (1, D, D)})
+    out.update({"skip": (1, D, D), "ca_q": (1, D, D), "ca_k": (1, D, Dt), "ca_v": (1, D, Dt), "ca_style.out": (1, D, D),
+                "w1": (E2, F_, D), "w2": (E2, D, F_), "ffn_style.out": (1, D, D), "sd_q": (1, D, D), "sd_k": (1, D, Dt),
+                "sd_v": (1, D, Dt), "sd_out": (1, D, D), "sd_f1": (1, 4 * D, D), "sd_f2": (1, D, 4 * D)})
+    return out
+
+
+def stream_plan(cfg: dict, precision: int) -> List[Stream]:
+    """The weight streams a PackedModel of `cfg` at `precision` wants, and the struct field each belongs to.  Pure: no device, no
+    library call (the library still refuses shapes through its `*_elems` queries when the plan is packed)."""
+    D, F_ = cfg["latent_dim"], cfg["ff_size"]
+    head_dim = D // cfg["num_heads"]
+    shapes = _layer_shapes(cfg)
+    # which kernels run, by width and precision
+    half_mlp = precision in (L.PREC_BF16, L.PREC_F16, L.PREC_MIXED)  # Linear-GELU-Linear pairs on 16-bit activations
+    expert_mlp = half_mlp and D in (512, 1024) and F_ % 256 == 0     # the shapes the fused expert MLP takes
+    dense_mlp = half_mlp and D == 512                                # 4x FFN of the text cross-attention (small width only)
+    throughput = dense_mlp and precision != L.PREC_MIXED             # mixed: Performer pair and stylization stay fp32-grade
+    style3 = D == 512                                                # every precision whose stylization planes are bf16x2
+    # the big model's D x D launches are latency chains on the tile kernel.  Never the expert matrices: only linear() hands
+    # MdmPacked.ws to a 16-bit launch, and the expert GEMMs of those modes take the fused MLP or the tile kernel
+    frag = D == 1024 and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_FP8)
+    # the fp32-grade mode's expert GEMM pair is 45 % of its step on the tile kernel
+    expert3 = precision == L.PREC_X3 and D % 128 == 0 and F_ % 128 == 0
+    plan: List[Stream] = []
+
+    def add(kind, struct, owner, field, *sources):
+        fmt = weight_format(sources[0], precision, head_dim)
+        if fmt == "f8" or (kind in _PAIR_KINDS and fmt != "bf16x2"):
+            return
+        h16 = "f16" if fmt == "f16" else "bf16"
+        shape = tuple(shapes[s.split(".", 1)[1]] for s in sources)
+        plan.append(Stream(kind + ":" + "+".join(sources), kind, sources, shape, h16, Slot(struct, owner, field)))
+
+    for li in range(2 * cfg["num_layers"]):
+        k = f"L{li}."
+        if expert_mlp:
+            add("mlp", "layer", k, "wstream", k + "w1", k + "w2")
+        if dense_mlp:
+            add("mlp", "layer", k, "sd_ffn_ws", k + "sd_f1", k + "sd_f2")
+        for q in (k + "local.", k + "global."):
+            if throughput:
+                add("mlp", "performer", q, "proj_ws", q + "proj0", q + "proj3")
+        for st in (k + "local.style.", k + "global.style.", k + "ca_style.", k + "ffn_style."):  # out_layers.2 of the StylizationBlocks
+            if throughput:
+                add("style", "style", st, "out_ws", st + "out")
+            if style3:
+                add("style3", "style", st, "out_ws3", st + "out")
+        for leaf, (_, N, K) in shapes.items():
+            if frag and leaf not in ("w1", "w2") and K in (512, 1024) and N % 256 == 0:
+                add("frag", "packed", k + leaf, "ws", k + leaf)
+            if expert3 and leaf in ("w1", "w2"):
+                add("expert3", "packed", k + leaf, "ws", k + leaf)
+    return plan
+
+
 class PackedModel:
     """Device-resident packed weights + the ctypes ``MdmModel`` that points at them, for ONE precision: the weight streams it
-    builds (and the ``MdmPacked.ws`` pointers of the model struct) are in the formats that precision's kernels read."""
+    builds (``streams``, by the key of their ``stream_plan`` entry) are in the formats that precision's kernels read."""
 
-    def __init__(self, sd: Dict[str, torch.Tensor], cfg: dict, eph, proj, device, with_lo: bool = True,
-                 counters: Dict[str, torch.Tensor] = None, precision: int = L.PREC_X3):
-        from .ops import PackedWeight  # HIP pack kernel
+    def __init__(self, sd: Dict[str, torch.Tensor], cfg: dict, eph, proj, device, counters: Dict[str, torch.Tensor] = None,
+                 precision: int = L.PREC_X3):
+        from .ops import PackedWeight, pack_stream  # HIP pack kernels
 
         self.cfg = dict(cfg)
         self.precision = precision
@@ -156,101 +229,33 @@ class PackedModel:
         dev = torch.device(device)
         if dev.type != "cuda":
             raise L.MdmError("PackedModel needs a GPU device: the denoising path has no CPU fallback")
-        lay = kernel_layout(sd, cfg, eph, proj)
         self._keep = []
         self.W: Dict[str, PackedWeight] = {}
         self.V: Dict[str, torch.Tensor] = {}
+        self.plan = stream_plan(cfg, precision)
+        self.streams: Dict[str, torch.Tensor] = {}
         with torch.cuda.device(dev):
-            for k, t in lay.items():
+            mats = {}  # fp32 device copies of the matrices: kept until the streams are packed
+            for k, t in kernel_layout(sd, cfg, eph, proj).items():
                 t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
                 if k.startswith("W:"):
-                    fmt = weight_format(k[2:], precision, head_dim)
-                    self.W[k[2:]] = PackedWeight(t, fmt=fmt if (with_lo or fmt != "bf16x2") else "bf16")
+                    mats[k[2:]] = t
+                    self.W[k[2:]] = PackedWeight(t, fmt=weight_format(k[2:], precision, head_dim))
                 else:
                     self.V[k[2:]] = t
+            for s in self.plan:
+                ws = pack_stream(s.kind, *(mats[n].reshape(shape) for n, shape in zip(s.sources, s.shape)),
+                                 dtype=torch.float16 if s.h16 == "f16" else torch.bfloat16)
+                if ws is not None:  # None: the library does not take the shape
+                    self.streams[s.key] = ws
+            del mats
             D, L_ = cfg["latent_dim"], cfg["num_layers"]
-            # weight streams of the expert MLPs for the streamed-weight fused kernel (csrc/mlp_stream.hip): the 16-bit
-            # modes at the shapes it takes
-            self.wstream = {}
-            E2, F_ = 2 * cfg["moe_num_experts"], cfg["ff_size"]
-            if D in (512, 1024) and F_ % 256 == 0 and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_MIXED):
-                from .ops import mlp_stream_pack
-                for li in range(2 * L_):
-                    k = f"L{li}."
-                    fmt = weight_format(k + "w1", precision, head_dim)
-                    dt = torch.float16 if fmt == "f16" else torch.bfloat16
-                    self.wstream[k] = mlp_stream_pack(lay["W:" + k + "w1"].to(dev).reshape(E2, F_, D),
-                                                      lay["W:" + k + "w2"].to(dev).reshape(E2, D, F_), dt)
-            # ... and of the dense Linear-GELU-Linear pairs (Performer output projection, 4x FFN of the text cross-attention),
-            # throughput modes only (their activations are 16-bit there); the mixed mode runs the FFN pair in fp16 as well
-            if D == 512 and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_MIXED):
-                from .ops import mlp_stream_pack
-                for li in range(2 * L_):
-                    k = f"L{li}."
-                    pairs = [(k + "sd_ffn", k + "sd_f1", k + "sd_f2")]
-                    if precision != L.PREC_MIXED:
-                        pairs += [(k + w + ".proj", k + w + ".proj0", k + w + ".proj3") for w in ("local", "global")]
-                    for name, a, b in pairs:
-                        fmt = weight_format(a, precision, head_dim)
-                        if fmt not in ("f16", "bf16x2", "bf16"):
-                            continue
-                        dt = torch.float16 if fmt == "f16" else torch.bfloat16
-                        self.wstream[name] = mlp_stream_pack(lay["W:" + a].to(dev), lay["W:" + b].to(dev), dt)
-                    # out_layers.2 of the four StylizationBlocks, for the fused stylization kernel (csrc/style_gemm.hip)
-                    if precision != L.PREC_MIXED:
-                        from .ops import gemm_stream_pack
-                        for st in (k + "local.style.", k + "global.style.", k + "ca_style.", k + "ffn_style."):
-                            fmt = weight_format(st + "out", precision, head_dim)
-                            dt = torch.float16 if fmt == "f16" else torch.bfloat16
-                            ws = gemm_stream_pack(lay["W:" + st + "out"].to(dev), dt)
-                            if ws is not None:
-                                self.wstream[st + "out"] = ws
-            # ... and its (hi, lo) pair streams for the fp32-grade form (csrc/style_gemm.hip style_gemm3): every format class whose
-            # stylization Linears are packed as bf16 hi + lo planes (fp32-grade and mixed runs)
-            if D == 512 and with_lo:
-                from .ops import gemm_stream3_pack
-                for li in range(2 * L_):
-                    k = f"L{li}."
-                    for st in (k + "local.style.", k + "global.style.", k + "ca_style.", k + "ffn_style."):
-                        if weight_format(st + "out", precision, head_dim) != "bf16x2":
-                            continue
-                        ws = gemm_stream3_pack(lay["W:" + st + "out"].to(dev))
-                        if ws is not None:
-                            self.wstream[st + "out3"] = ws
-            # fragment streams of the plain per-layer Linears for the streamed-weight GEMM (csrc/gemm_stream.hip): the 16-bit modes of the
-            # big model, whose D x D launches are latency chains on the tile kernel.
-            # Not the expert matrices: only linear() hands MdmPacked.ws to a 16-bit launch, and the expert GEMMs of those modes take the
-            # fused MLP (self.wstream) or the tile kernel.  self.wstream1 holds every MdmPacked.ws: these under the matrix name, the pair
-            # streams below under pair_key(name)
-            self.wstream1 = {}
-            if D == 1024 and precision in (L.PREC_BF16, L.PREC_F16, L.PREC_FP8):
-                from .ops import gemm_stream1_pack
-                for kk, t in lay.items():
-                    if not kk.startswith("W:L") or t.dim() != 2 or t.shape[1] not in (512, 1024) or t.shape[0] % 256:
-                        continue
-                    if kk.rsplit(".", 1)[1] in ("w1", "w2"):
-                        continue
-                    fmt = weight_format(kk[2:], precision, head_dim)
-                    if fmt not in ("f16", "bf16", "bf16x2"):
-                        continue
-                    ws = gemm_stream1_pack(t.to(dev), torch.float16 if fmt == "f16" else torch.bfloat16)
-                    if ws is not None:
-                        self.wstream1[kk[2:]] = ws
-            # (hi, lo) fragment-pair streams of the expert matrices for the streamed-weight bf16x3 GEMM (csrc/gemm_stream3.hip): the
-            # fp32-grade mode, whose expert GEMM pair is 45 % of its step on the tile kernel
-            if with_lo and precision == L.PREC_X3 and D % 128 == 0 and F_ % 128 == 0:
-                from .ops import gemm_stream3x_pack
-                for li in range(2 * L_):
-                    k = f"L{li}."
-                    for name, shape in ((k + "w1", (E2, F_, D)), (k + "w2", (E2, D, F_))):
-                        if weight_format(name, precision, head_dim) != "bf16x2":
-                            continue
-                        ws = gemm_stream3x_pack(lay["W:" + name].to(dev).reshape(*shape))
-                        if ws is not None:
-                            self.wstream1[pair_key(name)] = ws
             self.layers = (L.Layer * (2 * L_))()
             for li, (pre, tag) in enumerate(layer_tags(L_)):
                 self._fill_layer(self.layers[li], f"L{li}.", pre, counters)
+            for s in self.plan:
+                if s.key in self.streams:
+                    self._point(s.slot, self.streams[s.key])
             m = L.Model()
             m.D, m.F, m.Dt, m.H = D, cfg["ff_size"], cfg["text_latent_dim"], cfg["num_heads"]
             m.E, m.L, m.feats, m.num_frames = cfg["moe_num_experts"], L_, cfg["input_feats"], cfg["num_frames"]
@@ -267,24 +272,30 @@ class PackedModel:
             self.model = m
             torch.cuda.current_stream().synchronize()
 
+    def slot_struct(self, slot: Slot) -> C.Structure:
+        """The ctypes struct (a view into ``layers``) that `slot` names: its owner prefix spells the path of struct members."""
+        li, *path = slot.owner.rstrip(".").split(".")
+        s = self.layers[int(li[1:])]
+        for member in path:
+            s = getattr(s, "global_" if member == "global" else member)
+        assert type(s) is {"packed": L.Packed, "style": L.Style, "performer": L.Performer, "layer": L.Layer}[slot.struct], slot
+        return s
+
+    def _point(self, slot: Slot, ws: torch.Tensor):
+        s = self.slot_struct(slot)
+        setattr(s, slot.field, ws.data_ptr())
+        if slot.field == "wstream":  # group stride of the expert MLP stream: elements per expert
+            s.wstream_gs = 2 * self.cfg["latent_dim"] * self.cfg["ff_size"]
+
     def _packed(self, name: str) -> L.Packed:
         w = self.W[name]
         p = L.Packed()
         p.hi, p.lo, p.ld = w.hi.data_ptr(), (w.lo.data_ptr() if w.lo is not None else 0), w.Kp
-        # MdmPacked.ws: a 16-bit fragment stream (plain Linears of the 16-bit modes) or a (hi, lo) pair stream (expert matrices of
-        # the fp32-grade mode); the two loops above never fill both for one matrix
-        ws = self.wstream1.get(name, self.wstream1.get(pair_key(name)))
-        if ws is not None:
-            p.ws = ws.data_ptr()
         return p
 
     def _style(self, st: L.Style, pre: str):
         st.norm_w, st.norm_b = self.V[pre + "norm_w"].data_ptr(), self.V[pre + "norm_b"].data_ptr()
         st.out, st.out_b = self._packed(pre + "out"), self.V[pre + "out_b"].data_ptr()
-        if (pre + "out") in self.wstream:
-            st.out_ws = self.wstream[pre + "out"].data_ptr()
-        if (pre + "out3") in self.wstream:
-            st.out_ws3 = self.wstream[pre + "out3"].data_ptr()
 
     def _fill_layer(self, l: L.Layer, k: str, sd_prefix: str, counters):
         V, D = self.V, self.cfg["latent_dim"]
@@ -299,8 +310,6 @@ class PackedModel:
             p.feat = self._packed(q + "feat")
             p.proj0, p.proj0_b = self._packed(q + "proj0"), V[q + "proj0_b"].data_ptr()
             p.proj3, p.proj3_b = self._packed(q + "proj3"), V[q + "proj3_b"].data_ptr()
-            if (q + "proj") in self.wstream:
-                p.proj_ws = self.wstream[q + "proj"].data_ptr()
             self._style(p.style, q + "style.")
         l.skip, l.skip_b = self._packed(k + "skip"), V[k + "skip_b"].data_ptr()
         l.ca_norm_w, l.ca_norm_b = V[k + "ca_norm_w"].data_ptr(), V[k + "ca_norm_b"].data_ptr()
@@ -324,11 +333,6 @@ class PackedModel:
                 l.importance[b] = counters[br + ".expert_importance"].data_ptr()
         l.w1, l.b1 = self._packed(k + "w1"), V[k + "b1"].data_ptr()
         l.w2, l.b2 = self._packed(k + "w2"), V[k + "b2"].data_ptr()
-        if (k + "sd_ffn") in self.wstream:
-            l.sd_ffn_ws = self.wstream[k + "sd_ffn"].data_ptr()
-        ws = self.wstream.get(k)
-        if ws is not None:
-            l.wstream, l.wstream_gs = ws.data_ptr(), 2 * D * self.cfg["ff_size"]
         self._style(l.ffn_style, k + "ffn_style.")
         l.sd_ln_w, l.sd_ln_b = V[k + "sd_ln_w"].data_ptr(), V[k + "sd_ln_b"].data_ptr()
 

@@ -264,7 +264,7 @@ class MotionTransformer(nn.Module):
         if prec not in self._packed:
             sd = {k: v.detach() for k, v in self.state_dict().items()}
             self._packed[prec] = PackedModel(sd, self.kernel_cfg(), self._eph, self._proj, self.device,
-                                            with_lo=True, counters=self.moe_buffers(), precision=self.precision)
+                                            counters=self.moe_buffers(), precision=self.precision)
             self._text_cache = None
         return self._packed[prec]
 

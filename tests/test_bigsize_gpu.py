@@ -322,7 +322,8 @@ def test_big_width_streamed_weight_linears_compute_the_tile_kernels_function(pre
     in the last fp32 bit (7e-8 relative, tests/test_gemm_gpu.py), which a 16-bit store may round either way: gated at 16-bit noise."""
     L_ = pkg("_lib")
     m, _ = _big(precision)
-    assert m.pack().wstream1, "the big model packs fragment streams for its D x D Linears"
+    pm = m.pack()
+    assert [s for s in pm.plan if s.kind == "frag" and s.key in pm.streams], "the big model packs fragment streams for its D x D Linears"
     B, T = 4, 64
     x, length, xf_proj, xf_out = _inputs(B, T)
     length = length.clamp(max=T)

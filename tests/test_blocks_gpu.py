@@ -422,7 +422,9 @@ def test_fp32_grade_expert_gemms_on_the_streamed_kernel_change_nothing(B, S):
     order -- at group sizes from empty to several tiles (the router decides them)."""
     m, sd, eph, proj, h, emb, xf, length, sc, pre, (D, H, E) = _setup(B, S, 28, 3)
     L = pkg("_lib")
-    assert any(k.endswith("w1") for k in m.pack().wstream1), "the fp32-grade model packs pair streams for its expert matrices"
+    pm = m.pack()
+    assert any(s.kind == "expert3" and s.sources[0].endswith("w1") and s.key in pm.streams for s in pm.plan), \
+        "the fp32-grade model packs pair streams for its expert matrices"
     for block in (L.BLOCK_MOE, L.BLOCK_LAYER):
         out = _run_block(m, block, h, sc, length, xf)
         L.lib().mdm_set_gemm_variant(69)

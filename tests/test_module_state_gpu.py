@@ -118,10 +118,13 @@ def test_packed_streams_match_their_consumer(case, precision):
     linear() hands gemm_stream1 -- and never of an expert matrix, which no 16-bit launch reads through MdmPacked.ws."""
     L = pkg("_lib")
     lib = L.lib()
+    ops = pkg("ops")
     pm = _fresh(case, precision).pack()
-    pre = pkg("packing").pair_key("")  # pm.wstream1: 16-bit fragment streams by matrix name, pair streams under pair_key(name)
-    pairs = {n[len(pre):]: t for n, t in pm.wstream1.items() if n.startswith(pre)}
-    frag = {n: t for n, t in pm.wstream1.items() if not n.startswith(pre)}
+    plan = pkg("packing").stream_plan(pm.cfg, precision)
+    assert pm.plan == plan
+    # pm.streams: the packed entries of the plan by key; the MdmPacked.ws streams by the name of their matrix
+    pairs = {s.sources[0]: pm.streams[s.key] for s in plan if s.kind == "expert3" and s.key in pm.streams}
+    frag = {s.sources[0]: pm.streams[s.key] for s in plan if s.kind == "frag" and s.key in pm.streams}
     D, F, E2 = pm.cfg["latent_dim"], pm.cfg["ff_size"], 2 * pm.cfg["moe_num_experts"]
     experts = {"w1": (F, D), "w2": (D, F)}  # [2E * N, K] stacked
     sixteen_bit = precision in (L.PREC_BF16, L.PREC_F16, L.PREC_FP8)
@@ -151,6 +154,28 @@ def test_packed_streams_match_their_consumer(case, precision):
     for name, p in packed.items():
         ws = frag.get(name, pairs.get(name))
         assert (p.ws or 0) == (ws.data_ptr() if ws is not None else 0), name
+    # the same for all six stream fields: what is packed is what the plan asks for and the library takes, every packed stream's
+    # pointer is in its slot, and every other stream field of the model is null
+    assert set(pm.streams) == {s.key for s in plan if ops.stream_elems(s.kind, *s.shape) > 0}
+    want = {s.slot: pm.streams[s.key].data_ptr() for s in plan if s.key in pm.streams}
+    assert len(want) == len(pm.streams) == len({t.data_ptr() for t in pm.streams.values()})
+    for s in plan:
+        if s.key in pm.streams:
+            assert getattr(pm.slot_struct(s.slot), s.slot.field) == want[s.slot], s
+            assert pm.streams[s.key].dtype == (torch.float16 if s.h16 == "f16" else torch.bfloat16), s
+    Slot = pkg("packing").Slot
+    have = {Slot("packed", name, "ws"): p.ws for name, p in packed.items()}
+    for li in range(2 * pm.cfg["num_layers"]):
+        k, l = f"L{li}.", pm.layers[li]
+        have[Slot("layer", k, "wstream")], have[Slot("layer", k, "sd_ffn_ws")] = l.wstream, l.sd_ffn_ws
+        assert l.wstream_gs == (2 * D * F if l.wstream else 0)
+        styles = [(k + "ca_style.", l.ca_style), (k + "ffn_style.", l.ffn_style)]
+        for which, perf in (("local", l.local), ("global", l.global_)):
+            have[Slot("performer", f"{k}{which}.", "proj_ws")] = perf.proj_ws
+            styles.append((f"{k}{which}.style.", perf.style))
+        for pre, st in styles:
+            have[Slot("style", pre, "out_ws")], have[Slot("style", pre, "out_ws3")] = st.out_ws, st.out_ws3
+    assert {slot: p for slot, p in have.items() if p} == want
 
 
 @pytest.mark.parametrize("precision", [1, 2, 4, 5])  # one per weight-format class (3 shares its planes with 1)
