@@ -3,31 +3,26 @@
 * mdm_composed_update against an f64 restatement (K = 1, 2, 3, 8, fractional and negative weights, clip, noise, x0_prev,
   editing, aligned and misaligned buffers, n % 4 != 0), and K = 1 with w = 1 bitwise equal to mdm_guided_update and
   mdm_guided_update_inpaint;
-* every guided loop against the oracle's denoiser run once per prompt, with the composition and the loop restated here from
-  abar, teacher-forced on the device's trajectory, under timeline, body-part and negative-weight compositions, with an edit
-  mask, and with prompt captions of another token count than the empty one (both ragged_text modes);
+* every guided loop against the oracle's denoiser run once per prompt, with the composition and the loop restated in
+  tests/sampler_ref.py from abar, teacher-forced on the device's trajectory, under timeline, body-part and negative-weight
+  compositions, with an edit mask, and with prompt captions of another token count than the empty one (both ragged_text
+  modes);
 * row bookkeeping (identical prompts split w / 1 - w), graph == eager and two streams == one bitwise, the trainer's
   prompt_weights (K = 1 equal to plain generation, batch-split independence, bucketed == serial), the configs[1] shape in bf16.
 """
 import ctypes as C
-import os
-import sys
 import types
 
-import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, golden_state, pkg, rel_inf
-from test_motion_edit_gpu import _diffusion, _setup, _trainer, _vp
+from conftest import pkg, rel_inf
 
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import denoiser_ref as R  # noqa: E402
+import sampler_ref as S
+from sampler_ref import caption_trainer as _trainer, f32, make_diffusion as _diffusion, vp as _vp
+from test_motion_edit_gpu import _setup
 
 pytestmark = pytest.mark.gpu
-
-KIND = {"cfg": "ddpm", "cfg_ddim": "ddim", "cfg_dpmpp": "dpmpp"}
-f32 = lambda v: float(np.float32(v))  # noqa: E731
 
 
 # ---- kernel level ------------------------------------------------------------------------------------------------------
@@ -37,17 +32,6 @@ def _composed(x, eps, K, w, xp, nz, known, mask, tab, coef, steps, t, scale, cli
         _vp(x), _vp(eps), C.c_int32(K), _vp(w), _vp(xp), _vp(nz), _vp(known), _vp(mask), C.c_int64(x.numel()), _vp(tab),
         _vp(coef), C.c_int32(steps), C.c_void_p(0), C.c_int32(t), C.c_float(scale), C.c_int32(clip), _vp(xo), _vp(x0o),
         C.c_void_p(L.stream_ptr())), "mdm_composed_update")
-
-
-def _guided(x, ec, eu, xp, nz, known, mask, tab, coef, steps, t, scale, clip, xo, x0o):
-    L = pkg("_lib")
-    args = [_vp(x), _vp(ec), _vp(eu), _vp(xp), _vp(nz)]
-    tail = [C.c_int64(x.numel()), _vp(tab), _vp(coef), C.c_int32(steps), C.c_void_p(0), C.c_int32(t), C.c_float(scale),
-            C.c_int32(clip), _vp(xo), _vp(x0o), C.c_void_p(L.stream_ptr())]
-    if known is None:
-        L.check(L.lib().mdm_guided_update(*args, *tail), "mdm_guided_update")
-    else:
-        L.check(L.lib().mdm_guided_update_inpaint(*args, _vp(known), _vp(mask), *tail), "mdm_guided_update_inpaint")
 
 
 def _composed_ref(d, coef64, t, x, eps, K, w, xp, nz, known, mask, scale, clip):
@@ -151,7 +135,7 @@ def test_one_prompt_of_weight_one_is_the_guided_update_bitwise(shape):
                         xp_ = xp if kind == "dpmpp" else None
                         a, a0, b, b0 = (torch.empty(shape, device="cuda") for _ in range(4))
                         _composed(x, eps, 1, ones, xp_, nz_, k_, m_, tab, coef, N, t, 7.5, clip, a, a0)
-                        _guided(x, ec, eu, xp_, nz_, k_, m_, tab, coef, N, t, 7.5, clip, b, b0)
+                        S.guided_update(x, ec, eu, xp_, nz_, k_, m_, tab, coef, N, t, 7.5, clip, b, b0)
                         case = (kind, t, clip, nz_ is None, k_ is None)
                         assert torch.equal(a, b) and torch.equal(a0, b0), case
 
@@ -187,91 +171,20 @@ def _ckw(kw, prompts, w):
             "compose_xf_out": torch.stack([p[1] for p in prompts], 1).cuda()}
 
 
-def _loop(d, mode, m, kw, x_T, scale, eta, ns, use_graph, cb=None, seed=None):
-    shape = tuple(x_T.shape)
-    common = dict(noise=x_T, clip_denoised=False, model_kwargs=kw, step_noise=ns, use_graph=use_graph, seed=seed,
-                  cfg_scale=scale, callback=cb)
-    if mode == "cfg":
-        return d.p_sample_loop_with_cfg(m, shape, **common)
-    if mode == "cfg_ddim":
-        return d.ddim_sample_loop_with_cfg(m, shape, eta=eta, **common)
-    return d.dpm_solver_sample_loop_with_cfg(m, shape, **common)
-
-
-def _oracle(g, meta, d, mode, scale, prompts, w, inputs, check, eta=0.0, step_noise=None, known=None, mask=None,
-            uncond=None):
-    """x_{t-1} of the steps in ``check``, each from the device's own x_t (``inputs[i]``): the oracle's denoiser once per
-    prompt and once unconditionally, fed the original timesteps; x0 = x0_u + s sum_k w_k (x0_k - x0_u), the edit blend,
-    then the DDPM posterior step, the DDIM step or DPM-Solver++(2M), all restated from abar in f64."""
-    sd, eph, proj, mcfg = golden_state(meta)
-    B = g["x_T"].shape[0]
-    up, uo = uncond if uncond is not None else (g["xf_proj_uncond"][:1], g["xf_out_uncond"][:1])
-    up, uo = up.expand(B, -1), uo.expand(B, -1, -1)
-    acp, N = d.alphas_cumprod, d.num_timesteps
-    tmap = d.timestep_map if d.timestep_map is not None else np.arange(N)
-    lam = lambda i: 0.5 * np.log(acp[i] / (1 - acp[i]))  # noqa: E731
-    memo = {}
-
-    def x0_at(i):
-        if i not in memo:
-            t = N - 1 - i
-            x = inputs[i].double()
-            tt = torch.full((B,), int(tmap[t]), dtype=torch.int64)
-            a, b = f32((1 / acp[t]) ** 0.5), f32((1 / acp[t] - 1) ** 0.5)
-            with torch.no_grad():
-                x0u = a * x - b * R.denoiser_forward(sd, mcfg, x.float(), tt, g["length"], up, uo, eph, proj).double()
-                acc = 0
-                for k, (xp_k, xo_k) in enumerate(prompts):
-                    ek = R.denoiser_forward(sd, mcfg, x.float(), tt, g["length"], xp_k, xo_k, eph, proj).double()
-                    acc = acc + w[:, k].double() * (a * x - b * ek - x0u)
-            x0 = x0u + scale * acc
-            if known is not None:
-                x0 = (1 - mask.double()) * x0 + mask.double() * known.double()
-            memo[i] = x0
-        return memo[i]
-
-    want = {}
-    for i in check:
-        t = N - 1 - i
-        x, x0 = inputs[i].double(), x0_at(i)
-        ab, abp = acp[t], (acp[t - 1] if t > 0 else 1.0)
-        if KIND[mode] == "ddpm":
-            beta = 1 - ab / abp
-            x = beta * abp ** 0.5 / (1 - ab) * x0 + (1 - abp) * (1 - beta) ** 0.5 / (1 - ab) * x
-            if t > 0:
-                x = x + (beta * (1 - abp) / (1 - ab)) ** 0.5 * step_noise[i].double()
-        elif KIND[mode] == "ddim":
-            eps = (x - ab ** 0.5 * x0) / (1 - ab) ** 0.5
-            sig = eta * ((1 - abp) / (1 - ab)) ** 0.5 * (1 - ab / abp) ** 0.5
-            x = abp ** 0.5 * x0 + max(1 - abp - sig ** 2, 0.0) ** 0.5 * eps
-            if t > 0 and eta > 0:
-                x = x + sig * step_noise[i].double()
-        elif t == 0:
-            x = x0
-        else:
-            h = lam(t - 1) - lam(t)
-            D_ = x0
-            if i > 0:
-                r = (lam(t) - lam(t + 1)) / h
-                D_ = (1 + 1 / (2 * r)) * x0 - (1 / (2 * r)) * x0_at(i - 1)
-            x = ((1 - abp) / (1 - ab)) ** 0.5 * x - abp ** 0.5 * np.expm1(-h) * D_
-        want[i] = x
-    return want
-
-
 def _check_loop(g, meta, m, d, mode, eta, ckw, prompts, w, noises, known=None, mask=None, uncond=None, graph_vs_eager=True):
     N, scale = d.num_timesteps, meta["cfg_scale"]
+    uncond = S.golden_text(g)["uncond"] if uncond is None else uncond
     ns = noises(f"compose.{mode}.{eta}", N)
     finals = []
     for use_graph in ((True, False) if graph_vs_eager else (True,)):
         got = []
-        out = _loop(d, mode, m, ckw, g["x_T"].cuda(), scale, eta, ns, use_graph,
-                    cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
+        out = S.run_loop(d, mode, m, ckw, scale, eta, use_graph, x_T=g["x_T"].cuda(), step_noise=ns,
+                         cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
         assert len(got) == N and torch.equal(out, got[-1]) and torch.isfinite(out).all()
         if use_graph:
             check = sorted({0, 1, N // 2, N - 2, N - 1})
-            want = _oracle(g, meta, d, mode, scale, prompts, w, [g["x_T"]] + got[:-1], check, eta, ns, known, mask,
-                           uncond)
+            want = S.loop_ref(d, mode, scale, S.oracle_eps(g, meta), prompts=prompts, weights=w, uncond=uncond,
+                              inputs=[g["x_T"]] + got[:-1], check=check, eta=eta, step_noise=ns, known=known, mask=mask)
             for i in check:
                 e = rel_inf(got[i], want[i])
                 assert e < 1e-3, (i, e)
@@ -396,7 +309,8 @@ def test_progressive_loops_single_steps_and_unguided_modes():
                                        eta=0.5, step_noise=ns, use_graph=False).cpu()
     step = d.ddim_sample_with_cfg(m, x_t, t, clip_denoised=False, model_kwargs=ckw, cfg_scale=sc, eta=0.5,
                                   noise=ns[0].cuda())
-    want = _oracle(g, meta, d, "cfg_ddim", sc, prompts, ckw["compose_weights"].cpu(), [g["x_T"]], [0], 0.5, ns)
+    ref = dict(prompts=prompts, weights=ckw["compose_weights"].cpu(), uncond=S.golden_text(g)["uncond"])
+    want = S.loop_ref(d, "cfg_ddim", sc, S.oracle_eps(g, meta), inputs=[g["x_T"]], check=[0], eta=0.5, step_noise=ns, **ref)
     assert rel_inf(step["sample"].cpu(), want[0]) < 1e-3
     got = []
     again = d.ddim_sample_loop_with_cfg(m, (B, T, F_), noise=x_t, clip_denoised=False, model_kwargs=ckw, cfg_scale=sc,
@@ -404,8 +318,8 @@ def test_progressive_loops_single_steps_and_unguided_modes():
     assert torch.equal(got[0].cpu(), step["sample"].cpu()) and torch.equal(loop, again)
     one = d.p_sample_with_cfg(m, x_t, torch.full((B,), 3, dtype=torch.int64, device="cuda"), clip_denoised=False,
                               model_kwargs=ckw, cfg_scale=sc, noise=ns[0].cuda())
-    want = _oracle(g, meta, d, "cfg", sc, prompts, ckw["compose_weights"].cpu(), {d.num_timesteps - 4: g["x_T"]},
-                   [d.num_timesteps - 4], 0.0, {d.num_timesteps - 4: ns[0]})
+    want = S.loop_ref(d, "cfg", sc, S.oracle_eps(g, meta), inputs={d.num_timesteps - 4: g["x_T"]}, check=[d.num_timesteps - 4],
+                      step_noise={d.num_timesteps - 4: ns[0]}, **ref)
     assert rel_inf(one["sample"].cpu(), want[d.num_timesteps - 4]) < 1e-3
     for bad in (lambda: d.ddim_sample_loop(m, (B, T, F_), noise=x_t, model_kwargs=ckw),
                 lambda: d.p_sample_loop(m, (B, T, F_), noise=x_t, model_kwargs=ckw),

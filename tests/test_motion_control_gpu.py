@@ -5,9 +5,10 @@
   and P equal to mdm_motion_postprocess at radius 0 to the last bits (the loss of its own output is at rounding level);
 * mdm_joint_guidance: one iteration is x0 - scale * grad and moves x by c0[t] * delta, k iterations are k chained
   loss-grad steps, all-zero weights and masked entries leave x and x0 bit for bit, argument errors;
-* every loop against the loop restated here (the product's forward, the abar-derived update, the autograd guidance),
-  teacher-forced on the device's trajectory, also with an edit mask and with K = 2 composed prompts; graph == eager and
-  two streams == one bitwise; the trainer's result independent of the batch split;
+* every loop against the loop restated in tests/sampler_ref.py (the product's forward, the abar-derived update) with the
+  autograd guidance hooked in after the edit blend, teacher-forced on the device's trajectory, also with an edit mask and
+  with K = 2 composed prompts; graph == eager and two streams == one bitwise; the trainer's result independent of the batch
+  split;
 * behaviour: a root path cuts the final sample's loss to <= 0.1x the uncontrolled sample's; the configs[1] shape in bf16.
 """
 import ctypes as C
@@ -17,16 +18,13 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import build_module, load_golden, pkg, rel_inf
+from conftest import pkg, rel_inf
 from test_motion_control_host import ref_loss_grad
 
+import sampler_ref as S
+from sampler_ref import caption_trainer as _trainer, loops_setup as _setup, make_diffusion as _diffusion, vp as _vp
+
 pytestmark = pytest.mark.gpu
-
-KIND = {"cfg": "ddpm", "ddpm": "ddpm", "cfg_ddim": "ddim", "ddim": "ddim", "cfg_dpmpp": "dpmpp"}
-
-
-def _vp(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 def _stats(F, B, seed):
@@ -128,15 +126,6 @@ def _kernel_case(B=3, T=40, F=263, seed=3):
     w = _weights("frac", B, T, J, seed).cuda()
     lens = torch.tensor([T, T // 2, 1][:B], dtype=torch.int32).cuda()
     return x, x0, mean, std, tg, w, lens
-
-
-def _diffusion(schedule):
-    D = pkg("diffusion")
-    kw = lambda n: dict(betas=D.get_named_beta_schedule("linear", n), model_mean_type=D.ModelMeanType.EPSILON,  # noqa: E731
-                        model_var_type=D.ModelVarType.FIXED_SMALL, loss_type=D.LossType.MSE)
-    if schedule == "plain25":
-        return D.GaussianDiffusion(**kw(25))
-    return D.SpacedDiffusion(D.space_timesteps(1000, schedule), **kw(1000))
 
 
 def test_guidance_kernel_steps_and_update():
@@ -242,21 +231,6 @@ def test_argument_errors():
 
 
 # ---- loops --------------------------------------------------------------------------------------------------------------
-def _setup():
-    g, meta = load_golden("loops_tiny")
-    m, _ = build_module(meta, precision=3)
-    synth = pkg("synth")
-    B, T, F_ = g["x_T"].shape
-
-    def noises(tag, n):
-        return [synth.uniform_pm1((B, T, F_), f"noise.{tag}.{i}", meta["iseed"]) * (3.0 ** 0.5) for i in range(n)]
-
-    kw = {"xf_proj": g["xf_proj"].cuda(), "xf_out": g["xf_out"].cuda(), "length": g["length"].cuda(),
-          "text": ["a person walks"] * B}
-    m.set_uncond_embedding(g["xf_proj_uncond"][:1].cuda(), g["xf_out_uncond"][:1].cuda())
-    return g, meta, m, noises, kw
-
-
 def _control(B, T, F_=263, scale=0.001, iters=2):
     M = pkg("motion_control")
     tg, w = M.root_path_targets(T, [[0.0, 0.0], [1.0, 0.5], [1.5, 2.0]], [0, T // 2, T - 1])
@@ -273,88 +247,24 @@ def _cuda(kw):
     return {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in kw.items()}
 
 
-def _loop(d, mode, m, kw, x_T, scale, eta, ns, use_graph, cb=None, seed=None):
-    shape = tuple(x_T.shape)
-    common = dict(noise=x_T, clip_denoised=True, model_kwargs=kw, step_noise=ns, use_graph=use_graph, seed=seed)
-    if mode == "cfg":
-        return d.p_sample_loop_with_cfg(m, shape, cfg_scale=scale, callback=cb, **common)
-    if mode == "ddpm":
-        return d.p_sample_loop(m, shape, before_step_fn=None if cb is None else (lambda t, x: cb(None, t, x)), **common)
-    if mode == "ddim":
-        return d.ddim_sample_loop(m, shape, eta=eta, callback=cb, **common)
-    if mode == "cfg_ddim":
-        return d.ddim_sample_loop_with_cfg(m, shape, cfg_scale=scale, eta=eta, callback=cb, **common)
-    return d.dpm_solver_sample_loop_with_cfg(m, shape, cfg_scale=scale, callback=cb, **common)
-
-
-@torch.no_grad()
-def _eps(m, x, tt, length, xp, xo):
-    return m(x.cuda(), tt.cuda(), length.cuda(), xf_proj=xp.cuda(), xf_out=xo.cuda()).double().cpu()
-
-
 def _restated(d, mode, m, g, ctl, inputs, scale, eta=0.0, step_noise=None, known=None, mask=None, prompts=None, pw=None):
-    """x_{t-1} of every step from the device's x_t (teacher forcing): the product's forward (once per prompt and once
-    unconditionally), x0 from abar clamped to [-1, 1], the CFG / composed combination, the edit blend, ``iters`` autograd
-    guidance steps x0 -= scale (1 - m) grad, then the DDPM posterior step, the DDIM step or DPM-Solver++(2M), restated from
-    abar in f64.  The loops run clipped: the random-weight model's x0 at the first steps is ~1/sqrt(abar) times too large
-    unclipped, and the joint loss's curvature grows with the square of the positions, so no fixed step size would be
-    stable there."""
-    B = g["x_T"].shape[0]
-    length = g["length"]
-    up, uo = m.uncond_embedding(B, "cuda")
-    acp, N = d.alphas_cumprod, d.num_timesteps
-    tmap = d.timestep_map if d.timestep_map is not None else np.arange(N)
-    lam = lambda i: 0.5 * np.log(acp[i] / (1 - acp[i]))  # noqa: E731
-    f32 = lambda v: float(np.float32(v))  # noqa: E731
+    """x_{t-1} of every step from the device's x_t (teacher forcing) by tests/sampler_ref.py's loop: the product's forward
+    (once per prompt and once unconditionally), x0 from abar clamped to [-1, 1], the CFG / composed combination, the edit
+    blend, then ``iters`` autograd guidance steps x0 -= scale (1 - m) grad, then the update restated from abar in f64.  The
+    loops run clipped: the random-weight model's x0 at the first steps is ~1/sqrt(abar) times too large unclipped, and the
+    joint loss's curvature grows with the square of the positions, so no fixed step size would be stable there."""
     one_minus_m = 1.0 if mask is None else 1.0 - mask.double()
-    x0_prev, traj = None, []
-    for i in range(N):
-        t = N - 1 - i
-        x = inputs[i].double()
-        tt = torch.full((B,), int(tmap[t]), dtype=torch.int64)
-        ab, abp = acp[t], (acp[t - 1] if t > 0 else 1.0)
-        a, b = f32((1 / ab) ** 0.5), f32((1 / ab - 1) ** 0.5)
-        xin = inputs[i].float()
-        if prompts is None:
-            x0 = (a * x - b * _eps(m, xin, tt, length, g["xf_proj"], g["xf_out"])).clamp(-1, 1)
-        if mode.startswith("cfg"):
-            x0u = (a * x - b * _eps(m, xin, tt, length, up, uo)).clamp(-1, 1)
-            if prompts is None:
-                x0 = x0u + scale * (x0 - x0u)
-            else:
-                acc = 0.0
-                for k, (pp, po) in enumerate(prompts):
-                    acc = acc + pw[:, k].double() * ((a * x - b * _eps(m, xin, tt, length, pp, po)).clamp(-1, 1) - x0u)
-                x0 = x0u + scale * acc
-        if known is not None:
-            x0 = (1 - mask.double()) * x0 + mask.double() * known.double()
+
+    def guide(x0):
         for _ in range(ctl["control_iters"]):
-            _, gr = ref_loss_grad(x0, length, ctl["control_mean"], ctl["control_std"], ctl["control_joints"],
+            _, gr = ref_loss_grad(x0, g["length"], ctl["control_mean"], ctl["control_std"], ctl["control_joints"],
                                   ctl["control_weights"])
             x0 = x0 - ctl["control_scale"] * one_minus_m * gr
-        if KIND[mode] == "ddpm":
-            beta = 1 - ab / abp
-            x = beta * abp ** 0.5 / (1 - ab) * x0 + (1 - abp) * (1 - beta) ** 0.5 / (1 - ab) * x
-            if t > 0:
-                x = x + (beta * (1 - abp) / (1 - ab)) ** 0.5 * step_noise[i].double()
-        elif KIND[mode] == "ddim":
-            eps = (x - ab ** 0.5 * x0) / (1 - ab) ** 0.5
-            sig = eta * ((1 - abp) / (1 - ab)) ** 0.5 * (1 - ab / abp) ** 0.5
-            x = abp ** 0.5 * x0 + max(1 - abp - sig ** 2, 0.0) ** 0.5 * eps
-            if t > 0 and eta > 0:
-                x = x + sig * step_noise[i].double()
-        elif t == 0:
-            x = x0
-        else:
-            h = lam(t - 1) - lam(t)
-            D_ = x0
-            if i > 0:
-                r = (lam(t) - lam(t + 1)) / h
-                D_ = (1 + 1 / (2 * r)) * x0 - (1 / (2 * r)) * x0_prev
-            x = ((1 - abp) / (1 - ab)) ** 0.5 * x - abp ** 0.5 * np.expm1(-h) * D_
-        x0_prev = x0
-        traj.append(x)
-    return traj
+        return x0
+
+    return S.loop_ref(d, mode, scale, S.device_eps(m, g["length"]), prompts=prompts or [(g["xf_proj"], g["xf_out"])], weights=pw,
+                      uncond=m.uncond_embedding(g["x_T"].shape[0], "cuda"), inputs=inputs, eta=eta, step_noise=step_noise,
+                      clip=True, known=known, mask=mask, x0_hook=guide)
 
 
 def _check_against_restated(got, want, tag):
@@ -379,12 +289,12 @@ def test_controlled_loops_match_the_restated_loop(mode, eta, schedule):
     ctl = _control(B, T)
     ns = noises(f"ctl.{mode}.{eta}", N)
     got = []
-    out = _loop(d, mode, m, dict(kw, **_cuda(ctl)), g["x_T"].cuda(), sc, eta, ns, True,
-                cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
+    out = S.run_loop(d, mode, m, dict(kw, **_cuda(ctl)), sc, eta, True, x_T=g["x_T"].cuda(), step_noise=ns, clip=True,
+                     cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
     assert len(got) == N and torch.equal(out, got[-1]) and torch.isfinite(out).all()
     want = _restated(d, mode, m, g, ctl, [g["x_T"]] + got[:-1], sc, eta, ns)
     _check_against_restated(got, want, f"{mode} eta {eta} {schedule}")
-    plain = _loop(d, mode, m, kw, g["x_T"].cuda(), sc, eta, ns, True).cpu()
+    plain = S.run_loop(d, mode, m, kw, sc, eta, True, x_T=g["x_T"].cuda(), step_noise=ns, clip=True).cpu()
     assert not torch.equal(plain, out)
 
 
@@ -402,7 +312,8 @@ def test_control_with_an_edit_mask(mode, eta):
     ns = noises("ctl.edit", N)
     ekw = dict(kw, inpaint_motion=known.cuda(), inpaint_mask=mask.cuda(), **_cuda(ctl))
     got = []
-    out = _loop(d, mode, m, ekw, g["x_T"].cuda(), sc, eta, ns, True, cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
+    out = S.run_loop(d, mode, m, ekw, sc, eta, True, x_T=g["x_T"].cuda(), step_noise=ns, clip=True,
+                     cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
     keep = mask == 1
     assert torch.equal(out[keep], known[keep])
     want = _restated(d, mode, m, g, ctl, [g["x_T"]] + got[:-1], sc, eta, ns, known=known, mask=mask)
@@ -429,7 +340,8 @@ def test_control_with_two_composed_prompts(mode, eta):
            "compose_xf_out": torch.stack([p[1] for p in prompts], 1).cuda(), **_cuda(ctl)}
     ns = noises("ctl.compose", N)
     got = []
-    _loop(d, mode, m, ckw, g["x_T"].cuda(), sc, eta, ns, True, cb=lambda i, t, x: got.append(x.clone().cpu()))
+    S.run_loop(d, mode, m, ckw, sc, eta, True, x_T=g["x_T"].cuda(), step_noise=ns, clip=True,
+               cb=lambda i, t, x: got.append(x.clone().cpu()))
     want = _restated(d, mode, m, g, ctl, [g["x_T"]] + got[:-1], sc, eta, ns, prompts=prompts, pw=pw)
     _check_against_restated(got, want, f"compose {mode}")
 
@@ -469,20 +381,6 @@ def test_progressive_loop_and_single_step_carry_the_control():
 
 
 # ---- trainer ------------------------------------------------------------------------------------------------------------
-def _trainer(m, meta, steps=1000):
-    Tr = pkg("trainer")
-    synth = pkg("synth")
-    Dt = meta["text_latent_dim"]
-
-    def enc(text, device):
-        xo = torch.stack([synth.uniform_pm1((6, Dt), "cap." + t, 1) * (3.0 ** 0.5) for t in text])
-        return xo.mean(1).to(device), xo.to(device)
-
-    m.text_encoder_fn = enc
-    args = types.SimpleNamespace(device=torch.device("cuda"), diffusion_steps=steps, is_train=False, cfg_scale=2.5)
-    return Tr.DDPMTrainer(args, m)
-
-
 def _height_control(B, T):
     """Every joint's height pulled to 1 on every frame: the trainer samples unclipped, and heights are linear in x0 (no
     rotation enters them), so the loss is quadratic and a fixed step is stable whatever the size of the model's x0."""

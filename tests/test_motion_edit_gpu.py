@@ -4,82 +4,26 @@
   aligned and misaligned buffers, n % 4 != 0), and bitwise equal to mdm_guided_update under an all-zero mask;
 * all-zero masks leave the loops unchanged (bitwise for the few-step loops, within rounding for DDPM, whose update is
   associated differently);
-* every loop against the oracle's denoiser with the loop restated here from abar (not from the product's tables), on the
-  loops_tiny golden, under prefix, in-between and body-part masks, graph and eager; a binary mask's kept entries come out
-  bit for bit;
+* every loop against the oracle's denoiser with the loop restated in tests/sampler_ref.py from abar (not from the product's
+  tables), teacher-forced on the device's trajectory, on the loops_tiny golden, under prefix, in-between and body-part masks,
+  graph and eager; a binary mask's kept entries come out bit for bit;
 * graph == eager and two streams == one bitwise, progressive loops and single steps, the trainer's result independent of
   the batch split, the feature layout under recover_from_ric, and the configs[1] shape in bf16.
 """
-import ctypes as C
-import os
-import sys
 import types
 
-import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, build_module, golden_state, load_golden, pkg, rel_inf
+from conftest import pkg, rel_inf
 
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import denoiser_ref as R  # noqa: E402
+import sampler_ref as S
+from sampler_ref import KIND, caption_trainer as _trainer, make_diffusion as _diffusion
 
 pytestmark = pytest.mark.gpu
 
-KIND = {"cfg": "ddpm", "ddpm": "ddpm", "cfg_ddim": "ddim", "ddim": "ddim", "cfg_dpmpp": "dpmpp"}
-
-
-def _kw(steps):
-    D = pkg("diffusion")
-    return dict(betas=D.get_named_beta_schedule("linear", steps), model_mean_type=D.ModelMeanType.EPSILON,
-                model_var_type=D.ModelVarType.FIXED_SMALL, loss_type=D.LossType.MSE)
-
-
-def _diffusion(schedule):
-    D = pkg("diffusion")
-    if schedule == "plain25":
-        return D.GaussianDiffusion(**_kw(25))
-    return D.SpacedDiffusion(D.space_timesteps(1000, schedule), **_kw(1000))
-
-
-def _vp(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
 
 # ---- kernel level ------------------------------------------------------------------------------------------------------
-def _update(x, ec, eu, xp, nz, known, mask, tab, coef, steps, t, scale, clip, xo, x0o):
-    L = pkg("_lib")
-    args = [_vp(x), _vp(ec), _vp(eu), _vp(xp), _vp(nz)]
-    tail = [C.c_int64(x.numel()), _vp(tab), _vp(coef), C.c_int32(steps), C.c_void_p(0), C.c_int32(t), C.c_float(scale),
-            C.c_int32(clip), _vp(xo), _vp(x0o), C.c_void_p(L.stream_ptr())]
-    if known is None:
-        L.check(L.lib().mdm_guided_update(*args, *tail), "mdm_guided_update")
-    else:
-        L.check(L.lib().mdm_guided_update_inpaint(*args, _vp(known), _vp(mask), *tail), "mdm_guided_update_inpaint")
-
-
-def _update_ref(d, coef64, t, x, ec, eu, xp, nz, known, mask, scale, clip):
-    f32 = lambda v: float(np.float32(v))  # noqa: E731
-    a, b = f32(d.sqrt_recip_alphas_cumprod[t]), f32(d.sqrt_recipm1_alphas_cumprod[t])
-    x, ec = x.double(), ec.double()
-    x0 = a * x - b * ec
-    if clip:
-        x0 = x0.clamp(-1, 1)
-    if eu is not None:
-        x0u = a * x - b * eu.double()
-        if clip:
-            x0u = x0u.clamp(-1, 1)
-        x0 = x0u + scale * (x0 - x0u)
-    x0 = (1 - mask.double()) * x0 + mask.double() * known.double()
-    cx, c0, c1, cn = (f32(c) for c in coef64[t])
-    out = cx * x + c0 * x0
-    if xp is not None:
-        out = out + c1 * xp.double()
-    if nz is not None:
-        out = out + cn * nz.double()
-    return out, x0
-
-
 def test_inpaint_update_kernel_matches_f64_and_the_plain_kernel():
     d = _diffusion("ddim10")
     N = d.num_timesteps
@@ -100,10 +44,11 @@ def test_inpaint_update_kernel_matches_f64_and_the_plain_kernel():
                         xp_ = xp if kind == "dpmpp" else None
                         for name, mk in masks.items():
                             xo, x0o = torch.empty(shape, device="cuda"), torch.empty(shape, device="cuda")
-                            _update(x, ec, eu_, xp_, nz_, kn, mk, tab, coef, N, t, 2.5, clip, xo, x0o)
-                            ref, ref0 = _update_ref(d, coef64, t, x.cpu(), ec.cpu(), None if eu_ is None else eu_.cpu(),
-                                                    None if xp_ is None else xp_.cpu(), None if nz_ is None else nz_.cpu(),
-                                                    kn.cpu(), mk.cpu(), 2.5, clip)
+                            S.guided_update(x, ec, eu_, xp_, nz_, kn, mk, tab, coef, N, t, 2.5, clip, xo, x0o)
+                            ref, ref0 = S.update_kernel_ref(
+                                d, coef64, t, x.cpu(), ec.cpu(), None if eu_ is None else eu_.cpu(),
+                                None if xp_ is None else xp_.cpu(), None if nz_ is None else nz_.cpu(), kn.cpu(), mk.cpu(), 2.5,
+                                clip)
                             case = (kind, t, clip, eu_ is None, nz_ is None, name)
                             e = rel_inf(xo.cpu(), ref)
                             # x0 = a*x - b*eps cancels terms of ~a*|x|: its f32 error is measured against their size
@@ -116,35 +61,26 @@ def test_inpaint_update_kernel_matches_f64_and_the_plain_kernel():
                                 assert torch.equal(x0o[1, :3], kn[1, :3]), case
                             if name == "zero":  # the masked entry point with nothing masked is the plain kernel, bit for bit
                                 po, p0 = torch.empty(shape, device="cuda"), torch.empty(shape, device="cuda")
-                                _update(x, ec, eu_, xp_, nz_, None, None, tab, coef, N, t, 2.5, clip, po, p0)
+                                S.guided_update(x, ec, eu_, xp_, nz_, None, None, tab, coef, N, t, 2.5, clip, po, p0)
                                 assert torch.equal(xo, po) and torch.equal(x0o, p0), case
     # in place (x_out = x, x0_out = x0_prev) on buffers that are not 16-byte aligned (the element-wise form), and aligned
     coef, coef64 = d._device_coef("dpmpp", 0.0, 2, "cuda"), d.solver_coefficients("dpmpp", 0.0, 2)
     t = N // 2
-    ref, ref0 = _update_ref(d, coef64, t, x.cpu(), ec.cpu(), eu.cpu(), xp.cpu(), None, kn.cpu(), frac, 2.5, False)
+    ref, ref0 = S.update_kernel_ref(d, coef64, t, x.cpu(), ec.cpu(), eu.cpu(), xp.cpu(), None, kn.cpu(), frac, 2.5, False)
     for off in (1, 0):
         bufs = [torch.zeros(x.numel() + off, device="cuda") for _ in range(4)]
         xi, pi, ki, mi = (b[off:].view(shape) for b in bufs)
         xi.copy_(x), pi.copy_(xp), ki.copy_(kn), mi.copy_(frac.cuda())
-        _update(xi, ec, eu, pi, None, ki, mi, tab, coef, N, t, 2.5, 0, xi, pi)
+        S.guided_update(xi, ec, eu, pi, None, ki, mi, tab, coef, N, t, 2.5, 0, xi, pi)
         assert rel_inf(xi.cpu(), ref) < 1e-5 and rel_inf(pi.cpu(), ref0) < 1e-5, off
         assert torch.equal(pi[1, :3], kn[1, :3]), off
 
 
 # ---- loops -------------------------------------------------------------------------------------------------------------
 def _setup():
-    g, meta = load_golden("loops_tiny")
-    m, _ = build_module(meta, precision=3)
-    synth = pkg("synth")
-    B, T, F_ = g["x_T"].shape
-
-    def noises(tag, n):
-        return [synth.uniform_pm1((B, T, F_), f"noise.{tag}.{i}", meta["iseed"]) * (3.0 ** 0.5) for i in range(n)]
-
-    kw = {"xf_proj": g["xf_proj"].cuda(), "xf_out": g["xf_out"].cuda(), "length": g["length"].cuda(),
-          "text": ["a person walks"] * B}
-    m.set_uncond_embedding(g["xf_proj_uncond"][:1].cuda(), g["xf_out_uncond"][:1].cuda())
-    known = synth.uniform_pm1((B, T, F_), "edit.known", meta["iseed"]) * 1.5  # beyond [-1, 1]: k is never clamped
+    g, meta, m, noises, kw = S.loops_setup()
+    # beyond [-1, 1]: k is never clamped
+    known = pkg("synth").uniform_pm1(tuple(g["x_T"].shape), "edit.known", meta["iseed"]) * 1.5
     return g, meta, m, noises, kw, known
 
 
@@ -153,74 +89,6 @@ def _mask(kind, B, T, F_):
     m = {"prefix": E.prefix_mask(T, 5), "inbetween": E.inbetween_mask(T, 3, 4), "zero": torch.zeros(T, 1),
          "body": E.joint_feature_mask(E.LOWER_BODY)}[kind]
     return torch.broadcast_to(m, (B, T, F_))
-
-
-def _loop(d, mode, m, kw, x_T, scale, eta, ns, use_graph, cb=None, seed=None):
-    shape = tuple(x_T.shape)
-    common = dict(noise=x_T, clip_denoised=False, model_kwargs=kw, step_noise=ns, use_graph=use_graph, seed=seed)
-    if mode == "cfg":
-        return d.p_sample_loop_with_cfg(m, shape, cfg_scale=scale, callback=cb, **common)
-    if mode == "ddpm":
-        return d.p_sample_loop(m, shape, before_step_fn=None if cb is None else (lambda t, x: cb(None, t, x)), **common)
-    if mode == "ddim":
-        return d.ddim_sample_loop(m, shape, eta=eta, callback=cb, **common)
-    if mode == "cfg_ddim":
-        return d.ddim_sample_loop_with_cfg(m, shape, cfg_scale=scale, eta=eta, callback=cb, **common)
-    return d.dpm_solver_sample_loop_with_cfg(m, shape, cfg_scale=scale, callback=cb, **common)
-
-
-def _oracle(g, meta, d, mode, scale, known, mask, eta=0.0, step_noise=None, inputs=None):
-    """The loop restated from abar with the oracle's denoiser fed the original timesteps: (guided) x0, then
-    x0 <- (1 - m) x0 + m k, then the DDPM posterior step, the DDIM step (eps re-derived from x0) or DPM-Solver++(2M).
-    ``inputs``: x_t of every step taken from the device's trajectory (teacher forcing: each step is compared on its own, so a
-    top-1 routing near-tie resolved the other way by the two fp32 forwards cannot carry over into later steps)."""
-    sd, eph, proj, mcfg = golden_state(meta)
-    B = g["x_T"].shape[0]
-    xu_p, xu_o = g["xf_proj_uncond"][:1].expand(B, -1), g["xf_out_uncond"][:1].expand(B, -1, -1)
-    acp, N = d.alphas_cumprod, d.num_timesteps
-    tmap = d.timestep_map if d.timestep_map is not None else np.arange(N)
-    lam = lambda i: 0.5 * np.log(acp[i] / (1 - acp[i]))  # noqa: E731
-    f32 = lambda v: float(np.float32(v))  # noqa: E731
-    k, msk = known.double(), mask.double()
-    x, x0_prev, traj = g["x_T"].double(), None, []
-    for i in range(N):
-        t = N - 1 - i
-        if inputs is not None:
-            x = inputs[i].double()
-        tt = torch.full((B,), int(tmap[t]), dtype=torch.int64)
-        ab, abp = acp[t], (acp[t - 1] if t > 0 else 1.0)
-        a, b = f32((1 / ab) ** 0.5), f32((1 / ab - 1) ** 0.5)
-        with torch.no_grad():
-            ec = R.denoiser_forward(sd, mcfg, x.float(), tt, g["length"], g["xf_proj"], g["xf_out"], eph, proj).double()
-            x0 = a * x - b * ec
-            if mode.startswith("cfg"):
-                eu = R.denoiser_forward(sd, mcfg, x.float(), tt, g["length"], xu_p, xu_o, eph, proj).double()
-                x0u = a * x - b * eu
-                x0 = x0u + scale * (x0 - x0u)
-        x0 = (1 - msk) * x0 + msk * k
-        if KIND[mode] == "ddpm":
-            beta = 1 - ab / abp
-            x = beta * abp ** 0.5 / (1 - ab) * x0 + (1 - abp) * (1 - beta) ** 0.5 / (1 - ab) * x
-            if t > 0:
-                x = x + (beta * (1 - abp) / (1 - ab)) ** 0.5 * step_noise[i].double()
-        elif KIND[mode] == "ddim":
-            eps = (x - ab ** 0.5 * x0) / (1 - ab) ** 0.5
-            sig = eta * ((1 - abp) / (1 - ab)) ** 0.5 * (1 - ab / abp) ** 0.5
-            x = abp ** 0.5 * x0 + max(1 - abp - sig ** 2, 0.0) ** 0.5 * eps
-            if t > 0 and eta > 0:
-                x = x + sig * step_noise[i].double()
-        elif t == 0:
-            x = x0
-        else:
-            h = lam(t - 1) - lam(t)
-            D_ = x0
-            if i > 0:
-                r = (lam(t) - lam(t + 1)) / h
-                D_ = (1 + 1 / (2 * r)) * x0 - (1 / (2 * r)) * x0_prev
-            x = ((1 - abp) / (1 - ab)) ** 0.5 * x - abp ** 0.5 * np.expm1(-h) * D_
-        x0_prev = x0
-        traj.append(x.float())
-    return traj
 
 
 SOLVERS = [("cfg", 0.0), ("ddpm", 0.0), ("cfg_ddim", 0.0), ("cfg_ddim", 0.5), ("ddim", 0.0), ("ddim", 0.5),
@@ -241,11 +109,12 @@ def test_edited_loops_match_the_oracle(mode, eta, schedule, mask_kind):
     finals = []
     for use_graph in (True, False):
         got = []
-        out = _loop(d, mode, m, ekw, g["x_T"].cuda(), scale, eta, ns, use_graph,
-                    cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
+        out = S.run_loop(d, mode, m, ekw, scale, eta, use_graph, x_T=g["x_T"].cuda(), step_noise=ns,
+                         cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
         assert len(got) == N and torch.equal(out, got[-1])
         if use_graph:  # the eager run must reproduce it bitwise (below), so the oracle runs once
-            want = _oracle(g, meta, d, mode, scale, known, mask, eta, ns, inputs=[g["x_T"]] + got[:-1])
+            want = S.loop_ref(d, mode, scale, S.oracle_eps(g, meta), inputs=[g["x_T"]] + got[:-1], eta=eta, step_noise=ns,
+                              known=known, mask=mask, **S.golden_text(g))
             for i in sorted({0, 1, N // 2, N - 2, N - 1}):
                 e = rel_inf(got[i], want[i])
                 assert e < 1e-3, (i, e)
@@ -263,8 +132,8 @@ def test_an_all_zero_mask_changes_nothing(mode, eta):
     B, T, F_ = g["x_T"].shape
     ns = noises("zero", d.num_timesteps)
     ekw = dict(kw, inpaint_motion=known.cuda(), inpaint_mask=_mask("zero", B, T, F_).cuda())
-    plain = _loop(d, mode, m, kw, g["x_T"].cuda(), meta["cfg_scale"], eta, ns, True).cpu()
-    edited = _loop(d, mode, m, ekw, g["x_T"].cuda(), meta["cfg_scale"], eta, ns, True).cpu()
+    plain = S.run_loop(d, mode, m, kw, meta["cfg_scale"], eta, True, x_T=g["x_T"].cuda(), step_noise=ns).cpu()
+    edited = S.run_loop(d, mode, m, ekw, meta["cfg_scale"], eta, True, x_T=g["x_T"].cuda(), step_noise=ns).cpu()
     e = rel_inf(edited, plain)
     print(f"[zero mask] {mode} eta {eta}: rel_inf {e:.3e}")
     if mode in ("cfg_ddim", "cfg_dpmpp"):  # the same fused kernel's plain and masked instantiations
@@ -339,20 +208,6 @@ def test_progressive_loops_and_single_steps_edit_x0():
 
 
 # ---- trainer -----------------------------------------------------------------------------------------------------------
-def _trainer(m, meta, steps=1000):
-    Tr = pkg("trainer")
-    synth = pkg("synth")
-    Dt = meta["text_latent_dim"]
-
-    def enc(text, device):  # a different embedding per caption, so a mixed-up order would show
-        xo = torch.stack([synth.uniform_pm1((6, Dt), "cap." + t, 1) * (3.0 ** 0.5) for t in text])
-        return xo.mean(1).to(device), xo.to(device)
-
-    m.text_encoder_fn = enc
-    args = types.SimpleNamespace(device=torch.device("cuda"), diffusion_steps=steps, is_train=False, cfg_scale=2.5)
-    return Tr.DDPMTrainer(args, m)
-
-
 def test_trainer_edit_is_independent_of_the_batch_split():
     g, meta, m, noises, kw, known = _setup()
     E = pkg("motion_edit")

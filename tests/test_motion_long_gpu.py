@@ -4,36 +4,29 @@
   strides and buffers), copy mode bit for bit, nshared = 0 a no-op, the argument errors;
 * every sampler on a plain and a respaced schedule, graph and eager, with three windows of 16 / 12 / 16 frames and h = 4
   (a 36-frame canvas on the loops_tiny model, num_frames = 16): the overlap frames of neighbouring windows are equal bit for
-  bit after every step and in x_T, and each step agrees with the loop restated in f64 with the oracle's denoiser and a
-  numpy blend before the update (teacher-forced on the device's trajectory);
+  bit after every step and in x_T, and each step agrees with the loop restated in f64 (tests/sampler_ref.py) with the
+  oracle's denoiser and a numpy blend before the update (teacher-forced on the device's trajectory);
 * no overlap changes nothing (bitwise), graph == eager and two streams == one bitwise, a canvas prefix edit keeps its frames
   through the overlaps, and the trainer's generate_long / generate_long_joints (batch split, lengths, joints, the configs[1]
   shape in bf16).
 """
 import ctypes as C
-import os
-import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, build_module, golden_state, load_golden, pkg, rel_inf
+from conftest import pkg, rel_inf
 
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import denoiser_ref as R  # noqa: E402
+import sampler_ref as S
+from sampler_ref import caption_trainer as _trainer, make_diffusion as _diffusion, vp as _vp
 
 pytestmark = pytest.mark.gpu
 
-KIND = {"cfg": "ddpm", "ddpm": "ddpm", "cfg_ddim": "ddim", "ddim": "ddim", "cfg_dpmpp": "dpmpp"}
 LENS, H, T = [16, 12, 16], 4, 16
 SOLVERS = [("cfg", 0.0), ("ddpm", 0.0), ("cfg_ddim", 0.0), ("cfg_ddim", 0.5), ("ddim", 0.0), ("ddim", 0.5),
            ("cfg_dpmpp", 0.0)]
-
-
-def _vp(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 def _blend(x, groups, stride, F, ns, off, rows, w):
@@ -118,19 +111,6 @@ def test_blend_kernel_no_op_and_argument_errors():
 
 
 # ---- loops -------------------------------------------------------------------------------------------------------------
-def _kw_steps(steps):
-    D = pkg("diffusion")
-    return dict(betas=D.get_named_beta_schedule("linear", steps), model_mean_type=D.ModelMeanType.EPSILON,
-                model_var_type=D.ModelVarType.FIXED_SMALL, loss_type=D.LossType.MSE)
-
-
-def _diffusion(schedule):
-    D = pkg("diffusion")
-    if schedule == "plain25":
-        return D.GaussianDiffusion(**_kw_steps(25))
-    return D.SpacedDiffusion(D.space_timesteps(1000, schedule), **_kw_steps(1000))
-
-
 def _tables(lens=LENS, h=H, blend="linear"):
     ML = pkg("motion_long")
     starts, Cn = ML.plan_windows(lens, h)
@@ -141,35 +121,13 @@ def _tables(lens=LENS, h=H, blend="linear"):
 
 
 def _setup():
-    g, meta = load_golden("loops_tiny")
-    m, _ = build_module(meta, precision=3)
-    synth = pkg("synth")
-    B, F_ = len(LENS), g["x_T"].shape[2]
+    g, meta, m, noises, _ = S.loops_setup(B=len(LENS))
     sel = [0, 1, 0]
     text = {"xf_proj": g["xf_proj"][sel], "xf_out": g["xf_out"][sel], "length": torch.tensor(LENS)}
-
-    def noises(tag, n):
-        return [synth.uniform_pm1((B, T, F_), f"noise.{tag}.{i}", meta["iseed"]) * (3.0 ** 0.5) for i in range(n)]
-
     kw = {"xf_proj": text["xf_proj"].cuda(), "xf_out": text["xf_out"].cuda(), "length": text["length"].cuda(),
           "text": ["a", "b", "a"]}
-    m.set_uncond_embedding(g["xf_proj_uncond"][:1].cuda(), g["xf_out_uncond"][:1].cuda())
-    x_T = synth.uniform_pm1((B, T, F_), "long.x_T", meta["iseed"]) * (3.0 ** 0.5)
+    x_T = pkg("synth").uniform_pm1((len(LENS), T, g["x_T"].shape[2]), "long.x_T", meta["iseed"]) * (3.0 ** 0.5)
     return g, meta, m, noises, kw, text, x_T
-
-
-def _loop(d, mode, m, kw, x_T, scale, eta, ns, use_graph, cb=None, seed=None):
-    shape = tuple(x_T.shape)
-    common = dict(noise=x_T, clip_denoised=False, model_kwargs=kw, step_noise=ns, use_graph=use_graph, seed=seed)
-    if mode == "cfg":
-        return d.p_sample_loop_with_cfg(m, shape, cfg_scale=scale, callback=cb, **common)
-    if mode == "ddpm":
-        return d.p_sample_loop(m, shape, before_step_fn=None if cb is None else (lambda t, x: cb(None, t, x)), **common)
-    if mode == "ddim":
-        return d.ddim_sample_loop(m, shape, eta=eta, callback=cb, **common)
-    if mode == "cfg_ddim":
-        return d.ddim_sample_loop_with_cfg(m, shape, cfg_scale=scale, eta=eta, callback=cb, **common)
-    return d.dpm_solver_sample_loop_with_cfg(m, shape, cfg_scale=scale, callback=cb, **common)
 
 
 def _overlaps_equal(x):
@@ -202,58 +160,6 @@ def _blend_np(eps, t):
     return y.view_as(eps)
 
 
-def _oracle(g, meta, d, mode, scale, text, tab, inputs, eta=0.0, step_noise=None):
-    """The loop restated from abar with the oracle's denoiser (fed the original timesteps), a numpy blend of the cond and the
-    uncond eps rows, then (guided) x0 and the DDPM posterior step, the DDIM step or DPM-Solver++(2M); the step noise owner
-    copied.  Teacher-forced: x_t of step i is ``inputs[i]``."""
-    sd, eph, proj, mcfg = golden_state(meta)
-    B = len(LENS)
-    xu_p, xu_o = g["xf_proj_uncond"][:1].expand(B, -1), g["xf_out_uncond"][:1].expand(B, -1, -1)
-    acp, N = d.alphas_cumprod, d.num_timesteps
-    tmap = d.timestep_map if d.timestep_map is not None else np.arange(N)
-    lam = lambda i: 0.5 * np.log(acp[i] / (1 - acp[i]))  # noqa: E731
-    f32 = lambda v: float(np.float32(v))  # noqa: E731
-    x0_prev, traj = None, []
-    for i in range(N):
-        t = N - 1 - i
-        x = inputs[i].double()
-        tt = torch.full((B,), int(tmap[t]), dtype=torch.int64)
-        ab, abp = acp[t], (acp[t - 1] if t > 0 else 1.0)
-        a, b = f32((1 / ab) ** 0.5), f32((1 / ab - 1) ** 0.5)
-        with torch.no_grad():
-            ec = R.denoiser_forward(sd, mcfg, x.float(), tt, text["length"], text["xf_proj"], text["xf_out"], eph,
-                                    proj).double()
-            x0 = a * x - b * _blend_np(ec, tab)
-            if mode.startswith("cfg"):
-                eu = R.denoiser_forward(sd, mcfg, x.float(), tt, text["length"], xu_p, xu_o, eph, proj).double()
-                x0u = a * x - b * _blend_np(eu, tab)
-                x0 = x0u + scale * (x0 - x0u)
-        z = None if step_noise is None else _owner(step_noise[i], tab).double()
-        if KIND[mode] == "ddpm":
-            beta = 1 - ab / abp
-            x = beta * abp ** 0.5 / (1 - ab) * x0 + (1 - abp) * (1 - beta) ** 0.5 / (1 - ab) * x
-            if t > 0:
-                x = x + (beta * (1 - abp) / (1 - ab)) ** 0.5 * z
-        elif KIND[mode] == "ddim":
-            eps = (x - ab ** 0.5 * x0) / (1 - ab) ** 0.5
-            sig = eta * ((1 - abp) / (1 - ab)) ** 0.5 * (1 - ab / abp) ** 0.5
-            x = abp ** 0.5 * x0 + max(1 - abp - sig ** 2, 0.0) ** 0.5 * eps
-            if t > 0 and eta > 0:
-                x = x + sig * z
-        elif t == 0:
-            x = x0
-        else:
-            h = lam(t - 1) - lam(t)
-            D_ = x0
-            if i > 0:
-                r = (lam(t) - lam(t + 1)) / h
-                D_ = (1 + 1 / (2 * r)) * x0 - (1 / (2 * r)) * x0_prev
-            x = ((1 - abp) / (1 - ab)) ** 0.5 * x - abp ** 0.5 * np.expm1(-h) * D_
-        x0_prev = x0
-        traj.append(x.float())
-    return traj
-
-
 @pytest.mark.parametrize("schedule", ["plain25", "ddim10"])
 @pytest.mark.parametrize("mode,eta", SOLVERS)
 def test_overlaps_stay_bit_identical_and_match_the_oracle(mode, eta, schedule):
@@ -267,22 +173,25 @@ def test_overlaps_stay_bit_identical_and_match_the_oracle(mode, eta, schedule):
     finals = []
     for use_graph in (True, False):
         got = []
-        out = _loop(d, mode, m, lkw, x_T.cuda(), scale, eta, ns, use_graph,
-                    cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
+        out = S.run_loop(d, mode, m, lkw, scale, eta, use_graph, x_T=x_T.cuda(), step_noise=ns,
+                         cb=lambda i, t, x: got.append(x.clone().cpu())).cpu()
         assert len(got) == N and torch.equal(out, got[-1])
         for i, x in enumerate(got):
             assert _overlaps_equal(x), (use_graph, i)
         # x_T: the owner's values are copied in, so an x_T that already has them gives the same loop bit for bit
         if use_graph:
-            same = _loop(d, mode, m, lkw, _owner(x_T, tab).cuda(), scale, eta, ns, True).cpu()
+            same = S.run_loop(d, mode, m, lkw, scale, eta, True, x_T=_owner(x_T, tab).cuda(), step_noise=ns).cpu()
             assert torch.equal(same, out)
-            want = _oracle(g, meta, d, mode, scale, text, tab, [_owner(x_T, tab)] + got[:-1], eta, ns)
+            # the oracle's denoiser, a numpy blend of the cond and the uncond eps rows before x0, the step noise owner-copied
+            want = S.loop_ref(d, mode, scale, S.oracle_eps(g, meta, text["length"]), prompts=[(text["xf_proj"], text["xf_out"])],
+                              uncond=S.golden_text(g)["uncond"], inputs=[_owner(x_T, tab)] + got[:-1], eta=eta, step_noise=ns,
+                              eps_hook=lambda e: _blend_np(e, tab), noise_hook=lambda z: _owner(z, tab))
             worst = max(rel_inf(got[i], want[i]) for i in range(N))
             print(f"[long] {mode} eta {eta} {schedule}: worst step rel_inf vs restated loop {worst:.2e}")
             assert worst <= 1e-4, worst
         finals.append(out)
     assert torch.equal(finals[0], finals[1])
-    plain = _loop(d, mode, m, kw, x_T.cuda(), scale, eta, ns, True).cpu()
+    plain = S.run_loop(d, mode, m, kw, scale, eta, True, x_T=x_T.cuda(), step_noise=ns).cpu()
     assert not _overlaps_equal(plain)  # without handshakes the windows disagree
 
 
@@ -314,20 +223,6 @@ def test_no_overlap_changes_nothing_and_graph_streams_are_bitwise(mode, eta):
 
 
 # ---- trainer ------------------------------------------------------------------------------------------------------------
-def _trainer(m, meta, steps=1000):
-    Tr = pkg("trainer")
-    synth = pkg("synth")
-    Dt = meta["text_latent_dim"]
-
-    def enc(text, device):
-        xo = torch.stack([synth.uniform_pm1((6, Dt), "cap." + t, 1) * (3.0 ** 0.5) for t in text])
-        return xo.mean(1).to(device), xo.to(device)
-
-    m.text_encoder_fn = enc
-    args = types.SimpleNamespace(device=torch.device("cuda"), diffusion_steps=steps, is_train=False, cfg_scale=2.5)
-    return Tr.DDPMTrainer(args, m)
-
-
 SCRIPTS = [[("walk", 16), ("turn", 12), ("sit", 16)], [("jump", 16)], [("run", 10), ("stop", 12)]]
 
 

@@ -5,8 +5,8 @@
   rows [0, 2) and [2, 4) with sample0 equal the 4-row call bit for bit;
 * a partial loop is the tail of the full loop, bit for bit (x at level s from the full seeded loop's callback, given as
   ``noise=`` with ``start_step=s``), graph and eager, s at both ends and in the middle;
-* every sampler from a noised motion against the loop restated here from abar with the oracle's denoiser, teacher-forced on
-  the device's trajectory; DPM-Solver++'s start step against the first-order formula;
+* every sampler from a noised motion against the loop restated in tests/sampler_ref.py from abar with the oracle's denoiser,
+  teacher-forced on the device's trajectory; DPM-Solver++'s start step against the first-order formula;
 * inversion: every step against the oracle's denoiser and the f64 update, the device clock at ``to_step`` afterwards, graph ==
   eager and two half batches == the whole, bitwise, unguided and guided;
 * the trainer: strength 1 is the plain call and strength 0 the given motion, bitwise; the result does not depend on the batch
@@ -17,40 +17,23 @@ Everything runs on the loops_tiny golden model (at B = 4, T = 16), the 25-step p
 import ctypes as C
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, build_module, golden_state, load_golden, pkg, rel_inf
+from conftest import ROOT, pkg, rel_inf
 
 import motion_features_ref as MR
+import sampler_ref as S
+from sampler_ref import caption_trainer as _trainer, make_diffusion as _diffusion, vp as _vp
 
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import denoiser_ref as R  # noqa: E402
 import philox_ref as P  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 XT = 0x7FFFFFFF  # MDM_NOISE_STREAM_XT
-
-
-def _kw(steps):
-    D = pkg("diffusion")
-    return dict(betas=D.get_named_beta_schedule("linear", steps), model_mean_type=D.ModelMeanType.EPSILON,
-                model_var_type=D.ModelVarType.FIXED_SMALL, loss_type=D.LossType.MSE)
-
-
-def _diffusion(schedule):
-    D = pkg("diffusion")
-    if schedule == "plain25":
-        return D.GaussianDiffusion(**_kw(25))
-    return D.SpacedDiffusion(D.space_timesteps(1000, schedule), **_kw(1000))
-
-
-def _vp(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 # ---- kernel level ------------------------------------------------------------------------------------------------------
@@ -127,27 +110,19 @@ def test_start_kernel_rows_do_not_depend_on_the_split(shape):
 
 # ---- loops -------------------------------------------------------------------------------------------------------------
 def _setup():
-    g, meta = load_golden("loops_tiny")
-    m, _ = build_module(meta, precision=3)
+    g, meta, m, _, _ = S.loops_setup()
     synth = pkg("synth")
     B, T, F_ = 4, 16, g["x_T"].shape[2]  # the golden's model at four rows, so that a batch splits into halves
     _, _, length, xf_proj, xf_out = synth.synth_inputs(B, T, F_, 6, meta["text_latent_dim"], 9, min_len=4)
     g = dict(g, length=length, xf_proj=xf_proj, xf_out=xf_out)
     kw = {"xf_proj": g["xf_proj"].cuda(), "xf_out": g["xf_out"].cuda(), "length": g["length"].cuda(),
           "text": ["a person walks"] * B}
-    m.set_uncond_embedding(g["xf_proj_uncond"][:1].cuda(), g["xf_out_uncond"][:1].cuda())
     init = synth.uniform_pm1((B, T, F_), "start.init", meta["iseed"]) * 1.5
     return g, meta, m, kw, init
 
 
 def _loop(d, mode, m, kw, scale, eta, use_graph, cb=None, **more):
-    B, T, F_ = kw["xf_out"].shape[0], 16, 263
-    common = dict(clip_denoised=False, model_kwargs=kw, use_graph=use_graph, callback=cb, cfg_scale=scale, **more)
-    if mode == "cfg":
-        return d.p_sample_loop_with_cfg(m, (B, T, F_), **common)
-    if mode == "cfg_ddim":
-        return d.ddim_sample_loop_with_cfg(m, (B, T, F_), eta=eta, **common)
-    return d.dpm_solver_sample_loop_with_cfg(m, (B, T, F_), **common)
+    return S.run_loop(d, mode, m, kw, scale, eta, use_graph, cb=cb, shape=(kw["xf_out"].shape[0], 16, 263), **more)
 
 
 @pytest.mark.parametrize("mode,eta,schedule", [("cfg", 0.0, "plain25"), ("cfg_ddim", 0.0, "ddim10"), ("cfg_ddim", 0.5, "ddim10")])
@@ -173,26 +148,6 @@ def test_a_partial_loop_is_the_tail_of_the_full_loop(mode, eta, schedule):
         _loop(d, mode, m, kw, scale, eta, True, seed=11, start_step=3)
 
 
-def _forward(g, meta, x, t_orig, B):
-    sd, eph, proj, mcfg = golden_state(meta)
-    tt = torch.full((B,), int(t_orig), dtype=torch.int64)
-    xu_p, xu_o = g["xf_proj_uncond"][:1].expand(B, -1), g["xf_out_uncond"][:1].expand(B, -1, -1)
-    with torch.no_grad():
-        ec = R.denoiser_forward(sd, mcfg, x.float(), tt, g["length"], g["xf_proj"], g["xf_out"], eph, proj).double()
-        eu = R.denoiser_forward(sd, mcfg, x.float(), tt, g["length"], xu_p, xu_o, eph, proj).double()
-    return ec, eu
-
-
-def _x0(x, ec, eu, ab, scale):
-    """The (guided) x0 of a step in f64, with the two f32 table entries the kernels read."""
-    a, b = float(np.float32((1 / ab) ** 0.5)), float(np.float32((1 / ab - 1) ** 0.5))
-    x0 = a * x - b * ec
-    if eu is not None:
-        x0u = a * x - b * eu
-        x0 = x0u + scale * (x0 - x0u)
-    return x0
-
-
 @pytest.mark.parametrize("mode,eta,schedule", [("cfg", 0.0, "plain25"), ("cfg_ddim", 0.5, "ddim10"), ("cfg_dpmpp", 0.0, "ddim10"),
                                                ("cfg_dpmpp", 0.0, "plain25")])
 def test_samplers_from_a_noised_motion_match_the_oracle(mode, eta, schedule):
@@ -205,8 +160,6 @@ def test_samplers_from_a_noised_motion_match_the_oracle(mode, eta, schedule):
     B, T, F_ = init.shape
     s = N // 2
     acp = d.alphas_cumprod
-    tmap = d.timestep_map if d.timestep_map is not None else np.arange(N)
-    lam = lambda i: 0.5 * np.log(acp[i] / (1 - acp[i]))  # noqa: E731
     nz = torch.from_numpy(P.normal(T * F_, B, 0, seed, XT)).view(B, T, F_).double()
     x_s = acp[s] ** 0.5 * init.double() + (1 - acp[s]) ** 0.5 * nz
     got = []
@@ -215,38 +168,14 @@ def test_samplers_from_a_noised_motion_match_the_oracle(mode, eta, schedule):
     assert len(got) == s + 1 and torch.equal(out, got[-1])
     eager = _loop(d, mode, m, kw, scale, eta, False, seed=seed, init_motion=init.cuda(), start_step=s).cpu()
     assert torch.equal(eager, out)
-    inputs, x0_prev = [x_s.float()] + got[:-1], None
-    for i in sorted({0, 1, s // 2, s - 1, s}):
-        t = s - i
-        x = inputs[i].double()
-        ab, abp = acp[t], (acp[t - 1] if t > 0 else 1.0)
-        ec, eu = _forward(g, meta, x, tmap[t], B)
-        x0 = _x0(x, ec, eu, ab, scale)
-        z = torch.from_numpy(P.normal(T * F_, B, 0, seed, t)).view(B, T, F_).double()
-        if mode == "cfg":
-            beta = 1 - ab / abp
-            want = beta * abp ** 0.5 / (1 - ab) * x0 + (1 - abp) * (1 - beta) ** 0.5 / (1 - ab) * x
-            if t > 0:
-                want = want + (beta * (1 - abp) / (1 - ab)) ** 0.5 * z
-        elif mode == "cfg_ddim":
-            eps = (x - ab ** 0.5 * x0) / (1 - ab) ** 0.5
-            sig = eta * ((1 - abp) / (1 - ab)) ** 0.5 * (1 - ab / abp) ** 0.5
-            want = abp ** 0.5 * x0 + max(1 - abp - sig ** 2, 0.0) ** 0.5 * eps
-            if t > 0:
-                want = want + sig * z
-        elif t == 0:
-            want = x0
-        else:
-            h = lam(t - 1) - lam(t)
-            D_ = x0
-            if i > 0:  # second order needs the x0 of the step before: recomputed from that step's input
-                xp = inputs[i - 1].double()
-                x0_prev = _x0(xp, *_forward(g, meta, xp, tmap[t + 1], B), acp[t + 1], scale)
-                r = (lam(t) - lam(t + 1)) / h
-                D_ = (1 + 1 / (2 * r)) * x0 - (1 / (2 * r)) * x0_prev
-            want = ((1 - abp) / (1 - ab)) ** 0.5 * x - abp ** 0.5 * np.expm1(-h) * D_
-        e = rel_inf(got[i], want)
-        print(f"[start] {mode} eta {eta} {schedule}: step {i} (t = {t}) rel_inf {e:.2e}")
+    # second order needs the x0 of the step before: ``check`` recomputes it from that step's input; the step noise is keyed on t
+    steps = sorted({0, 1, s // 2, s - 1, s})
+    zs = {i: torch.from_numpy(P.normal(T * F_, B, 0, seed, s - i)).view(B, T, F_) for i in steps}
+    want = S.loop_ref(d, mode, scale, S.oracle_eps(g, meta), inputs=[x_s.float()] + got[:-1], check=steps, start=s, eta=eta,
+                      step_noise=zs, **S.golden_text(g))
+    for i in steps:
+        e = rel_inf(got[i], want[i])
+        print(f"[start] {mode} eta {eta} {schedule}: step {i} (t = {s - i}) rel_inf {e:.2e}")
         assert e < 1e-3, (i, e)
     if mode == "cfg_dpmpp":  # and the second-order formula at the start step is NOT what ran
         assert s < N - 1 and d.solver_coefficients("dpmpp")[s, 2] != 0.0
@@ -267,7 +196,7 @@ def test_samplers_from_a_noised_motion_match_the_oracle(mode, eta, schedule):
 def test_inversion(scale):
     g, meta, m, kw, init = _setup()
     d = _diffusion("ddim10")
-    N, acp, tmap = d.num_timesteps, d.alphas_cumprod, d.timestep_map
+    N = d.num_timesteps
     B, T, F_ = init.shape
     mode = "ddim" if scale == 1.0 else "cfg_ddim"
     runs = {}
@@ -280,14 +209,9 @@ def test_inversion(scale):
         assert [(i, t) for i, t, _ in got] == [(i, i) for i in range(N - 1)] and torch.equal(out, got[-1][2])
         runs[use_graph] = [x for _, _, x in got]
     assert all(torch.equal(a, b) for a, b in zip(runs[True], runs[False]))  # graph == eager
-    inputs = [init] + runs[True][:-1]
+    want = S.loop_ref(d, mode, scale, S.oracle_eps(g, meta), inputs=[init] + runs[True][:-1], direction=+1, **S.golden_text(g))
     for t in range(N - 1):  # every step: row t takes level t to level t + 1
-        x = inputs[t].double()
-        ec, eu = _forward(g, meta, x, tmap[t], B)
-        x0 = _x0(x, ec, None if scale == 1.0 else eu, acp[t], scale)
-        eps = (x - acp[t] ** 0.5 * x0) / (1 - acp[t]) ** 0.5
-        want = acp[t + 1] ** 0.5 * x0 + (1 - acp[t + 1]) ** 0.5 * eps
-        e = rel_inf(runs[True][t], want)
+        e = rel_inf(runs[True][t], want[t])
         print(f"[invert] scale {scale}: row {t} rel_inf {e:.2e}")
         assert e < 1e-3, (t, e)
     # the public loop, to the last step and to a step on the way
@@ -310,20 +234,6 @@ def test_inversion(scale):
 
 
 # ---- trainer -----------------------------------------------------------------------------------------------------------
-def _trainer(m, meta, steps=1000):
-    Tr = pkg("trainer")
-    synth = pkg("synth")
-    Dt = meta["text_latent_dim"]
-
-    def enc(text, device):  # a different embedding per caption, so a mixed-up order would show
-        xo = torch.stack([synth.uniform_pm1((6, Dt), "cap." + t, 1) * (3.0 ** 0.5) for t in text])
-        return xo.mean(1).to(device), xo.to(device)
-
-    m.text_encoder_fn = enc
-    args = types.SimpleNamespace(device=torch.device("cuda"), diffusion_steps=steps, is_train=False, cfg_scale=2.5)
-    return Tr.DDPMTrainer(args, m)
-
-
 CAPS = ["a", "b", "c", "d"]
 
 

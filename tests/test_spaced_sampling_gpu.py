@@ -1,33 +1,24 @@
 """GPU: timestep respacing and the few-step guided samplers (guided DDIM, DPM-Solver++(2M)).
 
 * the two new kernels (csrc/solver.hip) against an f64 restatement on random inputs;
-* the spaced loops against the oracle's denoiser fed the ORIGINAL timesteps, with the solver arithmetic restated here from
-  abar and lambda (not from the product's coefficient tables);
+* the spaced loops against the oracle's denoiser fed the ORIGINAL timesteps, with the solver arithmetic restated in
+  tests/sampler_ref.py from abar and lambda (not from the product's coefficient tables), free-running;
 * consistency: every step kept == the plain schedule, order-1 DPM-Solver++ == DDIM at eta 0, graph == eager and two
   streams == one bitwise, the trainer's result independent of the batch split;
 * the configs[1] shape in bf16 through DDPMTrainer.generate.
 """
 import ctypes as C
-import os
-import sys
 import types
 
-import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, build_module, golden_state, load_golden, pkg, rel_inf
+from conftest import pkg, rel_inf
 
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import denoiser_ref as R  # noqa: E402
+import sampler_ref as S
+from sampler_ref import caption_trainer as _trainer, diffusion_kwargs as _kw, loops_setup as _setup, vp as _vp
 
 pytestmark = pytest.mark.gpu
-
-
-def _kw(steps):
-    D = pkg("diffusion")
-    return dict(betas=D.get_named_beta_schedule("linear", steps), model_mean_type=D.ModelMeanType.EPSILON,
-                model_var_type=D.ModelVarType.FIXED_SMALL, loss_type=D.LossType.MSE)
 
 
 def _spaced(spacing, steps=1000):
@@ -35,40 +26,7 @@ def _spaced(spacing, steps=1000):
     return D.SpacedDiffusion(D.space_timesteps(steps, spacing), **_kw(steps))
 
 
-def _vp(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
 # ---- kernel level ------------------------------------------------------------------------------------------------------
-def _update(x, ec, eu, xp, nz, tab, coef, steps, t, scale, clip, xo, x0o):
-    L = pkg("_lib")
-    L.check(L.lib().mdm_guided_update(_vp(x), _vp(ec), _vp(eu), _vp(xp), _vp(nz), C.c_int64(x.numel()), _vp(tab), _vp(coef),
-                                      C.c_int32(steps), C.c_void_p(0), C.c_int32(t), C.c_float(scale), C.c_int32(clip),
-                                      _vp(xo), _vp(x0o), C.c_void_p(L.stream_ptr())), "mdm_guided_update")
-
-
-def _update_ref(d, coef64, t, x, ec, eu, xp, nz, scale, clip):
-    """f64 arithmetic on the kernel's inputs: the f64 table entries and coefficients rounded to f32 as they are handed over."""
-    f32 = lambda v: float(np.float32(v))  # noqa: E731
-    a, b = f32(d.sqrt_recip_alphas_cumprod[t]), f32(d.sqrt_recipm1_alphas_cumprod[t])
-    x, ec = x.double(), ec.double()
-    x0 = a * x - b * ec
-    if clip:
-        x0 = x0.clamp(-1, 1)
-    if eu is not None:
-        x0u = a * x - b * eu.double()
-        if clip:
-            x0u = x0u.clamp(-1, 1)
-        x0 = x0u + scale * (x0 - x0u)
-    cx, c0, c1, cn = (f32(c) for c in coef64[t])
-    out = cx * x + c0 * x0
-    if xp is not None:
-        out = out + c1 * xp.double()
-    if nz is not None:
-        out = out + cn * nz.double()
-    return out, x0
-
-
 @pytest.mark.parametrize("schedule", ["plain50", "ddim10", "ddim50"])
 def test_guided_update_kernel_matches_f64(schedule):
     d = pkg("diffusion").GaussianDiffusion(**_kw(50)) if schedule == "plain50" else _spaced(schedule)
@@ -86,9 +44,9 @@ def test_guided_update_kernel_matches_f64(schedule):
                 for guided in (True, False):
                     eu_ = eu if guided else None
                     xo, x0o = torch.empty(shape, device="cuda"), torch.empty(shape, device="cuda")
-                    _update(x.cuda(), ec.cuda(), eu_.cuda() if guided else None, xp.cuda(), nz.cuda(), tab, coef, N, t, 2.5,
-                            clip, xo, x0o)
-                    ref, ref0 = _update_ref(d, coef64, t, x, ec, eu_, xp, nz, 2.5, clip)
+                    S.guided_update(x.cuda(), ec.cuda(), eu_.cuda() if guided else None, xp.cuda(), nz.cuda(), None, None, tab,
+                                    coef, N, t, 2.5, clip, xo, x0o)
+                    ref, ref0 = S.update_kernel_ref(d, coef64, t, x, ec, eu_, xp, nz, None, None, 2.5, clip)
                     e = rel_inf(xo.cpu(), ref)
                     # a clamped x0 is at most 1 while a*x - b*eps cancels terms of ~a*|x| (a = 359 at t = 49 of 50): its f32
                     # error is measured against the size of those terms (unclamped, that IS the size of x0)
@@ -101,12 +59,12 @@ def test_guided_update_kernel_matches_f64(schedule):
     xb, pb = torch.zeros(x.numel() + 1, device="cuda"), torch.zeros(x.numel() + 1, device="cuda")
     xi, pi = xb[1:].view(shape), pb[1:].view(shape)
     xi.copy_(x.cuda()), pi.copy_(xp.cuda())
-    _update(xi, ec.cuda(), eu.cuda(), pi, None, tab, coef, N, t, 2.5, 0, xi, pi)
-    ref, ref0 = _update_ref(d, coef64, t, x, ec, eu, xp, None, 2.5, False)
+    S.guided_update(xi, ec.cuda(), eu.cuda(), pi, None, None, None, tab, coef, N, t, 2.5, 0, xi, pi)
+    ref, ref0 = S.update_kernel_ref(d, coef64, t, x, ec, eu, xp, None, None, None, 2.5, False)
     assert rel_inf(xi.cpu(), ref) < 1e-5 and rel_inf(pi.cpu(), ref0) < 1e-5
     # the same in place on aligned buffers
     xa, pa = x.cuda(), xp.cuda()
-    _update(xa, ec.cuda(), eu.cuda(), pa, None, tab, coef, N, t, 2.5, 0, xa, pa)
+    S.guided_update(xa, ec.cuda(), eu.cuda(), pa, None, None, None, tab, coef, N, t, 2.5, 0, xa, pa)
     assert rel_inf(xa.cpu(), ref) < 1e-5 and rel_inf(pa.cpu(), ref0) < 1e-5
 
 
@@ -126,60 +84,6 @@ def test_fill_timesteps_mapped_reads_the_device_counter():
 
 
 # ---- loops against the oracle --------------------------------------------------------------------------------------------
-def _setup():
-    g, meta = load_golden("loops_tiny")
-    m, _ = build_module(meta, precision=3)
-    synth = pkg("synth")
-    B, T, F_ = g["x_T"].shape
-
-    def noises(tag, n):
-        return [synth.uniform_pm1((B, T, F_), f"noise.{tag}.{i}", meta["iseed"]) * (3.0 ** 0.5) for i in range(n)]
-
-    kw = {"xf_proj": g["xf_proj"].cuda(), "xf_out": g["xf_out"].cuda(), "length": g["length"].cuda(),
-          "text": ["a person walks"] * B}
-    m.set_uncond_embedding(g["xf_proj_uncond"][:1].cuda(), g["xf_out_uncond"][:1].cuda())
-    return g, meta, m, noises, kw
-
-
-def _oracle(g, meta, d, kind, scale, eta=0.0, step_noise=None, order=2):
-    """The guided loop restated from abar: forwards of the oracle fed the original timesteps, guidance on pred_xstart,
-    then the DDIM update (eps re-derived from the guided x0) or DPM-Solver++(2M) in lambda = log(alpha / sigma)."""
-    sd, eph, proj, mcfg = golden_state(meta)
-    B = g["x_T"].shape[0]
-    xu_p, xu_o = g["xf_proj_uncond"][:1].expand(B, -1), g["xf_out_uncond"][:1].expand(B, -1, -1)
-    acp, N = d.alphas_cumprod, d.num_timesteps
-    lam = lambda i: 0.5 * np.log(acp[i] / (1 - acp[i]))  # noqa: E731
-    x, x0_prev, traj = g["x_T"].double(), None, []
-    for i in range(N):
-        t = N - 1 - i
-        tt = torch.full((B,), int(d.timestep_map[t]), dtype=torch.int64)
-        with torch.no_grad():
-            ec = R.denoiser_forward(sd, mcfg, x.float(), tt, g["length"], g["xf_proj"], g["xf_out"], eph, proj).double()
-            eu = R.denoiser_forward(sd, mcfg, x.float(), tt, g["length"], xu_p, xu_o, eph, proj).double()
-        a, b = float(np.float32(d.sqrt_recip_alphas_cumprod[t])), float(np.float32(d.sqrt_recipm1_alphas_cumprod[t]))
-        x0c, x0u = a * x - b * ec, a * x - b * eu
-        x0 = x0u + scale * (x0c - x0u)
-        ab, abp = acp[t], (acp[t - 1] if t > 0 else 1.0)
-        if kind == "ddim":
-            eps = (x - ab ** 0.5 * x0) / (1 - ab) ** 0.5
-            sig = eta * ((1 - abp) / (1 - ab)) ** 0.5 * (1 - ab / abp) ** 0.5
-            x = abp ** 0.5 * x0 + max(1 - abp - sig ** 2, 0.0) ** 0.5 * eps
-            if t > 0 and eta > 0:
-                x = x + sig * step_noise[i].double()
-        elif t == 0:
-            x = x0
-        else:
-            h = lam(t - 1) - lam(t)
-            D_ = x0
-            if order == 2 and i > 0:
-                r = (lam(t) - lam(t + 1)) / h
-                D_ = (1 + 1 / (2 * r)) * x0 - (1 / (2 * r)) * x0_prev
-            x = ((1 - abp) / (1 - ab)) ** 0.5 * x - abp ** 0.5 * np.expm1(-h) * D_
-        x0_prev = x0
-        traj.append(x.float())
-    return traj
-
-
 @pytest.mark.parametrize("use_graph", [True, False])
 @pytest.mark.parametrize("spacing", ["ddim10", [4, 3, 3]])
 @pytest.mark.parametrize("solver", ["ddim0", "ddim0.5", "dpmpp2m"])
@@ -195,13 +99,14 @@ def test_spaced_guided_loops_match_the_oracle(solver, spacing, use_graph):
     if solver == "dpmpp2m":
         d.dpm_solver_sample_loop_with_cfg(m, shape, noise=g["x_T"].cuda(), clip_denoised=False, model_kwargs=kw,
                                           cfg_scale=scale, use_graph=use_graph, callback=cb)
-        want = _oracle(g, meta, d, "dpmpp", scale)
+        want = S.loop_ref(d, "cfg_dpmpp", scale, S.oracle_eps(g, meta), x_T=g["x_T"], **S.golden_text(g))
     else:
         eta = float(solver[4:])
         ns = noises(f"spaced.{eta}", N)
         d.ddim_sample_loop_with_cfg(m, shape, noise=g["x_T"].cuda(), clip_denoised=False, model_kwargs=kw, cfg_scale=scale,
                                     eta=eta, step_noise=ns, use_graph=use_graph, callback=cb)
-        want = _oracle(g, meta, d, "ddim", scale, eta, ns)
+        want = S.loop_ref(d, "cfg_ddim", scale, S.oracle_eps(g, meta), x_T=g["x_T"], eta=eta, step_noise=ns,
+                          **S.golden_text(g))
     for i in (0, N // 2, N - 2, N - 1):
         e = rel_inf(got[i], want[i])
         assert e < 1e-3, (i, e)
@@ -262,20 +167,6 @@ def test_graph_equals_eager_and_two_streams_equal_one_bitwise(mode, eta):
 
 
 # ---- trainer -----------------------------------------------------------------------------------------------------------
-def _trainer(m, meta, steps=1000):
-    Tr = pkg("trainer")
-    synth = pkg("synth")
-    Dt = meta["text_latent_dim"]
-
-    def enc(text, device):  # a different embedding per caption, so a mixed-up order would show
-        xo = torch.stack([synth.uniform_pm1((6, Dt), "cap." + t, 1) * (3.0 ** 0.5) for t in text])
-        return xo.mean(1).to(device), xo.to(device)
-
-    m.text_encoder_fn = enc
-    args = types.SimpleNamespace(device=torch.device("cuda"), diffusion_steps=steps, is_train=False, cfg_scale=2.5)
-    return Tr.DDPMTrainer(args, m)
-
-
 def test_trainer_generate_few_step_is_independent_of_the_batch_split():
     g, meta, m, noises, kw = _setup()
     tr = _trainer(m, meta)
