@@ -612,6 +612,31 @@ int mdm_joint_guidance(float* x, float* x0, const float* mask, const int32_t* le
                        int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
                        void* stream);
 
+/* Joint-position control over the canvas of a long motion (csrc/motion_control_canvas.hip): the loss above
+ * over canvas frames.  Motion m < M owns canvas frames c in [motion_offsets[m], motion_offsets[m + 1]) (int32 (M + 1), rising
+ * from 0 to total_frames); the feature row of frame c is row frame_rows[c] of the (rows, F) buffers x / x0 / mask
+ * (frame_rows[c] = window_row * T + frame in a sampler batch); targets and weights are dense (total_frames, J, 3) in canvas
+ * order, mean / std (M, F).  L_m = sum over the motion's frames of W (P - G)^2 with P = recover_from_ric over the motion's
+ * rows in canvas order: a target late in the canvas reaches the root velocities of every earlier frame, whatever row holds
+ * them.  Any canvas length: per-frame state lives in `workspace`, mdm_canvas_control_workspace_floats(total_frames, F)
+ * floats (0 for an F not of the form 12 J - 1), the caller's, used by one call at a time.
+ * mdm_canvas_joint_loss_grad: loss_out (M) and grad_out (total_frames, F) dense in canvas order.  mdm_canvas_joint_guidance:
+ * as mdm_joint_guidance, x0 and x updated at the rows frame_rows names and nowhere else, nothing stored where delta == 0.
+ * The scans are wave-parallel fp64 sums: P agrees with mdm_motion_postprocess to rounding, not bit for bit.
+ * frame_rows must be in range and distinct and the offsets must rise: the caller's tables, not checked here.  No allocation,
+ * no host sync, graph-capturable.  MDM_ERR_ARG: a null pointer (mask excepted), a bad F, M < 0, iters outside
+ * [1, MDM_CONTROL_MAX_ITERS], a non-finite scale, steps <= 0 or t_imm outside [0, steps) without t_dev.
+ * MDM_ERR_UNSUPPORTED: more than 77 joints (the LDS tile the rows are transposed through).  M == 0 and empty motions are
+ * no-ops. */
+int64_t mdm_canvas_control_workspace_floats(int32_t total_frames, int32_t F);
+int mdm_canvas_joint_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
+                               const float* std, const float* targets, const float* weights, int32_t M, int32_t F,
+                               float* loss_out, float* grad_out, float* workspace, void* stream);
+int mdm_canvas_joint_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
+                              const float* mean, const float* std, const float* targets, const float* weights, int32_t M,
+                              int32_t F, float scale, int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev,
+                              int32_t t_imm, float* workspace, void* stream);
+
 /* ---- long-motion handshakes ---------------------------------------------------------------------
  * In place over the shared canvas frames only.  For every group g < groups, shared frame c < nshared and feature j < F:
  *   v = sum over entries e in [offsets[c], offsets[c+1]) of weights[e] * x[g*group_stride + rows[e]*F + j]

@@ -196,6 +196,9 @@ PROTOTYPES = {
     "mdm_joint_control_max_frames": (_I32, [_I32]),
     "mdm_joint_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mdm_joint_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F32, _I32, _P, _I32, _P, _I32, _P]),
+    "mdm_canvas_control_workspace_floats": (_I64, [_I32, _I32]),
+    "mdm_canvas_joint_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "mdm_canvas_joint_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _F32, _I32, _P, _I32, _P, _I32, _P, _P]),
     "mdm_handshake_blend": (_I32, [_P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
     "mdm_moe_train_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32]),
     "mdm_moe_ffn_train_forward": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _F32, _U64, _P, _P, _P, _P,

@@ -2,8 +2,9 @@
 
 ``expand_to`` is the one align-and-expand of a weight / mask tensor.  ``strength_steps`` and ``init_rows_from`` are the host
 side of motion-to-motion generation (a given motion as the start of a partial loop).  The
-``check_*_kwargs`` functions validate the ``model_kwargs`` of one sampler batch (motion editing, composed prompts, joint control, long-motion handshakes; DESIGN.md
-§11, §12, §14, §15) for ``diffusion._StepRunner``; ``diffusion`` imports them under the same names.  ``Conditioning``
+``check_*_kwargs`` functions validate the ``model_kwargs`` of one sampler batch (motion editing, composed prompts, joint
+control, long-motion handshakes, joint control over a long motion's canvas) for
+``diffusion._StepRunner``; ``diffusion`` imports them under the same names.  ``Conditioning``
 holds the checked conditioning of one public ``DDPMTrainer`` call and hands out each batch's share as ``model_kwargs``.
 Host logic only: runs on CPU tensors and never loads the HIP library.
 """
@@ -128,7 +129,7 @@ def check_control_kwargs(kw, shape):
     given = [k for k, v in zip(names, (g, w, mean, std)) if v is not None]
     extra = [k for k in ("control_scale", "control_iters") if kw.get(k) is not None]
     if not given:
-        if extra:
+        if extra and not any(kw.get(k) is not None for k in CANVAS_CONTROL_KEYS):  # they may belong to canvas control
             raise ValueError(f"{' / '.join(extra)} given without control_joints / control_weights / control_mean / control_std")
         return None
     if len(given) != 4:
@@ -169,6 +170,102 @@ def check_control_kwargs(kw, shape):
     return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters)}
 
 
+CANVAS_CONTROL_KEYS = ("canvas_control_offsets", "canvas_control_rows", "canvas_control_joints", "canvas_control_weights",
+                       "canvas_control_mean", "canvas_control_std")
+
+
+def check_canvas_control_kwargs(kw, shape):
+    """The canvas joint-control inputs of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when none
+    of the ``canvas_control_*`` keys is given, else a dict of CPU tensors ``offsets`` int32 (M + 1), ``rows`` int32 (total),
+    ``targets`` (total, J, 3), ``weights`` broadcast to it (a view), ``mean`` / ``std`` (M, F), and ``M``, ``total``, ``scale``
+    (default 1) and ``iters`` (default 1).  Motion m's canvas frames are ``[offsets[m], offsets[m + 1])``; frame c lives in row
+    ``rows[c]`` = window row * T + frame of the batch.  The tables describe whole motions, not batch rows: dist.shard_kwargs
+    refuses them.
+    Raises ValueError when only some of the six are given, without handshake tables when a motion spans several windows, for
+    offsets that do not rise from 0 to the row count, rows outside [0, B T), repeated, at or past their window's ``length`` or
+    naming a shared frame's copy instead of its owner, shape or broadcast errors, non-finite values, negative weights, a zero
+    std, a non-finite scale, iters outside [1, MDM_CONTROL_MAX_ITERS], and together with per-window control or composed
+    prompts.  Host logic."""
+    from .motion_control import joints_for_feats
+    names = CANVAS_CONTROL_KEYS
+    vals = [kw.get(k) for k in names]
+    given = [k for k, v in zip(names, vals) if v is not None]
+    if not given:
+        return None
+    if len(given) != len(names):
+        raise ValueError(f"canvas joint control needs all of {', '.join(names)}; missing "
+                         f"{', '.join(k for k in names if k not in given)}")
+    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std")):
+        raise ValueError("canvas_control_* and the per-window control_joints / control_weights are exclusive")
+    if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
+        raise ValueError("canvas joint control does not combine with composed prompts")
+    B, T, F_ = (int(v) for v in shape)
+    J = joints_for_feats(F_)
+    off, rows, g, w, mean, std = (torch.as_tensor(v).detach().cpu() for v in vals)
+    for name, v in ((names[0], off), (names[1], rows)):
+        if v.dim() != 1 or v.is_floating_point() or v.is_complex() or v.dtype == torch.bool:
+            raise ValueError(f"{name} must be a 1-D integer tensor, not {v.dtype} of shape {tuple(v.shape)}")
+    for name, v in zip(names[2:], (g, w, mean, std)):
+        if not v.is_floating_point():
+            raise ValueError(f"{name} must be floating point")
+    off, rows = off.to(torch.int64), rows.to(torch.int64)
+    total, M = rows.numel(), off.numel() - 1
+    if M < 0 or int(off[0]) != 0 or int(off[-1]) != total or bool((off[1:] < off[:-1]).any()):
+        raise ValueError(f"canvas_control_offsets must rise from 0 to the row count {total}")
+    if total and (int(rows.min()) < 0 or int(rows.max()) >= B * T):
+        raise ValueError(f"canvas_control_rows must lie in [0, B * T) = [0, {B * T})")
+    if torch.unique(rows).numel() != total:
+        raise ValueError("canvas_control_rows repeats a row: every canvas frame has one owner row")
+    length = kw.get("length")
+    if length is not None and total:
+        length = torch.as_tensor(length).detach().cpu().flatten().to(torch.int64)
+        if length.numel() != B:
+            raise ValueError(f"length must have {B} entries")
+        if bool((rows % T >= length[rows // T]).any()):
+            raise ValueError("canvas_control_rows points at a frame at or past its window's length")
+    hs_names = ("handshake_offsets", "handshake_rows", "handshake_weights", "handshake_owner_rows")
+    if all(kw.get(k) is None for k in hs_names):
+        win = rows // T
+        for m in range(M):
+            seg = win[int(off[m]):int(off[m + 1])]
+            if seg.numel() and int(seg.min()) != int(seg.max()):
+                raise ValueError(f"motion {m} spans several windows: canvas joint control needs the handshake tables that tie "
+                                 "them together")
+    elif kw.get("handshake_owner_rows") is not None and kw.get("handshake_offsets") is not None:
+        own = torch.as_tensor(kw["handshake_owner_rows"]).detach().cpu().flatten().to(torch.int64)
+        first = torch.zeros(own.numel(), dtype=torch.bool)
+        first[torch.as_tensor(kw["handshake_offsets"]).detach().cpu().flatten().to(torch.int64)[:-1]] = True
+        if bool(torch.isin(rows, own[~first]).any()):
+            raise ValueError("canvas_control_rows names a copy of a shared frame: every canvas frame is steered in its owner "
+                             "(left) window's row, and the copy takes the owner's values")
+    if tuple(g.shape) != (total, J, 3):
+        raise ValueError(f"canvas_control_joints has shape {tuple(g.shape)}, expected {(total, J, 3)}")
+    w = expand_to(w, 1, (total, J, 3), "canvas_control_weights", f"must lead with the row count {total}")
+    for name, v in (("canvas_control_mean", mean), ("canvas_control_std", std)):
+        if tuple(v.shape) != (M, F_):
+            raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(M, F_)} (one row per motion)")
+    if not bool(torch.isfinite(g).all()):
+        raise ValueError("canvas_control_joints has non-finite values")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("canvas_control_weights has non-finite values")
+    if not bool((w >= 0).all()):
+        raise ValueError("canvas_control_weights must be >= 0")
+    if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all())):
+        raise ValueError("canvas_control_mean / canvas_control_std have non-finite values")
+    if bool((std == 0).any()):
+        raise ValueError("canvas_control_std has zero entries")
+    scale = kw.get("control_scale")
+    scale = 1.0 if scale is None else float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("control_scale must be finite")
+    iters = kw.get("control_iters")
+    iters = 1 if iters is None else iters
+    if isinstance(iters, bool) or int(iters) != iters or not 1 <= int(iters) <= L.CONTROL_MAX_ITERS:
+        raise ValueError(f"control_iters must be an integer in [1, {L.CONTROL_MAX_ITERS}]")
+    return {"offsets": off.to(torch.int32), "rows": rows.to(torch.int32), "targets": g, "weights": w, "mean": mean, "std": std,
+            "M": M, "total": total, "scale": scale, "iters": int(iters)}
+
+
 def check_handshake_kwargs(kw, shape):
     """The long-motion tables of ``model_kwargs`` for a sample of ``shape`` (B, T, F): None when none of the ``handshake_*``
     keys is given or the tables have no shared frame, else a dict of CPU tensors ``offsets`` (nshared + 1), ``rows`` and
@@ -190,8 +287,8 @@ def check_handshake_kwargs(kw, shape):
     if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
         raise NotImplementedError("composed prompts over a long motion are not supported yet")
     if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std")):
-        raise NotImplementedError("joint control over a long motion is not supported yet: its targets would need canvas "
-                                  "coordinates")
+        raise NotImplementedError("per-window joint control over a long motion is not supported: targets need canvas "
+                                  "coordinates; give them as canvas_control_* (generate_long(control_joints=))")
     B, T, _ = (int(v) for v in shape)
     off, rows, w, own = (torch.as_tensor(v).detach().cpu() for v in vals)
     for name, v in zip(names, (off, rows, w, own)):

@@ -39,6 +39,12 @@ motion; every step then blends the eps rows of the shared canvas frames before i
 the loops' x_T) from each overlap's owner window (``mdm_handshake_blend``), so the overlaps stay bit for bit
 equal.
 
+Joint control over a long motion: with the handshake tables ``model_kwargs`` may carry ``canvas_control_offsets``
+/ ``canvas_control_rows`` (which batch row owns each canvas frame of each motion), ``canvas_control_joints`` /
+``canvas_control_weights`` in canvas frames and ``canvas_control_mean`` / ``canvas_control_std`` (one row per motion), with
+``control_scale`` / ``control_iters``; every step then runs the guidance once per motion over its whole canvas
+(``mdm_canvas_joint_guidance``) and copies the owner's x and x0 into every overlap.
+
 Motion to motion: the guided loops take ``init_motion`` and ``start_step`` and then start from that motion
 noised to the level of the start step (``mdm_diffuse_start``) and walk only the steps below it; ``ddim_invert_loop`` runs the
 deterministic DDIM update upwards from a clean motion, the ``"ddim_inverse"`` coefficient table through the same fused update,
@@ -58,7 +64,8 @@ import torch
 
 from . import _lib as L
 from .conditioning import GUIDED as _GUIDED  # the checks keep their names here as well (tests)
-from .conditioning import check_compose_kwargs, check_control_kwargs, check_handshake_kwargs, check_inpaint_kwargs
+from .conditioning import (check_canvas_control_kwargs, check_compose_kwargs, check_control_kwargs, check_handshake_kwargs,
+                           check_inpaint_kwargs)
 
 
 class ModelMeanType(enum.Enum):
@@ -706,9 +713,19 @@ class _StepRunner:
         # long motions: the handshake tables of the overlapping windows
         hs = check_handshake_kwargs(kw, shape)
         self.hs = None if hs is None else {k: v.to(dev).contiguous() if torch.is_tensor(v) else v for k, v in hs.items()}
+        # joint control over the canvases of long motions: the row tables, canvas-order targets and weights, the workspace
+        cc = check_canvas_control_kwargs(kw, shape)
+        self.cctl = None
+        if cc is not None:
+            J, tot = cc["targets"].shape[1], cc["total"]
+            nws = int(L.lib().mdm_canvas_control_workspace_floats(tot, Fe))
+            self.cctl = dict(scale=cc["scale"], iters=cc["iters"], M=cc["M"], offsets=cc["offsets"].to(dev).contiguous(),
+                             rows=cc["rows"].to(dev).contiguous(), targets=f32(cc["targets"], (tot, J, 3)),
+                             weights=f32(cc["weights"], (tot, J, 3)), mean=f32(cc["mean"], (cc["M"], Fe)),
+                             std=f32(cc["std"], (cc["M"], Fe)), ws=torch.empty(max(nws, 1), dtype=torch.float32, device=dev))
         # few-step modes (and every mode when editing, composing or controlling): per-step coefficients of the fused update;
         # self.x0 doubles as x0_prev (updated in place)
-        table = self.known is not None or self.cw is not None or self.ctl is not None
+        table = self.known is not None or self.cw is not None or self.ctl is not None or self.cctl is not None
         kind = _EDIT_COEF_KIND[self.mode] if table else _COEF_KIND.get(self.mode)
         if self.direction > 0:  # every inversion step through the fused update, under its own table
             if table:
@@ -796,6 +813,11 @@ class _StepRunner:
             c = self.ctl
             guide = (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"]), self.B,
                      self.T, self.Fe, c["scale"], c["iters"], p(self.coef)) + clock
+        self._guide_canvas = None  # the arguments of mdm_canvas_joint_guidance (None without canvas control)
+        if self.cctl is not None:
+            c = self.cctl
+            self._guide_canvas = (x, x0, p(self.mask), p(c["offsets"]), p(c["rows"]), p(c["mean"]), p(c["std"]), p(c["targets"]),
+                                  p(c["weights"]), c["M"], self.Fe, c["scale"], c["iters"], p(self.coef)) + clock + (p(c["ws"]),)
         if self.coef is None and self.mode == "ddim":
             return ("mdm_ddim_step", (x, eps), (self.n, p(self.tab)) + clock + (self.eta,) + out), guide
         tail = clock + (self.cfg_scale,) + out
@@ -838,6 +860,11 @@ class _StepRunner:
         L.check(getattr(lib, name)(*head, self.noise.data_ptr() if use_noise else 0, *tail, s), name)
         if self._guide is not None:  # x0 and x_{t-1} moved down the joint-position loss, before the counter moves
             L.check(lib.mdm_joint_guidance(*self._guide, s), "mdm_joint_guidance")
+        if self._guide_canvas is not None:  # once per long motion over its canvas, then the owner's bits into every overlap
+            L.check(lib.mdm_canvas_joint_guidance(*self._guide_canvas, s), "mdm_canvas_joint_guidance")
+            if self.hs is not None:
+                self._handshake(self.xx, 1, False, s)
+                self._handshake(self.x0, 1, False, s)
         L.check(lib.mdm_add_i32(t_dev, self.direction, s))
 
     def _handshake(self, buf, groups, blend: bool, s):

@@ -25,6 +25,9 @@ def shard_range(B: int, rank: int, world: int) -> Tuple[int, int]:
 def shard_kwargs(kw: Dict, lo: int, hi: int) -> Dict:
     out = {}
     for k, v in kw.items():
+        if k.startswith("canvas_control_") and v is not None:
+            raise ValueError(f"{k} describes whole long motions, not batch rows: canvas joint control cannot be sharded over "
+                             "ranks")
         if isinstance(v, torch.Tensor) and v.dim() >= 1:
             out[k] = v[lo:hi]
         elif isinstance(v, (list, tuple)):

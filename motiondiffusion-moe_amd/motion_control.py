@@ -12,7 +12,11 @@ columns (4 .. 3J) enter recover_from_ric, so only they are steered; rot6d, veloc
 denoiser.  J follows from the feature width F = 12J - 1 (263 -> 22, 251 -> 21).
 
 ``root_path_targets`` and ``keyframe_targets`` are host helpers returning float32 CPU tensors; ``joint_loss_grad`` runs
-the loss and its gradient on the device (``mdm_joint_loss_grad``)."""
+the loss and its gradient on the device (``mdm_joint_loss_grad``).
+
+Over a long motion (``DDPMTrainer.generate_long(..., control_joints=, control_weights=)``) the same loss
+runs over the whole canvas: targets are (canvas_len, J, 3) per motion, frame 0 of the canvas at the origin, and
+``canvas_loss_grad`` evaluates it on rows a table names (``mdm_canvas_joint_loss_grad``)."""
 from __future__ import annotations
 
 from typing import Iterable, Sequence
@@ -50,7 +54,7 @@ def root_path_targets(T: int, waypoints, frames: Sequence[int], joints_num: int 
     """A pelvis path on the ground plane: ``waypoints`` (K, 2) XZ positions reached at ``frames`` (K increasing ints in
     [0, T)), linearly interpolated in between.  Returns (targets, weights), each (T, joints_num, 3) float32: weight 1 on
     joint 0's X and Z at frames[0] .. frames[-1], 0 everywhere else (height, the other joints and the frames outside the
-    path are left free)."""
+    path are left free).  T is any frame count: a window's, or the canvas length of a long motion."""
     wp = torch.as_tensor(np.asarray(waypoints, dtype=np.float32))
     fr = [int(f) for f in frames]
     if wp.dim() != 2 or wp.shape[1] != 2 or wp.shape[0] != len(fr) or not fr:
@@ -73,7 +77,8 @@ def root_path_targets(T: int, waypoints, frames: Sequence[int], joints_num: int 
 def keyframe_targets(joints_xyz, frames: Iterable[int], joints: Iterable[int]):
     """Positions of ``joints`` at ``frames`` taken from ``joints_xyz`` (T, J, 3), e.g. ``recover_from_ric`` of another
     motion or hand-placed points.  Returns (targets, weights), each (T, J, 3) float32: the targets are ``joints_xyz``
-    itself and the weights are 1 on every coordinate of the chosen (frame, joint) pairs, 0 elsewhere."""
+    itself and the weights are 1 on every coordinate of the chosen (frame, joint) pairs, 0 elsewhere.  T is any frame
+    count: a window's, or the canvas length of a long motion."""
     g = torch.as_tensor(joints_xyz).detach().to("cpu", torch.float32)
     if g.dim() != 3 or g.shape[2] != 3:
         raise ValueError(f"joints_xyz of shape {tuple(g.shape)} must be (T, J, 3)")
@@ -131,4 +136,43 @@ def joint_loss_grad(x0: torch.Tensor, lengths, mean, std, targets, weights):
         L.check(L.lib().mdm_joint_loss_grad(
             x.data_ptr(), ln.data_ptr(), mean_t.data_ptr(), std_t.data_ptr(), tg.data_ptr(), w.data_ptr(), B, T, F, loss.data_ptr(),
             grad.data_ptr(), L.stream_ptr()), "mdm_joint_loss_grad")
+    return loss, grad
+
+
+@torch.no_grad()
+def canvas_loss_grad(rows: torch.Tensor, motion_offsets, frame_rows, mean, std, targets, weights):
+    """Loss (M,) and gradient (total, F), dense in canvas order, of the weighted squared joint-position distance over the
+    canvases of M long motions on a GPU, through ``mdm_canvas_joint_loss_grad``.  ``rows`` (R, F), or any
+    (..., F) tensor flattened to it: normalised feature rows; canvas frame c of motion m, c in ``[motion_offsets[m],
+    motion_offsets[m + 1])``, is row ``frame_rows[c]``.  ``mean`` / ``std``: (F,) or (M, F); ``targets`` (total, J, 3) in
+    canvas order; ``weights`` broadcastable to it.  Any canvas length.  The gradient is exactly 0 in every column past 3 J.
+    Raises ValueError for offsets that do not rise from 0 to total and for rows out of range or repeated."""
+    L.require_cuda(rows)
+    dev = rows.device
+    x = rows.detach().to(torch.float32).contiguous()
+    F = x.shape[-1]
+    x = x.reshape(-1, F)
+    J = joints_for_feats(F)
+    off = torch.as_tensor(motion_offsets).flatten().to(torch.int64).cpu()
+    fr = torch.as_tensor(frame_rows).flatten().to(torch.int64).cpu()
+    M, total = off.numel() - 1, fr.numel()
+    if M < 0 or int(off[0]) != 0 or int(off[-1]) != total or bool((off[1:] < off[:-1]).any()):
+        raise ValueError(f"motion_offsets must rise from 0 to the number of frame rows {total}")
+    if total and (int(fr.min()) < 0 or int(fr.max()) >= x.shape[0] or torch.unique(fr).numel() != total):
+        raise ValueError(f"frame_rows must be distinct rows in [0, {x.shape[0]})")
+    tg = torch.as_tensor(targets).to(dev, torch.float32)
+    if tuple(tg.shape) != (total, J, 3):
+        raise ValueError(f"targets of shape {tuple(tg.shape)} must be {(total, J, 3)}")
+    w = torch.broadcast_to(torch.as_tensor(weights).to(dev, torch.float32), (total, J, 3)).contiguous()
+    tg = tg.contiguous()
+    mean_t = _rows(mean, M, F, "mean").to(dev).contiguous()
+    std_t = _rows(std, M, F, "std").to(dev).contiguous()
+    off_d, fr_d = off.to(dev, torch.int32), fr.to(dev, torch.int32)
+    loss = torch.zeros(M, device=dev)
+    grad = torch.zeros((total, F), device=dev)
+    ws = torch.empty(max(int(L.lib().mdm_canvas_control_workspace_floats(total, F)), 1), device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().mdm_canvas_joint_loss_grad(
+            x.data_ptr(), off_d.data_ptr(), fr_d.data_ptr(), mean_t.data_ptr(), std_t.data_ptr(), tg.data_ptr(), w.data_ptr(), M, F,
+            loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), L.stream_ptr()), "mdm_canvas_joint_loss_grad")
     return loss, grad

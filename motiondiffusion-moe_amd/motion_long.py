@@ -11,7 +11,8 @@ the two eps rows back into both (``weights``: a linear crossfade, the right wind
 frame j, or ``"uniform"`` halves), and copies x_T and the step noise from the left ("owner") window into the right one.
 The overlap frames of neighbouring windows then stay bit for bit equal on every step, and the canvas is the windows' valid
 frames.  ``script_plans``, ``canvas_conditioning``, ``plan_batches``, ``batch_tables`` and ``gather_canvases`` are the host
-half of ``DDPMTrainer.generate_long``.  Host logic only: runs without a GPU.
+half of ``DDPMTrainer.generate_long``; ``canvas_frame_rows`` and ``batch_control_tables`` name the row that owns each canvas
+frame for joint control over the whole canvas.  Host logic only: runs without a GPU.
 """
 from __future__ import annotations
 
@@ -144,6 +145,86 @@ def batch_tables(plans, idx, T: int, overlap: int, blend: str = "linear") -> Dic
         tabs.append(handshake_tables(plans[i][2], plans[i][1], T, overlap, blend, first_row=row))
         row += len(plans[i][1])
     return {"handshake_" + k: torch.from_numpy(v) for k, v in merge_tables(tabs).items()}
+
+
+def canvas_frame_rows(starts, lengths, T: int, first_row: int = 0) -> np.ndarray:
+    """For every canvas frame of one long motion whose windows are batch rows ``first_row, first_row + 1, ...`` padded to T
+    frames, the row (``window_row * T + frame``) of its owner: the first (left) window that covers it, as in
+    ``handshake_tables``' ``owner_rows`` and ``windows_to_canvas``.  int32 (canvas_len,): every canvas frame exactly once."""
+    starts, lengths, C = _span(starts, lengths)
+    if _int(T, "T") < max(lengths):
+        raise ValueError(f"T = {T} is shorter than the longest window ({max(lengths)} frames)")
+    rows = np.empty(C, dtype=np.int32)
+    for i in reversed(range(len(starts))):  # a left window overwrites its right neighbour's share of an overlap
+        rows[starts[i]:starts[i] + lengths[i]] = (int(first_row) + i) * int(T) + np.arange(lengths[i], dtype=np.int32)
+    return rows
+
+
+def batch_control_tables(plans, idx, T: int, joints, weights) -> Dict[str, torch.Tensor]:
+    """The ``canvas_control_*`` table kwargs of one batch, next to ``batch_tables``: for the motions ``idx``,
+    whose windows are consecutive batch rows in that order padded to T frames, ``canvas_control_offsets`` (len(idx) + 1),
+    ``canvas_control_rows`` (``canvas_frame_rows`` of each, concatenated) and the canvas-order ``canvas_control_joints`` /
+    ``canvas_control_weights`` (sum of canvas lengths, J, 3) from ``joints[i]`` / ``weights[i]`` (C_i, J, 3)."""
+    offsets, rows, row = [0], [], 0
+    for i in idx:
+        rows.append(canvas_frame_rows(plans[i][2], plans[i][1], T, first_row=row))
+        offsets.append(offsets[-1] + plans[i][3])
+        row += len(plans[i][1])
+    return {"canvas_control_offsets": torch.tensor(offsets, dtype=torch.int32),
+            "canvas_control_rows": torch.from_numpy(np.concatenate(rows)),
+            "canvas_control_joints": torch.cat([joints[i] for i in idx]).contiguous(),
+            "canvas_control_weights": torch.cat([weights[i] for i in idx]).contiguous()}
+
+
+def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, control_scale=None, control_iters=None,
+                   mean=None, std=None, device=None):
+    """The joint-control inputs of ``DDPMTrainer.generate_long`` (described there), checked once for the call:
+    one (C_i, J, 3) target array per motion of ``plans`` in canvas frames and weights broadcastable to it (aligned on the
+    frame dim), with the dataset's ``mean`` / ``std``.  Returns ``tables(idx, T)``: the ``canvas_control_*`` model kwargs
+    (``batch_control_tables``, one mean / std row per motion, ``control_scale`` / ``control_iters`` where given) of the batch
+    of motions ``idx`` at T frames, on ``device``; {} without control.  Raises ValueError for targets without weights or the
+    reverse, a scale or iteration count without them, missing mean / std, not one entry per motion, and canvas shapes."""
+    if control_joints is None and control_weights is None:
+        if control_scale is not None or control_iters is not None:
+            raise ValueError("control_scale / control_iters given without control_joints / control_weights")
+        return lambda idx, T: {}
+    N = len(plans)
+    if control_joints is None or control_weights is None:
+        raise ValueError("control_joints and control_weights go together: give both or neither")
+    if mean is None or std is None:
+        raise ValueError("joint control needs the dataset's mean and std (the targets are de-normalised positions)")
+    for name, v in (("control_joints", control_joints), ("control_weights", control_weights)):
+        if torch.is_tensor(v) or isinstance(v, np.ndarray) or len(v) != N or any(x is None for x in v):
+            raise ValueError(f"{name} must hold one entry per motion ({N}), each over its canvas: for every motion or for none")
+    from .motion_control import joints_for_feats
+    J = joints_for_feats(dim_pose)
+    joints, weights = [], []
+    for i, (g, w) in enumerate(zip(control_joints, control_weights)):
+        C = plans[i][3]
+        g = torch.as_tensor(g).detach().to("cpu", torch.float32)
+        if tuple(g.shape) != (C, J, 3):
+            raise ValueError(f"control_joints of motion {i} has shape {tuple(g.shape)}, its canvas {(C, J, 3)}")
+        w = expand_to(torch.as_tensor(w).detach().to("cpu", torch.float32), 0, (C, J, 3), "control_weights",
+                      "has more dims than (canvas_len, J, 3)",
+                      f"{{name}} of motion {i} has shape {{shape}}, not broadcastable to its canvas {{target}} (aligned on the "
+                      "frame dim: (C,), (C, J) or (C, J, 3))")
+        joints.append(g)
+        weights.append(w)
+    ms = []
+    for name, v in (("mean", mean), ("std", std)):
+        v = torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v)).detach().to("cpu", torch.float32).flatten()
+        if v.numel() != dim_pose:
+            raise ValueError(f"{name} must have {dim_pose} entries")
+        ms.append(v)
+
+    def tables(idx, T):
+        kw = batch_control_tables(plans, idx, T, joints, weights)
+        kw.update(canvas_control_mean=ms[0].expand(len(idx), -1), canvas_control_std=ms[1].expand(len(idx), -1))
+        kw = {k: v.to(device) for k, v in kw.items()}
+        kw.update({k: v for k, v in (("control_scale", control_scale), ("control_iters", control_iters)) if v is not None})
+        return kw
+
+    return tables
 
 
 def gather_canvases(values, plans, idx, T: int, dim_pose: int, what: str) -> torch.Tensor:

@@ -308,7 +308,8 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
-                      sample_steps=None, eta=0.0, progress=False, **conditioning):
+                      sample_steps=None, eta=0.0, progress=False, control_joints=None, control_weights=None, control_scale=None,
+                      control_iters=None, **conditioning):
         """Long motions: ``scripts`` is a list of long motions, each a list of ``(caption, length)``
         segments of at most ``num_frames`` frames; neighbouring segments share ``overlap`` canvas frames, whose eps is
         blended on every step (``blend`` "linear" crossfade or "uniform") while x_T and the step noise come from the left
@@ -323,12 +324,20 @@ class DDPMTrainer(object):
         needs its mask.  ``edit_bvh`` / ``bvh_options``: one BVH file per motion in place of ``edit_joints``, as in
         ``generate``.  ``init_motion`` with ``strength``: one (canvas_len, dim_pose) motion per long motion to start from, as
         in ``generate``: each window takes its frames of the canvas, and an overlap starts from its owner
-        window's noised values.  These per-motion inputs are ``**conditioning``, checked by ``motion_long.canvas_conditioning``."""
+        window's noised values.  ``control_joints`` / ``control_weights`` (with ``mean`` / ``std``; ``control_scale`` /
+        ``control_iters``): one (canvas_len, J, 3) array of target joint positions per motion, in canvas frames, and weights
+        broadcastable to it, as in ``generate`` but over the whole canvas (targets from
+        ``motion_control.root_path_targets`` / ``keyframe_targets`` at T = canvas_len): a target late in the canvas moves the
+        root path of every window before it.  It combines with every sampler and with the edit and start inputs
+        (``motion_long.canvas_control`` checks it).  The other per-motion inputs are ``**conditioning``, checked by
+        ``motion_long.canvas_conditioning``."""
         m = self._model()
         self.eval_mode()
         plans = ML.script_plans(scripts, overlap, m.num_frames)
         device = getattr(self, "device", None)  # none on a trainer made without __init__ (host tests of the checks)
         window_rows = ML.canvas_conditioning(plans, dim_pose, device=device, **conditioning)
+        control = ML.canvas_control(plans, dim_pose, control_joints, control_weights, control_scale, control_iters,
+                                    conditioning.get("mean"), conditioning.get("std"), device)
         out, first = [None] * len(plans), 0
         for idx in ML.plan_batches(plans, batch_size):
             caps = [c for i in idx for c in plans[i][0]]
@@ -338,6 +347,7 @@ class DDPMTrainer(object):
             rows = window_rows(idx, T)  # the per-motion canvases given, as window rows
             if "edit_motion" in rows:
                 kw.update(inpaint_motion=rows["edit_motion"], inpaint_mask=rows["edit_mask"])
+            kw.update(control(idx, T))
             cond = Conditioning(caps, dim_pose, init_motion=rows.get("init_motion"), strength=conditioning.get("strength"))
             res = self._sample_rows(cond, slice(None), torch.tensor(lens), T, sampler, sample_steps, eta, extra=kw,
                                     progress=progress, noise=rows.get("noise"), seed=seed, sample_offset=first)
@@ -354,7 +364,7 @@ class DDPMTrainer(object):
         longest = max(p[3] for p in ML.script_plans(scripts, kw.get("overlap", 20), self._model().num_frames))
         if longest > most:
             raise ValueError(f"a canvas of {longest} frames: {what} takes at most {most} frames")
-        if kw.get("edit_joints") is not None or kw.get("edit_bvh") is not None:
+        if kw.get("edit_joints") is not None or kw.get("edit_bvh") is not None or kw.get("control_joints") is not None:
             kw = dict(kw, mean=mean, std=std)
         return self.generate_long(scripts, dim_pose, **kw)
 

@@ -32,6 +32,12 @@ neighbours sharing H frames (``generate_long``, eps blended and noise copied on 
 the same B windows, DDIM-50 and DPM-Solver++(2M)-20, alternating, as for ``--edit``.
 
     timeout -k 10 900 python tools/sample_time.py --long 20 --reps 5 --precisions 1
+
+``--long-control I`` (with ``--long H``, default 20) measures joint control over the canvases of those long motions: the same
+``generate_long`` without and with ``control_joints`` / ``control_weights`` over every canvas frame (every joint's height,
+``control_iters`` = I; I may be a list), DDIM-50 and DPM-Solver++(2M)-20, alternating, as for ``--edit``.
+
+    timeout -k 10 900 python tools/sample_time.py --long-control 1,5 --reps 5 --precisions 1
 """
 import argparse
 import importlib
@@ -59,6 +65,8 @@ def main():
     ap.add_argument("--control", default=None, help="I[,I...]: time joint control with I iterations against plain")
     ap.add_argument("--long", type=int, default=None, help="H: time long motions (4 windows each, H shared frames) "
                     "against plain generation of the same windows")
+    ap.add_argument("--long-control", default=None, help="I[,I...]: time canvas joint control with I iterations against "
+                    "plain long motions (overlap --long, default 20)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_time.py measures the GPU sampler: no GPU found")
@@ -78,6 +86,8 @@ def main():
         return compose_main(a, tr, m, caps, length, B, T)
     if a.control:
         return control_main(a, tr, m, caps, length, B, T)
+    if a.long_control:
+        return long_control_main(a, tr, m, caps, B, T)
     if a.long is not None:
         return long_main(a, tr, m, caps, B, T)
     rows = []
@@ -305,6 +315,58 @@ def long_main(a, tr, m, caps, B, T):
         spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
         print(f"{r['precision']:>9} {r['sampler']:>22} {r['plain_ms']:>9.1f} {r['long_ms']:>9.1f} {spread:>22} "
               f"{r['diff_us_per_step']:>8.1f} {r['diff_share']:>7.2%}")
+
+
+def long_control_main(a, tr, m, caps, B, T):
+    if B % 4:
+        raise SystemExit("--long-control needs a batch of whole 4-window motions")
+    h = 20 if a.long is None else a.long
+    C = 4 * T - 3 * h
+    scripts = [[(caps[4 * i + k], T) for k in range(4)] for i in range(B // 4)]
+    # every joint's height on every canvas frame: as --control, over the canvas
+    tg, w = [torch.zeros(C, 22, 3) for _ in scripts], [torch.zeros(C, 22, 3) for _ in scripts]
+    for g_, w_ in zip(tg, w):
+        g_[..., 1], w_[..., 1] = 1.0, 1.0
+    mean, std = torch.zeros(263), torch.ones(263)
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for iters in [int(k) for k in a.long_control.split(",")]:
+            for sampler, steps, n in (("ddim", 50, 50), ("dpmpp2m", 20, 20)):
+                def gen(ctl):
+                    extra = dict(control_joints=tg, control_weights=w, control_scale=0.05, control_iters=iters,
+                                 mean=mean, std=std) if ctl else {}
+                    return tr.generate_long(scripts, 263, overlap=h, batch_size=B, seed=0, sampler=sampler,
+                                            sample_steps=steps, **extra)
+                for ctl in (False, True):  # warm-up
+                    assert all(torch.isfinite(o).all() for o in gen(ctl))
+                ts = {False: [], True: []}
+                for _ in range(a.reps):
+                    for ctl in (False, True):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        gen(ctl)
+                        torch.cuda.synchronize()
+                        ts[ctl].append((time.perf_counter() - t0) * 1e3)
+                med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+                diff = sorted(c - p for p, c in zip(ts[False], ts[True]))
+                name = {"ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+                line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, overlap=h, motions=B // 4, canvas_frames=C,
+                            control_iters=iters, plain_ms=round(med[False], 2), control_ms=round(med[True], 2),
+                            diff_ms_median=round(diff[len(diff) // 2], 2), diff_ms_min=round(diff[0], 2),
+                            diff_ms_max=round(diff[-1], 2), diff_us_per_step=round(diff[len(diff) // 2] / n * 1e3, 1),
+                            plain_reps_ms=[round(t, 2) for t in ts[False]], control_reps_ms=[round(t, 2) for t in ts[True]])
+                rows.append(line)
+                print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}, guided (cfg 7.5), {B // 4} long motions of 4 windows, overlap {h} ({C}-frame "
+          f"canvases), joint control over the canvas (every joint's height); {torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'iters':>5} {'sampler':>22} {'plain ms':>9} {'control ms':>11} {'diff ms (min..max)':>22} "
+          f"{'us/step':>8}")
+    for r in rows:
+        spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
+        print(f"{r['precision']:>9} {r['control_iters']:>5} {r['sampler']:>22} {r['plain_ms']:>9.1f} "
+              f"{r['control_ms']:>11.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
 
 
 if __name__ == "__main__":
