@@ -637,6 +637,46 @@ int mdm_canvas_joint_guidance(float* x, float* x0, const float* mask, const int3
                               int32_t F, float scale, int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev,
                               int32_t t_imm, float* workspace, void* stream);
 
+/* Scene constraints (csrc/scene_sdf.h inside both control kernels): keep joints out of obstacles and above
+ * the floor.  A scene is K <= MDM_SCENE_MAX_PRIMS primitives per sample (or per long motion), fixed in the frame of
+ * recover_from_ric (the canvas frame of a long motion): `scene` dense fp32 (B or M, K, MDM_SCENE_REC), a record being
+ *   kind, sigma, weight a >= 0, margin m, and eight parameters:
+ *   MDM_SCENE_SPHERE      centre[3], radius                    d = |p - c| - r
+ *   MDM_SCENE_CAPSULE     end a[3], end b[3], radius           d = distance to the segment - r  (a == b: a sphere)
+ *   MDM_SCENE_BOX         centre[3], half extents[3], cos yaw, sin yaw (yaw about Y)
+ *                                                              d = |max(q, 0)| + min(max(q_x, q_y, q_z), 0), q = |local p| - h
+ *   MDM_SCENE_HALF_SPACE  unit normal[3], offset               d = n . p - o
+ *   MDM_SCENE_PAD (0) and any other kind: skipped.
+ * sigma = +1 keeps joints out, -1 keeps them in.  `joint_params` dense fp32 (B or M, J, 2): radius r_j >= 0 and weight
+ * u_j >= 0 of every joint (u_j == 0 exempts it).  The loss of the existing calls gains
+ *   L_scene = sum_{t < length, j} u_j sum_k a_k max(0, m_k + r_j - sigma_k d_k(P[t, j]))^2
+ * and everything else about them holds: the gradient, the guidance iterations, the update of x, what is left untouched.
+ * Where the gradient of d is undefined (the exact centre or axis) it is taken as 0.  targets and weights may both be NULL
+ * (no target term).  With K == 0 and targets the calls are the existing ones, launch for launch.
+ * The window calls keep the records in LDS: T <= mdm_joint_scene_max_frames(F, K) (202 at F = 263 and 208 at 251 with K = 16;
+ * 0 for a bad F or K).  MDM_ERR_ARG: K outside [0, MDM_SCENE_MAX_PRIMS], a null scene with K > 0, null joint_params, one of
+ * targets / weights without the other, T over the limit, and everything the existing calls refuse.  The values are the
+ * caller's (finite, a >= 0, radii and half extents > 0): not checked here. */
+enum { MDM_SCENE_MAX_PRIMS = 16, MDM_SCENE_REC = 12 };
+enum { MDM_SCENE_PAD = 0, MDM_SCENE_SPHERE = 1, MDM_SCENE_CAPSULE = 2, MDM_SCENE_BOX = 3, MDM_SCENE_HALF_SPACE = 4 };
+int mdm_joint_scene_max_frames(int32_t feats, int32_t prims);
+int mdm_joint_scene_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
+                              const float* weights, const float* scene, int32_t K, const float* joint_params, int32_t B,
+                              int32_t T, int32_t F, float* loss_out, float* grad_out, void* stream);
+int mdm_joint_scene_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
+                             const float* targets, const float* weights, const float* scene, int32_t K,
+                             const float* joint_params, int32_t B, int32_t T, int32_t F, float scale, int32_t iters,
+                             const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, void* stream);
+int mdm_canvas_scene_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
+                               const float* std, const float* targets, const float* weights, const float* scene, int32_t K,
+                               const float* joint_params, int32_t M, int32_t F, float* loss_out, float* grad_out,
+                               float* workspace, void* stream);
+int mdm_canvas_scene_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
+                              const float* mean, const float* std, const float* targets, const float* weights,
+                              const float* scene, int32_t K, const float* joint_params, int32_t M, int32_t F, float scale,
+                              int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
+                              float* workspace, void* stream);
+
 /* ---- long-motion handshakes ---------------------------------------------------------------------
  * In place over the shared canvas frames only.  For every group g < groups, shared frame c < nshared and feature j < F:
  *   v = sum over entries e in [offsets[c], offsets[c+1]) of weights[e] * x[g*group_stride + rows[e]*F + j]

@@ -134,7 +134,8 @@ BLOCK_DUAL, BLOCK_CROSS, BLOCK_MOE, BLOCK_SDCROSS, BLOCK_LAYER = 0, 1, 2, 3, 4
 NOISE_STREAM_XT = 0x7FFFFFFF  # MDM_NOISE_STREAM_XT
 COMPOSE_MAX_K = 8  # MDM_COMPOSE_MAX_K: prompts per sample of mdm_composed_update
 CONTROL_MAX_ITERS = 32  # MDM_CONTROL_MAX_ITERS: guidance iterations per step of mdm_joint_guidance
-TAB_ROWS = 7  # sqrt_recip_acp, sqrt_recipm1_acp, coef1, coef2, post_logvar_clipped, acp, acp_prev
+SCENE_MAX_PRIMS, SCENE_REC = 16, 12  # MDM_SCENE_MAX_PRIMS, MDM_SCENE_REC: primitives per scene, floats per record
+TAB_ROWS = 7 # sqrt_recip_acp, sqrt_recipm1_acp, coef1, coef2, post_logvar_clipped, acp, acp_prev
 
 
 _P, _I32, _I64, _U64, _F32, _F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
@@ -199,6 +200,13 @@ PROTOTYPES = {
     "mdm_canvas_control_workspace_floats": (_I64, [_I32, _I32]),
     "mdm_canvas_joint_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "mdm_canvas_joint_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _F32, _I32, _P, _I32, _P, _I32, _P, _P]),
+    "mdm_joint_scene_max_frames": (_I32, [_I32, _I32]),
+    "mdm_joint_scene_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "mdm_joint_scene_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _F32, _I32, _P, _I32, _P,
+                                        _I32, _P]),
+    "mdm_canvas_scene_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),
+    "mdm_canvas_scene_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _F32, _I32, _P, _I32, _P,
+                                         _I32, _P, _P]),
     "mdm_handshake_blend": (_I32, [_P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
     "mdm_moe_train_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32]),
     "mdm_moe_ffn_train_forward": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _F32, _U64, _P, _P, _P, _P,

@@ -122,39 +122,70 @@ def check_control_kwargs(kw, shape):
     slices them; the weights are aligned on that dim: (B,) per sample, (B, T) per frame, (B, T, J) per joint.
     Raises ValueError when only some of the four tensors are given (or a scale / iters without them), for an F not of the
     form 12 J - 1, a T over the kernels' LDS limit, shape or broadcast errors, non-finite targets, weights, mean or std,
-    negative weights, a zero std, a non-finite scale or iters outside [1, MDM_CONTROL_MAX_ITERS].  Host logic."""
+    negative weights, a zero std, a non-finite scale or iters outside [1, MDM_CONTROL_MAX_ITERS].
+    Scene constraints: ``control_scene`` (B, K, 12) primitive records (``motion_scene.pack_scene``) and
+    ``control_joint_params`` (B, J, 2), the joints' radius and weight (default: 0 and 1), come back as ``scene`` /
+    ``joint_params`` (absent without a scene).  A scene needs ``control_mean`` / ``control_std`` but no targets: ``targets``
+    and ``weights`` are then None.  Raises ValueError for joint parameters without a scene, records
+    ``motion_scene.check_records`` refuses, joint parameters of another shape, negative or not finite, and a T over the
+    limit of a scene of K primitives.  Host logic."""
     from .motion_control import joints_for_feats, max_frames
     names = ("control_joints", "control_weights", "control_mean", "control_std")
     g, w, mean, std = (kw.get(k) for k in names)
+    scene, jp = kw.get("control_scene"), kw.get("control_joint_params")
     given = [k for k, v in zip(names, (g, w, mean, std)) if v is not None]
     extra = [k for k in ("control_scale", "control_iters") if kw.get(k) is not None]
-    if not given:
-        if extra and not any(kw.get(k) is not None for k in CANVAS_CONTROL_KEYS):  # they may belong to canvas control
+    if jp is not None and scene is None:
+        raise ValueError("control_joint_params given without control_scene")
+    if not given and scene is None:
+        if extra and not any(kw.get(k) is not None for k in CANVAS_CONTROL_KEYS + CANVAS_SCENE_KEYS):  # canvas control's
             raise ValueError(f"{' / '.join(extra)} given without control_joints / control_weights / control_mean / control_std")
         return None
-    if len(given) != 4:
-        raise ValueError(f"joint control needs all of {', '.join(names)}; missing "
-                         f"{', '.join(k for k in names if k not in given)}")
+    need = names[2:] if scene is not None and g is None and w is None else names
+    if any(k not in given for k in need):
+        raise ValueError(f"joint control needs all of {', '.join(need)}; missing "
+                         f"{', '.join(k for k in need if k not in given)}")
     B, T, F_ = (int(v) for v in shape)
     J = joints_for_feats(F_)
-    if T > max_frames(F_):
-        raise ValueError(f"T = {T}: joint control takes at most {max_frames(F_)} frames at F = {F_}")
-    g, w, mean, std = (torch.as_tensor(v) for v in (g, w, mean, std))
+    out = {}
+    limit = max_frames(F_)
+    if scene is not None:
+        from .motion_scene import check_records, max_frames as scene_max_frames
+        scene = check_records(scene, "control_scene")
+        if scene.dim() != 3 or scene.shape[0] != B:
+            raise ValueError(f"control_scene has shape {tuple(scene.shape)}, expected ({B}, K, {L.SCENE_REC})")
+        limit = scene_max_frames(F_, int(scene.shape[1]))
+        if jp is None:
+            jp = torch.tensor([0.0, 1.0]).expand(B, J, 2)
+        jp = torch.as_tensor(jp)
+        if tuple(jp.shape) != (B, J, 2) or not jp.is_floating_point():
+            raise ValueError(f"control_joint_params of shape {tuple(jp.shape)} must be floating point {(B, J, 2)}")
+        if not bool(torch.isfinite(jp).all()) or bool((jp < 0).any()):
+            raise ValueError("control_joint_params (joint radius, joint weight) must be finite and >= 0")
+        out = {"scene": scene, "joint_params": jp}
+    if T > limit:
+        raise ValueError(f"T = {T}: joint control takes at most {limit} frames at F = {F_}"
+                         + (f" with {scene.shape[1]} primitives" if scene is not None else ""))
+    mean, std = torch.as_tensor(mean), torch.as_tensor(std)
+    if g is not None:
+        g, w = torch.as_tensor(g), torch.as_tensor(w)
     for name, v in zip(names, (g, w, mean, std)):
-        if not v.is_floating_point():
+        if v is not None and not v.is_floating_point():
             raise ValueError(f"{name} must be floating point")
-    if tuple(g.shape) != (B, T, J, 3):
-        raise ValueError(f"control_joints has shape {tuple(g.shape)}, expected {(B, T, J, 3)}")
-    w = expand_to(w, 1, (B, T, J, 3), "control_weights", f"must lead with the batch size {B}")
+    if g is not None:
+        if tuple(g.shape) != (B, T, J, 3):
+            raise ValueError(f"control_joints has shape {tuple(g.shape)}, expected {(B, T, J, 3)}")
+        w = expand_to(w, 1, (B, T, J, 3), "control_weights", f"must lead with the batch size {B}")
     for name, v in (("control_mean", mean), ("control_std", std)):
         if tuple(v.shape) != (B, F_):
             raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(B, F_)} (one row per sample)")
-    if not bool(torch.isfinite(g).all()):
-        raise ValueError("control_joints has non-finite values")
-    if not bool(torch.isfinite(w).all()):
-        raise ValueError("control_weights has non-finite values")
-    if not bool((w >= 0).all()):
-        raise ValueError("control_weights must be >= 0")
+    if g is not None:
+        if not bool(torch.isfinite(g).all()):
+            raise ValueError("control_joints has non-finite values")
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("control_weights has non-finite values")
+        if not bool((w >= 0).all()):
+            raise ValueError("control_weights must be >= 0")
     if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all())):
         raise ValueError("control_mean / control_std have non-finite values")
     if bool((std == 0).any()):
@@ -167,9 +198,10 @@ def check_control_kwargs(kw, shape):
     iters = 1 if iters is None else iters
     if isinstance(iters, bool) or int(iters) != iters or not 1 <= int(iters) <= L.CONTROL_MAX_ITERS:
         raise ValueError(f"control_iters must be an integer in [1, {L.CONTROL_MAX_ITERS}]")
-    return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters)}
+    return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters), **out}
 
 
+CANVAS_SCENE_KEYS = ("canvas_control_scene", "canvas_control_joint_params")
 CANVAS_CONTROL_KEYS = ("canvas_control_offsets", "canvas_control_rows", "canvas_control_joints", "canvas_control_weights",
                        "canvas_control_mean", "canvas_control_std")
 
@@ -185,17 +217,28 @@ def check_canvas_control_kwargs(kw, shape):
     offsets that do not rise from 0 to the row count, rows outside [0, B T), repeated, at or past their window's ``length`` or
     naming a shared frame's copy instead of its owner, shape or broadcast errors, non-finite values, negative weights, a zero
     std, a non-finite scale, iters outside [1, MDM_CONTROL_MAX_ITERS], and together with per-window control or composed
-    prompts.  Host logic."""
+    prompts.
+    Scene constraints: ``canvas_control_scene`` (M, K, 12) records in the canvas frame and
+    ``canvas_control_joint_params`` (M, J, 2) come back as ``scene`` / ``joint_params`` (absent without a scene), checked as
+    ``check_control_kwargs`` checks its own; with a scene ``canvas_control_joints`` / ``canvas_control_weights`` may both be
+    left out (``targets`` / ``weights`` None).  Host logic."""
     from .motion_control import joints_for_feats
     names = CANVAS_CONTROL_KEYS
     vals = [kw.get(k) for k in names]
+    scene, jp = (kw.get(k) for k in CANVAS_SCENE_KEYS)
     given = [k for k, v in zip(names, vals) if v is not None]
-    if not given:
+    if jp is not None and scene is None:
+        raise ValueError("canvas_control_joint_params given without canvas_control_scene")
+    if not given and scene is None:
         return None
-    if len(given) != len(names):
-        raise ValueError(f"canvas joint control needs all of {', '.join(names)}; missing "
-                         f"{', '.join(k for k in names if k not in given)}")
-    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std")):
+    aim = scene is None or vals[2] is not None or vals[3] is not None
+    need = names if aim else names[:2] + names[4:]
+    if any(k not in given for k in need):
+        raise ValueError(f"canvas joint control needs all of {', '.join(need)}; missing "
+                         f"{', '.join(k for k in need if k not in given)}")
+    if not aim:
+        vals[2] = vals[3] = torch.zeros(0)  # placeholders through the common conversions below
+    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std", "control_scene")):
         raise ValueError("canvas_control_* and the per-window control_joints / control_weights are exclusive")
     if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
         raise ValueError("canvas joint control does not combine with composed prompts")
@@ -238,9 +281,22 @@ def check_canvas_control_kwargs(kw, shape):
         if bool(torch.isin(rows, own[~first]).any()):
             raise ValueError("canvas_control_rows names a copy of a shared frame: every canvas frame is steered in its owner "
                              "(left) window's row, and the copy takes the owner's values")
-    if tuple(g.shape) != (total, J, 3):
-        raise ValueError(f"canvas_control_joints has shape {tuple(g.shape)}, expected {(total, J, 3)}")
-    w = expand_to(w, 1, (total, J, 3), "canvas_control_weights", f"must lead with the row count {total}")
+    out = {}
+    if scene is not None:
+        from .motion_scene import check_records
+        scene = check_records(scene, "canvas_control_scene").cpu()
+        if scene.dim() != 3 or scene.shape[0] != M:
+            raise ValueError(f"canvas_control_scene has shape {tuple(scene.shape)}, expected ({M}, K, {L.SCENE_REC})")
+        jp = torch.tensor([0.0, 1.0]).expand(M, J, 2) if jp is None else torch.as_tensor(jp).detach().cpu()
+        if tuple(jp.shape) != (M, J, 2) or not jp.is_floating_point():
+            raise ValueError(f"canvas_control_joint_params of shape {tuple(jp.shape)} must be floating point {(M, J, 2)}")
+        if not bool(torch.isfinite(jp).all()) or bool((jp < 0).any()):
+            raise ValueError("canvas_control_joint_params (joint radius, joint weight) must be finite and >= 0")
+        out = {"scene": scene, "joint_params": jp}
+    if aim:
+        if tuple(g.shape) != (total, J, 3):
+            raise ValueError(f"canvas_control_joints has shape {tuple(g.shape)}, expected {(total, J, 3)}")
+        w = expand_to(w, 1, (total, J, 3), "canvas_control_weights", f"must lead with the row count {total}")
     for name, v in (("canvas_control_mean", mean), ("canvas_control_std", std)):
         if tuple(v.shape) != (M, F_):
             raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(M, F_)} (one row per motion)")
@@ -262,8 +318,9 @@ def check_canvas_control_kwargs(kw, shape):
     iters = 1 if iters is None else iters
     if isinstance(iters, bool) or int(iters) != iters or not 1 <= int(iters) <= L.CONTROL_MAX_ITERS:
         raise ValueError(f"control_iters must be an integer in [1, {L.CONTROL_MAX_ITERS}]")
-    return {"offsets": off.to(torch.int32), "rows": rows.to(torch.int32), "targets": g, "weights": w, "mean": mean, "std": std,
-            "M": M, "total": total, "scale": scale, "iters": int(iters)}
+    return {"offsets": off.to(torch.int32), "rows": rows.to(torch.int32), "targets": g if aim else None,
+            "weights": w if aim else None, "mean": mean, "std": std, "M": M, "total": total, "scale": scale, "iters": int(iters),
+            **out}
 
 
 def check_handshake_kwargs(kw, shape):
@@ -286,7 +343,7 @@ def check_handshake_kwargs(kw, shape):
                          f"{', '.join(k for k in names if k not in given)}")
     if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
         raise NotImplementedError("composed prompts over a long motion are not supported yet")
-    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std")):
+    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std", "control_scene")):
         raise NotImplementedError("per-window joint control over a long motion is not supported: targets need canvas "
                                   "coordinates; give them as canvas_control_* (generate_long(control_joints=))")
     B, T, _ = (int(v) for v in shape)
@@ -462,6 +519,10 @@ class Conditioning:
     ``control_joints`` (N, T_max, J, 3) target joint positions and ``control_weights`` (N, ...) broadcastable to them, with the
     dataset's ``mean`` / ``std`` (dim_pose,), kept as float32: every step's x0 is moved ``control_iters`` times down the gradient
     of the weighted squared distance, scaled by ``control_scale`` (units in ``motion_control``; ``control``).
+    ``scene``: obstacles the joints keep out of, a list of ``motion_scene`` primitives shared by all samples or
+    one list per sample, with ``scene_joint_radius`` (J,) and ``scene_joint_weights`` (J,) (default 0 and 1); it needs ``mean`` /
+    ``std``, acts through the same guidance as ``control_joints`` (``control_scale`` / ``control_iters``) and may come without
+    targets (``scene_records`` / ``scene_joint_params``).
     ``edit_joints``: N joint clips (n_i, J, 3) in place of ``edit_motion`` (needs ``mean`` / ``std``), turned into feature rows
     once per call (``edit_rows_from_joints``: ``motion_features.joints_to_motion``) and zero-padded to the mask's
     frames; a clip of n frames gives n - 1 rows, so the mask may keep frames up to n - 2.
@@ -482,7 +543,8 @@ class Conditioning:
     def __init__(self, captions, dim_pose, edit_motion=None, edit_mask=None, prompt_weights=None, control_joints=None,
                  control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,
                  device=None, to_motion=None, edit_bvh=None, bvh_options=None, init_motion=None, init_joints=None,
-                 init_bvh=None, strength=None, latents=None, latent_step=None):
+                 init_bvh=None, strength=None, latents=None, latent_step=None, scene=None, scene_joint_radius=None,
+                 scene_joint_weights=None):
         self.captions, self.dim_pose = captions, dim_pose
         self.init, self.strength, self.latents, self.latent_step = None, None, None, None
         if init_motion is not None or init_joints is not None or init_bvh is not None:
@@ -528,7 +590,15 @@ class Conditioning:
             self.edit = (k, expand_to(edit_mask, None, k.shape, "edit_mask"))
             if rows is not None:
                 check_joint_edit_mask(self.edit[1], rows)
-        self.control = self._control(control_joints, control_weights, mean, std, dim_pose)
+        self.control = self._control(control_joints, control_weights, mean, std, dim_pose, scene is not None)
+        self.scene_records = self.scene_joint_params = None
+        if scene is not None:
+            from .motion_control import joints_for_feats
+            from .motion_scene import batch_scene, joint_params
+            self.scene_records = batch_scene(scene, len(captions))
+            self.scene_joint_params = joint_params(joints_for_feats(dim_pose), scene_joint_radius, scene_joint_weights)
+        elif scene_joint_radius is not None or scene_joint_weights is not None:
+            raise ValueError("scene_joint_radius / scene_joint_weights go with scene")
         self.control_scale, self.control_iters = control_scale, control_iters
 
     @staticmethod
@@ -549,20 +619,23 @@ class Conditioning:
         return w
 
     @staticmethod
-    def _control(control_joints, control_weights, mean, std, dim_pose):
-        if control_joints is None and control_weights is None:
+    def _control(control_joints, control_weights, mean, std, dim_pose, scene=False):
+        if control_joints is None and control_weights is None and not scene:
             return None
-        if control_joints is None or control_weights is None:
+        if (control_joints is None) != (control_weights is None):
             raise ValueError("control_joints and control_weights go together: give both or neither")
         if mean is None or std is None:
-            raise ValueError("joint control needs the dataset's mean and std (the targets are de-normalised positions)")
+            raise ValueError("joint control and scenes need the dataset's mean and std (targets and primitives are "
+                             "de-normalised positions)")
         from .motion_control import joints_for_feats
         J = joints_for_feats(dim_pose)
-        g = torch.as_tensor(control_joints, dtype=torch.float32)
-        if g.dim() != 4 or tuple(g.shape[2:]) != (J, 3):
-            raise ValueError(f"control_joints of shape {tuple(g.shape)} must be (N, T_max, {J}, 3)")
-        w = expand_to(torch.as_tensor(control_weights, dtype=torch.float32), 1, g.shape, "control_weights",
-                      f"must lead with N = {g.shape[0]}")
+        g = w = None
+        if control_joints is not None:
+            g = torch.as_tensor(control_joints, dtype=torch.float32)
+            if g.dim() != 4 or tuple(g.shape[2:]) != (J, 3):
+                raise ValueError(f"control_joints of shape {tuple(g.shape)} must be (N, T_max, {J}, 3)")
+            w = expand_to(torch.as_tensor(control_weights, dtype=torch.float32), 1, g.shape, "control_weights",
+                          f"must lead with N = {g.shape[0]}")
         ms = []
         for name, v in (("mean", mean), ("std", std)):
             v = torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v), dtype=torch.float32).flatten()
@@ -599,13 +672,18 @@ class Conditioning:
         """``control_*`` of rows ``rows``, their first T frames, on ``device``; {} without control."""
         if self.control is None:
             return {}
-        c = self.control
-        g = c["joints"][rows]
-        if g.shape[1] < T:
-            raise ValueError(f"control_joints has {g.shape[1]} frames, the batch {T}")
-        n = g.shape[0]
-        return {"control_joints": g[:, :T].to(device), "control_weights": c["weights"][rows][:, :T].to(device),
-                "control_mean": c["mean"].to(device).expand(n, -1), "control_std": c["std"].to(device).expand(n, -1),
+        c, out = self.control, {}
+        if c["joints"] is not None:
+            g = c["joints"][rows]
+            if g.shape[1] < T:
+                raise ValueError(f"control_joints has {g.shape[1]} frames, the batch {T}")
+            out = {"control_joints": g[:, :T].to(device), "control_weights": c["weights"][rows][:, :T].to(device)}
+        if self.scene_records is not None:
+            rec = self.scene_records[rows]
+            out.update(control_scene=rec.to(device),
+                       control_joint_params=self.scene_joint_params.to(device).expand(rec.shape[0], -1, -1))
+        n = len(self.captions_of(rows))
+        return {**out, "control_mean": c["mean"].to(device).expand(n, -1), "control_std": c["std"].to(device).expand(n, -1),
                 "control_scale": self.control_scale, "control_iters": self.control_iters}
 
     def start_kwargs(self, rows, T, lengths, num_steps, sampler, device):

@@ -14,6 +14,7 @@
 // per-frame sums need no atomics and the result is deterministic); the three scans run in one thread with fp64
 // accumulators.  No other column of the feature row enters recover_from_ric, so none is read or written.
 #include "kernels.h"
+#include "scene_sdf.h"
 
 #include <cmath>
 
@@ -49,19 +50,25 @@ __device__ __forceinline__ RotD rot_d(float cw, float sw) {
 
 // GUIDE = false: mdm_joint_loss_grad (one evaluation; loss_out and the dense gradient grad_out written).
 // GUIDE = true:  mdm_joint_guidance (iters steps of x0 -= scale (1 - m) grad in LDS, then x0 / x updated where delta != 0).
-template <bool GUIDE, bool MASK>
+// SCENE = true:  the mdm_joint_scene_* calls: the scene's penalty of every joint (scene_sdf.h) joins the loss
+//                and dL/dP, with K primitive records and the joints' (radius, weight) per sample; targets / weights may
+//                then both be null (no target term).
+template <bool GUIDE, bool MASK, bool SCENE>
 __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
     float* x0, float* x, const float* __restrict__ mask, const int* __restrict__ len, const float* __restrict__ mean,
     const float* __restrict__ sd, const float* __restrict__ targets, const float* __restrict__ weights, int T, int F,
     int J, float scale, int iters, const float* __restrict__ coef, int steps, const int* __restrict__ t_ptr, int t_imm,
-    float* __restrict__ loss_out, float* __restrict__ grad_out) {
+    float* __restrict__ loss_out, float* __restrict__ grad_out, const float* __restrict__ scene, int K,
+    const float* __restrict__ jparams) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int D = 3 * J + 1;               // steerable columns: root (4) + ric (3 (J - 1))
   const int DS = D | 1;                  // odd LDS row stride
   double* lossF = (double*)smem_raw;     // [T]
   float* lsd = (float*)(lossF + T);      // [DS] std and mean of the steerable columns (in LDS: as scalar loads hoisted
   float* lmean = lsd + DS;               //      out of the loops they would take scalar registers the kernel lacks)
-  float* xs = lmean + DS;                // [T][DS] the steerable columns of x0, normalised
+  float* prims = lmean + DS;             // SCENE: [K][SCENE_REC] the primitive records and [J][2] the joints' (radius, weight)
+  float* jp = prims + (SCENE ? K * scene::SCENE_REC : 0);
+  float* xs = jp + (SCENE ? 2 * J : 0);  // [T][DS] the steerable columns of x0, normalised
   // per-frame record fr[t * FR + k] (one LDS base for all of them):
   //   CW, SW   cos / sin of the heading of frame t
   //   RX, RZ   root velocity of frame t - 1 rotated by the heading of frame t
@@ -77,6 +84,7 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
   const float* tg = targets + (int64_t)b * T * J * 3;
   const float* wt = weights + (int64_t)b * T * J * 3;
   const float* mk = MASK ? mask + row0 : nullptr;
+  const bool aim = !SCENE || targets != nullptr;  // a scene may come without targets
   float c0 = 0.f;  // read before the iterations: keeps the table's pointers out of the loop's scalar registers
   if (GUIDE) {
     int ts = t_ptr ? *t_ptr : t_imm;
@@ -96,6 +104,10 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
     xs[t * DS + c] = x0[row0 + (int64_t)t * F + c];
   }
   for (int c = tid; c < D; c += CTRL_THREADS) lsd[c] = sd[(int64_t)b * F + c], lmean[c] = mean[(int64_t)b * F + c];
+  if (SCENE) {
+    for (int i = tid; i < K * scene::SCENE_REC; i += CTRL_THREADS) prims[i] = scene[(int64_t)b * K * scene::SCENE_REC + i];
+    for (int i = tid; i < 2 * J; i += CTRL_THREADS) jp[i] = jparams[(int64_t)b * 2 * J + i];
+  }
   __syncthreads();
   auto val = [&](int t, int c) { return add(mul(xs[t * DS + c], lsd[c]), lmean[c]); };
   // one gradient entry g (w.r.t. the normalised feature): written out, or the guidance step applied in LDS
@@ -145,6 +157,7 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
       double lsum = 0.0, sx = 0.0, sz = 0.0, sa = 0.0;
       float g[3];
       auto dl = [&](int k, float p) {  // dL/dP of one coordinate; W == 0 contributes nothing, whatever G holds
+        if (SCENE && !aim) return 0.f;
         const float w = wgt[k];
         if (w == 0.f) return 0.f;
         const float d = p - tgt[k];
@@ -152,7 +165,9 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
         return 2.f * w * d;
       };
       {  // joint 0: root XZ and height
-        g[0] = dl(0, qx), g[1] = dl(1, val(t, 3)), g[2] = dl(2, qz);
+        const float py = val(t, 3);
+        g[0] = dl(0, qx), g[1] = dl(1, py), g[2] = dl(2, qz);
+        if (SCENE) lsum += scene::penalty(prims, K, jp[0], jp[1], qx, py, qz, g);
         sx += g[0], sz += g[2];
         fr[t * FR + GH] = g[1];
       }
@@ -162,7 +177,9 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
         const float vx = val(t, col), vy = val(t, col + 1), vz = val(t, col + 2);
         float ox, oz;
         rot_y(c, -s, vx, vz, ox, oz);
-        g[0] = dl(3 * j, add(ox, qx)), g[1] = dl(3 * j + 1, vy), g[2] = dl(3 * j + 2, add(oz, qz));
+        const float px = add(ox, qx), pz = add(oz, qz);
+        g[0] = dl(3 * j, px), g[1] = dl(3 * j + 1, vy), g[2] = dl(3 * j + 2, pz);
+        if (SCENE) lsum += scene::penalty(prims, K, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
         if (GUIDE && g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) continue;  // no step: the entries keep their bits
         sx += g[0], sz += g[2];
         sa += 2.0 * ((double)g[0] * (r.e * vz + r.f * vx) + (double)g[2] * (r.f * vz - r.e * vx));
@@ -223,9 +240,11 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
 
 int control_joints(int F) { return (F + 1) % 12 == 0 && F >= 11 ? (F + 1) / 12 : 0; }
 
-size_t control_lds_bytes(int T, int J) {
+// prims < 0: no scene; else the K = prims primitive records and the joints' (radius, weight) as well
+size_t control_lds_bytes(int T, int J, int prims = -1) {
   const int DS = (3 * J + 1) | 1;
-  return (size_t)2 * DS * 4 + (size_t)T * ((size_t)DS * 4 + CTRL_FRAME_BYTES);
+  const size_t scene = prims < 0 ? 0 : ((size_t)prims * scene::SCENE_REC + 2 * J) * 4;
+  return (size_t)2 * DS * 4 + scene + (size_t)T * ((size_t)DS * 4 + CTRL_FRAME_BYTES);
 }
 
 }  // namespace
@@ -248,9 +267,9 @@ int mdm_joint_loss_grad(const float* x0, const int32_t* length, const float* mea
   if (J == 0 || B < 0 || T < 1 || T > mdm_joint_control_max_frames(F)) return MDM_ERR_ARG;
   if (B == 0) return MDM_OK;
   const size_t smem = mdm::control_lds_bytes(T, J);
-  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
+  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
                      const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J, 0.f, 1,
-                     nullptr, 1, nullptr, 0, loss_out, grad_out);
+                     nullptr, 1, nullptr, 0, loss_out, grad_out, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -267,13 +286,65 @@ int mdm_joint_guidance(float* x, float* x0, const float* mask, const int32_t* le
   if (B == 0) return MDM_OK;
   const size_t smem = mdm::control_lds_bytes(T, J);
   if (mask)
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
                        x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev, t_imm,
-                       nullptr, nullptr);
+                       nullptr, nullptr, nullptr, 0, nullptr);
   else
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
                        x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev,
-                       t_imm, nullptr, nullptr);
+                       t_imm, nullptr, nullptr, nullptr, 0, nullptr);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_joint_scene_max_frames(int32_t feats, int32_t prims) {
+  const int J = mdm::control_joints(feats);
+  if (J == 0 || prims < 0 || prims > MDM_SCENE_MAX_PRIMS) return 0;
+  const size_t fixed = mdm::control_lds_bytes(0, J, prims), frame = mdm::control_lds_bytes(1, J, prims) - fixed;
+  return (int)((mdm::CTRL_LDS_BYTES - fixed) / frame);
+}
+
+int mdm_joint_scene_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
+                              const float* weights, const float* scene, int32_t K, const float* joint_params, int32_t B,
+                              int32_t T, int32_t F, float* loss_out, float* grad_out, void* stream) {
+  if (!x0 || !length || !mean || !std || !joint_params || !loss_out || !grad_out || !targets != !weights) return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::control_joints(F);
+  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
+  if (K == 0 && targets)  // no scene: the launch of mdm_joint_loss_grad
+    return mdm_joint_loss_grad(x0, length, mean, std, targets, weights, B, T, F, loss_out, grad_out, stream);
+  if (B == 0) return MDM_OK;
+  const size_t smem = mdm::control_lds_bytes(T, J, K);
+  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
+                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J,
+                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_joint_scene_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
+                             const float* targets, const float* weights, const float* scene, int32_t K,
+                             const float* joint_params, int32_t B, int32_t T, int32_t F, float scale, int32_t iters,
+                             const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, void* stream) {
+  if (!x || !x0 || !length || !mean || !std || !joint_params || !coef || !targets != !weights) return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::control_joints(F);
+  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
+  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
+  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
+  if (K == 0 && targets)  // no scene: the launch of mdm_joint_guidance
+    return mdm_joint_guidance(x, x0, mask, length, mean, std, targets, weights, B, T, F, scale, iters, coef, steps, t_dev, t_imm,
+                              stream);
+  if (B == 0) return MDM_OK;
+  const size_t smem = mdm::control_lds_bytes(T, J, K);
+  if (mask)
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
+                       (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps,
+                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params);
+  else
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
+                       (hipStream_t)stream, x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef,
+                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }

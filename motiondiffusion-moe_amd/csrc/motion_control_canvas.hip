@@ -21,6 +21,7 @@
 // of the loops around barriers depend on the motion alone.  The summation order differs from motion_post_kernel's serial
 // scans: P agrees with mdm_motion_postprocess to rounding, not bit for bit.
 #include "kernels.h"
+#include "scene_sdf.h"
 
 #include <cmath>
 #include <cstdint>
@@ -86,19 +87,25 @@ __device__ __forceinline__ double block_scan(double v, double& carry, double* sl
 }
 
 // GUIDE = false: mdm_canvas_joint_loss_grad.  GUIDE = true: mdm_canvas_joint_guidance.
-template <bool GUIDE, bool MASK>
+// SCENE = true: the mdm_canvas_scene_* calls: the scene's penalty of every joint (scene_sdf.h) joins the loss
+// and dL/dP, with K primitive records and the joints' (radius, weight) per motion, in the canvas frame; targets / weights
+// may then both be null.
+template <bool GUIDE, bool MASK, bool SCENE>
 __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
     float* x0, float* x, const float* __restrict__ mask, const int* __restrict__ offs, const int* __restrict__ frows,
     const float* __restrict__ mean, const float* __restrict__ sd, const float* __restrict__ targets,
     const float* __restrict__ weights, int F, int J, float scale, int iters, const float* __restrict__ coef, int steps,
-    const int* __restrict__ t_ptr, int t_imm, float* loss_out, float* grad_out, float* ws) {
+    const int* __restrict__ t_ptr, int t_imm, float* loss_out, float* grad_out, float* ws,
+    const float* __restrict__ scene, int K, const float* __restrict__ jparams) {
   __shared__ double slots[3][CV_WAVES];  // the wave totals of up to three scans in flight
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int D = 3 * J + 1;          // steerable columns: root (4) + ric (3 (J - 1))
   float* lsd = (float*)smem_raw;    // [D] std and mean of the steerable columns
   float* lmean = lsd + D;           // [D]
   const int DS = D | 1;             // odd row stride of the tile: frames along the lanes without bank conflicts
-  float* tile = lmean + D;          // [CV_TILE][DS]
+  float* prims = lmean + D;         // SCENE: [K][SCENE_REC] the primitive records and [J][2] the joints' (radius, weight)
+  float* jp = prims + (SCENE ? K * scene::SCENE_REC : 0);
+  float* tile = jp + (SCENE ? 2 * J : 0);  // [CV_TILE][DS]
   const int m = blockIdx.x, tid = threadIdx.x;
   const int c0 = offs[m];
   const int n = min(max(offs[m + 1] - c0, 0), INT32_MAX / (D + FR));  // offsets inside a motion's state are int32
@@ -112,6 +119,7 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
   const int* rows = frows + c0;
   const float* tg = targets + (int64_t)c0 * J * 3;
   const float* wt = weights + (int64_t)c0 * J * 3;
+  const bool aim = !SCENE || targets != nullptr;  // a scene may come without targets
   float c0t = 0.f;
   if (GUIDE) {
     int ts = t_ptr ? *t_ptr : t_imm;
@@ -144,6 +152,10 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
     __syncthreads();
   }
   for (int c = tid; c < D; c += CV_THREADS) lsd[c] = sd[(int64_t)m * F + c], lmean[c] = mean[(int64_t)m * F + c];
+  if (SCENE) {
+    for (int i = tid; i < K * scene::SCENE_REC; i += CV_THREADS) prims[i] = scene[(int64_t)m * K * scene::SCENE_REC + i];
+    for (int i = tid; i < 2 * J; i += CV_THREADS) jp[i] = jparams[(int64_t)m * 2 * J + i];
+  }
   __syncthreads();
   auto val = [&](int t, int c) { return add(mul(xs[c * n + t], lsd[c]), lmean[c]); };
   // one gradient entry g (w.r.t. the normalised feature): written out, or the guidance step applied to the working copy
@@ -190,7 +202,16 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
           lsum += (double)w * (double)d * (double)d;
           return 2.f * w * d;
         };
-        g[0] = dl(wgt[0], tgt[0], qx), g[1] = dl(wgt[1], tgt[1], val(t, 3)), g[2] = dl(wgt[2], tgt[2], qz);  // joint 0
+        {  // joint 0
+          const float py = val(t, 3);
+          float w0[3] = {0.f, 0.f, 0.f}, g0[3] = {0.f, 0.f, 0.f};
+          if (aim) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) w0[k] = wgt[k], g0[k] = tgt[k];
+          }
+          g[0] = dl(w0[0], g0[0], qx), g[1] = dl(w0[1], g0[1], py), g[2] = dl(w0[2], g0[2], qz);
+          if (SCENE) lsum += scene::penalty(prims, K, jp[0], jp[1], qx, py, qz, g);
+        }
         sx += g[0], sz += g[2];
         fr[t * FR + GH] = g[1];
         // CV_JOINTS joints at a time, every load of a group issued before its first store (the working copy and the
@@ -204,7 +225,7 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
             const int j = min(j0 + u, J - 1), col = 4 + 3 * (j - 1);  // a group past the last joint re-reads it, unused
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-              wv[u][k] = wgt[3 * j + k], gv[u][k] = tgt[3 * j + k], xv[u][k] = xs[(col + k) * n + t];
+              wv[u][k] = aim ? wgt[3 * j + k] : 0.f, gv[u][k] = aim ? tgt[3 * j + k] : 0.f, xv[u][k] = xs[(col + k) * n + t];
               mv[u][k] = GUIDE && MASK ? mask[(int64_t)rows[t] * F + col + k] : 0.f;
             }
           }
@@ -216,8 +237,9 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
                         vz = add(mul(xv[u][2], lsd[col + 2]), lmean[col + 2]);
             float rx, rz;
             rot_y(c, -s, vx, vz, rx, rz);
-            g[0] = dl(wv[u][0], gv[u][0], add(rx, qx)), g[1] = dl(wv[u][1], gv[u][1], vy);
-            g[2] = dl(wv[u][2], gv[u][2], add(rz, qz));
+            const float px = add(rx, qx), pz = add(rz, qz);
+            g[0] = dl(wv[u][0], gv[u][0], px), g[1] = dl(wv[u][1], gv[u][1], vy), g[2] = dl(wv[u][2], gv[u][2], pz);
+            if (SCENE) lsum += scene::penalty(prims, K, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
             if (GUIDE && g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) continue;  // no step: the entries keep their bits
             sx += g[0], sz += g[2];
             sa += 2.0 * ((double)g[0] * (r.e * vz + r.f * vx) + (double)g[2] * (r.f * vz - r.e * vx));
@@ -314,9 +336,11 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
 
 int canvas_joints(int F) { return (F + 1) % 12 == 0 && F >= 11 ? (F + 1) / 12 : 0; }
 
-size_t canvas_lds_bytes(int J) {
+// prims < 0: no scene; else the K = prims primitive records and the joints' (radius, weight) as well
+size_t canvas_lds_bytes(int J, int prims = -1) {
   const int D = 3 * J + 1;
-  return ((size_t)2 * D + (size_t)CV_TILE * (D | 1)) * 4;
+  const size_t scene = prims < 0 ? 0 : (size_t)prims * scene::SCENE_REC + 2 * J;
+  return ((size_t)2 * D + scene + (size_t)CV_TILE * (D | 1)) * 4;
 }
 
 }  // namespace
@@ -340,9 +364,9 @@ int mdm_canvas_joint_loss_grad(const float* x0, const int32_t* motion_offsets, c
   if (M == 0) return MDM_OK;
   const size_t smem = mdm::canvas_lds_bytes(J);
   if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream,
+  hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream,
                      const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace);
+                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -361,13 +385,68 @@ int mdm_canvas_joint_guidance(float* x, float* x0, const float* mask, const int3
   const size_t smem = mdm::canvas_lds_bytes(J);
   if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
   if (mask)
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
+    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
                        x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale, iters, coef, steps, t_dev,
-                       t_imm, nullptr, nullptr, workspace);
+                       t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr);
   else
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
+    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
                        x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, workspace);
+                       t_dev, t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_canvas_scene_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
+                               const float* std, const float* targets, const float* weights, const float* scene, int32_t K,
+                               const float* joint_params, int32_t M, int32_t F, float* loss_out, float* grad_out,
+                               float* workspace, void* stream) {
+  if (!x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !loss_out || !grad_out || !workspace ||
+      !targets != !weights)
+    return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::canvas_joints(F);
+  if (J == 0 || M < 0) return MDM_ERR_ARG;
+  if (K == 0 && targets)  // no scene: the launch of mdm_canvas_joint_loss_grad
+    return mdm_canvas_joint_loss_grad(x0, motion_offsets, frame_rows, mean, std, targets, weights, M, F, loss_out, grad_out,
+                                      workspace, stream);
+  if (M == 0) return MDM_OK;
+  const size_t smem = mdm::canvas_lds_bytes(J, K);
+  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
+                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std,
+                     targets, weights, F, J, 0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, scene, K,
+                     joint_params);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_canvas_scene_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
+                              const float* mean, const float* std, const float* targets, const float* weights,
+                              const float* scene, int32_t K, const float* joint_params, int32_t M, int32_t F, float scale,
+                              int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
+                              float* workspace, void* stream) {
+  if (!x || !x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !coef || !workspace ||
+      !targets != !weights)
+    return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::canvas_joints(F);
+  if (J == 0 || M < 0) return MDM_ERR_ARG;
+  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
+  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
+  if (K == 0 && targets)  // no scene: the launch of mdm_canvas_joint_guidance
+    return mdm_canvas_joint_guidance(x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, M, F, scale, iters,
+                                     coef, steps, t_dev, t_imm, workspace, stream);
+  if (M == 0) return MDM_OK;
+  const size_t smem = mdm::canvas_lds_bytes(J, K);
+  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
+  if (mask)
+    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
+                       (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale,
+                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params);
+  else
+    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
+                       (hipStream_t)stream, x0, x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
+                       scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }

@@ -29,9 +29,10 @@ combines ``x0 = x0_u + s * sum_k w_k (x0_k - x0_u)`` in one fused kernel (``mdm_
 time-varied and body-part control, negative prompts.
 
 Joint-position control: ``model_kwargs`` may carry ``control_joints`` (B, T, J, 3) targets, ``control_weights``,
-``control_mean`` / ``control_std`` (B, F), ``control_scale`` and ``control_iters``; every loop and single step then moves
-its x0 down the gradient of the weighted squared distance of ``recover_from_ric(x0 * std + mean)`` to the targets after its
-update, and x_{t-1} with it (``mdm_joint_guidance``): trajectories, keyframes, end positions.
+``control_mean`` / ``control_std`` (B, F), ``control_scale`` and ``control_iters``, and with or without the targets a scene
+(``control_scene`` (B, K, 12) primitive records, ``control_joint_params`` (B, J, 2), whose penalty joins the
+loss: ``mdm_joint_scene_guidance``); every loop and single step then moves its x0 down the gradient of the weighted
+squared distance of ``recover_from_ric(x0 * std + mean)`` to the targets after its update, and x_{t-1} with it (``mdm_joint_guidance``): trajectories, keyframes, end positions.
 
 Long motions: ``model_kwargs`` may carry handshake tables (``handshake_offsets``, ``handshake_rows``,
 ``handshake_weights``, ``handshake_owner_rows``, from ``motion_long``) over the rows of overlapping windows of one long
@@ -706,10 +707,16 @@ class _StepRunner:
         ctl = check_control_kwargs(kw, shape)
         self.ctl = None
         if ctl is not None:
-            J = ctl["targets"].shape[2]
+            J = (Fe + 1) // 12
+            aim = ctl["targets"] is not None  # a scene may come without targets
             self.ctl = dict(scale=ctl["scale"], iters=ctl["iters"], len=length.contiguous(),
-                            targets=f32(ctl["targets"], (B, T, J, 3)), weights=f32(ctl["weights"], (B, T, J, 3)),
+                            targets=f32(ctl["targets"], (B, T, J, 3)) if aim else None,
+                            weights=f32(ctl["weights"], (B, T, J, 3)) if aim else None,
                             mean=f32(ctl["mean"], (B, Fe)), std=f32(ctl["std"], (B, Fe)))
+            if "scene" in ctl:  # scene constraints: the primitive records and the joints' (radius, weight)
+                K = int(ctl["scene"].shape[1])
+                self.ctl.update(K=K, scene=f32(ctl["scene"], (B, K, L.SCENE_REC)) if K else None,
+                                joint_params=f32(ctl["joint_params"], (B, J, 2)))
         # long motions: the handshake tables of the overlapping windows
         hs = check_handshake_kwargs(kw, shape)
         self.hs = None if hs is None else {k: v.to(dev).contiguous() if torch.is_tensor(v) else v for k, v in hs.items()}
@@ -717,12 +724,17 @@ class _StepRunner:
         cc = check_canvas_control_kwargs(kw, shape)
         self.cctl = None
         if cc is not None:
-            J, tot = cc["targets"].shape[1], cc["total"]
+            J, tot = (Fe + 1) // 12, cc["total"]
+            aim = cc["targets"] is not None
             nws = int(L.lib().mdm_canvas_control_workspace_floats(tot, Fe))
             self.cctl = dict(scale=cc["scale"], iters=cc["iters"], M=cc["M"], offsets=cc["offsets"].to(dev).contiguous(),
-                             rows=cc["rows"].to(dev).contiguous(), targets=f32(cc["targets"], (tot, J, 3)),
-                             weights=f32(cc["weights"], (tot, J, 3)), mean=f32(cc["mean"], (cc["M"], Fe)),
+                             rows=cc["rows"].to(dev).contiguous(), targets=f32(cc["targets"], (tot, J, 3)) if aim else None,
+                             weights=f32(cc["weights"], (tot, J, 3)) if aim else None, mean=f32(cc["mean"], (cc["M"], Fe)),
                              std=f32(cc["std"], (cc["M"], Fe)), ws=torch.empty(max(nws, 1), dtype=torch.float32, device=dev))
+            if "scene" in cc:
+                K = int(cc["scene"].shape[1])
+                self.cctl.update(K=K, scene=f32(cc["scene"], (cc["M"], K, L.SCENE_REC)) if K else None,
+                                 joint_params=f32(cc["joint_params"], (cc["M"], J, 2)))
         # few-step modes (and every mode when editing, composing or controlling): per-step coefficients of the fused update;
         # self.x0 doubles as x0_prev (updated in place)
         table = self.known is not None or self.cw is not None or self.ctl is not None or self.cctl is not None
@@ -800,7 +812,8 @@ class _StepRunner:
 
     def _plan_update(self):
         """The update of a step, ``(entry name, arguments before the noise pointer, arguments after it)``, and the
-        arguments of mdm_joint_guidance (None without control).  Every pointer belongs to a buffer the runner owns for its
+        entry and arguments of the joint guidance, mdm_joint_guidance or with a scene mdm_joint_scene_guidance (None without
+        control).  Every pointer belongs to a buffer the runner owns for its
         lifetime; the noise pointer and the stream are the launch's.  Plain "cfg" / "ddpm" keep mdm_cfg_posterior_step and
         plain "ddim" mdm_ddim_step; with a coefficient table the three fused entries share their head and tail."""
         p = L.ptr
@@ -811,13 +824,18 @@ class _StepRunner:
         guide = None
         if self.ctl is not None:
             c = self.ctl
-            guide = (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"]), self.B,
-                     self.T, self.Fe, c["scale"], c["iters"], p(self.coef)) + clock
-        self._guide_canvas = None  # the arguments of mdm_canvas_joint_guidance (None without canvas control)
+            scene = (p(c["scene"]), c["K"], p(c["joint_params"])) if "K" in c else ()
+            guide = ("mdm_joint_scene_guidance" if scene else "mdm_joint_guidance",
+                     (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"])) + scene
+                     + (self.B, self.T, self.Fe, c["scale"], c["iters"], p(self.coef)) + clock)
+        self._guide_canvas = None  # the entry and arguments of the canvas guidance (None without canvas control)
         if self.cctl is not None:
             c = self.cctl
-            self._guide_canvas = (x, x0, p(self.mask), p(c["offsets"]), p(c["rows"]), p(c["mean"]), p(c["std"]), p(c["targets"]),
-                                  p(c["weights"]), c["M"], self.Fe, c["scale"], c["iters"], p(self.coef)) + clock + (p(c["ws"]),)
+            scene = (p(c["scene"]), c["K"], p(c["joint_params"])) if "K" in c else ()
+            self._guide_canvas = ("mdm_canvas_scene_guidance" if scene else "mdm_canvas_joint_guidance",
+                                  (x, x0, p(self.mask), p(c["offsets"]), p(c["rows"]), p(c["mean"]), p(c["std"]),
+                                   p(c["targets"]), p(c["weights"])) + scene
+                                  + (c["M"], self.Fe, c["scale"], c["iters"], p(self.coef)) + clock + (p(c["ws"]),))
         if self.coef is None and self.mode == "ddim":
             return ("mdm_ddim_step", (x, eps), (self.n, p(self.tab)) + clock + (self.eta,) + out), guide
         tail = clock + (self.cfg_scale,) + out
@@ -859,9 +877,9 @@ class _StepRunner:
         name, head, tail = self._update
         L.check(getattr(lib, name)(*head, self.noise.data_ptr() if use_noise else 0, *tail, s), name)
         if self._guide is not None:  # x0 and x_{t-1} moved down the joint-position loss, before the counter moves
-            L.check(lib.mdm_joint_guidance(*self._guide, s), "mdm_joint_guidance")
+            L.check(getattr(lib, self._guide[0])(*self._guide[1], s), self._guide[0])
         if self._guide_canvas is not None:  # once per long motion over its canvas, then the owner's bits into every overlap
-            L.check(lib.mdm_canvas_joint_guidance(*self._guide_canvas, s), "mdm_canvas_joint_guidance")
+            L.check(getattr(lib, self._guide_canvas[0])(*self._guide_canvas[1], s), self._guide_canvas[0])
             if self.hs is not None:
                 self._handshake(self.xx, 1, False, s)
                 self._handshake(self.x0, 1, False, s)

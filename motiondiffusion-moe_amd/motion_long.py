@@ -164,42 +164,60 @@ def batch_control_tables(plans, idx, T: int, joints, weights) -> Dict[str, torch
     """The ``canvas_control_*`` table kwargs of one batch, next to ``batch_tables``: for the motions ``idx``,
     whose windows are consecutive batch rows in that order padded to T frames, ``canvas_control_offsets`` (len(idx) + 1),
     ``canvas_control_rows`` (``canvas_frame_rows`` of each, concatenated) and the canvas-order ``canvas_control_joints`` /
-    ``canvas_control_weights`` (sum of canvas lengths, J, 3) from ``joints[i]`` / ``weights[i]`` (C_i, J, 3)."""
+    ``canvas_control_weights`` (sum of canvas lengths, J, 3) from ``joints[i]`` / ``weights[i]`` (C_i, J, 3); ``joints`` None
+    (a scene without targets): the two row tables alone."""
     offsets, rows, row = [0], [], 0
     for i in idx:
         rows.append(canvas_frame_rows(plans[i][2], plans[i][1], T, first_row=row))
         offsets.append(offsets[-1] + plans[i][3])
         row += len(plans[i][1])
-    return {"canvas_control_offsets": torch.tensor(offsets, dtype=torch.int32),
-            "canvas_control_rows": torch.from_numpy(np.concatenate(rows)),
-            "canvas_control_joints": torch.cat([joints[i] for i in idx]).contiguous(),
-            "canvas_control_weights": torch.cat([weights[i] for i in idx]).contiguous()}
+    out = {"canvas_control_offsets": torch.tensor(offsets, dtype=torch.int32),
+           "canvas_control_rows": torch.from_numpy(np.concatenate(rows))}
+    if joints is not None:
+        out.update(canvas_control_joints=torch.cat([joints[i] for i in idx]).contiguous(),
+                   canvas_control_weights=torch.cat([weights[i] for i in idx]).contiguous())
+    return out
 
 
 def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, control_scale=None, control_iters=None,
-                   mean=None, std=None, device=None):
+                   mean=None, std=None, device=None, scene=None, scene_joint_radius=None, scene_joint_weights=None):
     """The joint-control inputs of ``DDPMTrainer.generate_long`` (described there), checked once for the call:
     one (C_i, J, 3) target array per motion of ``plans`` in canvas frames and weights broadcastable to it (aligned on the
     frame dim), with the dataset's ``mean`` / ``std``.  Returns ``tables(idx, T)``: the ``canvas_control_*`` model kwargs
     (``batch_control_tables``, one mean / std row per motion, ``control_scale`` / ``control_iters`` where given) of the batch
     of motions ``idx`` at T frames, on ``device``; {} without control.  Raises ValueError for targets without weights or the
-    reverse, a scale or iteration count without them, missing mean / std, not one entry per motion, and canvas shapes."""
-    if control_joints is None and control_weights is None:
+    reverse, a scale or iteration count without them, missing mean / std, not one entry per motion, and canvas shapes.
+    ``scene``: one list of ``motion_scene`` primitives per motion, in its canvas frame, with
+    ``scene_joint_radius`` / ``scene_joint_weights`` (J,); it may come without targets, and adds ``canvas_control_scene`` /
+    ``canvas_control_joint_params`` to the tables."""
+    aim = control_joints is not None or control_weights is not None
+    if scene is None and (scene_joint_radius is not None or scene_joint_weights is not None):
+        raise ValueError("scene_joint_radius / scene_joint_weights go with scene")
+    if not aim and scene is None:
         if control_scale is not None or control_iters is not None:
             raise ValueError("control_scale / control_iters given without control_joints / control_weights")
         return lambda idx, T: {}
     N = len(plans)
-    if control_joints is None or control_weights is None:
+    if aim and (control_joints is None or control_weights is None):
         raise ValueError("control_joints and control_weights go together: give both or neither")
     if mean is None or std is None:
-        raise ValueError("joint control needs the dataset's mean and std (the targets are de-normalised positions)")
-    for name, v in (("control_joints", control_joints), ("control_weights", control_weights)):
+        raise ValueError("joint control and scenes need the dataset's mean and std (targets and primitives are "
+                         "de-normalised positions)")
+    for name, v in (("control_joints", control_joints), ("control_weights", control_weights)) if aim else ():
         if torch.is_tensor(v) or isinstance(v, np.ndarray) or len(v) != N or any(x is None for x in v):
             raise ValueError(f"{name} must hold one entry per motion ({N}), each over its canvas: for every motion or for none")
     from .motion_control import joints_for_feats
     J = joints_for_feats(dim_pose)
+    records = params = None
+    if scene is not None:
+        from .motion_scene import Primitive, batch_scene, joint_params
+        if torch.is_tensor(scene) or isinstance(scene, np.ndarray) or len(scene) != N or any(
+                s is None or isinstance(s, Primitive) for s in scene):
+            raise ValueError(f"scene must hold one list of primitives per motion ({N}), in its canvas frame")
+        records = batch_scene(scene, N)
+        params = joint_params(J, scene_joint_radius, scene_joint_weights)
     joints, weights = [], []
-    for i, (g, w) in enumerate(zip(control_joints, control_weights)):
+    for i, (g, w) in enumerate(zip(control_joints, control_weights) if aim else ()):
         C = plans[i][3]
         g = torch.as_tensor(g).detach().to("cpu", torch.float32)
         if tuple(g.shape) != (C, J, 3):
@@ -218,7 +236,9 @@ def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, c
         ms.append(v)
 
     def tables(idx, T):
-        kw = batch_control_tables(plans, idx, T, joints, weights)
+        kw = batch_control_tables(plans, idx, T, joints if aim else None, weights)
+        if records is not None:
+            kw.update(canvas_control_scene=records[list(idx)], canvas_control_joint_params=params.expand(len(idx), -1, -1))
         kw.update(canvas_control_mean=ms[0].expand(len(idx), -1), canvas_control_std=ms[1].expand(len(idx), -1))
         kw = {k: v.to(device) for k, v in kw.items()}
         kw.update({k: v for k, v in (("control_scale", control_scale), ("control_iters", control_iters)) if v is not None})

@@ -269,7 +269,8 @@ class DDPMTrainer(object):
         list of ``(m_len, joints_num, 3)`` joint positions, temporally smoothed with a gaussian of width ``sigma``.
         ``edit_motion`` / ``edit_mask``: motion editing in normalised feature space, as in ``generate``;
         ``prompt_weights``: composed prompts, as in ``generate``; ``control_joints`` / ``control_weights`` /
-        ``control_scale`` / ``control_iters``: joint-position control under this call's ``mean`` / ``std``;
+        ``control_scale`` / ``control_iters``: joint-position control under this call's ``mean`` / ``std``; ``scene`` /
+        ``scene_joint_radius`` / ``scene_joint_weights``: obstacles the joints keep out of (DESIGN.md §24), under the same;
         ``edit_joints`` (through ``**kw``): joint clips in place of ``edit_motion``, converted under the same ``mean`` /
         ``std``.  ``from_rotations``: joints by forward kinematics of the rot6d columns (``postprocess.motion_to_joints_fk``,
         DESIGN.md §17: rigid bones) on ``offsets`` (J, 3) or one (J, 3) per motion; None: every motion's own mean bone
@@ -309,7 +310,7 @@ class DDPMTrainer(object):
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
                       sample_steps=None, eta=0.0, progress=False, control_joints=None, control_weights=None, control_scale=None,
-                      control_iters=None, **conditioning):
+                      control_iters=None, scene=None, scene_joint_radius=None, scene_joint_weights=None, **conditioning):
         """Long motions: ``scripts`` is a list of long motions, each a list of ``(caption, length)``
         segments of at most ``num_frames`` frames; neighbouring segments share ``overlap`` canvas frames, whose eps is
         blended on every step (``blend`` "linear" crossfade or "uniform") while x_T and the step noise come from the left
@@ -329,7 +330,10 @@ class DDPMTrainer(object):
         broadcastable to it, as in ``generate`` but over the whole canvas (targets from
         ``motion_control.root_path_targets`` / ``keyframe_targets`` at T = canvas_len): a target late in the canvas moves the
         root path of every window before it.  It combines with every sampler and with the edit and start inputs
-        (``motion_long.canvas_control`` checks it).  The other per-motion inputs are ``**conditioning``, checked by
+        (``motion_long.canvas_control`` checks it).  ``scene`` (with ``mean`` / ``std``; ``scene_joint_radius`` /
+        ``scene_joint_weights`` (J,)): one list of ``motion_scene`` primitives per motion, in its canvas frame, that the joints
+        keep out of on every step, through the same canvas-wide guidance and with or without targets.
+        The other per-motion inputs are ``**conditioning``, checked by
         ``motion_long.canvas_conditioning``."""
         m = self._model()
         self.eval_mode()
@@ -337,7 +341,8 @@ class DDPMTrainer(object):
         device = getattr(self, "device", None)  # none on a trainer made without __init__ (host tests of the checks)
         window_rows = ML.canvas_conditioning(plans, dim_pose, device=device, **conditioning)
         control = ML.canvas_control(plans, dim_pose, control_joints, control_weights, control_scale, control_iters,
-                                    conditioning.get("mean"), conditioning.get("std"), device)
+                                    conditioning.get("mean"), conditioning.get("std"), device, scene, scene_joint_radius,
+                                    scene_joint_weights)
         out, first = [None] * len(plans), 0
         for idx in ML.plan_batches(plans, batch_size):
             caps = [c for i in idx for c in plans[i][0]]
@@ -364,7 +369,8 @@ class DDPMTrainer(object):
         longest = max(p[3] for p in ML.script_plans(scripts, kw.get("overlap", 20), self._model().num_frames))
         if longest > most:
             raise ValueError(f"a canvas of {longest} frames: {what} takes at most {most} frames")
-        if kw.get("edit_joints") is not None or kw.get("edit_bvh") is not None or kw.get("control_joints") is not None:
+        if kw.get("edit_joints") is not None or kw.get("edit_bvh") is not None or kw.get("control_joints") is not None or \
+                kw.get("scene") is not None:
             kw = dict(kw, mean=mean, std=std)
         return self.generate_long(scripts, dim_pose, **kw)
 

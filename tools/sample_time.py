@@ -33,6 +33,11 @@ the same B windows, DDIM-50 and DPM-Solver++(2M)-20, alternating, as for ``--edi
 
     timeout -k 10 900 python tools/sample_time.py --long 20 --reps 5 --precisions 1
 
+``--control I --scene K`` measures scene constraints: the controlled generations above without and with
+a scene of K primitives (spheres, pillars, boxes and floors in turn, every joint with a radius), alternating, as for ``--edit``.
+
+    timeout -k 10 900 python tools/sample_time.py --control 1,5 --scene 4,16 --reps 5 --precisions 1
+
 ``--long-control I`` (with ``--long H``, default 20) measures joint control over the canvases of those long motions: the same
 ``generate_long`` without and with ``control_joints`` / ``control_weights`` over every canvas frame (every joint's height,
 ``control_iters`` = I; I may be a list), DDIM-50 and DPM-Solver++(2M)-20, alternating, as for ``--edit``.
@@ -63,6 +68,8 @@ def main():
     ap.add_argument("--edit", default=None, help="prefix:N | inbetween:H,T: time editing against plain generation")
     ap.add_argument("--compose", default=None, help="K[,K...]: time K-prompt composed generation against plain")
     ap.add_argument("--control", default=None, help="I[,I...]: time joint control with I iterations against plain")
+    ap.add_argument("--scene", default=None, help="K[,K...] (with --control): time a scene of K primitives against joint "
+                    "control alone")
     ap.add_argument("--long", type=int, default=None, help="H: time long motions (4 windows each, H shared frames) "
                     "against plain generation of the same windows")
     ap.add_argument("--long-control", default=None, help="I[,I...]: time canvas joint control with I iterations against "
@@ -84,6 +91,8 @@ def main():
         return edit_main(a, tr, m, caps, length, B, T)
     if a.compose:
         return compose_main(a, tr, m, caps, length, B, T)
+    if a.control and a.scene:
+        return scene_main(a, tr, m, caps, length, B, T)
     if a.control:
         return control_main(a, tr, m, caps, length, B, T)
     if a.long_control:
@@ -268,6 +277,65 @@ def control_main(a, tr, m, caps, length, B, T):
         spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
         print(f"{r['precision']:>9} {r['control_iters']:>5} {r['sampler']:>22} {r['plain_ms']:>9.1f} "
               f"{r['control_ms']:>11.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
+
+
+def scene_main(a, tr, m, caps, length, B, T):
+    # the controlled generation of control_main, without and with a scene: keep-out primitives of every kind in turn (their
+    # force is bounded by their size, so the unclipped random-weight samples stay finite) around the origin
+    MS = importlib.import_module("motiondiffusion-moe_amd.motion_scene")
+    tg, w = torch.zeros(B, T, 22, 3), torch.zeros(B, T, 22, 3)
+    tg[..., 1], w[..., 1] = 1.0, 1.0
+    mean, std = torch.zeros(263), torch.ones(263)
+
+    def scene_of(K):
+        out = []
+        for k in range(K):
+            x, z = 0.8 * (k % 4) - 1.2, 0.8 * (k // 4) - 1.2
+            out.append([MS.sphere((x, 1.0, z), 0.4, margin=0.05), MS.capsule((x, 0.0, z), (x, 2.0, z), 0.2),
+                        MS.box((x, 0.5, z), (0.3, 0.5, 0.2), 0.3 * k), MS.floor(-0.1 * k)][k % 4])
+        return out
+
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for iters in [int(k) for k in a.control.split(",")]:
+            for K in [int(k) for k in a.scene.split(",")]:
+                scene = scene_of(K)
+                for sampler, steps, n in (("ddim", 50, 50), ("dpmpp2m", 20, 20)):
+                    def gen(sc):
+                        extra = dict(scene=scene, scene_joint_radius=[0.05] * 22) if sc else {}
+                        return tr.generate(caps, length, 263, batch_size=B, seed=0, sampler=sampler, sample_steps=steps,
+                                           control_joints=tg, control_weights=w, control_scale=0.05, control_iters=iters,
+                                           mean=mean, std=std, **extra)
+                    for sc in (False, True):  # warm-up
+                        assert all(torch.isfinite(o).all() for o in gen(sc))
+                    ts = {False: [], True: []}
+                    for _ in range(a.reps):
+                        for sc in (False, True):
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            gen(sc)
+                            torch.cuda.synchronize()
+                            ts[sc].append((time.perf_counter() - t0) * 1e3)
+                    med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+                    diff = sorted(c - p for p, c in zip(ts[False], ts[True]))
+                    name = {"ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+                    line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, control_iters=iters, prims=K,
+                                control_ms=round(med[False], 2), scene_ms=round(med[True], 2),
+                                diff_ms_median=round(diff[len(diff) // 2], 2), diff_ms_min=round(diff[0], 2),
+                                diff_ms_max=round(diff[-1], 2), diff_us_per_step=round(diff[len(diff) // 2] / n * 1e3, 1),
+                                control_reps_ms=[round(t, 2) for t in ts[False]], scene_reps_ms=[round(t, 2) for t in ts[True]])
+                    rows.append(line)
+                    print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}, guided (cfg 7.5), joint control (every joint's height) without and with a scene; "
+          f"{torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'iters':>5} {'prims':>5} {'sampler':>22} {'control ms':>11} {'scene ms':>9} {'diff ms (min..max)':>22} "
+          f"{'us/step':>8}")
+    for r in rows:
+        spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
+        print(f"{r['precision']:>9} {r['control_iters']:>5} {r['prims']:>5} {r['sampler']:>22} {r['control_ms']:>11.1f} "
+              f"{r['scene_ms']:>9.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
 
 
 def long_main(a, tr, m, caps, B, T):
