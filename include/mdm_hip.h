@@ -677,6 +677,41 @@ int mdm_canvas_scene_guidance(float* x, float* x0, const float* mask, const int3
                               int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
                               float* workspace, void* stream);
 
+/* Tracks: primitives that move.  A track is a primitive of the scene whose record may differ in every frame
+ * (a swinging bar, a rolling ball, the bones of another character); kind MDM_SCENE_PAD makes it absent in a frame.  `tracks`
+ * dense fp32 (B, T, Km, MDM_SCENE_REC) for the window calls, (total canvas frames, Km, MDM_SCENE_REC) in canvas order for
+ * the canvas calls, Km <= MDM_SCENE_MAX_TRACKS, records and frame as above.  The loss of the scene calls gains
+ *   L_tracks = sum_{t < length, j} u_j sum_k a_{t,k} max(0, m_{t,k} + r_j - sigma_{t,k} d(R[t, k]; P[t, j]))^2
+ * with R[t, k] the record of track k at frame t.  Records are data: no gradient reaches them.  The records stay in global
+ * memory (the LDS layout and mdm_joint_scene_max_frames are those of the scene calls).
+ * `track_bounds` (B, T, 4) / (total, 4) or NULL: per frame a ball (centre[3], radius) that contains every keep-out track of
+ * weight > 0 of that frame inflated by its margin.  A joint with |P - centre| > radius + r_j skips the frame's records, which
+ * changes no result as long as the ball does contain them: inflate it against fp32 rounding.  Radius +inf (a frame with a
+ * half-space or a keep-in track) never skips, -inf (no live track) always; NULL never skips.
+ * tracks and track_bounds are read 16 bytes at a time.  `scene` with K == 0, targets / weights and track_bounds may be NULL.
+ * With Km == 0 the calls are the scene calls, launch for launch.  MDM_ERR_ARG: Km outside [0, MDM_SCENE_MAX_TRACKS], null
+ * tracks with Km > 0, tracks or track_bounds not 16-byte aligned, and everything the scene calls refuse (the T limit is
+ * theirs). */
+enum { MDM_SCENE_MAX_TRACKS = 24 };
+int mdm_joint_tracks_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
+                               const float* weights, const float* scene, int32_t K, const float* joint_params,
+                               const float* tracks, int32_t Km, const float* track_bounds, int32_t B, int32_t T, int32_t F,
+                               float* loss_out, float* grad_out, void* stream);
+int mdm_joint_tracks_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
+                              const float* targets, const float* weights, const float* scene, int32_t K,
+                              const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds, int32_t B,
+                              int32_t T, int32_t F, float scale, int32_t iters, const float* coef, int32_t steps,
+                              const int32_t* t_dev, int32_t t_imm, void* stream);
+int mdm_canvas_tracks_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
+                                const float* std, const float* targets, const float* weights, const float* scene, int32_t K,
+                                const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds, int32_t M,
+                                int32_t F, float* loss_out, float* grad_out, float* workspace, void* stream);
+int mdm_canvas_tracks_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
+                               const float* mean, const float* std, const float* targets, const float* weights,
+                               const float* scene, int32_t K, const float* joint_params, const float* tracks, int32_t Km,
+                               const float* track_bounds, int32_t M, int32_t F, float scale, int32_t iters, const float* coef,
+                               int32_t steps, const int32_t* t_dev, int32_t t_imm, float* workspace, void* stream);
+
 /* ---- long-motion handshakes ---------------------------------------------------------------------
  * In place over the shared canvas frames only.  For every group g < groups, shared frame c < nshared and feature j < F:
  *   v = sum over entries e in [offsets[c], offsets[c+1]) of weights[e] * x[g*group_stride + rows[e]*F + j]

@@ -128,17 +128,23 @@ def check_control_kwargs(kw, shape):
     ``joint_params`` (absent without a scene).  A scene needs ``control_mean`` / ``control_std`` but no targets: ``targets``
     and ``weights`` are then None.  Raises ValueError for joint parameters without a scene, records
     ``motion_scene.check_records`` refuses, joint parameters of another shape, negative or not finite, and a T over the
-    limit of a scene of K primitives.  Host logic."""
+    limit of a scene of K primitives.
+    Tracks: ``control_tracks`` (B, T, Km, 12), per-frame records (``motion_scene.batch_tracks``), with or
+    without a scene (one of no primitives then stands in) and with or without targets, come back as ``tracks`` and
+    ``track_bounds`` (B, T, 4), the balls of the kernels' broad phase, computed here, once.  Raises ValueError for records
+    ``motion_scene.check_tracks`` refuses and another shape.  Host logic."""
     from .motion_control import joints_for_feats, max_frames
     names = ("control_joints", "control_weights", "control_mean", "control_std")
     g, w, mean, std = (kw.get(k) for k in names)
-    scene, jp = kw.get("control_scene"), kw.get("control_joint_params")
+    scene, jp, tracks = kw.get("control_scene"), kw.get("control_joint_params"), kw.get("control_tracks")
+    if tracks is not None and scene is None:
+        scene = torch.zeros((int(shape[0]), 0, L.SCENE_REC))
     given = [k for k, v in zip(names, (g, w, mean, std)) if v is not None]
     extra = [k for k in ("control_scale", "control_iters") if kw.get(k) is not None]
     if jp is not None and scene is None:
         raise ValueError("control_joint_params given without control_scene")
     if not given and scene is None:
-        if extra and not any(kw.get(k) is not None for k in CANVAS_CONTROL_KEYS + CANVAS_SCENE_KEYS):  # canvas control's
+        if extra and not any(kw.get(k) is not None for k in CANVAS_CONTROL_KEYS + CANVAS_SCENE_KEYS + (CANVAS_TRACKS_KEY,)):  # canvas control's
             raise ValueError(f"{' / '.join(extra)} given without control_joints / control_weights / control_mean / control_std")
         return None
     need = names[2:] if scene is not None and g is None and w is None else names
@@ -163,6 +169,12 @@ def check_control_kwargs(kw, shape):
         if not bool(torch.isfinite(jp).all()) or bool((jp < 0).any()):
             raise ValueError("control_joint_params (joint radius, joint weight) must be finite and >= 0")
         out = {"scene": scene, "joint_params": jp}
+    if tracks is not None:
+        from .motion_scene import check_tracks, track_bounds
+        tracks = check_tracks(tracks, "control_tracks")
+        if tracks.dim() != 4 or tuple(tracks.shape[:2]) != (B, T):
+            raise ValueError(f"control_tracks has shape {tuple(tracks.shape)}, expected ({B}, {T}, Km, {L.SCENE_REC})")
+        out.update(tracks=tracks, track_bounds=track_bounds(tracks))
     if T > limit:
         raise ValueError(f"T = {T}: joint control takes at most {limit} frames at F = {F_}"
                          + (f" with {scene.shape[1]} primitives" if scene is not None else ""))
@@ -202,6 +214,7 @@ def check_control_kwargs(kw, shape):
 
 
 CANVAS_SCENE_KEYS = ("canvas_control_scene", "canvas_control_joint_params")
+CANVAS_TRACKS_KEY = "canvas_control_tracks"
 CANVAS_CONTROL_KEYS = ("canvas_control_offsets", "canvas_control_rows", "canvas_control_joints", "canvas_control_weights",
                        "canvas_control_mean", "canvas_control_std")
 
@@ -221,15 +234,20 @@ def check_canvas_control_kwargs(kw, shape):
     Scene constraints: ``canvas_control_scene`` (M, K, 12) records in the canvas frame and
     ``canvas_control_joint_params`` (M, J, 2) come back as ``scene`` / ``joint_params`` (absent without a scene), checked as
     ``check_control_kwargs`` checks its own; with a scene ``canvas_control_joints`` / ``canvas_control_weights`` may both be
-    left out (``targets`` / ``weights`` None).  Host logic."""
+    left out (``targets`` / ``weights`` None).
+    Tracks: ``canvas_control_tracks`` (total, Km, 12), per-frame records in canvas order, with or without a
+    scene and targets, come back as ``tracks`` and ``track_bounds`` (total, 4).  Host logic."""
     from .motion_control import joints_for_feats
     names = CANVAS_CONTROL_KEYS
     vals = [kw.get(k) for k in names]
     scene, jp = (kw.get(k) for k in CANVAS_SCENE_KEYS)
+    tracks = kw.get(CANVAS_TRACKS_KEY)
+    if tracks is not None and scene is None and vals[0] is not None:
+        scene = torch.zeros((max(torch.as_tensor(vals[0]).numel() - 1, 0), 0, L.SCENE_REC))
     given = [k for k, v in zip(names, vals) if v is not None]
     if jp is not None and scene is None:
         raise ValueError("canvas_control_joint_params given without canvas_control_scene")
-    if not given and scene is None:
+    if not given and scene is None and tracks is None:
         return None
     aim = scene is None or vals[2] is not None or vals[3] is not None
     need = names if aim else names[:2] + names[4:]
@@ -238,7 +256,8 @@ def check_canvas_control_kwargs(kw, shape):
                          f"{', '.join(k for k in need if k not in given)}")
     if not aim:
         vals[2] = vals[3] = torch.zeros(0)  # placeholders through the common conversions below
-    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std", "control_scene")):
+    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std", "control_scene",
+                                           "control_tracks")):
         raise ValueError("canvas_control_* and the per-window control_joints / control_weights are exclusive")
     if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
         raise ValueError("canvas joint control does not combine with composed prompts")
@@ -293,6 +312,12 @@ def check_canvas_control_kwargs(kw, shape):
         if not bool(torch.isfinite(jp).all()) or bool((jp < 0).any()):
             raise ValueError("canvas_control_joint_params (joint radius, joint weight) must be finite and >= 0")
         out = {"scene": scene, "joint_params": jp}
+    if tracks is not None:
+        from .motion_scene import check_tracks, track_bounds
+        tracks = check_tracks(tracks, CANVAS_TRACKS_KEY).cpu()
+        if tracks.dim() != 3 or tracks.shape[0] != total:
+            raise ValueError(f"canvas_control_tracks has shape {tuple(tracks.shape)}, expected ({total}, Km, {L.SCENE_REC})")
+        out.update(tracks=tracks, track_bounds=track_bounds(tracks))
     if aim:
         if tuple(g.shape) != (total, J, 3):
             raise ValueError(f"canvas_control_joints has shape {tuple(g.shape)}, expected {(total, J, 3)}")
@@ -343,7 +368,8 @@ def check_handshake_kwargs(kw, shape):
                          f"{', '.join(k for k in names if k not in given)}")
     if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
         raise NotImplementedError("composed prompts over a long motion are not supported yet")
-    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std", "control_scene")):
+    if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std", "control_scene",
+                                           "control_tracks")):
         raise NotImplementedError("per-window joint control over a long motion is not supported: targets need canvas "
                                   "coordinates; give them as canvas_control_* (generate_long(control_joints=))")
     B, T, _ = (int(v) for v in shape)
@@ -523,6 +549,9 @@ class Conditioning:
     one list per sample, with ``scene_joint_radius`` (J,) and ``scene_joint_weights`` (J,) (default 0 and 1); it needs ``mean`` /
     ``std``, acts through the same guidance as ``control_joints`` (``control_scale`` / ``control_iters``) and may come without
     targets (``scene_records`` / ``scene_joint_params``).
+    ``scene_tracks``: obstacles that move, a list of ``motion_scene`` track stacks (``moving_sphere`` ...,
+    ``character_tracks``) shared by all samples or one list per sample (or packed records), over T_max frames; with or without
+    ``scene`` and targets, under the same ``mean`` / ``std``, joint radius and weights and guidance (``track_records``).
     ``edit_joints``: N joint clips (n_i, J, 3) in place of ``edit_motion`` (needs ``mean`` / ``std``), turned into feature rows
     once per call (``edit_rows_from_joints``: ``motion_features.joints_to_motion``) and zero-padded to the mask's
     frames; a clip of n frames gives n - 1 rows, so the mask may keep frames up to n - 2.
@@ -544,7 +573,7 @@ class Conditioning:
                  control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,
                  device=None, to_motion=None, edit_bvh=None, bvh_options=None, init_motion=None, init_joints=None,
                  init_bvh=None, strength=None, latents=None, latent_step=None, scene=None, scene_joint_radius=None,
-                 scene_joint_weights=None):
+                 scene_joint_weights=None, scene_tracks=None):
         self.captions, self.dim_pose = captions, dim_pose
         self.init, self.strength, self.latents, self.latent_step = None, None, None, None
         if init_motion is not None or init_joints is not None or init_bvh is not None:
@@ -590,16 +619,27 @@ class Conditioning:
             self.edit = (k, expand_to(edit_mask, None, k.shape, "edit_mask"))
             if rows is not None:
                 check_joint_edit_mask(self.edit[1], rows)
-        self.control = self._control(control_joints, control_weights, mean, std, dim_pose, scene is not None)
-        self.scene_records = self.scene_joint_params = None
-        if scene is not None:
+        self.control = self._control(control_joints, control_weights, mean, std, dim_pose,
+                                     scene is not None or scene_tracks is not None)
+        self.scene_records = self.scene_joint_params = self.track_records = None
+        if scene is not None or scene_tracks is not None:
             from .motion_control import joints_for_feats
-            from .motion_scene import batch_scene, joint_params
-            self.scene_records = batch_scene(scene, len(captions))
+            from .motion_scene import batch_scene, batch_tracks, joint_params
+            self.scene_records = batch_scene([] if scene is None else scene, len(captions))
             self.scene_joint_params = joint_params(joints_for_feats(dim_pose), scene_joint_radius, scene_joint_weights)
+            if scene_tracks is not None:
+                self.track_records = batch_tracks(scene_tracks, len(captions), self._track_frames(scene_tracks))
         elif scene_joint_radius is not None or scene_joint_weights is not None:
-            raise ValueError("scene_joint_radius / scene_joint_weights go with scene")
+            raise ValueError("scene_joint_radius / scene_joint_weights go with scene or scene_tracks")
         self.control_scale, self.control_iters = control_scale, control_iters
+
+    @staticmethod
+    def _track_frames(tracks):
+        """T_max of ``scene_tracks``: the frames of packed records, the longest stack of lists."""
+        if torch.is_tensor(tracks) or isinstance(tracks, np.ndarray):
+            return int(tracks.shape[-3])
+        flat = [t for v in tracks for t in ([v] if hasattr(v, "ndim") else v)]
+        return max([int(t.shape[0]) for t in flat] + [1])
 
     @staticmethod
     def _compose(captions, prompt_weights, dim_pose):
@@ -682,6 +722,11 @@ class Conditioning:
             rec = self.scene_records[rows]
             out.update(control_scene=rec.to(device),
                        control_joint_params=self.scene_joint_params.to(device).expand(rec.shape[0], -1, -1))
+        if self.track_records is not None:
+            trk = self.track_records[rows]
+            if trk.shape[1] < T:  # a track ends where its stack ends: padding from there on
+                trk = torch.cat([trk, trk.new_zeros((trk.shape[0], T - trk.shape[1]) + tuple(trk.shape[2:]))], dim=1)
+            out.update(control_tracks=trk[:, :T].contiguous().to(device))
         n = len(self.captions_of(rows))
         return {**out, "control_mean": c["mean"].to(device).expand(n, -1), "control_std": c["std"].to(device).expand(n, -1),
                 "control_scale": self.control_scale, "control_iters": self.control_iters}

@@ -53,13 +53,16 @@ __device__ __forceinline__ RotD rot_d(float cw, float sw) {
 // SCENE = true:  the mdm_joint_scene_* calls: the scene's penalty of every joint (scene_sdf.h) joins the loss
 //                and dL/dP, with K primitive records and the joints' (radius, weight) per sample; targets / weights may
 //                then both be null (no target term).
-template <bool GUIDE, bool MASK, bool SCENE>
+// TRACKS = true: the mdm_joint_tracks_* calls, with SCENE: Km more records per frame, read from global memory
+//                at tracks + ((b T + t) Km) SCENE_REC, behind the frame's bounding ball of tbounds (null: never skipped).
+template <bool GUIDE, bool MASK, bool SCENE, bool TRACKS = false>
 __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
     float* x0, float* x, const float* __restrict__ mask, const int* __restrict__ len, const float* __restrict__ mean,
     const float* __restrict__ sd, const float* __restrict__ targets, const float* __restrict__ weights, int T, int F,
     int J, float scale, int iters, const float* __restrict__ coef, int steps, const int* __restrict__ t_ptr, int t_imm,
     float* __restrict__ loss_out, float* __restrict__ grad_out, const float* __restrict__ scene, int K,
-    const float* __restrict__ jparams) {
+    const float* __restrict__ jparams, const float* __restrict__ tracks, int Km, const float* __restrict__ tbounds) {
+  static_assert(SCENE || !TRACKS, "tracks use the scene's joint parameters");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int D = 3 * J + 1;               // steerable columns: root (4) + ric (3 (J - 1))
   const int DS = D | 1;                  // odd LDS row stride
@@ -81,15 +84,26 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
   int n = len[b];
   n = n < 0 ? 0 : (n > T ? T : n);
   const int64_t row0 = (int64_t)b * T * F;
-  const float* tg = targets + (int64_t)b * T * J * 3;
-  const float* wt = weights + (int64_t)b * T * J * 3;
-  const float* mk = MASK ? mask + row0 : nullptr;
+  const float* tg = scene::own<TRACKS>(targets + (int64_t)b * T * J * 3);
+  const float* wt = scene::own<TRACKS>(weights + (int64_t)b * T * J * 3);
+  const float* mk = MASK ? scene::own<TRACKS>(mask + row0) : nullptr;
   const bool aim = !SCENE || targets != nullptr;  // a scene may come without targets
+  grad_out = scene::own<TRACKS && !GUIDE>(grad_out);
+  x0 = scene::own<TRACKS>(x0), x = scene::own<TRACKS && GUIDE>(x);
   float c0 = 0.f;  // read before the iterations: keeps the table's pointers out of the loop's scalar registers
   if (GUIDE) {
     int ts = t_ptr ? *t_ptr : t_imm;
     ts = min(max(ts, 0), steps - 1);
     c0 = coef[4 * ts + 1];
+  }
+
+  // TRACKS: the records and the ball of frame tid, as addresses of this thread's own (in vector registers: the two pointers
+  // would take scalar registers the iteration loop lacks)
+  const float* trk0 = nullptr;
+  const float* bnd0 = nullptr;
+  if (TRACKS) {
+    trk0 = tracks + ((int64_t)b * T + tid) * Km * scene::SCENE_REC;
+    if (tbounds) bnd0 = tbounds + ((int64_t)b * T + tid) * 4;
   }
 
   if (!GUIDE) {  // every entry that cannot receive gradient: frames past the length and the columns past D
@@ -156,6 +170,15 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
       const float* wgt = wt + (int64_t)t * J * 3;
       double lsum = 0.0, sx = 0.0, sz = 0.0, sa = 0.0;
       float g[3];
+      const float* trk = nullptr;  // TRACKS: the frame's records and its ball
+      float ball[4] = {0.f, 0.f, 0.f, INFINITY};
+      if (TRACKS) {
+        trk = trk0 + (int64_t)(t - tid) * Km * scene::SCENE_REC;
+        if (bnd0) {
+          const float4 bb = *reinterpret_cast<const float4*>(bnd0 + (int64_t)(t - tid) * 4);
+          ball[0] = bb.x, ball[1] = bb.y, ball[2] = bb.z, ball[3] = bb.w;
+        }
+      }
       auto dl = [&](int k, float p) {  // dL/dP of one coordinate; W == 0 contributes nothing, whatever G holds
         if (SCENE && !aim) return 0.f;
         const float w = wgt[k];
@@ -167,7 +190,8 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
       {  // joint 0: root XZ and height
         const float py = val(t, 3);
         g[0] = dl(0, qx), g[1] = dl(1, py), g[2] = dl(2, qz);
-        if (SCENE) lsum += scene::penalty(prims, K, jp[0], jp[1], qx, py, qz, g);
+        if (SCENE && !TRACKS) lsum += scene::penalty(prims, K, jp[0], jp[1], qx, py, qz, g);
+        if (TRACKS) lsum += scene::penalty_tracks(prims, K, trk, Km, ball, jp[0], jp[1], qx, py, qz, g);
         sx += g[0], sz += g[2];
         fr[t * FR + GH] = g[1];
       }
@@ -179,7 +203,8 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
         rot_y(c, -s, vx, vz, ox, oz);
         const float px = add(ox, qx), pz = add(oz, qz);
         g[0] = dl(3 * j, px), g[1] = dl(3 * j + 1, vy), g[2] = dl(3 * j + 2, pz);
-        if (SCENE) lsum += scene::penalty(prims, K, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
+        if (SCENE && !TRACKS) lsum += scene::penalty(prims, K, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
+        if (TRACKS) lsum += scene::penalty_tracks(prims, K, trk, Km, ball, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
         if (GUIDE && g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) continue;  // no step: the entries keep their bits
         sx += g[0], sz += g[2];
         sa += 2.0 * ((double)g[0] * (r.e * vz + r.f * vx) + (double)g[2] * (r.f * vz - r.e * vx));
@@ -247,6 +272,8 @@ size_t control_lds_bytes(int T, int J, int prims = -1) {
   return (size_t)2 * DS * 4 + scene + (size_t)T * ((size_t)DS * 4 + CTRL_FRAME_BYTES);
 }
 
+static_assert(scene::MAX_TRACKS == MDM_SCENE_MAX_TRACKS, "scene_sdf.h and mdm_hip.h disagree");
+
 }  // namespace
 }  // namespace mdm
 
@@ -269,7 +296,7 @@ int mdm_joint_loss_grad(const float* x0, const int32_t* length, const float* mea
   const size_t smem = mdm::control_lds_bytes(T, J);
   hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
                      const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J, 0.f, 1,
-                     nullptr, 1, nullptr, 0, loss_out, grad_out, nullptr, 0, nullptr);
+                     nullptr, 1, nullptr, 0, loss_out, grad_out, nullptr, 0, nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -288,11 +315,11 @@ int mdm_joint_guidance(float* x, float* x0, const float* mask, const int32_t* le
   if (mask)
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
                        x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev, t_imm,
-                       nullptr, nullptr, nullptr, 0, nullptr);
+                       nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
                        x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev,
-                       t_imm, nullptr, nullptr, nullptr, 0, nullptr);
+                       t_imm, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -317,7 +344,7 @@ int mdm_joint_scene_loss_grad(const float* x0, const int32_t* length, const floa
   const size_t smem = mdm::control_lds_bytes(T, J, K);
   hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
                      (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params);
+                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -340,11 +367,61 @@ int mdm_joint_scene_guidance(float* x, float* x0, const float* mask, const int32
   if (mask)
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
                        (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params);
+                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
                        (hipStream_t)stream, x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef,
-                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params);
+                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, nullptr, 0, nullptr);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_joint_tracks_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
+                               const float* weights, const float* scene, int32_t K, const float* joint_params,
+                               const float* tracks, int32_t Km, const float* track_bounds, int32_t B, int32_t T, int32_t F,
+                               float* loss_out, float* grad_out, void* stream) {
+  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
+  if (Km == 0)  // no tracks: the launch of mdm_joint_scene_loss_grad
+    return mdm_joint_scene_loss_grad(x0, length, mean, std, targets, weights, scene, K, joint_params, B, T, F, loss_out, grad_out,
+                                     stream);
+  if (!x0 || !length || !mean || !std || !joint_params || !loss_out || !grad_out || !targets != !weights) return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::control_joints(F);
+  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
+  if (B == 0) return MDM_OK;
+  const size_t smem = mdm::control_lds_bytes(T, J, K);
+  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
+                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J,
+                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, tracks, Km, track_bounds);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_joint_tracks_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
+                              const float* targets, const float* weights, const float* scene, int32_t K,
+                              const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds, int32_t B,
+                              int32_t T, int32_t F, float scale, int32_t iters, const float* coef, int32_t steps,
+                              const int32_t* t_dev, int32_t t_imm, void* stream) {
+  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
+  if (Km == 0)  // no tracks: the launch of mdm_joint_scene_guidance
+    return mdm_joint_scene_guidance(x, x0, mask, length, mean, std, targets, weights, scene, K, joint_params, B, T, F, scale,
+                                    iters, coef, steps, t_dev, t_imm, stream);
+  if (!x || !x0 || !length || !mean || !std || !joint_params || !coef || !targets != !weights) return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::control_joints(F);
+  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
+  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
+  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
+  if (B == 0) return MDM_OK;
+  const size_t smem = mdm::control_lds_bytes(T, J, K);
+  if (mask)
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
+                       (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps,
+                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds);
+  else
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
+                       (hipStream_t)stream, x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef,
+                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }

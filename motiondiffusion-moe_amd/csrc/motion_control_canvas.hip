@@ -90,13 +90,17 @@ __device__ __forceinline__ double block_scan(double v, double& carry, double* sl
 // SCENE = true: the mdm_canvas_scene_* calls: the scene's penalty of every joint (scene_sdf.h) joins the loss
 // and dL/dP, with K primitive records and the joints' (radius, weight) per motion, in the canvas frame; targets / weights
 // may then both be null.
-template <bool GUIDE, bool MASK, bool SCENE>
+// TRACKS = true: the mdm_canvas_tracks_* calls, with SCENE: Km more records per canvas frame, read from global
+// memory at tracks + ((motion_offsets[m] + t) Km) SCENE_REC, behind the frame's bounding ball of tbounds (null: never skipped).
+template <bool GUIDE, bool MASK, bool SCENE, bool TRACKS = false>
 __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
     float* x0, float* x, const float* __restrict__ mask, const int* __restrict__ offs, const int* __restrict__ frows,
     const float* __restrict__ mean, const float* __restrict__ sd, const float* __restrict__ targets,
     const float* __restrict__ weights, int F, int J, float scale, int iters, const float* __restrict__ coef, int steps,
     const int* __restrict__ t_ptr, int t_imm, float* loss_out, float* grad_out, float* ws,
-    const float* __restrict__ scene, int K, const float* __restrict__ jparams) {
+    const float* __restrict__ scene, int K, const float* __restrict__ jparams, const float* __restrict__ tracks, int Km,
+    const float* __restrict__ tbounds) {
+  static_assert(SCENE || !TRACKS, "tracks use the scene's joint parameters");
   __shared__ double slots[3][CV_WAVES];  // the wave totals of up to three scans in flight
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int D = 3 * J + 1;          // steerable columns: root (4) + ric (3 (J - 1))
@@ -110,21 +114,32 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
   const int c0 = offs[m];
   const int n = min(max(offs[m + 1] - c0, 0), INT32_MAX / (D + FR));  // offsets inside a motion's state are int32
   const int nblk = (n + CV_THREADS - 1) / CV_THREADS;
-  float* xs = ws + (int64_t)c0 * (D + FR);  // [D][n] the steerable columns of x0, normalised
-  float* fr = xs + D * n;                   // [n][FR] the record (read back by the thread that wrote it):
+  float* xs = scene::own<TRACKS>(ws + (int64_t)c0 * (D + FR));  // [D][n] the steerable columns of x0, normalised
+  float* fr = xs + D * n;  // [n][FR] the record (read back by the thread that wrote it):
   //   CW, SW   cos / sin of the heading of frame t
   //   GX, GZ   sum_j dL/dP[t, j, x] and z
   //   GA       dL/dang[t] of the ric joints
   //   GH       dL/dv[t, 3] (root height)
-  const int* rows = frows + c0;
-  const float* tg = targets + (int64_t)c0 * J * 3;
-  const float* wt = weights + (int64_t)c0 * J * 3;
+  const int* rows = scene::own<TRACKS>(frows + c0);
+  const float* tg = scene::own<TRACKS>(targets + (int64_t)c0 * J * 3);
+  const float* wt = scene::own<TRACKS>(weights + (int64_t)c0 * J * 3);
   const bool aim = !SCENE || targets != nullptr;  // a scene may come without targets
+  mask = scene::own<TRACKS && MASK>(mask), grad_out = scene::own<TRACKS && !GUIDE>(grad_out);
+  x0 = scene::own<TRACKS>(x0), x = scene::own<TRACKS && GUIDE>(x), loss_out = scene::own<TRACKS && !GUIDE>(loss_out);
   float c0t = 0.f;
   if (GUIDE) {
     int ts = t_ptr ? *t_ptr : t_imm;
     ts = min(max(ts, 0), steps - 1);
     c0t = coef[4 * ts + 1];
+  }
+
+  // TRACKS: the records and the ball of canvas frame tid of this motion, as addresses of this thread's own (in vector
+  // registers: the two pointers would take scalar registers the iteration loop lacks)
+  const float* trk0 = nullptr;
+  const float* bnd0 = nullptr;
+  if (TRACKS) {
+    trk0 = tracks + ((int64_t)c0 + tid) * Km * scene::SCENE_REC;
+    if (tbounds) bnd0 = tbounds + ((int64_t)c0 + tid) * 4;
   }
 
   if (!GUIDE) {  // the columns past D never receive gradient
@@ -196,6 +211,15 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
         const float* wgt = wt + (int64_t)t * J * 3;
         double lsum = 0.0, sx = 0.0, sz = 0.0, sa = 0.0;
         float g[3];
+        const float* trk = nullptr;  // TRACKS: the frame's records and its ball
+        float ball[4] = {0.f, 0.f, 0.f, INFINITY};
+        if (TRACKS) {
+          trk = trk0 + (int64_t)(t - tid) * Km * scene::SCENE_REC;
+          if (bnd0) {
+            const float4 bb = *reinterpret_cast<const float4*>(bnd0 + (int64_t)(t - tid) * 4);
+            ball[0] = bb.x, ball[1] = bb.y, ball[2] = bb.z, ball[3] = bb.w;
+          }
+        }
         auto dl = [&](float w, float gk, float p) {  // dL/dP of one coordinate; W == 0 contributes nothing, whatever G holds
           if (w == 0.f) return 0.f;
           const float d = p - gk;
@@ -210,7 +234,8 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
             for (int k = 0; k < 3; ++k) w0[k] = wgt[k], g0[k] = tgt[k];
           }
           g[0] = dl(w0[0], g0[0], qx), g[1] = dl(w0[1], g0[1], py), g[2] = dl(w0[2], g0[2], qz);
-          if (SCENE) lsum += scene::penalty(prims, K, jp[0], jp[1], qx, py, qz, g);
+          if (SCENE && !TRACKS) lsum += scene::penalty(prims, K, jp[0], jp[1], qx, py, qz, g);
+          if (TRACKS) lsum += scene::penalty_tracks(prims, K, trk, Km, ball, jp[0], jp[1], qx, py, qz, g);
         }
         sx += g[0], sz += g[2];
         fr[t * FR + GH] = g[1];
@@ -239,7 +264,8 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
             rot_y(c, -s, vx, vz, rx, rz);
             const float px = add(rx, qx), pz = add(rz, qz);
             g[0] = dl(wv[u][0], gv[u][0], px), g[1] = dl(wv[u][1], gv[u][1], vy), g[2] = dl(wv[u][2], gv[u][2], pz);
-            if (SCENE) lsum += scene::penalty(prims, K, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
+            if (SCENE && !TRACKS) lsum += scene::penalty(prims, K, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
+            if (TRACKS) lsum += scene::penalty_tracks(prims, K, trk, Km, ball, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
             if (GUIDE && g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) continue;  // no step: the entries keep their bits
             sx += g[0], sz += g[2];
             sa += 2.0 * ((double)g[0] * (r.e * vz + r.f * vx) + (double)g[2] * (r.f * vz - r.e * vx));
@@ -366,7 +392,7 @@ int mdm_canvas_joint_loss_grad(const float* x0, const int32_t* motion_offsets, c
   if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
   hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream,
                      const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, nullptr, 0, nullptr);
+                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -387,11 +413,11 @@ int mdm_canvas_joint_guidance(float* x, float* x0, const float* mask, const int3
   if (mask)
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
                        x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale, iters, coef, steps, t_dev,
-                       t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr);
+                       t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
                        x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr);
+                       t_dev, t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -415,7 +441,7 @@ int mdm_canvas_scene_loss_grad(const float* x0, const int32_t* motion_offsets, c
   hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
                      (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std,
                      targets, weights, F, J, 0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, scene, K,
-                     joint_params);
+                     joint_params, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -442,11 +468,71 @@ int mdm_canvas_scene_guidance(float* x, float* x0, const float* mask, const int3
   if (mask)
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
                        (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale,
-                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params);
+                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
                        (hipStream_t)stream, x0, x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
-                       scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params);
+                       scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, nullptr, 0,
+                       nullptr);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_canvas_tracks_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
+                                const float* std, const float* targets, const float* weights, const float* scene, int32_t K,
+                                const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds, int32_t M,
+                                int32_t F, float* loss_out, float* grad_out, float* workspace, void* stream) {
+  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
+  if (Km == 0)  // no tracks: the launch of mdm_canvas_scene_loss_grad
+    return mdm_canvas_scene_loss_grad(x0, motion_offsets, frame_rows, mean, std, targets, weights, scene, K, joint_params, M, F,
+                                      loss_out, grad_out, workspace, stream);
+  if (!x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !loss_out || !grad_out || !workspace ||
+      !targets != !weights)
+    return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::canvas_joints(F);
+  if (J == 0 || M < 0) return MDM_ERR_ARG;
+  if (M == 0) return MDM_OK;
+  const size_t smem = mdm::canvas_lds_bytes(J, K);
+  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
+                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std,
+                     targets, weights, F, J, 0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, scene, K,
+                     joint_params, tracks, Km, track_bounds);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_canvas_tracks_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
+                               const float* mean, const float* std, const float* targets, const float* weights,
+                               const float* scene, int32_t K, const float* joint_params, const float* tracks, int32_t Km,
+                               const float* track_bounds, int32_t M, int32_t F, float scale, int32_t iters, const float* coef,
+                               int32_t steps, const int32_t* t_dev, int32_t t_imm, float* workspace, void* stream) {
+  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
+  if (Km == 0)  // no tracks: the launch of mdm_canvas_scene_guidance
+    return mdm_canvas_scene_guidance(x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, scene, K, joint_params,
+                                     M, F, scale, iters, coef, steps, t_dev, t_imm, workspace, stream);
+  if (!x || !x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !coef || !workspace ||
+      !targets != !weights)
+    return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::canvas_joints(F);
+  if (J == 0 || M < 0) return MDM_ERR_ARG;
+  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
+  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
+  if (M == 0) return MDM_OK;
+  const size_t smem = mdm::canvas_lds_bytes(J, K);
+  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
+  if (mask)
+    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
+                       (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale,
+                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
+                       track_bounds);
+  else
+    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
+                       (hipStream_t)stream, x0, x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
+                       scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
+                       track_bounds);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }

@@ -90,5 +90,49 @@ __device__ __forceinline__ double penalty(const float* prims, int K, float r, fl
   return loss;
 }
 
+// A workgroup-uniform pointer as a value of the thread's own, bit for bit (every lane reads its own lane): the compiler then
+// keeps it in vector registers.  The instantiations with tracks hold the pointers their loops use this way: they have vector
+// registers to spare and not one scalar register.  ON = false: the pointer itself.
+template <bool ON, typename T>
+__device__ __forceinline__ T* own(T* p) {
+  if (!ON) return p;
+  return reinterpret_cast<T*>(__shfl((unsigned long long)p, (int)(threadIdx.x & 63), 64));
+}
+
+// The scene's penalty of one joint with tracks: the K records of `prims` and then the Km records of the
+// joint's frame at `recs` in global memory (16-byte aligned, three 4-float loads a record), in one walk.  bound: the frame's
+// ball (centre, radius) around every live keep-out track inflated by its margin; a joint whose own sphere lies outside it
+// leaves the frame's records out of its walk.  A radius of +inf never does, one of -inf (no live track) always.
+// One loop with one trip count per joint, not a second loop behind nested conditions: each level costs a pair of the
+// scalar registers the control kernels have none to spare of.
+__device__ __forceinline__ double penalty_tracks(const float* prims, int K, const float* recs, int Km, const float bound[4],
+                                                 float r, float u, float px, float py, float pz, float g[3]) {
+  double loss = 0.0;
+  const float dx = px - bound[0], dy = py - bound[1], dz = pz - bound[2];
+  const int trips = K + (sqrtf(dx * dx + dy * dy + dz * dz) > bound[3] + r ? 0 : Km);
+#pragma unroll 1
+  for (int k = 0; k < trips; ++k) {
+    float q[SCENE_REC];
+    if (k < K) {
+#pragma unroll
+      for (int i = 0; i < SCENE_REC; ++i) q[i] = prims[k * SCENE_REC + i];
+    } else {
+      const float4* src = reinterpret_cast<const float4*>(recs + (k - K) * SCENE_REC);
+      const float4 h = src[0], a = src[1], b = src[2];
+      q[0] = h.x, q[1] = h.y, q[2] = h.z, q[3] = h.w, q[4] = a.x, q[5] = a.y, q[6] = a.z, q[7] = a.w;
+      q[8] = b.x, q[9] = b.y, q[10] = b.z, q[11] = b.w;
+    }
+    loss += penalty(q, 1, r, u, px, py, pz, g);  // skips padding and a joint of weight 0
+  }
+  return loss;
+}
+
+// the track arguments of the mdm_*_tracks_* calls: 0 to MAX_TRACKS records a frame; records and bounds are read 16 bytes at a time
+constexpr int MAX_TRACKS = 24;
+inline bool tracks_ok(const float* tracks, int Km, const float* bounds) {
+  if (Km < 0 || Km > MAX_TRACKS || (Km > 0 && !tracks)) return false;
+  return (uintptr_t)tracks % 16 == 0 && (uintptr_t)bounds % 16 == 0;
+}
+
 }  // namespace scene
 }  // namespace mdm

@@ -31,7 +31,8 @@ time-varied and body-part control, negative prompts.
 Joint-position control: ``model_kwargs`` may carry ``control_joints`` (B, T, J, 3) targets, ``control_weights``,
 ``control_mean`` / ``control_std`` (B, F), ``control_scale`` and ``control_iters``, and with or without the targets a scene
 (``control_scene`` (B, K, 12) primitive records, ``control_joint_params`` (B, J, 2), whose penalty joins the
-loss: ``mdm_joint_scene_guidance``); every loop and single step then moves its x0 down the gradient of the weighted
+loss: ``mdm_joint_scene_guidance``; DESIGN.md §25: ``control_tracks`` (B, T, Km, 12), records that differ per frame, moving
+obstacles: ``mdm_joint_tracks_guidance``); every loop and single step then moves its x0 down the gradient of the weighted
 squared distance of ``recover_from_ric(x0 * std + mean)`` to the targets after its update, and x_{t-1} with it (``mdm_joint_guidance``): trajectories, keyframes, end positions.
 
 Long motions: ``model_kwargs`` may carry handshake tables (``handshake_offsets``, ``handshake_rows``,
@@ -717,6 +718,10 @@ class _StepRunner:
                 K = int(ctl["scene"].shape[1])
                 self.ctl.update(K=K, scene=f32(ctl["scene"], (B, K, L.SCENE_REC)) if K else None,
                                 joint_params=f32(ctl["joint_params"], (B, J, 2)))
+            if "tracks" in ctl and ctl["tracks"].shape[2]:  # tracks: per-frame records and their balls
+                Km = int(ctl["tracks"].shape[2])
+                self.ctl.update(Km=Km, tracks=f32(ctl["tracks"], (B, T, Km, L.SCENE_REC)),
+                                track_bounds=f32(ctl["track_bounds"], (B, T, 4)))
         # long motions: the handshake tables of the overlapping windows
         hs = check_handshake_kwargs(kw, shape)
         self.hs = None if hs is None else {k: v.to(dev).contiguous() if torch.is_tensor(v) else v for k, v in hs.items()}
@@ -735,6 +740,10 @@ class _StepRunner:
                 K = int(cc["scene"].shape[1])
                 self.cctl.update(K=K, scene=f32(cc["scene"], (cc["M"], K, L.SCENE_REC)) if K else None,
                                  joint_params=f32(cc["joint_params"], (cc["M"], J, 2)))
+            if "tracks" in cc and cc["tracks"].shape[1]:
+                Km = int(cc["tracks"].shape[1])
+                self.cctl.update(Km=Km, tracks=f32(cc["tracks"], (tot, Km, L.SCENE_REC)),
+                                 track_bounds=f32(cc["track_bounds"], (tot, 4)))
         # few-step modes (and every mode when editing, composing or controlling): per-step coefficients of the fused update;
         # self.x0 doubles as x0_prev (updated in place)
         table = self.known is not None or self.cw is not None or self.ctl is not None or self.cctl is not None
@@ -825,14 +834,19 @@ class _StepRunner:
         if self.ctl is not None:
             c = self.ctl
             scene = (p(c["scene"]), c["K"], p(c["joint_params"])) if "K" in c else ()
-            guide = ("mdm_joint_scene_guidance" if scene else "mdm_joint_guidance",
+            if "Km" in c:  # with tracks
+                scene += (p(c["tracks"]), c["Km"], p(c["track_bounds"]))
+            guide = ("mdm_joint_tracks_guidance" if "Km" in c else "mdm_joint_scene_guidance" if scene else "mdm_joint_guidance",
                      (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"])) + scene
                      + (self.B, self.T, self.Fe, c["scale"], c["iters"], p(self.coef)) + clock)
         self._guide_canvas = None  # the entry and arguments of the canvas guidance (None without canvas control)
         if self.cctl is not None:
             c = self.cctl
             scene = (p(c["scene"]), c["K"], p(c["joint_params"])) if "K" in c else ()
-            self._guide_canvas = ("mdm_canvas_scene_guidance" if scene else "mdm_canvas_joint_guidance",
+            if "Km" in c:
+                scene += (p(c["tracks"]), c["Km"], p(c["track_bounds"]))
+            self._guide_canvas = ("mdm_canvas_tracks_guidance" if "Km" in c else
+                                  "mdm_canvas_scene_guidance" if scene else "mdm_canvas_joint_guidance",
                                   (x, x0, p(self.mask), p(c["offsets"]), p(c["rows"]), p(c["mean"]), p(c["std"]),
                                    p(c["targets"]), p(c["weights"])) + scene
                                   + (c["M"], self.Fe, c["scale"], c["iters"], p(self.coef)) + clock + (p(c["ws"]),))

@@ -180,7 +180,8 @@ def batch_control_tables(plans, idx, T: int, joints, weights) -> Dict[str, torch
 
 
 def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, control_scale=None, control_iters=None,
-                   mean=None, std=None, device=None, scene=None, scene_joint_radius=None, scene_joint_weights=None):
+                   mean=None, std=None, device=None, scene=None, scene_joint_radius=None, scene_joint_weights=None,
+                   scene_tracks=None):
     """The joint-control inputs of ``DDPMTrainer.generate_long`` (described there), checked once for the call:
     one (C_i, J, 3) target array per motion of ``plans`` in canvas frames and weights broadcastable to it (aligned on the
     frame dim), with the dataset's ``mean`` / ``std``.  Returns ``tables(idx, T)``: the ``canvas_control_*`` model kwargs
@@ -189,10 +190,13 @@ def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, c
     reverse, a scale or iteration count without them, missing mean / std, not one entry per motion, and canvas shapes.
     ``scene``: one list of ``motion_scene`` primitives per motion, in its canvas frame, with
     ``scene_joint_radius`` / ``scene_joint_weights`` (J,); it may come without targets, and adds ``canvas_control_scene`` /
-    ``canvas_control_joint_params`` to the tables."""
+    ``canvas_control_joint_params`` to the tables.  ``scene_tracks``: one list of ``motion_scene`` track stacks
+    per motion, over its canvas frames, with or without ``scene`` and targets; it adds ``canvas_control_tracks``."""
     aim = control_joints is not None or control_weights is not None
-    if scene is None and (scene_joint_radius is not None or scene_joint_weights is not None):
-        raise ValueError("scene_joint_radius / scene_joint_weights go with scene")
+    if scene is None and scene_tracks is None and (scene_joint_radius is not None or scene_joint_weights is not None):
+        raise ValueError("scene_joint_radius / scene_joint_weights go with scene or scene_tracks")
+    if scene is None and scene_tracks is not None:
+        scene = [[] for _ in plans]
     if not aim and scene is None:
         if control_scale is not None or control_iters is not None:
             raise ValueError("control_scale / control_iters given without control_joints / control_weights")
@@ -216,6 +220,13 @@ def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, c
             raise ValueError(f"scene must hold one list of primitives per motion ({N}), in its canvas frame")
         records = batch_scene(scene, N)
         params = joint_params(J, scene_joint_radius, scene_joint_weights)
+    tracks = None
+    if scene_tracks is not None:
+        from .motion_scene import _is_stack, pack_tracks
+        if torch.is_tensor(scene_tracks) or isinstance(scene_tracks, np.ndarray) or len(scene_tracks) != N or any(
+                t is None or _is_stack(t) for t in scene_tracks):
+            raise ValueError(f"scene_tracks must hold one list of track stacks per motion ({N}), over its canvas frames")
+        tracks = [pack_tracks(t, plans[i][3]) for i, t in enumerate(scene_tracks)]
     joints, weights = [], []
     for i, (g, w) in enumerate(zip(control_joints, control_weights) if aim else ()):
         C = plans[i][3]
@@ -239,6 +250,10 @@ def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, c
         kw = batch_control_tables(plans, idx, T, joints if aim else None, weights)
         if records is not None:
             kw.update(canvas_control_scene=records[list(idx)], canvas_control_joint_params=params.expand(len(idx), -1, -1))
+        if tracks is not None:
+            Km = max(tracks[i].shape[1] for i in idx)
+            kw.update(canvas_control_tracks=torch.cat([torch.nn.functional.pad(tracks[i], (0, 0, 0, Km - tracks[i].shape[1]))
+                                                       for i in idx]).contiguous())
         kw.update(canvas_control_mean=ms[0].expand(len(idx), -1), canvas_control_std=ms[1].expand(len(idx), -1))
         kw = {k: v.to(device) for k, v in kw.items()}
         kw.update({k: v for k, v in (("control_scale", control_scale), ("control_iters", control_iters)) if v is not None})

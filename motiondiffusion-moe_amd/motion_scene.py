@@ -11,7 +11,19 @@ radius r_j >= 0 and a weight u_j >= 0 (0 exempts it).  The guidance of joint con
 ``sphere``, ``capsule``, ``box``, ``half_space`` and ``floor`` make primitives, ``pack_scene`` turns a list of them into the
 (K, 12) float32 records the kernels read (kind, sigma, weight, margin, eight parameters; a box's yaw is stored as its cosine
 and sine).  ``scene_loss_grad`` / ``canvas_scene_loss_grad`` run the loss and its gradient on the device
-(``mdm_joint_scene_loss_grad`` / ``mdm_canvas_scene_loss_grad``); ``penetration`` checks a result in plain torch."""
+(``mdm_joint_scene_loss_grad`` / ``mdm_canvas_scene_loss_grad``); ``penetration`` checks a result in plain torch.
+
+Tracks are primitives that move: a track is a (T, 12) stack of records, one per frame (kind 0: absent in that
+frame), made by ``moving_sphere`` / ``moving_capsule`` / ``moving_box`` / ``moving_half_space`` or, for a generated character as
+an obstacle, ``character_tracks`` (one capsule per bone; ``to_world`` / ``to_local`` / ``records_to_local`` move joints and
+records between a character's own frame and the world).  At most ``MAX_TRACKS`` per sample; ``pack_tracks`` / ``batch_tracks``
+give the (T, Km, 12) / (N, T, Km, 12) records of the kernels and ``track_bounds`` the per-frame balls of their broad phase.
+They add
+
+    L_tracks,b = sum_{t < len_b} sum_j u_j sum_k a_tk max(0, m_tk + r_j - sigma_tk d(R[t, k]; P[t, j]))^2
+
+to the loss; the records are data (no gradient reaches the obstacle's own motion).  ``scene_loss_grad`` /
+``canvas_scene_loss_grad`` / ``penetration`` take ``tracks=``."""
 from __future__ import annotations
 
 import math
@@ -22,7 +34,7 @@ import torch
 from . import _lib as L
 from .motion_control import LDS_BYTES, _rows, joints_for_feats, steerable_columns
 
-MAX_PRIMS, REC = L.SCENE_MAX_PRIMS, L.SCENE_REC
+MAX_PRIMS, REC, MAX_TRACKS = L.SCENE_MAX_PRIMS, L.SCENE_REC, L.SCENE_MAX_TRACKS
 PAD, SPHERE, CAPSULE, BOX, HALF_SPACE = 0, 1, 2, 3, 4
 
 
@@ -94,14 +106,16 @@ def floor(height=0.0, *, margin=0.0, weight=1.0):
     return half_space((0.0, 1.0, 0.0), height, margin=margin, weight=weight)
 
 
-def check_records(rec, name="scene"):
-    """``rec`` (..., K, REC), packed records, as a float32 tensor; ValueError for more than MAX_PRIMS primitives, non-finite
-    values, an unknown kind, a sign other than +-1, a weight < 0, a radius or half extent <= 0 and a zero normal."""
+def check_records(rec, name="scene", limit=MAX_PRIMS):
+    """``rec`` (..., K, REC), packed records, as a float32 tensor; ValueError for more than ``limit`` primitives (MAX_PRIMS of a
+    scene, MAX_TRACKS of a frame's tracks), non-finite values, an unknown kind, a sign other than +-1, a weight < 0, a radius or
+    half extent <= 0 and a zero normal."""
     rec = torch.as_tensor(rec)
     if rec.dim() < 2 or rec.shape[-1] != REC or not rec.is_floating_point():
         raise ValueError(f"{name} of shape {tuple(rec.shape)} must be floating point (..., K, {REC})")
-    if rec.shape[-2] > MAX_PRIMS:
-        raise ValueError(f"{name} has {rec.shape[-2]} primitives: a scene takes at most {MAX_PRIMS}")
+    if rec.shape[-2] > limit:
+        raise ValueError(f"{name} has {rec.shape[-2]} primitives: " + (f"a scene takes at most {MAX_PRIMS}" if limit == MAX_PRIMS
+                                                                      else f"at most {limit} are allowed"))
     r = rec.detach().to("cpu", torch.float32).reshape(-1, REC)
     if not bool(torch.isfinite(r).all()):
         raise ValueError(f"{name} has non-finite values")
@@ -216,33 +230,335 @@ def signed_distances(p: torch.Tensor, records: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def penetration(joints, lengths, scene, joint_radius=None):
+def penetration(joints, lengths, scene, joint_radius=None, tracks=None):
     """How far a result violates a scene, per sample: ``(depth (B,), share (B,))``.  ``joints`` (B, T, J, 3) joint positions
     (``recover_from_ric`` units) with ``lengths`` (B,), ``scene`` as in ``DDPMTrainer.generate`` (one list, or one per
     sample), ``joint_radius`` (J,) or None.  ``depth``: the deepest penetration of any joint's sphere into any primitive
     (out of a keep-in one), max(0, r_j - sigma_k d_k), margins not counted; ``share``: the share of the sample's frames in
-    which any joint is inside a margin (m_k + r_j - sigma_k d_k > 0).  Primitives of weight 0 are ignored.  Plain torch ops
-    on the device the joints are on."""
+    which any joint is inside a margin (m_k + r_j - sigma_k d_k > 0).  Primitives of weight 0 are ignored.  ``tracks``
+    (as ``batch_tracks`` takes them; ``scene`` may then be None): the moving primitives of §25 count as well, every frame
+    against its own records.  Plain torch ops on the device the joints are on."""
     P = torch.as_tensor(joints)
     if P.dim() != 4 or P.shape[-1] != 3:
         raise ValueError(f"joints of shape {tuple(P.shape)} must be (B, T, J, 3)")
     B, T, J, _ = P.shape
-    rec = batch_scene(scene, B)
+    rec = batch_scene([] if scene is None else scene, B)
     r = joint_params(J, joint_radius)[:, 0].to(P.device, P.dtype)
     ln = torch.as_tensor(lengths).flatten().to(P.device)
     if ln.numel() != B:
         raise ValueError(f"lengths must hold {B} entries")
+    trk = None if tracks is None else batch_tracks(tracks, B, T, ln.cpu())
     depth, share = P.new_zeros(B), P.new_zeros(B)
     for b in range(B):
         n = min(max(int(ln[b]), 0), T)
         live = rec[b][(rec[b][:, 0] != PAD) & (rec[b][:, 2] > 0)]
-        if n == 0 or live.shape[0] == 0:
+        if n == 0:
             continue
-        q = live.to(P.device, P.dtype)
-        sd = q[:, 1] * signed_distances(P[b, :n], live)  # (n, J, K)
-        depth[b] = (r[None, :, None] - sd).clamp(min=0).max()
-        share[b] = ((q[:, 3] + r[None, :, None] - sd) > 0).any(-1).any(-1).to(P.dtype).mean()
+        deep, inside = P.new_zeros(()), torch.zeros(n, dtype=torch.bool, device=P.device)
+        if live.shape[0]:
+            q = live.to(P.device, P.dtype)
+            sd = q[:, 1] * signed_distances(P[b, :n], live)  # (n, J, K)
+            deep = (r[None, :, None] - sd).clamp(min=0).max()
+            inside = ((q[:, 3] + r[None, :, None] - sd) > 0).any(-1).any(-1)
+        if trk is not None and trk.shape[2]:
+            q = trk[b, :n].to(P.device, P.dtype)[:, None]  # (n, 1, Km, REC)
+            on = (q[..., 0] != PAD) & (q[..., 2] > 0)
+            sd = q[..., 1] * track_distances(P[b, :n], trk[b, :n])  # (n, J, Km)
+            deep = torch.maximum(deep, torch.where(on, (r[None, :, None] - sd).clamp(min=0), torch.zeros_like(sd)).max())
+            inside = inside | (on & ((q[..., 3] + r[None, :, None] - sd) > 0)).any(-1).any(-1)
+        depth[b], share[b] = deep, inside.to(P.dtype).mean()
     return depth, share
+
+
+# ---- tracks (DESIGN.md §25): primitives whose record differs from frame to frame ----------------------------------------
+def _per_frame(cols, active):
+    """``cols``: (value, width, name) per parameter, each a (width,) vector (a scalar for width 1) or (T, width) / (T,)
+    per frame; ``active`` None or (T,) bool.  Returns T and the (T, width) float64 arrays.  ValueError for non-finite values,
+    other shapes, per-frame lengths that disagree and no per-frame argument at all."""
+    arrs, T = [], None
+    if active is not None:
+        active = np.asarray(active)
+        if active.ndim != 1 or active.dtype != np.bool_:
+            raise ValueError(f"active must be a (T,) bool array, not {active.dtype} of shape {active.shape}")
+        T = active.shape[0]
+    for v, n, name in cols:
+        a = np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+        if not np.isfinite(a).all():
+            raise ValueError(f"{name} has non-finite values")
+        if a.ndim == 0 and n == 1:
+            a = a.reshape(1)
+        if a.ndim == 1 and n == 1 and a.shape[0] != 1:
+            a = a[:, None]  # (T,) -> (T, 1)
+        if a.ndim == 1 and a.shape[0] == n:
+            arrs.append(a)
+            continue
+        if a.ndim != 2 or a.shape[1] != n:
+            raise ValueError(f"{name} of shape {np.shape(v)} must be ({n},) or (T, {n})" if n > 1 else
+                             f"{name} of shape {np.shape(v)} must be a scalar or (T,)")
+        if T is not None and a.shape[0] != T:
+            raise ValueError(f"per-frame shapes disagree: {name} has {a.shape[0]} frames, another argument {T}")
+        T = a.shape[0]
+        arrs.append(a)
+    if T is None:
+        raise ValueError("a moving primitive needs a per-frame argument (T, .) or active= (T,)")
+    return T, [np.broadcast_to(a, (T, a.shape[-1])) for a in arrs]
+
+
+def _track(kind, cols, margin, weight, inside, active):
+    """The (T, REC) float64 record stack of one track; a frame with ``active`` False is padding (kind 0, all zeros)."""
+    T, arrs = _per_frame(list(cols) + [(margin, 1, "margin"), (weight, 1, "weight")], active)
+    margin, weight = arrs[-2][:, 0], arrs[-1][:, 0]
+    if (weight < 0).any():
+        raise ValueError("weight must be finite and >= 0")
+    rec = np.zeros((T, REC))
+    rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = kind, -1.0 if inside else 1.0, weight, margin
+    params = np.concatenate(arrs[:-2], axis=1)
+    rec[:, 4:4 + params.shape[1]] = params
+    if active is not None:
+        rec[~np.asarray(active)] = 0.0
+    return torch.from_numpy(rec)
+
+
+def _all_positive(a, name):
+    if (a <= 0).any():
+        raise ValueError(f"{name} must be > 0")
+
+
+def moving_sphere(centers, radius, *, margin=0.0, weight=1.0, inside=False, active=None):
+    """A sphere whose centre (T, 3) (and radius, a scalar or (T,)) changes with the frame: the (T, REC) record stack of one
+    track.  ``margin`` / ``weight`` (scalars or (T,)) / ``inside`` as ``sphere``; ``active`` (T,) bool: False leaves the
+    track out of that frame."""
+    T, (c, r) = _per_frame([(centers, 3, "centers"), (radius, 1, "radius")], active)
+    _all_positive(r, "radius")
+    return _track(SPHERE, [(c, 3, "centers"), (r, 1, "radius")], margin, weight, inside, active)
+
+
+def moving_capsule(a, b, radius, *, margin=0.0, weight=1.0, inside=False, active=None):
+    """A capsule with ends ``a`` and ``b`` (T, 3) per frame (a limb, a swinging bar)."""
+    T, (pa, pb, r) = _per_frame([(a, 3, "a"), (b, 3, "b"), (radius, 1, "radius")], active)
+    _all_positive(r, "radius")
+    return _track(CAPSULE, [(pa, 3, "a"), (pb, 3, "b"), (r, 1, "radius")], margin, weight, inside, active)
+
+
+def moving_box(centers, half_extents, yaw=0.0, *, margin=0.0, weight=1.0, inside=False, active=None):
+    """A box with centre (T, 3), half extents (3,) or (T, 3) and yaw (radians about Y; a scalar or (T,)) per frame."""
+    T, (c, h, y) = _per_frame([(centers, 3, "centers"), (half_extents, 3, "half_extents"), (yaw, 1, "yaw")], active)
+    _all_positive(h, "every half extent")
+    return _track(BOX, [(c, 3, "centers"), (h, 3, "half_extents"), (np.cos(y), 1, "yaw"), (np.sin(y), 1, "yaw")], margin, weight,
+                  inside, active)
+
+
+def moving_half_space(normals, offsets, *, margin=0.0, weight=1.0, inside=False, active=None):
+    """A half-space with normal (3,) or (T, 3) (normalised here) and offset (a scalar or (T,)) per frame: a rising floor, a
+    closing wall."""
+    T, (n, o) = _per_frame([(normals, 3, "normals"), (offsets, 1, "offsets")], active)
+    length = np.linalg.norm(n, axis=1, keepdims=True)
+    if (length == 0).any():
+        raise ValueError("normal must not be zero")
+    return _track(HALF_SPACE, [(n / length, 3, "normals"), (o, 1, "offsets")], margin, weight, inside, active)
+
+
+def check_tracks(rec, name="tracks"):
+    """``rec`` (..., T, Km, REC), packed track records, as a float32 tensor, checked as ``check_records`` checks a scene's, with
+    at most MAX_TRACKS of them a frame."""
+    rec = torch.as_tensor(rec)
+    if rec.dim() < 3:
+        raise ValueError(f"{name} of shape {tuple(rec.shape)} must be (..., T, Km, {REC})")
+    return check_records(rec, name, MAX_TRACKS)
+
+
+def pack_tracks(tracks, T: int) -> torch.Tensor:
+    """A list of track stacks (Tk, REC) as the (T, Km, REC) float32 records of the kernels (CPU): the first T frames of
+    every track; frames past a track's own length are padding.  ValueError for more than MAX_TRACKS."""
+    tracks = list(tracks)
+    if len(tracks) > MAX_TRACKS:
+        raise ValueError(f"{len(tracks)} tracks: a sample takes at most {MAX_TRACKS}")
+    out = torch.zeros((int(T), len(tracks), REC), dtype=torch.float64)
+    for k, tr in enumerate(tracks):
+        tr = torch.as_tensor(tr)
+        if tr.dim() != 2 or tr.shape[1] != REC:
+            raise ValueError(f"track {k} of shape {tuple(tr.shape)} must be a (T, {REC}) record stack (moving_sphere / "
+                             "moving_capsule / moving_box / moving_half_space / character_tracks)")
+        n = min(int(T), tr.shape[0])
+        out[:n, k] = tr[:n].to(torch.float64)
+    return check_tracks(out.to(torch.float32))
+
+
+def canvas_tracks(tracks, motion_offsets) -> torch.Tensor:
+    """``tracks``, one list of track stacks per motion in that motion's canvas frames (or packed (total, Km, REC) records),
+    as the (total, Km, REC) float32 records in canvas order of the canvas kernels: Km the longest list, the rest padding.
+    ValueError for packed records that are not ``total`` frames long."""
+    off = [int(v) for v in torch.as_tensor(motion_offsets).flatten().tolist()]
+    M, total = len(off) - 1, off[-1]
+    if torch.is_tensor(tracks) or isinstance(tracks, np.ndarray):
+        rec = check_tracks(tracks)
+        if rec.dim() != 3 or rec.shape[0] != total:
+            raise ValueError(f"tracks of shape {tuple(rec.shape)} must be ({total}, Km, {REC}) in canvas order: shorter or longer "
+                             "than the motions' lengths")
+        return rec.contiguous()
+    tracks = list(tracks)
+    if len(tracks) != M or any(_is_stack(t) for t in tracks):
+        raise ValueError(f"tracks must hold one list of track stacks per motion ({M}), in its canvas frames")
+    packed = [pack_tracks(t, off[m + 1] - off[m]) for m, t in enumerate(tracks)]
+    out = torch.zeros((total, max([p.shape[1] for p in packed] + [0]), REC))
+    for m, p in enumerate(packed):
+        out[off[m]:off[m + 1], :p.shape[1]] = p
+    return out
+
+
+def _is_stack(v):
+    return (torch.is_tensor(v) or isinstance(v, np.ndarray)) and v.ndim == 2
+
+
+def batch_tracks(tracks, N: int, T: int, lengths=None) -> torch.Tensor:
+    """``tracks``, one list of track stacks shared by N samples or one list per sample (or packed records (Tt, Km, REC) /
+    (N, Tt, Km, REC)), as (N, T, Km, REC) float32 records: Km the longest list, shorter ones and frames past a track's own
+    length padded with kind 0, frames past T dropped.  ValueError for packed records with fewer frames than a sample's
+    ``lengths`` entry (T without ``lengths``)."""
+    T = int(T)
+    if torch.is_tensor(tracks) or isinstance(tracks, np.ndarray):
+        rec = check_tracks(tracks)
+        if rec.dim() == 3:
+            rec = rec[None].expand(N, -1, -1, -1)
+        if rec.dim() != 4 or rec.shape[0] != N:
+            raise ValueError(f"tracks of shape {tuple(rec.shape)} must be (T, Km, {REC}) or ({N}, T, Km, {REC})")
+        need = T if lengths is None else min(T, max([int(v) for v in torch.as_tensor(lengths).flatten().tolist()] + [0]))
+        if rec.shape[1] < need:
+            raise ValueError(f"tracks hold {rec.shape[1]} frames: shorter than a sample's length {need}")
+        out = torch.zeros((N, T, rec.shape[2], REC))
+        n = min(T, rec.shape[1])
+        out[:, :n] = rec[:, :n]
+        return out
+    tracks = list(tracks)
+    if all(_is_stack(t) for t in tracks):
+        return pack_tracks(tracks, T)[None].expand(N, -1, -1, -1).contiguous()
+    if len(tracks) != N or any(_is_stack(t) for t in tracks):
+        raise ValueError(f"tracks must be one list of track stacks, or one list per sample ({N}), not {len(tracks)} entries")
+    packed = [pack_tracks(t, T) for t in tracks]
+    out = torch.zeros((N, T, max(p.shape[1] for p in packed), REC))
+    for i, p in enumerate(packed):
+        out[i, :, :p.shape[1]] = p
+    return out
+
+
+BOUND_REL, BOUND_ABS = 1e-3, 1e-3  # the broad phase's ball is inflated by this share of its radius plus this many metres
+
+
+def track_bounds(records) -> torch.Tensor:
+    """The broad phase of the kernels: for packed track records (..., T, Km, REC) the (..., T, 4) float32 balls (centre,
+    radius) that contain, per frame, every keep-out track of weight > 0 inflated by its margin, computed in float64 and
+    inflated by BOUND_REL of the radius plus BOUND_ABS metres, so that float32 rounding in the kernel cannot skip a record
+    that penalises.  A joint of radius r farther than radius + r from the centre touches none of the frame's tracks.  Radius
+    +inf for a frame with a half-space or a keep-in track of weight > 0 (never skipped), -inf for a frame without a live
+    track (always skipped)."""
+    rec = torch.as_tensor(records).detach().cpu().to(torch.float64)
+    if rec.dim() < 3 or rec.shape[-1] != REC:
+        raise ValueError(f"records of shape {tuple(rec.shape)} must be (..., T, Km, {REC})")
+    lead, Km = rec.shape[:-2], rec.shape[-2]
+    q = rec.reshape(math.prod(lead), Km, REC).numpy()
+    kind, live = q[..., 0], (q[..., 0] != PAD) & (q[..., 2] > 0)
+    m = np.maximum(q[..., 3], 0.0)
+    centre = np.where((kind == CAPSULE)[..., None], 0.5 * (q[..., 4:7] + q[..., 7:10]), q[..., 4:7])
+    reach = np.where(kind == SPHERE, q[..., 7], np.where(kind == CAPSULE, 0.5 * np.linalg.norm(q[..., 7:10] - q[..., 4:7], axis=-1)
+                                                         + q[..., 10], np.linalg.norm(q[..., 7:10], axis=-1))) + m
+    count = live.sum(-1)
+    mid = (centre * live[..., None]).sum(1) / np.maximum(count, 1)[:, None]
+    mid = mid.astype(np.float32).astype(np.float64)  # the centre the kernel reads
+    far = np.where(live, np.linalg.norm(centre - mid[:, None], axis=-1) + reach, 0.0).max(-1) if Km else np.zeros(q.shape[0])
+    radius = far * (1.0 + BOUND_REL) + BOUND_ABS
+    unbounded = (live & ((kind == HALF_SPACE) | (q[..., 1] < 0))).any(-1)
+    radius = np.where(unbounded, np.inf, np.where(count > 0, radius, -np.inf))
+    out = np.concatenate([np.where((count > 0)[:, None], mid, 0.0), radius[:, None]], axis=1)
+    return torch.from_numpy(out).to(torch.float32).reshape(*lead, 4)
+
+
+def _rot_y(p, yaw, inverse=False):
+    """R_y(yaw) p (R_y(-yaw) p with ``inverse``) of points (..., 3): x' = cos x + sin z, z' = -sin x + cos z; in p's dtype."""
+    yaw = -float(yaw) if inverse else float(yaw)
+    c, s = math.cos(yaw), math.sin(yaw)
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    return torch.stack([c * x + s * z, y, -s * x + c * z], -1)
+
+
+def _shift(p, position):
+    x, z = (float(v) for v in position)
+    return torch.tensor([x, 0.0, z], dtype=p.dtype, device=p.device)
+
+
+def to_world(joints, position, yaw):
+    """Joints (..., 3) of a character's own frame (``recover_from_ric``'s: it starts at the origin with heading 0) in the
+    world: p_world = R_y(yaw) p + (x, 0, z) with ``position`` = (x, z).  In the joints' dtype, on their device."""
+    p = torch.as_tensor(joints)
+    return _rot_y(p, yaw) + _shift(p, position)
+
+
+def to_local(joints, position, yaw):
+    """The inverse of ``to_world``: p = R_y(-yaw) (p_world - (x, 0, z))."""
+    p = torch.as_tensor(joints)
+    return _rot_y(p - _shift(p, position), yaw, inverse=True)
+
+
+def records_to_local(records, position, yaw) -> torch.Tensor:
+    """Packed records (..., REC) given in the world, in the frame of a character at ``position`` = (x, z) turned by ``yaw``
+    (``to_local`` of the primitives): centres and ends moved, a box's yaw reduced by ``yaw``, a half-space's normal turned
+    and its offset reduced by n . (x, 0, z).  Float64; padding stays padding."""
+    q = torch.as_tensor(records).detach().cpu().to(torch.float64).clone()
+    if q.shape[-1] != REC:
+        raise ValueError(f"records of shape {tuple(q.shape)} must be (..., {REC})")
+    kind = q[..., 0]
+    point = (kind == SPHERE) | (kind == CAPSULE) | (kind == BOX)
+    cap, box_, half = kind == CAPSULE, kind == BOX, kind == HALF_SPACE
+    a, b = to_local(q[..., 4:7], position, yaw), to_local(q[..., 7:10], position, yaw)
+    n = _rot_y(q[..., 4:7], yaw, inverse=True)
+    off = q[..., 7] - (q[..., 4:7] * _shift(q, position)).sum(-1)
+    c, s, cy, sy = q[..., 10].clone(), q[..., 11].clone(), math.cos(float(yaw)), math.sin(float(yaw))
+    q[..., 4:7] = torch.where(point[..., None], a, torch.where(half[..., None], n, q[..., 4:7]))
+    q[..., 7:10] = torch.where(cap[..., None], b, q[..., 7:10])
+    q[..., 7] = torch.where(half, off, q[..., 7])
+    q[..., 10] = torch.where(box_, c * cy + s * sy, q[..., 10])
+    q[..., 11] = torch.where(box_, s * cy - c * sy, q[..., 11])
+    return q
+
+
+def character_tracks(joints, radius=0.08, *, margin=0.0, weight=1.0, bones=None):
+    """A generated character as an obstacle: one capsule track of ``radius`` along every bone of ``joints`` (T, J, 3), 21 for
+    the 22-joint skeleton, ends at the joints.  ``bones``: (parent, child) pairs; by default the tree of the skeleton with J
+    joints in ``motion_features.SKELETONS`` (the one forward kinematics walks).  ``margin`` / ``weight`` as ``capsule``."""
+    P = torch.as_tensor(joints).detach().cpu().to(torch.float64)
+    if P.dim() != 3 or P.shape[-1] != 3:
+        raise ValueError(f"joints of shape {tuple(P.shape)} must be (T, J, 3)")
+    if bones is None:
+        from .motion_features import SKELETONS
+        trees = {sk.joints: sk.parents for sk in SKELETONS.values()}
+        if P.shape[1] not in trees:
+            raise ValueError(f"no skeleton with {P.shape[1]} joints: give bones= as (parent, child) pairs")
+        bones = [(p, c) for c, p in enumerate(trees[P.shape[1]]) if p >= 0]
+    bones = [(int(p), int(c)) for p, c in bones]
+    if any(not (0 <= p < P.shape[1] and 0 <= c < P.shape[1]) for p, c in bones):
+        raise ValueError(f"bones must name joints in [0, {P.shape[1]})")
+    return [moving_capsule(P[:, p], P[:, c], radius, margin=margin, weight=weight) for p, c in bones]
+
+
+def track_distances(p: torch.Tensor, records: torch.Tensor) -> torch.Tensor:
+    """d(R[t, k]; p[t, j]) of points ``p`` (T, J, 3) to the per-frame records (T, Km, REC): (T, J, Km) in p's dtype on p's
+    device; 0 for padding.  Plain torch ops, every kind evaluated on every record and selected by the record's kind."""
+    q = records.detach().to(p.device, p.dtype)[:, None]  # (T, 1, Km, REC)
+    x = p[:, :, None]  # (T, J, 1, 3)
+    kind = q[..., 0]
+    d_sphere = (x - q[..., 4:7]).norm(dim=-1) - q[..., 7]
+    e, v = q[..., 7:10] - q[..., 4:7], x - q[..., 4:7]
+    den = (e * e).sum(-1)
+    h = torch.where(den > 0, (v * e).sum(-1) / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den)).clamp(0, 1)
+    d_capsule = (v - h[..., None] * e).norm(dim=-1) - q[..., 10]
+    c, s = q[..., 10], q[..., 11]
+    dx, dz = x[..., 0] - q[..., 4], x[..., 2] - q[..., 6]
+    loc = torch.stack([c * dx - s * dz, x[..., 1] - q[..., 5], s * dx + c * dz], -1)
+    qq = loc.abs() - q[..., 7:10]
+    d_box = qq.clamp(min=0).norm(dim=-1) + qq.max(dim=-1).values.clamp(max=0)
+    d_half = (x * q[..., 4:7]).sum(-1) - q[..., 7]
+    zero = torch.zeros_like(d_half)
+    return torch.where(kind == SPHERE, d_sphere, torch.where(kind == CAPSULE, d_capsule, torch.where(
+        kind == BOX, d_box, torch.where(kind == HALF_SPACE, d_half, zero))))
 
 
 def _scene_args(scene, N, J, joint_radius, joint_weights, dev):
@@ -251,13 +567,22 @@ def _scene_args(scene, N, J, joint_radius, joint_weights, dev):
     return rec, jp
 
 
+def _track_args(tracks, N, T, lengths, bounds, dev):
+    """The (N, T, Km, REC) records on the device and their balls (None without the broad phase or without tracks)."""
+    trk = batch_tracks(tracks, N, T, lengths)
+    bnd = track_bounds(trk).to(dev).contiguous() if bounds and trk.shape[2] else None
+    return trk.to(dev).contiguous(), bnd
+
+
 @torch.no_grad()
 def scene_loss_grad(x0: torch.Tensor, lengths, mean, std, scene, joint_radius=None, joint_weights=None, targets=None,
-                    weights=None):
+                    weights=None, tracks=None, bounds=True):
     """Loss (B,) and gradient (B, T, F) of L_scene (module docstring), plus §14's target term when ``targets`` (B, T, J, 3)
     and ``weights`` are given, with respect to the normalised features ``x0`` (B, T, F) on a GPU, through
     ``mdm_joint_scene_loss_grad``.  ``scene``: one list of primitives, or one per sample; ``mean`` / ``std``: (F,) or (B, F).
-    The gradient is exactly 0 in every column past 3 J and in every frame at or past ``lengths[b]``."""
+    The gradient is exactly 0 in every column past 3 J and in every frame at or past ``lengths[b]``.  ``tracks`` (as
+    ``batch_tracks`` takes them; ``scene`` may then be None) adds L_tracks through ``mdm_joint_tracks_loss_grad``, behind the
+    broad phase of ``track_bounds`` (``bounds=False``: without it; the result is the same bit for bit)."""
     L.require_cuda(x0)
     dev = x0.device
     x = x0.detach().to(torch.float32).contiguous()
@@ -265,7 +590,7 @@ def scene_loss_grad(x0: torch.Tensor, lengths, mean, std, scene, joint_radius=No
         raise ValueError(f"x0 of shape {tuple(x.shape)} must be (B, T, F)")
     B, T, F = x.shape
     J = joints_for_feats(F)
-    rec, jp = _scene_args(scene, B, J, joint_radius, joint_weights, dev)
+    rec, jp = _scene_args([] if scene is None else scene, B, J, joint_radius, joint_weights, dev)
     K = rec.shape[1]
     if not 1 <= T <= max_frames(F, K):
         raise ValueError(f"T = {T}: with {K} primitives the control kernels take 1 to {max_frames(F, K)} frames at F = {F}")
@@ -284,19 +609,27 @@ def scene_loss_grad(x0: torch.Tensor, lengths, mean, std, scene, joint_radius=No
         raise ValueError(f"lengths must hold {B} entries")
     loss = torch.empty(B, device=dev)
     grad = torch.empty_like(x)
+    head = (x.data_ptr(), ln.data_ptr(), mean_t.data_ptr(), std_t.data_ptr(), L.ptr(tg), L.ptr(w), rec.data_ptr() if K else 0, K,
+            jp.data_ptr())
+    tail = (B, T, F, loss.data_ptr(), grad.data_ptr(), L.stream_ptr())
     with torch.cuda.device(dev):
-        L.check(L.lib().mdm_joint_scene_loss_grad(
-            x.data_ptr(), ln.data_ptr(), mean_t.data_ptr(), std_t.data_ptr(), L.ptr(tg), L.ptr(w), rec.data_ptr() if K else 0, K,
-            jp.data_ptr(), B, T, F, loss.data_ptr(), grad.data_ptr(), L.stream_ptr()), "mdm_joint_scene_loss_grad")
+        if tracks is None:
+            L.check(L.lib().mdm_joint_scene_loss_grad(*head, *tail), "mdm_joint_scene_loss_grad")
+        else:
+            trk, bnd = _track_args(tracks, B, T, ln.cpu(), bounds, dev)
+            L.check(L.lib().mdm_joint_tracks_loss_grad(*head, trk.data_ptr() if trk.shape[2] else 0, trk.shape[2], L.ptr(bnd),
+                                                       *tail), "mdm_joint_tracks_loss_grad")
     return loss, grad
 
 
 @torch.no_grad()
 def canvas_scene_loss_grad(rows: torch.Tensor, motion_offsets, frame_rows, mean, std, scene, joint_radius=None,
-                           joint_weights=None, targets=None, weights=None):
+                           joint_weights=None, targets=None, weights=None, tracks=None, bounds=True):
     """``scene_loss_grad`` over the canvases of M long motions, as ``motion_control.canvas_loss_grad``: loss (M,) and gradient
     (total, F) dense in canvas order, through ``mdm_canvas_scene_loss_grad``.  ``scene``: one list of primitives, or one per
-    motion, in the canvas frame; ``targets`` (total, J, 3) in canvas order and ``weights``, or neither.  Any canvas length."""
+    motion, in the canvas frame; ``targets`` (total, J, 3) in canvas order and ``weights``, or neither.  Any canvas length.
+    ``tracks``: one list of track stacks per motion, in canvas frames (or packed (total, Km, REC) records in canvas order),
+    through ``mdm_canvas_tracks_loss_grad``; ``bounds`` as in ``scene_loss_grad``."""
     L.require_cuda(rows)
     dev = rows.device
     x = rows.detach().to(torch.float32).contiguous()
@@ -310,7 +643,7 @@ def canvas_scene_loss_grad(rows: torch.Tensor, motion_offsets, frame_rows, mean,
         raise ValueError(f"motion_offsets must rise from 0 to the number of frame rows {total}")
     if total and (int(fr.min()) < 0 or int(fr.max()) >= x.shape[0] or torch.unique(fr).numel() != total):
         raise ValueError(f"frame_rows must be distinct rows in [0, {x.shape[0]})")
-    rec, jp = _scene_args(scene, M, J, joint_radius, joint_weights, dev)
+    rec, jp = _scene_args([] if scene is None else scene, M, J, joint_radius, joint_weights, dev)
     K = rec.shape[1]
     if (targets is None) != (weights is None):
         raise ValueError("targets and weights go together: give both or neither")
@@ -326,9 +659,16 @@ def canvas_scene_loss_grad(rows: torch.Tensor, motion_offsets, frame_rows, mean,
     loss = torch.zeros(M, device=dev)
     grad = torch.zeros((total, F), device=dev)
     ws = torch.empty(max(int(L.lib().mdm_canvas_control_workspace_floats(total, F)), 1), device=dev)
+    head = (x.data_ptr(), off_d.data_ptr(), fr_d.data_ptr(), mean_t.data_ptr(), std_t.data_ptr(), L.ptr(tg), L.ptr(w),
+            rec.data_ptr() if K else 0, K, jp.data_ptr())
+    tail = (M, F, loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), L.stream_ptr())
     with torch.cuda.device(dev):
-        L.check(L.lib().mdm_canvas_scene_loss_grad(
-            x.data_ptr(), off_d.data_ptr(), fr_d.data_ptr(), mean_t.data_ptr(), std_t.data_ptr(), L.ptr(tg), L.ptr(w),
-            rec.data_ptr() if K else 0, K, jp.data_ptr(), M, F, loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), L.stream_ptr()),
-            "mdm_canvas_scene_loss_grad")
+        if tracks is None:
+            L.check(L.lib().mdm_canvas_scene_loss_grad(*head, *tail), "mdm_canvas_scene_loss_grad")
+        else:
+            trk = canvas_tracks(tracks, off)
+            bnd = track_bounds(trk).to(dev).contiguous() if bounds and trk.shape[1] else None
+            trk = trk.to(dev).contiguous()
+            L.check(L.lib().mdm_canvas_tracks_loss_grad(*head, trk.data_ptr() if trk.shape[1] else 0, trk.shape[1], L.ptr(bnd),
+                                                        *tail), "mdm_canvas_tracks_loss_grad")
     return loss, grad

@@ -271,6 +271,7 @@ class DDPMTrainer(object):
         ``prompt_weights``: composed prompts, as in ``generate``; ``control_joints`` / ``control_weights`` /
         ``control_scale`` / ``control_iters``: joint-position control under this call's ``mean`` / ``std``; ``scene`` /
         ``scene_joint_radius`` / ``scene_joint_weights``: obstacles the joints keep out of (DESIGN.md §24), under the same;
+        ``scene_tracks``: obstacles that move, e.g. ``motion_scene.character_tracks`` of another character (DESIGN.md §25);
         ``edit_joints`` (through ``**kw``): joint clips in place of ``edit_motion``, converted under the same ``mean`` /
         ``std``.  ``from_rotations``: joints by forward kinematics of the rot6d columns (``postprocess.motion_to_joints_fk``,
         DESIGN.md §17: rigid bones) on ``offsets`` (J, 3) or one (J, 3) per motion; None: every motion's own mean bone
@@ -280,6 +281,63 @@ class DDPMTrainer(object):
         motions = gen(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)
         return MO.to_joints(motions, MO.valid_lengths(motions, m_lens), dim_pose, mean, std, joints_num, sigma, from_rotations,
                             offsets, fix_feet=fix_feet, blend=blend)
+
+    @torch.no_grad()
+    def generate_together(self, scenes, dim_pose, mean, std, *, radius=0.08, margin=0.05, weight=5.0, bones=None, seed=None,
+                          **kw):
+        """Several characters in one world: ``scenes`` is a list of scenes, each a list of characters
+        ``dict(caption=, length=, position=(x, z), yaw=, control_joints=, control_weights=, scene=)``; ``position`` / ``yaw``
+        (default the origin, 0) place the character's own frame in the world (``motion_scene.to_world``), and targets
+        (length, J, 3), their weights (aligned on the frame dim) and the static primitives of ``scene`` are given in world
+        coordinates.  Stage i generates character i of every scene that has one in one ``generate_joints`` batch: the
+        characters 0 ... i - 1 of its scene, already generated, are obstacles that move, ``motion_scene.character_tracks``
+        of their joints (capsules of ``radius`` along ``bones``, ``margin`` and ``weight`` as a primitive's; padding past an
+        earlier character's length), moved with the world targets and primitives into character i's own frame.  Earlier
+        characters do not react to later ones.  A frame takes ``motion_scene.MAX_TRACKS`` tracks: two earlier characters
+        need a ``bones`` subset.  ``weight`` follows §14's rule, ``control_scale`` x curvature < 2.  Returns
+        the joints in the world, one list of (length, J, 3) per scene.  ``seed``: stage i samples under ``seed + i``;
+        ``**kw`` goes to ``generate_joints`` (``control_scale``, ``control_iters``, the sampler, ``sigma``, ...).  A scene of
+        one character is ``generate_joints`` followed by ``to_world``, bit for bit."""
+        from . import motion_scene as MS
+        J = (dim_pose + 1) // 12
+        out = [[None] * len(s) for s in scenes]
+        for i in range(max([len(s) for s in scenes] + [0])):
+            rows = [k for k, s in enumerate(scenes) if len(s) > i]
+            chars = [scenes[k][i] for k in rows]
+            lens = [int(c["length"]) for c in chars]
+            place = [(tuple(c.get("position", (0.0, 0.0))), float(c.get("yaw", 0.0))) for c in chars]
+            tracks = [[t for prev in out[k][:i] for t in MS.character_tracks(MS.to_local(prev, *pl), radius, margin=margin,
+                                                                              weight=weight, bones=bones)]
+                      for k, pl in zip(rows, place)]
+            if max(len(t) for t in tracks) > MS.MAX_TRACKS:
+                raise ValueError(f"{max(len(t) for t in tracks)} tracks for character {i} of a scene: a frame takes at most "
+                                 f"{MS.MAX_TRACKS}; give a bones= subset")
+            static = [MS.records_to_local(MS.pack_scene(c.get("scene") or []), *pl).to(torch.float32) for c, pl in zip(chars, place)]
+            cond = {}
+            if any(tracks):
+                cond["scene_tracks"] = tracks
+            if any(s.shape[0] for s in static):
+                rec = torch.zeros((len(chars), max(s.shape[0] for s in static), MS.REC))
+                for n, s in enumerate(static):
+                    rec[n, :s.shape[0]] = s
+                cond["scene"] = rec
+            if any(c.get("control_joints") is not None for c in chars):
+                g, w = torch.zeros((len(chars), max(lens), J, 3)), torch.zeros((len(chars), max(lens), J, 3))
+                for n, (c, pl) in enumerate(zip(chars, place)):
+                    if c.get("control_joints") is None:
+                        continue
+                    tg = torch.as_tensor(c["control_joints"], dtype=torch.float32)
+                    wt = torch.as_tensor(c["control_weights"], dtype=torch.float32)
+                    if tuple(tg.shape) != (lens[n], J, 3):
+                        raise ValueError(f"control_joints of shape {tuple(tg.shape)} must be {(lens[n], J, 3)}, in the world")
+                    g[n, :lens[n]] = MS.to_local(tg, *pl)
+                    w[n, :lens[n]] = wt.reshape(tuple(wt.shape) + (1,) * (3 - wt.dim())).expand(lens[n], J, 3)
+                cond.update(control_joints=g, control_weights=w)
+            joints = self.generate_joints([c["caption"] for c in chars], torch.tensor(lens), dim_pose, mean, std,
+                                          seed=None if seed is None else seed + i, **cond, **kw)
+            for k, pl, j in zip(rows, place, joints):
+                out[k][i] = MS.to_world(j, *pl)
+        return out
 
     @torch.no_grad()
     def generate_rotations(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, offsets=None, fix_feet=False,
@@ -310,7 +368,8 @@ class DDPMTrainer(object):
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
                       sample_steps=None, eta=0.0, progress=False, control_joints=None, control_weights=None, control_scale=None,
-                      control_iters=None, scene=None, scene_joint_radius=None, scene_joint_weights=None, **conditioning):
+                      control_iters=None, scene=None, scene_joint_radius=None, scene_joint_weights=None, scene_tracks=None,
+                      **conditioning):
         """Long motions: ``scripts`` is a list of long motions, each a list of ``(caption, length)``
         segments of at most ``num_frames`` frames; neighbouring segments share ``overlap`` canvas frames, whose eps is
         blended on every step (``blend`` "linear" crossfade or "uniform") while x_T and the step noise come from the left
@@ -333,6 +392,8 @@ class DDPMTrainer(object):
         (``motion_long.canvas_control`` checks it).  ``scene`` (with ``mean`` / ``std``; ``scene_joint_radius`` /
         ``scene_joint_weights`` (J,)): one list of ``motion_scene`` primitives per motion, in its canvas frame, that the joints
         keep out of on every step, through the same canvas-wide guidance and with or without targets.
+        ``scene_tracks``: one list of ``motion_scene`` track stacks per motion, moving obstacles over its canvas frames
+        (DESIGN.md §25), under the same.
         The other per-motion inputs are ``**conditioning``, checked by
         ``motion_long.canvas_conditioning``."""
         m = self._model()
@@ -342,7 +403,7 @@ class DDPMTrainer(object):
         window_rows = ML.canvas_conditioning(plans, dim_pose, device=device, **conditioning)
         control = ML.canvas_control(plans, dim_pose, control_joints, control_weights, control_scale, control_iters,
                                     conditioning.get("mean"), conditioning.get("std"), device, scene, scene_joint_radius,
-                                    scene_joint_weights)
+                                    scene_joint_weights, scene_tracks)
         out, first = [None] * len(plans), 0
         for idx in ML.plan_batches(plans, batch_size):
             caps = [c for i in idx for c in plans[i][0]]
@@ -370,7 +431,7 @@ class DDPMTrainer(object):
         if longest > most:
             raise ValueError(f"a canvas of {longest} frames: {what} takes at most {most} frames")
         if kw.get("edit_joints") is not None or kw.get("edit_bvh") is not None or kw.get("control_joints") is not None or \
-                kw.get("scene") is not None:
+                kw.get("scene") is not None or kw.get("scene_tracks") is not None:
             kw = dict(kw, mean=mean, std=std)
         return self.generate_long(scripts, dim_pose, **kw)
 

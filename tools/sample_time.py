@@ -38,6 +38,12 @@ a scene of K primitives (spheres, pillars, boxes and floors in turn, every joint
 
     timeout -k 10 900 python tools/sample_time.py --control 1,5 --scene 4,16 --reps 5 --precisions 1
 
+``--control I --scene K --tracks far,near,near_nobounds`` measures tracks: the controlled generation with
+a scene of K primitives without and with the 21 capsule tracks of a character (``motion_scene.character_tracks``): far from the
+motion (every joint outside the frames' balls), around it, and around it without the broad phase.
+
+    timeout -k 10 900 python tools/sample_time.py --control 1,5 --scene 4 --tracks far,near,near_nobounds --reps 5 --precisions 1
+
 ``--long-control I`` (with ``--long H``, default 20) measures joint control over the canvases of those long motions: the same
 ``generate_long`` without and with ``control_joints`` / ``control_weights`` over every canvas frame (every joint's height,
 ``control_iters`` = I; I may be a list), DDIM-50 and DPM-Solver++(2M)-20, alternating, as for ``--edit``.
@@ -70,6 +76,8 @@ def main():
     ap.add_argument("--control", default=None, help="I[,I...]: time joint control with I iterations against plain")
     ap.add_argument("--scene", default=None, help="K[,K...] (with --control): time a scene of K primitives against joint "
                     "control alone")
+    ap.add_argument("--tracks", default=None, help="far,near,near_nobounds (with --control and --scene): time 21 character tracks "
+                    "against control with the scene alone")
     ap.add_argument("--long", type=int, default=None, help="H: time long motions (4 windows each, H shared frames) "
                     "against plain generation of the same windows")
     ap.add_argument("--long-control", default=None, help="I[,I...]: time canvas joint control with I iterations against "
@@ -91,6 +99,8 @@ def main():
         return edit_main(a, tr, m, caps, length, B, T)
     if a.compose:
         return compose_main(a, tr, m, caps, length, B, T)
+    if a.control and a.scene and a.tracks:
+        return tracks_main(a, tr, m, caps, length, B, T)
     if a.control and a.scene:
         return scene_main(a, tr, m, caps, length, B, T)
     if a.control:
@@ -336,6 +346,77 @@ def scene_main(a, tr, m, caps, length, B, T):
         spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
         print(f"{r['precision']:>9} {r['control_iters']:>5} {r['prims']:>5} {r['sampler']:>22} {r['control_ms']:>11.1f} "
               f"{r['scene_ms']:>9.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
+
+
+def tracks_main(a, tr, m, caps, length, B, T):
+    # scene_main's generation with its scene, without and with the 21 capsule tracks of a character.  The unclipped
+    # random-weight samples are hundreds of metres across, so the character "around the motion" is a cloud of that size (every
+    # joint inside the frames' balls: every record is walked; thin capsules, so the forces stay bounded) and the one "far from
+    # it" the same cloud 1e6 m away (every joint outside: the broad phase skips every frame).
+    MS = importlib.import_module("motiondiffusion-moe_amd.motion_scene")
+    tg, w = torch.zeros(B, T, 22, 3), torch.zeros(B, T, 22, 3)
+    tg[..., 1], w[..., 1] = 1.0, 1.0
+    mean, std = torch.zeros(263), torch.ones(263)
+    K = int(a.scene.split(",")[0])
+    scene = []
+    for k in range(K):
+        x, z = 0.8 * (k % 4) - 1.2, 0.8 * (k // 4) - 1.2
+        scene.append([MS.sphere((x, 1.0, z), 0.4, margin=0.05), MS.capsule((x, 0.0, z), (x, 2.0, z), 0.2),
+                      MS.box((x, 0.5, z), (0.3, 0.5, 0.2), 0.3 * k), MS.floor(-0.1 * k)][k % 4])
+    gen_ = torch.Generator().manual_seed(0)
+    cloud = torch.randn(1, 22, 3, generator=gen_, dtype=torch.float64) * 300 + torch.cumsum(
+        torch.randn(T, 1, 3, generator=gen_, dtype=torch.float64) * 5, 0)
+    bounds_of = MS.track_bounds
+
+    def no_bounds(rec):
+        out = bounds_of(rec)
+        out[..., 3] = float("inf")
+        return out
+
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for iters in [int(k) for k in a.control.split(",")]:
+            for case in a.tracks.split(","):
+                shift = torch.tensor([1e6, 0.0, 0.0], dtype=torch.float64) if case == "far" else 0.0
+                tracks = MS.character_tracks(cloud + shift, 0.08, margin=0.05)
+                MS.track_bounds = no_bounds if case.endswith("nobounds") else bounds_of
+                for sampler, steps, n in (("ddim", 50, 50), ("dpmpp2m", 20, 20)):
+                    def gen(trk):
+                        extra = dict(scene_tracks=tracks) if trk else {}
+                        return tr.generate(caps, length, 263, batch_size=B, seed=0, sampler=sampler, sample_steps=steps,
+                                           control_joints=tg, control_weights=w, control_scale=0.05, control_iters=iters,
+                                           mean=mean, std=std, scene=scene, scene_joint_radius=[0.05] * 22, **extra)
+                    for trk in (False, True):  # warm-up
+                        assert all(torch.isfinite(o).all() for o in gen(trk))
+                    ts = {False: [], True: []}
+                    for _ in range(a.reps):
+                        for trk in (False, True):
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            gen(trk)
+                            torch.cuda.synchronize()
+                            ts[trk].append((time.perf_counter() - t0) * 1e3)
+                    med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+                    diff = sorted(c - p for p, c in zip(ts[False], ts[True]))
+                    name = {"ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+                    line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, control_iters=iters, prims=K, tracks=case,
+                                scene_ms=round(med[False], 2), tracks_ms=round(med[True], 2),
+                                diff_ms_median=round(diff[len(diff) // 2], 2), diff_ms_min=round(diff[0], 2),
+                                diff_ms_max=round(diff[-1], 2), diff_us_per_step=round(diff[len(diff) // 2] / n * 1e3, 1),
+                                scene_reps_ms=[round(t, 2) for t in ts[False]], tracks_reps_ms=[round(t, 2) for t in ts[True]])
+                    rows.append(line)
+                    print(json.dumps(line), flush=True)
+    MS.track_bounds = bounds_of
+    print(f"\nconfigs[1] shape B={B} T={T}, guided (cfg 7.5), joint control (every joint's height) with a scene of {K} primitives, "
+          f"without and with 21 character tracks; {torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'iters':>5} {'tracks':>14} {'sampler':>22} {'scene ms':>9} {'tracks ms':>10} {'diff ms (min..max)':>22} "
+          f"{'us/step':>8}")
+    for r in rows:
+        spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
+        print(f"{r['precision']:>9} {r['control_iters']:>5} {r['tracks']:>14} {r['sampler']:>22} {r['scene_ms']:>9.1f} "
+              f"{r['tracks_ms']:>10.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
 
 
 def long_main(a, tr, m, caps, B, T):
