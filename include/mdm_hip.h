@@ -585,6 +585,35 @@ int mdm_motion_render(const float* joints, const int32_t* length, const MdmSkele
                       int32_t H, int32_t W, const float* camera, const float* style, int32_t mode, const int32_t* frames,
                       int32_t n_frames, uint8_t* out, float* scratch, void* stream);
 
+/* World view of the motion preview (csrc/motion_world_render.hip): C <= 4 characters and the primitives of a
+ * scene in one picture per frame, in world coordinates (no root subtraction).  joints (B, C, T, J, 3) fp32, lengths (B, C)
+ * int32 or NULL (= T): a character of length 0 is absent, a character is not drawn at or past its own length, the world's
+ * length is the longest character's.  scene (B, K, MDM_SCENE_REC), K <= MDM_SCENE_MAX_PRIMS, and tracks
+ * (B, T, Km, MDM_SCENE_REC), Km <= MDM_SCENE_MAX_TRACKS: the records of the scene calls below (kind 0 draws nothing; margins
+ * and weights are not read).  mdm_world_extent: extent_out (B, 6) = per-axis minimum (3) and maximum (3) over the valid
+ * frames of every character, the boxes around static spheres, capsules and boxes, and those around the same kinds among the
+ * track records of frames below the world's length; +inf / -inf for a world with none of these.
+ * mdm_world_render: camera[8], mode, frames / n_frames and out as in mdm_motion_render, an output frame whose index is outside
+ * [0, the world's length) being all zero.  ground (B) device fp32: the height of each world's ground, the extent's XZ
+ * rectangle grown by 0.5 m.  style[18 + 5 C (1 + nchains)]: background r, g, b; floor r, g, b, alpha; solid r, g, b, alpha
+ * (primitives); edge r, g, b and full width in points (a box's edges); the shade factors of a box's top, its local-x sides
+ * and its local-z sides; then per character r, g, b, alpha, width of its trajectory and of every chain.  After the ground and
+ * the trajectories the drawn primitives (static, then tracks) and the (character, chain) groups are composited far to near by
+ * the view depth of a reference point, ties to the lower index: a painter's order per item (DESIGN.md §26 defines every
+ * item's picture).  scratch: mdm_world_render_scratch_floats(B, C, T, n_frames, K, Km) floats (n_frames = T without frames;
+ * -1 for bad arguments).  Three launches, stream-ordered, no allocation, no host synchronisation.
+ * MDM_ERR_ARG, before the device is touched: a null pointer (lengths, frames, and scene / tracks with K / Km == 0 excepted),
+ * B < 0, C outside [1, 4], T < 1, J outside [1, 32], K or Km outside their limits, and for mdm_world_render everything
+ * mdm_motion_render refuses (sizes, mode, frames, alignment of out, skeleton, camera, non-finite style, a negative width).
+ * MDM_ERR_UNSUPPORTED: B or NF above 65535 (grid dimensions). */
+int mdm_world_extent(const float* joints, const int32_t* lengths, const float* scene, int32_t K, const float* tracks, int32_t Km,
+                     int32_t B, int32_t C, int32_t T, int32_t J, float* extent_out, void* stream);
+int64_t mdm_world_render_scratch_floats(int32_t B, int32_t C, int32_t T, int32_t n_frames, int32_t K, int32_t Km);
+int mdm_world_render(const float* joints, const int32_t* lengths, const MdmSkeleton* skeleton, const float* scene, int32_t K,
+                     const float* tracks, int32_t Km, int32_t B, int32_t C, int32_t T, int32_t J, int32_t H, int32_t W,
+                     const float* camera, const float* style, const float* ground, int32_t mode, const int32_t* frames,
+                     int32_t n_frames, uint8_t* out, float* scratch, void* stream);
+
 /* Joint-position control (csrc/motion_control.hip).  For sample b, with J = (F + 1) / 12 joints (F must be
  * 12 J - 1: 263 -> 22, 251 -> 21), targets G and weights W dense fp32 (B, T, J, 3), W >= 0 and finite, mean / std fp32
  * (B, F) (one row per sample), and P = recover_from_ric(x0 * std + mean) without temporal filter (as mdm_motion_postprocess

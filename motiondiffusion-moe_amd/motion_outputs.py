@@ -8,7 +8,7 @@ import torch
 from torch.nn.utils.rnn import pad_sequence
 
 from .motion_features import pad_clips, skeleton_for_feats
-from .motion_render import gif_bytes, render_motion, write_gif
+from .motion_render import gif_bytes, render_motion, render_world, write_gif
 from .motion_rig import DEFAULT_FPS, bvh_text, retime_ratio, rig_of, rotations_to_rig
 from .postprocess import fk_max_frames, motion_to_joints, motion_to_joints_fk, remove_foot_skate
 
@@ -97,6 +97,41 @@ def to_frames(joints, size, camera, palette, style):
     x, lens = pad_clips(joints, joints[0].shape[1])
     frames = render_motion(x, lens, size=size, camera=camera, palette=palette, **(style or {}))
     return [frames[i, :n] for i, n in enumerate(lens.tolist())]
+
+
+def to_world_frames(worlds, scene, tracks, size, camera, palette, style):
+    """``motion_render.render_world`` over a list of worlds, each a list of (n_i, J, 3) joint clips in world
+    coordinates, one call for all: per world ``(n, H, W, 3)`` uint8 frames or ``(n, H, W)`` palette indices, n the length of
+    its longest character.  ``scene`` / ``tracks``: as ``render_world`` takes them; packed canvas-order track records
+    (total, Km, REC), as ``generate_long`` takes them, are cut at the worlds' lengths."""
+    lens = [max(int(c.shape[0]) for c in w) for w in worlds]
+    if torch.is_tensor(tracks) and tracks.dim() == 3 and tracks.shape[0] == sum(lens) and len(lens) > 1:
+        rows = torch.zeros((len(lens), max(lens)) + tuple(tracks.shape[1:]), dtype=tracks.dtype)
+        for i, (n, part) in enumerate(zip(lens, torch.split(tracks.detach().cpu(), lens))):
+            rows[i, :n] = part
+        tracks = rows
+    frames = render_world(worlds, scene=scene, tracks=tracks, size=size, camera=camera, palette=palette, **(style or {}))
+    return [frames[i, :n] for i, n in enumerate(lens)]
+
+
+def world_scene(characters):
+    """The primitives a world is drawn with: the union of its characters' ``scene`` lists, in order, each primitive once."""
+    out = []
+    for c in characters:
+        for p in c.get("scene") or []:
+            if p not in out:
+                out.append(p)
+    return out
+
+
+def to_frames_view(view, joints, cond, size, camera, palette, style):
+    """``to_frames`` (``view`` "root", §21) or the world view of the same clips (``view`` "world", §26), one character to a
+    world, with the ``scene`` / ``scene_tracks`` of ``cond`` that steered them."""
+    if view == "root":
+        return to_frames(joints, size, camera, palette, style)
+    if view != "world":
+        raise ValueError(f"view must be \"root\" or \"world\", not {view!r}")
+    return to_world_frames([[j] for j in joints], cond.get("scene"), cond.get("scene_tracks"), size, camera, palette, style)
 
 
 def to_gifs(frames, dim_pose, paths, fps):

@@ -6,6 +6,10 @@ skeleton's five kinematic chains in red, blue, black, red, blue, all relative to
 project's own and is defined in DESIGN.md §21 (a look-at pinhole camera, capsules with a one-pixel coverage ramp), not
 matplotlib's: two implementations of that definition agree to a grey level.  All pixels are made in the kernel; no eager
 fallback.
+
+``render_world`` (``mdm_world_render`` in csrc/motion_world_render.hip) is the world view under the same
+definition: up to four characters and the primitives and tracks of a ``motion_scene`` scene in world coordinates, composited
+far to near per item; ``world_extent`` / ``fit_camera`` give the camera that shows all of it.
 """
 from __future__ import annotations
 
@@ -272,3 +276,227 @@ def gif_bytes(indices, fps: float, length=None) -> bytes:
     buf = io.BytesIO()
     write_gif(indices, buf, fps, length)
     return buf.getvalue()
+
+
+# ---- the world view: several characters and the primitives of a scene, in world coordinates ----------------
+MAX_CHARACTERS = 4
+GREEN, ORANGE, PURPLE, TEAL, BROWN, OLIVE = (0.0, 0.55, 0.0), (1.0, 0.55, 0.0), (0.55, 0.0, 0.7), (0.0, 0.6, 0.6), (0.55, 0.3, 0.1), (0.5, 0.5, 0.0)
+WORLD_STYLE = dict(background=(1.0, 1.0, 1.0),
+                   floor_color=(0.5, 0.5, 0.5), floor_alpha=0.5,
+                   trajectory_colors=(BLUE, GREEN, PURPLE, BROWN), trajectory_alpha=1.0, trajectory_width=1.0,
+                   character_colors=((RED, BLUE, BLACK, RED, BLUE), (GREEN, ORANGE, BLACK, GREEN, ORANGE),
+                                     (PURPLE, TEAL, BLACK, PURPLE, TEAL), (BROWN, OLIVE, BLACK, BROWN, OLIVE)),
+                   chain_alpha=1.0, chain_width=4.0,
+                   solid_color=(0.55, 0.6, 0.7), solid_alpha=0.9, edge_color=(0.15, 0.15, 0.2), edge_width=1.5,
+                   shade=(1.0, 0.8, 0.62))  # a box's top and bottom, its local-x sides, its local-z sides; choices, all of them
+
+
+def world_style_block(C_: int, nchains: int, **style):
+    """The floats of ``mdm_world_render``'s style argument from the keyword arguments of ``render_world`` (``WORLD_STYLE`` holds
+    the names and defaults): background; floor colour and alpha; ``solid_color`` / ``solid_alpha`` of the primitives;
+    ``edge_color`` / ``edge_width`` of a box's edges; ``shade``; then per character the colour, alpha and width of its
+    trajectory and of every chain.  ``trajectory_alpha`` / ``trajectory_width``: one value or one per character;
+    ``chain_alpha`` / ``chain_width``: anything that broadcasts to (characters, chains); ``trajectory_colors``: one colour per
+    character, ``character_colors``: one list of chain colours per character, both repeated in turn where there are more."""
+    unknown = set(style) - set(WORLD_STYLE)
+    if unknown:
+        raise ValueError(f"unknown style arguments {sorted(unknown)}: the style is {sorted(WORLD_STYLE)}")
+    st = dict(WORLD_STYLE, **style)
+
+    def rgb(v, what):
+        v = [float(x) for x in v]
+        if len(v) != 3 or not all(0.0 <= x <= 1.0 for x in v):
+            raise ValueError(f"{what} must be three values in [0, 1]")
+        return v
+
+    def spread(v, shape, what, most=None):
+        try:
+            a = np.broadcast_to(np.asarray(v, np.float64), shape)
+        except ValueError:
+            raise ValueError(f"{what} must broadcast to {shape}") from None
+        if not np.isfinite(a).all() or (a < 0).any() or (most is not None and (a > most).any()):
+            raise ValueError(f"{what} must be finite and >= 0" + (f", at most {most}" if most is not None else ""))
+        return a
+
+    traj_colors = [rgb(c, "a trajectory colour") for c in st["trajectory_colors"]]
+    sets = [[rgb(c, "a chain colour") for c in s] for s in st["character_colors"]]
+    if not traj_colors or not sets or not all(sets):
+        raise ValueError("trajectory_colors and character_colors must not be empty")
+    ta, tw = spread(st["trajectory_alpha"], (C_,), "trajectory_alpha", 1.0), spread(st["trajectory_width"], (C_,), "trajectory_width")
+    ca, cw = spread(st["chain_alpha"], (C_, nchains), "chain_alpha", 1.0), spread(st["chain_width"], (C_, nchains), "chain_width")
+    v = rgb(st["background"], "background")
+    v += rgb(st["floor_color"], "floor_color") + [float(spread(st["floor_alpha"], (), "floor_alpha", 1.0))]
+    v += rgb(st["solid_color"], "solid_color") + [float(spread(st["solid_alpha"], (), "solid_alpha", 1.0))]
+    v += rgb(st["edge_color"], "edge_color") + [float(spread(st["edge_width"], (), "edge_width"))]
+    v += [float(x) for x in spread(st["shade"], (3,), "shade", 1.0)]
+    for c in range(C_):
+        v += traj_colors[c % len(traj_colors)] + [float(ta[c]), float(tw[c])]
+        colors = sets[c % len(sets)]
+        for g in range(nchains):
+            v += colors[g % len(colors)] + [float(ca[c, g]), float(cw[c, g])]
+    return (C.c_float * len(v))(*v)
+
+
+def pack_world(characters, lengths=None):
+    """The characters of B worlds as ``(joints (B, C, T, J, 3) float32, lengths (B, C) int64 on the CPU)``.  ``characters``:
+    a tensor (B, C, T, J, 3) with ``lengths`` (B, C) in [0, T] (None: all T), or a list of worlds, each a list of (n_i, J, 3)
+    joint clips in world coordinates, which is what ``DDPMTrainer.generate_together`` returns: padded with zeros to the
+    longest clip, a world with fewer characters than another gets absent ones (length 0).  At most ``MAX_CHARACTERS``."""
+    if isinstance(characters, (list, tuple)):
+        if lengths is not None:
+            raise ValueError("a list of worlds carries its own lengths")
+        worlds = [[torch.as_tensor(c) for c in w] for w in characters]
+        clips = [c for w in worlds for c in w]
+        if not clips:
+            raise ValueError("a world needs at least one character")
+        if any(c.dim() != 3 or c.shape[-1] != 3 or c.shape[1] != clips[0].shape[1] for c in clips):
+            raise ValueError("every character must be (n, J, 3) joints, with one J")
+        Cn = max(len(w) for w in worlds)
+        if Cn > MAX_CHARACTERS:
+            raise ValueError(f"{Cn} characters in a world: the world view draws at most {MAX_CHARACTERS}")
+        T = max(max(c.shape[0] for c in clips), 1)
+        x = torch.zeros((len(worlds), Cn, T, clips[0].shape[1], 3), dtype=torch.float32, device=clips[0].device)
+        ln = torch.zeros((len(worlds), Cn), dtype=torch.int64)
+        for b, w in enumerate(worlds):
+            for c, clip in enumerate(w):
+                x[b, c, :clip.shape[0]] = clip.to(x.device, torch.float32)
+                ln[b, c] = clip.shape[0]
+        return x, ln
+    x = torch.as_tensor(characters)
+    if x.dim() != 5 or x.shape[-1] != 3:
+        raise ValueError(f"characters of shape {tuple(x.shape)} must be (B, C, T, J, 3), or a list of worlds of (n, J, 3) clips")
+    B, Cn, T = x.shape[:3]
+    if not 1 <= Cn <= MAX_CHARACTERS:
+        raise ValueError(f"{Cn} characters in a world: the world view draws 1 to {MAX_CHARACTERS}")
+    if T < 1:
+        raise ValueError("a motion needs at least one frame")
+    if lengths is None:
+        ln = torch.full((B, Cn), T, dtype=torch.int64)
+    else:
+        ln = torch.as_tensor(lengths).to(torch.int64).cpu()
+        if tuple(ln.shape) != (B, Cn) or (ln.numel() and (int(ln.min()) < 0 or int(ln.max()) > T)):
+            raise ValueError(f"lengths must be {(B, Cn)} entries in [0, {T}] (0: the character is absent)")
+    return x.detach().to(torch.float32), ln
+
+
+def world_ground(records):
+    """The ground rule of ``render_world(ground=None)``: static records (B, K, 12) -> ``(ground (B,) float32, records)``.  A
+    world's ground lies at the offset of its first keep-out half-space whose normal is exactly (0, 1, 0), the one
+    ``motion_scene.floor`` makes, and that record becomes padding in the returned copy (it is the ground and is not drawn a
+    second time); without one the ground is at 0."""
+    rec = torch.as_tensor(records).detach().to("cpu", torch.float32).clone()
+    ground = torch.zeros(rec.shape[0])
+    for b in range(rec.shape[0]):
+        for k in range(rec.shape[1]):
+            q = rec[b, k]
+            if q[0] == 4 and q[1] == 1 and q[4] == 0 and q[5] == 1 and q[6] == 0:
+                ground[b] = q[7]
+                rec[b, k] = 0.0
+                break
+    return ground, rec
+
+
+def _world(characters, lengths, scene, tracks):
+    """The device arguments both world calls share: joints, lengths (CPU and device), static and track records."""
+    from . import motion_scene as MS
+    x, ln = pack_world(characters, lengths)
+    B, Cn, T, J = x.shape[:4]
+    rec = None if scene is None else MS.batch_scene(scene, B)
+    trk = None if tracks is None else MS.batch_tracks(tracks, B, T, ln.max(dim=1).values if B else None)
+    L.require_cuda(x)
+    return dict(x=x.contiguous(), ln=ln, ln_dev=ln.to(x.device, torch.int32).contiguous(), rec=rec, trk=trk, B=B, C=Cn, T=T, J=J)
+
+
+def _records(a):
+    dev = a["x"].device
+    rec = None if a["rec"] is None or a["rec"].shape[1] == 0 else a["rec"].to(dev).contiguous()
+    trk = None if a["trk"] is None or a["trk"].shape[2] == 0 else a["trk"].to(dev).contiguous()
+    return rec, (0 if rec is None else rec.shape[1]), trk, (0 if trk is None else trk.shape[2])
+
+
+def _extent(a, rec, K, trk, Km):
+    out = torch.empty((a["B"], 6), dtype=torch.float32, device=a["x"].device)
+    with torch.cuda.device(a["x"].device):
+        L.check(L.lib().mdm_world_extent(a["x"].data_ptr(), a["ln_dev"].data_ptr(), L.ptr(rec), K, L.ptr(trk), Km, a["B"], a["C"],
+                                         a["T"], a["J"], out.data_ptr(), L.stream_ptr()), "mdm_world_extent")
+    return out
+
+
+@torch.no_grad()
+def world_extent(characters, lengths=None, scene=None, tracks=None):
+    """The extent of B worlds on the device: (B, 6) float32, per-axis minimum then maximum over the valid frames
+    of every character, the boxes around the static spheres, capsules and boxes of ``scene`` and around the same kinds among
+    the live records of ``tracks`` in frames below the world's length.  Arguments as ``render_world``."""
+    a = _world(characters, lengths, scene, tracks)
+    return _extent(a, *_records(a))
+
+
+def fit_camera(extent, elev=30.0, azim=0.0, fov=40.0, size=(480, 480)) -> Camera:
+    """A ``Camera`` that shows all of ``extent`` ((6,) or (B, 6): the union of the rows that are finite): its target is the
+    extent's centre, and its distance puts the sphere around the extent's box inside the frame of ``size`` = (H, W) at the
+    vertical field of view ``fov``.  A tensor on the device is copied to the host, once."""
+    e = (extent.detach().cpu().numpy() if torch.is_tensor(extent) else np.asarray(extent)).astype(np.float64).reshape(-1, 6)
+    e = e[np.isfinite(e).all(1)]
+    if not len(e):
+        return Camera(elev=float(elev), azim=float(azim), fov=float(fov))
+    lo, hi = e[:, :3].min(0), e[:, 3:].max(0)
+    H, W = (float(v) for v in size)
+    half = np.deg2rad(float(fov)) / 2.0
+    half = min(half, np.arctan(np.tan(half) * W / H))  # the narrower of the frame's two half angles
+    radius = max(0.5 * float(np.linalg.norm(hi - lo)), 1e-3)
+    dist = radius / np.sin(half)
+    return Camera(elev=float(elev), azim=float(azim), dist=float(dist), fov=float(fov), target=tuple(float(v) for v in 0.5 * (lo + hi)),
+                  near=float(min(0.1, 0.5 * (dist - radius) if dist - radius > 0 else 0.5 * dist)))
+
+
+@torch.no_grad()
+def render_world(characters, lengths=None, scene=None, tracks=None, skeleton=None, size=(480, 480), camera=None, palette=False,
+                 frames=None, ground=None, **style):
+    """The world view: every character and every primitive of B worlds in one picture per frame, in world
+    coordinates -> (B, T, H, W, 3) uint8 on the device, or (B, T, H, W) palette indices.  ``characters`` / ``lengths``: as
+    ``pack_world`` takes them, e.g. what ``generate_together`` returns; a character is not drawn at or past its own length, and
+    frames at or past the longest character's are zero.  ``scene`` / ``tracks``: ``motion_scene`` primitives / track stacks,
+    one list for all worlds or one per world, or packed records, through ``motion_scene.batch_scene`` / ``batch_tracks``
+    (their limits apply); margins and weights do not change the picture.  ``ground``: the height of the ground rectangle, one
+    value or one per world; None: ``world_ground``'s rule (the scene's ``floor()``, else 0).  ``camera``: a ``Camera`` or a
+    dict of its fields; None: ``fit_camera`` of the union of the batch's extents, one camera for all worlds, at the cost of
+    one copy of (B, 6) floats to the host.  ``skeleton`` / ``size`` / ``palette`` / ``frames`` as in ``render_motion``;
+    ``**style``: see ``WORLD_STYLE``.  Items are composited far to near, one depth per item (a painter's order)."""
+    from .motion_features import _skeleton_struct
+    a = _world(characters, lengths, scene, tracks)
+    B, Cn, T, J = a["B"], a["C"], a["T"], a["J"]
+    sk = _skeleton_for(skeleton, J)
+    H, W = (int(v) for v in size)
+    if H < 4 or W < 4 or W % 4:
+        raise ValueError(f"size (H, W) = {(H, W)}: both at least 4 and W a multiple of 4 (a thread stores 4 pixels)")
+    st = world_style_block(Cn, len(sk.chains), **style)
+    idx = frame_indices(frames, T)
+    dev = a["x"].device
+    if ground is None:
+        if a["rec"] is None:
+            gr = torch.zeros(B)
+        else:
+            gr, a["rec"] = world_ground(a["rec"])
+    else:
+        gr = torch.as_tensor(ground, dtype=torch.float32).flatten()
+        if gr.numel() not in (1, B) or not bool(torch.isfinite(gr).all()):
+            raise ValueError(f"ground must be one finite height, or one per world ({B})")
+        gr = gr.expand(B)
+    rec, K, trk, Km = _records(a)
+    if camera is None:
+        camera = fit_camera(_extent(a, rec, K, trk, Km), size=(H, W))
+    cam = as_camera(camera).block()
+    gr = gr.to(dev, torch.float32).contiguous()
+    fr = None if idx is None else torch.tensor(idx, dtype=torch.int32, device=dev)
+    NF = T if idx is None else len(idx)
+    if B > 65535 or NF > 65535:
+        raise ValueError("at most 65535 worlds and 65535 frames per call")
+    out = torch.empty((B, NF, H, W) + (() if palette else (3,)), dtype=torch.uint8, device=dev)
+    lib = L.lib()
+    scratch = torch.empty(max(1, int(lib.mdm_world_render_scratch_floats(B, Cn, T, NF, K, Km))), dtype=torch.float32, device=dev)
+    s = _skeleton_struct(sk)
+    with torch.cuda.device(dev):
+        L.check(lib.mdm_world_render(a["x"].data_ptr(), a["ln_dev"].data_ptr(), C.byref(s), L.ptr(rec), K, L.ptr(trk), Km, B, Cn, T,
+                                     J, H, W, cam, st, gr.data_ptr(), 1 if palette else 0, L.ptr(fr), NF, out.data_ptr(),
+                                     scratch.data_ptr(), L.stream_ptr()), "mdm_world_render")
+    return out

@@ -462,34 +462,59 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_frames(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, size=(480, 480), camera=None,
-                        palette=False, style=None, **kw):
+                        palette=False, style=None, view="root", **kw):
         """``generate_joints`` followed by the motion preview (``motion_render.render_motion``) on the device:
         a list of ``(m_len, H, W, 3)`` uint8 frames, ``size`` = (H, W); with ``palette`` ``(m_len, H, W)`` indices into
         ``motion_render.PALETTE``.  ``camera``: a ``motion_render.Camera`` or a dict of its fields; ``style``: a dict of
         ``render_motion``'s colour and width arguments.  ``**kw`` goes to ``generate_joints`` untouched: ``from_rotations``,
-        ``fix_feet``, the sampler, edit and control arguments."""
+        ``fix_feet``, the sampler, edit and control arguments.  ``view="world"``: the world view instead
+        (``motion_render.render_world``): each character in world coordinates with the ``scene`` /
+        ``scene_tracks`` that steered it; ``camera`` None then fits one camera to the batch, ``style`` is ``render_world``'s."""
         joints = self.generate_joints(caption, m_lens, dim_pose, mean, std, batch_size, **kw)
-        return MO.to_frames(joints, size, camera, palette, style)
+        return MO.to_frames_view(view, joints, kw, size, camera, palette, style)
 
     @torch.no_grad()
     def generate_gif(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, paths=None, fps=None, size=(480, 480),
-                     camera=None, style=None, **kw):
+                     camera=None, style=None, view="root", **kw):
         """``generate_frames`` in palette mode followed by ``motion_render.write_gif``: one animated GIF per caption, as
         bytes, or written to ``paths[i]`` where given (the path is then returned in its place).  ``fps`` defaults to
-        ``motion_rig.DEFAULT_FPS`` (20 at dim_pose 263, 12.5 at 251); a GIF's frame delay is whole centiseconds."""
+        ``motion_rig.DEFAULT_FPS`` (20 at dim_pose 263, 12.5 at 251); a GIF's frame delay is whole centiseconds.  ``view`` as in
+        ``generate_frames``."""
         MO.check_paths(paths, len(caption), "caption")
         frames = self.generate_frames(caption, m_lens, dim_pose, mean, std, batch_size, size=size, camera=camera, palette=True,
-                                      style=style, **kw)
+                                      style=style, view=view, **kw)
         return MO.to_gifs(frames, dim_pose, paths, fps)
 
     @torch.no_grad()
     def generate_long_gif(self, scripts, dim_pose, mean, std, *, paths=None, fps=None, size=(480, 480), camera=None,
-                          style=None, **kw):
+                          style=None, view="root", **kw):
         """``generate_long_joints`` followed by the motion preview and ``write_gif``, as ``generate_gif``: one GIF per long
-        motion.  ``**kw`` goes to ``generate_long_joints`` untouched."""
+        motion.  ``**kw`` goes to ``generate_long_joints`` untouched.  ``view="world"``: the world view with each motion's
+        ``scene`` and its canvas ``scene_tracks`` (targets are not drawn)."""
         MO.check_paths(paths, len(scripts), "motion")
         joints = self.generate_long_joints(scripts, dim_pose, mean, std, **kw)
-        return MO.to_gifs(MO.to_frames(joints, size, camera, True, style), dim_pose, paths, fps)
+        return MO.to_gifs(MO.to_frames_view(view, joints, kw, size, camera, True, style), dim_pose, paths, fps)
+
+    @torch.no_grad()
+    def generate_together_frames(self, scenes, dim_pose, mean, std, *, size=(480, 480), camera=None, palette=False, style=None,
+                                 **kw):
+        """``generate_together`` followed by the world view (``motion_render.render_world``): per scene
+        ``(n, H, W, 3)`` uint8 frames (``(n, H, W)`` palette indices with ``palette``), n the length of its longest character,
+        showing every character of the scene and the union of the characters' ``scene`` primitives (already in world
+        coordinates).  ``camera`` None: one camera fitted to all scenes of the call; ``style``: a dict of ``render_world``'s
+        style arguments.  ``**kw`` goes to ``generate_together``."""
+        worlds = self.generate_together(scenes, dim_pose, mean, std, **kw)
+        return MO.to_world_frames(worlds, [MO.world_scene(s) for s in scenes], None, size, camera, palette, style)
+
+    @torch.no_grad()
+    def generate_together_gif(self, scenes, dim_pose, mean, std, *, paths=None, fps=None, size=(480, 480), camera=None,
+                              style=None, **kw):
+        """``generate_together_frames`` in palette mode followed by ``motion_render.write_gif``, as ``generate_gif``: one GIF
+        per scene, the length of its longest character."""
+        MO.check_paths(paths, len(scenes), "scene")
+        frames = self.generate_together_frames(scenes, dim_pose, mean, std, size=size, camera=camera, palette=True, style=style,
+                                               **kw)
+        return MO.to_gifs(frames, dim_pose, paths, fps)
 
     def save(self, file_name, ep, total_it):
         state = {"opt_encoder": getattr(self, "opt_encoder_state", {}), "ep": ep, "total_it": total_it,
