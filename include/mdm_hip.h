@@ -563,6 +563,33 @@ int mdm_rig_joints(const float* values, const int32_t* length, int32_t B, int32_
                    int32_t den, int32_t T_out, const int32_t* length_out, float* joints_out, float* quaternions_out,
                    void* stream);
 
+/* Rig retargeting (csrc/motion_retarget.hip): joints (B, T, J, 3), rotations (B, T, J, 3, 3) and offsets
+ * (B, J, 3) fp32 in the layout of mdm_motion_fk's outputs -> the channels of a given hierarchy of n_nodes <= 128 nodes, retimed
+ * as in mdm_rig_channels (the same integers, quaternions, slerp and Euler angles).  The target is one table of
+ * mdm_retarget_table_words() 32-bit words that motion_rig.target_rig derives: tables_host is the host copy, which is checked,
+ * tables_dev the same words on the device, which the kernels read.  Integers: [0] n_nodes, [1] J <= 32, [2] whether the legs
+ * can take IK, [4 + 6 l ..] per leg the source's hip, knee and ankle joint and the target's thigh and shin node; then 16 per
+ * node from word 16: parent, res (the nearest node at or above that has a rule, or -1), kind (0 none, 1 copy, 2 fit), src (the
+ * joint whose R is copied; a fitted node's own joint), fa, fb (a = x[fa] - x[fb]), nb <= 8 and bj[8] (b = the sum of the unit
+ * directions from x[src] to x[bj[.]]).  Floats from word 16 + 16 * 128: basis[9] row-major, the target's leg length, per leg l1,
+ * l2 and the rest unit directions of thigh and shin (8 floats); then 12 per node from float 32: OFFSET[3] and M[9] row-major.
+ * Launch 1 writes globals_out (B, T, n_nodes, 3, 3), the nodes' global rotations in the file's axes at the source frames: I
+ * where res < 0, basis^T R[src] M for a copy, basis^T F(a, b) M for a fit (F: columns e1 = unit(a), e2 = e3 x e1, e3 =
+ * unit(e1 x b); basis^T R[src] basis in a frame where a or e1 x b has no length), and with leg_ik = 1 thigh and shin turned by
+ * the two-bone IK that puts the ankle node at s basis^T x[ankle], s = the target's leg length over the sample's (offsets).
+ * Launch 2 writes channels_out (B, T_out, 3 + 3 n_nodes): s basis^T lerp(x[0]) - OFFSET[0], then per node the angles in
+ * degrees of G[parent]^T G[node] in the order axis0, axis1, axis2.  Globals at or past length[b] and channels at or past
+ * length_out[b] are zero; source frames at or past length[b] are never read.  Any T (no LDS).  MDM_ERR_ARG, before any launch: a
+ * null pointer (length and length_out excepted), T or T_out < 1, num or den < 1, axes that are no permutation, leg_ik other than
+ * 0 / 1 or 1 where the table has no legs, (T_out - 1) den > (T - 1) num, and a malformed table: n_nodes outside [1, 128], J
+ * other than the table's or above 32, a parent not smaller than its node, a res, kind, joint or node index out of range, nb
+ * outside [1, 8], a non-finite float, a leg length that is not > 0. */
+int64_t mdm_retarget_table_words(void);
+int mdm_retarget_channels(const float* joints, const float* rotations, const float* offsets, const int32_t* length, int32_t B,
+                          int32_t T, int32_t J, const int32_t* tables_host, const int32_t* tables_dev, int32_t leg_ik,
+                          int32_t axis0, int32_t axis1, int32_t axis2, int32_t num, int32_t den, int32_t T_out,
+                          const int32_t* length_out, float* globals_out, float* channels_out, void* stream);
+
 /* Motion preview (csrc/motion_render.hip): joints -> image frames.  joints (B, T, J, 3) fp32, length (B) int32 or
  * NULL (= T); of the skeleton the chains are used (group 2 + c draws the links of chain c) and J must be its joint count.
  * The image is defined in DESIGN.md §21: the scene of the reference's plot_3d_motion (floor rectangle from the clip's extent,

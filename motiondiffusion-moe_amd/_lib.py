@@ -193,6 +193,9 @@ PROTOTYPES = {
     "mdm_foot_skate": (_I32, [_P, _P, _P, _P, _I64, _P, _F64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "mdm_rig_channels": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _F32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "mdm_rig_joints": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _F32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "mdm_retarget_table_words": (_I64, []),
+    "mdm_retarget_channels": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P,
+                                     _P]),
     "mdm_motion_render_scratch_floats": (_I64, [_I32, _I32]),
     "mdm_motion_render": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P]),
     "mdm_world_extent": (_I32, [_P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),

@@ -9,7 +9,8 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .motion_features import pad_clips, skeleton_for_feats
 from .motion_render import gif_bytes, render_motion, render_world, write_gif
-from .motion_rig import DEFAULT_FPS, bvh_text, retime_ratio, rig_of, rotations_to_rig
+from .motion_rig import DEFAULT_FPS, bvh_text, retarget_to_rig, retime_ratio, rig_of, rotations_to_rig, target_bvh_text
+from .motion_rig import target_rig as make_target_rig
 from .postprocess import fk_max_frames, motion_to_joints, motion_to_joints_fk, remove_foot_skate
 
 MAX_JOINTS_FRAMES = 3276  # frames of mdm_motion_postprocess: 5 T floats of LDS per workgroup, 64 KiB
@@ -71,20 +72,36 @@ def to_joints(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotati
     return [j[i, :n] for i, n in enumerate(lens)]
 
 
-def to_bvh(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, paths, fps, fps_out, euler, scale):
+def to_bvh(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, paths, fps, fps_out, euler, scale, target_rig=None,
+           target_joint_map=None, target_up="Y", leg_ik=None):
     """Rows -> one BVH text per motion: ``joints_batch`` with rotations and no filter, one
-    ``motion_rig.rotations_to_rig`` over the padded batch, ``motion_rig.bvh_text`` per sample."""
+    ``motion_rig.rotations_to_rig`` over the padded batch, ``motion_rig.bvh_text`` per sample.  ``target_rig`` (BVH text, a
+    path, a parsed file or ``motion_rig.target_rig``'s namespace; ``target_joint_map`` / ``target_up`` as it takes them): the
+    motion goes onto that character's hierarchy instead, ``motion_rig.retarget_to_rig`` with ``leg_ik`` and
+    ``motion_rig.target_bvh_text``; its units decide, so ``scale`` is refused."""
+    if target_rig is not None:
+        if float(scale) != 1.0:
+            raise ValueError("scale does not combine with target_rig: the target's own units decide")
+        if not hasattr(target_rig, "table"):
+            target_rig = make_target_rig(target_rig, target_joint_map, target_up, skeleton=skeleton_for_feats(dim_pose))
     j, r, o, lens = joints_batch(motions, lens, dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True, offsets, True,
                                  fix_feet=fix_feet, blend=blend)
     skel = skeleton_for_feats(dim_pose)
     rig = rig_of(skel)
-    chan, lens_out = rotations_to_rig(j[:, :max(lens)], r[:, :max(lens)], torch.tensor(lens), skeleton=skel, euler=euler,
-                                      fps=fps, fps_out=fps_out, scale=scale)
+    if target_rig is None:
+        chan, lens_out = rotations_to_rig(j[:, :max(lens)], r[:, :max(lens)], torch.tensor(lens), skeleton=skel, euler=euler,
+                                          fps=fps, fps_out=fps_out, scale=scale)
+    else:
+        chan, lens_out = retarget_to_rig(j[:, :max(lens)], r[:, :max(lens)], torch.tensor(lens), target_rig, offsets=o,
+                                         skeleton=skel, euler=euler, fps=fps, fps_out=fps_out, leg_ik=leg_ik)
     num, den, fps = retime_ratio(skel, fps, fps_out)
     frame_time = den / (num * float(fps))
     chan, texts = chan.cpu(), []
     for i in range(len(lens)):
-        texts.append(bvh_text(rig, o[i], chan[i], int(lens_out[i]), frame_time, euler=euler, scale=scale))
+        if target_rig is None:
+            texts.append(bvh_text(rig, o[i], chan[i], int(lens_out[i]), frame_time, euler=euler, scale=scale))
+        else:
+            texts.append(target_bvh_text(target_rig, chan[i], int(lens_out[i]), frame_time, euler=euler))
         if paths is not None and paths[i] is not None:
             with open(paths[i], "w") as f:
                 f.write(texts[-1])

@@ -12,7 +12,11 @@ prints numbers and does no arithmetic on the motion.
 Rig import is the way back, for any hierarchy: ``parse_bvh`` / ``read_bvh`` (host, no arithmetic) ->
 ``resolve_joint_map`` (which node stands for which joint: ``JOINT_MAPS``) -> ``bvh_to_joints``, whose arithmetic (local
 rotations from the channels, slerp retiming, the walk from a node up to the root) is in ``mdm_rig_joints``
-(csrc/motion_rig_import.hip); ``bvh_to_motion`` goes on to feature rows.  No eager fallback either."""
+(csrc/motion_rig_import.hip); ``bvh_to_motion`` goes on to feature rows.  No eager fallback either.
+
+Rig retargeting writes a motion onto a given hierarchy, a character's own: ``target_rig`` (host, float64: which
+node copies which bone's rotation with which rest-pose correction, which is fitted, the legs) -> ``retarget_to_rig``, whose
+arithmetic is in ``mdm_retarget_channels`` (csrc/motion_retarget.hip) -> ``target_bvh_text``.  No eager fallback either."""
 from __future__ import annotations
 
 import ctypes as C
@@ -633,3 +637,360 @@ def bvh_to_motion(sources, mean, std, *, target_offsets=None, skeleton="t2m", **
     clips = bvh_to_joints(sources, **kw)
     rows = joints_to_motion(clips, None, mean, std, skeleton=skeleton, target_offsets=target_offsets)
     return rows, torch.tensor([int(c.shape[0]) - 1 for c in clips], dtype=torch.int64)
+
+
+# ---- rig retargeting ----
+
+MAX_TARGET_JOINTS = 32  # mapped joints of mdm_retarget_channels
+MAX_FIT_CHILDREN = 8    # children summed into b at a fitted node
+RT_NONE, RT_COPY, RT_FIT = 0, 1, 2
+_RT_I_HEAD, _RT_I_NODE, _RT_F_HEAD, _RT_F_NODE = 16, 16, 32, 12
+_RT_F_BASE = _RT_I_HEAD + _RT_I_NODE * MAX_IMPORT_NODES
+RT_WORDS = _RT_F_BASE + _RT_F_HEAD + _RT_F_NODE * MAX_IMPORT_NODES  # mdm_retarget_table_words()
+
+
+def _unit(v):
+    return v / np.linalg.norm(v)
+
+
+def across(u):
+    """The fixed unit vector across the unit vector ``u``: unit(u x e_m), m the axis of u's smallest component in absolute
+    value, the lowest index on ties.  Half a turn about it is the rule for the shortest arc between opposite directions."""
+    m = int(np.argmin(np.abs(u)))  # argmin takes the first of equal entries
+    return _unit(np.cross(u, np.eye(3)[m]))
+
+
+def shortest_arc(u, v):
+    """The rotation (3, 3) float64 that takes the unit vector ``u`` onto the unit vector ``v`` about u x v; where they are
+    opposite (1 + u.v < 1e-10), half a turn about ``across(u)``."""
+    u, v = np.asarray(u, np.float64), np.asarray(v, np.float64)
+    c = float(u @ v)
+    if 1.0 + c < 1e-10:
+        h = across(u)
+        return 2.0 * np.outer(h, h) - np.eye(3)
+    k = np.cross(u, v)
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + K + K @ K / (1.0 + c)
+
+
+def two_vector_frame(a, b):
+    """F(a, b) of §27 as a (3, 3) float64 matrix with the columns e1 = unit(a), e2 = e3 x e1, e3 = unit(e1 x b), or None where a
+    or e1 x b has no length (below 1e-9 of |a|, and of |b| for the cross product)."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    la, lb = np.linalg.norm(a), np.linalg.norm(b)
+    if not la > 0 or not lb > 0:
+        return None
+    e1 = a / la
+    c = np.cross(e1, b)
+    if not np.linalg.norm(c) > 1e-9 * lb:
+        return None
+    e3 = _unit(c)
+    return np.stack([e1, np.cross(e3, e1), e3], axis=1)
+
+
+def skeleton_legs(skeleton):
+    """Per leg (hip, knee, ankle) of a skeleton, as ``mdm_foot_skate`` finds them: the three joints above the toe joint
+    ``feet[2 l + 1]`` in the chain that ends in it."""
+    from .motion_features import get_skeleton
+    sk = get_skeleton(skeleton)
+    legs = []
+    for l in range(2):
+        ankle, toe = sk.feet[2 * l], sk.feet[2 * l + 1]
+        for c in sk.chains:
+            if len(c) >= 4 and c[-1] == toe and c[-2] == ankle:
+                legs.append((c[-4], c[-3], c[-2]))
+    if len(legs) != 2:
+        raise ValueError("the skeleton has no two legs of hip, knee, ankle and toe")
+    return legs
+
+
+def _rotation_basis(up, basis):
+    if basis is None:
+        if up not in UP_BASIS:
+            raise ValueError(f"up must be one of {sorted(UP_BASIS)}, not {up!r}")
+        basis = UP_BASIS[up]
+    basis = np.asarray(basis.detach().cpu() if torch.is_tensor(basis) else basis, dtype=np.float64)
+    if basis.shape != (3, 3) or not np.isfinite(basis).all():
+        raise ValueError("basis must be a finite 3 x 3 matrix")
+    if np.abs(basis.T @ basis - np.eye(3)).max() > 1e-6 or np.linalg.det(basis) < 0:
+        raise ValueError("basis must be a rotation (orthonormal, determinant +1): rotations are carried through it")
+    return basis
+
+
+def target_rig(source, joint_map=None, up="Y", basis=None, skeleton=None):
+    """The description of a character to put motions on.  ``source``: BVH text, a path or ``parse_bvh``'s
+    namespace (its MOTION rows are not used); ``joint_map`` as in ``resolve_joint_map``; ``up`` / ``basis`` as in
+    ``bvh_to_joints``: source world vectors are taken into the file's axes by ``basis^T``, so that importing the written file
+    with the same ``up`` gives back our world.  ``skeleton``: "t2m" / "kit", default by the number of mapped joints (22 / 21).
+    -> a namespace of ``names``, ``parent``, ``offsets`` (N, 3) in the file's units and ``end_sites``, verbatim; ``pick``
+    (``resolve_joint_map``'s; ``N + n`` is the End Site of node n, a child to point at that owns no channels); ``basis``;
+    ``rest`` (N, 3) and ``joint_rest`` (J, 3), the rest positions (sums of OFFSETs); per node ``kind`` (``RT_NONE`` it turns with
+    the node above, ``RT_COPY`` ``G = basis^T R[src] M``, ``RT_FIT`` ``G = basis^T F(cur) M``), ``res`` (the nearest node at or
+    above with a rule, or -1), ``src`` and ``M`` (N, 3, 3); ``fit`` {node: (fa, fb, [bj])}; ``legs`` / ``leg_nodes`` /
+    ``leg_rest`` ((l1, l2, u1, u2) per leg) / ``leg_ok`` / ``leg_length``; and ``table``, the ``RT_WORDS`` int32 words that
+    ``mdm_retarget_channels`` takes.  All derived in float64.
+
+    A mapped node with one mapped child at a non-zero rest distance copies that child's bone rotation, corrected by the
+    shortest arc ``A`` from its rest direction u to the source's rest axis v (``M = basis A``, A from u to ``basis^T v``;
+    ``shortest_arc`` states the rule for u = -v); with two or more it is fitted (``two_vector_frame``; a, from the pair of
+    children whose rest directions have the smallest dot product, lowest indices on ties; b, the sum of the unit directions to
+    the others, or to the two; a rest frame without length makes the node copy its lowest child instead); with none, and every
+    unmapped node, it turns with the node above.  Raises ValueError for more than ``MAX_IMPORT_NODES`` nodes or
+    ``MAX_TARGET_JOINTS`` joints, a root joint that is not on the file's root, two joints on one node, a joint whose parent
+    joint sits on an End Site, a mapped node that is not below the node of its parent joint (an End Site may end that very
+    node), a fitted node with more than ``MAX_FIT_CHILDREN + 2`` children, and legs without length."""
+    from .motion_features import get_skeleton
+    bvh = _as_bvh(source)
+    N = len(bvh.names)
+    if N > MAX_IMPORT_NODES:
+        raise ValueError(f"the target has {N} nodes: at most {MAX_IMPORT_NODES}")
+    pick = [int(p) for p in resolve_joint_map(bvh, joint_map)]
+    J = len(pick)
+    if J > MAX_TARGET_JOINTS:
+        raise ValueError(f"{J} mapped joints: at most {MAX_TARGET_JOINTS}")
+    if skeleton is None:
+        skeleton = {22: "t2m", 21: "kit"}.get(J)
+        if skeleton is None:
+            raise ValueError(f"{J} mapped joints fit no skeleton: name one")
+    sk = get_skeleton(skeleton)
+    if sk.joints != J:
+        raise ValueError(f"the joint map names {J} joints, the skeleton has {sk.joints}")
+    B = _rotation_basis(up, basis)
+    parent = [int(p) for p in bvh.parent]
+    offsets = np.asarray(bvh.offsets, np.float64).reshape(N, 3)
+    end_sites = {int(n): np.asarray(v, np.float64) for n, v in bvh.end_sites.items()}
+    if len(set(pick)) != J:
+        twice = sorted({p for p in pick if pick.count(p) > 1})
+        raise ValueError(f"the joint map puts two joints on one node: {[bvh.names[p % N] + ('/End' if p >= N else '') for p in twice]}")
+    if pick[0] != 0:
+        raise ValueError(f"the root joint must sit on the file's root node {bvh.names[0]!r}, not on {bvh.names[pick[0] % N]!r}")
+    rest = np.zeros((N, 3))  # relative to the root node: its own OFFSET moves the whole figure
+    for n in range(1, N):
+        rest[n] = rest[parent[n]] + offsets[n]
+    for p in pick:
+        if p >= N and p - N not in end_sites:
+            raise ValueError(f"pick {p}: node {p - N} has no End Site")
+    joint_rest = np.stack([rest[p] if p < N else rest[p - N] + end_sites[p - N] for p in pick])
+    node_of = [p if p < N else -1 for p in pick]
+
+    def below(n, top, or_equal=False):
+        if or_equal and n == top:
+            return True
+        n = parent[n]
+        while n >= 0:
+            if n == top:
+                return True
+            n = parent[n]
+        return False
+
+    for j in range(1, J):
+        pj = sk.parents[j]
+        if node_of[pj] < 0:
+            raise ValueError(f"joint {pj} sits on an End Site, which cannot carry joint {j} below it")
+        ok = below(node_of[j], node_of[pj]) if node_of[j] >= 0 else below(pick[j] - N, node_of[pj], or_equal=True)
+        if not ok:
+            raise ValueError(f"joint {j} on {bvh.names[pick[j] % N]!r} is not below {bvh.names[node_of[pj]]!r}, the node of its "
+                             f"parent joint {pj}: give a joint_map that follows the target's tree")
+    extent = max(float(np.abs(joint_rest).max()), 1e-30)
+    raw = np.asarray(sk.raw_offsets, np.float64)
+    kind, src, M, fit = [RT_NONE] * N, [-1] * N, np.tile(np.eye(3), (N, 1, 1)), {}
+
+    def copy_rule(n, jc):
+        v = raw[jc]
+        if not np.linalg.norm(v) > 0:
+            raise ValueError(f"joint {jc} has no rest axis in the skeleton")
+        kind[n], src[n] = RT_COPY, jc
+        M[n] = B @ shortest_arc(_unit(joint_rest[jc] - rest[n]), B.T @ _unit(v))
+
+    for j in range(J):
+        n = node_of[j]
+        if n < 0:
+            continue
+        kids = [jc for jc in range(J) if sk.parents[jc] == j and np.linalg.norm(joint_rest[jc] - rest[n]) > 1e-9 * extent]
+        if len(kids) == 1:
+            copy_rule(n, kids[0])
+        elif len(kids) >= 2:
+            dirs = {jc: _unit(joint_rest[jc] - rest[n]) for jc in kids}
+            best, pair = None, None
+            for i, ja in enumerate(kids):
+                for jb in kids[i + 1:]:
+                    d = float(dirs[ja] @ dirs[jb])
+                    if best is None or d < best:
+                        best, pair = d, (ja, jb)
+            others = [jc for jc in kids if jc not in pair] or list(pair)
+            if len(others) > MAX_FIT_CHILDREN:
+                raise ValueError(f"node {bvh.names[n]!r} has {len(kids)} mapped children: at most {MAX_FIT_CHILDREN + 2}")
+            F = two_vector_frame(joint_rest[pair[0]] - joint_rest[pair[1]], sum(dirs[jc] for jc in others))
+            if F is None:
+                copy_rule(n, kids[0])  # no rest frame: the node follows its lowest child
+            else:
+                kind[n], src[n], M[n], fit[n] = RT_FIT, j, F.T, (pair[0], pair[1], others)
+    res = []
+    for n in range(N):
+        res.append(n if kind[n] != RT_NONE else (res[parent[n]] if parent[n] >= 0 else -1))
+    legs = skeleton_legs(sk)
+    leg_nodes, leg_rest, leg_ok = [], [], True
+    for hip, knee, ankle in legs:
+        d1, d2 = joint_rest[knee] - joint_rest[hip], joint_rest[ankle] - joint_rest[knee]
+        l1, l2 = float(np.linalg.norm(d1)), float(np.linalg.norm(d2))
+        if not (l1 > 1e-9 * extent and l2 > 1e-9 * extent):
+            raise ValueError("a leg of the target has no length under this joint_map: the root cannot be rescaled")
+        leg_nodes.append((node_of[hip], node_of[knee], node_of[ankle]))
+        leg_rest.append((l1, l2, d1 / l1, d2 / l2))
+        th, sh = node_of[hip], node_of[knee]
+        leg_ok = leg_ok and min(th, sh, node_of[ankle]) >= 1 and kind[th] == RT_COPY and src[th] == knee \
+            and kind[sh] == RT_COPY and src[sh] == ankle
+    leg_length = float(np.mean([l[0] + l[1] for l in leg_rest]))
+    table = np.zeros(RT_WORDS, np.int32)
+    ftab = table.view(np.float32)[_RT_F_BASE:]
+    table[0], table[1], table[2] = N, J, int(leg_ok)
+    for l, ((hip, knee, ankle), (th, sh, _), (l1, l2, u1, u2)) in enumerate(zip(legs, leg_nodes, leg_rest)):
+        table[4 + 6 * l:9 + 6 * l] = [hip, knee, ankle, max(th, 0), max(sh, 0)]
+        ftab[10 + 8 * l:18 + 8 * l] = [l1, l2, *u1, *u2]
+    ftab[:9], ftab[9] = B.reshape(9), leg_length
+    for n in range(N):
+        row = [parent[n], res[n], kind[n], max(src[n], 0)] + [0] * 12
+        if kind[n] == RT_FIT:
+            fa, fb, others = fit[n]
+            row[4:7] = [fa, fb, len(others)]
+            row[7:7 + len(others)] = others
+        table[_RT_I_HEAD + _RT_I_NODE * n:_RT_I_HEAD + _RT_I_NODE * (n + 1)] = row
+        ftab[_RT_F_HEAD + _RT_F_NODE * n:_RT_F_HEAD + _RT_F_NODE * (n + 1)] = [*offsets[n], *M[n].reshape(9)]
+    return SimpleNamespace(names=list(bvh.names), parent=parent, offsets=offsets, end_sites=end_sites, pick=pick, n_nodes=N,
+                           joints=J, skeleton=skeleton if isinstance(skeleton, str) else None, basis=B, rest=rest,
+                           joint_rest=joint_rest, kind=kind, res=res, src=src, M=M, fit=fit, legs=legs, leg_nodes=leg_nodes,
+                           leg_rest=leg_rest, leg_ok=bool(leg_ok), leg_length=leg_length, table=table, _device={})
+
+
+def check_retarget(joints, rotations, lengths, target, offsets, skeleton="t2m", euler="ZXY", fps=None, fps_out=None, leg_ik=None):
+    """Argument checks of ``retarget_to_rig`` that need no device: -> (joints (B, T, J, 3), rotations (B, T, J, 3, 3), lengths
+    (B,) int64 or None, offsets (B, J, 3) float32, the target, the three axis indices, num, den, lengths_out (B,) int64, leg_ik
+    as a bool).  Raises ValueError."""
+    from .motion_features import get_skeleton
+    if not (isinstance(target, SimpleNamespace) and hasattr(target, "table")):
+        target = target_rig(target, skeleton=skeleton)
+    sk = get_skeleton(skeleton)
+    J = int(sk.joints)
+    if target.joints != J or (isinstance(skeleton, str) and target.skeleton not in (None, skeleton)):
+        raise ValueError(f"the target maps {target.joints} joints of {target.skeleton!r}, the motion is of {skeleton!r} ({J})")
+    axes = _axes(euler)
+    x, r = torch.as_tensor(joints), torch.as_tensor(rotations)
+    if x.dim() == 3:
+        x = x[None]
+    if r.dim() == 4:
+        r = r[None]
+    if x.dim() != 4 or tuple(x.shape[2:]) != (J, 3):
+        raise ValueError(f"joints of shape {tuple(x.shape)} must be (B, T, {J}, 3) for this skeleton")
+    B, T = x.shape[:2]
+    if tuple(r.shape) != (B, T, J, 3, 3):
+        raise ValueError(f"rotations of shape {tuple(r.shape)} must be ({B}, {T}, {J}, 3, 3)")
+    if T < 1:
+        raise ValueError("a motion needs at least 1 frame")
+    if offsets is None:
+        raise ValueError("offsets are required: the (B, J, 3) bone offsets the forward kinematics returned")
+    off = torch.as_tensor(offsets).detach().to(torch.float32)
+    if off.dim() == 2:
+        off = off[None].expand(B, J, 3)
+    if tuple(off.shape) != (B, J, 3):
+        raise ValueError(f"offsets of shape {tuple(off.shape)} must be ({J}, 3) or ({B}, {J}, 3)")
+    if leg_ik is None:
+        leg_ik = target.leg_ok
+    if leg_ik and not target.leg_ok:
+        raise ValueError("leg_ik needs hip, knee and ankle of both legs on nodes of the target, each with its one bone")
+    num, den, _ = retime_ratio(skeleton, fps, fps_out)
+    if lengths is not None:
+        lengths = L.check_lengths(lengths, B, T)
+    n = torch.full((B,), T, dtype=torch.int64) if lengths is None else lengths
+    lengths_out = (n - 1) * num // den + 1
+    if B and int(lengths_out.max()) * (3 + 3 * target.n_nodes) >= 2 ** 31:
+        raise ValueError("the retimed motion is too long")
+    return x, r, lengths, off, target, axes, num, den, lengths_out, bool(leg_ik)
+
+
+@torch.no_grad()
+def retarget_to_rig(joints, rotations, lengths, target, *, offsets, skeleton="t2m", euler="ZXY", fps=None, fps_out=None,
+                    leg_ik=None, return_globals=False):
+    """A motion onto a given character.  joints (B, T, J, 3), global rotations (B, T, J, 3, 3) and ``offsets``
+    ((B, J, 3) or (J, 3)) on a GPU, as ``motion_to_joints_fk(..., sigma=0, return_rotations=True, return_offsets=True)`` or
+    ``remove_foot_skate(..., rotations=)`` give them, and ``target``, ``target_rig``'s namespace (or what it takes) ->
+    ``(channels (B, T_out, 3 + 3 N), lengths_out (B,))`` for the N nodes of the target's own hierarchy: the root's X Y Z in the
+    file's units and axes, ``s basis^T x[0] - OFFSET[root]`` with s the target's leg length over the sample's, then three angles
+    in degrees per node in ``euler`` order, as ``rotations_to_rig`` writes them.  Bone directions are the source's wherever a
+    node has one mapped bone; unmapped nodes (fingers, twist bones) keep their rest pose.  ``leg_ik`` (default: on where the
+    target's legs allow it): thigh and shin are turned so that the ankle nodes sit at ``s basis^T x[ankle]``.  ``fps`` /
+    ``fps_out``: retimed as in ``rotations_to_rig``.  ``return_globals``: also the nodes' global rotations at the source
+    frames (B, T, N, 3, 3), zero past each length.  The arithmetic is in ``mdm_retarget_channels``
+    (csrc/motion_retarget.hip); no eager fallback."""
+    x, r, lengths, off, target, axes, num, den, lengths_out, leg_ik = check_retarget(
+        joints, rotations, lengths, target, offsets, skeleton, euler, fps, fps_out, leg_ik)
+    L.require_cuda(x, r)
+    dev = x.device
+    if r.device != dev:
+        raise ValueError("rotations must be on the joints' device")
+    x, r = x.detach().to(torch.float32).contiguous(), r.detach().to(torch.float32).contiguous()
+    off = off.to(dev).contiguous()
+    B, T, J = x.shape[:3]
+    N = target.n_nodes
+    T_out = int(lengths_out.max()) if B else 1
+    ln = None if lengths is None else lengths.to(dev, torch.int32).contiguous()
+    ln_out = lengths_out.to(dev, torch.int32).contiguous()
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in target._device:  # one small device buffer per target
+        target._device[key] = torch.from_numpy(target.table).to(dev)
+    table = np.ascontiguousarray(target.table, np.int32)
+    if table.size != L.lib().mdm_retarget_table_words():
+        raise ValueError(f"the target's table has {table.size} words, the library takes {L.lib().mdm_retarget_table_words()}")
+    chan = torch.empty(B, T_out, 3 + 3 * N, device=dev)
+    glob = torch.empty(B, T, N, 3, 3, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().mdm_retarget_channels(
+            x.data_ptr(), r.data_ptr(), off.data_ptr(), L.ptr(ln), B, T, J, table.ctypes.data_as(C.c_void_p),
+            target._device[key].data_ptr(), int(leg_ik), axes[0], axes[1], axes[2], num, den, T_out, ln_out.data_ptr(),
+            glob.data_ptr(), chan.data_ptr(), L.stream_ptr()), "mdm_retarget_channels")
+    return (chan, lengths_out, glob) if return_globals else (chan, lengths_out)
+
+
+def target_bvh_text(target, channels, n_frames, frame_time, *, euler="ZXY"):
+    """The BVH file of one sample on the target's own hierarchy, as a ``str``: the names, OFFSETs and End Sites of ``target``
+    (``target_rig``'s namespace) as they are, ``CHANNELS 6`` (X Y Z position, then the rotations in ``euler`` order) on the
+    root and ``CHANNELS 3`` on every other node, then the first ``n_frames`` rows of ``channels`` (T, 3 + 3 N) from
+    ``retarget_to_rig`` with the same ``euler``.  Numbers are printed with ``%.9g`` (``%.17g`` for float64 channels).  It does
+    no arithmetic on the motion."""
+    axes = _axes(euler)
+    N = target.n_nodes
+    ch = channels.detach().cpu().numpy() if torch.is_tensor(channels) else np.asarray(channels)
+    if ch.dtype not in (np.float32, np.float64):
+        ch = ch.astype(np.float32)
+    if ch.ndim != 2 or ch.shape[1] != 3 + 3 * N:
+        raise ValueError(f"channels of shape {ch.shape} must be (T, {3 + 3 * N}) for this target")
+    n_frames = int(n_frames)
+    if not 0 <= n_frames <= ch.shape[0]:
+        raise ValueError(f"n_frames must lie in [0, {ch.shape[0]}]")
+    if not (np.isfinite(float(frame_time)) and float(frame_time) > 0):
+        raise ValueError("frame_time must be > 0")
+    fmt = "%.17g" if ch.dtype == np.float64 else "%.9g"
+    kids = [[] for _ in range(N)]
+    for n in range(1, N):
+        kids[target.parent[n]].append(n)
+    rot = " ".join("XYZ"[a] + "rotation" for a in axes)
+    out = ["HIERARCHY"]
+
+    def vec(v):
+        return " ".join(fmt % float(e) for e in v)
+
+    def node(n, depth):
+        pad = "  " * depth
+        out.append(f"{pad}{'ROOT' if n == 0 else 'JOINT'} {target.names[n]}")
+        out.append(pad + "{")
+        out.append(f"{pad}  OFFSET {vec(target.offsets[n])}")
+        out.append(f"{pad}  CHANNELS 6 Xposition Yposition Zposition {rot}" if n == 0 else f"{pad}  CHANNELS 3 {rot}")
+        for k in kids[n]:
+            node(k, depth + 1)
+        if n in target.end_sites:
+            out.extend([f"{pad}  End Site", pad + "  {", f"{pad}    OFFSET {vec(target.end_sites[n])}", pad + "  }"])
+        out.append(pad + "}")
+
+    node(0, 0)
+    out.extend(["MOTION", f"Frames: {n_frames}", "Frame Time: %.9g" % float(frame_time)])
+    out.extend(" ".join([fmt % v for v in row]) for row in ch[:n_frames].tolist())
+    return "\n".join(out) + "\n"

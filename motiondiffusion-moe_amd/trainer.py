@@ -353,17 +353,20 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_bvh(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, paths=None, fps=None, fps_out=None,
-                     euler="ZXY", scale=1.0, offsets=None, fix_feet=False, blend=5, **kw):
+                     euler="ZXY", scale=1.0, offsets=None, fix_feet=False, blend=5, target_rig=None, target_joint_map=None,
+                     target_up="Y", leg_ik=None, **kw):
         """``generate`` followed by forward kinematics and the rig export (``motion_rig``): one BVH text per
         sample, written to ``paths[i]`` where given.  ``fps`` (default 20 at dim_pose 263, 12.5 at 251) / ``fps_out``: retimed
         to the frame rate a tool works at; ``euler``: the channels' rotation order; ``scale``: of positions and offsets (100
         for centimetres).  ``offsets`` / ``fix_feet`` / ``blend`` as in ``generate_rotations``, ``**kw`` as for ``generate``:
         with ``edit_bvh=`` / ``edit_mask=`` a file from a rig is continued and written back as one (converted under this
-        call's ``mean`` / ``std``)."""
+        call's ``mean`` / ``std``).  ``target_rig`` (BVH text, a path or ``motion_rig.target_rig``'s namespace; with
+        ``target_joint_map`` / ``target_up``, and ``leg_ik``): the motion is written onto that character's own hierarchy
+        (``motion_rig.retarget_to_rig``) in its units, so ``scale`` is refused."""
         MO.check_paths(paths, len(caption), "caption")
         motions = self.generate(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)  # unused without an edit or control
         return MO.to_bvh(motions, MO.valid_lengths(motions, m_lens), dim_pose, mean, std, offsets, fix_feet, blend, paths, fps,
-                         fps_out, euler, scale)
+                         fps_out, euler, scale, target_rig, target_joint_map, target_up, leg_ik)
 
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
@@ -451,14 +454,16 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_long_bvh(self, scripts, dim_pose, mean, std, *, paths=None, fps=None, fps_out=None, euler="ZXY", scale=1.0,
-                          offsets=None, fix_feet=False, feet_blend=5, **kw):
+                          offsets=None, fix_feet=False, feet_blend=5, target_rig=None, target_joint_map=None, target_up="Y",
+                          leg_ik=None, **kw):
         """``generate_long`` followed by forward kinematics over each whole canvas and the rig export, as ``generate_bvh``:
         one BVH text per motion (at most ``postprocess.fk_max_frames()`` canvas frames).  ``feet_blend`` is ``generate_bvh``'s
-        ``blend`` (``blend`` is ``generate_long``'s here); ``**kw`` as for ``generate_long``."""
+        ``blend`` (``blend`` is ``generate_long``'s here); ``target_rig`` / ``target_joint_map`` / ``target_up`` / ``leg_ik`` as
+        in ``generate_bvh``; ``**kw`` as for ``generate_long``."""
         MO.check_paths(paths, len(scripts), "motion")
         motions = self._long_motions(scripts, dim_pose, mean, std, MO.canvas_frame_limit(True), "forward kinematics", kw)
         return MO.to_bvh(motions, MO.valid_lengths(motions), dim_pose, mean, std, offsets, fix_feet, feet_blend, paths, fps,
-                         fps_out, euler, scale)
+                         fps_out, euler, scale, target_rig, target_joint_map, target_up, leg_ik)
 
     @torch.no_grad()
     def generate_frames(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, size=(480, 480), camera=None,
