@@ -861,6 +861,9 @@ enum MdmVariant {
 /* One more value of the same knob, kept apart from the enum above, whose values (all below 128) are a closed set that
  * tests/test_abi.py pins: the MoE router as its own three launches, not inside the stylization launch in front of the block. */
 enum MdmRouteVariant { MDM_VAR_ROUTE_LAUNCH = 171 };
+/* Likewise: the dual block's skip projection as its own GEMM launch, not on the idle CUs of its first Performer's pair + tail
+ * launch. */
+enum MdmSkipVariant { MDM_VAR_SKIP_LAUNCH = 172 };
 int mdm_set_gemm_variant(int variant);
 
 /* Measurement probe for bench.py: while enabled, every launch of the dominant kernel (the fused expert MLP inside

@@ -65,6 +65,7 @@ int mdm_set_gemm_variant(int v) {
     case MDM_VAR_STREAM3_NEVER:
     case MDM_VAR_STREAM3_ALWAYS:
     case MDM_VAR_ROUTE_LAUNCH:
+    case MDM_VAR_SKIP_LAUNCH:
       mdm::g_variant = v;
       return MDM_OK;
     default:

@@ -76,6 +76,18 @@ int gemm_stream3x(const GemmArgs& a, hipStream_t stream);
 // mlp_stream.hip: the same MLP with the weights streamed global -> registers from a packed fragment stream
 bool fused_mlp_stream_supported(const MdmMlpDesc& a);
 int fused_mlp_stream(const MdmMlpDesc& a, hipStream_t stream);
+// work that rides on the CUs a pair + tail launch leaves idle (csrc/mlp_stream.hip: skip_rider): C = GELU(X W^T + bias) for a
+// D x D Linear at D = 512, with the arithmetic of the tile GEMM launch it replaces (csrc/gemm2.hip)
+struct SkipRider {
+  const uint16_t* X;  // 16-bit rows [M, 512]
+  int64_t ldx;
+  const uint16_t* W;  // the weight's row-major 16-bit plane [512, ldw] (MdmPacked.hi / .ld)
+  int64_t ldw;
+  const float* bias;  // [512]
+  float* C;           // fp32 [M, 512]
+  int64_t ldc;
+  int M;
+};
 // the Performer tail behind the proj_out pair, in the pair's launch (csrc/mlp_stream.hip: pair_tail)
 struct PairTail {
   const float *pw, *pb;   // post_norm
@@ -95,9 +107,13 @@ struct PairTail {
   const float* skip;      // [M, D] fp32, or NULL
   float skip_scale;
   const float *l2w, *l2b;
+  // optional (host side only; NULL: none, the launch as it is without): independent work for the launch's idle CUs
+  const SkipRider* rider;
 };
 bool fused_pair_style_supported(const MdmMlpDesc& a);
-int fused_pair_style(const MdmMlpDesc& a, const PairTail& t, hipStream_t stream);
+// rode: whether t.rider was taken into the launch (only where the idle CUs finish it in at most two items each); if not, the
+// caller launches that work itself
+int fused_pair_style(const MdmMlpDesc& a, const PairTail& t, hipStream_t stream, bool* rode = nullptr);
 int64_t mlp_stream_elems(int G, int F, int Din, int Dout);
 int mlp_stream_pack(const float* w1, const float* w2, int G, int F, int Din, int Dout, int h16, uint16_t* out, hipStream_t stream);
 // style_gemm.hip: stylization input + its D x D Linear + the residual in one launch (streamed weights)

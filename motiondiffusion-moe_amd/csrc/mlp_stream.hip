@@ -383,9 +383,11 @@ __device__ __forceinline__ void pair_tail(const PairTail& st, f32x4 (&y)[RT][4],
   }
 }
 
+// The tile walk of one persistent workgroup: workgroup wg of nwg takes tiles remap(wg), remap(wg) + nwg, ...  (nwg is the launch's
+// grid, or the tile workgroups' share of it where riders fill the rest: pair_tail_rider_kernel)
 // TAIL: 0 = the fused pair alone, 1 = the pair + the Performer tail (post-norm, stylization, out_layers.2, residual) behind it
 template <typename HT, int RT, int NJ, int DIN, int TAIL>
-__global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDesc g, const int tile_h, const PairTail st) {
+__device__ __forceinline__ void mlp_stream_tiles(const MdmMlpDesc& g, const int tile_h, const PairTail& st, const int wg, const int nwg) {
   typedef typename HT::frag_t frag_t;
   static_assert(!TAIL || (NJ == 4 && DIN == 512 && RT <= 4), "the tail is written for D = 512 rows");
   typedef XGeo<RT, DIN, NJ, TAIL != 0> G;
@@ -407,9 +409,9 @@ __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDes
     lds_barrier();
   }
 
-  // Persistent over tiles: workgroup b takes tiles remap(b), remap(b) + grid, ...; round k hands an XCD a contiguous range of
+  // Persistent over tiles: workgroup b takes tiles remap(b), remap(b) + nwg, ...; round k hands an XCD a contiguous range of
   // tiles (~1 group: its weights stay in that XCD's L2).
-  for (int mt = xcd_remap(blockIdx.x, gridDim.x);; mt += gridDim.x) {
+  for (int mt = xcd_remap(wg, nwg);; mt += nwg) {
     // the thread id is made opaque per tile (and again per chunk / for the epilogue): otherwise every lane-constant address of
     // the body is hoisted out of this loop and lives in (spilled) registers across it; recomputing is a few instructions
     int tid = threadIdx.x;
@@ -608,6 +610,129 @@ __global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDes
   }
 }
 
+template <typename HT, int RT, int NJ, int DIN, int TAIL>
+__global__ __launch_bounds__(NT, 2) void fused_mlp_stream_kernel(const MdmMlpDesc g, const int tile_h, const PairTail st) {
+  mlp_stream_tiles<HT, RT, NJ, DIN, TAIL>(g, tile_h, st, blockIdx.x, gridDim.x);
+}
+
+// ---- the skip rider: DualSelfAttentionBlock's skip = GELU(Lin(x)) (fast_attention.py:219-225) on the CUs the pair + tail launch of
+// the block's first Performer leaves idle (196 tiles on 256 CUs at both time scales) -------------------------------------------
+// Rider r of nr takes the items r, r + nr, ...: 112 rows x all 512 columns, the waves split the columns (64 each: 28 accumulators).
+// The 16-bit rows are the shared operand: resident in LDS in the X image layout of the tiles (16-B chunk c of row m at slot
+// c ^ (m & 15)).  The weights are private to a wave: global -> registers straight from the ROW-MAJOR 16-bit plane (lane l of
+// fragment (column tile, K step s) holds W[16 ct + (l & 15)][32 s + 8 (l >> 4) ..]: one 16-byte load, as csrc/proj_phase.h reads
+// q | k | v) through a ring four K steps ahead.  An output element goes through the arithmetic of the tile GEMM launch this
+// replaces (csrc/gemm2.hip with ACT_GELU, alpha = out_scale = r1_scale = 1, no residual): the same MFMA with the weight fragment as
+// A, from zero over K in ascending steps of 32, then gelu_erf2(acc + bias) -- so a block's output does not depend on whether its
+// shape got riders.
+constexpr int RIDER_RT = 7, RIDER_ROWS = RIDER_RT * 16, RIDER_SMEM = RIDER_ROWS * 1024;
+
+template <typename HT>
+__device__ __forceinline__ void skip_rider(const SkipRider& rd, const int r, const int nr) {
+  typedef typename HT::frag_t frag_t;
+  extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
+  constexpr int RT = RIDER_RT, NR = 16, AHEAD = NR / 4;  // weight ring: 4 column tiles x AHEAD K steps
+  const int items = (rd.M + RIDER_ROWS - 1) / RIDER_ROWS;
+#pragma unroll 1
+  for (int it = r; it < items; it += nr) {
+    // lane-constant addresses are recomputed per item from an opaque thread id (see mlp_stream_tiles)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, frow = lane & 15, fq = lane >> 4;
+    const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int row0 = it * RIDER_ROWS;
+    // fragment (j, s) of this wave: wp + j * jst + 64 s
+    const uint8_t* const wp = (const uint8_t*)(rd.W + (int64_t)(wn * 64 + frow) * rd.ldw + 8 * fq);
+    const int64_t jst = 32 * rd.ldw;
+    frag_t R[NR];
+#pragma unroll
+    for (int f = 0; f < NR; ++f) R[f] = ldg<frag_t>(wp + (f & 3) * jst + (f >> 2) * 64);
+
+    // ---- rows -> LDS: wave w < 7 brings rows 16 w .. 16 w + 15; one instruction = 8 rows x one 128-B line; rows past M: copies
+    // of the last row, never stored
+    if (wn < RT) {
+      const uint8_t* xp[2];
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        int srow = row0 + 16 * wn + 8 * hf + (lane >> 3);
+        srow = srow < rd.M ? srow : rd.M - 1;
+        xp[hf] = (const uint8_t*)(rd.X + (int64_t)srow * rd.ldx) + (lane & 7) * 16;
+      }
+      uint4 v[2][8];
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) v[hf][c] = ldg<uint4>(xp[hf] + c * 128);
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          const int rr = 16 * wn + 8 * hf + (lane >> 3);
+          const int ch = (8 * c + (lane & 7)) ^ (rr & 15);
+          *(uint4*)(smem + rr * 1024 + (ch << 4)) = v[hf][c];
+        }
+    }
+    f32x4 y[RT][4];
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) y[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    lds_barrier();
+    {
+      const int xb = frow * 1024 + ((fq ^ frow) << 4);  // (row frow, K step 0); step s reads chunk (4 s + fq) ^ frow
+      frag_t A[2][RT];
+#pragma unroll
+      for (int i = 0; i < RT; ++i) A[0][i] = *(const frag_t*)(smem + xb + i * 16384);
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {
+        if (s + 1 < 16) {
+#pragma unroll
+          for (int i = 0; i < RT; ++i) A[(s + 1) & 1][i] = *(const frag_t*)(smem + (xb ^ (64 * ((s + 1) & 3))) + ((s + 1) >> 2) * 256 + i * 16384);
+        }
+        const int sn = s + AHEAD < 16 ? s + AHEAD : 15;  // past the end: the last K step again, never used
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int slot = (s * 4 + j) & (NR - 1);
+#pragma unroll
+          for (int i = 0; i < RT; ++i) y[i][j] = HT::mfma16(R[slot], A[s & 1][i], y[i][j]);
+          R[slot] = ldg<frag_t>(wp + j * jst + sn * 64);
+        }
+        pin();
+      }
+    }
+    // straight from the accumulators: a lane holds 4 consecutive columns of one row (16-byte stores)
+    int te = threadIdx.x;
+    asm volatile("" : "+v"(te));
+    const int er = te & 15, eq = (te & 63) >> 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = wn * 64 + 16 * j + 4 * eq;
+      const f32x4 bb = *(const f32x4*)(rd.bias + n);
+#pragma unroll
+      for (int i = 0; i < RT; ++i) {
+        const int m = row0 + i * 16 + er;
+        const f32x2 a = gelu_erf2((f32x2){y[i][j][0] + bb[0], y[i][j][1] + bb[1]});
+        const f32x2 b = gelu_erf2((f32x2){y[i][j][2] + bb[2], y[i][j][3] + bb[3]});
+        // (+ 0: the launch this replaces adds its absent residuals, which turns a -0 into +0)
+        if (m < rd.M) *(f32x4*)(rd.C + (int64_t)m * rd.ldc + n) = (f32x4){a[0] + 0.f, a[1] + 0.f, b[0] + 0.f, b[1] + 0.f};
+      }
+    }
+    lds_barrier();  // every wave is past its reads of this item's rows before the next item's land
+  }
+}
+
+// The pair + tail launch with riders: workgroups [0, ntile_wg) walk the tiles exactly as fused_mlp_stream_kernel<HT, RT, 4, 512, 1>
+// does on a grid of ntile_wg, the others compute the skip projection and leave.  No workgroup waits for another.
+template <typename HT, int RT>
+__global__ __launch_bounds__(NT, 2) void pair_tail_rider_kernel(const MdmMlpDesc g, const int tile_h, const PairTail st, const SkipRider rd,
+                                                                const int ntile_wg) {
+  if ((int)blockIdx.x < ntile_wg) {
+    mlp_stream_tiles<HT, RT, 4, 512, 1>(g, tile_h, st, blockIdx.x, ntile_wg);
+  } else {
+    skip_rider<HT>(rd, (int)blockIdx.x - ntile_wg, (int)gridDim.x - ntile_wg);
+  }
+}
+
 // ---- weight stream packing: fp32 row-major expert weights -> the per-(group, wave) fragment stream ----------------------
 // One fragment = 64 lanes x 8 elements: lane l holds row (l & 15), k = 8 (l >> 4) + e of a 16 x 32 block (the MFMA A operand).
 // With f1 = 2 Din/32 (phase-1 fragments per chunk), q = 4 NJ (phase-2 fragments per half), C = F / 256 chunks, the stream of
@@ -761,12 +886,60 @@ bool fused_pair_style_supported(const MdmMlpDesc& a) {
   return fused_mlp_stream_supported(a) && a.Din == 512 && a.Dout == 512 && !a.goff && !a.gather && !a.rowscale && !a.R1 && !a.R2;
 }
 
-int fused_pair_style(const MdmMlpDesc& a, const PairTail& t, hipStream_t stream) {
+// the same launch with `riders` more workgroups behind the tile workgroups (pair_tail_rider_kernel)
+template <int RT>
+static int launch_riders(const MdmMlpDesc& a, int th, hipStream_t stream, const PairTail& tail, int ntile_wg, int riders) {
+  constexpr int tile_smem = XGeo<RT, 512, 4, true>::SMEM + 512;
+  constexpr int smem = tile_smem > RIDER_SMEM ? tile_smem : RIDER_SMEM;
+  static_assert(smem <= 160 * 1024, "one CU's LDS");
+  static DevOnce attr;
+  if (!attr) {
+    if (hipFuncSetAttribute((const void*)pair_tail_rider_kernel<HB, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess ||
+        hipFuncSetAttribute((const void*)pair_tail_rider_kernel<HF, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
+      return MDM_ERR_LAUNCH;
+    attr = true;
+  }
+  if (a.h16 == MDM_H16_F16) {
+    hipLaunchKernelGGL((pair_tail_rider_kernel<HF, RT>), dim3(ntile_wg + riders), dim3(NT), smem, stream, a, th, tail, *tail.rider, ntile_wg);
+  } else {
+    hipLaunchKernelGGL((pair_tail_rider_kernel<HB, RT>), dim3(ntile_wg + riders), dim3(NT), smem, stream, a, th, tail, *tail.rider, ntile_wg);
+  }
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+// How many rider workgroups the launch takes (0: none).  The riders get the CUs the tile workgroups leave idle, so the whole grid
+// stays one workgroup per CU, and they are taken only where each finishes in at most two items: with fewer idle CUs the riders
+// would outlast the tiles.  Shapes and the device only, never data.
+static int rider_count(const MdmMlpDesc& a, int th, const SkipRider& r, int& ntile_wg) {
+  const int cus = device_cus();
+  const int tiles = a.M / th + 1;  // as launch_stream counts them (dense: one group)
+  ntile_wg = tiles < cus ? tiles : cus;
+  if (!r.X || !r.W || !r.bias || !r.C || r.M < 1 || (r.ldx % 8) || (r.ldw % 8) || r.ldw < 512 || (r.ldc & 3) ||
+      ((((uintptr_t)r.X) | ((uintptr_t)r.W) | ((uintptr_t)r.bias) | ((uintptr_t)r.C)) & 15))
+    return 0;
+  const int items = (r.M + RIDER_ROWS - 1) / RIDER_ROWS;
+  const int riders = cus - ntile_wg < items ? cus - ntile_wg : items;
+  if (riders < 1 || (items + riders - 1) / riders > 2) return 0;
+  return riders;
+}
+
+int fused_pair_style(const MdmMlpDesc& a, const PairTail& t, hipStream_t stream, bool* rode) {
+  if (rode) *rode = false;
   if (!a.X || !fused_pair_style_supported(a)) return MDM_ERR_UNSUPPORTED;
   if (!t.pw || !t.pb || !t.sw || !t.sb || !t.sc || t.S <= 0 || !t.ws || !t.bias || !t.resid || !t.out || (t.ln16 && (!t.lw || !t.lb)) ||
       ((uintptr_t)t.ws & 15) || (t.skip && (!t.lw || !t.lb)) || (t.l2w && (!t.l2b || !t.ln16 || !t.skip)))
     return MDM_ERR_ARG;
   const int th = mlp_stream_tile_h(a.M, 4);  // the tail stages fp32 rows: 64-row tiles at most
+  if (t.rider && rode) {
+    int ntile_wg;
+    const int riders = rider_count(a, th, *t.rider, ntile_wg);
+    if (riders) {
+      const int rc = th <= 32 ? launch_riders<2>(a, th, stream, t, ntile_wg, riders) : launch_riders<4>(a, th, stream, t, ntile_wg, riders);
+      *rode = rc == MDM_OK;
+      return rc;
+    }
+  }
   if (th <= 32) return launch_stream<2, 512, 1>(a, th, stream, t);
   return launch_stream<4, 512, 1>(a, th, stream, t);
 }

@@ -312,8 +312,10 @@ PerfCore perf_core_path(const Ctx& c, const MdmPerformer& p, bool xn16) {
 // PerformerSelfAttention (fast_attention.py:137-179): xn = pre_norm(x) already computed; out = x + 0.1*style(...)
 // pt: the caller's LayerNorms / block tail behind it (csrc/gemm.h StyleTail3) where proj_path() / style_path() say they run; the
 // 16-bit modes' pair_tail (csrc/mlp_stream.hip) writes ln_out as 16-bit rows
+// rider / rode: independent work offered to the idle CUs of the pair + tail launch, and whether it was taken (csrc/gemm.h)
 int performer(const Ctx& c, const MdmPerformer& p, const float* x, Act xn, const float* sc, float* out,
-              const StyleTail3& pt = StyleTail3()) {
+              const StyleTail3& pt = StyleTail3(), const SkipRider* rider = nullptr, bool* rode = nullptr) {
+  if (rode) *rode = false;
   const MdmModel& m = *c.m;
   const int D = m.D, H = m.H, dh = D / H, mf = dh;  // m = min(dh, 256) = dh for dh <= 256
   const Work& w = c.w;
@@ -398,7 +400,8 @@ int performer(const Ctx& c, const MdmPerformer& p, const float* x, Act xn, const
       t.pw = p.post_w, t.pb = p.post_b, t.sw = p.style.norm_w, t.sb = p.style.norm_b, t.sc = sc, t.S = c.S;
       t.ws = p.style.out_ws, t.bias = p.style.out_b, t.resid = x, t.out_scale = 0.1f, t.out = out;
       t.lw = pt.lw, t.lb = pt.lb, t.ln16 = (uint16_t*)pt.ln_out, t.skip = pt.skip, t.skip_scale = pt.skip_scale, t.l2w = pt.l2w, t.l2b = pt.l2b;
-      return fused_pair_style(proj_pair_desc(c, p), t, c.s);
+      t.rider = rider;
+      return fused_pair_style(proj_pair_desc(c, p), t, c.s, rode);
     }
     case ProjPath::PAIR:
       MDM_TRY(fused_mlp_stream(proj_pair_desc(c, p), c.s));
@@ -448,18 +451,25 @@ int dual_block(const Ctx& c, const MdmLayer& l, const float* x, const uint16_t* 
   const Act xa = c.bf ? act_bf16(x16) : act_f32(x);
   LinOpts so;  // skip = GELU(Lin(x))                                (:219-225)
   so.act = ACT_GELU;
-  switch (dual_tail_path(c, l)) {
+  const DualTail path = dual_tail_path(c, l);
+  switch (path) {
     case DualTail::T16:
     case DualTail::T3: {
-      // skip is computed FIRST (into the FFN's hidden buffer, free during this block), and the second Performer's launch ends
+      // skip is computed into the FFN's hidden buffer (free during this block), and the second Performer's launch ends
       // with out = post_norm(skip + 0.1 * global_out) and the next block's pre-norm -- no D x D GEMM waiting behind the
-      // attention chain, no LayerNorm launch behind that
-      MDM_TRY(linear(c, xa, c.M, D, l.skip, l.skip_b, D, w.f1, nullptr, so));
+      // attention chain, no LayerNorm launch behind that.  T16: nothing but that tail reads skip and nothing in the block
+      // writes x16, so the first Performer's pair + tail launch is offered the projection for its idle CUs (riders,
+      // csrc/mlp_stream.hip; MDM_VAR_SKIP_LAUNCH: not); where it declines, or on T3, skip is a launch of its own
+      const bool offer = path == DualTail::T16 && g_variant != MDM_VAR_SKIP_LAUNCH;
+      const SkipRider sr = {x16, D, l.skip.hi, l.skip.ld, l.skip_b, w.f1, D, (int)c.M};
+      bool rode = false;
+      if (!offer) MDM_TRY(linear(c, xa, c.M, D, l.skip, l.skip_b, D, w.f1, nullptr, so));
       // h = pre_norm(x) -> t1 ; local.pre_norm(h) -> t3
       MDM_TRY(ln_chain(x, c.M, D, l.dual_pre_w, l.dual_pre_b, w.t1, 0, l.local.pre_w, l.local.pre_b, w.t3, xnf, c.s));
       StyleTail3 pt;  // local_out -> t5, global.pre_norm(local_out) -> t3 (t3 is dead by then)
       pt.lw = l.global.pre_w, pt.lb = l.global.pre_b, pt.ln_out = w.t3, pt.ln_x2 = c.x2;
-      MDM_TRY(performer(c, l.local, w.t1, act_x2(c, w.t3), sc4 + 0 * scs, w.t5, pt));
+      MDM_TRY(performer(c, l.local, w.t1, act_x2(c, w.t3), sc4 + 0 * scs, w.t5, pt, offer ? &sr : nullptr, &rode));
+      if (offer && !rode) MDM_TRY(linear(c, xa, c.M, D, l.skip, l.skip_b, D, w.f1, nullptr, so));
       StyleTail3 bt;
       bt.skip = w.f1, bt.skip_scale = 0.1f, bt.lw = l.dual_post_w, bt.lb = l.dual_post_b;
       if (next_w) bt.l2w = next_w, bt.l2b = next_b, bt.ln_out = w.t2, bt.ln_x2 = c.x2;
