@@ -864,6 +864,8 @@ enum MdmRouteVariant { MDM_VAR_ROUTE_LAUNCH = 171 };
 /* Likewise: the dual block's skip projection as its own GEMM launch, not on the idle CUs of its first Performer's pair + tail
  * launch. */
 enum MdmSkipVariant { MDM_VAR_SKIP_LAUNCH = 172 };
+/* Likewise: no launch touches the weights of the launch behind it (csrc/warm.h); the results are the same either way. */
+enum MdmWarmVariant { MDM_VAR_NO_WARM = 173 };
 int mdm_set_gemm_variant(int variant);
 
 /* Measurement probe for bench.py: while enabled, every launch of the dominant kernel (the fused expert MLP inside

@@ -66,6 +66,7 @@ int mdm_set_gemm_variant(int v) {
     case MDM_VAR_STREAM3_ALWAYS:
     case MDM_VAR_ROUTE_LAUNCH:
     case MDM_VAR_SKIP_LAUNCH:
+    case MDM_VAR_NO_WARM:
       mdm::g_variant = v;
       return MDM_OK;
     default:

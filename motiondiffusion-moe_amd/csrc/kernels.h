@@ -1,6 +1,7 @@
 // Internal launchers of the non-GEMM kernels (rowwise.hip).  All are stream-ordered, allocation free.
 #pragma once
 #include "mdm_common.h"
+#include "warm.h"
 
 namespace mdm {
 
@@ -48,7 +49,7 @@ bool perf_attn_supported(int dh, int S);
 bool perf_attn_qkv_supported(int dh, int S, int H);
 int perf_attn_qkv(const uint16_t* xn, const uint16_t* wqkv, int ldw, const float* bias, float alpha, uint16_t* qscratch, int h16,
                   const uint16_t* PT, int ldp, const float* hn_w, const float* hn_b, const int* len, int B, int S, int H, int dh,
-                  uint16_t* out, hipStream_t s);
+                  uint16_t* out, hipStream_t s, const Warm* warm = nullptr);  // warm: what the next launch reads first (csrc/warm.h)
 int perf_attn(const void* qkv, int h16, const uint16_t* PT, int ldp, const float* hn_w, const float* hn_b, const int* len, int B,
               int S, int H, int dh, uint16_t* out, hipStream_t s);
 // perf_attn2.hip: the same core at head_dim 256 (big model) in two launches (feature maps; KV state + num + LN); scratch:

@@ -296,6 +296,8 @@ ProjPath proj_path(const Ctx& c, const MdmPerformer& p) {
 // the core's launch, k and v never leave the CU (MDM_VAR_QKV_SPLIT: CORE16).  CORE16: LN/L2 -> feature maps -> KV state ->
 // num/den -> LN in ONE kernel per (batch, head).  CHAIN: five launches (MDM_VAR_GENERIC_DH256 at head_dim 256).
 enum class PerfCore { CORE3, CORE256, CORE16_QKV, CORE16, CHAIN };
+// weight warming (csrc/warm.h) is on unless the knob says otherwise: MDM_VAR_NO_WARM leaves every Warm empty
+inline bool warm_on() { return g_variant != MDM_VAR_NO_WARM; }
 PerfCore perf_core_path(const Ctx& c, const MdmPerformer& p, bool xn16) {
   const int D = c.m->D, H = c.m->H, dh = D / H;
   if (c.bf && g_variant != MDM_VAR_GENERIC_DH256 && perf_attn256_supported(dh, c.S) &&
@@ -338,10 +340,20 @@ int performer(const Ctx& c, const MdmPerformer& p, const float* x, Act xn, const
       MDM_TRY(linear(c, xn, c.M, D, p.qkv, p.qkv_b, 3 * D, nullptr, (uint16_t*)w.qkv, qo));
       MDM_TRY(perf_attn256(w.qkv, c.h16, p.feat.hi, (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, (uint16_t*)w.t4, w.phi, c.s));
       break;
-    case PerfCore::CORE16_QKV:
+    case PerfCore::CORE16_QKV: {
+      // the core warms what the pair + tail launch behind it reads first (csrc/warm.h): the pair's stream, the stream of
+      // out_layers.2, the plane its riders read, then the biases on its dependent chain
+      Warm wm = {};
+      if (warm_on() && proj_path(c, p) == ProjPath::PAIR_TAIL) {
+        warm_add(wm, p.proj_ws, 2 * (int64_t)D * D * 2);
+        warm_add(wm, p.style.out_ws, (int64_t)D * D * 2);
+        if (rider) warm_add(wm, rider->W, (int64_t)D * rider->ldw * 2);
+        warm_add(wm, p.proj0_b, D * 4), warm_add(wm, p.proj3_b, D * 4), warm_add(wm, p.style.out_b, D * 4);
+      }
       MDM_TRY(perf_attn_qkv((const uint16_t*)xn.p, p.qkv.hi, (int)p.qkv.ld, p.qkv_b, 0.1f, (uint16_t*)w.qkv, c.h16, p.feat.hi,
-                            (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, dh, (uint16_t*)w.t4, c.s));
+                            (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, dh, (uint16_t*)w.t4, c.s, &wm));
       break;
+    }
     case PerfCore::CORE16:  // (:44-90)
       MDM_TRY(linear(c, xn, c.M, D, p.qkv, p.qkv_b, 3 * D, nullptr, (uint16_t*)w.qkv, qo));
       MDM_TRY(perf_attn(w.qkv, c.h16, p.feat.hi, (int)p.feat.ld, p.hn_w, p.hn_b, c.len, c.B, c.S, H, dh, (uint16_t*)w.t4, c.s));

@@ -55,7 +55,7 @@ template <typename HT, int QMT>  // QMT: 0 = q | k | v rows read from memory; 7 
 __global__ __launch_bounds__(NTH) void perf_attn_kernel(uint16_t* __restrict__ qkv, const uint16_t* __restrict__ PT,
                                                            int ldp, const float* __restrict__ hn_w,
                                                            const float* __restrict__ hn_b, const int* __restrict__ len,
-                                                           int S, int H, uint16_t* __restrict__ out, const PerfQkv qa) {
+                                                           int S, int H, uint16_t* __restrict__ out, const PerfQkv qa, const Warm wm) {
   typedef typename HT::frag_t frag_t;
   constexpr bool QKV = QMT > 0;
   extern __shared__ __attribute__((aligned(1024))) uint8_t smem_raw[];
@@ -250,6 +250,8 @@ __global__ __launch_bounds__(NTH) void perf_attn_kernel(uint16_t* __restrict__ q
 #pragma unroll
   for (int i = 0; i < MAXT; ++i)  // k registers are free: request the q rows now, they land during the V / KV phases
     if (wid + NW * i < ntile) raw_load(0, wid + NW * i, kq[i]);
+  // the last rows are requested: touch what the next launch reads first (csrc/warm.h); the V, KV and Q phases are still ahead
+  const WarmTok wtok = warm_touch(wm, blockIdx.x, gridDim.x, tid, NTH);
   __syncthreads();  // kphi^T complete
 
   // ---- V: v^T[d][t] ------------------------------------------------------------------------------
@@ -389,6 +391,7 @@ __global__ __launch_bounds__(NTH) void perf_attn_kernel(uint16_t* __restrict__ q
       }
     }
   }
+  warm_done(wtok);
 }
 
 }  // namespace
@@ -400,7 +403,7 @@ bool perf_attn_qkv_supported(int dh, int S, int H) { return dh == DH && H == 4 &
 namespace {
 template <int QMT>
 int launch_perf_attn(uint16_t* qkv, int h16, const uint16_t* PT, int ldp, const float* hn_w, const float* hn_b, const int* len, int B,
-                     int S, int H, uint16_t* out, const PerfQkv& qa, hipStream_t s) {
+                     int S, int H, uint16_t* out, const PerfQkv& qa, const Warm& wm, hipStream_t s) {
   const int TP = (S + 31) & ~31, TS = TP + 8;
   const int vreg = (TP * DH > MF * PS) ? TP * DH : MF * PS;
   int smem = (MF * TS + vreg + DH * PS) * 2;
@@ -416,9 +419,9 @@ int launch_perf_attn(uint16_t* qkv, int h16, const uint16_t* PT, int ldp, const 
     attr = smem;
   }
   if (h16 == MDM_H16_F16) {
-    hipLaunchKernelGGL((perf_attn_kernel<HF, QMT>), dim3(B * H), dim3(NTH), smem, s, qkv, PT, ldp, hn_w, hn_b, len, S, H, out, qa);
+    hipLaunchKernelGGL((perf_attn_kernel<HF, QMT>), dim3(B * H), dim3(NTH), smem, s, qkv, PT, ldp, hn_w, hn_b, len, S, H, out, qa, wm);
   } else {
-    hipLaunchKernelGGL((perf_attn_kernel<HB, QMT>), dim3(B * H), dim3(NTH), smem, s, qkv, PT, ldp, hn_w, hn_b, len, S, H, out, qa);
+    hipLaunchKernelGGL((perf_attn_kernel<HB, QMT>), dim3(B * H), dim3(NTH), smem, s, qkv, PT, ldp, hn_w, hn_b, len, S, H, out, qa, wm);
   }
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
@@ -430,22 +433,23 @@ int perf_attn(const void* qkv, int h16, const uint16_t* PT, int ldp, const float
               int S, int H, int dh, uint16_t* out, hipStream_t s) {
   if (!perf_attn_supported(dh, S) || (h16 != MDM_H16_BF16 && h16 != MDM_H16_F16)) return MDM_ERR_UNSUPPORTED;
   if (!qkv || !PT || !hn_w || !hn_b || !len || !out || (ldp & 7)) return MDM_ERR_ARG;
-  return launch_perf_attn<0>((uint16_t*)qkv, h16, PT, ldp, hn_w, hn_b, len, B, S, H, out, PerfQkv(), s);
+  return launch_perf_attn<0>((uint16_t*)qkv, h16, PT, ldp, hn_w, hn_b, len, B, S, H, out, PerfQkv(), Warm(), s);
 }
 
 // the same with the q | k | v projection inside: xn 16-bit [B S, D] (format h16), wqkv the 16-bit plane [3 D][ldw] of the stacked
 // query | key | value weights, bias [3 D], q | k | v = alpha * (xn W^T + b); qscratch = a [B S, 3 D] 16-bit buffer (its q third is used)
 int perf_attn_qkv(const uint16_t* xn, const uint16_t* wqkv, int ldw, const float* bias, float alpha, uint16_t* qscratch, int h16,
                   const uint16_t* PT, int ldp, const float* hn_w, const float* hn_b, const int* len, int B, int S, int H, int dh,
-                  uint16_t* out, hipStream_t s) {
+                  uint16_t* out, hipStream_t s, const Warm* warm) {
   if (!perf_attn_qkv_supported(dh, S, H) || (h16 != MDM_H16_BF16 && h16 != MDM_H16_F16)) return MDM_ERR_UNSUPPORTED;
   if (!xn || !wqkv || !bias || !qscratch || !PT || !hn_w || !hn_b || !len || !out || (ldp & 7) || (ldw & 7) ||
       ((((uintptr_t)xn) | ((uintptr_t)wqkv) | ((uintptr_t)qscratch)) & 15))
     return MDM_ERR_ARG;
   const PerfQkv qa = {xn, wqkv, ldw, bias, alpha};
+  const Warm wm = warm ? *warm : Warm();
   // 7 row tiles cover the coarse scale (S <= 112), 13 the full one: the count is compiled in (see QkvGeo)
-  if (S <= 112) return launch_perf_attn<7>(qscratch, h16, PT, ldp, hn_w, hn_b, len, B, S, H, out, qa, s);
-  return launch_perf_attn<13>(qscratch, h16, PT, ldp, hn_w, hn_b, len, B, S, H, out, qa, s);
+  if (S <= 112) return launch_perf_attn<7>(qscratch, h16, PT, ldp, hn_w, hn_b, len, B, S, H, out, qa, wm, s);
+  return launch_perf_attn<13>(qscratch, h16, PT, ldp, hn_w, hn_b, len, B, S, H, out, qa, wm, s);
 }
 
 }  // namespace mdm
