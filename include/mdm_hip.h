@@ -517,6 +517,32 @@ int mdm_foot_skate(const float* joints, const int32_t* length, const MdmSkeleton
                    const float* rotations_in, float* joints_out, float* rotations_out, float* slide_out, int32_t* pairs_out,
                    float* scratch, void* stream);
 
+/* Exact reach (csrc/limb_pin.hip): pin the end joints of two-bone limbs to 3-D targets by limb IK.  joints,
+ * targets and weights (B, T, J, 3) fp32 (targets and weights in the units and frame of joint control's), length (B) int32 or
+ * NULL (= T).  limbs: a HOST array (L, 4) int32 of rows (root, mid, end, tip), 1 <= L <= 8, tip = -1 where the end joint has
+ * no child.  Frame t < length[b] is a pin frame of a limb iff weights[b, t, end, c] > 0 for c = 0, 1, 2; targets are read
+ * nowhere else, weights on other joints and their magnitudes do not matter.  In a pin frame delta = target[end] - p[end];
+ * up to `blend` frames outside, delta = (wL dL + wR dR) / max(1, wL + wR) of the nearest pin frame within `blend` on either
+ * side, w = 1 - smoothstep(k / (blend + 1)).  The end joint goes to end + delta by mdm_foot_skate's two-bone solve with the
+ * limb root fixed (the same reach clamp, bend plane and fallbacks; out of reach the limb goes as far as it goes), the tip is
+ * carried rigidly: tip' = end' + Q2 (tip - end), Q2 the shortest arc from the old mid -> end bone to the new one.  A
+ * (frame, limb) that is neither a pin frame nor within `blend` of one, and every joint outside the limbs, is copied bit for
+ * bit.  rotations_in (B, T, J, 3, 3), the layout of mdm_motion_fk's rotations_out, or NULL: rotations_out[mid] = Q1 R[mid]
+ * (Q1 the shortest arc of the root -> mid bone), [end] = Q2 R[end], [tip] = Q2 R[tip]; all others copied.  error_out
+ * (B, L, 4) or NULL: per limb over its pin frames the mean (double, frame order) and the maximum of |p[end] - target[end]|
+ * before [0], [1] and after [2], [3] (0 without a pin frame); counts_out (B, L, 2) int32 or NULL: the pin frames and those of
+ * them whose target lay outside the reach clamp.  scratch: (B, T, L, 3) fp32.  Frames at or past length[b] are zero in the
+ * outputs and are never read.  Nothing is updated in place.
+ * MDM_ERR_ARG: a null required pointer (joints, targets, weights, limbs, joints_out, scratch), T < 1, blend < 0, L outside
+ * 1 .. 8, J outside 3 .. 32, a limb index out of range or repeated within a limb, a joint that two limbs move or that one
+ * moves and another starts at, rotations_in without rotations_out or the reverse, an output that is an input;
+ * MDM_ERR_UNSUPPORTED: T > mdm_limb_pin_max_frames() (9 bytes of LDS per frame). */
+int mdm_limb_pin_max_frames(void);
+int mdm_limb_pin(const float* joints, const int32_t* length, const float* targets, const float* weights,
+                 const int32_t* limbs, int32_t L, int32_t J, int32_t blend, int32_t B, int32_t T, const float* rotations_in,
+                 float* joints_out, float* rotations_out, float* error_out, int32_t* counts_out, float* scratch,
+                 void* stream);
+
 /* Rig export (csrc/motion_rig.hip): global rotations -> the channels of a node tree, retimed.  joints
  * (B, T, J, 3) and rotations (B, T, J, 3, 3) fp32 in the layout of mdm_motion_fk's outputs (R[c] orients the bone
  * parent(c) -> c), length (B) int32 or NULL (= T).  The node tree is three host arrays of n_nodes <= 64 entries, parents before

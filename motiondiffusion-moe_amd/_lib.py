@@ -191,6 +191,8 @@ PROTOTYPES = {
     "mdm_motion_fk": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "mdm_foot_skate_max_frames": (_I32, []),
     "mdm_foot_skate": (_I32, [_P, _P, _P, _P, _I64, _P, _F64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "mdm_limb_pin_max_frames": (_I32, []),
+    "mdm_limb_pin": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "mdm_rig_channels": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _F32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "mdm_rig_joints": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _F32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "mdm_retarget_table_words": (_I64, []),

@@ -11,7 +11,7 @@ from .motion_features import pad_clips, skeleton_for_feats
 from .motion_render import gif_bytes, render_motion, render_world, write_gif
 from .motion_rig import DEFAULT_FPS, bvh_text, retarget_to_rig, retime_ratio, rig_of, rotations_to_rig, target_bvh_text
 from .motion_rig import target_rig as make_target_rig
-from .postprocess import fk_max_frames, motion_to_joints, motion_to_joints_fk, remove_foot_skate
+from .postprocess import fk_max_frames, motion_to_joints, motion_to_joints_fk, pin_limbs, remove_foot_skate
 
 MAX_JOINTS_FRAMES = 3276  # frames of mdm_motion_postprocess: 5 T floats of LDS per workgroup, 64 KiB
 
@@ -33,14 +33,57 @@ def canvas_frame_limit(forward_kinematics=False):
     return fk_max_frames() if forward_kinematics else MAX_JOINTS_FRAMES
 
 
+def pin_pair(pin, B, T, J):
+    """``pin=`` of ``joints_batch``: (targets (N, T', J, 3), weights broadcastable to it as ``control_weights`` are), or one
+    (T'_i, J, 3) target array and weights aligned on its frame dim per motion (canvases) -> (targets, weights) float32
+    (B, T, J, 3) on the CPU: frames past T cut, missing frames under weight 0.  Raises ValueError."""
+    from .conditioning import expand_to
+    if not isinstance(pin, (tuple, list)) or len(pin) != 2 or pin[0] is None or pin[1] is None:
+        raise ValueError("pin is a (targets, weights) pair")
+    g, w = pin
+    if not torch.is_tensor(g) and isinstance(g, (tuple, list)):  # one canvas per motion
+        if isinstance(w, torch.Tensor) or len(g) != B or len(w) != B:
+            raise ValueError(f"pin: one target array and one weight array per motion ({B})")
+        pairs = [pin_pair((torch.as_tensor(a)[None], torch.as_tensor(b)[None]), 1, T, J) for a, b in zip(g, w)]
+        return torch.cat([a for a, _ in pairs]), torch.cat([b for _, b in pairs])
+    g = torch.as_tensor(g).detach().to("cpu", torch.float32)
+    if g.dim() != 4 or g.shape[0] != B or tuple(g.shape[2:]) != (J, 3):
+        raise ValueError(f"pin targets of shape {tuple(g.shape)} must be ({B}, T, {J}, 3)")
+    w = expand_to(torch.as_tensor(w).detach().to("cpu", torch.float32), 1, g.shape, "pin weights", f"must lead with {B}")
+    n = min(T, g.shape[1])
+    go, wo = torch.zeros(B, T, J, 3), torch.zeros(B, T, J, 3)
+    go[:, :n], wo[:, :n] = g[:, :n], w[:, :n]
+    return go, wo
+
+
+def pin_of(pin_targets, kw):
+    """``pin_targets=`` of the trainer's output methods: None when off, else the call's own ``control_joints`` /
+    ``control_weights`` out of its keyword arguments; ValueError without them."""
+    if not pin_targets:
+        return None
+    if kw.get("control_joints") is None or kw.get("control_weights") is None:
+        raise ValueError("pin_targets=True pins the call's own control_joints / control_weights: give both")
+    return kw["control_joints"], kw["control_weights"]
+
+
+def pin_kw(pin, pin_blend=5):
+    """The keyword arguments that hand a pin on: none when there is none, so that a call without pins is the call it was."""
+    return {} if pin is None else dict(pin=pin, pin_blend=pin_blend)
+
+
 def joints_batch(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotations=False, offsets=None,
-                 return_rotations=False, fix_feet=False, blend=5):
+                 return_rotations=False, fix_feet=False, blend=5, *, pin=None, pin_blend=5):
     """``postprocess.motion_to_joints`` over the first ``lens[i]`` frames of every motion, or with ``from_rotations``
     ``postprocess.motion_to_joints_fk``: one launch for all.  -> (joints (B, T, J, 3), rotations (B, T, J, 3, 3), offsets
     (B, J, 3), lens), zero past each length; rotations and offsets are None without forward kinematics.  ``fix_feet``:
     ``postprocess.remove_foot_skate`` on the result, filtered first (filtering afterwards would smear the pins), labels from
-    the rows' contact columns read in place; rotations go through it, so that joints and rotations still agree."""
+    the rows' contact columns read in place; rotations go through it, so that joints and rotations still agree.
+    ``pin``: a (targets, weights) pair over the padded batch, ``control_joints`` / ``control_weights`` as the call took them;
+    ``postprocess.pin_limbs`` with ``pin_blend`` runs last: temporal filter -> ``fix_feet`` -> pins, so
+    that nothing smears a pin, and where a foot-skate pin and a target both touch an ankle the target wins."""
     skel = skeleton_for_feats(dim_pose)
+    if pin is not None and (skel is None or dim_pose != 12 * joints_num - 1):
+        raise ValueError(f"pin needs dim_pose 263 (22 joints) or 251 (21), not {dim_pose} ({joints_num})")
     if fix_feet and (skel is None or dim_pose != 12 * joints_num - 1):
         raise ValueError(f"fix_feet needs dim_pose 263 (22 joints) or 251 (21), not {dim_pose} ({joints_num})")
     if (offsets is not None or return_rotations) and not from_rotations:
@@ -50,6 +93,8 @@ def joints_batch(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rot
         j = motion_to_joints(x, mean, std, torch.tensor(lens), joints_num, sigma)
         if fix_feet:
             j = remove_foot_skate(j, torch.tensor(lens), (x, mean, std), skeleton=skel, blend=blend)
+        if pin is not None:
+            j = pin_limbs(j, torch.tensor(lens), *pin_pair(pin, x.shape[0], x.shape[1], joints_num), skeleton=skel, blend=pin_blend)
         return j, None, None, lens
     if dim_pose != 12 * joints_num - 1 or dim_pose not in (263, 251):
         raise ValueError(f"forward kinematics needs dim_pose 263 (22 joints) or 251 (21), not {dim_pose} ({joints_num})")
@@ -59,33 +104,38 @@ def joints_batch(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rot
                                   return_rotations=True, return_offsets=True)
     if fix_feet:
         j, r = remove_foot_skate(j, torch.tensor(lens), (x, mean, std), skeleton=skel, blend=blend, rotations=r)
+    if pin is not None:
+        j, r = pin_limbs(j, torch.tensor(lens), *pin_pair(pin, x.shape[0], x.shape[1], joints_num), skeleton=skel,
+                         blend=pin_blend, rotations=r)
     return j, r, o, lens
 
 
 def to_joints(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotations=False, offsets=None,
-              return_rotations=False, fix_feet=False, blend=5):
-    """``joints_batch`` as a list per motion: joints (lens[i], J, 3), or with ``return_rotations`` (joints, rotations, offsets)."""
+              return_rotations=False, fix_feet=False, blend=5, *, pin=None, pin_blend=5):
+    """``joints_batch`` as a list per motion: joints (lens[i], J, 3), or with ``return_rotations`` (joints, rotations, offsets).
+    ``pin`` / ``pin_blend``: limb pins as the last stage, as ``joints_batch`` takes them."""
     j, r, o, lens = joints_batch(motions, lens, dim_pose, mean, std, joints_num, sigma, from_rotations, offsets,
-                                 return_rotations, fix_feet, blend)
+                                 return_rotations, fix_feet, blend, **pin_kw(pin, pin_blend))
     if return_rotations:
         return [(j[i, :n], r[i, :n], o[i]) for i, n in enumerate(lens)]
     return [j[i, :n] for i, n in enumerate(lens)]
 
 
 def to_bvh(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, paths, fps, fps_out, euler, scale, target_rig=None,
-           target_joint_map=None, target_up="Y", leg_ik=None):
+           target_joint_map=None, target_up="Y", leg_ik=None, *, pin=None, pin_blend=5):
     """Rows -> one BVH text per motion: ``joints_batch`` with rotations and no filter, one
     ``motion_rig.rotations_to_rig`` over the padded batch, ``motion_rig.bvh_text`` per sample.  ``target_rig`` (BVH text, a
     path, a parsed file or ``motion_rig.target_rig``'s namespace; ``target_joint_map`` / ``target_up`` as it takes them): the
     motion goes onto that character's hierarchy instead, ``motion_rig.retarget_to_rig`` with ``leg_ik`` and
-    ``motion_rig.target_bvh_text``; its units decide, so ``scale`` is refused."""
+    ``motion_rig.target_bvh_text``; its units decide, so ``scale`` is refused.  ``pin`` / ``pin_blend``: limb pins (DESIGN.md
+    §28) after ``fix_feet`` and before the export, as ``joints_batch`` takes them; the rotations turn with the limbs."""
     if target_rig is not None:
         if float(scale) != 1.0:
             raise ValueError("scale does not combine with target_rig: the target's own units decide")
         if not hasattr(target_rig, "table"):
             target_rig = make_target_rig(target_rig, target_joint_map, target_up, skeleton=skeleton_for_feats(dim_pose))
     j, r, o, lens = joints_batch(motions, lens, dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True, offsets, True,
-                                 fix_feet=fix_feet, blend=blend)
+                                 fix_feet=fix_feet, blend=blend, **pin_kw(pin, pin_blend))
     skel = skeleton_for_feats(dim_pose)
     rig = rig_of(skel)
     if target_rig is None:

@@ -8,8 +8,11 @@ Host mirror of what the reference does on the CPU after sampling (tools/visualiz
 bone offsets (``recover_from_rot``, utils/motion_process.py:384-398), in ``mdm_motion_fk`` (csrc/motion_fk.hip).  Bones are
 rigid by construction, and the per-joint global rotations come with it.
 
-``remove_foot_skate`` is the last stage: where a foot-contact label is on, the ankle is pinned to its mean
-position over the run by two-bone leg IK and the toe is aimed at its own, in ``mdm_foot_skate`` (csrc/foot_skate.hip)."""
+``remove_foot_skate`` is the next stage: where a foot-contact label is on, the ankle is pinned to its mean
+position over the run by two-bone leg IK and the toe is aimed at its own, in ``mdm_foot_skate`` (csrc/foot_skate.hip).
+
+``pin_limbs`` is the last stage: where a wrist or ankle has a 3-D target, the joint is put on it by two-bone
+IK of its limb, in ``mdm_limb_pin`` (csrc/limb_pin.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -271,4 +274,148 @@ def remove_foot_skate(joints, lengths=None, contacts=None, *, skeleton="t2m", fe
             x.data_ptr(), L.ptr(ln), C.byref(s), cptr, stride, thre_c, feet_thre, int(blend), B, T, L.ptr(rot), out.data_ptr(),
             L.ptr(rot_out), L.ptr(slide), L.ptr(pairs), scratch.data_ptr(), L.stream_ptr()), "mdm_foot_skate")
     res = (out,) + ((rot_out,) if rot is not None else ()) + (((slide, pairs),) if return_slide else ())
+    return res if len(res) > 1 else out
+
+
+LIMB_NAMES = ("right_leg", "left_leg", "right_arm", "left_arm")
+MAX_LIMBS = 8
+
+
+def limb_pin_max_frames() -> int:
+    """The longest motion ``mdm_limb_pin`` takes (9 bytes of LDS per frame); longer ones are MDM_ERR_UNSUPPORTED."""
+    return int(L.lib().mdm_limb_pin_max_frames())
+
+
+def limbs(skeleton="t2m"):
+    """The two-bone limbs of a skeleton by name, each ``(root, mid, end, tip)`` with ``tip = -1`` where the end joint has no
+    child: ``right_leg`` / ``left_leg`` (hip, knee, ankle, toe: ``leg_joints``, the legs of ``remove_foot_skate``) and
+    ``right_arm`` / ``left_arm`` (shoulder, elbow, wrist, -1: the last three entries of the chains that do not start at
+    joint 0).  The right side is the one whose chain holds ``face[0]`` (legs) / ``face[2]`` (arms)."""
+    from .motion_features import get_skeleton
+    sk = get_skeleton(skeleton)
+    legs = sorted(leg_joints(sk), key=lambda leg: sk.face[0] not in [c for c in sk.chains if c[-1] == leg[-1]][0])
+    arms = sorted([c for c in sk.chains if c[0] != 0 and len(c) >= 3], key=lambda c: sk.face[2] not in c)
+    if len(arms) != 2:
+        raise ValueError("the skeleton has no two arm chains (chains of 3 or more joints that do not start at joint 0)")
+    rows = [tuple(int(j) for j in leg) for leg in legs] + [tuple(int(j) for j in c[-3:]) + (-1,) for c in arms]
+    return dict(zip(LIMB_NAMES, rows))
+
+
+def _limb_table(limbs_arg, skeleton, J):
+    """``limbs=`` of ``pin_limbs`` -> int32 (L, 4): None (all four defaults), names of ``limbs(skeleton)``, or rows."""
+    if limbs_arg is None:
+        limbs_arg = LIMB_NAMES
+    if isinstance(limbs_arg, str):
+        limbs_arg = (limbs_arg,)
+    rows = []
+    named = None
+    for q in limbs_arg:
+        if isinstance(q, str):
+            named = limbs(skeleton) if named is None else named
+            if q not in named:
+                raise ValueError(f"limbs: {q!r} is not one of {sorted(named)}")
+            q = named[q]
+        q = [int(v) for v in np.asarray(q).reshape(-1)] if np.asarray(q).size in (3, 4) else None
+        if q is None:
+            raise ValueError("limbs: a limb is a name or (root, mid, end[, tip])")
+        rows.append(q + [-1] * (4 - len(q)))
+    if not 1 <= len(rows) <= MAX_LIMBS:
+        raise ValueError(f"limbs: between 1 and {MAX_LIMBS} limbs, not {len(rows)}")
+    moved = []
+    for q in rows:
+        if any(not (-1 if k == 3 else 0) <= v < J for k, v in enumerate(q)):
+            raise ValueError(f"limbs: {tuple(q)} has a joint outside 0 .. {J - 1} (only the tip may be -1)")
+        if len(set(q)) != 4:
+            raise ValueError(f"limbs: {tuple(q)} names a joint twice")
+        moved += [v for v in q[1:] if v >= 0]
+    if len(set(moved)) != len(moved) or any(q[0] in moved for q in rows):
+        raise ValueError("limbs: a joint that one limb moves belongs to no other limb")
+    return np.ascontiguousarray(rows, dtype=np.int32)
+
+
+def check_pin_limbs(joints, lengths, targets, weights, rotations, sk, limbs=None, blend=5, skeleton="t2m"):
+    """Argument checks of ``pin_limbs`` that need no device: -> (joints (B, T, J, 3), lengths (B,) int64 or None, targets
+    (B, T, J, 3), weights expanded to (B, T, J, 3), rotations (B, T, J, 3, 3) or None, limb table int32 (L, 4)).  Weights
+    broadcast as ``control_weights`` do: aligned on the leading dims, (B,) per sample, (B, T) per frame, (B, T, J) per joint.
+    Raises ValueError: shapes, weights that are negative or not finite in a frame that counts, limb tables, ``blend``, CPU
+    tensors."""
+    from .conditioning import expand_to
+    J = sk.joints
+    x = torch.as_tensor(joints)
+    g, w = torch.as_tensor(targets), torch.as_tensor(weights)
+    if x.dim() == 3:  # one clip: targets (T, J, 3), weights aligned on the frame dim
+        x, g, w = x[None], g[None], w[None]
+    if x.dim() != 4 or tuple(x.shape[2:]) != (J, 3):
+        raise ValueError(f"joints of shape {tuple(x.shape)} must be (B, T, {J}, 3) for this skeleton")
+    B, T = x.shape[:2]
+    if T < 1:
+        raise ValueError("a motion needs at least 1 frame")
+    if int(blend) != blend or blend < 0:
+        raise ValueError("blend must be a whole number of frames >= 0")
+    if lengths is not None:
+        lengths = L.check_lengths(lengths, B, T)
+    if tuple(g.shape) != (B, T, J, 3):
+        raise ValueError(f"targets of shape {tuple(g.shape)} must be {(B, T, J, 3)}")
+    if not (g.dtype.is_floating_point and w.dtype.is_floating_point):
+        raise ValueError("targets and weights must be floating point")
+    w = expand_to(w, 1, (B, T, J, 3), "weights", f"must lead with the batch size {B}")
+    wv = w if lengths is None else w[torch.arange(T)[None] < lengths[:, None]]  # frames past a length are never read
+    if not bool(torch.isfinite(wv).all()):
+        raise ValueError("weights has non-finite values")
+    if bool((wv < 0).any()):
+        raise ValueError("weights must be >= 0")
+    table = _limb_table(limbs, skeleton, J)
+    if rotations is not None:
+        rotations = torch.as_tensor(rotations)
+        if rotations.dim() == 4:
+            rotations = rotations[None]
+        if tuple(rotations.shape) != (B, T, J, 3, 3):
+            raise ValueError(f"rotations of shape {tuple(rotations.shape)} must be ({B}, {T}, {J}, 3, 3)")
+    for name, v in (("joints", x), ("rotations", rotations)):
+        if v is not None and v.device.type == "cpu":
+            raise ValueError(f"{name} must be on a GPU: limb pins have no CPU path")
+    if T > limb_pin_max_frames():
+        raise ValueError(f"a motion of {T} frames: limb pins take at most {limb_pin_max_frames()} frames")
+    return x, lengths, g, w, rotations, table
+
+
+@torch.no_grad()
+def pin_limbs(joints, lengths, targets, weights, *, skeleton="t2m", limbs=None, blend=5, rotations=None, return_error=False):
+    """joints (B, T, J, 3) on a GPU -> joints whose wrists and ankles lie on their targets; frames >=
+    lengths[b] are zero.  ``targets`` (B, T, J, 3) and ``weights`` broadcastable to it are ``control_joints`` /
+    ``control_weights`` as joint control takes them (on any device): frame t is a pin frame of a limb where all three
+    weights of its end joint are > 0; targets on other joints or with fewer weighted coordinates are ignored, targets under
+    weight 0 are never read, and a weight's size does not matter.  In a pin frame the end joint is moved onto its target by
+    two-bone IK with the limb root (hip, shoulder) fixed, the mid joint staying in its bend plane and the tip (toe) carried
+    rigidly; ``blend`` frames either side of a pin frame the correction fades out.  A target out of the limb's reach is
+    approached as far as the limb goes.  ``limbs``: names out of ``limbs(skeleton)`` (default all four) or rows
+    ``(root, mid, end, tip)``.  ``rotations`` (B, T, J, 3, 3) global rotations (``motion_to_joints_fk(...,
+    return_rotations=True)``) are turned with the bones and returned after the joints.  ``return_error``: also
+    ``(error (B, L, 2, 2), counts (B, L, 2))``: per limb over its pin frames the mean and maximum distance of the end joint
+    to its target before [:, :, 0] and after [:, :, 1], and the number of pin frames and of those out of reach."""
+    from .motion_features import get_skeleton
+    sk = get_skeleton(skeleton)
+    x, lengths, g, w, rot, table = check_pin_limbs(joints, lengths, targets, weights, rotations, sk, limbs, blend, skeleton)
+    L.require_cuda(x, rot)
+    dev = x.device
+    x = x.detach().to(torch.float32).contiguous()
+    B, T, J = x.shape[:3]
+    ln = None if lengths is None else lengths.to(dev, torch.int32).contiguous()
+    g = g.detach().to(dev, torch.float32).contiguous()
+    w = w.detach().to(dev, torch.float32).contiguous()
+    if rot is not None:
+        if rot.device != dev:
+            raise ValueError("rotations must be on the joints' device")
+        rot = rot.detach().to(torch.float32).contiguous()
+    nl = int(table.shape[0])
+    out = torch.empty_like(x)
+    rot_out = None if rot is None else torch.empty_like(rot)
+    scratch = torch.empty(B, T, nl, 3, device=dev)
+    err = torch.empty(B, nl, 2, 2, device=dev) if return_error else None
+    counts = torch.empty(B, nl, 2, dtype=torch.int32, device=dev) if return_error else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().mdm_limb_pin(
+            x.data_ptr(), L.ptr(ln), g.data_ptr(), w.data_ptr(), table.ctypes.data, nl, J, int(blend), B, T, L.ptr(rot),
+            out.data_ptr(), L.ptr(rot_out), L.ptr(err), L.ptr(counts), scratch.data_ptr(), L.stream_ptr()), "mdm_limb_pin")
+    res = (out,) + ((rot_out,) if rot is not None else ()) + (((err, counts),) if return_error else ())
     return res if len(res) > 1 else out

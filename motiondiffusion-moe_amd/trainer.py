@@ -264,7 +264,8 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_joints(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, joints_num=22, sigma=1.0,
-                        bucketed=False, from_rotations=False, offsets=None, fix_feet=False, blend=5, **kw):
+                        bucketed=False, from_rotations=False, offsets=None, fix_feet=False, blend=5, pin_targets=False,
+                        pin_blend=5, **kw):
         """``generate`` followed by the reference's post-processing (tools/visualization.py:21-27,89) on the device:
         list of ``(m_len, joints_num, 3)`` joint positions, temporally smoothed with a gaussian of width ``sigma``.
         ``edit_motion`` / ``edit_mask``: motion editing in normalised feature space, as in ``generate``;
@@ -276,11 +277,15 @@ class DDPMTrainer(object):
         ``std``.  ``from_rotations``: joints by forward kinematics of the rot6d columns (``postprocess.motion_to_joints_fk``,
         DESIGN.md §17: rigid bones) on ``offsets`` (J, 3) or one (J, 3) per motion; None: every motion's own mean bone
         lengths.  ``fix_feet``: foot-skate clean-up after the temporal filter (``postprocess.remove_foot_skate``, DESIGN.md
-        §18), the labels being the generated rows' own foot-contact columns; ``blend`` frames of fade either side of a contact."""
+        §18), the labels being the generated rows' own foot-contact columns; ``blend`` frames of fade either side of a contact.
+        ``pin_targets``: exact reach (``postprocess.pin_limbs``) as the last stage: where this call's
+        ``control_joints`` / ``control_weights`` weight all three coordinates of a wrist or an ankle, the joint is put on its
+        target by two-bone IK of its limb, ``pin_blend`` frames of fade either side; without them a ValueError."""
+        pin = MO.pin_of(pin_targets, kw)
         gen = self.generate_bucketed if bucketed else self.generate  # mean / std go along: unused without control
         motions = gen(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)
         return MO.to_joints(motions, MO.valid_lengths(motions, m_lens), dim_pose, mean, std, joints_num, sigma, from_rotations,
-                            offsets, fix_feet=fix_feet, blend=blend)
+                            offsets, fix_feet=fix_feet, blend=blend, **MO.pin_kw(pin, pin_blend))
 
     @torch.no_grad()
     def generate_together(self, scenes, dim_pose, mean, std, *, radius=0.08, margin=0.05, weight=5.0, bones=None, seed=None,
@@ -296,10 +301,15 @@ class DDPMTrainer(object):
         characters do not react to later ones.  A frame takes ``motion_scene.MAX_TRACKS`` tracks: two earlier characters
         need a ``bones`` subset.  ``weight`` follows §14's rule, ``control_scale`` x curvature < 2.  Returns
         the joints in the world, one list of (length, J, 3) per scene.  ``seed``: stage i samples under ``seed + i``;
-        ``**kw`` goes to ``generate_joints`` (``control_scale``, ``control_iters``, the sampler, ``sigma``, ...).  A scene of
+        ``**kw`` goes to ``generate_joints`` (``control_scale``, ``control_iters``, the sampler, ``sigma``, ...; with
+        ``pin_targets=True`` every character's wrists and ankles end on their targets, moved into its own frame, §28; a stage
+        none of whose characters has targets runs without pins).  A scene of
         one character is ``generate_joints`` followed by ``to_world``, bit for bit."""
         from . import motion_scene as MS
         J = (dim_pose + 1) // 12
+        pin = bool(kw.pop("pin_targets", False))
+        if pin and not any(c.get("control_joints") is not None for s in scenes for c in s):
+            raise ValueError("pin_targets=True pins the characters' own control_joints / control_weights: none has any")
         out = [[None] * len(s) for s in scenes]
         for i in range(max([len(s) for s in scenes] + [0])):
             rows = [k for k, s in enumerate(scenes) if len(s) > i]
@@ -334,27 +344,30 @@ class DDPMTrainer(object):
                     w[n, :lens[n]] = wt.reshape(tuple(wt.shape) + (1,) * (3 - wt.dim())).expand(lens[n], J, 3)
                 cond.update(control_joints=g, control_weights=w)
             joints = self.generate_joints([c["caption"] for c in chars], torch.tensor(lens), dim_pose, mean, std,
-                                          seed=None if seed is None else seed + i, **cond, **kw)
+                                          seed=None if seed is None else seed + i, **cond, **kw,
+                                          **(dict(pin_targets=True) if pin and "control_joints" in cond else {}))
             for k, pl, j in zip(rows, place, joints):
                 out[k][i] = MS.to_world(j, *pl)
         return out
 
     @torch.no_grad()
     def generate_rotations(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, offsets=None, fix_feet=False,
-                           blend=5, **kw):
+                           blend=5, pin_targets=False, pin_blend=5, **kw):
         """``generate`` followed by forward kinematics (``postprocess.motion_to_joints_fk``): per sample
         ``(joints (m, J, 3), rotations (m, J, 3, 3), offsets (J, 3))``: the joints on rigid bones, unfiltered so that they
         agree with the rotations, the global rotation matrix of every joint (the root's at joint 0) and the bone offsets
         used (``offsets``, or the sample's own mean bone lengths).  ``fix_feet`` / ``blend``: foot-skate clean-up as in
-        ``generate_joints``; the rotations of knees, ankles and toes turn with their bones.  ``**kw`` as for ``generate``."""
+        ``generate_joints``; the rotations of knees, ankles and toes turn with their bones.  ``pin_targets`` / ``pin_blend``:
+        exact reach as in ``generate_joints``; the rotations of the pinned limbs turn with them.  ``**kw`` as for ``generate``."""
+        pin = MO.pin_of(pin_targets, kw)
         motions = self.generate(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)  # unused without an edit or control
         return MO.to_joints(motions, MO.valid_lengths(motions, m_lens), dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True,
-                            offsets, True, fix_feet=fix_feet, blend=blend)
+                            offsets, True, fix_feet=fix_feet, blend=blend, **MO.pin_kw(pin, pin_blend))
 
     @torch.no_grad()
     def generate_bvh(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, paths=None, fps=None, fps_out=None,
                      euler="ZXY", scale=1.0, offsets=None, fix_feet=False, blend=5, target_rig=None, target_joint_map=None,
-                     target_up="Y", leg_ik=None, **kw):
+                     target_up="Y", leg_ik=None, pin_targets=False, pin_blend=5, **kw):
         """``generate`` followed by forward kinematics and the rig export (``motion_rig``): one BVH text per
         sample, written to ``paths[i]`` where given.  ``fps`` (default 20 at dim_pose 263, 12.5 at 251) / ``fps_out``: retimed
         to the frame rate a tool works at; ``euler``: the channels' rotation order; ``scale``: of positions and offsets (100
@@ -362,11 +375,13 @@ class DDPMTrainer(object):
         with ``edit_bvh=`` / ``edit_mask=`` a file from a rig is continued and written back as one (converted under this
         call's ``mean`` / ``std``).  ``target_rig`` (BVH text, a path or ``motion_rig.target_rig``'s namespace; with
         ``target_joint_map`` / ``target_up``, and ``leg_ik``): the motion is written onto that character's own hierarchy
-        (``motion_rig.retarget_to_rig``) in its units, so ``scale`` is refused."""
+        (``motion_rig.retarget_to_rig``) in its units, so ``scale`` is refused.  ``pin_targets`` /
+        ``pin_blend``: exact reach before the export, as in ``generate_rotations``."""
         MO.check_paths(paths, len(caption), "caption")
+        pin = MO.pin_of(pin_targets, kw)
         motions = self.generate(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)  # unused without an edit or control
         return MO.to_bvh(motions, MO.valid_lengths(motions, m_lens), dim_pose, mean, std, offsets, fix_feet, blend, paths, fps,
-                         fps_out, euler, scale, target_rig, target_joint_map, target_up, leg_ik)
+                         fps_out, euler, scale, target_rig, target_joint_map, target_up, leg_ik, **MO.pin_kw(pin, pin_blend))
 
     @torch.no_grad()
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
@@ -440,30 +455,33 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_long_joints(self, scripts, dim_pose, mean, std, *, joints_num=22, sigma=1.0, from_rotations=False,
-                             offsets=None, fix_feet=False, feet_blend=5, **kw):
+                             offsets=None, fix_feet=False, feet_blend=5, pin_targets=False, pin_blend=5, **kw):
         """``generate_long`` followed by ``postprocess.motion_to_joints`` over each whole canvas (one continuous root
         path): a list of ``(canvas_len, joints_num, 3)`` joint positions.  The post-processing kernel holds a canvas in
         LDS: at most MAX_JOINTS_FRAMES frames.  ``edit_joints`` / ``edit_mask`` (through ``**kw``): continue joint clips, as
         in ``generate_long``, under this call's ``mean`` / ``std``.  ``from_rotations`` / ``offsets``: forward kinematics,
         as in ``generate_joints`` (at most ``postprocess.fk_max_frames()`` frames).  ``fix_feet`` / ``feet_blend``:
         foot-skate clean-up over each whole canvas, as ``fix_feet`` / ``blend`` of ``generate_joints`` (``blend`` is
-        ``generate_long``'s here): a contact that spans an overlap is one run."""
+        ``generate_long``'s here): a contact that spans an overlap is one run.  ``pin_targets`` / ``pin_blend``: exact reach
+         over each whole canvas on the call's canvas ``control_joints`` / ``control_weights``, one pair per motion."""
+        pin = MO.pin_of(pin_targets, kw)
         motions = self._long_motions(scripts, dim_pose, mean, std, MO.canvas_frame_limit(from_rotations), "joint recovery", kw)
         return MO.to_joints(motions, MO.valid_lengths(motions), dim_pose, mean, std, joints_num, sigma, from_rotations, offsets,
-                            fix_feet=fix_feet, blend=feet_blend)
+                            fix_feet=fix_feet, blend=feet_blend, **MO.pin_kw(pin, pin_blend))
 
     @torch.no_grad()
     def generate_long_bvh(self, scripts, dim_pose, mean, std, *, paths=None, fps=None, fps_out=None, euler="ZXY", scale=1.0,
                           offsets=None, fix_feet=False, feet_blend=5, target_rig=None, target_joint_map=None, target_up="Y",
-                          leg_ik=None, **kw):
+                          leg_ik=None, pin_targets=False, pin_blend=5, **kw):
         """``generate_long`` followed by forward kinematics over each whole canvas and the rig export, as ``generate_bvh``:
         one BVH text per motion (at most ``postprocess.fk_max_frames()`` canvas frames).  ``feet_blend`` is ``generate_bvh``'s
         ``blend`` (``blend`` is ``generate_long``'s here); ``target_rig`` / ``target_joint_map`` / ``target_up`` / ``leg_ik`` as
-        in ``generate_bvh``; ``**kw`` as for ``generate_long``."""
+        in ``generate_bvh``; ``pin_targets`` / ``pin_blend`` as in ``generate_long_joints``; ``**kw`` as for ``generate_long``."""
         MO.check_paths(paths, len(scripts), "motion")
+        pin = MO.pin_of(pin_targets, kw)
         motions = self._long_motions(scripts, dim_pose, mean, std, MO.canvas_frame_limit(True), "forward kinematics", kw)
         return MO.to_bvh(motions, MO.valid_lengths(motions), dim_pose, mean, std, offsets, fix_feet, feet_blend, paths, fps,
-                         fps_out, euler, scale, target_rig, target_joint_map, target_up, leg_ik)
+                         fps_out, euler, scale, target_rig, target_joint_map, target_up, leg_ik, **MO.pin_kw(pin, pin_blend))
 
     @torch.no_grad()
     def generate_frames(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, size=(480, 480), camera=None,
@@ -472,7 +490,7 @@ class DDPMTrainer(object):
         a list of ``(m_len, H, W, 3)`` uint8 frames, ``size`` = (H, W); with ``palette`` ``(m_len, H, W)`` indices into
         ``motion_render.PALETTE``.  ``camera``: a ``motion_render.Camera`` or a dict of its fields; ``style``: a dict of
         ``render_motion``'s colour and width arguments.  ``**kw`` goes to ``generate_joints`` untouched: ``from_rotations``,
-        ``fix_feet``, the sampler, edit and control arguments.  ``view="world"``: the world view instead
+        ``fix_feet``, ``pin_targets``, the sampler, edit and control arguments.  ``view="world"``: the world view instead
         (``motion_render.render_world``): each character in world coordinates with the ``scene`` /
         ``scene_tracks`` that steered it; ``camera`` None then fits one camera to the batch, ``style`` is ``render_world``'s."""
         joints = self.generate_joints(caption, m_lens, dim_pose, mean, std, batch_size, **kw)
