@@ -882,8 +882,14 @@ int stem_embeddings(const Ctx& c, const int64_t* timesteps, const float* xf_proj
     MDM_TRY(gated_mix_gather(sc_cache->time_table, timesteps, sc_cache->steps, sc_cache->gx, B, D, c.bf ? nullptr : mix,
                              c.bf ? (uint16_t*)mix : nullptr, c.h16, c.s));
   } else {
-    MDM_TRY(stem_time_branch(c, timesteps, B, w.s_b));
-    MDM_TRY(stem_text_branch(c, xf_proj, B, w.s_a));
+    // the two chains read fp32 rows and weights packed bf16 hi + lo in every mode: always the bf16x3 arithmetic, as the stem
+    // cache tabulates them.  At the run's own `prec` the 16-bit modes made a single pass on the bf16 hi plane -- the fp16 mode
+    // too, which has no fp16 image of these weights: a (scale | shift) row was then 5e-3 off in the mode whose rows hold 7e-4
+    // (tests/frame_probe.py), and a forward with and without a stem cache differed by that much.
+    Ctx c3 = c;
+    c3.prec = 3;
+    MDM_TRY(stem_time_branch(c3, timesteps, B, w.s_b));
+    MDM_TRY(stem_text_branch(c3, xf_proj, B, w.s_a));
     MDM_TRY(gated_mix(w.s_b, w.s_a, (int64_t)B * D, w.s_c, c.s));
     if (c.bf) {
       MDM_TRY(to_bf16(w.s_c, (int64_t)B * D, (uint16_t*)w.s_b, c.h16, c.s));
