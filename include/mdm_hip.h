@@ -794,6 +794,61 @@ int mdm_canvas_tracks_guidance(float* x, float* x0, const float* mask, const int
                                const float* track_bounds, int32_t M, int32_t F, float scale, int32_t iters, const float* coef,
                                int32_t steps, const int32_t* t_dev, int32_t t_imm, float* workspace, void* stream);
 
+/* Terrain (csrc/terrain.h inside both control kernels): a height-map ground that joints stay above and planted
+ * feet stand on.  `terrain` dense fp32 (B or M, Gz, Gx): per sample (per long motion) a grid of heights in metres, row major
+ * (the sample of cell column i, row k at k Gx + i), 2 <= Gx, Gz <= MDM_TERRAIN_MAX_GRID.  `terrain_rec` dense fp32
+ * (B or M, MDM_TERRAIN_REC): origin x, origin z, cos yaw, sin yaw, 1 / cell_x, 1 / cell_z, weight a >= 0, margin m, in the
+ * frame of recover_from_ric (the canvas frame of a long motion).  For a point p:
+ *   (lx, lz) = R_y(-yaw) (p_xz - origin),  u = clamp(lx / cell_x, 0, Gx - 1),  v = clamp(lz / cell_z, 0, Gz - 1),
+ *   i = min(floor(u), Gx - 2),  k = min(floor(v), Gz - 2),  h(p) bilinear in the four samples around (i, k);
+ *   outside the grid the nearest edge's height holds, with zero slope in the clamped direction;
+ *   e = p_y - h(p): the vertical clearance, not the true distance to the surface.
+ * `stand` dense fp32 (B, T, J) for the window calls, (total canvas frames, J) in canvas order for the canvas calls, or NULL
+ * (all 0): S[t, j] >= 0 says how strongly joint j is planted in frame t.  The loss of the tracks calls gains
+ *   L_terrain = sum_{t < length, j} u_j a (max(0, m + r_j - e)^2 + S[t, j] max(0, e - r_j - m)^2)
+ * with (r_j, u_j) the joint_params of the scene calls (required here as well).  The grid and S are data: no gradient reaches
+ * them.  On a grid line, where the slope of h jumps, the cell that floor() gives is taken.  The grid stays in global memory
+ * (the LDS layout and mdm_joint_scene_max_frames are those of the scene calls); scene with K == 0, tracks with Km == 0,
+ * targets / weights, track_bounds and stand may be NULL.  With terrain == NULL the calls are the tracks calls, launch for
+ * launch, and the other terrain arguments are not looked at.  MDM_ERR_ARG: Gx or Gz outside [2, MDM_TERRAIN_MAX_GRID], a
+ * NULL terrain_rec with a grid, terrain_rec not 16-byte aligned (it is read 16 bytes at a time), terrain or stand not 4-byte
+ * aligned, and everything the tracks calls refuse (the T limit is the scene's).  The values are the caller's (finite,
+ * a >= 0, S >= 0, cells > 0): not checked here. */
+enum { MDM_TERRAIN_MAX_GRID = 512, MDM_TERRAIN_REC = 8 };
+int mdm_joint_terrain_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
+                                const float* weights, const float* scene, int32_t K, const float* joint_params,
+                                const float* tracks, int32_t Km, const float* track_bounds, const float* terrain,
+                                const float* terrain_rec, int32_t Gx, int32_t Gz, const float* stand, int32_t B, int32_t T,
+                                int32_t F, float* loss_out, float* grad_out, void* stream);
+int mdm_joint_terrain_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
+                               const float* targets, const float* weights, const float* scene, int32_t K,
+                               const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds,
+                               const float* terrain, const float* terrain_rec, int32_t Gx, int32_t Gz, const float* stand,
+                               int32_t B, int32_t T, int32_t F, float scale, int32_t iters, const float* coef, int32_t steps,
+                               const int32_t* t_dev, int32_t t_imm, void* stream);
+int mdm_canvas_terrain_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
+                                 const float* std, const float* targets, const float* weights, const float* scene, int32_t K,
+                                 const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds,
+                                 const float* terrain, const float* terrain_rec, int32_t Gx, int32_t Gz, const float* stand,
+                                 int32_t M, int32_t F, float* loss_out, float* grad_out, float* workspace, void* stream);
+int mdm_canvas_terrain_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
+                                const float* mean, const float* std, const float* targets, const float* weights,
+                                const float* scene, int32_t K, const float* joint_params, const float* tracks, int32_t Km,
+                                const float* track_bounds, const float* terrain, const float* terrain_rec, int32_t Gx,
+                                int32_t Gz, const float* stand, int32_t M, int32_t F, float scale, int32_t iters,
+                                const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, float* workspace,
+                                void* stream);
+/* Stand weights from a step's foot-contact labels (csrc/terrain.hip): out (n_frames, J) = 1 at foot joint feet[k] of a frame
+ * whose de-normalised contact column (x0[row, F - 4 + k] * std[F - 4 + k] + mean[F - 4 + k], two fp32 operations) exceeds
+ * threshold, 0 at every other joint.  x0 rows of F floats; frame f reads row frame_rows[f], or row f with frame_rows NULL;
+ * mean / std on the device: (F,) with stat_group == 0, else one row of F per stat_group frames (frame f takes row
+ * f / stat_group: a batch of windows of T frames with per-sample statistics is stat_group = T, one launch); feet: four joint
+ * indices in host memory, read before the call returns.  Stream-ordered, allocation free, graph-capturable.  MDM_ERR_ARG: a
+ * null pointer (frame_rows excepted), n_frames < 0, stat_group < 0, F + 1 no multiple of 12, a foot outside [0, J), a
+ * non-finite threshold; n_frames == 0 is a no-op. */
+int mdm_terrain_stand_weights(const float* x0, const int32_t* frame_rows, int32_t n_frames, const float* mean, const float* std,
+                              int32_t F, int32_t stat_group, const int32_t* feet, float threshold, float* out, void* stream);
+
 /* ---- long-motion handshakes ---------------------------------------------------------------------
  * In place over the shared canvas frames only.  For every group g < groups, shared frame c < nshared and feature j < F:
  *   v = sum over entries e in [offsets[c], offsets[c+1]) of weights[e] * x[g*group_stride + rows[e]*F + j]

@@ -136,6 +136,7 @@ COMPOSE_MAX_K = 8  # MDM_COMPOSE_MAX_K: prompts per sample of mdm_composed_updat
 CONTROL_MAX_ITERS = 32  # MDM_CONTROL_MAX_ITERS: guidance iterations per step of mdm_joint_guidance
 SCENE_MAX_PRIMS, SCENE_REC = 16, 12  # MDM_SCENE_MAX_PRIMS, MDM_SCENE_REC: primitives per scene, floats per record
 SCENE_MAX_TRACKS = 24  # MDM_SCENE_MAX_TRACKS: per-frame records (moving primitives) per sample
+TERRAIN_MAX_GRID, TERRAIN_REC = 512, 8  # MDM_TERRAIN_MAX_GRID, MDM_TERRAIN_REC: samples per grid side, floats per record
 TAB_ROWS = 7 # sqrt_recip_acp, sqrt_recipm1_acp, coef1, coef2, post_logvar_clipped, acp, acp_prev
 
 
@@ -223,6 +224,15 @@ PROTOTYPES = {
     "mdm_canvas_tracks_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P]),
     "mdm_canvas_tracks_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32, _I32, _F32, _I32,
                                           _P, _I32, _P, _I32, _P, _P]),
+    "mdm_joint_terrain_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _I32, _I32, _P, _I32, _I32,
+                                           _I32, _P, _P, _P]),
+    "mdm_joint_terrain_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _I32, _I32, _P, _I32,
+                                          _I32, _I32, _F32, _I32, _P, _I32, _P, _I32, _P]),
+    "mdm_canvas_terrain_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _I32, _I32, _P, _I32,
+                                            _I32, _P, _P, _P, _P]),
+    "mdm_canvas_terrain_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _I32, _I32, _P,
+                                           _I32, _I32, _F32, _I32, _P, _I32, _P, _I32, _P, _P]),
+    "mdm_terrain_stand_weights": (_I32, [_P, _P, _I32, _P, _P, _I32, _I32, _P, _F32, _P, _P]),
     "mdm_handshake_blend": (_I32, [_P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
     "mdm_moe_train_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32]),
     "mdm_moe_ffn_train_forward": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _F32, _U64, _P, _P, _P, _P,

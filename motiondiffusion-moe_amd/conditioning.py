@@ -132,19 +132,29 @@ def check_control_kwargs(kw, shape):
     Tracks: ``control_tracks`` (B, T, Km, 12), per-frame records (``motion_scene.batch_tracks``), with or
     without a scene (one of no primitives then stands in) and with or without targets, come back as ``tracks`` and
     ``track_bounds`` (B, T, 4), the balls of the kernels' broad phase, computed here, once.  Raises ValueError for records
-    ``motion_scene.check_tracks`` refuses and another shape.  Host logic."""
+    ``motion_scene.check_tracks`` refuses and another shape.
+    Terrain: ``control_terrain`` (B, Gz, Gx) height grids with ``control_terrain_rec`` (B, 8), their records
+    (``motion_scene.batch_terrain``), with or without a scene, tracks and targets, come back as ``terrain`` / ``terrain_rec``;
+    ``control_stand``, the stand weights (B, T, J) >= 0, or ``"contacts"`` (the step's own foot-contact labels over
+    ``control_stand_threshold``, default 0.5, on the feet of the skeleton of width F), as ``stand`` (a tensor, or the feet and
+    the threshold as ``stand_feet`` / ``stand_threshold``).  Raises ValueError for a record or stand weights without a grid, a
+    grid without a record, what ``motion_scene.check_terrain`` / ``check_stand`` refuse, another batch size, ``"contacts"`` at
+    a feature width without a skeleton and a non-finite threshold.  Host logic."""
     from .motion_control import joints_for_feats, max_frames
     names = ("control_joints", "control_weights", "control_mean", "control_std")
     g, w, mean, std = (kw.get(k) for k in names)
     scene, jp, tracks = kw.get("control_scene"), kw.get("control_joint_params"), kw.get("control_tracks")
-    if tracks is not None and scene is None:
+    terrain, trec, stand = kw.get("control_terrain"), kw.get("control_terrain_rec"), kw.get("control_stand")
+    if terrain is None and any(kw.get(k) is not None for k in ("control_terrain_rec", "control_stand", "control_stand_threshold")):
+        raise ValueError("control_terrain_rec / control_stand / control_stand_threshold given without control_terrain")
+    if (tracks is not None or terrain is not None) and scene is None:
         scene = torch.zeros((int(shape[0]), 0, L.SCENE_REC))
     given = [k for k, v in zip(names, (g, w, mean, std)) if v is not None]
     extra = [k for k in ("control_scale", "control_iters") if kw.get(k) is not None]
     if jp is not None and scene is None:
         raise ValueError("control_joint_params given without control_scene")
     if not given and scene is None:
-        if extra and not any(kw.get(k) is not None for k in CANVAS_CONTROL_KEYS + CANVAS_SCENE_KEYS + (CANVAS_TRACKS_KEY,)):  # canvas control's
+        if extra and not any(kw.get(k) is not None for k in CANVAS_CONTROL_KEYS + CANVAS_SCENE_KEYS + (CANVAS_TRACKS_KEY,) + CANVAS_TERRAIN_KEYS):  # canvas control's
             raise ValueError(f"{' / '.join(extra)} given without control_joints / control_weights / control_mean / control_std")
         return None
     need = names[2:] if scene is not None and g is None and w is None else names
@@ -175,6 +185,8 @@ def check_control_kwargs(kw, shape):
         if tracks.dim() != 4 or tuple(tracks.shape[:2]) != (B, T):
             raise ValueError(f"control_tracks has shape {tuple(tracks.shape)}, expected ({B}, {T}, Km, {L.SCENE_REC})")
         out.update(tracks=tracks, track_bounds=track_bounds(tracks))
+    if terrain is not None:
+        out.update(_terrain_inputs(terrain, trec, stand, kw.get("control_stand_threshold"), B, (B, T, J), F_, "control_"))
     if T > limit:
         raise ValueError(f"T = {T}: joint control takes at most {limit} frames at F = {F_}"
                          + (f" with {scene.shape[1]} primitives" if scene is not None else ""))
@@ -213,8 +225,37 @@ def check_control_kwargs(kw, shape):
     return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters), **out}
 
 
+def _terrain_inputs(terrain, trec, stand, threshold, N, stand_shape, F_, prefix):
+    """The checked terrain entries of ``check_control_kwargs`` (N = B) and ``check_canvas_control_kwargs`` (N = M): ``terrain``
+    (N, Gz, Gx), ``terrain_rec`` (N, 8) and ``stand`` of ``stand_shape`` or, for "contacts", ``stand_feet`` / ``stand_threshold``."""
+    from .motion_scene import check_stand, check_terrain
+    if trec is None:
+        raise ValueError(f"{prefix}terrain given without {prefix}terrain_rec")
+    terrain, trec = check_terrain(terrain, trec, prefix + "terrain")
+    if terrain.dim() != 3 or terrain.shape[0] != N:
+        raise ValueError(f"{prefix}terrain has shape {tuple(terrain.shape)}, expected ({N}, Gz, Gx)")
+    out = {"terrain": terrain.cpu(), "terrain_rec": trec.cpu()}
+    if isinstance(stand, str):
+        from .motion_features import SKELETONS, skeleton_for_feats
+        name = skeleton_for_feats(F_)
+        if stand != "contacts" or name is None:
+            raise ValueError(f'{prefix}stand must be stand weights {tuple(stand_shape)} or "contacts" (at a feature width with a '
+                             f"skeleton), not {stand!r} at F = {F_}")
+        thr = 0.5 if threshold is None else float(threshold)
+        if not math.isfinite(thr):
+            raise ValueError(f"{prefix}stand_threshold must be finite")
+        out.update(stand_feet=tuple(SKELETONS[name].feet), stand_threshold=thr)
+    else:
+        if threshold is not None:
+            raise ValueError(f'{prefix}stand_threshold goes with {prefix}stand="contacts"')
+        if stand is not None:
+            out.update(stand=check_stand(stand, stand_shape, prefix + "stand").cpu())
+    return out
+
+
 CANVAS_SCENE_KEYS = ("canvas_control_scene", "canvas_control_joint_params")
 CANVAS_TRACKS_KEY = "canvas_control_tracks"
+CANVAS_TERRAIN_KEYS = ("canvas_control_terrain", "canvas_control_terrain_rec", "canvas_control_stand", "canvas_control_stand_threshold")
 CANVAS_CONTROL_KEYS = ("canvas_control_offsets", "canvas_control_rows", "canvas_control_joints", "canvas_control_weights",
                        "canvas_control_mean", "canvas_control_std")
 
@@ -236,18 +277,27 @@ def check_canvas_control_kwargs(kw, shape):
     ``check_control_kwargs`` checks its own; with a scene ``canvas_control_joints`` / ``canvas_control_weights`` may both be
     left out (``targets`` / ``weights`` None).
     Tracks: ``canvas_control_tracks`` (total, Km, 12), per-frame records in canvas order, with or without a
-    scene and targets, come back as ``tracks`` and ``track_bounds`` (total, 4).  Host logic."""
+    scene and targets, come back as ``tracks`` and ``track_bounds`` (total, 4).
+    Terrain: ``canvas_control_terrain`` (M, Gz, Gx) with ``canvas_control_terrain_rec`` (M, 8), one ground per
+    motion in its canvas frame, with or without a scene, tracks and targets, come back as ``terrain`` / ``terrain_rec``;
+    ``canvas_control_stand``, stand weights (total, J) in canvas order or ``"contacts"`` (with
+    ``canvas_control_stand_threshold``, default 0.5), as ``stand`` or ``stand_feet`` / ``stand_threshold``, checked as
+    ``check_control_kwargs`` checks its own.  Host logic."""
     from .motion_control import joints_for_feats
     names = CANVAS_CONTROL_KEYS
     vals = [kw.get(k) for k in names]
     scene, jp = (kw.get(k) for k in CANVAS_SCENE_KEYS)
     tracks = kw.get(CANVAS_TRACKS_KEY)
-    if tracks is not None and scene is None and vals[0] is not None:
+    terrain, trec, stand, sthr = (kw.get(k) for k in CANVAS_TERRAIN_KEYS)
+    if terrain is None and (trec is not None or stand is not None or sthr is not None):
+        raise ValueError("canvas_control_terrain_rec / canvas_control_stand / canvas_control_stand_threshold given without "
+                         "canvas_control_terrain")
+    if (tracks is not None or terrain is not None) and scene is None and vals[0] is not None:
         scene = torch.zeros((max(torch.as_tensor(vals[0]).numel() - 1, 0), 0, L.SCENE_REC))
     given = [k for k, v in zip(names, vals) if v is not None]
     if jp is not None and scene is None:
         raise ValueError("canvas_control_joint_params given without canvas_control_scene")
-    if not given and scene is None and tracks is None:
+    if not given and scene is None and tracks is None and terrain is None:
         return None
     aim = scene is None or vals[2] is not None or vals[3] is not None
     need = names if aim else names[:2] + names[4:]
@@ -257,7 +307,7 @@ def check_canvas_control_kwargs(kw, shape):
     if not aim:
         vals[2] = vals[3] = torch.zeros(0)  # placeholders through the common conversions below
     if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std", "control_scene",
-                                           "control_tracks")):
+                                           "control_tracks", "control_terrain")):
         raise ValueError("canvas_control_* and the per-window control_joints / control_weights are exclusive")
     if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
         raise ValueError("canvas joint control does not combine with composed prompts")
@@ -318,6 +368,8 @@ def check_canvas_control_kwargs(kw, shape):
         if tracks.dim() != 3 or tracks.shape[0] != total:
             raise ValueError(f"canvas_control_tracks has shape {tuple(tracks.shape)}, expected ({total}, Km, {L.SCENE_REC})")
         out.update(tracks=tracks, track_bounds=track_bounds(tracks))
+    if terrain is not None:
+        out.update(_terrain_inputs(terrain, trec, stand, sthr, M, (total, J), F_, "canvas_control_"))
     if aim:
         if tuple(g.shape) != (total, J, 3):
             raise ValueError(f"canvas_control_joints has shape {tuple(g.shape)}, expected {(total, J, 3)}")
@@ -369,7 +421,7 @@ def check_handshake_kwargs(kw, shape):
     if any(kw.get(k) is not None for k in ("compose_weights", "compose_xf_proj", "compose_xf_out", "compose_text")):
         raise NotImplementedError("composed prompts over a long motion are not supported yet")
     if any(kw.get(k) is not None for k in ("control_joints", "control_weights", "control_mean", "control_std", "control_scene",
-                                           "control_tracks")):
+                                           "control_tracks", "control_terrain")):
         raise NotImplementedError("per-window joint control over a long motion is not supported: targets need canvas "
                                   "coordinates; give them as canvas_control_* (generate_long(control_joints=))")
     B, T, _ = (int(v) for v in shape)
@@ -552,6 +604,12 @@ class Conditioning:
     ``scene_tracks``: obstacles that move, a list of ``motion_scene`` track stacks (``moving_sphere`` ...,
     ``character_tracks``) shared by all samples or one list per sample (or packed records), over T_max frames; with or without
     ``scene`` and targets, under the same ``mean`` / ``std``, joint radius and weights and guidance (``track_records``).
+    ``terrain``: a height-map ground, one ``motion_scene`` terrain (``heightfield`` / ``ramp`` / ``stairs``)
+    shared by all samples or a list of one per sample: every joint is kept above it, by its ``scene_joint_radius`` and under
+    its ``scene_joint_weights``, through the same guidance, with or without ``scene``, ``scene_tracks`` and targets
+    (``terrain_grids`` / ``terrain_records``).  ``terrain_stand``: which joints are pulled down onto the ground as well: None
+    (none), ``"contacts"`` (on every step the foot joints whose foot-contact label in that step's x0, de-normalised, exceeds
+    ``terrain_stand_threshold``), or stand weights (N, T_max, J) >= 0.
     ``edit_joints``: N joint clips (n_i, J, 3) in place of ``edit_motion`` (needs ``mean`` / ``std``), turned into feature rows
     once per call (``edit_rows_from_joints``: ``motion_features.joints_to_motion``) and zero-padded to the mask's
     frames; a clip of n frames gives n - 1 rows, so the mask may keep frames up to n - 2.
@@ -573,7 +631,7 @@ class Conditioning:
                  control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,
                  device=None, to_motion=None, edit_bvh=None, bvh_options=None, init_motion=None, init_joints=None,
                  init_bvh=None, strength=None, latents=None, latent_step=None, scene=None, scene_joint_radius=None,
-                 scene_joint_weights=None, scene_tracks=None):
+                 scene_joint_weights=None, scene_tracks=None, terrain=None, terrain_stand=None, terrain_stand_threshold=0.5):
         self.captions, self.dim_pose = captions, dim_pose
         self.init, self.strength, self.latents, self.latent_step = None, None, None, None
         if init_motion is not None or init_joints is not None or init_bvh is not None:
@@ -620,17 +678,32 @@ class Conditioning:
             if rows is not None:
                 check_joint_edit_mask(self.edit[1], rows)
         self.control = self._control(control_joints, control_weights, mean, std, dim_pose,
-                                     scene is not None or scene_tracks is not None)
+                                     scene is not None or scene_tracks is not None or terrain is not None)
         self.scene_records = self.scene_joint_params = self.track_records = None
-        if scene is not None or scene_tracks is not None:
+        self.terrain_grids = self.terrain_records = self.terrain_stand = self.terrain_stand_threshold = None
+        if scene is not None or scene_tracks is not None or terrain is not None:
             from .motion_control import joints_for_feats
-            from .motion_scene import batch_scene, batch_tracks, joint_params
+            from .motion_scene import batch_scene, batch_terrain, batch_tracks, joint_params
             self.scene_records = batch_scene([] if scene is None else scene, len(captions))
             self.scene_joint_params = joint_params(joints_for_feats(dim_pose), scene_joint_radius, scene_joint_weights)
             if scene_tracks is not None:
                 self.track_records = batch_tracks(scene_tracks, len(captions), self._track_frames(scene_tracks))
+            if terrain is not None:
+                self.terrain_grids, self.terrain_records = batch_terrain(terrain, len(captions))
+                if isinstance(terrain_stand, str):
+                    if terrain_stand != "contacts":
+                        raise ValueError(f'terrain_stand must be None, "contacts" or stand weights, not {terrain_stand!r}')
+                    self.terrain_stand, self.terrain_stand_threshold = terrain_stand, float(terrain_stand_threshold)
+                elif terrain_stand is not None:
+                    st = torch.as_tensor(terrain_stand, dtype=torch.float32)
+                    if st.dim() != 3 or st.shape[0] != len(captions) or st.shape[2] != joints_for_feats(dim_pose):
+                        raise ValueError(f"terrain_stand of shape {tuple(st.shape)} must be (N = {len(captions)}, T_max, "
+                                         f"{joints_for_feats(dim_pose)})")
+                    self.terrain_stand = st
         elif scene_joint_radius is not None or scene_joint_weights is not None:
-            raise ValueError("scene_joint_radius / scene_joint_weights go with scene or scene_tracks")
+            raise ValueError("scene_joint_radius / scene_joint_weights go with scene, scene_tracks or terrain")
+        if terrain is None and terrain_stand is not None:
+            raise ValueError("terrain_stand goes with terrain")
         self.control_scale, self.control_iters = control_scale, control_iters
 
     @staticmethod
@@ -727,6 +800,15 @@ class Conditioning:
             if trk.shape[1] < T:  # a track ends where its stack ends: padding from there on
                 trk = torch.cat([trk, trk.new_zeros((trk.shape[0], T - trk.shape[1]) + tuple(trk.shape[2:]))], dim=1)
             out.update(control_tracks=trk[:, :T].contiguous().to(device))
+        if self.terrain_grids is not None:
+            out.update(control_terrain=self.terrain_grids[rows].to(device), control_terrain_rec=self.terrain_records[rows].to(device))
+            if isinstance(self.terrain_stand, str):
+                out.update(control_stand=self.terrain_stand, control_stand_threshold=self.terrain_stand_threshold)
+            elif self.terrain_stand is not None:
+                st = self.terrain_stand[rows]
+                if st.shape[1] < T:
+                    raise ValueError(f"terrain_stand has {st.shape[1]} frames, the batch {T}")
+                out.update(control_stand=st[:, :T].contiguous().to(device))
         n = len(self.captions_of(rows))
         return {**out, "control_mean": c["mean"].to(device).expand(n, -1), "control_std": c["std"].to(device).expand(n, -1),
                 "control_scale": self.control_scale, "control_iters": self.control_iters}

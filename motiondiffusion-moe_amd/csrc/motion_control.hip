@@ -15,6 +15,7 @@
 // accumulators.  No other column of the feature row enters recover_from_ric, so none is read or written.
 #include "kernels.h"
 #include "scene_sdf.h"
+#include "terrain.h"
 
 #include <cmath>
 
@@ -55,14 +56,19 @@ __device__ __forceinline__ RotD rot_d(float cw, float sw) {
 //                then both be null (no target term).
 // TRACKS = true: the mdm_joint_tracks_* calls, with SCENE: Km more records per frame, read from global memory
 //                at tracks + ((b T + t) Km) SCENE_REC, behind the frame's bounding ball of tbounds (null: never skipped).
-template <bool GUIDE, bool MASK, bool SCENE, bool TRACKS = false>
+// TERRAIN = true: the mdm_joint_terrain_* calls, with TRACKS (Km may be 0): the height grid of the sample at
+//                terrain + b Gz Gx with its record at trec + b TERRAIN_REC, gdim = Gx | Gz << 16, and the stand weights of
+//                frame t at stand + (b T + t) J (null: all 0), all three read from global memory (terrain.h).
+template <bool GUIDE, bool MASK, bool SCENE, bool TRACKS = false, bool TERRAIN = false>
 __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
     float* x0, float* x, const float* __restrict__ mask, const int* __restrict__ len, const float* __restrict__ mean,
     const float* __restrict__ sd, const float* __restrict__ targets, const float* __restrict__ weights, int T, int F,
     int J, float scale, int iters, const float* __restrict__ coef, int steps, const int* __restrict__ t_ptr, int t_imm,
     float* __restrict__ loss_out, float* __restrict__ grad_out, const float* __restrict__ scene, int K,
-    const float* __restrict__ jparams, const float* __restrict__ tracks, int Km, const float* __restrict__ tbounds) {
+    const float* __restrict__ jparams, const float* __restrict__ tracks, int Km, const float* __restrict__ tbounds,
+    const float* __restrict__ terrain, const float* __restrict__ trec, int gdim, const float* __restrict__ stand) {
   static_assert(SCENE || !TRACKS, "tracks use the scene's joint parameters");
+  static_assert(TRACKS || !TERRAIN, "the terrain rides on the forms that keep their pointers in vector registers");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int D = 3 * J + 1;               // steerable columns: root (4) + ric (3 (J - 1))
   const int DS = D | 1;                  // odd LDS row stride
@@ -103,7 +109,23 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
   const float* bnd0 = nullptr;
   if (TRACKS) {
     trk0 = tracks + ((int64_t)b * T + tid) * Km * scene::SCENE_REC;
-    if (tbounds) bnd0 = tbounds + ((int64_t)b * T + tid) * 4;
+    if (!TERRAIN && tbounds) bnd0 = tbounds + ((int64_t)b * T + tid) * 4;  // TERRAIN: set below, never null
+  }
+  // TERRAIN: the grid, the record and the stand weights of frame tid, held the same way; the grid's sides in one register.
+  // Without stand weights (and without balls) the reads go to the sample's record with steps of 0, and their bits are
+  // masked out: a test of the pointer inside the iteration loop is hoisted as a lane mask into a pair of scalar registers.
+  const float* hgrid = nullptr;
+  const float* hrec = nullptr;
+  const float* std0 = nullptr;
+  int gd = 0, sstep = 0, bstep = 0;
+  if (TERRAIN) {
+    gd = terrain::own(gdim);
+    hgrid = scene::own<TERRAIN>(terrain + (int64_t)b * (gdim & 0xffff) * (gdim >> 16));
+    hrec = scene::own<TERRAIN>(trec + (int64_t)b * terrain::TERRAIN_REC);
+    std0 = scene::own<TERRAIN>(stand ? stand + ((int64_t)b * T + tid) * J : trec + (int64_t)b * terrain::TERRAIN_REC);
+    sstep = terrain::own(stand ? 1 : 0);
+    bnd0 = scene::own<TERRAIN>(tbounds ? tbounds + ((int64_t)b * T + tid) * 4 : trec + (int64_t)b * terrain::TERRAIN_REC);
+    bstep = terrain::own(tbounds ? 1 : 0);
   }
 
   if (!GUIDE) {  // every entry that cannot receive gradient: frames past the length and the columns past D
@@ -125,10 +147,13 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
   __syncthreads();
   auto val = [&](int t, int c) { return add(mul(xs[t * DS + c], lsd[c]), lmean[c]); };
   // one gradient entry g (w.r.t. the normalised feature): written out, or the guidance step applied in LDS
+  // TERRAIN: the step size and the mask's row stride as values of the thread's own as well
+  const float step = TERRAIN ? __int_as_float(terrain::own(__float_as_int(scale))) : scale;
+  const int mF = TERRAIN && MASK ? terrain::own(F) : F;
   auto emit = [&](int t, int c, float g) {
     if (GUIDE) {
-      const float u = MASK ? (1.f - mk[(int64_t)t * F + c]) * g : g;
-      xs[t * DS + c] = xs[t * DS + c] - scale * u;
+      const float u = MASK ? (1.f - mk[(int64_t)t * mF + c]) * g : g;
+      xs[t * DS + c] = xs[t * DS + c] - step * u;
     } else {
       grad_out[row0 + (int64_t)t * F + c] = g;
     }
@@ -174,10 +199,18 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
       float ball[4] = {0.f, 0.f, 0.f, INFINITY};
       if (TRACKS) {
         trk = trk0 + (int64_t)(t - tid) * Km * scene::SCENE_REC;
-        if (bnd0) {
+        if (!TERRAIN && bnd0) {
           const float4 bb = *reinterpret_cast<const float4*>(bnd0 + (int64_t)(t - tid) * 4);
           ball[0] = bb.x, ball[1] = bb.y, ball[2] = bb.z, ball[3] = bb.w;
         }
+      }
+      float hr[terrain::TERRAIN_REC];  // TERRAIN: the sample's record and the frame's stand weights
+      const float* stw = nullptr;
+      if (TERRAIN) {
+        terrain::load_record(hrec, hr);
+        stw = std0 + (int64_t)(t - tid) * J * sstep;
+        const float4 bb = *reinterpret_cast<const float4*>(bnd0 + (int64_t)(t - tid) * 4 * bstep);
+        ball[0] = bb.x, ball[1] = bb.y, ball[2] = bb.z, ball[3] = terrain::pick(bb.w, INFINITY, bstep);  // no balls: never skipped
       }
       auto dl = [&](int k, float p) {  // dL/dP of one coordinate; W == 0 contributes nothing, whatever G holds
         if (SCENE && !aim) return 0.f;
@@ -192,6 +225,9 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
         g[0] = dl(0, qx), g[1] = dl(1, py), g[2] = dl(2, qz);
         if (SCENE && !TRACKS) lsum += scene::penalty(prims, K, jp[0], jp[1], qx, py, qz, g);
         if (TRACKS) lsum += scene::penalty_tracks(prims, K, trk, Km, ball, jp[0], jp[1], qx, py, qz, g);
+        if (TERRAIN)
+          lsum += terrain::penalty(hgrid, gd & 0xffff, gd >> 16, hr, jp[0], jp[1], terrain::stand_weight(stw, 0, sstep), qx, py,
+                                   qz, g);
         sx += g[0], sz += g[2];
         fr[t * FR + GH] = g[1];
       }
@@ -205,6 +241,9 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
         g[0] = dl(3 * j, px), g[1] = dl(3 * j + 1, vy), g[2] = dl(3 * j + 2, pz);
         if (SCENE && !TRACKS) lsum += scene::penalty(prims, K, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
         if (TRACKS) lsum += scene::penalty_tracks(prims, K, trk, Km, ball, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
+        if (TERRAIN)
+          lsum += terrain::penalty(hgrid, gd & 0xffff, gd >> 16, hr, jp[2 * j], jp[2 * j + 1],
+                                   terrain::stand_weight(stw, j, sstep), px, vy, pz, g);
         if (GUIDE && g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) continue;  // no step: the entries keep their bits
         sx += g[0], sz += g[2];
         sa += 2.0 * ((double)g[0] * (r.e * vz + r.f * vx) + (double)g[2] * (r.f * vz - r.e * vx));
@@ -273,6 +312,7 @@ size_t control_lds_bytes(int T, int J, int prims = -1) {
 }
 
 static_assert(scene::MAX_TRACKS == MDM_SCENE_MAX_TRACKS, "scene_sdf.h and mdm_hip.h disagree");
+static_assert(terrain::MAX_GRID == MDM_TERRAIN_MAX_GRID && terrain::TERRAIN_REC == MDM_TERRAIN_REC, "terrain.h and mdm_hip.h disagree");
 
 }  // namespace
 }  // namespace mdm
@@ -296,7 +336,8 @@ int mdm_joint_loss_grad(const float* x0, const int32_t* length, const float* mea
   const size_t smem = mdm::control_lds_bytes(T, J);
   hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
                      const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J, 0.f, 1,
-                     nullptr, 1, nullptr, 0, loss_out, grad_out, nullptr, 0, nullptr, nullptr, 0, nullptr);
+                     nullptr, 1, nullptr, 0, loss_out, grad_out, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                     nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -315,11 +356,11 @@ int mdm_joint_guidance(float* x, float* x0, const float* mask, const int32_t* le
   if (mask)
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
                        x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev, t_imm,
-                       nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr);
+                       nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
                        x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev,
-                       t_imm, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr);
+                       t_imm, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -344,7 +385,8 @@ int mdm_joint_scene_loss_grad(const float* x0, const int32_t* length, const floa
   const size_t smem = mdm::control_lds_bytes(T, J, K);
   hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
                      (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, nullptr, 0, nullptr);
+                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, nullptr, 0, nullptr,
+                     nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -367,11 +409,12 @@ int mdm_joint_scene_guidance(float* x, float* x0, const float* mask, const int32
   if (mask)
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
                        (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, nullptr, 0, nullptr);
+                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
                        (hipStream_t)stream, x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef,
-                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, nullptr, 0, nullptr);
+                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, nullptr, 0, nullptr,
+                       nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -392,7 +435,8 @@ int mdm_joint_tracks_loss_grad(const float* x0, const int32_t* length, const flo
   const size_t smem = mdm::control_lds_bytes(T, J, K);
   hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
                      (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, tracks, Km, track_bounds);
+                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, tracks, Km, track_bounds,
+                     nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -417,11 +461,70 @@ int mdm_joint_tracks_guidance(float* x, float* x0, const float* mask, const int3
   if (mask)
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
                        (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds);
+                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds,
+                       nullptr, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
                        (hipStream_t)stream, x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef,
-                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds);
+                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds,
+                       nullptr, nullptr, 0, nullptr);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_joint_terrain_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
+                                const float* weights, const float* scene, int32_t K, const float* joint_params,
+                                const float* tracks, int32_t Km, const float* track_bounds, const float* terrain,
+                                const float* terrain_rec, int32_t Gx, int32_t Gz, const float* stand, int32_t B, int32_t T,
+                                int32_t F, float* loss_out, float* grad_out, void* stream) {
+  if (!terrain)  // no terrain: the launch of mdm_joint_tracks_loss_grad
+    return mdm_joint_tracks_loss_grad(x0, length, mean, std, targets, weights, scene, K, joint_params, tracks, Km, track_bounds, B,
+                                      T, F, loss_out, grad_out, stream);
+  if (!mdm::terrain::terrain_ok(terrain, terrain_rec, Gx, Gz, stand)) return MDM_ERR_ARG;
+  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
+  if (!x0 || !length || !mean || !std || !joint_params || !loss_out || !grad_out || !targets != !weights) return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::control_joints(F);
+  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
+  if (B == 0) return MDM_OK;
+  const size_t smem = mdm::control_lds_bytes(T, J, K);
+  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
+                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J,
+                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, tracks, Km, track_bounds, terrain,
+                     terrain_rec, Gx | Gz << 16, stand);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_joint_terrain_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
+                               const float* targets, const float* weights, const float* scene, int32_t K,
+                               const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds,
+                               const float* terrain, const float* terrain_rec, int32_t Gx, int32_t Gz, const float* stand,
+                               int32_t B, int32_t T, int32_t F, float scale, int32_t iters, const float* coef, int32_t steps,
+                               const int32_t* t_dev, int32_t t_imm, void* stream) {
+  if (!terrain)  // no terrain: the launch of mdm_joint_tracks_guidance
+    return mdm_joint_tracks_guidance(x, x0, mask, length, mean, std, targets, weights, scene, K, joint_params, tracks, Km,
+                                     track_bounds, B, T, F, scale, iters, coef, steps, t_dev, t_imm, stream);
+  if (!mdm::terrain::terrain_ok(terrain, terrain_rec, Gx, Gz, stand)) return MDM_ERR_ARG;
+  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
+  if (!x || !x0 || !length || !mean || !std || !joint_params || !coef || !targets != !weights) return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::control_joints(F);
+  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
+  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
+  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
+  if (B == 0) return MDM_OK;
+  const size_t smem = mdm::control_lds_bytes(T, J, K);
+  if (mask)
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
+                       (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps,
+                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds, terrain, terrain_rec,
+                       Gx | Gz << 16, stand);
+  else
+    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
+                       (hipStream_t)stream, x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef,
+                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds, terrain,
+                       terrain_rec, Gx | Gz << 16, stand);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }

@@ -22,6 +22,7 @@
 // scans: P agrees with mdm_motion_postprocess to rounding, not bit for bit.
 #include "kernels.h"
 #include "scene_sdf.h"
+#include "terrain.h"
 
 #include <cmath>
 #include <cstdint>
@@ -92,15 +93,20 @@ __device__ __forceinline__ double block_scan(double v, double& carry, double* sl
 // may then both be null.
 // TRACKS = true: the mdm_canvas_tracks_* calls, with SCENE: Km more records per canvas frame, read from global
 // memory at tracks + ((motion_offsets[m] + t) Km) SCENE_REC, behind the frame's bounding ball of tbounds (null: never skipped).
-template <bool GUIDE, bool MASK, bool SCENE, bool TRACKS = false>
+// TERRAIN = true: the mdm_canvas_terrain_* calls, with TRACKS (Km may be 0): the height grid of motion m at
+// terrain + m Gz Gx with its record at trec + m TERRAIN_REC, gdim = Gx | Gz << 16, and the stand weights of canvas frame t at
+// stand + (motion_offsets[m] + t) J (null: all 0), all three read from global memory (terrain.h), in the canvas frame.
+template <bool GUIDE, bool MASK, bool SCENE, bool TRACKS = false, bool TERRAIN = false>
 __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
     float* x0, float* x, const float* __restrict__ mask, const int* __restrict__ offs, const int* __restrict__ frows,
     const float* __restrict__ mean, const float* __restrict__ sd, const float* __restrict__ targets,
     const float* __restrict__ weights, int F, int J, float scale, int iters, const float* __restrict__ coef, int steps,
     const int* __restrict__ t_ptr, int t_imm, float* loss_out, float* grad_out, float* ws,
     const float* __restrict__ scene, int K, const float* __restrict__ jparams, const float* __restrict__ tracks, int Km,
-    const float* __restrict__ tbounds) {
+    const float* __restrict__ tbounds, const float* __restrict__ terrain, const float* __restrict__ trec, int gdim,
+    const float* __restrict__ stand) {
   static_assert(SCENE || !TRACKS, "tracks use the scene's joint parameters");
+  static_assert(TRACKS || !TERRAIN, "the terrain rides on the forms that keep their pointers in vector registers");
   __shared__ double slots[3][CV_WAVES];  // the wave totals of up to three scans in flight
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int D = 3 * J + 1;          // steerable columns: root (4) + ric (3 (J - 1))
@@ -139,7 +145,23 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
   const float* bnd0 = nullptr;
   if (TRACKS) {
     trk0 = tracks + ((int64_t)c0 + tid) * Km * scene::SCENE_REC;
-    if (tbounds) bnd0 = tbounds + ((int64_t)c0 + tid) * 4;
+    if (!TERRAIN && tbounds) bnd0 = tbounds + ((int64_t)c0 + tid) * 4;  // TERRAIN: set below, never null
+  }
+  // TERRAIN: the grid, the record and the stand weights of canvas frame tid, held the same way; the grid's sides in one
+  // register.  Without stand weights (and without balls) the reads go to the motion's record with steps of 0, and their bits
+  // are masked out: a test of the pointer inside the iteration loop is hoisted as a lane mask into a pair of scalar registers.
+  const float* hgrid = nullptr;
+  const float* hrec = nullptr;
+  const float* std0 = nullptr;
+  int gd = 0, sstep = 0, bstep = 0;
+  if (TERRAIN) {
+    gd = terrain::own(gdim);
+    hgrid = scene::own<TERRAIN>(terrain + (int64_t)m * (gdim & 0xffff) * (gdim >> 16));
+    hrec = scene::own<TERRAIN>(trec + (int64_t)m * terrain::TERRAIN_REC);
+    std0 = scene::own<TERRAIN>(stand ? stand + ((int64_t)c0 + tid) * J : trec + (int64_t)m * terrain::TERRAIN_REC);
+    sstep = terrain::own(stand ? 1 : 0);
+    bnd0 = scene::own<TERRAIN>(tbounds ? tbounds + ((int64_t)c0 + tid) * 4 : trec + (int64_t)m * terrain::TERRAIN_REC);
+    bstep = terrain::own(tbounds ? 1 : 0);
   }
 
   if (!GUIDE) {  // the columns past D never receive gradient
@@ -185,8 +207,9 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
   };
 
   double lacc = 0.0;  // this thread's frames' share of the loss
+  const int passes = TERRAIN && !GUIDE ? 1 : iters;  // the loss and gradient are one evaluation: no counter to hold
 #pragma unroll 1
-  for (int it = 0; it < iters; ++it) {
+  for (int it = 0; it < passes; ++it) {
     // ---- forward pass ----
     double cang = 0.0, cpx = 0.0, cpz = 0.0;
 #pragma unroll 1
@@ -215,10 +238,18 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
         float ball[4] = {0.f, 0.f, 0.f, INFINITY};
         if (TRACKS) {
           trk = trk0 + (int64_t)(t - tid) * Km * scene::SCENE_REC;
-          if (bnd0) {
+          if (!TERRAIN && bnd0) {
             const float4 bb = *reinterpret_cast<const float4*>(bnd0 + (int64_t)(t - tid) * 4);
             ball[0] = bb.x, ball[1] = bb.y, ball[2] = bb.z, ball[3] = bb.w;
           }
+        }
+        float hr[terrain::TERRAIN_REC];  // TERRAIN: the motion's record and the frame's stand weights
+        const float* stw = nullptr;
+        if (TERRAIN) {
+          terrain::load_record(hrec, hr);
+          stw = std0 + (int64_t)(t - tid) * J * sstep;
+          const float4 bb = *reinterpret_cast<const float4*>(bnd0 + (int64_t)(t - tid) * 4 * bstep);
+          ball[0] = bb.x, ball[1] = bb.y, ball[2] = bb.z, ball[3] = terrain::pick(bb.w, INFINITY, bstep);  // no balls: never skipped
         }
         auto dl = [&](float w, float gk, float p) {  // dL/dP of one coordinate; W == 0 contributes nothing, whatever G holds
           if (w == 0.f) return 0.f;
@@ -236,6 +267,9 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
           g[0] = dl(w0[0], g0[0], qx), g[1] = dl(w0[1], g0[1], py), g[2] = dl(w0[2], g0[2], qz);
           if (SCENE && !TRACKS) lsum += scene::penalty(prims, K, jp[0], jp[1], qx, py, qz, g);
           if (TRACKS) lsum += scene::penalty_tracks(prims, K, trk, Km, ball, jp[0], jp[1], qx, py, qz, g);
+          if (TERRAIN)
+            lsum += terrain::penalty(hgrid, gd & 0xffff, gd >> 16, hr, jp[0], jp[1], terrain::stand_weight(stw, 0, sstep), qx, py,
+                                     qz, g);
         }
         sx += g[0], sz += g[2];
         fr[t * FR + GH] = g[1];
@@ -266,6 +300,9 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
             g[0] = dl(wv[u][0], gv[u][0], px), g[1] = dl(wv[u][1], gv[u][1], vy), g[2] = dl(wv[u][2], gv[u][2], pz);
             if (SCENE && !TRACKS) lsum += scene::penalty(prims, K, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
             if (TRACKS) lsum += scene::penalty_tracks(prims, K, trk, Km, ball, jp[2 * j], jp[2 * j + 1], px, vy, pz, g);
+            if (TERRAIN)
+              lsum += terrain::penalty(hgrid, gd & 0xffff, gd >> 16, hr, jp[2 * j], jp[2 * j + 1],
+                                       terrain::stand_weight(stw, j, sstep), px, vy, pz, g);
             if (GUIDE && g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) continue;  // no step: the entries keep their bits
             sx += g[0], sz += g[2];
             sa += 2.0 * ((double)g[0] * (r.e * vz + r.f * vx) + (double)g[2] * (r.f * vz - r.e * vx));
@@ -392,7 +429,8 @@ int mdm_canvas_joint_loss_grad(const float* x0, const int32_t* motion_offsets, c
   if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
   hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream,
                      const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr);
+                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                     nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -413,11 +451,13 @@ int mdm_canvas_joint_guidance(float* x, float* x0, const float* mask, const int3
   if (mask)
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
                        x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale, iters, coef, steps, t_dev,
-                       t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr);
+                       t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                       nullptr, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
                        x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr);
+                       t_dev, t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                       nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -441,7 +481,7 @@ int mdm_canvas_scene_loss_grad(const float* x0, const int32_t* motion_offsets, c
   hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
                      (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std,
                      targets, weights, F, J, 0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, scene, K,
-                     joint_params, nullptr, 0, nullptr);
+                     joint_params, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -468,12 +508,13 @@ int mdm_canvas_scene_guidance(float* x, float* x0, const float* mask, const int3
   if (mask)
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
                        (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale,
-                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, nullptr, 0, nullptr);
+                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, nullptr, 0, nullptr,
+                       nullptr, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
                        (hipStream_t)stream, x0, x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
                        scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, nullptr, 0,
-                       nullptr);
+                       nullptr, nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -498,7 +539,7 @@ int mdm_canvas_tracks_loss_grad(const float* x0, const int32_t* motion_offsets, 
   hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
                      (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std,
                      targets, weights, F, J, 0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, scene, K,
-                     joint_params, tracks, Km, track_bounds);
+                     joint_params, tracks, Km, track_bounds, nullptr, nullptr, 0, nullptr);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }
@@ -527,12 +568,76 @@ int mdm_canvas_tracks_guidance(float* x, float* x0, const float* mask, const int
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
                        (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale,
                        iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
-                       track_bounds);
+                       track_bounds, nullptr, nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
                        (hipStream_t)stream, x0, x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
                        scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
-                       track_bounds);
+                       track_bounds, nullptr, nullptr, 0, nullptr);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_canvas_terrain_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
+                                 const float* std, const float* targets, const float* weights, const float* scene, int32_t K,
+                                 const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds,
+                                 const float* terrain, const float* terrain_rec, int32_t Gx, int32_t Gz, const float* stand,
+                                 int32_t M, int32_t F, float* loss_out, float* grad_out, float* workspace, void* stream) {
+  if (!terrain)  // no terrain: the launch of mdm_canvas_tracks_loss_grad
+    return mdm_canvas_tracks_loss_grad(x0, motion_offsets, frame_rows, mean, std, targets, weights, scene, K, joint_params, tracks,
+                                       Km, track_bounds, M, F, loss_out, grad_out, workspace, stream);
+  if (!mdm::terrain::terrain_ok(terrain, terrain_rec, Gx, Gz, stand)) return MDM_ERR_ARG;
+  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
+  if (!x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !loss_out || !grad_out || !workspace ||
+      !targets != !weights)
+    return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::canvas_joints(F);
+  if (J == 0 || M < 0) return MDM_ERR_ARG;
+  if (M == 0) return MDM_OK;
+  const size_t smem = mdm::canvas_lds_bytes(J, K);
+  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
+                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std,
+                     targets, weights, F, J, 0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, scene, K,
+                     joint_params, tracks, Km, track_bounds, terrain, terrain_rec, Gx | Gz << 16, stand);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int mdm_canvas_terrain_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
+                                const float* mean, const float* std, const float* targets, const float* weights,
+                                const float* scene, int32_t K, const float* joint_params, const float* tracks, int32_t Km,
+                                const float* track_bounds, const float* terrain, const float* terrain_rec, int32_t Gx,
+                                int32_t Gz, const float* stand, int32_t M, int32_t F, float scale, int32_t iters,
+                                const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, float* workspace,
+                                void* stream) {
+  if (!terrain)  // no terrain: the launch of mdm_canvas_tracks_guidance
+    return mdm_canvas_tracks_guidance(x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, scene, K, joint_params,
+                                      tracks, Km, track_bounds, M, F, scale, iters, coef, steps, t_dev, t_imm, workspace, stream);
+  if (!mdm::terrain::terrain_ok(terrain, terrain_rec, Gx, Gz, stand)) return MDM_ERR_ARG;
+  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
+  if (!x || !x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !coef || !workspace ||
+      !targets != !weights)
+    return MDM_ERR_ARG;
+  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
+  const int J = mdm::canvas_joints(F);
+  if (J == 0 || M < 0) return MDM_ERR_ARG;
+  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
+  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
+  if (M == 0) return MDM_OK;
+  const size_t smem = mdm::canvas_lds_bytes(J, K);
+  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
+  if (mask)
+    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
+                       (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale,
+                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
+                       track_bounds, terrain, terrain_rec, Gx | Gz << 16, stand);
+  else
+    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
+                       (hipStream_t)stream, x0, x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
+                       scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
+                       track_bounds, terrain, terrain_rec, Gx | Gz << 16, stand);
   MDM_RETURN_IF_LAUNCH_FAILED();
   return MDM_OK;
 }

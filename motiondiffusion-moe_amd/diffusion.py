@@ -32,7 +32,9 @@ Joint-position control: ``model_kwargs`` may carry ``control_joints`` (B, T, J, 
 ``control_mean`` / ``control_std`` (B, F), ``control_scale`` and ``control_iters``, and with or without the targets a scene
 (``control_scene`` (B, K, 12) primitive records, ``control_joint_params`` (B, J, 2), whose penalty joins the
 loss: ``mdm_joint_scene_guidance``; DESIGN.md §25: ``control_tracks`` (B, T, Km, 12), records that differ per frame, moving
-obstacles: ``mdm_joint_tracks_guidance``); every loop and single step then moves its x0 down the gradient of the weighted
+obstacles: ``mdm_joint_tracks_guidance``; DESIGN.md §29: ``control_terrain`` (B, Gz, Gx) with ``control_terrain_rec`` (B, 8)
+and ``control_stand``, a height-map ground: ``mdm_joint_terrain_guidance``); every loop and single step then moves its x0
+down the gradient of the weighted
 squared distance of ``recover_from_ric(x0 * std + mean)`` to the targets after its update, and x_{t-1} with it (``mdm_joint_guidance``): trajectories, keyframes, end positions.
 
 Long motions: ``model_kwargs`` may carry handshake tables (``handshake_offsets``, ``handshake_rows``,
@@ -57,6 +59,7 @@ The host-side validation of these inputs (``check_*_kwargs``) lives in ``conditi
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 import enum
 import math
 from typing import Callable, Optional
@@ -722,6 +725,15 @@ class _StepRunner:
                 Km = int(ctl["tracks"].shape[2])
                 self.ctl.update(Km=Km, tracks=f32(ctl["tracks"], (B, T, Km, L.SCENE_REC)),
                                 track_bounds=f32(ctl["track_bounds"], (B, T, 4)))
+            if "terrain" in ctl:  # terrain: the height grids, their records and the stand weights
+                Gz, Gx = (int(v) for v in ctl["terrain"].shape[1:])
+                self.ctl.update(Gx=Gx, Gz=Gz, terrain=f32(ctl["terrain"], (B, Gz, Gx)), stand=None,
+                                terrain_rec=f32(ctl["terrain_rec"], (B, L.TERRAIN_REC)))
+                if "stand" in ctl:
+                    self.ctl["stand"] = f32(ctl["stand"], (B, T, J))
+                elif "stand_feet" in ctl:  # written on every step from that step's x0, in front of the guidance
+                    self.ctl.update(stand=torch.zeros((B, T, J), dtype=torch.float32, device=dev),
+                                    stand_feet=(C.c_int32 * 4)(*ctl["stand_feet"]), stand_threshold=ctl["stand_threshold"])
         # long motions: the handshake tables of the overlapping windows
         hs = check_handshake_kwargs(kw, shape)
         self.hs = None if hs is None else {k: v.to(dev).contiguous() if torch.is_tensor(v) else v for k, v in hs.items()}
@@ -744,6 +756,17 @@ class _StepRunner:
                 Km = int(cc["tracks"].shape[1])
                 self.cctl.update(Km=Km, tracks=f32(cc["tracks"], (tot, Km, L.SCENE_REC)),
                                  track_bounds=f32(cc["track_bounds"], (tot, 4)))
+            if "terrain" in cc:  # terrain: one grid and record per motion, stand weights in canvas order
+                Gz, Gx = (int(v) for v in cc["terrain"].shape[1:])
+                self.cctl.update(Gx=Gx, Gz=Gz, terrain=f32(cc["terrain"], (cc["M"], Gz, Gx)), stand=None,
+                                 terrain_rec=f32(cc["terrain_rec"], (cc["M"], L.TERRAIN_REC)))
+                if "stand" in cc:
+                    self.cctl["stand"] = f32(cc["stand"], (tot, J))
+                elif "stand_feet" in cc:
+                    off = cc["offsets"].tolist()
+                    self.cctl.update(stand=torch.zeros((max(tot, 1), J), dtype=torch.float32, device=dev),
+                                     stand_feet=(C.c_int32 * 4)(*cc["stand_feet"]), stand_threshold=cc["stand_threshold"],
+                                     spans=[(a, b) for a, b in zip(off[:-1], off[1:]) if b > a])
         # few-step modes (and every mode when editing, composing or controlling): per-step coefficients of the fused update;
         # self.x0 doubles as x0_prev (updated in place)
         table = self.known is not None or self.cw is not None or self.ctl is not None or self.cctl is not None
@@ -821,9 +844,9 @@ class _StepRunner:
 
     def _plan_update(self):
         """The update of a step, ``(entry name, arguments before the noise pointer, arguments after it)``, and the
-        entry and arguments of the joint guidance, mdm_joint_guidance or with a scene mdm_joint_scene_guidance (None without
-        control).  Every pointer belongs to a buffer the runner owns for its
-        lifetime; the noise pointer and the stream are the launch's.  Plain "cfg" / "ddpm" keep mdm_cfg_posterior_step and
+        entry and arguments of the joint guidance, mdm_joint_guidance, with a scene mdm_joint_scene_guidance, with tracks
+        mdm_joint_tracks_guidance, with a terrain mdm_joint_terrain_guidance (None without control).  Every pointer belongs
+        to a buffer the runner owns for its lifetime; the noise pointer and the stream are the launch's.  Plain "cfg" / "ddpm" keep mdm_cfg_posterior_step and
         plain "ddim" mdm_ddim_step; with a coefficient table the three fused entries share their head and tail."""
         p = L.ptr
         x, eps, x0 = p(self.xx), p(self.eps), p(self.x0)  # x_t is rows [0, B) of xx, updated in place
@@ -836,8 +859,13 @@ class _StepRunner:
             scene = (p(c["scene"]), c["K"], p(c["joint_params"])) if "K" in c else ()
             if "Km" in c:  # with tracks
                 scene += (p(c["tracks"]), c["Km"], p(c["track_bounds"]))
-            guide = ("mdm_joint_tracks_guidance" if "Km" in c else "mdm_joint_scene_guidance" if scene else "mdm_joint_guidance",
-                     (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"])) + scene
+            name = "mdm_joint_tracks_guidance" if "Km" in c else "mdm_joint_scene_guidance" if scene else "mdm_joint_guidance"
+            if "terrain" in c:  # with a terrain, on top of the tracks arguments
+                if "Km" not in c:
+                    scene += (0, 0, 0)
+                scene += (p(c["terrain"]), p(c["terrain_rec"]), c["Gx"], c["Gz"], p(c["stand"]))
+                name = "mdm_joint_terrain_guidance"
+            guide = (name, (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"])) + scene
                      + (self.B, self.T, self.Fe, c["scale"], c["iters"], p(self.coef)) + clock)
         self._guide_canvas = None  # the entry and arguments of the canvas guidance (None without canvas control)
         if self.cctl is not None:
@@ -845,8 +873,13 @@ class _StepRunner:
             scene = (p(c["scene"]), c["K"], p(c["joint_params"])) if "K" in c else ()
             if "Km" in c:
                 scene += (p(c["tracks"]), c["Km"], p(c["track_bounds"]))
-            self._guide_canvas = ("mdm_canvas_tracks_guidance" if "Km" in c else
-                                  "mdm_canvas_scene_guidance" if scene else "mdm_canvas_joint_guidance",
+            name = "mdm_canvas_tracks_guidance" if "Km" in c else "mdm_canvas_scene_guidance" if scene else "mdm_canvas_joint_guidance"
+            if "terrain" in c:
+                if "Km" not in c:
+                    scene += (0, 0, 0)
+                scene += (p(c["terrain"]), p(c["terrain_rec"]), c["Gx"], c["Gz"], p(c["stand"]))
+                name = "mdm_canvas_terrain_guidance"
+            self._guide_canvas = (name,
                                   (x, x0, p(self.mask), p(c["offsets"]), p(c["rows"]), p(c["mean"]), p(c["std"]),
                                    p(c["targets"]), p(c["weights"])) + scene
                                   + (c["M"], self.Fe, c["scale"], c["iters"], p(self.coef)) + clock + (p(c["ws"]),))
@@ -890,6 +923,17 @@ class _StepRunner:
             self._handshake(self.eps, self.R // B, True, s)
         name, head, tail = self._update
         L.check(getattr(lib, name)(*head, self.noise.data_ptr() if use_noise else 0, *tail, s), name)
+        if self.ctl is not None and "stand_feet" in self.ctl:  # terrain_stand="contacts": this step's planted feet, one launch
+            c = self.ctl                                          # (a row of mean / std per T frames)
+            L.check(lib.mdm_terrain_stand_weights(self.x0.data_ptr(), None, B * self.T, c["mean"].data_ptr(), c["std"].data_ptr(),
+                                                  self.Fe, self.T, c["stand_feet"], c["stand_threshold"], c["stand"].data_ptr(), s),
+                    "mdm_terrain_stand_weights")
+        if self.cctl is not None and "stand_feet" in self.cctl:  # the same over the canvases, through their row tables: a
+            c = self.cctl                                         # launch per long motion (its own mean / std row)
+            for m, (lo, hi) in enumerate(c["spans"]):
+                L.check(lib.mdm_terrain_stand_weights(self.x0.data_ptr(), c["rows"][lo:].data_ptr(), hi - lo, c["mean"][m].data_ptr(),
+                                                      c["std"][m].data_ptr(), self.Fe, 0, c["stand_feet"], c["stand_threshold"],
+                                                      c["stand"][lo:].data_ptr(), s), "mdm_terrain_stand_weights")
         if self._guide is not None:  # x0 and x_{t-1} moved down the joint-position loss, before the counter moves
             L.check(getattr(lib, self._guide[0])(*self._guide[1], s), self._guide[0])
         if self._guide_canvas is not None:  # once per long motion over its canvas, then the owner's bits into every overlap

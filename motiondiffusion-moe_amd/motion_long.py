@@ -181,7 +181,7 @@ def batch_control_tables(plans, idx, T: int, joints, weights) -> Dict[str, torch
 
 def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, control_scale=None, control_iters=None,
                    mean=None, std=None, device=None, scene=None, scene_joint_radius=None, scene_joint_weights=None,
-                   scene_tracks=None):
+                   scene_tracks=None, terrain=None, terrain_stand=None, terrain_stand_threshold=0.5):
     """The joint-control inputs of ``DDPMTrainer.generate_long`` (described there), checked once for the call:
     one (C_i, J, 3) target array per motion of ``plans`` in canvas frames and weights broadcastable to it (aligned on the
     frame dim), with the dataset's ``mean`` / ``std``.  Returns ``tables(idx, T)``: the ``canvas_control_*`` model kwargs
@@ -191,11 +191,16 @@ def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, c
     ``scene``: one list of ``motion_scene`` primitives per motion, in its canvas frame, with
     ``scene_joint_radius`` / ``scene_joint_weights`` (J,); it may come without targets, and adds ``canvas_control_scene`` /
     ``canvas_control_joint_params`` to the tables.  ``scene_tracks``: one list of ``motion_scene`` track stacks
-    per motion, over its canvas frames, with or without ``scene`` and targets; it adds ``canvas_control_tracks``."""
+    per motion, over its canvas frames, with or without ``scene`` and targets; it adds ``canvas_control_tracks``.
+    ``terrain`` (DESIGN.md §29): one ``motion_scene`` terrain per motion, in its canvas frame, with or without the rest;
+    ``terrain_stand``: None, ``"contacts"`` (with ``terrain_stand_threshold``) or one (C_i, J) array of stand weights per
+    motion; they add ``canvas_control_terrain`` / ``canvas_control_terrain_rec`` / ``canvas_control_stand``."""
     aim = control_joints is not None or control_weights is not None
-    if scene is None and scene_tracks is None and (scene_joint_radius is not None or scene_joint_weights is not None):
-        raise ValueError("scene_joint_radius / scene_joint_weights go with scene or scene_tracks")
-    if scene is None and scene_tracks is not None:
+    if scene is None and scene_tracks is None and terrain is None and (scene_joint_radius is not None or scene_joint_weights is not None):
+        raise ValueError("scene_joint_radius / scene_joint_weights go with scene, scene_tracks or terrain")
+    if terrain is None and terrain_stand is not None:
+        raise ValueError("terrain_stand goes with terrain")
+    if scene is None and (scene_tracks is not None or terrain is not None):
         scene = [[] for _ in plans]
     if not aim and scene is None:
         if control_scale is not None or control_iters is not None:
@@ -227,6 +232,19 @@ def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, c
                 t is None or _is_stack(t) for t in scene_tracks):
             raise ValueError(f"scene_tracks must hold one list of track stacks per motion ({N}), over its canvas frames")
         tracks = [pack_tracks(t, plans[i][3]) for i, t in enumerate(scene_tracks)]
+    grounds = stands = None
+    if terrain is not None:
+        from .motion_scene import Terrain, batch_terrain, check_stand
+        if isinstance(terrain, Terrain) or len(terrain) != N:
+            raise ValueError(f"terrain must hold one terrain per motion ({N}), in its canvas frame")
+        grounds = batch_terrain(list(terrain), N)
+        if isinstance(terrain_stand, str):
+            if terrain_stand != "contacts":
+                raise ValueError(f'terrain_stand must be None, "contacts" or one array of stand weights per motion, not {terrain_stand!r}')
+        elif terrain_stand is not None:
+            if torch.is_tensor(terrain_stand) or isinstance(terrain_stand, np.ndarray) or len(terrain_stand) != N:
+                raise ValueError(f"terrain_stand must hold one (canvas_len, J) array of stand weights per motion ({N})")
+            stands = [check_stand(s, (plans[i][3], J), f"terrain_stand of motion {i}") for i, s in enumerate(terrain_stand)]
     joints, weights = [], []
     for i, (g, w) in enumerate(zip(control_joints, control_weights) if aim else ()):
         C = plans[i][3]
@@ -254,8 +272,14 @@ def canvas_control(plans, dim_pose, control_joints=None, control_weights=None, c
             Km = max(tracks[i].shape[1] for i in idx)
             kw.update(canvas_control_tracks=torch.cat([torch.nn.functional.pad(tracks[i], (0, 0, 0, Km - tracks[i].shape[1]))
                                                        for i in idx]).contiguous())
+        if grounds is not None:
+            kw.update(canvas_control_terrain=grounds[0][list(idx)], canvas_control_terrain_rec=grounds[1][list(idx)])
+            if stands is not None:
+                kw.update(canvas_control_stand=torch.cat([stands[i] for i in idx]).contiguous())
         kw.update(canvas_control_mean=ms[0].expand(len(idx), -1), canvas_control_std=ms[1].expand(len(idx), -1))
         kw = {k: v.to(device) for k, v in kw.items()}
+        if grounds is not None and isinstance(terrain_stand, str):
+            kw.update(canvas_control_stand=terrain_stand, canvas_control_stand_threshold=float(terrain_stand_threshold))
         kw.update({k: v for k, v in (("control_scale", control_scale), ("control_iters", control_iters)) if v is not None})
         return kw
 

@@ -23,7 +23,19 @@ They add
     L_tracks,b = sum_{t < len_b} sum_j u_j sum_k a_tk max(0, m_tk + r_j - sigma_tk d(R[t, k]; P[t, j]))^2
 
 to the loss; the records are data (no gradient reaches the obstacle's own motion).  ``scene_loss_grad`` /
-``canvas_scene_loss_grad`` / ``penetration`` take ``tracks=``."""
+``canvas_scene_loss_grad`` / ``penetration`` take ``tracks=``.
+
+A terrain is a height-map ground: a grid of heights (Gz, Gx) in metres with cells of ``cell_x`` by ``cell_z``
+metres, its corner sample at ``origin`` = (x, z), turned by ``yaw`` about Y, interpolated bilinearly and continued flat past
+its edges.  ``heightfield`` makes one from an array of heights, ``ramp`` and ``stairs`` rasterise into one, ``batch_terrain``
+gives the (N, Gz, Gx) grids and (N, 8) records of the kernels, ``terrain_height`` evaluates h in plain torch and
+``terrain_to_local`` moves a terrain from the world into a character's frame.  With e = p_y - h(p) the *vertical* clearance (not
+the true distance to the surface) and stand weights S[t, j] >= 0 it adds
+
+    L_terrain,b = sum_{t < len_b} sum_j u_j a (max(0, m + r_j - e)^2 + S[t, j] max(0, e - r_j - m)^2)
+
+to the loss: every joint stays above the ground, and a joint said to be planted (S > 0) is pulled down onto it.  The grid and S
+are data.  ``scene_loss_grad`` / ``canvas_scene_loss_grad`` take ``terrain=`` and ``stand=``, ``penetration`` takes ``terrain=``."""
 from __future__ import annotations
 
 import math
@@ -35,6 +47,7 @@ from . import _lib as L
 from .motion_control import LDS_BYTES, _rows, joints_for_feats, steerable_columns
 
 MAX_PRIMS, REC, MAX_TRACKS = L.SCENE_MAX_PRIMS, L.SCENE_REC, L.SCENE_MAX_TRACKS
+MAX_GRID, TERRAIN_REC = L.TERRAIN_MAX_GRID, L.TERRAIN_REC
 PAD, SPHERE, CAPSULE, BOX, HALF_SPACE = 0, 1, 2, 3, 4
 
 
@@ -230,14 +243,16 @@ def signed_distances(p: torch.Tensor, records: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def penetration(joints, lengths, scene, joint_radius=None, tracks=None):
+def penetration(joints, lengths, scene, joint_radius=None, tracks=None, terrain=None):
     """How far a result violates a scene, per sample: ``(depth (B,), share (B,))``.  ``joints`` (B, T, J, 3) joint positions
     (``recover_from_ric`` units) with ``lengths`` (B,), ``scene`` as in ``DDPMTrainer.generate`` (one list, or one per
     sample), ``joint_radius`` (J,) or None.  ``depth``: the deepest penetration of any joint's sphere into any primitive
     (out of a keep-in one), max(0, r_j - sigma_k d_k), margins not counted; ``share``: the share of the sample's frames in
     which any joint is inside a margin (m_k + r_j - sigma_k d_k > 0).  Primitives of weight 0 are ignored.  ``tracks``
     (as ``batch_tracks`` takes them; ``scene`` may then be None): the moving primitives of §25 count as well, every frame
-    against its own records.  Plain torch ops on the device the joints are on."""
+    against its own records.  ``terrain`` (as ``batch_terrain`` takes it): the ground of §29 counts as well, with the vertical
+    clearance e = p_y - h(p) in the place of a distance (a terrain of weight 0 is ignored).  Plain torch ops on the device the
+    joints are on."""
     P = torch.as_tensor(joints)
     if P.dim() != 4 or P.shape[-1] != 3:
         raise ValueError(f"joints of shape {tuple(P.shape)} must be (B, T, J, 3)")
@@ -248,6 +263,7 @@ def penetration(joints, lengths, scene, joint_radius=None, tracks=None):
     if ln.numel() != B:
         raise ValueError(f"lengths must hold {B} entries")
     trk = None if tracks is None else batch_tracks(tracks, B, T, ln.cpu())
+    ground = None if terrain is None else batch_terrain(terrain, B)
     depth, share = P.new_zeros(B), P.new_zeros(B)
     for b in range(B):
         n = min(max(int(ln[b]), 0), T)
@@ -266,6 +282,11 @@ def penetration(joints, lengths, scene, joint_radius=None, tracks=None):
             sd = q[..., 1] * track_distances(P[b, :n], trk[b, :n])  # (n, J, Km)
             deep = torch.maximum(deep, torch.where(on, (r[None, :, None] - sd).clamp(min=0), torch.zeros_like(sd)).max())
             inside = inside | (on & ((q[..., 3] + r[None, :, None] - sd) > 0)).any(-1).any(-1)
+        if ground is not None and float(ground[1][b, 6]) > 0:
+            g = ground[1][b].to(P.device, P.dtype)
+            e = P[b, :n, :, 1] - _terrain_height(P[b, :n, :, 0], P[b, :n, :, 2], ground[0][b].to(P.device, P.dtype), g)  # (n, J)
+            deep = torch.maximum(deep, (r[None] - e).clamp(min=0).max())
+            inside = inside | ((g[7] + r[None] - e) > 0).any(-1)
         depth[b], share[b] = deep, inside.to(P.dtype).mean()
     return depth, share
 
@@ -561,6 +582,163 @@ def track_distances(p: torch.Tensor, records: torch.Tensor) -> torch.Tensor:
         kind == BOX, d_box, torch.where(kind == HALF_SPACE, d_half, zero))))
 
 
+# ---- terrain: a height-map ground ----------------------------------------------------------------------
+class Terrain:
+    """A height field: ``heights`` (Gz, Gx) float32 on the CPU and ``record`` (8,) float64 = origin x, origin z, cos yaw,
+    sin yaw, 1 / cell_x, 1 / cell_z, weight, margin.  Made by ``heightfield`` / ``ramp`` / ``stairs``."""
+
+    def __init__(self, heights, record):
+        self.heights, self.record = heights, record
+
+
+def check_terrain(heights, record, name="terrain"):
+    """``heights`` (..., Gz, Gx) and ``record`` (..., 8) as float32 tensors; ValueError for a grid under 2 or over MAX_GRID on
+    either side, non-finite values, a cell <= 0 and a weight < 0."""
+    h, r = torch.as_tensor(heights), torch.as_tensor(record)
+    if h.dim() < 2 or not h.is_floating_point():
+        raise ValueError(f"{name} heights of shape {tuple(h.shape)} must be floating point (..., Gz, Gx)")
+    if not all(2 <= int(g) <= MAX_GRID for g in h.shape[-2:]):
+        raise ValueError(f"{name} grid of {h.shape[-2]} x {h.shape[-1]} samples: 2 to {MAX_GRID} are allowed on either side")
+    if r.shape[-1:] != (TERRAIN_REC,) or r.shape[:-1] != h.shape[:-2] or not r.is_floating_point():
+        raise ValueError(f"{name} record of shape {tuple(r.shape)} must be floating point {tuple(h.shape[:-2]) + (TERRAIN_REC,)}")
+    if not bool(torch.isfinite(h).all()) or not bool(torch.isfinite(r).all()):
+        raise ValueError(f"{name} has non-finite values")
+    if bool((r[..., 4:6] <= 0).any()):
+        raise ValueError(f"{name}: a cell must be > 0")
+    if bool((r[..., 6] < 0).any()):
+        raise ValueError(f"{name}: the weight must be >= 0")
+    return h.detach().to(torch.float32), r.detach().to(torch.float32)
+
+
+def heightfield(heights, cell, origin=(0.0, 0.0), yaw=0.0, *, margin=0.0, weight=1.0) -> Terrain:
+    """A terrain from ``heights`` (Gz, Gx) in metres: sample [k, i] stands at local (i cell_x, k cell_z), local = R_y(-yaw)
+    (p_xz - origin).  ``cell``: a scalar or (cell_x, cell_z), metres > 0.  ``margin`` / ``weight`` as a primitive's.  ValueError
+    for non-finite heights, cell <= 0, weight < 0 and a grid under 2 or over MAX_GRID on either side."""
+    h = torch.as_tensor(heights.detach().cpu() if torch.is_tensor(heights) else np.asarray(heights, dtype=np.float64))
+    if h.dim() != 2:
+        raise ValueError(f"heights of shape {tuple(h.shape)} must be (Gz, Gx)")
+    c = np.asarray(cell, dtype=np.float64).reshape(-1)
+    if c.size not in (1, 2):
+        raise ValueError("cell must be a scalar or (cell_x, cell_z)")
+    cx, cz = (_positive(v, "cell") for v in (c[0], c[-1]))
+    yaw, margin, weight = float(yaw), float(margin), float(weight)
+    if not (math.isfinite(yaw) and math.isfinite(margin)):
+        raise ValueError("yaw and margin must be finite")
+    if not (math.isfinite(weight) and weight >= 0):
+        raise ValueError(f"weight must be finite and >= 0, not {weight}")
+    rec = torch.tensor(_vec(origin, 2, "origin") + [math.cos(yaw), math.sin(yaw), 1.0 / cx, 1.0 / cz, weight, margin],
+                       dtype=torch.float64)
+    hh, _ = check_terrain(h.to(torch.float64), rec)
+    return Terrain(hh.contiguous(), rec)
+
+
+def _corner(start, yaw, width):
+    """The grid's corner for a strip of ``width`` centred on ``start`` = (x, z) that runs along local +X."""
+    x, z = _vec(start, 2, "start")
+    half = 0.5 * _positive(width, "width")
+    c, s = math.cos(float(yaw)), math.sin(float(yaw))
+    return (x - s * half, z - c * half)  # start + R_y(yaw) (0, 0, -width / 2)
+
+
+def ramp(start, yaw, length, rise, width, *, margin=0.0, weight=1.0) -> Terrain:
+    """A ramp of ``width`` metres centred on ``start`` = (x, z): height 0 at ``start`` and before it, rising linearly by ``rise``
+    metres (negative: down) over ``length`` metres along R_y(yaw) (1, 0, 0), flat at ``rise`` behind.  A 2 x 2 grid."""
+    length, rise = _positive(length, "length"), float(rise)
+    if not math.isfinite(rise):
+        raise ValueError("rise must be finite")
+    return heightfield([[0.0, rise], [0.0, rise]], (length, _positive(width, "width")), _corner(start, yaw, width), yaw,
+                       margin=margin, weight=weight)
+
+
+def stairs(start, yaw, steps, rise, run, width, cell=0.05, *, margin=0.0, weight=1.0) -> Terrain:
+    """``steps`` stairs of ``rise`` metres each (negative: down) and treads of ``run`` metres, ``width`` metres wide and centred
+    on ``start`` = (x, z), climbing along R_y(yaw) (1, 0, 0): height 0 at ``start`` and before it, s ``rise`` on tread s, the top
+    tread's height behind.  Rasterised at ``cell`` metres along the climb (``run`` is rounded to whole cells, two at least):
+    every riser spans one cell, the first from ``start`` on."""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("steps must be >= 1")
+    cell, rise = _positive(cell, "cell"), float(rise)
+    if not math.isfinite(rise):
+        raise ValueError("rise must be finite")
+    per = max(2, int(round(_positive(run, "run") / cell)))
+    i = np.arange(steps * per + 1)
+    row = rise * np.minimum(steps, (i + per - 1) // per)
+    return heightfield(np.stack([row, row]), (cell, _positive(width, "width")), _corner(start, yaw, width), yaw, margin=margin,
+                       weight=weight)
+
+
+def batch_terrain(terrain, N: int):
+    """``terrain``, one ``Terrain`` shared by N samples or a list of one per sample, as ``(heights (N, Gz, Gx), records (N, 8))``
+    float32 on the CPU: Gz and Gx the largest of the list, smaller grids padded by repeating their last row and column (which
+    changes no height: past its edge a terrain continues flat)."""
+    items = [terrain] * N if isinstance(terrain, Terrain) else list(terrain)
+    if len(items) != N or not all(isinstance(t, Terrain) for t in items):
+        raise ValueError(f"terrain must be one terrain made by heightfield / ramp / stairs, or a list of one per sample ({N})")
+    if N == 0:
+        return torch.zeros((0, 2, 2)), torch.zeros((0, TERRAIN_REC))
+    gz, gx = max(t.heights.shape[0] for t in items), max(t.heights.shape[1] for t in items)
+    hs = []
+    for t in items:
+        h = t.heights
+        h = torch.cat([h, h[-1:].expand(gz - h.shape[0], -1)], 0)
+        hs.append(torch.cat([h, h[:, -1:].expand(-1, gx - h.shape[1])], 1))
+    return check_terrain(torch.stack(hs), torch.stack([t.record for t in items]))
+
+
+def _terrain_height(p_x, p_z, h, r):
+    """h(p) of points with coordinates ``p_x`` / ``p_z`` (...) over the grid ``h`` (Gz, Gx) with record ``r`` (8,), both in the
+    points' dtype on their device."""
+    gz, gx = h.shape
+    dx, dz = p_x - r[0], p_z - r[1]
+    u = ((r[2] * dx - r[3] * dz) * r[4]).clamp(0, gx - 1)
+    v = ((r[3] * dx + r[2] * dz) * r[5]).clamp(0, gz - 1)
+    i, k = u.floor().long().clamp(max=gx - 2), v.floor().long().clamp(max=gz - 2)
+    fu, fv = u - i, v - k
+    lo = h[k, i] + fu * (h[k, i + 1] - h[k, i])
+    hi = h[k + 1, i] + fu * (h[k + 1, i + 1] - h[k + 1, i])
+    return lo + fv * (hi - lo)
+
+
+def terrain_height(terrain: Terrain, xz) -> torch.Tensor:
+    """h at the points ``xz`` (..., 2) = (x, z): (...) in xz's dtype on its device.  Plain torch ops."""
+    p = torch.as_tensor(xz)
+    if p.shape[-1:] != (2,) or not p.is_floating_point():
+        raise ValueError(f"xz of shape {tuple(p.shape)} must be floating point (..., 2)")
+    return _terrain_height(p[..., 0], p[..., 1], terrain.heights.to(p.device, p.dtype), terrain.record.to(p.device, p.dtype))
+
+
+def terrain_to_local(terrain: Terrain, position, yaw) -> Terrain:
+    """A terrain given in the world, in the frame of a character at ``position`` = (x, z) turned by ``yaw`` (``to_local`` of the
+    ground): the origin moved and the yaw reduced by ``yaw``; the heights are shared, only the record changes."""
+    r = terrain.record.clone()
+    o = to_local(torch.tensor([float(r[0]), 0.0, float(r[1])], dtype=torch.float64), position, yaw)
+    cy, sy = math.cos(float(yaw)), math.sin(float(yaw))
+    c, s = float(r[2]), float(r[3])
+    r[0], r[1], r[2], r[3] = o[0], o[2], c * cy + s * sy, s * cy - c * sy
+    return Terrain(terrain.heights, r)
+
+
+def check_stand(stand, shape, name="stand"):
+    """Stand weights as a float32 tensor of ``shape``; ValueError for another shape, non-finite or negative values."""
+    s = torch.as_tensor(stand)
+    if tuple(s.shape) != tuple(shape):
+        raise ValueError(f"{name} of shape {tuple(s.shape)} must be {tuple(shape)}")
+    s = s.detach().to(torch.float32)
+    if not bool(torch.isfinite(s).all()) or bool((s < 0).any()):
+        raise ValueError(f"{name} must be finite and >= 0")
+    return s
+
+
+def _terrain_args(terrain, stand, N, stand_shape, dev):
+    """The grids, records and stand weights (None without) on the device, and the ctypes arguments between track_bounds and the
+    sizes of the mdm_*_terrain_* calls."""
+    hs, rec = batch_terrain(terrain, N)
+    hs, rec = hs.to(dev).contiguous(), rec.to(dev).contiguous()
+    st = None if stand is None else check_stand(stand, stand_shape).to(dev).contiguous()
+    return (hs, rec, st), (hs.data_ptr(), rec.data_ptr(), hs.shape[2], hs.shape[1], L.ptr(st))
+
+
 def _scene_args(scene, N, J, joint_radius, joint_weights, dev):
     rec = batch_scene(scene, N).to(dev).contiguous()
     jp = joint_params(J, joint_radius, joint_weights)[None].expand(N, -1, -1).to(dev).contiguous()
@@ -576,14 +754,18 @@ def _track_args(tracks, N, T, lengths, bounds, dev):
 
 @torch.no_grad()
 def scene_loss_grad(x0: torch.Tensor, lengths, mean, std, scene, joint_radius=None, joint_weights=None, targets=None,
-                    weights=None, tracks=None, bounds=True):
+                    weights=None, tracks=None, bounds=True, terrain=None, stand=None):
     """Loss (B,) and gradient (B, T, F) of L_scene (module docstring), plus §14's target term when ``targets`` (B, T, J, 3)
     and ``weights`` are given, with respect to the normalised features ``x0`` (B, T, F) on a GPU, through
     ``mdm_joint_scene_loss_grad``.  ``scene``: one list of primitives, or one per sample; ``mean`` / ``std``: (F,) or (B, F).
     The gradient is exactly 0 in every column past 3 J and in every frame at or past ``lengths[b]``.  ``tracks`` (as
     ``batch_tracks`` takes them; ``scene`` may then be None) adds L_tracks through ``mdm_joint_tracks_loss_grad``, behind the
-    broad phase of ``track_bounds`` (``bounds=False``: without it; the result is the same bit for bit)."""
+    broad phase of ``track_bounds`` (``bounds=False``: without it; the result is the same bit for bit).  ``terrain`` (as
+    ``batch_terrain`` takes it; ``scene`` and ``tracks`` may then be None) adds L_terrain through
+    ``mdm_joint_terrain_loss_grad``, with the stand weights ``stand`` (B, T, J) >= 0 (None: all 0)."""
     L.require_cuda(x0)
+    if stand is not None and terrain is None:
+        raise ValueError("stand weights need a terrain")
     dev = x0.device
     x = x0.detach().to(torch.float32).contiguous()
     if x.dim() != 3:
@@ -613,24 +795,31 @@ def scene_loss_grad(x0: torch.Tensor, lengths, mean, std, scene, joint_radius=No
             jp.data_ptr())
     tail = (B, T, F, loss.data_ptr(), grad.data_ptr(), L.stream_ptr())
     with torch.cuda.device(dev):
-        if tracks is None:
+        if tracks is None and terrain is None:
             L.check(L.lib().mdm_joint_scene_loss_grad(*head, *tail), "mdm_joint_scene_loss_grad")
+            return loss, grad
+        trk, bnd = _track_args([] if tracks is None else tracks, B, T, ln.cpu(), bounds, dev)
+        mid = (trk.data_ptr() if trk.shape[2] else 0, trk.shape[2], L.ptr(bnd))
+        if terrain is None:
+            L.check(L.lib().mdm_joint_tracks_loss_grad(*head, *mid, *tail), "mdm_joint_tracks_loss_grad")
         else:
-            trk, bnd = _track_args(tracks, B, T, ln.cpu(), bounds, dev)
-            L.check(L.lib().mdm_joint_tracks_loss_grad(*head, trk.data_ptr() if trk.shape[2] else 0, trk.shape[2], L.ptr(bnd),
-                                                       *tail), "mdm_joint_tracks_loss_grad")
+            keep, ground = _terrain_args(terrain, stand, B, (B, T, J), dev)
+            L.check(L.lib().mdm_joint_terrain_loss_grad(*head, *mid, *ground, *tail), "mdm_joint_terrain_loss_grad")
     return loss, grad
 
 
 @torch.no_grad()
 def canvas_scene_loss_grad(rows: torch.Tensor, motion_offsets, frame_rows, mean, std, scene, joint_radius=None,
-                           joint_weights=None, targets=None, weights=None, tracks=None, bounds=True):
+                           joint_weights=None, targets=None, weights=None, tracks=None, bounds=True, terrain=None, stand=None):
     """``scene_loss_grad`` over the canvases of M long motions, as ``motion_control.canvas_loss_grad``: loss (M,) and gradient
     (total, F) dense in canvas order, through ``mdm_canvas_scene_loss_grad``.  ``scene``: one list of primitives, or one per
     motion, in the canvas frame; ``targets`` (total, J, 3) in canvas order and ``weights``, or neither.  Any canvas length.
     ``tracks``: one list of track stacks per motion, in canvas frames (or packed (total, Km, REC) records in canvas order),
-    through ``mdm_canvas_tracks_loss_grad``; ``bounds`` as in ``scene_loss_grad``."""
+    through ``mdm_canvas_tracks_loss_grad``; ``bounds`` as in ``scene_loss_grad``.  ``terrain``: one terrain, or one per motion,
+    in the canvas frame, with ``stand`` (total, J) in canvas order or None, through ``mdm_canvas_terrain_loss_grad``."""
     L.require_cuda(rows)
+    if stand is not None and terrain is None:
+        raise ValueError("stand weights need a terrain")
     dev = rows.device
     x = rows.detach().to(torch.float32).contiguous()
     F = x.shape[-1]
@@ -663,12 +852,16 @@ def canvas_scene_loss_grad(rows: torch.Tensor, motion_offsets, frame_rows, mean,
             rec.data_ptr() if K else 0, K, jp.data_ptr())
     tail = (M, F, loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), L.stream_ptr())
     with torch.cuda.device(dev):
-        if tracks is None:
+        if tracks is None and terrain is None:
             L.check(L.lib().mdm_canvas_scene_loss_grad(*head, *tail), "mdm_canvas_scene_loss_grad")
+            return loss, grad
+        trk = canvas_tracks([[] for _ in range(M)] if tracks is None else tracks, off)
+        bnd = track_bounds(trk).to(dev).contiguous() if bounds and trk.shape[1] else None
+        trk = trk.to(dev).contiguous()
+        mid = (trk.data_ptr() if trk.shape[1] else 0, trk.shape[1], L.ptr(bnd))
+        if terrain is None:
+            L.check(L.lib().mdm_canvas_tracks_loss_grad(*head, *mid, *tail), "mdm_canvas_tracks_loss_grad")
         else:
-            trk = canvas_tracks(tracks, off)
-            bnd = track_bounds(trk).to(dev).contiguous() if bounds and trk.shape[1] else None
-            trk = trk.to(dev).contiguous()
-            L.check(L.lib().mdm_canvas_tracks_loss_grad(*head, trk.data_ptr() if trk.shape[1] else 0, trk.shape[1], L.ptr(bnd),
-                                                        *tail), "mdm_canvas_tracks_loss_grad")
+            keep, ground = _terrain_args(terrain, stand, M, (total, J), dev)
+            L.check(L.lib().mdm_canvas_terrain_loss_grad(*head, *mid, *ground, *tail), "mdm_canvas_terrain_loss_grad")
     return loss, grad

@@ -387,7 +387,7 @@ class DDPMTrainer(object):
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
                       sample_steps=None, eta=0.0, progress=False, control_joints=None, control_weights=None, control_scale=None,
                       control_iters=None, scene=None, scene_joint_radius=None, scene_joint_weights=None, scene_tracks=None,
-                      **conditioning):
+                      terrain=None, terrain_stand=None, terrain_stand_threshold=0.5, **conditioning):
         """Long motions: ``scripts`` is a list of long motions, each a list of ``(caption, length)``
         segments of at most ``num_frames`` frames; neighbouring segments share ``overlap`` canvas frames, whose eps is
         blended on every step (``blend`` "linear" crossfade or "uniform") while x_T and the step noise come from the left
@@ -411,7 +411,9 @@ class DDPMTrainer(object):
         ``scene_joint_weights`` (J,)): one list of ``motion_scene`` primitives per motion, in its canvas frame, that the joints
         keep out of on every step, through the same canvas-wide guidance and with or without targets.
         ``scene_tracks``: one list of ``motion_scene`` track stacks per motion, moving obstacles over its canvas frames
-        (DESIGN.md §25), under the same.
+        (DESIGN.md §25), under the same.  ``terrain``: one ``motion_scene`` terrain per motion, a height-map ground in its
+        canvas frame, with ``terrain_stand`` None, ``"contacts"`` (over ``terrain_stand_threshold``) or one
+        (canvas_len, J) array of stand weights per motion, under the same.
         The other per-motion inputs are ``**conditioning``, checked by
         ``motion_long.canvas_conditioning``."""
         m = self._model()
@@ -421,7 +423,7 @@ class DDPMTrainer(object):
         window_rows = ML.canvas_conditioning(plans, dim_pose, device=device, **conditioning)
         control = ML.canvas_control(plans, dim_pose, control_joints, control_weights, control_scale, control_iters,
                                     conditioning.get("mean"), conditioning.get("std"), device, scene, scene_joint_radius,
-                                    scene_joint_weights, scene_tracks)
+                                    scene_joint_weights, scene_tracks, terrain, terrain_stand, terrain_stand_threshold)
         out, first = [None] * len(plans), 0
         for idx in ML.plan_batches(plans, batch_size):
             caps = [c for i in idx for c in plans[i][0]]
@@ -449,7 +451,7 @@ class DDPMTrainer(object):
         if longest > most:
             raise ValueError(f"a canvas of {longest} frames: {what} takes at most {most} frames")
         if kw.get("edit_joints") is not None or kw.get("edit_bvh") is not None or kw.get("control_joints") is not None or \
-                kw.get("scene") is not None or kw.get("scene_tracks") is not None:
+                kw.get("scene") is not None or kw.get("scene_tracks") is not None or kw.get("terrain") is not None:
             kw = dict(kw, mean=mean, std=std)
         return self.generate_long(scripts, dim_pose, **kw)
 

@@ -38,6 +38,11 @@ a scene of K primitives (spheres, pillars, boxes and floors in turn, every joint
 
     timeout -k 10 900 python tools/sample_time.py --control 1,5 --scene 4,16 --reps 5 --precisions 1
 
+``--control I --terrain G`` measures a terrain: the controlled generations above without and with a
+G x G height field and ``terrain_stand="contacts"``:
+
+    timeout -k 10 900 python tools/sample_time.py --control 1,5 --terrain 128 --reps 5 --precisions 1
+
 ``--control I --scene K --tracks far,near,near_nobounds`` measures tracks: the controlled generation with
 a scene of K primitives without and with the 21 capsule tracks of a character (``motion_scene.character_tracks``): far from the
 motion (every joint outside the frames' balls), around it, and around it without the broad phase.
@@ -78,6 +83,8 @@ def main():
                     "control alone")
     ap.add_argument("--tracks", default=None, help="far,near,near_nobounds (with --control and --scene): time 21 character tracks "
                     "against control with the scene alone")
+    ap.add_argument("--terrain", type=int, default=None, help="G (with --control): time a G x G terrain with "
+                    'terrain_stand="contacts" against joint control alone')
     ap.add_argument("--long", type=int, default=None, help="H: time long motions (4 windows each, H shared frames) "
                     "against plain generation of the same windows")
     ap.add_argument("--long-control", default=None, help="I[,I...]: time canvas joint control with I iterations against "
@@ -103,6 +110,8 @@ def main():
         return tracks_main(a, tr, m, caps, length, B, T)
     if a.control and a.scene:
         return scene_main(a, tr, m, caps, length, B, T)
+    if a.control and a.terrain:
+        return terrain_main(a, tr, m, caps, length, B, T)
     if a.control:
         return control_main(a, tr, m, caps, length, B, T)
     if a.long_control:
@@ -346,6 +355,58 @@ def scene_main(a, tr, m, caps, length, B, T):
         spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
         print(f"{r['precision']:>9} {r['control_iters']:>5} {r['prims']:>5} {r['sampler']:>22} {r['control_ms']:>11.1f} "
               f"{r['scene_ms']:>9.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
+
+
+def terrain_main(a, tr, m, caps, length, B, T):
+    # the controlled generation of control_main, without and with a terrain of G x G samples: rolling
+    # ground of 0.25 m cells centred on the origin, 0.3 m high, so that joints lie under and over it and walk across its cells;
+    # the stand weights come from every step's own contact labels.  The term is quadratic in a joint's height, as the targets'.
+    MS = importlib.import_module("motiondiffusion-moe_amd.motion_scene")
+    tg, w = torch.zeros(B, T, 22, 3), torch.zeros(B, T, 22, 3)
+    tg[..., 1], w[..., 1] = 1.0, 1.0
+    mean, std = torch.zeros(263), torch.ones(263)
+    G, cell = a.terrain, 0.25
+    i = torch.arange(G, dtype=torch.float64) * cell
+    ground = MS.heightfield(0.3 * torch.sin(i[None] * 0.7) * torch.cos(i[:, None] * 0.5), cell,
+                            (-0.5 * (G - 1) * cell, -0.5 * (G - 1) * cell), 0.3, margin=0.02)
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for iters in [int(k) for k in a.control.split(",")]:
+            for sampler, steps, n in (("ddim", 50, 50), ("dpmpp2m", 20, 20)):
+                def gen(on):
+                    extra = dict(terrain=ground, terrain_stand="contacts", scene_joint_radius=[0.05] * 22) if on else {}
+                    return tr.generate(caps, length, 263, batch_size=B, seed=0, sampler=sampler, sample_steps=steps,
+                                       control_joints=tg, control_weights=w, control_scale=0.05, control_iters=iters,
+                                       mean=mean, std=std, **extra)
+                for on in (False, True):  # warm-up
+                    assert all(torch.isfinite(o).all() for o in gen(on))
+                ts = {False: [], True: []}
+                for _ in range(a.reps):
+                    for on in (False, True):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        gen(on)
+                        torch.cuda.synchronize()
+                        ts[on].append((time.perf_counter() - t0) * 1e3)
+                med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+                diff = sorted(c - p for p, c in zip(ts[False], ts[True]))
+                name = {"ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+                line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, control_iters=iters, grid=G,
+                            control_ms=round(med[False], 2), terrain_ms=round(med[True], 2),
+                            diff_ms_median=round(diff[len(diff) // 2], 2), diff_ms_min=round(diff[0], 2),
+                            diff_ms_max=round(diff[-1], 2), diff_us_per_step=round(diff[len(diff) // 2] / n * 1e3, 1),
+                            control_reps_ms=[round(t, 2) for t in ts[False]], terrain_reps_ms=[round(t, 2) for t in ts[True]])
+                rows.append(line)
+                print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}, guided (cfg 7.5), joint control (every joint's height) without and with a "
+          f"{G} x {G} terrain, terrain_stand=\"contacts\"; {torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'iters':>5} {'sampler':>22} {'control ms':>11} {'terrain ms':>11} {'diff ms (min..max)':>22} {'us/step':>8}")
+    for r in rows:
+        spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
+        print(f"{r['precision']:>9} {r['control_iters']:>5} {r['sampler']:>22} {r['control_ms']:>11.1f} "
+              f"{r['terrain_ms']:>11.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
 
 
 def tracks_main(a, tr, m, caps, length, B, T):
