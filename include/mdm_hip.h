@@ -616,6 +616,29 @@ int mdm_retarget_channels(const float* joints, const float* rotations, const flo
                           int32_t axis0, int32_t axis1, int32_t axis2, int32_t num, int32_t den, int32_t T_out,
                           const int32_t* length_out, float* globals_out, float* channels_out, void* stream);
 
+/* Linear blend skinning (csrc/motion_skin.hip): joints and global rotations move the vertices of a mesh.
+ * joints (B, T, J, 3) and rotations (B, T, J, 3, 3) fp32 in the layout of mdm_motion_fk's outputs, length (B) int32 or NULL
+ * (= T); parent[J], a host array (parent[0] is not read).  Bone 0 is the root: rotation R[0], pivot joint 0.  Bone c >= 1 is
+ * the segment parent(c) -> c: rotation R[c], pivot joint parent(c).  The mesh, on the device: vertices (V, 3), or (B, V, 3)
+ * with vertices_per_sample != 0; normals in the same shape, or NULL; bind_joints G (J, 3), or (B, J, 3) with bind_per_sample
+ * != 0: the joints in the mesh's bind pose; bind_rotations Q (J, 3, 3) row-major or NULL (= identity): the bones' orientation
+ * in the bind pose relative to the rest pose of the rotations; bone_index (V, 4) int32 and bone_weight (V, 4), shared by the
+ * batch, the weights of a vertex summing to 1.  For t < length[b]:
+ *   A_c(x) = P[t, pivot(c)] + R[t, c] Q[c]^T (x - G[pivot(c)])
+ *   vertices_out[b, t, i] = sum_k w[i, k] A_{idx[i, k]}(v[i]), evaluated as v[i] + sum_k w[i, k] (A(v[i]) - v[i]): identity
+ *   rotations with P = G give v[i] bit for bit;
+ *   normals_out[b, t, i] = normalise(sum_k w[i, k] R[t, idx[i, k]] Q[idx[i, k]]^T n[i]), a zero sum staying zero.
+ * vertices_out (B, T, V, 3); normals_out the same or NULL (it needs normals).  A slot of weight 0 contributes nothing and its
+ * index is not used; a live index is clamped into [0, J).  Frames at or past length[b] are zero in both outputs and are never
+ * read.  Every sample equals its own run alone bit for bit.  Any T and V: J <= 32 maps of 16 frames per workgroup in LDS, 64-bit
+ * offsets into the outputs.  MDM_ERR_ARG: a null pointer (length, normals, bind_rotations, normals_out excepted), normals_out
+ * without normals, T, J or V < 1, B < 0, a parent[c >= 1] outside [0, J) or equal to c.  MDM_ERR_UNSUPPORTED: J > 32, B or
+ * T / 16 above 65535. */
+int mdm_skin_vertices(const float* joints, const float* rotations, const int32_t* length, int32_t B, int32_t T, int32_t J,
+                      const int32_t* parent, const float* vertices, const float* normals, int32_t V, int32_t vertices_per_sample,
+                      const float* bind_joints, int32_t bind_per_sample, const float* bind_rotations, const int32_t* bone_index,
+                      const float* bone_weight, float* vertices_out, float* normals_out, void* stream);
+
 /* Motion preview (csrc/motion_render.hip): joints -> image frames.  joints (B, T, J, 3) fp32, length (B) int32 or
  * NULL (= T); of the skeleton the chains are used (group 2 + c draws the links of chain c) and J must be its joint count.
  * The image is defined in DESIGN.md §21: the scene of the reference's plot_3d_motion (floor rectangle from the clip's extent,

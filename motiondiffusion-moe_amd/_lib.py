@@ -199,6 +199,7 @@ PROTOTYPES = {
     "mdm_retarget_table_words": (_I64, []),
     "mdm_retarget_channels": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P,
                                      _P]),
+    "mdm_skin_vertices": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "mdm_motion_render_scratch_floats": (_I64, [_I32, _I32]),
     "mdm_motion_render": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P]),
     "mdm_world_extent": (_I32, [_P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),

@@ -1,6 +1,7 @@
-"""The output chain of generated motions: rows -> joints -> rotations -> BVH, and joints -> frames -> GIF; what the output
-methods of ``DDPMTrainer`` run on the motions ``generate``, ``generate_bucketed`` or ``generate_long`` returned.  ``joints_batch``
-keeps the zero-padded batch the kernels work on: ``to_joints`` slices it per motion, ``to_bvh`` hands it on as it is.
+"""The output chain of generated motions: rows -> joints -> rotations -> BVH or a skinned mesh and its glTF, and joints ->
+frames -> GIF; what the output methods of ``DDPMTrainer`` run on the motions ``generate``, ``generate_bucketed`` or
+``generate_long`` returned.  ``joints_batch`` keeps the zero-padded batch the kernels work on: ``to_joints`` slices it per
+motion, ``to_bvh``, ``to_meshes`` and ``to_glb`` hand it on as it is.
 """
 from __future__ import annotations
 
@@ -8,6 +9,7 @@ import torch
 from torch.nn.utils.rnn import pad_sequence
 
 from .motion_features import pad_clips, skeleton_for_feats
+from .motion_mesh import capsule_body, glb_bytes, skin_vertices
 from .motion_render import gif_bytes, render_motion, render_world, write_gif
 from .motion_rig import DEFAULT_FPS, bvh_text, retarget_to_rig, retime_ratio, rig_of, rotations_to_rig, target_bvh_text
 from .motion_rig import target_rig as make_target_rig
@@ -156,6 +158,50 @@ def to_bvh(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, paths, 
             with open(paths[i], "w") as f:
                 f.write(texts[-1])
     return texts
+
+
+def skinned_batch(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, mesh, pin, pin_blend):
+    """What ``to_meshes`` and ``to_glb`` share: ``joints_batch`` as ``to_bvh`` runs it (forward kinematics, rotations, no
+    filter, ``fix_feet``, pins), so that joints, rotations and pins agree, and the mesh: the caller's, or ``capsule_body`` of
+    the offsets used, one body per motion.  -> (joints, rotations, offsets, lens, skeleton name, mesh)."""
+    j, r, o, lens = joints_batch(motions, lens, dim_pose, mean, std, (dim_pose + 1) // 12, 0.0, True, offsets, True,
+                                 fix_feet=fix_feet, blend=blend, **pin_kw(pin, pin_blend))
+    skel = skeleton_for_feats(dim_pose)
+    if mesh is None:
+        mesh = capsule_body(o, skel)
+    return j, r, o, lens, skel, mesh
+
+
+def to_meshes(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, mesh=None, normals=False, *, pin=None, pin_blend=5):
+    """Rows -> per motion ``(vertices (lens[i], V, 3), faces)``, with ``normals`` ``(vertices, normals, faces)`` (DESIGN.md
+    §30): ``skinned_batch`` and one ``motion_mesh.skin_vertices`` over the padded batch.  ``faces`` (F, 3) is one tensor that
+    every motion shares."""
+    j, r, o, lens, skel, mesh = skinned_batch(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, mesh, pin, pin_blend)
+    out = skin_vertices(mesh, j[:, :max(lens)], r[:, :max(lens)], torch.tensor(lens), return_normals=normals)
+    faces = torch.from_numpy(mesh.faces)
+    if normals:
+        return [(out[0][i, :n], out[1][i, :n], faces) for i, n in enumerate(lens)]
+    return [(out[i, :n], faces) for i, n in enumerate(lens)]
+
+
+def to_glb(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, paths, fps, fps_out, scale, mesh=None, *, pin=None,
+           pin_blend=5):
+    """Rows -> one glTF binary per motion: ``skinned_batch``, one ``motion_rig.rotations_to_rig`` over the
+    padded batch for the retimed root path and local quaternions, ``motion_mesh.glb_bytes`` per sample, written to
+    ``paths[i]`` where given."""
+    j, r, o, lens, skel, mesh = skinned_batch(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, mesh, pin, pin_blend)
+    rig = rig_of(skel)
+    chan, lens_out, quat = rotations_to_rig(j[:, :max(lens)], r[:, :max(lens)], torch.tensor(lens), skeleton=skel, fps=fps,
+                                            fps_out=fps_out, return_quaternions=True)
+    num, den, fps = retime_ratio(skel, fps, fps_out)
+    frame_time = den / (num * float(fps))
+    root, quat, o, out = chan[:, :, :3].cpu(), quat.cpu(), o.cpu(), []
+    for i in range(len(lens)):
+        out.append(glb_bytes(mesh.sample(i), rig, o[i], root[i], quat[i], int(lens_out[i]), frame_time, scale))
+        if paths is not None and paths[i] is not None:
+            with open(paths[i], "wb") as f:
+                f.write(out[-1])
+    return out
 
 
 def to_frames(joints, size, camera, palette, style):

@@ -486,6 +486,58 @@ class DDPMTrainer(object):
                          fps_out, euler, scale, target_rig, target_joint_map, target_up, leg_ik, **MO.pin_kw(pin, pin_blend))
 
     @torch.no_grad()
+    def generate_mesh(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, mesh=None, normals=False, offsets=None,
+                      fix_feet=False, blend=5, pin_targets=False, pin_blend=5, **kw):
+        """``generate`` followed by forward kinematics and linear blend skinning on the device (``motion_mesh``, DESIGN.md
+        §30): per sample ``(vertices (m, V, 3), faces (F, 3))``, with ``normals`` ``(vertices, normals (m, V, 3), faces)``;
+        ``faces`` is one tensor that all samples share.  ``mesh``: a ``motion_mesh.Mesh`` (``from_dense_weights`` for a
+        user's own); None: ``motion_mesh.capsule_body`` of the offsets used, one body per sample.  ``offsets`` / ``fix_feet`` /
+        ``blend`` / ``pin_targets`` / ``pin_blend`` as in ``generate_rotations``: the vertices follow the same joints and
+        rotations; ``**kw`` as for ``generate``."""
+        pin = MO.pin_of(pin_targets, kw)
+        motions = self.generate(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)  # unused without an edit or control
+        return MO.to_meshes(motions, MO.valid_lengths(motions, m_lens), dim_pose, mean, std, offsets, fix_feet, blend, mesh,
+                            normals, **MO.pin_kw(pin, pin_blend))
+
+    @torch.no_grad()
+    def generate_glb(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, paths=None, fps=None, fps_out=None,
+                     scale=1.0, mesh=None, offsets=None, fix_feet=False, blend=5, pin_targets=False, pin_blend=5, **kw):
+        """``generate`` followed by forward kinematics, the rig's local quaternions and ``motion_mesh.glb_bytes`` (DESIGN.md
+        §30): one glTF 2.0 binary (``bytes``) per sample -- the mesh, its skin on the node tree of ``motion_rig.rig_of`` and
+        the animation -- written to ``paths[i]`` where given.  ``fps`` / ``fps_out`` / ``scale`` as in ``generate_bvh``;
+        ``mesh`` and the rest as in ``generate_mesh``."""
+        MO.check_paths(paths, len(caption), "caption")
+        pin = MO.pin_of(pin_targets, kw)
+        motions = self.generate(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)  # unused without an edit or control
+        return MO.to_glb(motions, MO.valid_lengths(motions, m_lens), dim_pose, mean, std, offsets, fix_feet, blend, paths, fps,
+                         fps_out, scale, mesh, **MO.pin_kw(pin, pin_blend))
+
+    @torch.no_grad()
+    def generate_long_mesh(self, scripts, dim_pose, mean, std, *, mesh=None, normals=False, offsets=None, fix_feet=False,
+                           feet_blend=5, pin_targets=False, pin_blend=5, **kw):
+        """``generate_long`` followed by forward kinematics over each whole canvas and the skinning, as ``generate_mesh``: per
+        motion ``(vertices (canvas_len, V, 3)[, normals], faces)`` (at most ``postprocess.fk_max_frames()`` canvas frames).
+        ``feet_blend`` is ``generate_mesh``'s ``blend`` (``blend`` is ``generate_long``'s here); ``pin_targets`` / ``pin_blend`` as
+        in ``generate_long_joints``; ``**kw`` as for ``generate_long``."""
+        pin = MO.pin_of(pin_targets, kw)
+        motions = self._long_motions(scripts, dim_pose, mean, std, MO.canvas_frame_limit(True), "forward kinematics", kw)
+        return MO.to_meshes(motions, MO.valid_lengths(motions), dim_pose, mean, std, offsets, fix_feet, feet_blend, mesh, normals,
+                            **MO.pin_kw(pin, pin_blend))
+
+    @torch.no_grad()
+    def generate_long_glb(self, scripts, dim_pose, mean, std, *, paths=None, fps=None, fps_out=None, scale=1.0, mesh=None,
+                          offsets=None, fix_feet=False, feet_blend=5, pin_targets=False, pin_blend=5, **kw):
+        """``generate_long`` followed by forward kinematics over each whole canvas and the glTF export, as ``generate_glb``:
+        one binary per motion (at most ``postprocess.fk_max_frames()`` canvas frames).  ``feet_blend`` is ``generate_glb``'s
+        ``blend`` (``blend`` is ``generate_long``'s here); ``pin_targets`` / ``pin_blend`` as in ``generate_long_joints``;
+        ``**kw`` as for ``generate_long``."""
+        MO.check_paths(paths, len(scripts), "motion")
+        pin = MO.pin_of(pin_targets, kw)
+        motions = self._long_motions(scripts, dim_pose, mean, std, MO.canvas_frame_limit(True), "forward kinematics", kw)
+        return MO.to_glb(motions, MO.valid_lengths(motions), dim_pose, mean, std, offsets, fix_feet, feet_blend, paths, fps,
+                         fps_out, scale, mesh, **MO.pin_kw(pin, pin_blend))
+
+    @torch.no_grad()
     def generate_frames(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, size=(480, 480), camera=None,
                         palette=False, style=None, view="root", **kw):
         """``generate_joints`` followed by the motion preview (``motion_render.render_motion``) on the device:
