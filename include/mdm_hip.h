@@ -987,6 +987,12 @@ int mdm_route_dump(int32_t* buf, int64_t capacity);
  * off[3] perm (4 M) int32, off[4] rowscale (4 M) fp32, off[5] pos4 (M, 4) int32, off[6] goff (2 E + 1) int32, off[7] cursor
  * (2 E) int32; M = the rows of that block (B * T / 2 at the coarse scale). */
 int mdm_route_workspace(const MdmModel* m, int32_t B, int32_t T, int32_t N, int64_t* off);
+/* Test aid, the sibling of mdm_route_workspace: where the expert stage of that block left its buffers.  Byte offsets:
+ * off[0] hn_scale (2, M) fp32, the per-row scales of e4m3 hn rows (MDM_PREC_FP8 only), off[1] hid (4 M, F), the hidden layer in
+ * slab order (e4m3 bytes at MDM_PREC_FP8; not written where both expert GEMMs run in one launch), off[2] y2 (4 M, D), the
+ * experts' outputs times their gate probabilities in slab order (fp16 at MDM_PREC_FP8 and MDM_PREC_F16, bf16 at MDM_PREC_BF16,
+ * else fp32).  Rows at or past goff[2 E] are never written. */
+int mdm_expert_workspace(const MdmModel* m, int32_t B, int32_t T, int32_t N, int64_t* off);
 /* Number of passes (of <= 128 folded text columns, whole heads) the fused text cross-attention takes for H heads and N text
  * tokens, 0 when the folded path is not taken (D != 512, or more than two passes: N > 64 at H = 4, where the GEMM chain
  * measures faster).  Sizes the optional MdmTextCache buffers:

@@ -249,6 +249,7 @@ PROTOTYPES = {
     "mdm_probe_enable": (_I32, [_I32]),
     "mdm_route_dump": (_I32, [_P, _I64]),
     "mdm_route_workspace": (_I32, [_P, _I32, _I32, _I32, _P]),
+    "mdm_expert_workspace": (_I32, [_P, _I32, _I32, _I32, _P]),
     "mdm_sd_fold_passes": (_I32, [_I32, _I32, _I32]),
     "mdm_probe_read": (_I32, [_P, _P, _I32]),
     "mdm_gru_bidir_workspace_bytes": (_I64, [_I32, _I32]),

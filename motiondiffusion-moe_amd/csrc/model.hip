@@ -1279,6 +1279,15 @@ int mdm_route_workspace(const MdmModel* m, int32_t B, int32_t T, int32_t N, int6
   return MDM_OK;
 }
 
+int mdm_expert_workspace(const MdmModel* m, int32_t B, int32_t T, int32_t N, int64_t* off) {
+  if (check_model(m) != MDM_OK || B <= 0 || T <= 0 || !off) return MDM_ERR_ARG;
+  uint8_t* const base = (uint8_t*)4096;  // (never dereferenced: carve() only adds to it)
+  const Work w = carve(*m, B, T, N, base);
+  const void* p[3] = {w.hn_scale, w.hid, w.y2};
+  for (int i = 0; i < 3; ++i) off[i] = (const uint8_t*)p[i] - base;
+  return MDM_OK;
+}
+
 int mdm_route_dump(int32_t* buf, int64_t capacity) {
   if (buf && capacity <= 0) return MDM_ERR_ARG;
   g_route_dump = buf, g_route_cap = buf ? capacity : 0;

@@ -129,6 +129,32 @@ struct Row {
       store((float*)p + row * D, D, lane);
     }
   }
+  // e4m3 copy of the row (D bytes) and its scale = amax / 448 (1 for an all-zero row), the amax taken over the wave: the scale
+  // rule and the conversion of gate16_row (csrc/moe_gate_row.h), for the widths the LDS-staged router does not take.  Padded
+  // lanes hold 0 and do not move the amax.
+  __device__ __forceinline__ void store_e4m3(uint8_t* __restrict__ p, float* __restrict__ scale_out, int D, int lane) const {
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < NE; ++j) amax = fmaxf(amax, fabsf(e[j]));
+    amax = wave_max(amax);
+    const float scale = amax > 0.f ? amax * (1.f / 448.f) : 1.f, inv = 1.f / scale;
+    if constexpr (VEC) {
+#pragma unroll
+      for (int c = 0; c < NE / 4; ++c) {
+        uint32_t q8 = 0;
+        q8 = __builtin_amdgcn_cvt_pk_fp8_f32(e[4 * c + 0] * inv, e[4 * c + 1] * inv, q8, false);
+        q8 = __builtin_amdgcn_cvt_pk_fp8_f32(e[4 * c + 2] * inv, e[4 * c + 3] * inv, q8, true);
+        *(uint32_t*)(p + 4 * (lane + 64 * c)) = q8;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < NE; ++j) {
+        const int i = lane + 64 * j;
+        if (i < D) p[i] = (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(e[j] * inv, 0.f, 0u, false) & 0xff);
+      }
+    }
+    if (lane == 0) *scale_out = scale;
+  }
   __device__ __forceinline__ float sum() const {
     float s = 0.f;
 #pragma unroll

@@ -130,7 +130,9 @@ __global__ __launch_bounds__(256) void style_in_kernel(const float* __restrict__
 }
 
 // ---- MoE router: both branches' LayerNorm + gate + softmax + top-2 (lowest index wins ties) -----
-template <int NE, bool VEC>
+// F8: the hn rows are e4m3 bytes with per-row scales (p.hn_bf16 == 3); a template argument, so that the other formats' code is
+// the code it was (the generic 16-element form already spills registers)
+template <int NE, bool VEC, bool F8>
 __global__ __launch_bounds__(256) void moe_gate_kernel(const float* __restrict__ x, int64_t M, int D, int E,
                                                        MoeGateParams p) {
   // per-block counters in LDS, flushed with ONE global atomic per (branch, expert) per block: thousands of
@@ -147,7 +149,11 @@ __global__ __launch_bounds__(256) void moe_gate_kernel(const float* __restrict__
     for (int br = 0; br < 2; ++br) {
       Row<NE, VEC> r = xr;
       r.layernorm(p.ln_w[br], p.ln_b[br], D, lane);
-      r.store_as(p.hn, (int64_t)br * M + row, D, lane, p.hn_bf16);
+      if constexpr (F8) {  // e4m3 rows and their scales, as the LDS-staged router writes them (csrc/moe_gate_row.h)
+        r.store_e4m3((uint8_t*)p.hn + ((int64_t)br * M + row) * D, p.hn_scale + (int64_t)br * M + row, D, lane);
+      } else {
+        r.store_as(p.hn, (int64_t)br * M + row, D, lane, p.hn_bf16);
+      }
       float logit[16];
       float mx = -INFINITY;
 #pragma unroll
@@ -855,6 +861,7 @@ int moe_route(const float* x, int64_t M, int D, int E, const MoeGateParams& p, i
               float* rowscale, int* pos4, hipStream_t s) {
   if (M <= 0) return MDM_OK;
   if (E < 2 || E > 16 || !x || !p.hn || !p.hist || !p.uimp || !p.top_idx || !p.top_val) return MDM_ERR_ARG;
+  if (p.hn_bf16 == 3 && !p.hn_scale) return MDM_ERR_ARG;  // e4m3 rows go with their per-row scales
   int nparts = 0;
   // the LDS-staged router exists for D / 64 in {1, 2, 4, 8, 16}; every other width (768, 320, 1000, ...) takes the row kernel
   const int nv = D % 64 == 0 ? D / 64 : 0;
@@ -892,7 +899,14 @@ int moe_route(const float* x, int64_t M, int D, int E, const MoeGateParams& p, i
   } else {
   const int gate_grid = row_grid(M) > 512 ? 512 : row_grid(M);
   nparts = gate_grid;
-#define CALL(NE, VEC) hipLaunchKernelGGL((moe_gate_kernel<NE, VEC>), dim3(gate_grid), dim3(256), 0, s, x, M, D, E, p)
+#define CALL(NE, VEC)                                                                                         \
+  do {                                                                                                        \
+    if (p.hn_bf16 == 3) {                                                                                     \
+      hipLaunchKernelGGL((moe_gate_kernel<NE, VEC, true>), dim3(gate_grid), dim3(256), 0, s, x, M, D, E, p);  \
+    } else {                                                                                                  \
+      hipLaunchKernelGGL((moe_gate_kernel<NE, VEC, false>), dim3(gate_grid), dim3(256), 0, s, x, M, D, E, p); \
+    }                                                                                                         \
+  } while (0)
   MDM_ROW_DISPATCH(D, CALL);
 #undef CALL
   }

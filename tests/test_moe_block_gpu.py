@@ -70,8 +70,9 @@ class Block:
             out, info = MB.moe_block(h.double().cuda(), sc.double().cuda(), self.sd64, self.E, forced)
         return out.cpu(), info
 
-    def run(self, prec, h, sc, length, forced=None, knob=0, dump=False, status=False, pack_prec=None):
-        """One launch chain of the block.  Returns out (CPU) [, dumped decisions (2, M, 2)]; status=True: (status, out) unchecked."""
+    def run(self, prec, h, sc, length, forced=None, knob=0, dump=False, status=False, pack_prec=None, workspace=False):
+        """One launch chain of the block.  Returns out (CPU) [, dumped decisions (2, M, 2)] [, the workspace tensor (GPU) as the block
+        left it: workspace=True]; status=True: (status, out) unchecked."""
         L = pkg("_lib")
         lib = L.lib()
         self.m.precision = pack_prec or prec
@@ -100,7 +101,8 @@ class Block:
         if status:
             return st, out.cpu()
         L.check(st, "mdm_block_forward(MDM_BLOCK_MOE)")
-        return (out.cpu(), buf.reshape(2, M, 2).cpu().long()) if dump else out.cpu()
+        res = (out.cpu(),) + ((buf.reshape(2, M, 2).cpu().long(),) if dump else ()) + ((ws,) if workspace else ())
+        return res if len(res) > 1 else res[0]
 
 
 def block(shape):
@@ -182,7 +184,7 @@ def free_case(shape, prec, B, S, knob=0, calls=1):
     err = float((out.reshape(M, D)[ok].double() - ref.reshape(M, D)[ok]).abs().max() / ref.abs().max()) if bool(ok.any()) else 0.0
     print(f"{tag(shape, prec, B, S, knob)} [free routing]: rel err {err:.2e}; " + "; ".join(line))
     assert torch.isfinite(out).all()
-    if prec in TOL:  # the fp8 mode's arithmetic is gated in tests/test_fp8_gpu.py
+    if prec in TOL:  # the fp8 mode's arithmetic is gated stage by stage in tests/test_fp8_block_gpu.py
         assert err < TOL[prec], (shape, prec, err)
     return out, idx
 

@@ -68,3 +68,128 @@ def test_the_derived_margin_leaves_out_at_most_half_a_percent(D, H, E):
 
 
 MB_SEED = 3
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the fp8 mode's staged reference: e4m3 helpers, and a torch emulation of the chain that must pass it and, with a seeded
+# fault, fail exactly the stage the fault is in
+# ---------------------------------------------------------------------------------------------------------------------
+def test_e4m3_decode_table_is_torchs():
+    b = torch.arange(256, dtype=torch.uint8)
+    got, want = MB.e4m3_decode(b), b.view(torch.float8_e4m3fn).double()
+    nan = torch.isnan(want)
+    assert b[nan].tolist() == [0x7F, 0xFF] and torch.equal(torch.isnan(got), nan)
+    assert torch.equal(got[~nan], want[~nan]) and float(got[~nan].max()) == 448.0 and float(got[~nan].min()) == -448.0
+    assert MB.e4m3_nan_bytes(b) == 2
+
+
+def test_e4m3_half_step_property_of_torchs_quantiser():
+    """|q - v| <= e4m3_step(v) / 2 for torch's nearest-even conversion over +-448, subnormals and zero included, and the bound
+    is nearly attained (so it is no wider than the format's)."""
+    g = torch.Generator().manual_seed(0)
+    v = torch.cat([(torch.rand(100000, generator=g, dtype=torch.float64) * 2 - 1) * 448,
+                   (torch.rand(50000, generator=g, dtype=torch.float64) * 2 - 1) * 2.0 ** -5,  # the subnormal range, |v| < 2^-6, and the binade above
+                   (torch.rand(50000, generator=g, dtype=torch.float64) * 2 - 1),
+                   torch.tensor([0.0, 448.0, -448.0, 2.0 ** -9, 2.0 ** -10, 2.0 ** -6, 1.0, 256.0])]).float().double()
+    q = MB.e4m3_decode(v.float().to(torch.float8_e4m3fn).view(torch.uint8))
+    ratio = (q - v).abs() / MB.e4m3_step(v)
+    print(f"worst |q - v| / step over {v.numel()} values: {float(ratio.max()):.6f}")
+    assert float(ratio.max()) <= 0.5 and float(ratio.max()) > 0.49
+    assert MB.e4m3_step(torch.tensor([0.0, 2.0 ** -9, 0.01, 1.0, 1.9, 300.0, 448.0])).tolist() == [2.0 ** -9, 2.0 ** -9, 2.0 ** -9, 0.125, 0.125, 32.0, 32.0]
+
+
+def _rne8(v):
+    return v.float().to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def _trunc8(v):
+    """e4m3 by truncation toward zero: nearest-even, one code down wherever that rounded away from zero."""
+    q = _rne8(v)
+    return torch.where(MB.e4m3_decode(q).abs() > v.abs().double(), q - 1, q)
+
+
+def _assign(idx, vals, E):
+    """A slab assignment of decisions idx (2, M, 2) with probabilities vals: perm, goff, pos4, rowscale as the router leaves them
+    (tests/test_route_fold_gpu.py check_assignment), entries in (branch, token, k) order inside a slab."""
+    M = idx.shape[1]
+    group = (idx + E * torch.arange(2)[:, None, None]).reshape(-1)
+    order = torch.sort(group, stable=True).indices  # slab row -> entry
+    goff = torch.cat([torch.zeros(1, dtype=torch.int64), torch.bincount(group, minlength=2 * E).cumsum(0)])
+    row_of = (torch.arange(2)[:, None] * M + torch.arange(M)[None, :])[:, :, None].expand(2, M, 2).reshape(-1)
+    pos = torch.empty(4 * M, dtype=torch.int64)
+    pos[order] = torch.arange(4 * M)
+    return row_of[order], goff, pos.reshape(2, M, 2).permute(1, 0, 2).reshape(M, 4), vals.reshape(-1)[order]
+
+
+FP8_SHAPE, FP8_TOKENS = (128, 4, 256, 5), (2, 37)
+FAULTS = {"rows converted by truncation": 1, "hidden layer converted by truncation": 2, "activation scale by slab position": 2,
+          "first GEMM's channel scales of the group before": 2, "second GEMM's channel scales of the group before": 3,
+          "hidden scale 4 with inverse 1/8": 2}
+_FP8_CASE = {}
+
+
+def _fp8_case():
+    if not _FP8_CASE:
+        D, H, Fd, E = FP8_SHAPE
+        sd = MB.block_state(D, H, Fd, E, MB_SEED)
+        sd64 = MB.cast_state(sd, torch.float64)
+        h, sc, _ = MB.block_inputs(*FP8_TOKENS, D, MB_SEED)
+        with torch.no_grad():
+            _, info = MB.moe_block(h.double(), sc.double(), sd64, E)
+        _FP8_CASE.update(sd=sd, sd64=sd64, h=h, sc=sc, idx=torch.stack([i["idx"] for i in info]), e_ln=MB.ln_margin(h, sd, sd64))
+    return _FP8_CASE
+
+
+def _emulate(fault=None):
+    """The fp8 mode's chain in torch: fp32 LayerNorm, amax / 448 scales, torch e4m3 casts, fp32 matmuls, the x 8 hidden scale, an
+    fp16 y2, an fp32 tail; the fp64 reference's decisions.  Returns (dev, wq) as MB.fp8_block_stages takes them."""
+    c = _fp8_case()
+    D, H, Fd, E = FP8_SHAPE
+    sd, h, sc, idx = c["sd"], c["h"], c["sc"], c["idx"]
+    B, S = FP8_TOKENS
+    M = B * S
+    vals = torch.stack([F.softmax(MB.gate_logits(h, sd, br), dim=1).gather(1, idx[br]) for br in range(2)])
+    perm, goff, pos4, rowscale = _assign(idx, vals, E)
+    h32 = torch.stack([MB._ln(h, sd, f"{MB.PRE}.branches.{br}.layernorm").reshape(M, D) for br in range(2)])
+    x8, s = MB.quantize_rows_e4m3(h32)
+    if fault == "rows converted by truncation":
+        x8 = _trunc8(h32 * (1.0 / s)[..., None])
+    stack = lambda leaf: torch.stack([sd[f"{MB.PRE}.branches.{g // E}.moe.experts.{g % E}.{leaf}"] for g in range(2 * E)])
+    (w1q, w1s), (w2q, w2s) = MB.quantize_rows_e4m3(stack("0.weight")), MB.quantize_rows_e4m3(stack("2.weight"))
+    b1, b2 = stack("0.bias"), stack("2.bias")
+    srow = s.reshape(-1)[torch.arange(4 * M) % (2 * M) if fault == "activation scale by slab position" else perm]
+    a8 = MB.e4m3_decode(x8).float().reshape(2 * M, D)[perm]
+    hs = 4.0 if fault == "hidden scale 4 with inverse 1/8" else 8.0
+    hid, y2 = torch.zeros((4 * M, Fd), dtype=torch.uint8), torch.zeros((4 * M, D), dtype=torch.float16)
+    for g in range(2 * E):
+        lo, hi = int(goff[g]), int(goff[g + 1])
+        g1 = (g - 1) % (2 * E) if fault == "first GEMM's channel scales of the group before" else g
+        g2 = (g - 1) % (2 * E) if fault == "second GEMM's channel scales of the group before" else g
+        v = hs * F.gelu((a8[lo:hi] @ MB.e4m3_decode(w1q[g]).float().T) * srow[lo:hi, None] * w1s[g1][None, :] + b1[g])
+        hid[lo:hi] = (_trunc8 if fault == "hidden layer converted by truncation" else _rne8)(v.clamp(-448, 448))
+        y = ((MB.e4m3_decode(hid[lo:hi]).float() @ MB.e4m3_decode(w2q[g]).float().T) * 0.125 * w2s[g2][None, :] + b2[g]) * rowscale[lo:hi, None]
+        y2[lo:hi] = y.half()
+    out = MB.block_tail(h, (0.5 * y2.float()[pos4].sum(1)).view(B, S, D), sc, sd)
+    return dict(x8=x8, s=s, perm=perm, goff=goff, pos4=pos4, rowscale=rowscale, hid=hid, y2=y2, out=out), dict(w1q=w1q, w1s=w1s, w2q=w2q, w2s=w2s)
+
+
+def _stages(fault=None):
+    c = _fp8_case()
+    with torch.no_grad():
+        dev, wq = _emulate(fault)
+        checks, _ = MB.fp8_block_stages(c["h"].double(), c["sc"].double(), c["sd64"], FP8_SHAPE[3], c["e_ln"], dev, wq)
+    for k in checks:
+        print(f"{fault or 'no fault'}: stage {k.stage} {k.what}: {'ok' if k.ok else 'FAILS'} (worst {k.worst:.3g})")
+    return checks
+
+
+def test_fp8_stage_bounds_are_satisfiable_by_a_torch_emulation():
+    checks = _stages()
+    assert sorted({k.stage for k in checks}) == [1, 2, 3, 4] and MB.failed_stages(checks) == []
+    assert 0 < _fp8_case()["e_ln"] < 1e-4
+
+
+@pytest.mark.parametrize("fault", list(FAULTS))
+def test_fp8_stage_checks_fail_the_stage_of_a_seeded_fault(fault):
+    """Every stage is checked on what the stage before it left, so a fault shows in its own stage and in no other."""
+    assert MB.failed_stages(_stages(fault)) == [FAULTS[fault]]
