@@ -970,6 +970,9 @@ enum MdmRouteVariant { MDM_VAR_ROUTE_LAUNCH = 171 };
 enum MdmSkipVariant { MDM_VAR_SKIP_LAUNCH = 172 };
 /* Likewise: no launch touches the weights of the launch behind it (csrc/warm.h); the results are the same either way. */
 enum MdmWarmVariant { MDM_VAR_NO_WARM = 173 };
+/* Likewise: the folded text cross-attention (sd_fold) as its own launch, not in the epilogue of the MoE block's stylization launch
+ * in front of it; the results are the same either way. */
+enum MdmTextVariant { MDM_VAR_TEXT_LAUNCH = 174 };
 int mdm_set_gemm_variant(int variant);
 
 /* Measurement probe for bench.py: while enabled, every launch of the dominant kernel (the fused expert MLP inside

@@ -67,6 +67,7 @@ int mdm_set_gemm_variant(int v) {
     case MDM_VAR_ROUTE_LAUNCH:
     case MDM_VAR_SKIP_LAUNCH:
     case MDM_VAR_NO_WARM:
+    case MDM_VAR_TEXT_LAUNCH:
       mdm::g_variant = v;
       return MDM_OK;
     default:

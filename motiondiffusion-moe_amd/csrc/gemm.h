@@ -141,6 +141,19 @@ struct StyleRoute {
   int E = 0;
   int* cursor = nullptr;  // [2 E]
 };
+// text descriptor of style_gemm: with it the launch also runs the folded text cross-attention and its LayerNorm on its finished
+// rows -- the work of sd_fold (csrc/kernels.h) on the out16 rows, bit for bit -- and leaves o32 / ln16 for the FFN behind it.  The
+// launch then tiles per sample (M = B * S rows) and needs 16-bit source rows; not together with a StyleRoute.
+struct StyleText {
+  const uint16_t* kfold = nullptr;  // the layer's folded text side as sd_fold takes it
+  const float* cb = nullptr;
+  const uint16_t* vfold = nullptr;
+  const float *bout = nullptr, *ln_w = nullptr, *ln_b = nullptr;
+  float* o32 = nullptr;      // [M, D]
+  uint16_t* ln16 = nullptr;  // [M, D]
+  int H = 0, N = 0, hpp = 0, npass = 0;
+};
+bool style_gemm_text_supported(int D, int64_t M, int S, int H, int N);
 bool style_gemm_route_supported(int D, int64_t M, int E, int hn_fmt, int h16);
 int64_t style_gemm_route_parts(int64_t M);
 int style_gemm3(const float* src, int64_t M, int D, int S, const float* pw, const float* pb, const float* sw, const float* sb,
@@ -148,6 +161,7 @@ int style_gemm3(const float* src, int64_t M, int D, int S, const float* pw, cons
                 const float* colscale, float* out, const StyleTail3& t, hipStream_t s);
 int style_gemm(const void* src, int src_fmt, int64_t M, int D, int S, const float* pw, const float* pb, const float* sw, const float* sb,
                const float* sc, const int* pos4, const uint16_t* ws, const float* bias, const float* resid, float out_scale,
-               const float* colscale, float* out, uint16_t* out16, int h16, hipStream_t s, const StyleRoute* route = nullptr);
+               const float* colscale, float* out, uint16_t* out16, int h16, hipStream_t s, const StyleRoute* route = nullptr,
+               const StyleText* text = nullptr);
 
 }  // namespace mdm

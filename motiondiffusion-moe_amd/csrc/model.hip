@@ -248,14 +248,15 @@ StylePath style_path(const Ctx& c, const MdmStyle& st, bool src16, bool out16, b
 // says FUSED3_TAIL (elsewhere the caller runs those LayerNorms itself)
 int style_apply(const Ctx& c, const MdmStyle& st, const float* src, const float* pw, const float* pb, const int* pos4,
                 const float* sc, float* tmp, const float* resid, float out_scale, const float* colscale, float* out,
-                uint16_t* out16 = nullptr, bool src_bf16 = false, const StyleTail3* t3 = nullptr, const StyleRoute* route = nullptr) {
+                uint16_t* out16 = nullptr, bool src_bf16 = false, const StyleTail3* t3 = nullptr, const StyleRoute* route = nullptr,
+                const StyleText* text = nullptr) {
   const int D = c.m->D;
   const StylePath path = style_path(c, st, src_bf16, out16 != nullptr, t3 != nullptr);
-  if (route && path != StylePath::FUSED16) return MDM_ERR_UNSUPPORTED;  // (route_path() asks for it on the one-launch form only)
+  if ((route || text) && path != StylePath::FUSED16) return MDM_ERR_UNSUPPORTED;  // (route_path() / text_path() ask for them on the one-launch form only)
   switch (path) {
     case StylePath::FUSED16:
       return style_gemm(src, src_bf16 ? c.h16 : 0, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws, st.out_b, resid,
-                        out_scale, colscale, out, out16, c.h16, c.s, route);
+                        out_scale, colscale, out, out16, c.h16, c.s, route, text);
     case StylePath::FUSED3:
     case StylePath::FUSED3_TAIL:
       return style_gemm3(src, c.M, D, c.S, pw, pb, st.norm_w, st.norm_b, sc, pos4, st.out_ws3, st.out_b, resid, out_scale, colscale, out,
@@ -620,10 +621,29 @@ MoePath moe_path(const Ctx& c, const MdmMlpDesc& f) {
   return mlp16(c) && fused_mlp_supported(f) ? MoePath::FUSED : MoePath::GROUPED;
 }
 
+// the expert MLP of one layer as one launch of the fused kernel: routed hn rows -> W1_e, GELU, W2_e -> y2
+MdmMlpDesc moe_mlp_desc(const Ctx& c, const MdmLayer& l) {
+  const int D = c.m->D, F = c.m->F, E = c.m->E;
+  const Work& w = c.w;
+  MdmMlpDesc f = {};
+  f.X = (const uint16_t*)w.hn, f.ldx = D, f.gather = w.perm;
+  f.M = (int)(4 * c.M), f.Din = D, f.F = F, f.Dout = D;
+  f.goff = w.goff, f.ngroups = 2 * E;
+  f.w1 = l.w1.hi, f.ldw1 = l.w1.ld, f.w1_gs = (int64_t)F * l.w1.ld, f.b1 = l.b1, f.b1_gs = F;
+  f.w2 = l.w2.hi, f.ldw2 = l.w2.ld, f.w2_gs = (int64_t)D * l.w2.ld, f.b2 = l.b2, f.b2_gs = D;
+  f.rowscale = w.rowscale, f.r1_scale = 1.f;
+  f.C = w.y2, f.ldc = D;
+  f.h16 = c.h16;
+  f.wstream = l.wstream, f.wstream_gs = l.wstream_gs;
+  return f;
+}
+
 // MoEMultiBranchFFN (multi_branch.py:52-61) with SwitchMoELayer top-2 routing (switch_moe.py:44-111)
 // rp == FOLDED: the launch that produced x has run the gate already (cross_block with a StyleRoute)
+// text: the stylization launch also runs the folded text cross-attention behind the block (TextPath::EPILOGUE); out16 is then
+// not written
 int moe_block(const Ctx& c, const MdmLayer& l, const float* x, const float* sc, const int* forced, float* out,
-              uint16_t* out16, int32_t* route_out = nullptr, RoutePath rp = RoutePath::LAUNCH) {
+              uint16_t* out16, int32_t* route_out = nullptr, RoutePath rp = RoutePath::LAUNCH, const StyleText* text = nullptr) {
   const MdmModel& m = *c.m;
   const int D = m.D, F = m.F, E = m.E;
   const Work& w = c.w;
@@ -636,17 +656,10 @@ int moe_block(const Ctx& c, const MdmLayer& l, const float* x, const float* sc, 
   }
   if (route_out && hipMemcpyAsync(route_out, w.top_idx, 4 * c.M * sizeof(int32_t), hipMemcpyDeviceToDevice, c.s) != hipSuccess)
     return MDM_ERR_LAUNCH;
-  MdmMlpDesc f = {};
-  f.X = (const uint16_t*)w.hn, f.ldx = D, f.gather = w.perm;
-  f.M = (int)(4 * c.M), f.Din = D, f.F = F, f.Dout = D;
-  f.goff = w.goff, f.ngroups = 2 * E;
-  f.w1 = l.w1.hi, f.ldw1 = l.w1.ld, f.w1_gs = (int64_t)F * l.w1.ld, f.b1 = l.b1, f.b1_gs = F;
-  f.w2 = l.w2.hi, f.ldw2 = l.w2.ld, f.w2_gs = (int64_t)D * l.w2.ld, f.b2 = l.b2, f.b2_gs = D;
-  f.rowscale = w.rowscale, f.r1_scale = 1.f;
-  f.C = w.y2, f.ldc = D;
-  f.h16 = c.h16;
-  f.wstream = l.wstream, f.wstream_gs = l.wstream_gs;
-  switch (moe_path(c, f)) {
+  MdmMlpDesc f = moe_mlp_desc(c, l);
+  const MoePath mp = moe_path(c, f);
+  if (text && !(mp == MoePath::FUSED && c.bf)) return MDM_ERR_UNSUPPORTED;  // (text_path() asks for it on 16-bit y2 rows only)
+  switch (mp) {
     case MoePath::FP8: {
       // fp8 experts (switch_moe.py:19-25,104-109 on e4m3 operands): hidden = e4m3(8 * GELU(dequant(X8 W1_8^T) + b1)), then
       // y2 = prob * (dequant(hidden8 W2_8^T) / 8 + b2).  Row scales come from the router kernel, channel scales from packing.
@@ -664,7 +677,8 @@ int moe_block(const Ctx& c, const MdmLayer& l, const float* x, const float* sc, 
       MDM_TRY(probe_begin(c.s));
       MDM_TRY(fused_mlp(f, c.s));
       MDM_TRY(probe_end(c.s, f.M));
-      return style_apply(c, l.ffn_style, w.y2, nullptr, nullptr, w.pos4, sc, w.t2, x, 1.f, nullptr, out, out16, c.bf);
+      return style_apply(c, l.ffn_style, w.y2, nullptr, nullptr, w.pos4, sc, w.t2, x, 1.f, nullptr, out, text ? nullptr : out16, c.bf,
+                         nullptr, nullptr, text);
     }
     case MoePath::GROUPED: {  // bracketed for the measurement probe like the fused kernel
       MDM_TRY(probe_begin(c.s));
@@ -710,9 +724,12 @@ struct SdFold {  // folded text side of one layer (MdmTextCache.sd_kfold / sd_cb
 // (MDM_VAR_X3_XATTN_CHAIN: CHAIN).  CORE (16-bit): scores, softmax, PV in one launch (MDM_VAR_GENERIC_DH256 at head_dim 256:
 // CHAIN).  CHAIN: two batched contractions around a row softmax.
 enum class SdPath { FOLD_PAIR, FOLD, CORE3, CORE, CHAIN };
+bool sd_folded(const Ctx& c, const SdFold& fold) {
+  return c.bf && fold.kfold && g_variant != MDM_VAR_SD_UNFOLDED && sd_fold_policy(c.m->D, c.m->H, c.N) > 0;
+}
 SdPath sd_path(const Ctx& c, const MdmLayer& l, const SdFold& fold, const MdmMlpDesc& f) {
   const int D = c.m->D, H = c.m->H, dh = D / H, N = c.N;
-  if (c.bf && fold.kfold && g_variant != MDM_VAR_SD_UNFOLDED && sd_fold_policy(D, H, N) > 0)
+  if (sd_folded(c, fold))
     return l.sd_ffn_ws && c.S >= 128 && fused_mlp_stream_supported(f) ? SdPath::FOLD_PAIR : SdPath::FOLD;
   if (x3_flow(c) && g_variant != MDM_VAR_X3_XATTN_CHAIN && xattn3_supported(dh, N) && l.sd_q.lo && D % 32 == 0 && (c.M * D) % 8 == 0)
     return SdPath::CORE3;
@@ -735,8 +752,32 @@ int sd_ffn(const Ctx& c, const MdmLayer& l, const float* x, float* out, uint16_t
   return linear(c, Act{w.f1, h, x2}, c.M, 4 * D, l.sd_f2, l.sd_f2_b, D, out, out16, o);
 }
 
+// Where the folded text cross-attention runs.  EPILOGUE (inside decoder_layer, 16-bit modes, D = 512, the MoE block on the fused
+// 16-bit path, sd_path() FOLD_PAIR / FOLD with at most two passes): in the epilogue of the MoE block's stylization launch, on the
+// rows that launch has just finished (csrc/style_gemm.hip TX form) -- the sd_fold launch and the 16-bit [M, D] tensor in front of
+// it are gone, t3 / t4 come out bit-identical.  LAUNCH: sd_fold as a launch of its own (MDM_VAR_TEXT_LAUNCH); also for a block
+// that runs alone.  The choice depends on the mode and the shapes of a SAMPLE (S, N), never on the batch.
+enum class TextPath { EPILOGUE, LAUNCH };
+TextPath text_path(const Ctx& c, const MdmLayer& l, const SdFold& fold) {
+  const int D = c.m->D, H = c.m->H;
+  if (g_variant == MDM_VAR_TEXT_LAUNCH || !sd_folded(c, fold) || c.fp8 || sd_fold_passes(H, c.N) > 2) return TextPath::LAUNCH;
+  if (moe_path(c, moe_mlp_desc(c, l)) != MoePath::FUSED || style_path(c, l.ffn_style, true, false, false) != StylePath::FUSED16 ||
+      c.M != (int64_t)c.B * c.S || !style_gemm_text_supported(D, c.M, c.S, H, c.N))
+    return TextPath::LAUNCH;
+  return TextPath::EPILOGUE;
+}
+// the operands of the text epilogue: what sd_fold takes in sdcross_block
+StyleText text_operands(const Ctx& c, const MdmLayer& l, const SdFold& fold) {
+  StyleText t;
+  t.kfold = fold.kfold, t.cb = fold.cb, t.vfold = fold.vfold, t.bout = l.sd_out_b, t.ln_w = l.sd_ln_w, t.ln_b = l.sd_ln_b;
+  t.o32 = c.w.t3, t.ln16 = (uint16_t*)c.w.t4;
+  t.H = c.m->H, t.N = c.N, t.hpp = sd_fold_heads_per_pass(c.m->H, c.N), t.npass = sd_fold_passes(c.m->H, c.N);
+  return t;
+}
+
+// tp == EPILOGUE: the launch that produced x has left o (t3) and LN(o) (t4) already (moe_block with a StyleText)
 int sdcross_block(const Ctx& c, const MdmLayer& l, const float* kc, const float* vc, const float* x, const uint16_t* x16,
-                  float* out, uint16_t* out16, const SdFold& fold = SdFold()) {
+                  float* out, uint16_t* out16, const SdFold& fold = SdFold(), TextPath tp = TextPath::LAUNCH) {
   const MdmModel& m = *c.m;
   const int D = m.D, H = m.H, dh = D / H, N = c.N;
   const Work& w = c.w;
@@ -753,8 +794,9 @@ int sdcross_block(const Ctx& c, const MdmLayer& l, const float* kc, const float*
   switch (path) {
     case SdPath::FOLD_PAIR:
     case SdPath::FOLD:
-      MDM_TRY(sd_fold(x16, fold.kfold, fold.cb, fold.vfold, l.sd_out_b, l.sd_ln_w, l.sd_ln_b, c.B, c.S, D, H, N, w.t3,
-                      (uint16_t*)w.t4, c.h16, c.s));
+      if (tp == TextPath::LAUNCH)
+        MDM_TRY(sd_fold(x16, fold.kfold, fold.cb, fold.vfold, l.sd_out_b, l.sd_ln_w, l.sd_ln_b, c.B, c.S, D, H, N, w.t3,
+                        (uint16_t*)w.t4, c.h16, c.s));
       return path == SdPath::FOLD_PAIR ? fused_mlp_stream(f, c.s) : sd_ffn(c, l, x, out, out16);
     case SdPath::CORE3: {
       uint16_t* const qh = (uint16_t*)w.t1;
@@ -833,9 +875,12 @@ int decoder_layer(const Ctx& c, int layer, const MdmTextCache& tc, float* x, uin
   sr.gate = &gp, sr.E = m.E, sr.cursor = c.w.cursor;
   MDM_TRY(cross_block(c, l, tc_at(m, tc, layer), y, sc4 + 2 * scs, x, true, rp == RoutePath::FOLDED ? &sr : nullptr));
   MDM_TRY(dump(1, x));
-  MDM_TRY(moe_block(c, l, x, sc4 + 3 * scs, forced, y, y16, route_out, rp));
+  const SdFold fold = tc_fold(m, tc, layer);
+  const TextPath tp = text_path(c, l, fold);
+  const StyleText st = text_operands(c, l, fold);
+  MDM_TRY(moe_block(c, l, x, sc4 + 3 * scs, forced, y, y16, route_out, rp, tp == TextPath::EPILOGUE ? &st : nullptr));
   MDM_TRY(dump(2, y));
-  MDM_TRY(sdcross_block(c, l, tc_k(m, tc, layer), tc_v(m, tc, layer), y, y16, x, x16, tc_fold(m, tc, layer)));
+  MDM_TRY(sdcross_block(c, l, tc_k(m, tc, layer), tc_v(m, tc, layer), y, y16, x, x16, fold, tp));
   return dump(3, x);
 }
 

@@ -20,7 +20,15 @@
 //     group runs the router's row body (csrc/moe_gate_row.h, the one moe_gate16_kernel<8, true, RE, FMT> runs) on its row: hn rows,
 //     top-2, and this workgroup's histogram / usage / importance partials at p.hist / p.uimp [blockIdx.x].  Workgroup 0 zeroes the
 //     slab cursors for moe_assign_kernel<true>.  The gate data REPLACES the staging: 64 KiB of LDS at E = 8 (as without the
-//     routing), 72.4 KiB at E = 16 -- two workgroups per CU either way.
+//     routing), 72.4 KiB at E = 16 -- two workgroups per CU either way;
+//   * text epilogue (TX: the MoE block's stylization in front of the folded text cross-attention, when the caller passes a
+//     StyleText): tiles follow the sample (ceil(S / 32) tiles of ceil(S / tiles) rows, as csrc/sdfold.hip tiles it), the finished
+//     rows go back into LDS as the 16-bit rows the store phase writes to out16, and the workgroup runs what sd_fold_kernel runs
+//     on them -- scores against K', softmax per (row, head), P V', + bout, LayerNorm -- with the same MFMAs in the same order,
+//     K' and V' streamed global -> registers (wave-private: wave w owns score columns 16 w .. and output columns 16 w .. of every
+//     128-column slab).  The staging is dead by then: row image 32 KiB | scores 16.5 KiB | P 8 KiB | reductions 2 KiB.
+#include <type_traits>
+
 #include "gemm.h"
 #include "kernels.h"
 #include "moe_gate_row.h"
@@ -37,6 +45,14 @@ __device__ __forceinline__ void sg_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
+}
+
+// the lane's number in its wave, from the lane count and opaque to the compiler: what an epilogue derives from it is computed
+// where it is used instead of living in a register through the phases before, which have none to spare
+__device__ __forceinline__ int sg_lane_again() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
 }
 
 struct StyleGemmArgs {
@@ -71,13 +87,28 @@ struct StyleRouteArgs {  // the routing epilogue's operands (unused where RE == 
   int* cursor;
 };
 
+struct StyleTextArgs {  // the text epilogue's operands (TX forms only): the folded text side as sd_fold_kernel reads it
+  const uint16_t* kfold;  // [B][npass][128][D]
+  const float* cb;        // [B][npass][128]
+  const uint16_t* vfold;  // [B][npass][D][128]
+  const float *bout, *ln_w, *ln_b;
+  float* o32;      // [M, D] attention output + bout
+  uint16_t* ln16;  // [M, D] LayerNorm of it, 16-bit
+  int H, N, hpp, npass;
+  int ntile, rpt;  // tiles per sample, rows per tile
+};
+constexpr int SGT_SC_LD = 132;  // fp32 score row stride (floats), as csrc/sdfold.hip
+constexpr int sg_text_lds_bytes(int rows) { return rows * 1024 + rows * SGT_SC_LD * 4 + rows * 256 + 2 * rows * 8 * 4; }
+
 // LDS of one workgroup: the fp32 staging, or the router's image where that is larger (RE = 16)
 constexpr int sg_lds_bytes(int RT, int RE) {
   return RE > 0 && gate16_lds_bytes(RE, SG_D) > 16 * RT * SG_D * 4 ? gate16_lds_bytes(RE, SG_D) : 16 * RT * SG_D * 4;
 }
 
-template <typename HT, bool SRC16, int SG_RT, int RE = 0>
-__global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel(const StyleGemmArgs g, const StyleRouteArgs rt) {
+template <typename HT, bool SRC16, int SG_RT, int RE = 0, bool TX = false>
+__global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel(
+    const StyleGemmArgs g, const typename std::conditional<TX, StyleTextArgs, StyleRouteArgs>::type rt) {
+  static_assert(!TX || RE == 0, "the text epilogue and the routing epilogue both take the staging");
   constexpr int SG_ROWS = 16 * SG_RT, RPW = SG_ROWS / 8;  // rows per wave in the row phase
   typedef typename HT::frag_t frag_t;
   typedef Row<8, true> R8;
@@ -85,14 +116,26 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
   extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t row0 = (int64_t)blockIdx.x * SG_ROWS;
+  // the tile's rows [row0, mend): flat 32-row tiles, or (TX) tile tl of sample bs -- a tile never crosses a sample
+  int64_t row0 = (int64_t)blockIdx.x * SG_ROWS, mend = g.M;
+  int bs = 0;
+  if constexpr (TX) {
+    // consecutive tiles -- the tiles of a sample, which share its K' and V' -- on one XCD, whose L2 then holds them
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    bs = wg / rt.ntile;
+    const int t0 = (wg - bs * rt.ntile) * rt.rpt;
+    const int nrows = g.S - t0 < rt.rpt ? g.S - t0 : rt.rpt;
+    if (nrows <= 0) return;
+    row0 = (int64_t)bs * g.S + t0, mend = row0 + nrows;
+  }
 
   // the wave's weight stream: 64 fragments of 1 KiB; the ring's first 8 are requested before the row phase
   const uint8_t* wp = (const uint8_t*)g.ws + (int64_t)wn * 64 * 1024 + lane * 16;
   constexpr int NR = SG_RT <= 2 ? 16 : 8;  // ring depth: with 32 accumulator registers there is room for 16 fragments in flight
   frag_t R[NR];  // the first 8 are requested before the row phase, the rest behind it (the row phase needs the registers)
+  constexpr int NPRE = TX ? 6 : 8;  // (the text form keeps more scalars, some of them in a vector register's lanes: 6)
 #pragma unroll
-  for (int f = 0; f < 8; ++f) R[f] = *(const frag_t*)(wp + f * 1024);
+  for (int f = 0; f < NPRE; ++f) R[f] = *(const frag_t*)(wp + f * 1024);
 
   // ---- row phase (csrc/rowwise.hip style_in_rows, one wave per row) ------------------------------------------------------
   {
@@ -103,7 +146,7 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
     for (int q = 0; q < RPW; ++q) {
       const int rl = RPW * wn + q;
       int64_t row = row0 + rl;
-      row = row < g.M ? row : g.M - 1;  // rows past the end: recomputed copies of the last row, never stored
+      row = row < mend ? row : mend - 1;  // rows past the end: recomputed copies of the last row, never stored
       const float* scb = g.sc + (row / g.S) * 2 * (int64_t)D;
       R8 r, scale, shift;
       scale.load(scb, D, lane);
@@ -152,7 +195,7 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
     }
   }
 #pragma unroll
-  for (int f = 8; f < NR; ++f) R[f] = *(const frag_t*)(wp + f * 1024);
+  for (int f = NPRE; f < NR; ++f) R[f] = *(const frag_t*)(wp + f * 1024);
   wp += NR * 1024;
   sg_barrier();
 
@@ -189,6 +232,13 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
   // ---- epilogue: (y + b) * out_scale * colscale staged as fp32 [rows][512], full rows out with the residual -----------------
   sg_barrier();
   float* stg = (float*)smem;
+  int frow_e = frow, fq_e = fq;
+  if constexpr (TX) {  // (the text form has no register to carry them through the GEMM phase)
+    const int l = sg_lane_again();
+    frow_e = l & 15, fq_e = l >> 4;
+  }
+  {
+  const int frow = frow_e, fq = fq_e;
 #pragma unroll
   for (int j = 0; j < SG_NJ; ++j) {
     const int n = wn * 64 + 16 * j + 4 * fq;
@@ -206,25 +256,44 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
       *(f32x4*)(stg + ml * D + (((n >> 2) ^ (ml & 31)) << 2)) = v;
     }
   }
+  }
   // the thread's residual pieces are all requested before its first store: the residual is usually updated in place (out == resid), so
   // the compiler may not move a row's load above the previous row's store, and on gfx950 stores count in vmcnt -- left in the loop
   // every row waited for the row before it to be written (8 serial write round trips per tile)
-  const int cl = tid & 127, n = 4 * cl;
+  const int ts = TX ? wn * 64 + sg_lane_again() : tid;
+  const int cl = ts & 127, n = 4 * cl;
+  // (TX) the wave's 16 fragments of K' rows [16 w, 16 w + 16), then of its V' rows: the GEMM accumulators are dead, the first 8
+  // fragments of K' are requested here
+  [[maybe_unused]] frag_t F[TX ? 16 : 1];
+  [[maybe_unused]] uint2 pk[TX ? SG_ROWS / 4 : 1];  // (TX) the thread's pieces of the finished rows, 16-bit
+  if constexpr (TX) {
+    const uint8_t* kb = (const uint8_t*)(rt.kfold + (int64_t)bs * rt.npass * 128 * D);  // (uniform base + 32-bit lane offset)
+    const int ln = ts & 63;
+    const uint32_t ko = ((16 * wn + (ln & 15)) * D + 8 * (ln >> 4)) * 2;
+#pragma unroll
+    for (int f = 0; f < 8; ++f) F[f] = *(const frag_t*)(kb + ko + 64 * f);
+  }
   f32x4 q[SG_ROWS / 4];
 #pragma unroll
   for (int k = 0; k < SG_ROWS / 4; ++k) {
-    int64_t m = row0 + (tid >> 7) + 4 * k;
-    m = m < g.M ? m : g.M - 1;
+    int64_t m = row0 + (ts >> 7) + 4 * k;
+    m = m < mend ? m : mend - 1;
     q[k] = g.resid ? *(const f32x4*)(g.resid + m * D + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   sg_barrier();
 #pragma unroll
   for (int k = 0; k < SG_ROWS / 4; ++k) {
-    const int ml = (tid >> 7) + 4 * k;
+    const int ml = (ts >> 7) + 4 * k;
     const int64_t m = row0 + ml;
-    if (m >= g.M) continue;
+    if constexpr (!TX) {
+      if (m >= mend) continue;
+    }
     f32x4 v = *(const f32x4*)(stg + ml * D + ((cl ^ (ml & 31)) << 2));
     if (g.resid) v[0] += q[k][0], v[1] += q[k][1], v[2] += q[k][2], v[3] += q[k][3];
+    if constexpr (TX) {  // rows past the end stay copies of the last row for the epilogue; they are not stored
+      pk[k] = make_uint2(HT::pack(v[0], v[1]), HT::pack(v[2], v[3]));
+      if (m >= mend) continue;
+    }
     *(f32x4*)(g.out + m * D + n) = v;
     if (g.out16) *(uint2*)(g.out16 + m * D + n) = make_uint2(HT::pack(v[0], v[1]), HT::pack(v[2], v[3]));
     if constexpr (RE > 0) *(f32x4*)(stg + ml * D + ((cl ^ (ml & 31)) << 2)) = v;  // the finished row, for the router below
@@ -283,6 +352,245 @@ __global__ __launch_bounds__(SG_NT, (SG_RT <= 2 ? 4 : 2)) void style_gemm_kernel
       p.hist[blockIdx.x * 32 + tid] = s_hist[tid];
       p.uimp[blockIdx.x * 64 + tid] = s_usage[tid];
       p.uimp[blockIdx.x * 64 + 32 + tid] = s_imp[tid];
+    }
+  }
+
+  // ---- text epilogue: the folded text cross-attention and its LayerNorm on the finished rows (csrc/sdfold.hip) --------------
+  // sd_fold_kernel's arithmetic element for element -- the same MFMAs with the text fragment first, K ascending in steps of 32,
+  // its softmax grouping and loops, its lane <-> column ownership and reduction order in the LayerNorm -- on 32 rows instead of 64
+  if constexpr (TX) {
+    static_assert(SG_RT == 2 && SG_ROWS * 16 == SG_NT, "32 rows: the softmax has a thread for every (row, head, lane of G)");
+    static_assert(sg_text_lds_bytes(SG_ROWS) <= sg_lds_bytes(SG_RT, 0), "the epilogue's images replace the staging");
+    uint8_t* const pim = smem + SG_ROWS * 1024 + SG_ROWS * SGT_SC_LD * 4;
+    float* const sc = (float*)(smem + SG_ROWS * 1024);
+    float* const red1 = (float*)(pim + SG_ROWS * 256);
+    float* const red2 = red1 + SG_ROWS * 8;
+    // the lane's fragment coordinates again, from the lane count: nothing of this epilogue is then live in the phases before it,
+    // which have no register to spare; operands are addressed as a uniform base + a 32-bit lane offset
+    const int ln = sg_lane_again();
+    const int te0 = wn * 64 + ln, cl = te0 & 127;  // (the thread index, as the store phase has it)
+    // K' fragments 8 .. 15 of the first pass take the registers the store phase has just left
+    {
+      const uint8_t* kb = (const uint8_t*)(rt.kfold + (int64_t)bs * rt.npass * 128 * D);
+      const uint32_t ko = ((16 * wn + (ln & 15)) * D + 8 * (ln >> 4)) * 2;
+#pragma unroll
+      for (int f = 8; f < 16; ++f) F[f] = *(const frag_t*)(kb + ko + 64 * f);
+    }
+    sg_barrier();  // every thread has its pieces of the staging: the row image takes its place (layout of the row phase's image)
+#pragma unroll
+    for (int k = 0; k < SG_ROWS / 4; ++k) {
+      const int ml = (te0 >> 7) + 4 * k;
+      *(uint2*)(smem + ml * 1024 + (((cl >> 1) ^ (ml & 15)) << 4) + (cl & 1) * 8) = pk[k];
+    }
+    f32x4 o[4][SG_RT];
+
+    // One pass of <= 128 folded columns.  The first pass has the registers for all 16 fragments of K' (requested around the store
+    // phase) and then of V' (requested before the softmax): the output accumulators do not exist yet.  A further pass (N > 32 at
+    // four heads) walks both through an 8-fragment ring beside them.
+    auto text_pass = [&](auto first_c, const int pass) {
+      constexpr bool FIRST = decltype(first_c)::value;
+      // the thread index is taken again per pass: otherwise every lane-constant address of the softmax is hoisted out of the pass
+      // loop and lives in (spilled) registers across it; recomputing is a few instructions
+      const int te = wn * 64 + sg_lane_again();
+      const int frow = te & 15, fq = (te >> 4) & 3;
+      const uint32_t ko = ((16 * wn + frow) * D + 8 * fq) * 2;  // K'[16 w + frow][8 fq ..], + 64 bytes per K step
+      const uint32_t vo = ((16 * wn + frow) * 128 + 8 * fq) * 2;  // V'[16 w + frow][8 fq ..], + 32 KiB per slab, + 64 bytes per K step
+      const int xb = frow * 1024 + ((fq ^ frow) << 4);  // as in the GEMM phase: K step s reads chunk (4 s) ^ (fq ^ frow)
+      const int hcnt = (rt.H - pass * rt.hpp) < rt.hpp ? (rt.H - pass * rt.hpp) : rt.hpp;  // heads of this pass
+      const int64_t bp = (int64_t)bs * rt.npass + pass;
+      const uint8_t* kb = (const uint8_t*)(rt.kfold + bp * 128 * D);
+      const int n0 = 16 * wn + 4 * fq;
+      f32x4 cbv;  // (requested ahead of the scores where there is a register for it)
+      if constexpr (FIRST) cbv = *(const f32x4*)((const uint8_t*)(rt.cb + bp * 128) + (uint32_t)(4 * n0));
+      if constexpr (!FIRST) {
+#pragma unroll
+        for (int f = 0; f < 8; ++f) F[f] = *(const frag_t*)(kb + ko + 64 * f);
+      }
+      // zero the probability image (its columns >= hcnt * N stay zero: they multiply the zero padding of V'); the previous
+      // pass's readers are behind the barrier that ends it
+      uint32_t z = 0;
+      asm volatile("" : "+v"(z));  // (a zero made here: hoisted out of the pass loop it is four registers held across it)
+      *(uint4*)(pim + te * 16) = make_uint4(z, z, z, z);
+      sg_barrier();
+
+      // scores[32 x 128] = rows . K'^T + cb; lane: rows 16 i + frow, columns 16 w + 4 fq ..
+      f32x4 acc[SG_RT];
+#pragma unroll
+      for (int i = 0; i < SG_RT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {
+#pragma unroll
+        for (int i = 0; i < SG_RT; ++i) {
+          const frag_t xf = *(const frag_t*)(smem + (xb ^ (64 * (s & 3))) + (s >> 2) * 256 + i * 16384);
+          acc[i] = HT::mfma16(F[FIRST ? s : (s & 7)], xf, acc[i]);
+        }
+        if constexpr (!FIRST) {
+          if (s < 8) F[s] = *(const frag_t*)(kb + ko + 64 * (s + 8));
+        }
+      }
+      if constexpr (!FIRST) cbv = *(const f32x4*)((const uint8_t*)(rt.cb + bp * 128) + (uint32_t)(4 * n0));
+#pragma unroll
+      for (int i = 0; i < SG_RT; ++i) {
+        f32x4 v = acc[i];
+        v[0] += cbv[0], v[1] += cbv[1], v[2] += cbv[2], v[3] += cbv[3];
+        *(f32x4*)(sc + (16 * i + frow) * SGT_SC_LD + n0) = v;
+      }
+      // the wave's 16 fragments of V': rows 128 sidx + 16 w .. (its output columns) x K step ks, fragment 4 ks + sidx -- in flight
+      // across the softmax
+      const uint8_t* vb = (const uint8_t*)(rt.vfold + bp * D * 128);
+#pragma unroll
+      for (int f = 0; f < (FIRST ? 16 : 8); ++f) F[f] = *(const frag_t*)(vb + vo + (f & 3) * 32768 + 64 * (f >> 2));
+      sg_barrier();  // scores complete
+
+      // softmax over each head's N key columns, probabilities as 16-bit rows
+      {
+        // G lanes per (row, head) as sd_fold_kernel has them (8 with one head in the pass, 4 with two, 2 with three or four, 1
+        // beyond): the order of a row's sum follows G, so it is not widened for the 32 rows of this tile.  A thread's scores
+        // (i = sub, sub + G, ..: at most 128 / (hcnt G) of them) are read once, into registers; max, sum and the probabilities
+        // are sd_fold_kernel's, in its order
+        auto softmax = [&](auto g_c) {
+          constexpr int G = decltype(g_c)::value, SMX = G == 1 ? 25 : (G == 2 ? 21 : 16);
+          const int N = rt.N;
+          const int unit = te / G, sub = te - unit * G;
+          const bool on = unit < SG_ROWS * hcnt;
+          const int row = on ? unit / hcnt : 0, h = on ? unit - row * hcnt : 0;
+          const float* p = sc + row * SGT_SC_LD + h * N + sub;
+          float pv[SMX];
+#pragma unroll
+          for (int k = 0; k < SMX; ++k) {  // (unconditional reads: past the row they stay inside the workgroup's LDS, and are dropped)
+            const float t = p[k * G];
+            pv[k] = sub + k * G < N ? t : -INFINITY;
+          }
+          float mx = -INFINITY;
+#pragma unroll
+          for (int k = 0; k < SMX; ++k) mx = fmaxf(mx, pv[k]);
+#pragma unroll
+          for (int o2 = 1; o2 < G; o2 <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o2, 64));
+          float sum = 0.f;
+#pragma unroll
+          for (int k = 0; k < SMX; ++k) {
+            pv[k] = exp_fast(pv[k] - mx);
+            sum += pv[k];  // (past the head's tokens: exp(-inf) = +0, which leaves the sum as it is)
+          }
+#pragma unroll
+          for (int o2 = 1; o2 < G; o2 <<= 1) sum += __shfl_xor(sum, o2, 64);
+          const float inv = 1.f / sum;
+          // (unconditional stores: what has no place in the image goes to the thread's own two bytes of the reduction buffers)
+          // (the bound is taken on the column, in unsigned arithmetic: the 25 lane masks of the reads above would otherwise be kept
+          // for these stores, in scalar registers the kernel does not have)
+          uint8_t* const dump = (uint8_t*)red1 + te * 2;
+          const uint32_t c0 = (uint32_t)(h * N + sub), cend = on ? (uint32_t)(h * N) + (uint32_t)N : 0u;
+#pragma unroll
+          for (int k = 0; k < SMX; ++k) {
+            const uint32_t c = c0 + (uint32_t)(k * G);
+            uint8_t* const dst = pim + row * 256 + ((((c >> 3) ^ (row & 15))) << 4) + (c & 7) * 2;
+            *(uint16_t*)(c < cend ? dst : dump) = (uint16_t)(HT::pack(pv[k] * inv, 0.f) & 0xffff);
+          }
+        };
+        const int gq = 8 / hcnt;
+        if (gq >= 8) softmax(std::integral_constant<int, 8>{});
+        else if (gq >= 4) softmax(std::integral_constant<int, 4>{});
+        else if (gq >= 2) softmax(std::integral_constant<int, 2>{});
+        else softmax(std::integral_constant<int, 1>{});
+      }
+      sg_barrier();
+
+      // out[32 x 512] += P . V'^T; every accumulator takes its K steps in ascending order
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        frag_t pf[SG_RT];
+#pragma unroll
+        for (int i = 0; i < SG_RT; ++i) {
+          const int ra = 16 * i + frow;
+          pf[i] = *(const frag_t*)(pim + ra * 256 + (((ks * 4 + fq) ^ (ra & 15)) << 4));
+        }
+#pragma unroll
+        for (int sidx = 0; sidx < 4; ++sidx) {
+          const int f = 4 * ks + sidx;
+#pragma unroll
+          for (int i = 0; i < SG_RT; ++i)
+            o[sidx][i] = HT::mfma16(F[FIRST ? f : (f & 7)], pf[i], FIRST && ks == 0 ? (f32x4){0.f, 0.f, 0.f, 0.f} : o[sidx][i]);
+          if constexpr (!FIRST) {
+            if (f < 8) F[f] = *(const frag_t*)(vb + vo + sidx * 32768 + 64 * (ks + 2));
+          }
+        }
+      }
+      if (pass + 1 < rt.npass) sg_barrier();  // every wave is done with this pass's scores and probability image
+    };
+    text_pass(std::true_type{}, 0);
+#pragma unroll 1
+    for (int pass = 1; pass < rt.npass; ++pass) text_pass(std::false_type{}, pass);
+
+    // + bout, LayerNorm over the 512 columns (two passes through LDS across the 8 waves)
+    // lane: rows m = 16 i + frow, columns j = 128 s + 16 w + 4 fq + r
+    // (the LayerNorm's weights are requested with bout: they arrive behind the two barriers)
+    const int te = sg_lane_again();
+    const int frow = te & 15, fq = te >> 4;
+    f32x4 bov[4], lwv[4], lbv[4];
+#pragma unroll
+    for (int sidx = 0; sidx < 4; ++sidx) {
+      const uint32_t jo = 4 * (128 * sidx + 16 * wn + 4 * fq);
+      bov[sidx] = *(const f32x4*)((const uint8_t*)rt.bout + jo);
+      lwv[sidx] = *(const f32x4*)((const uint8_t*)rt.ln_w + jo);
+      lbv[sidx] = *(const f32x4*)((const uint8_t*)rt.ln_b + jo);
+    }
+    float ps[SG_RT];
+#pragma unroll
+    for (int i = 0; i < SG_RT; ++i) ps[i] = 0.f;
+#pragma unroll
+    for (int sidx = 0; sidx < 4; ++sidx) {
+      const f32x4 bo = bov[sidx];
+#pragma unroll
+      for (int i = 0; i < SG_RT; ++i) {
+        o[sidx][i][0] += bo[0], o[sidx][i][1] += bo[1], o[sidx][i][2] += bo[2], o[sidx][i][3] += bo[3];
+        ps[i] += (o[sidx][i][0] + o[sidx][i][1]) + (o[sidx][i][2] + o[sidx][i][3]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < SG_RT; ++i) {
+      ps[i] += __shfl_xor(ps[i], 16, 64);
+      ps[i] += __shfl_xor(ps[i], 32, 64);
+      if (fq == 0) red1[(16 * i + frow) * 8 + wn] = ps[i];
+    }
+    sg_barrier();
+    float mean[SG_RT], rstd[SG_RT];
+#pragma unroll
+    for (int i = 0; i < SG_RT; ++i) {
+      const f32x4 a = *(const f32x4*)(red1 + (16 * i + frow) * 8), c = *(const f32x4*)(red1 + (16 * i + frow) * 8 + 4);
+      mean[i] = (((a[0] + a[1]) + (a[2] + a[3])) + ((c[0] + c[1]) + (c[2] + c[3]))) * (1.f / D);
+      float v = 0.f;
+#pragma unroll
+      for (int sidx = 0; sidx < 4; ++sidx)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float d = o[sidx][i][r] - mean[i];
+          v += d * d;
+        }
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      if (fq == 0) red2[(16 * i + frow) * 8 + wn] = v;
+    }
+    sg_barrier();
+#pragma unroll
+    for (int i = 0; i < SG_RT; ++i) {
+      const f32x4 a = *(const f32x4*)(red2 + (16 * i + frow) * 8), c = *(const f32x4*)(red2 + (16 * i + frow) * 8 + 4);
+      rstd[i] = rsqrtf((((a[0] + a[1]) + (a[2] + a[3])) + ((c[0] + c[1]) + (c[2] + c[3]))) * (1.f / D) + 1e-5f);
+    }
+    const int nrows = (int)(mend - row0);
+#pragma unroll
+    for (int sidx = 0; sidx < 4; ++sidx) {
+      const int j = 128 * sidx + 16 * wn + 4 * fq;
+      const f32x4 w = lwv[sidx], bb = lbv[sidx];
+#pragma unroll
+      for (int i = 0; i < SG_RT; ++i) {
+        const int m = 16 * i + frow;
+        if (m >= nrows) continue;
+        const f32x4 v = o[sidx][i];
+        *(f32x4*)((uint8_t*)(rt.o32 + row0 * D) + (uint32_t)(4 * (m * D + j))) = v;
+        const float y0 = (v[0] - mean[i]) * rstd[i] * w[0] + bb[0], y1 = (v[1] - mean[i]) * rstd[i] * w[1] + bb[1];
+        const float y2 = (v[2] - mean[i]) * rstd[i] * w[2] + bb[2], y3 = (v[3] - mean[i]) * rstd[i] * w[3] + bb[3];
+        *(uint2*)((uint8_t*)(rt.ln16 + row0 * D) + (uint32_t)(2 * (m * D + j))) = make_uint2(HT::pack(y0, y1), HT::pack(y2, y3));
+      }
     }
   }
 }
@@ -543,6 +851,28 @@ static int launch_style_gemm(const StyleGemmArgs& g, const StyleRouteArgs& rt, b
   return MDM_OK;
 }
 
+// The text epilogue: 16-bit source rows, 32-row tiles that follow the sample
+static int launch_style_gemm_text(const StyleGemmArgs& g, const StyleTextArgs& tx, int64_t B, int h16, hipStream_t s) {
+  constexpr int smem = sg_lds_bytes(2, 0);
+  static DevOnce attr;
+  if (!attr) {
+    const void* fns[2] = {(const void*)style_gemm_kernel<HB, true, 2, 0, true>, (const void*)style_gemm_kernel<HF, true, 2, 0, true>};
+    for (const void* fn : fns)
+      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return MDM_ERR_LAUNCH;
+    attr = true;
+  }
+  const dim3 grid((unsigned)(B * tx.ntile));
+  if (h16 == MDM_H16_F16) hipLaunchKernelGGL((style_gemm_kernel<HF, true, 2, 0, true>), grid, dim3(SG_NT), smem, s, g, tx);
+  else hipLaunchKernelGGL((style_gemm_kernel<HB, true, 2, 0, true>), grid, dim3(SG_NT), smem, s, g, tx);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+// whole samples of S rows, a text side sd_fold itself would take, a grid that fits
+bool style_gemm_text_supported(int D, int64_t M, int S, int H, int N) {
+  return style_gemm_supported(D, M) && S > 0 && M % S == 0 && sd_fold_supported(D, H, N) && (M / S) * ((S + 31) / 32) < (1ll << 30);
+}
+
 // The routing epilogue exists for E = 8 / 16 with hn rows in the launch's own 16-bit format; its partials are indexed by workgroup,
 // so the grid has to fit the partial buffers ([1024][32] / [1024][64])
 bool style_gemm_route_supported(int D, int64_t M, int E, int hn_fmt, int h16) {
@@ -554,7 +884,7 @@ int64_t style_gemm_route_parts(int64_t M) { return (M + 31) / 32; }
 // src_fmt: 0 = fp32 source rows, else the launch's 16-bit format (must equal h16)
 int style_gemm(const void* src, int src_fmt, int64_t M, int D, int S, const float* pw, const float* pb, const float* sw, const float* sb,
                const float* sc, const int* pos4, const uint16_t* ws, const float* bias, const float* resid, float out_scale,
-               const float* colscale, float* out, uint16_t* out16, int h16, hipStream_t s, const StyleRoute* route) {
+               const float* colscale, float* out, uint16_t* out16, int h16, hipStream_t s, const StyleRoute* route, const StyleText* text) {
   if (M <= 0) return MDM_OK;
   if (!style_gemm_supported(D, M)) return MDM_ERR_UNSUPPORTED;
   if (!src || !sw || !sb || !sc || !ws || !bias || !out || S <= 0 || (pw && !pb)) return MDM_ERR_ARG;
@@ -564,6 +894,20 @@ int style_gemm(const void* src, int src_fmt, int64_t M, int D, int S, const floa
   g.resid = resid, g.out_scale = out_scale, g.colscale = colscale, g.out = out, g.out16 = out16;
   // 64-row tiles (one workgroup per CU, half the weight bytes per row) measured 1 % of a step SLOWER than two co-resident 32-row
   // workgroups per CU at 12544 rows; a row's arithmetic does not depend on the tile height
+  if (text) {
+    const StyleText& t = *text;
+    if (route || src_fmt == 0) return MDM_ERR_UNSUPPORTED;
+    if (!style_gemm_text_supported(D, M, S, t.H, t.N)) return MDM_ERR_UNSUPPORTED;
+    if (!t.kfold || !t.cb || !t.vfold || !t.bout || !t.ln_w || !t.ln_b || !t.o32 || !t.ln16 || ((uintptr_t)t.kfold & 15) ||
+        ((uintptr_t)t.vfold & 15) || ((uintptr_t)t.cb & 15) || ((uintptr_t)t.bout & 15) || ((uintptr_t)t.ln_w & 15) || ((uintptr_t)t.ln_b & 15))
+      return MDM_ERR_ARG;
+    if (t.hpp != sd_fold_heads_per_pass(t.H, t.N) || t.npass != sd_fold_passes(t.H, t.N)) return MDM_ERR_ARG;
+    StyleTextArgs tx = {};
+    tx.kfold = t.kfold, tx.cb = t.cb, tx.vfold = t.vfold, tx.bout = t.bout, tx.ln_w = t.ln_w, tx.ln_b = t.ln_b, tx.o32 = t.o32, tx.ln16 = t.ln16;
+    tx.H = t.H, tx.N = t.N, tx.hpp = t.hpp, tx.npass = t.npass;
+    tx.ntile = (S + 31) / 32, tx.rpt = (S + tx.ntile - 1) / tx.ntile;
+    return launch_style_gemm_text(g, tx, M / S, h16, s);
+  }
   StyleRouteArgs rt = {};
   if (route) {
     if (!route->gate || !route->cursor) return MDM_ERR_ARG;
