@@ -872,6 +872,41 @@ int mdm_canvas_terrain_guidance(float* x, float* x0, const float* mask, const in
 int mdm_terrain_stand_weights(const float* x0, const int32_t* frame_rows, int32_t n_frames, const float* mean, const float* std,
                               int32_t F, int32_t stat_group, const int32_t* feet, float threshold, float* out, void* stream);
 
+/* Characters sampled together (csrc/motion_partners.hip): from a step's x0 (B, T, F), the tracks and targets of
+ * the tracks / terrain guidance calls above, so that every row avoids and reaches for its partners' current estimate.  Row b
+ * has length[b], mean / std rows (B, F) and a placement placements[b] = (x, z, cos yaw, sin yaw) (fp32 (B, 4), 16-byte
+ * aligned).  With P_b = recover_from_ric(x0[b] * std + mean) unfiltered (mdm_motion_postprocess at radius 0 on x0 * std + mean
+ * as two fp32 roundings, bit for bit: the launch of that call is reused; `scratch`, the caller's, holds
+ * mdm_partner_tracks_scratch_floats(B, T, F) floats, 0 for a bad size):
+ *   world (B, T, J, 3), the caller's scratch: W_b[t, j] = R_y(yaw_b) P_b[t, j] + (x_b, 0, z_b) in fp32, zero at t >= length[b];
+ *   L_b(w) = R_y(-yaw_b) (w - (x_b, 0, z_b)).
+ * partner_rows int32 (B, Pm): the rows that row b avoids, or -1 for an empty slot.  bones int32 (nb, 2) in host memory, read
+ * before the call returns.  Behind the Ks static records of `tracks` (B, T, Km, MDM_SCENE_REC), Km = Ks + Pm nb, which are
+ * only read, record Ks + q nb + i of frame t is written: for p = partner_rows[b, q] >= 0 and t < min(length[b], length[p]) a
+ * keep-out MDM_SCENE_CAPSULE with ends L_b(W_p[t, bones[i, 0]]), L_b(W_p[t, bones[i, 1]]) and the call's radius, margin and
+ * weight, else twelve zero floats.  track_bounds (B, T, 4): per frame the ball of the tracks calls' broad phase over all Km
+ * records of the frame, in fp32 and inflated by 1e-3 of its radius plus 1e-3 m (+inf with a live half-space or keep-in
+ * record, -inf without a live record).  Both are written 16 bytes at a time.
+ * contacts: Nc entries of eight 32-bit words: row a, joint a, row b, joint b, first, last (int32), meet (fp32), 0.  For
+ * first <= t < min(last, length[a], length[b]), m = W_a[t, joint a] + meet (W_b[t, joint b] - W_a[t, joint a]) and
+ * targets[a, t, joint a] = L_a(m), targets[b, t, joint b] = L_b(m), targets (B, T, J, 3); nothing else of targets is written.
+ * partner_rows and contacts are on the device; partner_rows_host and contacts_host are the same tables in host memory, which
+ * are what is checked here, before any launch (keeping the two equal is the caller's).  Every record is built from the x0 the
+ * call is given: the result depends on no order among the rows.  Up to five launches, stream-ordered, allocation free, no
+ * atomics, graph-capturable.  MDM_ERR_ARG: a null required pointer (tracks / track_bounds with Km == 0, the partner tables
+ * with Pm nb == 0 and contacts / targets with Nc == 0 excepted), Km outside [0, MDM_SCENE_MAX_TRACKS], Ks + Pm nb != Km, F + 1
+ * no multiple of 12, a bone or a contact joint outside [0, J), a partner row outside [-1, B) or equal to its own row, a contact
+ * row outside [0, B), placements, tracks or track_bounds not 16-byte aligned, first > last, meet outside [0, 1] or not finite,
+ * radius <= 0, weight < 0, a non-finite radius, margin or weight.  MDM_ERR_UNSUPPORTED: T > mdm_partner_tracks_max_frames()
+ * (20 bytes of LDS per frame).  B == 0 or T == 0 is a no-op. */
+int mdm_partner_tracks_max_frames(void);
+int64_t mdm_partner_tracks_scratch_floats(int32_t B, int32_t T, int32_t F);
+int mdm_partner_tracks(const float* x0, const int32_t* length, const float* mean, const float* std, const float* placements,
+                       const int32_t* partner_rows, const int32_t* partner_rows_host, int32_t Pm, const int32_t* bones,
+                       int32_t nb, float radius, float margin, float weight, int32_t Ks, int32_t Km, const int32_t* contacts,
+                       const int32_t* contacts_host, int32_t Nc, int32_t B, int32_t T, int32_t F, float* world, float* scratch,
+                       float* tracks, float* track_bounds, float* targets, void* stream);
+
 /* ---- long-motion handshakes ---------------------------------------------------------------------
  * In place over the shared canvas frames only.  For every group g < groups, shared frame c < nshared and feature j < F:
  *   v = sum over entries e in [offsets[c], offsets[c+1]) of weights[e] * x[g*group_stride + rows[e]*F + j]

@@ -139,15 +139,35 @@ def check_control_kwargs(kw, shape):
     ``control_stand_threshold``, default 0.5, on the feet of the skeleton of width F), as ``stand`` (a tensor, or the feet and
     the threshold as ``stand_feet`` / ``stand_threshold``).  Raises ValueError for a record or stand weights without a grid, a
     grid without a record, what ``motion_scene.check_terrain`` / ``check_stand`` refuse, another batch size, ``"contacts"`` at
-    a feature width without a skeleton and a non-finite threshold.  Host logic."""
+    a feature width without a skeleton and a non-finite threshold.
+    Characters sampled together: ``control_partner_scenes`` (one list of batch rows per scene) with
+    ``control_partner_placements`` (B, 3) = x, z, yaw and optionally ``control_partner_bones`` / ``control_partner_radius`` /
+    ``control_partner_margin`` / ``control_partner_weight`` and ``control_contact_list`` (``motion_scene.contact`` entries
+    between batch rows; a ``control_partner_weight`` of 0 leaves the partner slots out), with or without ``control_tracks`` (the static tracks in front of the partner slots), a scene, targets
+    and a terrain, come back as ``partners``, the ``motion_scene.PartnerTables`` (made with ``model_kwargs["length"]``); the
+    returned ``weights`` are then the tables' (the static weights plus the contacts') and ``targets`` zeros where none are
+    given.  Raises ValueError for the other partner / contact keys without the scenes and placements and for everything
+    ``motion_scene.partner_tables`` refuses.  Host logic."""
     from .motion_control import joints_for_feats, max_frames
     names = ("control_joints", "control_weights", "control_mean", "control_std")
+    partner = {k: kw.get(k) for k in PARTNER_KEYS}
+    if any(v is not None for v in partner.values()):
+        if partner["control_partner_scenes"] is None or partner["control_partner_placements"] is None:
+            raise ValueError("characters sampled together need control_partner_scenes and control_partner_placements")
+        if kw.get("length") is None:
+            raise ValueError("characters sampled together need model_kwargs['length']")
+        long = [k for k, v in kw.items() if v is not None and (k.startswith("handshake_") or k.startswith("canvas_control_"))]
+        if long:
+            raise ValueError(f"characters sampled together (control_partner_* / control_contact_*) cannot be combined with "
+                             f"{', '.join(sorted(long))}: long motions are out of their scope")
+    else:
+        partner = None
     g, w, mean, std = (kw.get(k) for k in names)
     scene, jp, tracks = kw.get("control_scene"), kw.get("control_joint_params"), kw.get("control_tracks")
     terrain, trec, stand = kw.get("control_terrain"), kw.get("control_terrain_rec"), kw.get("control_stand")
     if terrain is None and any(kw.get(k) is not None for k in ("control_terrain_rec", "control_stand", "control_stand_threshold")):
         raise ValueError("control_terrain_rec / control_stand / control_stand_threshold given without control_terrain")
-    if (tracks is not None or terrain is not None) and scene is None:
+    if (tracks is not None or terrain is not None or partner is not None) and scene is None:
         scene = torch.zeros((int(shape[0]), 0, L.SCENE_REC))
     given = [k for k, v in zip(names, (g, w, mean, std)) if v is not None]
     extra = [k for k in ("control_scale", "control_iters") if kw.get(k) is not None]
@@ -222,7 +242,21 @@ def check_control_kwargs(kw, shape):
     iters = 1 if iters is None else iters
     if isinstance(iters, bool) or int(iters) != iters or not 1 <= int(iters) <= L.CONTROL_MAX_ITERS:
         raise ValueError(f"control_iters must be an integer in [1, {L.CONTROL_MAX_ITERS}]")
+    if partner is not None:
+        from .motion_scene import partner_tables
+        opts = {k: partner["control_partner_" + k] for k in ("radius", "margin", "weight") if partner["control_partner_" + k] is not None}
+        tables = partner_tables(partner["control_partner_scenes"], partner["control_partner_placements"], kw["length"],
+                                partner["control_partner_bones"], T=T, J=J, contacts=partner["control_contact_list"] or (),
+                                static_tracks=0 if tracks is None else int(tracks.shape[2]), control_weights=w,
+                                avoid=float(opts.get("weight", 1.0)) > 0, **opts)
+        out["partners"] = tables
+        if len(tables.contacts) or g is not None:
+            g, w = torch.zeros((B, T, J, 3)) if g is None else g, tables.weights
     return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters), **out}
+
+
+PARTNER_KEYS = ("control_partner_scenes", "control_partner_placements", "control_partner_bones", "control_partner_radius",
+                "control_partner_margin", "control_partner_weight", "control_contact_list")
 
 
 def _terrain_inputs(terrain, trec, stand, threshold, N, stand_shape, F_, prefix):

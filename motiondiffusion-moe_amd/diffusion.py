@@ -725,6 +725,21 @@ class _StepRunner:
                 Km = int(ctl["tracks"].shape[2])
                 self.ctl.update(Km=Km, tracks=f32(ctl["tracks"], (B, T, Km, L.SCENE_REC)),
                                 track_bounds=f32(ctl["track_bounds"], (B, T, 4)))
+            if "partners" in ctl and (ctl["partners"].Km or len(ctl["partners"].contacts)):
+                # characters sampled together: the partner slots behind the static tracks, the balls and the
+                # contact targets are rewritten on every step from that step's x0, in front of the guidance
+                from .motion_scene import partner_scratch_floats
+                pt = ctl["partners"]
+                if pt.Km:
+                    trk = torch.zeros((B, T, pt.Km, L.SCENE_REC), dtype=torch.float32, device=dev)
+                    if pt.Ks:
+                        trk[:, :, :pt.Ks].copy_(ctl["tracks"])
+                    self.ctl.update(Km=pt.Km, tracks=trk, track_bounds=torch.empty((B, T, 4), dtype=torch.float32, device=dev))
+                self.ctl["partners"] = dict(tables=pt, dev=tuple(v.to(dev).contiguous() for v in (pt.placements, pt.partner_rows,
+                                                                                                  pt.contacts)),
+                                            world=torch.empty((B, T, J, 3), dtype=torch.float32, device=dev),
+                                            scratch=torch.empty(max(partner_scratch_floats(B, T, Fe), 1), dtype=torch.float32,
+                                                                device=dev))
             if "terrain" in ctl:  # terrain: the height grids, their records and the stand weights
                 Gz, Gx = (int(v) for v in ctl["terrain"].shape[1:])
                 self.ctl.update(Gx=Gx, Gz=Gz, terrain=f32(ctl["terrain"], (B, Gz, Gx)), stand=None,
@@ -934,6 +949,11 @@ class _StepRunner:
                 L.check(lib.mdm_terrain_stand_weights(self.x0.data_ptr(), c["rows"][lo:].data_ptr(), hi - lo, c["mean"][m].data_ptr(),
                                                       c["std"][m].data_ptr(), self.Fe, 0, c["stand_feet"], c["stand_threshold"],
                                                       c["stand"][lo:].data_ptr(), s), "mdm_terrain_stand_weights")
+        if self.ctl is not None and "partners" in self.ctl:  # every row's partner tracks and contact targets from this step's x0
+            from .motion_scene import partner_launch
+            c, q = self.ctl, self.ctl["partners"]
+            partner_launch(self.x0, c["len"], c["mean"], c["std"], q["tables"], q["dev"], q["world"], q["scratch"], c.get("tracks"),
+                           c.get("track_bounds"), c["targets"])
         if self._guide is not None:  # x0 and x_{t-1} moved down the joint-position loss, before the counter moves
             L.check(getattr(lib, self._guide[0])(*self._guide[1], s), self._guide[0])
         if self._guide_canvas is not None:  # once per long motion over its canvas, then the owner's bits into every overlap

@@ -28,6 +28,8 @@ def shard_kwargs(kw: Dict, lo: int, hi: int) -> Dict:
         if k.startswith("canvas_control_") and v is not None:
             raise ValueError(f"{k} describes whole long motions, not batch rows: canvas joint control cannot be sharded over "
                              "ranks")
+        if (k.startswith("control_partner_") or k.startswith("control_contact_")) and v is not None:
+            raise ValueError(f"{k} names batch rows of characters sampled together: a mutual batch cannot be sharded over ranks")
         if isinstance(v, torch.Tensor) and v.dim() >= 1:
             out[k] = v[lo:hi]
         elif isinstance(v, (list, tuple)):

@@ -35,7 +35,13 @@ the true distance to the surface) and stand weights S[t, j] >= 0 it adds
     L_terrain,b = sum_{t < len_b} sum_j u_j a (max(0, m + r_j - e)^2 + S[t, j] max(0, e - r_j - m)^2)
 
 to the loss: every joint stays above the ground, and a joint said to be planted (S > 0) is pulled down onto it.  The grid and S
-are data.  ``scene_loss_grad`` / ``canvas_scene_loss_grad`` take ``terrain=`` and ``stand=``, ``penetration`` takes ``terrain=``."""
+are data.  ``scene_loss_grad`` / ``canvas_scene_loss_grad`` take ``terrain=`` and ``stand=``, ``penetration`` takes ``terrain=``.
+
+Characters sampled together: the characters of a scene are rows of one batch, and on every step the tracks a
+row avoids are the capsules of its partners' current estimate and the targets it reaches for the meeting points of its
+contacts.  ``contact`` makes a contact, ``partner_tables`` the host tables (partner rows, bones, placements, the contact table
+and the constant target weights) and ``partner_tracks`` runs the device call (``mdm_partner_tracks``) on its own:
+``(tracks, track_bounds, targets)`` as the tracks guidance takes them."""
 from __future__ import annotations
 
 import math
@@ -865,3 +871,206 @@ def canvas_scene_loss_grad(rows: torch.Tensor, motion_offsets, frame_rows, mean,
             keep, ground = _terrain_args(terrain, stand, M, (total, J), dev)
             L.check(L.lib().mdm_canvas_terrain_loss_grad(*head, *mid, *ground, *tail), "mdm_canvas_terrain_loss_grad")
     return loss, grad
+
+
+# ---- characters sampled together: every row avoids and reaches for its partners' current estimate ----------
+class Contact(tuple):
+    """One contact: (a, joint_a, b, joint_b, first, last, weight, meet), frames [first, last).  Made by ``contact``."""
+
+
+def contact(a, joint_a, b, joint_b, frames, weight=1.0, meet=0.5) -> Contact:
+    """Joint ``joint_a`` of character ``a`` and joint ``joint_b`` of character ``b`` meet in ``frames`` (a ``range`` of step 1 or
+    consecutive frame numbers) at m = W_a + meet (W_b - W_a): ``meet`` 0 lets b do all the reaching, 0.5 is halfway, 1 lets a.
+    ``weight`` >= 0 is the target weight of both.  ``a`` / ``b`` are character indices of a scene in
+    ``DDPMTrainer.generate_together`` and batch rows in ``partner_tables``.  ValueError for a == b, negative indices, frames
+    that are not consecutive or run backwards (``first > last``), a weight < 0 and a ``meet`` outside [0, 1] or non-finite."""
+    a, joint_a, b, joint_b = (int(v) for v in (a, joint_a, b, joint_b))
+    if min(a, joint_a, b, joint_b) < 0:
+        raise ValueError("a contact's characters and joints must be >= 0")
+    if a == b:
+        raise ValueError("a contact joins two different characters")
+    if isinstance(frames, range):
+        if frames.step != 1:
+            raise ValueError("a contact's frames must be consecutive (a range of step 1)")
+        first, last = frames.start, frames.stop
+    else:
+        fr = [int(f) for f in frames]
+        if any(y != x + 1 for x, y in zip(fr, fr[1:])):
+            raise ValueError("a contact's frames must be consecutive")
+        first, last = (fr[0], fr[-1] + 1) if fr else (0, 0)
+    if first > last or first < 0:
+        raise ValueError(f"a contact's frames must run forward from a frame >= 0 (first > last: {first} > {last})")
+    weight, meet = float(weight), float(meet)
+    if not (math.isfinite(weight) and weight >= 0):
+        raise ValueError(f"weight must be finite and >= 0, not {weight}")
+    if not (math.isfinite(meet) and 0.0 <= meet <= 1.0):
+        raise ValueError(f"meet must lie in [0, 1], not {meet}")
+    return Contact((a, joint_a, b, joint_b, int(first), int(last), weight, meet))
+
+
+def skeleton_bones(J: int):
+    """The (parent, child) pairs of the skeleton with J joints in ``motion_features.SKELETONS``: ``character_tracks``' default."""
+    from .motion_features import SKELETONS
+    trees = {sk.joints: sk.parents for sk in SKELETONS.values()}
+    if J not in trees:
+        raise ValueError(f"no skeleton with {J} joints: give bones= as (parent, child) pairs")
+    return [(p, c) for c, p in enumerate(trees[J]) if p >= 0]
+
+
+class PartnerTables:
+    """The host half of ``mdm_partner_tracks``, made by ``partner_tables``: ``partner_rows`` (B, Pm) int32, ``bones`` (nb, 2)
+    int32, ``placements`` (B, 4) float32 = x, z, cos yaw, sin yaw, ``contacts`` (Nc, 8) int32 words (row a, joint a, row b,
+    joint b, first, last, the bits of meet as fp32, 0), ``weights`` (B, T, J, 3) float32, constant over a run (the static control
+    weights plus every contact's), ``lengths`` (B,) int32, and the scalars ``radius``, ``margin``, ``weight``, ``Ks``, ``Km``,
+    ``Pm``, ``nb``, ``B``, ``T``, ``J``; ``pose`` (B, 3) float64 keeps the x, z, yaw the placements were made from.  All on the CPU."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def partner_tables(scenes_rows, placements, lengths, bones=None, *, T, J, contacts=(), radius=0.08, margin=0.05, weight=5.0,
+                   static_tracks=0, control_weights=None, avoid=True) -> PartnerTables:
+    """The tables of characters sampled together.  ``scenes_rows``: one list of batch rows per scene (every row of a scene is
+    a partner of every other; a row in no scene, or alone in one, has none); ``placements`` (B, 3) = x, z, yaw per row;
+    ``lengths`` (B,); ``bones``: (parent, child) pairs, by default the skeleton's (``skeleton_bones(J)``); ``contacts``:
+    ``contact(...)`` entries whose ``a`` / ``b`` are batch rows of one scene; ``radius`` / ``margin`` / ``weight``: of every partner
+    capsule; ``static_tracks`` = Ks, the number of user tracks in front of the partner slots; ``control_weights`` (B, T, J, 3) or
+    None: the static target weights the contacts must not land on; ``avoid=False``: no partner slots at all (Pm = 0), the
+    scenes then only say which rows a contact may join.  Slot q of row b holds the q-th other row of its scene in
+    the scene's order, -1 behind; bone i of slot q is track Ks + q nb + i.  A contact's weight is written on all three axes
+    of (a, t, joint_a) and (b, t, joint_b) for first <= t < min(last, n_a, n_b); a side that does none of the reaching (a at
+    ``meet`` 0, b at 1) carries weight 0: its target would be its own joint.  ValueError for a row outside [0, B) or in two
+    scenes, Ks + Pm nb over MAX_TRACKS, a bone or contact joint outside [0, J), contact rows that are not two rows of one
+    scene, a contact on a (row, frame, joint) with a non-zero static weight, two contacts on one (row, frame, joint), and
+    non-finite placements, radius <= 0, weight < 0."""
+    T, J, Ks = int(T), int(J), int(static_tracks)
+    pl = np.asarray(placements.detach().cpu().numpy() if torch.is_tensor(placements) else placements, dtype=np.float64)
+    if pl.ndim != 2 or pl.shape[1] != 3:
+        raise ValueError(f"placements of shape {pl.shape} must be (B, 3) = x, z, yaw")
+    if not np.isfinite(pl).all():
+        raise ValueError("placements have non-finite values")
+    B = pl.shape[0]
+    ln = L.check_lengths(lengths, B, T, least=0).to(torch.int32)
+    radius, margin, weight = _positive(radius, "radius"), float(margin), float(weight)
+    if not math.isfinite(margin):
+        raise ValueError("margin must be finite")
+    if not (math.isfinite(weight) and weight >= 0):
+        raise ValueError(f"weight must be finite and >= 0, not {weight}")
+    bones = [(int(p), int(c)) for p, c in (skeleton_bones(J) if bones is None else bones)]
+    if any(not (0 <= p < J and 0 <= c < J) for p, c in bones):
+        raise ValueError(f"bones must name joints in [0, {J})")
+    nb = len(bones)
+    scene_of = {}
+    scenes_rows = [[int(r) for r in rows] for rows in scenes_rows]
+    for s, rows in enumerate(scenes_rows):
+        for r in rows:
+            if not 0 <= r < B:
+                raise ValueError(f"scene {s} names row {r}: outside [0, {B})")
+            if r in scene_of:
+                raise ValueError(f"row {r} is in two scenes (or twice in one)")
+            scene_of[r] = s
+    Pm = max([len(rows) - 1 for rows in scenes_rows] + [0]) if avoid else 0
+    if not 0 <= Ks <= MAX_TRACKS or Ks + Pm * nb > MAX_TRACKS:
+        raise ValueError(f"{Ks} static tracks + {Pm} partners x {nb} bones = {Ks + Pm * nb} tracks a frame: at most {MAX_TRACKS} "
+                         "are allowed; give a bones= subset (fewer capsules per partner)")
+    prow = np.full((B, Pm), -1, dtype=np.int32)
+    for rows in scenes_rows:
+        for r in rows:
+            others = [p for p in rows if p != r][:Pm]
+            prow[r, :len(others)] = others
+    w = torch.zeros((B, T, J, 3))
+    if control_weights is not None:
+        cw = torch.as_tensor(control_weights).detach().to("cpu", torch.float32)
+        if tuple(cw.shape) != (B, T, J, 3):
+            raise ValueError(f"control_weights of shape {tuple(cw.shape)} must be {(B, T, J, 3)}")
+        w = cw.clone()
+    taken = w.abs().sum(-1) != 0  # (B, T, J)
+    table = np.zeros((len(contacts), 8), dtype=np.int32)
+    for i, c in enumerate(contacts):
+        if not isinstance(c, Contact):
+            raise ValueError("contacts is a list of entries made by motion_scene.contact")
+        a, ja, b, jb, first, last, cwt, meet = c
+        if not (0 <= a < B and 0 <= b < B) or scene_of.get(a, -1) != scene_of.get(b, -2):
+            raise ValueError(f"contact {i}: rows {a} and {b} must be two rows of one scene")
+        if not (0 <= ja < J and 0 <= jb < J):
+            raise ValueError(f"contact {i}: joints {ja} and {jb} must lie in [0, {J})")
+        end = min(last, int(ln[a]), int(ln[b]))
+        for row, joint, share in ((a, ja, meet), (b, jb, 1.0 - meet)):
+            if first < end:
+                if bool(taken[row, first:end, joint].any()):
+                    raise ValueError(f"contact {i} lands on (row {row}, joint {joint}) in frames that carry a static control "
+                                     "weight or another contact")
+                taken[row, first:end, joint] = True
+                w[row, first:end, joint] = cwt if share > 0 else 0.0
+        table[i, :6] = (a, ja, b, jb, first, last)
+        table[i, 6] = np.float32(meet).view(np.int32)
+    place = np.stack([pl[:, 0], pl[:, 1], np.cos(pl[:, 2]), np.sin(pl[:, 2])], 1).astype(np.float32)
+    return PartnerTables(partner_rows=torch.from_numpy(prow), bones=torch.tensor(bones, dtype=torch.int32).reshape(nb, 2),
+                         placements=torch.from_numpy(place), pose=torch.from_numpy(pl.copy()), contacts=torch.from_numpy(table), weights=w, lengths=ln,
+                         radius=radius, margin=margin, weight=weight, Ks=Ks, Km=Ks + Pm * nb, Pm=Pm, nb=nb, B=B, T=T, J=J)
+
+
+def partner_scratch_floats(B: int, T: int, F: int) -> int:
+    """Floats of the scratch ``mdm_partner_tracks`` needs next to the world joints."""
+    return int(L.lib().mdm_partner_tracks_scratch_floats(B, T, F))
+
+
+def partner_launch(x0, lengths, mean_rows, std_rows, tables: PartnerTables, dev_tables, world, scratch, tracks, bounds, targets):
+    """One ``mdm_partner_tracks`` call on the current stream: every tensor is the caller's, on the device, float32 (int32
+    lengths) and contiguous; ``dev_tables`` = (placements, partner_rows, contacts) of ``tables`` on the device, ``scratch``
+    ``partner_scratch_floats`` floats.  Allocation
+    free: the sampling runner calls it inside graph capture."""
+    t = tables
+    place, prow, cont = dev_tables
+    B, T, F = x0.shape
+    L.check(L.lib().mdm_partner_tracks(
+        x0.data_ptr(), lengths.data_ptr(), mean_rows.data_ptr(), std_rows.data_ptr(), place.data_ptr(),
+        prow.data_ptr() if t.Pm else 0, t.partner_rows.data_ptr() if t.Pm else 0, t.Pm, t.bones.data_ptr() if t.nb else 0, t.nb,
+        t.radius, t.margin, t.weight, t.Ks, t.Km, cont.data_ptr() if len(t.contacts) else 0,
+        t.contacts.data_ptr() if len(t.contacts) else 0, len(t.contacts), B, T, F, world.data_ptr(), scratch.data_ptr(),
+        L.ptr(tracks), L.ptr(bounds),
+        L.ptr(targets), L.stream_ptr()), "mdm_partner_tracks")
+
+
+@torch.no_grad()
+def partner_tracks(x0, lengths, mean, std, tables: PartnerTables, static_tracks=None, return_world=False):
+    """The device call of characters sampled together on its own: from ``x0`` (B, T, F) on a GPU, ``mean`` / ``std`` (F,) or
+    (B, F) and ``partner_tables``' result, ``(tracks (B, T, Km, REC), track_bounds (B, T, 4), targets (B, T, J, 3))`` as the
+    tracks guidance takes them (``tables.weights`` are the targets' weights).  ``static_tracks``: the Ks user tracks as
+    ``batch_tracks`` takes them (``tables.Ks`` of them).  ``return_world``: also the world joints (B, T, J, 3)."""
+    L.require_cuda(x0)
+    dev = x0.device
+    x = x0.detach().to(torch.float32).contiguous()
+    if x.dim() != 3:
+        raise ValueError(f"x0 of shape {tuple(x.shape)} must be (B, T, F)")
+    B, T, F = x.shape
+    t = tables
+    if (B, T, joints_for_feats(F)) != (t.B, t.T, t.J):
+        raise ValueError(f"x0 of shape {tuple(x.shape)} does not fit tables made for B = {t.B}, T = {t.T}, J = {t.J}")
+    ln = torch.as_tensor(lengths).flatten().to(torch.int32)
+    if ln.numel() != B or not bool((ln.cpu() == t.lengths).all()):
+        raise ValueError("lengths must be the lengths the tables were made for")
+    tracks = torch.zeros((B, T, t.Km, REC), device=dev)
+    if t.Ks:
+        if static_tracks is None:
+            raise ValueError(f"the tables reserve {t.Ks} static tracks: give static_tracks")
+        st = batch_tracks(static_tracks, B, T, t.lengths)
+        if st.shape[2] != t.Ks:
+            raise ValueError(f"static_tracks hold {st.shape[2]} tracks, the tables reserve {t.Ks}")
+        tracks[:, :, :t.Ks] = st.to(dev)
+    elif static_tracks is not None:
+        raise ValueError("static_tracks given, but the tables reserve none (static_tracks=0)")
+    bounds = torch.empty((B, T, 4), device=dev)
+    targets = torch.zeros((B, T, t.J, 3), device=dev)
+    world = torch.empty((B, T, t.J, 3), device=dev)
+    scratch = torch.empty(max(partner_scratch_floats(B, T, F), 1), device=dev)
+    mean_t = _rows(mean, B, F, "mean").to(dev).contiguous()
+    std_t = _rows(std, B, F, "std").to(dev).contiguous()
+    dev_tables = tuple(v.to(dev).contiguous() for v in (t.placements, t.partner_rows, t.contacts))
+    with torch.cuda.device(dev):
+        partner_launch(x, ln.to(dev).contiguous(), mean_t, std_t, t, dev_tables, world, scratch, tracks if t.Km else None,
+                       bounds if t.Km else None, targets)
+    if not t.Km:
+        bounds.fill_(-math.inf)
+        bounds[..., :3] = 0.0
+    return (tracks, bounds, targets, world) if return_world else (tracks, bounds, targets)

@@ -23,6 +23,7 @@ conditioning once (``conditioning.Conditioning``, the one description of its key
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 from torch.nn.utils.rnn import pad_sequence
 
@@ -117,15 +118,20 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate(self, caption, m_lens, dim_pose, batch_size=8, *, progress=False, seed=None, noises=None, sampler="ddpm",
-                 sample_steps=None, eta=0.0, **conditioning):
+                 sample_steps=None, eta=0.0, sample_offset=0, model_extra=None, **conditioning):
         """``seed``: sample i's noise is then a function of (seed, i) only (counter-based device generator), so the result
         does not depend on ``batch_size``; without it the torch generator is used, as in the reference.
         ``noises``: optional list with one ``(x_T, [step noise, ...])`` pair per batch, replacing the draws (parity tests).
         ``sampler`` / ``sample_steps`` / ``eta``: see ``sampling_diffusion``; e.g. ``sampler="dpmpp2m", sample_steps=20``.
         ``**conditioning``: motion editing, composed prompts, joint-position control, a motion or latents to start from; see
         ``conditioning.Conditioning``, the one description of every such keyword.  Each batch takes its samples' rows and
-        its first T frames of them."""
+        its first T frames of them.  ``sample_offset``: the call's samples are samples ``sample_offset`` ... of a larger one
+        (under ``seed`` sample i's noise is a function of (seed, sample_offset + i)).  ``model_extra``: further ``model_kwargs``
+        that name the rows of one batch (``control_partner_*`` / ``control_contact_*``): the call must then
+        be one batch."""
         N = len(caption)
+        if model_extra and N > batch_size:
+            raise ValueError(f"model_extra names the rows of one batch: {N} samples do not fit batch_size = {batch_size}")
         self.eval_mode()
         cond = Conditioning(caption, dim_pose, device=self.device, **conditioning)
         all_output = []
@@ -135,7 +141,8 @@ class DDPMTrainer(object):
             lens = torch.as_tensor(m_lens[cur:end])
             T = min(int(lens.max()), self._model().num_frames)
             out = self._sample_rows(cond, slice(cur, end), lens, T, sampler, sample_steps, eta, progress=progress,
-                                    noise=x_T, step_noise=step_noise, seed=seed, sample_offset=cur)
+                                    noise=x_T, step_noise=step_noise, seed=seed, sample_offset=sample_offset + cur,
+                                    **({"extra": model_extra} if model_extra else {}))
             all_output.extend(out[i] for i in range(out.shape[0]))
         return all_output
 
@@ -289,7 +296,7 @@ class DDPMTrainer(object):
 
     @torch.no_grad()
     def generate_together(self, scenes, dim_pose, mean, std, *, radius=0.08, margin=0.05, weight=5.0, bones=None, seed=None,
-                          **kw):
+                          mutual=False, contacts=None, **kw):
         """Several characters in one world: ``scenes`` is a list of scenes, each a list of characters
         ``dict(caption=, length=, position=(x, z), yaw=, control_joints=, control_weights=, scene=)``; ``position`` / ``yaw``
         (default the origin, 0) place the character's own frame in the world (``motion_scene.to_world``), and targets
@@ -304,9 +311,23 @@ class DDPMTrainer(object):
         ``**kw`` goes to ``generate_joints`` (``control_scale``, ``control_iters``, the sampler, ``sigma``, ...; with
         ``pin_targets=True`` every character's wrists and ankles end on their targets, moved into its own frame, §28; a stage
         none of whose characters has targets runs without pins).  A scene of
-        one character is ``generate_joints`` followed by ``to_world``, bit for bit."""
+        one character is ``generate_joints`` followed by ``to_world``, bit for bit.
+        ``mutual=True``: the characters of a scene are sampled together, rows of one ``generate_joints``
+        batch, and on every step each avoids the capsules of the others' current estimate: nobody is furniture, and the
+        result depends on no order among them.  Scenes are dealt whole, in order, into batches of at most ``batch_size``
+        rows; sample i's noise is a function of (``seed``, its index in the scene-then-character order).  ``contacts``: one
+        list per scene of ``motion_scene.contact(a, joint_a, b, joint_b, frames, weight, meet)`` between its characters
+        ``a`` / ``b``: both joints are drawn to the meeting point of the current estimate.  ``weight=0`` leaves the avoidance
+        out.  With ``pin_targets=True`` every contact's meeting point, computed from the final joints, joins both characters'
+        pin targets (``postprocess.pin_limbs`` decides what it can pin).  ValueError for ``contacts`` without ``mutual``, a
+        scene of more characters than ``batch_size`` and one whose (C - 1) x len(bones) partner capsules do not fit the
+        ``motion_scene.MAX_TRACKS`` tracks of a frame (give a ``bones=`` subset)."""
         from . import motion_scene as MS
         J = (dim_pose + 1) // 12
+        if contacts is not None and not mutual:
+            raise ValueError("contacts join characters that are sampled together: pass mutual=True")
+        if mutual:
+            return self._generate_mutual(scenes, dim_pose, mean, std, radius, margin, weight, bones, seed, contacts, kw)
         pin = bool(kw.pop("pin_targets", False))
         if pin and not any(c.get("control_joints") is not None for s in scenes for c in s):
             raise ValueError("pin_targets=True pins the characters' own control_joints / control_weights: none has any")
@@ -348,6 +369,104 @@ class DDPMTrainer(object):
                                           **(dict(pin_targets=True) if pin and "control_joints" in cond else {}))
             for k, pl, j in zip(rows, place, joints):
                 out[k][i] = MS.to_world(j, *pl)
+        return out
+
+    def _generate_mutual(self, scenes, dim_pose, mean, std, radius, margin, weight, bones, seed, contacts, kw):
+        """``generate_together(mutual=True)``: see there."""
+        from . import motion_scene as MS
+        from .motion_features import skeleton_for_feats
+        from .postprocess import pin_limbs
+        J = (dim_pose + 1) // 12
+        kw = dict(kw)
+        pin, pin_blend, batch_size = bool(kw.pop("pin_targets", False)), kw.pop("pin_blend", 5), int(kw.pop("batch_size", 8))
+        contacts = [[] for _ in scenes] if contacts is None else [list(c) for c in contacts]
+        if len(contacts) != len(scenes):
+            raise ValueError(f"contacts must hold one list per scene ({len(scenes)}), not {len(contacts)}")
+        if pin and not any(c.get("control_joints") is not None for s in scenes for c in s) and not any(contacts):
+            raise ValueError("pin_targets=True pins control_joints / control_weights and contacts: the scenes have neither")
+        bone_list = MS.skeleton_bones(J) if bones is None else [(int(p), int(c)) for p, c in bones]
+        avoid = float(weight) > 0
+        for k, (s, cs) in enumerate(zip(scenes, contacts)):
+            if len(s) > batch_size:
+                raise ValueError(f"scene {k} has {len(s)} characters, a batch {batch_size} rows: raise batch_size (characters "
+                                 "sampled together share a batch; a bones= subset makes room for more partners)")
+            if avoid and (len(s) - 1) * len(bone_list) > MS.MAX_TRACKS:
+                raise ValueError(f"scene {k}: {len(s) - 1} partners x {len(bone_list)} bones = {(len(s) - 1) * len(bone_list)} "
+                                 f"tracks a frame, at most {MS.MAX_TRACKS} are allowed: give a bones= subset")
+            for c in cs:
+                if not isinstance(c, MS.Contact) or max(c[0], c[2]) >= len(s):
+                    raise ValueError(f"scene {k}: contacts are motion_scene.contact(...) entries between its {len(s)} characters")
+        batches, cur = [], []  # whole scenes, in order
+        for k, s in enumerate(scenes):
+            if cur and sum(len(scenes[i]) for i in cur) + len(s) > batch_size:
+                batches.append(cur)
+                cur = []
+            if len(s):
+                cur.append(k)
+        if cur:
+            batches.append(cur)
+        first = np.cumsum([0] + [len(s) for s in scenes]).tolist()  # a scene's first row in the flattened order
+        out = [[None] * len(s) for s in scenes]
+        for batch in batches:
+            chars = [c for k in batch for c in scenes[k]]
+            base = first[batch[0]]
+            row_of = {(k, i): first[k] - base + i for k in batch for i in range(len(scenes[k]))}
+            lens = [int(c["length"]) for c in chars]
+            place = [(tuple(c.get("position", (0.0, 0.0))), float(c.get("yaw", 0.0))) for c in chars]
+            static = [MS.records_to_local(MS.pack_scene(c.get("scene") or []), *pl).to(torch.float32) for c, pl in zip(chars, place)]
+            cond = {}
+            if any(s.shape[0] for s in static):
+                rec = torch.zeros((len(chars), max(s.shape[0] for s in static), MS.REC))
+                for n, s in enumerate(static):
+                    rec[n, :s.shape[0]] = s
+                cond["scene"] = rec
+            g = w = None
+            if any(c.get("control_joints") is not None for c in chars):
+                g, w = torch.zeros((len(chars), max(lens), J, 3)), torch.zeros((len(chars), max(lens), J, 3))
+                for n, (c, pl) in enumerate(zip(chars, place)):
+                    if c.get("control_joints") is None:
+                        continue
+                    tg = torch.as_tensor(c["control_joints"], dtype=torch.float32)
+                    wt = torch.as_tensor(c["control_weights"], dtype=torch.float32)
+                    if tuple(tg.shape) != (lens[n], J, 3):
+                        raise ValueError(f"control_joints of shape {tuple(tg.shape)} must be {(lens[n], J, 3)}, in the world")
+                    g[n, :lens[n]] = MS.to_local(tg, *pl)
+                    w[n, :lens[n]] = wt.reshape(tuple(wt.shape) + (1,) * (3 - wt.dim())).expand(lens[n], J, 3)
+                cond.update(control_joints=g, control_weights=w)
+            rows_contacts = [MS.Contact((row_of[k, c[0]], c[1], row_of[k, c[2]], c[3]) + tuple(c[4:]))
+                             for k in batch for c in contacts[k]]
+            multi = avoid and any(len(scenes[k]) > 1 for k in batch)
+            extra = None
+            if multi or rows_contacts:  # else: nothing to avoid and nothing to reach for, the call generate_joints makes
+                extra = dict(control_partner_scenes=[[row_of[k, i] for i in range(len(scenes[k]))] for k in batch],
+                             control_partner_placements=torch.tensor([[pl[0][0], pl[0][1], pl[1]] for pl in place],
+                                                                     dtype=torch.float64),
+                             control_partner_bones=bone_list, control_partner_radius=radius, control_partner_margin=margin,
+                             control_partner_weight=weight, control_contact_list=rows_contacts)
+                if "scene" not in cond and "control_joints" not in cond:
+                    cond["scene"] = []  # the guidance needs mean / std: an empty scene switches it on
+            joints = self.generate_joints([c["caption"] for c in chars], torch.tensor(lens), dim_pose, mean, std,
+                                          batch_size=len(chars), seed=seed, sample_offset=base,
+                                          **(dict(model_extra=extra) if extra else {}), **cond, **kw)
+            world = [MS.to_world(j, *pl) for j, pl in zip(joints, place)]
+            if pin and (g is not None or rows_contacts):
+                tg = torch.zeros((len(chars), max(lens), J, 3)) if g is None else g.clone()
+                wt = torch.zeros_like(tg) if w is None else w.clone()
+                for a, ja, b, jb, f0, f1, cw, meet in rows_contacts:
+                    f1 = min(f1, lens[a], lens[b])
+                    if f0 >= f1 or cw <= 0:
+                        continue
+                    m = world[a][f0:f1, ja] + meet * (world[b][f0:f1, jb] - world[a][f0:f1, ja])
+                    for r, jr in ((a, ja), (b, jb)):
+                        tg[r, f0:f1, jr] = MS.to_local(m, *place[r]).to(tg)
+                        wt[r, f0:f1, jr] = cw
+                padded = pad_sequence(list(joints), batch_first=True)
+                pinned = pin_limbs(padded, torch.tensor(lens), tg, wt, skeleton=skeleton_for_feats(dim_pose, strict=True),
+                                   blend=pin_blend)
+                world = [MS.to_world(pinned[n, :lens[n]], *pl) for n, pl in enumerate(place)]
+            for k in batch:
+                for i in range(len(scenes[k])):
+                    out[k][i] = world[row_of[k, i]]
         return out
 
     @torch.no_grad()
@@ -579,7 +698,7 @@ class DDPMTrainer(object):
         ``(n, H, W, 3)`` uint8 frames (``(n, H, W)`` palette indices with ``palette``), n the length of its longest character,
         showing every character of the scene and the union of the characters' ``scene`` primitives (already in world
         coordinates).  ``camera`` None: one camera fitted to all scenes of the call; ``style``: a dict of ``render_world``'s
-        style arguments.  ``**kw`` goes to ``generate_together``."""
+        style arguments.  ``**kw`` goes to ``generate_together``, ``mutual=`` and ``contacts=`` included."""
         worlds = self.generate_together(scenes, dim_pose, mean, std, **kw)
         return MO.to_world_frames(worlds, [MO.world_scene(s) for s in scenes], None, size, camera, palette, style)
 

@@ -43,6 +43,9 @@ G x G height field and ``terrain_stand="contacts"``:
 
     timeout -k 10 900 python tools/sample_time.py --control 1,5 --terrain 128 --reps 5 --precisions 1
 
+``--partners`` measures characters sampled together: 16 scenes of two characters against the same rows
+with 21 static tracks and against the sequential two-stage ``generate_together``, DDIM-50 and DPM-Solver++(2M)-20:
+    timeout -k 10 900 python tools/sample_time.py --partners --reps 5 --precisions 1 > profiles/partners_sample_time.txt
 ``--control I --scene K --tracks far,near,near_nobounds`` measures tracks: the controlled generation with
 a scene of K primitives without and with the 21 capsule tracks of a character (``motion_scene.character_tracks``): far from the
 motion (every joint outside the frames' balls), around it, and around it without the broad phase.
@@ -83,6 +86,8 @@ def main():
                     "control alone")
     ap.add_argument("--tracks", default=None, help="far,near,near_nobounds (with --control and --scene): time 21 character tracks "
                     "against control with the scene alone")
+    ap.add_argument("--partners", action="store_true", help="time characters sampled together (16 scenes of two, 21 bones) "
+                    "against 21 static character tracks and against the two-stage sequential generate_together")
     ap.add_argument("--terrain", type=int, default=None, help="G (with --control): time a G x G terrain with "
                     'terrain_stand="contacts" against joint control alone')
     ap.add_argument("--long", type=int, default=None, help="H: time long motions (4 windows each, H shared frames) "
@@ -102,6 +107,8 @@ def main():
     import types
     tr = Tr.DDPMTrainer(types.SimpleNamespace(device=dev, diffusion_steps=1000, is_train=False, cfg_scale=7.5), m)
     caps = [f"caption {i}" for i in range(B)]
+    if a.partners:
+        return partners_main(a, tr, m, caps, B, T)
     if a.edit:
         return edit_main(a, tr, m, caps, length, B, T)
     if a.compose:
@@ -478,6 +485,72 @@ def tracks_main(a, tr, m, caps, length, B, T):
         spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
         print(f"{r['precision']:>9} {r['control_iters']:>5} {r['tracks']:>14} {r['sampler']:>22} {r['scene_ms']:>9.1f} "
               f"{r['tracks_ms']:>10.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
+
+
+def partners_main(a, tr, m, caps, B, T):
+    # B / 2 scenes of two characters sampled together, in alternating pairs against (a) the same rows with
+    # 21 static "near" character tracks (tracks_main's cloud around the samples): what the producer launch costs on top of the
+    # guidance it feeds, and (b) the two-stage sequential generate_together: two generations of B / 2 rows against one of B.
+    MS = importlib.import_module("motiondiffusion-moe_amd.motion_scene")
+    if B % 2:
+        raise SystemExit("--partners needs a batch of whole two-character scenes")
+    # The unclipped random-weight samples are rows of size thousands: the de-normalisation scales them down (std 0.002 for the
+    # root velocities and the height, 0.0005 for the joint columns, 1e-4 for the heading velocity; the "bodies" are still
+    # clouds that wander hundreds of metres), and the step and the avoidance weight are small, so that the guidance stays
+    # finite over 196 frames (the warm-up asserts it).  The cost does not depend on the weight.  The static tracks are
+    # tracks_main's "near" cloud, of the samples' own extent: most joints are inside the frames' balls and walk all 21 records.
+    mean, std = torch.zeros(263), torch.full((263,), 0.002)
+    std[0], std[4:67] = 1e-4, 0.0005
+    tg, w = torch.zeros(T, 22, 3), torch.zeros(T, 22)
+    tg[..., 1], w[:] = 1.0, 1.0  # every joint's height, as tracks_main: all modes run the guidance with targets
+    scenes = [[dict(caption=caps[2 * i], length=T, control_joints=tg, control_weights=w),
+               dict(caption=caps[2 * i + 1], length=T, position=(0.5, 0.0), yaw=0.3, control_joints=tg, control_weights=w)]
+              for i in range(B // 2)]
+    gen_ = torch.Generator().manual_seed(0)
+    cloud = torch.randn(1, 22, 3, generator=gen_, dtype=torch.float64) * 300 + torch.cumsum(
+        torch.randn(T, 1, 3, generator=gen_, dtype=torch.float64) * 5, 0)
+    tracks = MS.character_tracks(cloud, 0.08, margin=0.05, weight=0.01)
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for sampler, steps, n in (("ddim", 50, 50), ("dpmpp2m", 20, 20)):
+            opts = dict(seed=0, sampler=sampler, sample_steps=steps, control_scale=5.0, control_iters=1, sigma=0.0, batch_size=B)
+            pair = dict(radius=0.08, margin=0.05, weight=0.01)
+            runs = {"mutual": lambda: tr.generate_together(scenes, 263, mean, std, mutual=True, **pair, **opts),
+                    "static": lambda: tr.generate_joints(caps, torch.full((B,), T), 263, mean, std, scene_tracks=tracks,
+                                                         control_joints=tg[None].expand(B, -1, -1, -1),
+                                                         control_weights=w[None].expand(B, -1, -1), **opts),
+                    "sequential": lambda: tr.generate_together(scenes, 263, mean, std, **pair, **opts)}
+            for other in ("static", "sequential"):
+                for k in ("mutual", other):  # warm-up
+                    res = runs[k]()
+                    assert all(torch.isfinite(j).all() for v in res for j in (v if isinstance(v, list) else [v])), k
+                ts = {"mutual": [], other: []}
+                for _ in range(a.reps):
+                    for k in (other, "mutual"):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        runs[k]()
+                        torch.cuda.synchronize()
+                        ts[k].append((time.perf_counter() - t0) * 1e3)
+                med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+                diff = sorted(c - p for p, c in zip(ts[other], ts["mutual"]))
+                name = {"ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+                line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, against=other, other_ms=round(med[other], 2),
+                            mutual_ms=round(med["mutual"], 2), diff_ms_median=round(diff[len(diff) // 2], 2),
+                            diff_ms_min=round(diff[0], 2), diff_ms_max=round(diff[-1], 2),
+                            diff_us_per_step=round(diff[len(diff) // 2] / n * 1e3, 1),
+                            other_reps_ms=[round(t, 2) for t in ts[other]], mutual_reps_ms=[round(t, 2) for t in ts["mutual"]])
+                rows.append(line)
+                print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}: {B // 2} scenes of two characters sampled together (21 bones, control_iters 1) against "
+          f"the same rows with 21 static near tracks and against the sequential generate_together; {torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'against':>11} {'sampler':>22} {'other ms':>9} {'mutual ms':>10} {'diff ms (min..max)':>22} {'us/step':>8}")
+    for r in rows:
+        spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
+        print(f"{r['precision']:>9} {r['against']:>11} {r['sampler']:>22} {r['other_ms']:>9.1f} {r['mutual_ms']:>10.1f} {spread:>22} "
+              f"{r['diff_us_per_step']:>8.1f}")
 
 
 def long_main(a, tr, m, caps, B, T):
