@@ -13,41 +13,20 @@
 // (no bank conflicts between frame threads).  Frame phases run one thread per frame (a thread walks its frame's J joints, so
 // per-frame sums need no atomics and the result is deterministic); the three scans run in one thread with fp64
 // accumulators.  No other column of the feature row enters recover_from_ric, so none is read or written.
+// Host side: the eight entries fill joint_control.h's Terms and Clock, name their level and call launch_control, which holds
+// the frame limit, the common checks (args_ok), the choice of the kernel form and the file's one launch.
+#include "joint_control.h"
 #include "kernels.h"
-#include "scene_sdf.h"
-#include "terrain.h"
-
-#include <cmath>
 
 namespace mdm {
 namespace {
+
+using namespace control;
 
 constexpr int CTRL_THREADS = 256;
 constexpr int CTRL_LDS_BYTES = 64 * 1024;
 enum { CW, SW, RX, RZ, PX, PZ, GX, GZ, GA, GH, FR };  // fields of the per-frame record
 constexpr int CTRL_FRAME_BYTES = FR * 4 + 8;          // per frame: the record + the fp64 loss
-
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-
-// motion_post.hip's rot_y with q = qy, w: the same operations in the same order (P agrees with mdm_motion_postprocess)
-__device__ __forceinline__ void rot_y(float w, float qy, float vx, float vz, float& ox, float& oz) {
-  const float uvx = mul(qy, vz), uvz = -mul(qy, vx);
-  const float uuvx = mul(qy, uvz), uuvz = -mul(qy, uvx);
-  ox = add(vx, mul(2.f, add(mul(w, uvx), uuvx)));
-  oz = add(vz, mul(2.f, add(mul(w, uvz), uuvz)));
-}
-
-// Partials of rot_y(w = cos a, qy = -sin a) in exact arithmetic:
-//   ox = a11 vx + a13 vz, oz = -a13 vx + a11 vz with a11 = 1 - 2 qy^2, a13 = 2 w qy
-//   dox/da = 2 (e vz + f vx), doz/da = 2 (f vz - e vx) with e = qy^2 - w^2, f = 2 qy w
-struct RotD {
-  double a11, a13, e, f;
-};
-__device__ __forceinline__ RotD rot_d(float cw, float sw) {
-  const double w = cw, q = -(double)sw;
-  return {1.0 - 2.0 * q * q, 2.0 * w * q, q * q - w * w, 2.0 * q * w};
-}
 
 // GUIDE = false: mdm_joint_loss_grad (one evaluation; loss_out and the dense gradient grad_out written).
 // GUIDE = true:  mdm_joint_guidance (iters steps of x0 -= scale (1 - m) grad in LDS, then x0 / x updated where delta != 0).
@@ -302,8 +281,6 @@ __global__ __launch_bounds__(CTRL_THREADS) void joint_control_kernel(
   }
 }
 
-int control_joints(int F) { return (F + 1) % 12 == 0 && F >= 11 ? (F + 1) / 12 : 0; }
-
 // prims < 0: no scene; else the K = prims primitive records and the joints' (radius, weight) as well
 size_t control_lds_bytes(int T, int J, int prims = -1) {
   const int DS = (3 * J + 1) | 1;
@@ -311,134 +288,96 @@ size_t control_lds_bytes(int T, int J, int prims = -1) {
   return (size_t)2 * DS * 4 + scene + (size_t)T * ((size_t)DS * 4 + CTRL_FRAME_BYTES);
 }
 
-static_assert(scene::MAX_TRACKS == MDM_SCENE_MAX_TRACKS, "scene_sdf.h and mdm_hip.h disagree");
-static_assert(terrain::MAX_GRID == MDM_TERRAIN_MAX_GRID && terrain::TERRAIN_REC == MDM_TERRAIN_REC, "terrain.h and mdm_hip.h disagree");
+// Every entry below: the checks of an entry of `level`, then the one launch, of the form the terms present ask for.
+// g: the clock of a guidance call (x and x0 updated), null for a loss_grad call (loss_out and grad_out written).
+int launch_control(Level level, const Clock* g, float* x, float* x0, const float* mask, const int32_t* length, const float* mean,
+                   const float* std, const float* targets, const float* weights, const Terms& o, int B, int T, int F,
+                   float* loss_out, float* grad_out, void* stream) {
+  if (!x0 || !length || !mean || !std || (g ? !x : !loss_out || !grad_out)) return MDM_ERR_ARG;
+  if (!args_ok(level, targets, weights, o, g)) return MDM_ERR_ARG;
+  const int J = control_joints(F);
+  // the frame limit is the level's, also where the call falls through to a form that would hold more frames
+  const int limit = level == PLAIN ? mdm_joint_control_max_frames(F) : mdm_joint_scene_max_frames(F, o.K);
+  if (J == 0 || B < 0 || T < 1 || T > limit) return MDM_ERR_ARG;
+  if (B == 0) return MDM_OK;
+  const Level form = kernel_form(targets, o.K, o.Km, o.terrain);
+  const Terms u = terms_of(form, o);
+  const Clock c = g ? *g : ONE_EVALUATION;
+  const size_t smem = control_lds_bytes(T, J, form == PLAIN ? -1 : u.K);
+  dispatch(g != nullptr, mask != nullptr, form, [&](auto k) {
+    using Kn = decltype(k);
+    hipLaunchKernelGGL((joint_control_kernel<Kn::GUIDE, Kn::MASK, Kn::SCENE, Kn::TRACKS, Kn::TERRAIN>), dim3(B), dim3(CTRL_THREADS),
+                       smem, (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, c.scale, c.iters,
+                       c.coef, c.steps, c.t_dev, c.t_imm, loss_out, grad_out, u.scene, u.K, u.joint_params, u.tracks, u.Km,
+                       u.track_bounds, u.terrain, u.terrain_rec, u.Gx | u.Gz << 16, u.stand);
+  });
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
+int max_frames(int J, int prims) {
+  const size_t fixed = control_lds_bytes(0, J, prims), frame = control_lds_bytes(1, J, prims) - fixed;
+  return (int)((CTRL_LDS_BYTES - fixed) / frame);
+}
 
 }  // namespace
 }  // namespace mdm
 
+namespace ctl = mdm::control;
+
 extern "C" {
 
 int mdm_joint_control_max_frames(int32_t feats) {
-  const int J = mdm::control_joints(feats);
-  if (J == 0) return 0;
-  const size_t fixed = mdm::control_lds_bytes(0, J), frame = mdm::control_lds_bytes(1, J) - fixed;
-  return (int)((mdm::CTRL_LDS_BYTES - fixed) / frame);
+  const int J = ctl::control_joints(feats);
+  return J == 0 ? 0 : mdm::max_frames(J, -1);
+}
+
+int mdm_joint_scene_max_frames(int32_t feats, int32_t prims) {
+  const int J = ctl::control_joints(feats);
+  return J == 0 || prims < 0 || prims > MDM_SCENE_MAX_PRIMS ? 0 : mdm::max_frames(J, prims);
 }
 
 int mdm_joint_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
                         const float* weights, int32_t B, int32_t T, int32_t F, float* loss_out, float* grad_out,
                         void* stream) {
-  if (!x0 || !length || !mean || !std || !targets || !weights || !loss_out || !grad_out) return MDM_ERR_ARG;
-  const int J = mdm::control_joints(F);
-  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_control_max_frames(F)) return MDM_ERR_ARG;
-  if (B == 0) return MDM_OK;
-  const size_t smem = mdm::control_lds_bytes(T, J);
-  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
-                     const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J, 0.f, 1,
-                     nullptr, 1, nullptr, 0, loss_out, grad_out, nullptr, 0, nullptr, nullptr, 0, nullptr,
-                     nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  return mdm::launch_control(ctl::PLAIN, nullptr, nullptr, const_cast<float*>(x0), nullptr, length, mean, std, targets,
+                             weights, ctl::Terms{}, B, T, F, loss_out, grad_out, stream);
 }
 
 int mdm_joint_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
                        const float* targets, const float* weights, int32_t B, int32_t T, int32_t F, float scale,
                        int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
                        void* stream) {
-  if (!x || !x0 || !length || !mean || !std || !targets || !weights || !coef) return MDM_ERR_ARG;
-  const int J = mdm::control_joints(F);
-  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_control_max_frames(F)) return MDM_ERR_ARG;
-  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
-  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
-  if (B == 0) return MDM_OK;
-  const size_t smem = mdm::control_lds_bytes(T, J);
-  if (mask)
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
-                       x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev, t_imm,
-                       nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr);
-  else
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, false>), dim3(B), dim3(mdm::CTRL_THREADS), smem, (hipStream_t)stream,
-                       x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps, t_dev,
-                       t_imm, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
-}
-
-int mdm_joint_scene_max_frames(int32_t feats, int32_t prims) {
-  const int J = mdm::control_joints(feats);
-  if (J == 0 || prims < 0 || prims > MDM_SCENE_MAX_PRIMS) return 0;
-  const size_t fixed = mdm::control_lds_bytes(0, J, prims), frame = mdm::control_lds_bytes(1, J, prims) - fixed;
-  return (int)((mdm::CTRL_LDS_BYTES - fixed) / frame);
+  const ctl::Clock g = {scale, iters, coef, steps, t_dev, t_imm};
+  return mdm::launch_control(ctl::PLAIN, &g, x, x0, mask, length, mean, std, targets, weights, ctl::Terms{}, B, T, F, nullptr,
+                             nullptr, stream);
 }
 
 int mdm_joint_scene_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
                               const float* weights, const float* scene, int32_t K, const float* joint_params, int32_t B,
                               int32_t T, int32_t F, float* loss_out, float* grad_out, void* stream) {
-  if (!x0 || !length || !mean || !std || !joint_params || !loss_out || !grad_out || !targets != !weights) return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::control_joints(F);
-  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
-  if (K == 0 && targets)  // no scene: the launch of mdm_joint_loss_grad
-    return mdm_joint_loss_grad(x0, length, mean, std, targets, weights, B, T, F, loss_out, grad_out, stream);
-  if (B == 0) return MDM_OK;
-  const size_t smem = mdm::control_lds_bytes(T, J, K);
-  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
-                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, nullptr, 0, nullptr,
-                     nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params};
+  return mdm::launch_control(ctl::SCENE, nullptr, nullptr, const_cast<float*>(x0), nullptr, length, mean, std, targets,
+                             weights, o, B, T, F, loss_out, grad_out, stream);
 }
 
 int mdm_joint_scene_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
                              const float* targets, const float* weights, const float* scene, int32_t K,
                              const float* joint_params, int32_t B, int32_t T, int32_t F, float scale, int32_t iters,
                              const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, void* stream) {
-  if (!x || !x0 || !length || !mean || !std || !joint_params || !coef || !targets != !weights) return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::control_joints(F);
-  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
-  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
-  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
-  if (K == 0 && targets)  // no scene: the launch of mdm_joint_guidance
-    return mdm_joint_guidance(x, x0, mask, length, mean, std, targets, weights, B, T, F, scale, iters, coef, steps, t_dev, t_imm,
-                              stream);
-  if (B == 0) return MDM_OK;
-  const size_t smem = mdm::control_lds_bytes(T, J, K);
-  if (mask)
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
-                       (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr);
-  else
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
-                       (hipStream_t)stream, x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef,
-                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, nullptr, 0, nullptr,
-                       nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params};
+  const ctl::Clock g = {scale, iters, coef, steps, t_dev, t_imm};
+  return mdm::launch_control(ctl::SCENE, &g, x, x0, mask, length, mean, std, targets, weights, o, B, T, F, nullptr,
+                             nullptr, stream);
 }
 
 int mdm_joint_tracks_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
                                const float* weights, const float* scene, int32_t K, const float* joint_params,
                                const float* tracks, int32_t Km, const float* track_bounds, int32_t B, int32_t T, int32_t F,
                                float* loss_out, float* grad_out, void* stream) {
-  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
-  if (Km == 0)  // no tracks: the launch of mdm_joint_scene_loss_grad
-    return mdm_joint_scene_loss_grad(x0, length, mean, std, targets, weights, scene, K, joint_params, B, T, F, loss_out, grad_out,
-                                     stream);
-  if (!x0 || !length || !mean || !std || !joint_params || !loss_out || !grad_out || !targets != !weights) return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::control_joints(F);
-  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
-  if (B == 0) return MDM_OK;
-  const size_t smem = mdm::control_lds_bytes(T, J, K);
-  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
-                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, tracks, Km, track_bounds,
-                     nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params, tracks, Km, track_bounds};
+  return mdm::launch_control(ctl::TRACKS, nullptr, nullptr, const_cast<float*>(x0), nullptr, length, mean, std, targets,
+                             weights, o, B, T, F, loss_out, grad_out, stream);
 }
 
 int mdm_joint_tracks_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
@@ -446,30 +385,10 @@ int mdm_joint_tracks_guidance(float* x, float* x0, const float* mask, const int3
                               const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds, int32_t B,
                               int32_t T, int32_t F, float scale, int32_t iters, const float* coef, int32_t steps,
                               const int32_t* t_dev, int32_t t_imm, void* stream) {
-  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
-  if (Km == 0)  // no tracks: the launch of mdm_joint_scene_guidance
-    return mdm_joint_scene_guidance(x, x0, mask, length, mean, std, targets, weights, scene, K, joint_params, B, T, F, scale,
-                                    iters, coef, steps, t_dev, t_imm, stream);
-  if (!x || !x0 || !length || !mean || !std || !joint_params || !coef || !targets != !weights) return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::control_joints(F);
-  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
-  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
-  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
-  if (B == 0) return MDM_OK;
-  const size_t smem = mdm::control_lds_bytes(T, J, K);
-  if (mask)
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
-                       (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds,
-                       nullptr, nullptr, 0, nullptr);
-  else
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
-                       (hipStream_t)stream, x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef,
-                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds,
-                       nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params, tracks, Km, track_bounds};
+  const ctl::Clock g = {scale, iters, coef, steps, t_dev, t_imm};
+  return mdm::launch_control(ctl::TRACKS, &g, x, x0, mask, length, mean, std, targets, weights, o, B, T, F, nullptr,
+                             nullptr, stream);
 }
 
 int mdm_joint_terrain_loss_grad(const float* x0, const int32_t* length, const float* mean, const float* std, const float* targets,
@@ -477,23 +396,9 @@ int mdm_joint_terrain_loss_grad(const float* x0, const int32_t* length, const fl
                                 const float* tracks, int32_t Km, const float* track_bounds, const float* terrain,
                                 const float* terrain_rec, int32_t Gx, int32_t Gz, const float* stand, int32_t B, int32_t T,
                                 int32_t F, float* loss_out, float* grad_out, void* stream) {
-  if (!terrain)  // no terrain: the launch of mdm_joint_tracks_loss_grad
-    return mdm_joint_tracks_loss_grad(x0, length, mean, std, targets, weights, scene, K, joint_params, tracks, Km, track_bounds, B,
-                                      T, F, loss_out, grad_out, stream);
-  if (!mdm::terrain::terrain_ok(terrain, terrain_rec, Gx, Gz, stand)) return MDM_ERR_ARG;
-  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
-  if (!x0 || !length || !mean || !std || !joint_params || !loss_out || !grad_out || !targets != !weights) return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::control_joints(F);
-  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
-  if (B == 0) return MDM_OK;
-  const size_t smem = mdm::control_lds_bytes(T, J, K);
-  hipLaunchKernelGGL((mdm::joint_control_kernel<false, false, true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
-                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, length, mean, std, targets, weights, T, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, scene, K, joint_params, tracks, Km, track_bounds, terrain,
-                     terrain_rec, Gx | Gz << 16, stand);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params, tracks, Km, track_bounds, terrain, terrain_rec, Gx, Gz, stand};
+  return mdm::launch_control(ctl::TERRAIN, nullptr, nullptr, const_cast<float*>(x0), nullptr, length, mean, std,
+                             targets, weights, o, B, T, F, loss_out, grad_out, stream);
 }
 
 int mdm_joint_terrain_guidance(float* x, float* x0, const float* mask, const int32_t* length, const float* mean, const float* std,
@@ -502,31 +407,10 @@ int mdm_joint_terrain_guidance(float* x, float* x0, const float* mask, const int
                                const float* terrain, const float* terrain_rec, int32_t Gx, int32_t Gz, const float* stand,
                                int32_t B, int32_t T, int32_t F, float scale, int32_t iters, const float* coef, int32_t steps,
                                const int32_t* t_dev, int32_t t_imm, void* stream) {
-  if (!terrain)  // no terrain: the launch of mdm_joint_tracks_guidance
-    return mdm_joint_tracks_guidance(x, x0, mask, length, mean, std, targets, weights, scene, K, joint_params, tracks, Km,
-                                     track_bounds, B, T, F, scale, iters, coef, steps, t_dev, t_imm, stream);
-  if (!mdm::terrain::terrain_ok(terrain, terrain_rec, Gx, Gz, stand)) return MDM_ERR_ARG;
-  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
-  if (!x || !x0 || !length || !mean || !std || !joint_params || !coef || !targets != !weights) return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::control_joints(F);
-  if (J == 0 || B < 0 || T < 1 || T > mdm_joint_scene_max_frames(F, K)) return MDM_ERR_ARG;
-  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
-  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
-  if (B == 0) return MDM_OK;
-  const size_t smem = mdm::control_lds_bytes(T, J, K);
-  if (mask)
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, true, true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
-                       (hipStream_t)stream, x0, x, mask, length, mean, std, targets, weights, T, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds, terrain, terrain_rec,
-                       Gx | Gz << 16, stand);
-  else
-    hipLaunchKernelGGL((mdm::joint_control_kernel<true, false, true, true, true>), dim3(B), dim3(mdm::CTRL_THREADS), smem,
-                       (hipStream_t)stream, x0, x, nullptr, length, mean, std, targets, weights, T, F, J, scale, iters, coef,
-                       steps, t_dev, t_imm, nullptr, nullptr, scene, K, joint_params, tracks, Km, track_bounds, terrain,
-                       terrain_rec, Gx | Gz << 16, stand);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params, tracks, Km, track_bounds, terrain, terrain_rec, Gx, Gz, stand};
+  const ctl::Clock g = {scale, iters, coef, steps, t_dev, t_imm};
+  return mdm::launch_control(ctl::TERRAIN, &g, x, x0, mask, length, mean, std, targets, weights, o, B, T, F, nullptr,
+                             nullptr, stream);
 }
 
 }  // extern "C"

@@ -20,15 +20,17 @@
 // Every lane executes every shuffle and barrier: frames at or past the motion's end contribute zeros, and the trip counts
 // of the loops around barriers depend on the motion alone.  The summation order differs from motion_post_kernel's serial
 // scans: P agrees with mdm_motion_postprocess to rounding, not bit for bit.
+// Host side: the eight entries fill joint_control.h's Terms and Clock, name their level and call launch_canvas, which holds
+// the workspace and LDS-size checks, the common checks (args_ok), the choice of the kernel form and the file's one launch.
+#include "joint_control.h"
 #include "kernels.h"
-#include "scene_sdf.h"
-#include "terrain.h"
 
-#include <cmath>
 #include <cstdint>
 
 namespace mdm {
 namespace {
+
+using namespace control;
 
 constexpr int CV_THREADS = 256;
 constexpr int CV_WAVES = CV_THREADS / 64;
@@ -36,26 +38,6 @@ constexpr int CV_JOINTS = 3;  // joints whose inputs a frame's thread has in fli
 constexpr int CV_TILE = 64;  // frames per LDS tile when the working copy is loaded and written back
 constexpr int CV_BATCH = 6;  // elements of a tile a thread has in flight in the write-back
 enum { CW, SW, GX, GZ, GA, GH, FR };  // fields of the per-frame record
-
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-
-// motion_post.hip's rot_y with q = qy, w: the same operations in the same order
-__device__ __forceinline__ void rot_y(float w, float qy, float vx, float vz, float& ox, float& oz) {
-  const float uvx = mul(qy, vz), uvz = -mul(qy, vx);
-  const float uuvx = mul(qy, uvz), uuvz = -mul(qy, uvx);
-  ox = add(vx, mul(2.f, add(mul(w, uvx), uuvx)));
-  oz = add(vz, mul(2.f, add(mul(w, uvz), uuvz)));
-}
-
-// partials of rot_y(w = cos a, qy = -sin a): see motion_control.hip
-struct RotD {
-  double a11, a13, e, f;
-};
-__device__ __forceinline__ RotD rot_d(float cw, float sw) {
-  const double w = cw, q = -(double)sw;
-  return {1.0 - 2.0 * q * q, 2.0 * w * q, q * q - w * w, 2.0 * q * w};
-}
 
 // Inclusive prefix (REVERSE: suffix) sum of v over the workgroup's threads, on top of `carry`, the sum of the blocks
 // already scanned; `carry` then takes this block in.  `excl` (may be null): the same without the thread's own value.
@@ -397,8 +379,6 @@ __global__ __launch_bounds__(CV_THREADS) void canvas_control_kernel(
   }
 }
 
-int canvas_joints(int F) { return (F + 1) % 12 == 0 && F >= 11 ? (F + 1) / 12 : 0; }
-
 // prims < 0: no scene; else the K = prims primitive records and the joints' (radius, weight) as well
 size_t canvas_lds_bytes(int J, int prims = -1) {
   const int D = 3 * J + 1;
@@ -406,13 +386,42 @@ size_t canvas_lds_bytes(int J, int prims = -1) {
   return ((size_t)2 * D + scene + (size_t)CV_TILE * (D | 1)) * 4;
 }
 
+// Every entry below: the checks of an entry of `level`, then the one launch, of the form the terms present ask for.
+// g: the clock of a guidance call (x and x0 updated), null for a loss_grad call (loss_out and grad_out written).
+int launch_canvas(Level level, const Clock* g, float* x, float* x0, const float* mask, const int32_t* motion_offsets,
+                  const int32_t* frame_rows, const float* mean, const float* std, const float* targets, const float* weights,
+                  const Terms& o, int M, int F, float* loss_out, float* grad_out, float* workspace, void* stream) {
+  if (!x0 || !motion_offsets || !frame_rows || !mean || !std || !workspace || (g ? !x : !loss_out || !grad_out))
+    return MDM_ERR_ARG;
+  if (!args_ok(level, targets, weights, o, g)) return MDM_ERR_ARG;
+  const int J = control_joints(F);
+  if (J == 0 || M < 0) return MDM_ERR_ARG;
+  if (M == 0) return MDM_OK;
+  const Level form = kernel_form(targets, o.K, o.Km, o.terrain);
+  const Terms u = terms_of(form, o);
+  const Clock c = g ? *g : ONE_EVALUATION;
+  const size_t smem = canvas_lds_bytes(J, form == PLAIN ? -1 : u.K);
+  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
+  dispatch(g != nullptr, mask != nullptr, form, [&](auto k) {
+    using Kn = decltype(k);
+    hipLaunchKernelGGL((canvas_control_kernel<Kn::GUIDE, Kn::MASK, Kn::SCENE, Kn::TRACKS, Kn::TERRAIN>), dim3(M), dim3(CV_THREADS),
+                       smem, (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
+                       c.scale, c.iters, c.coef, c.steps, c.t_dev, c.t_imm, loss_out, grad_out, workspace, u.scene, u.K,
+                       u.joint_params, u.tracks, u.Km, u.track_bounds, u.terrain, u.terrain_rec, u.Gx | u.Gz << 16, u.stand);
+  });
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return MDM_OK;
+}
+
 }  // namespace
 }  // namespace mdm
+
+namespace ctl = mdm::control;
 
 extern "C" {
 
 int64_t mdm_canvas_control_workspace_floats(int32_t total_frames, int32_t F) {
-  const int J = mdm::canvas_joints(F);
+  const int J = ctl::control_joints(F);
   if (J == 0 || total_frames < 0) return 0;
   return (int64_t)total_frames * (3 * J + 1 + mdm::FR);
 }
@@ -420,70 +429,26 @@ int64_t mdm_canvas_control_workspace_floats(int32_t total_frames, int32_t F) {
 int mdm_canvas_joint_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
                                const float* std, const float* targets, const float* weights, int32_t M, int32_t F,
                                float* loss_out, float* grad_out, float* workspace, void* stream) {
-  if (!x0 || !motion_offsets || !frame_rows || !mean || !std || !targets || !weights || !loss_out || !grad_out || !workspace)
-    return MDM_ERR_ARG;
-  const int J = mdm::canvas_joints(F);
-  if (J == 0 || M < 0) return MDM_ERR_ARG;
-  if (M == 0) return MDM_OK;
-  const size_t smem = mdm::canvas_lds_bytes(J);
-  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream,
-                     const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
-                     0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr,
-                     nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  return mdm::launch_canvas(ctl::PLAIN, nullptr, nullptr, const_cast<float*>(x0), nullptr, motion_offsets, frame_rows, mean, std,
+                            targets, weights, ctl::Terms{}, M, F, loss_out, grad_out, workspace, stream);
 }
 
 int mdm_canvas_joint_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
                               const float* mean, const float* std, const float* targets, const float* weights, int32_t M,
                               int32_t F, float scale, int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev,
                               int32_t t_imm, float* workspace, void* stream) {
-  if (!x || !x0 || !motion_offsets || !frame_rows || !mean || !std || !targets || !weights || !coef || !workspace)
-    return MDM_ERR_ARG;
-  const int J = mdm::canvas_joints(F);
-  if (J == 0 || M < 0) return MDM_ERR_ARG;
-  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
-  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
-  if (M == 0) return MDM_OK;
-  const size_t smem = mdm::canvas_lds_bytes(J);
-  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
-  if (mask)
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
-                       x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale, iters, coef, steps, t_dev,
-                       t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr,
-                       nullptr, nullptr, 0, nullptr);
-  else
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, false>), dim3(M), dim3(mdm::CV_THREADS), smem, (hipStream_t)stream, x0,
-                       x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale, iters, coef, steps,
-                       t_dev, t_imm, nullptr, nullptr, workspace, nullptr, 0, nullptr, nullptr, 0, nullptr,
-                       nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Clock g = {scale, iters, coef, steps, t_dev, t_imm};
+  return mdm::launch_canvas(ctl::PLAIN, &g, x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, ctl::Terms{}, M,
+                            F, nullptr, nullptr, workspace, stream);
 }
 
 int mdm_canvas_scene_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
                                const float* std, const float* targets, const float* weights, const float* scene, int32_t K,
                                const float* joint_params, int32_t M, int32_t F, float* loss_out, float* grad_out,
                                float* workspace, void* stream) {
-  if (!x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !loss_out || !grad_out || !workspace ||
-      !targets != !weights)
-    return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::canvas_joints(F);
-  if (J == 0 || M < 0) return MDM_ERR_ARG;
-  if (K == 0 && targets)  // no scene: the launch of mdm_canvas_joint_loss_grad
-    return mdm_canvas_joint_loss_grad(x0, motion_offsets, frame_rows, mean, std, targets, weights, M, F, loss_out, grad_out,
-                                      workspace, stream);
-  if (M == 0) return MDM_OK;
-  const size_t smem = mdm::canvas_lds_bytes(J, K);
-  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
-                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std,
-                     targets, weights, F, J, 0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, scene, K,
-                     joint_params, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params};
+  return mdm::launch_canvas(ctl::SCENE, nullptr, nullptr, const_cast<float*>(x0), nullptr, motion_offsets, frame_rows, mean, std,
+                            targets, weights, o, M, F, loss_out, grad_out, workspace, stream);
 }
 
 int mdm_canvas_scene_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
@@ -491,57 +456,19 @@ int mdm_canvas_scene_guidance(float* x, float* x0, const float* mask, const int3
                               const float* scene, int32_t K, const float* joint_params, int32_t M, int32_t F, float scale,
                               int32_t iters, const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm,
                               float* workspace, void* stream) {
-  if (!x || !x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !coef || !workspace ||
-      !targets != !weights)
-    return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::canvas_joints(F);
-  if (J == 0 || M < 0) return MDM_ERR_ARG;
-  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
-  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
-  if (K == 0 && targets)  // no scene: the launch of mdm_canvas_joint_guidance
-    return mdm_canvas_joint_guidance(x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, M, F, scale, iters,
-                                     coef, steps, t_dev, t_imm, workspace, stream);
-  if (M == 0) return MDM_OK;
-  const size_t smem = mdm::canvas_lds_bytes(J, K);
-  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
-  if (mask)
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
-                       (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale,
-                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, nullptr, 0, nullptr,
-                       nullptr, nullptr, 0, nullptr);
-  else
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
-                       (hipStream_t)stream, x0, x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
-                       scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, nullptr, 0,
-                       nullptr, nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params};
+  const ctl::Clock g = {scale, iters, coef, steps, t_dev, t_imm};
+  return mdm::launch_canvas(ctl::SCENE, &g, x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, o, M, F, nullptr,
+                            nullptr, workspace, stream);
 }
 
 int mdm_canvas_tracks_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
                                 const float* std, const float* targets, const float* weights, const float* scene, int32_t K,
                                 const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds, int32_t M,
                                 int32_t F, float* loss_out, float* grad_out, float* workspace, void* stream) {
-  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
-  if (Km == 0)  // no tracks: the launch of mdm_canvas_scene_loss_grad
-    return mdm_canvas_scene_loss_grad(x0, motion_offsets, frame_rows, mean, std, targets, weights, scene, K, joint_params, M, F,
-                                      loss_out, grad_out, workspace, stream);
-  if (!x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !loss_out || !grad_out || !workspace ||
-      !targets != !weights)
-    return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::canvas_joints(F);
-  if (J == 0 || M < 0) return MDM_ERR_ARG;
-  if (M == 0) return MDM_OK;
-  const size_t smem = mdm::canvas_lds_bytes(J, K);
-  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
-                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std,
-                     targets, weights, F, J, 0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, scene, K,
-                     joint_params, tracks, Km, track_bounds, nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params, tracks, Km, track_bounds};
+  return mdm::launch_canvas(ctl::TRACKS, nullptr, nullptr, const_cast<float*>(x0), nullptr, motion_offsets, frame_rows, mean, std,
+                            targets, weights, o, M, F, loss_out, grad_out, workspace, stream);
 }
 
 int mdm_canvas_tracks_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
@@ -549,33 +476,10 @@ int mdm_canvas_tracks_guidance(float* x, float* x0, const float* mask, const int
                                const float* scene, int32_t K, const float* joint_params, const float* tracks, int32_t Km,
                                const float* track_bounds, int32_t M, int32_t F, float scale, int32_t iters, const float* coef,
                                int32_t steps, const int32_t* t_dev, int32_t t_imm, float* workspace, void* stream) {
-  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
-  if (Km == 0)  // no tracks: the launch of mdm_canvas_scene_guidance
-    return mdm_canvas_scene_guidance(x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, scene, K, joint_params,
-                                     M, F, scale, iters, coef, steps, t_dev, t_imm, workspace, stream);
-  if (!x || !x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !coef || !workspace ||
-      !targets != !weights)
-    return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::canvas_joints(F);
-  if (J == 0 || M < 0) return MDM_ERR_ARG;
-  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
-  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
-  if (M == 0) return MDM_OK;
-  const size_t smem = mdm::canvas_lds_bytes(J, K);
-  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
-  if (mask)
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
-                       (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale,
-                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
-                       track_bounds, nullptr, nullptr, 0, nullptr);
-  else
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
-                       (hipStream_t)stream, x0, x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
-                       scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
-                       track_bounds, nullptr, nullptr, 0, nullptr);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params, tracks, Km, track_bounds};
+  const ctl::Clock g = {scale, iters, coef, steps, t_dev, t_imm};
+  return mdm::launch_canvas(ctl::TRACKS, &g, x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, o, M, F, nullptr,
+                            nullptr, workspace, stream);
 }
 
 int mdm_canvas_terrain_loss_grad(const float* x0, const int32_t* motion_offsets, const int32_t* frame_rows, const float* mean,
@@ -583,26 +487,9 @@ int mdm_canvas_terrain_loss_grad(const float* x0, const int32_t* motion_offsets,
                                  const float* joint_params, const float* tracks, int32_t Km, const float* track_bounds,
                                  const float* terrain, const float* terrain_rec, int32_t Gx, int32_t Gz, const float* stand,
                                  int32_t M, int32_t F, float* loss_out, float* grad_out, float* workspace, void* stream) {
-  if (!terrain)  // no terrain: the launch of mdm_canvas_tracks_loss_grad
-    return mdm_canvas_tracks_loss_grad(x0, motion_offsets, frame_rows, mean, std, targets, weights, scene, K, joint_params, tracks,
-                                       Km, track_bounds, M, F, loss_out, grad_out, workspace, stream);
-  if (!mdm::terrain::terrain_ok(terrain, terrain_rec, Gx, Gz, stand)) return MDM_ERR_ARG;
-  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
-  if (!x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !loss_out || !grad_out || !workspace ||
-      !targets != !weights)
-    return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::canvas_joints(F);
-  if (J == 0 || M < 0) return MDM_ERR_ARG;
-  if (M == 0) return MDM_OK;
-  const size_t smem = mdm::canvas_lds_bytes(J, K);
-  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((mdm::canvas_control_kernel<false, false, true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
-                     (hipStream_t)stream, const_cast<float*>(x0), nullptr, nullptr, motion_offsets, frame_rows, mean, std,
-                     targets, weights, F, J, 0.f, 1, nullptr, 1, nullptr, 0, loss_out, grad_out, workspace, scene, K,
-                     joint_params, tracks, Km, track_bounds, terrain, terrain_rec, Gx | Gz << 16, stand);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params, tracks, Km, track_bounds, terrain, terrain_rec, Gx, Gz, stand};
+  return mdm::launch_canvas(ctl::TERRAIN, nullptr, nullptr, const_cast<float*>(x0), nullptr, motion_offsets, frame_rows, mean,
+                            std, targets, weights, o, M, F, loss_out, grad_out, workspace, stream);
 }
 
 int mdm_canvas_terrain_guidance(float* x, float* x0, const float* mask, const int32_t* motion_offsets, const int32_t* frame_rows,
@@ -612,34 +499,10 @@ int mdm_canvas_terrain_guidance(float* x, float* x0, const float* mask, const in
                                 int32_t Gz, const float* stand, int32_t M, int32_t F, float scale, int32_t iters,
                                 const float* coef, int32_t steps, const int32_t* t_dev, int32_t t_imm, float* workspace,
                                 void* stream) {
-  if (!terrain)  // no terrain: the launch of mdm_canvas_tracks_guidance
-    return mdm_canvas_tracks_guidance(x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, scene, K, joint_params,
-                                      tracks, Km, track_bounds, M, F, scale, iters, coef, steps, t_dev, t_imm, workspace, stream);
-  if (!mdm::terrain::terrain_ok(terrain, terrain_rec, Gx, Gz, stand)) return MDM_ERR_ARG;
-  if (!mdm::scene::tracks_ok(tracks, Km, track_bounds)) return MDM_ERR_ARG;
-  if (!x || !x0 || !motion_offsets || !frame_rows || !mean || !std || !joint_params || !coef || !workspace ||
-      !targets != !weights)
-    return MDM_ERR_ARG;
-  if (K < 0 || K > MDM_SCENE_MAX_PRIMS || (K > 0 && !scene)) return MDM_ERR_ARG;
-  const int J = mdm::canvas_joints(F);
-  if (J == 0 || M < 0) return MDM_ERR_ARG;
-  if (iters < 1 || iters > MDM_CONTROL_MAX_ITERS || !std::isfinite(scale)) return MDM_ERR_ARG;
-  if (steps <= 0 || (!t_dev && (t_imm < 0 || t_imm >= steps))) return MDM_ERR_ARG;
-  if (M == 0) return MDM_OK;
-  const size_t smem = mdm::canvas_lds_bytes(J, K);
-  if (smem > 60 * 1024) return MDM_ERR_UNSUPPORTED;
-  if (mask)
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, true, true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
-                       (hipStream_t)stream, x0, x, mask, motion_offsets, frame_rows, mean, std, targets, weights, F, J, scale,
-                       iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
-                       track_bounds, terrain, terrain_rec, Gx | Gz << 16, stand);
-  else
-    hipLaunchKernelGGL((mdm::canvas_control_kernel<true, false, true, true, true>), dim3(M), dim3(mdm::CV_THREADS), smem,
-                       (hipStream_t)stream, x0, x, nullptr, motion_offsets, frame_rows, mean, std, targets, weights, F, J,
-                       scale, iters, coef, steps, t_dev, t_imm, nullptr, nullptr, workspace, scene, K, joint_params, tracks, Km,
-                       track_bounds, terrain, terrain_rec, Gx | Gz << 16, stand);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  return MDM_OK;
+  const ctl::Terms o = {scene, K, joint_params, tracks, Km, track_bounds, terrain, terrain_rec, Gx, Gz, stand};
+  const ctl::Clock g = {scale, iters, coef, steps, t_dev, t_imm};
+  return mdm::launch_canvas(ctl::TERRAIN, &g, x, x0, mask, motion_offsets, frame_rows, mean, std, targets, weights, o, M, F,
+                            nullptr, nullptr, workspace, stream);
 }
 
 }  // extern "C"

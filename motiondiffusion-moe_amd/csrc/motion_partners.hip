@@ -14,6 +14,7 @@
 //   3. partner_contacts_kernel: one thread per (contact, frame): the meeting point in the world, written into both
 //      characters' targets in their own frames.
 // Records and targets are data: nothing here is differentiated.  No atomics, no allocation, stream-ordered.
+#include "joint_control.h"
 #include "kernels.h"
 
 #include <cmath>
@@ -174,8 +175,8 @@ __global__ __launch_bounds__(CONTACT_THREADS) void partner_contacts_kernel(const
 extern "C" int mdm_partner_tracks_max_frames(void) { return 64 * 1024 / (5 * (int)sizeof(float)); }
 
 extern "C" int64_t mdm_partner_tracks_scratch_floats(int32_t B, int32_t T, int32_t F) {
-  if (B < 0 || T < 0 || F < 11 || (F + 1) % 12) return 0;
-  const int64_t J = (F + 1) / 12, D = 3 * J + 1;
+  const int64_t J = mdm::control::control_joints(F), D = 3 * J + 1;
+  if (B < 0 || T < 0 || J == 0) return 0;
   return (int64_t)B * T * (D + 3 * J) + 2 * D;
 }
 
@@ -188,7 +189,7 @@ extern "C" int mdm_partner_tracks(const float* x0, const int32_t* length, const 
   if (!x0 || !length || !mean || !std || !placements || !world || !scratch || B < 0 || T < 0) return MDM_ERR_ARG;
   if (Km < 0 || Km > MDM_SCENE_MAX_TRACKS || Ks < 0 || Pm < 0 || nb < 0 || Nc < 0) return MDM_ERR_ARG;
   if ((int64_t)Ks + (int64_t)Pm * nb != Km) return MDM_ERR_ARG;
-  const int J = (F + 1) % 12 == 0 && F >= 11 ? (F + 1) / 12 : 0;
+  const int J = mdm::control::control_joints(F);
   if (J == 0) return MDM_ERR_ARG;
   if ((uintptr_t)placements & 15) return MDM_ERR_ARG;
   if (Km > 0 && (!tracks || !track_bounds || ((uintptr_t)tracks & 15) || ((uintptr_t)track_bounds & 15))) return MDM_ERR_ARG;

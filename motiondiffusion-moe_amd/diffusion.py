@@ -598,6 +598,23 @@ _COEF_KIND = {"cfg_ddim": "ddim", "cfg_dpmpp": "dpmpp"}
 _EDIT_COEF_KIND = {"cfg": "ddpm", "ddpm": "ddpm", "ddim": "ddim", "cfg_ddim": "ddim", "cfg_dpmpp": "dpmpp"}
 
 
+def _guidance_entry(family, c):
+    """The guidance entry of a control dict ``c`` over a window (``family`` "joint") or a canvas ("canvas"), and its
+    optional arguments between the weights and the sizes: the lowest entry whose signature carries what ``c`` holds, a scene
+    ("K"), tracks ("Km", §25), a terrain (§29, on top of the tracks arguments)."""
+    p = L.ptr
+    terms = (p(c["scene"]), c["K"], p(c["joint_params"])) if "K" in c else ()
+    if "Km" in c:
+        terms += (p(c["tracks"]), c["Km"], p(c["track_bounds"]))
+    level = "_tracks" if "Km" in c else "_scene" if terms else "_joint" if family == "canvas" else ""
+    if "terrain" in c:
+        if "Km" not in c:
+            terms += (0, 0, 0)
+        terms += (p(c["terrain"]), p(c["terrain_rec"]), c["Gx"], c["Gz"], p(c["stand"]))
+        level = "_terrain"
+    return f"mdm_{family}{level}_guidance", terms
+
+
 class _StepRunner:
     """Static buffers + (optionally) one captured hipGraph for a whole denoising step.  Which forward and which update
     entry a step launches follows from the mode and the ``model_kwargs``: both are decided once, at construction."""
@@ -859,10 +876,10 @@ class _StepRunner:
 
     def _plan_update(self):
         """The update of a step, ``(entry name, arguments before the noise pointer, arguments after it)``, and the
-        entry and arguments of the joint guidance, mdm_joint_guidance, with a scene mdm_joint_scene_guidance, with tracks
-        mdm_joint_tracks_guidance, with a terrain mdm_joint_terrain_guidance (None without control).  Every pointer belongs
-        to a buffer the runner owns for its lifetime; the noise pointer and the stream are the launch's.  Plain "cfg" / "ddpm" keep mdm_cfg_posterior_step and
-        plain "ddim" mdm_ddim_step; with a coefficient table the three fused entries share their head and tail."""
+        entry and arguments of the joint guidance (``_guidance_entry``; None without control); the canvas guidance goes to
+        ``_guide_canvas``.  Every pointer belongs to a buffer the runner owns for its lifetime; the noise pointer and the
+        stream are the launch's.  Plain "cfg" / "ddpm" keep mdm_cfg_posterior_step and plain "ddim" mdm_ddim_step; with a
+        coefficient table the three fused entries share their head and tail."""
         p = L.ptr
         x, eps, x0 = p(self.xx), p(self.eps), p(self.x0)  # x_t is rows [0, B) of xx, updated in place
         eps_u = p(self.eps[self.B:] if self.mode in _GUIDED else None)
@@ -871,32 +888,16 @@ class _StepRunner:
         guide = None
         if self.ctl is not None:
             c = self.ctl
-            scene = (p(c["scene"]), c["K"], p(c["joint_params"])) if "K" in c else ()
-            if "Km" in c:  # with tracks
-                scene += (p(c["tracks"]), c["Km"], p(c["track_bounds"]))
-            name = "mdm_joint_tracks_guidance" if "Km" in c else "mdm_joint_scene_guidance" if scene else "mdm_joint_guidance"
-            if "terrain" in c:  # with a terrain, on top of the tracks arguments
-                if "Km" not in c:
-                    scene += (0, 0, 0)
-                scene += (p(c["terrain"]), p(c["terrain_rec"]), c["Gx"], c["Gz"], p(c["stand"]))
-                name = "mdm_joint_terrain_guidance"
-            guide = (name, (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"])) + scene
+            name, terms = _guidance_entry("joint", c)
+            guide = (name, (x, x0, p(self.mask), p(c["len"]), p(c["mean"]), p(c["std"]), p(c["targets"]), p(c["weights"])) + terms
                      + (self.B, self.T, self.Fe, c["scale"], c["iters"], p(self.coef)) + clock)
         self._guide_canvas = None  # the entry and arguments of the canvas guidance (None without canvas control)
         if self.cctl is not None:
             c = self.cctl
-            scene = (p(c["scene"]), c["K"], p(c["joint_params"])) if "K" in c else ()
-            if "Km" in c:
-                scene += (p(c["tracks"]), c["Km"], p(c["track_bounds"]))
-            name = "mdm_canvas_tracks_guidance" if "Km" in c else "mdm_canvas_scene_guidance" if scene else "mdm_canvas_joint_guidance"
-            if "terrain" in c:
-                if "Km" not in c:
-                    scene += (0, 0, 0)
-                scene += (p(c["terrain"]), p(c["terrain_rec"]), c["Gx"], c["Gz"], p(c["stand"]))
-                name = "mdm_canvas_terrain_guidance"
+            name, terms = _guidance_entry("canvas", c)
             self._guide_canvas = (name,
                                   (x, x0, p(self.mask), p(c["offsets"]), p(c["rows"]), p(c["mean"]), p(c["std"]),
-                                   p(c["targets"]), p(c["weights"])) + scene
+                                   p(c["targets"]), p(c["weights"])) + terms
                                   + (c["M"], self.Fe, c["scale"], c["iters"], p(self.coef)) + clock + (p(c["ws"]),))
         if self.coef is None and self.mode == "ddim":
             return ("mdm_ddim_step", (x, eps), (self.n, p(self.tab)) + clock + (self.eta,) + out), guide

@@ -758,6 +758,27 @@ def _track_args(tracks, N, T, lengths, bounds, dev):
     return trk.to(dev).contiguous(), bnd
 
 
+def _target_args(targets, weights, shape, dev):
+    """The targets of ``shape`` and the weights broadcast to it on the device, or (None, None) without either."""
+    if (targets is None) != (weights is None):
+        raise ValueError("targets and weights go together: give both or neither")
+    if targets is None:
+        return None, None
+    tg = torch.as_tensor(targets).to(dev, torch.float32).contiguous()
+    if tuple(tg.shape) != shape:
+        raise ValueError(f"targets of shape {tuple(tg.shape)} must be {shape}")
+    return tg, torch.broadcast_to(torch.as_tensor(weights).to(dev, torch.float32), shape).contiguous()
+
+
+def _loss_grad(family, head, tail, trk=None, bnd=None, ground=()):
+    """One call of mdm_{family}_{scene|tracks|terrain}_loss_grad, the lowest entry whose signature carries what is given:
+    ``head`` up to the joint parameters, the (..., Km, REC) track records ``trk`` and their balls, the terrain arguments
+    ``ground`` (on top of the tracks arguments), ``tail`` from the sizes on."""
+    mid = () if trk is None else (trk.data_ptr() if trk.shape[-2] else 0, trk.shape[-2], L.ptr(bnd))
+    name = f"mdm_{family}_{'terrain' if ground else 'scene' if trk is None else 'tracks'}_loss_grad"
+    L.check(getattr(L.lib(), name)(*head, *mid, *ground, *tail), name)
+
+
 @torch.no_grad()
 def scene_loss_grad(x0: torch.Tensor, lengths, mean, std, scene, joint_radius=None, joint_weights=None, targets=None,
                     weights=None, tracks=None, bounds=True, terrain=None, stand=None):
@@ -782,14 +803,7 @@ def scene_loss_grad(x0: torch.Tensor, lengths, mean, std, scene, joint_radius=No
     K = rec.shape[1]
     if not 1 <= T <= max_frames(F, K):
         raise ValueError(f"T = {T}: with {K} primitives the control kernels take 1 to {max_frames(F, K)} frames at F = {F}")
-    if (targets is None) != (weights is None):
-        raise ValueError("targets and weights go together: give both or neither")
-    tg = w = None
-    if targets is not None:
-        tg = torch.as_tensor(targets).to(dev, torch.float32).contiguous()
-        if tuple(tg.shape) != (B, T, J, 3):
-            raise ValueError(f"targets of shape {tuple(tg.shape)} must be {(B, T, J, 3)}")
-        w = torch.broadcast_to(torch.as_tensor(weights).to(dev, torch.float32), (B, T, J, 3)).contiguous()
+    tg, w = _target_args(targets, weights, (B, T, J, 3), dev)
     mean_t = _rows(mean, B, F, "mean").to(dev).contiguous()
     std_t = _rows(std, B, F, "std").to(dev).contiguous()
     ln = torch.as_tensor(lengths).to(dev, torch.int32).contiguous()
@@ -801,16 +815,11 @@ def scene_loss_grad(x0: torch.Tensor, lengths, mean, std, scene, joint_radius=No
             jp.data_ptr())
     tail = (B, T, F, loss.data_ptr(), grad.data_ptr(), L.stream_ptr())
     with torch.cuda.device(dev):
-        if tracks is None and terrain is None:
-            L.check(L.lib().mdm_joint_scene_loss_grad(*head, *tail), "mdm_joint_scene_loss_grad")
-            return loss, grad
-        trk, bnd = _track_args([] if tracks is None else tracks, B, T, ln.cpu(), bounds, dev)
-        mid = (trk.data_ptr() if trk.shape[2] else 0, trk.shape[2], L.ptr(bnd))
-        if terrain is None:
-            L.check(L.lib().mdm_joint_tracks_loss_grad(*head, *mid, *tail), "mdm_joint_tracks_loss_grad")
-        else:
-            keep, ground = _terrain_args(terrain, stand, B, (B, T, J), dev)
-            L.check(L.lib().mdm_joint_terrain_loss_grad(*head, *mid, *ground, *tail), "mdm_joint_terrain_loss_grad")
+        trk = bnd = None
+        if tracks is not None or terrain is not None:
+            trk, bnd = _track_args([] if tracks is None else tracks, B, T, ln.cpu(), bounds, dev)
+        keep, ground = ((), ()) if terrain is None else _terrain_args(terrain, stand, B, (B, T, J), dev)
+        _loss_grad("joint", head, tail, trk, bnd, ground)
     return loss, grad
 
 
@@ -840,14 +849,7 @@ def canvas_scene_loss_grad(rows: torch.Tensor, motion_offsets, frame_rows, mean,
         raise ValueError(f"frame_rows must be distinct rows in [0, {x.shape[0]})")
     rec, jp = _scene_args([] if scene is None else scene, M, J, joint_radius, joint_weights, dev)
     K = rec.shape[1]
-    if (targets is None) != (weights is None):
-        raise ValueError("targets and weights go together: give both or neither")
-    tg = w = None
-    if targets is not None:
-        tg = torch.as_tensor(targets).to(dev, torch.float32).contiguous()
-        if tuple(tg.shape) != (total, J, 3):
-            raise ValueError(f"targets of shape {tuple(tg.shape)} must be {(total, J, 3)}")
-        w = torch.broadcast_to(torch.as_tensor(weights).to(dev, torch.float32), (total, J, 3)).contiguous()
+    tg, w = _target_args(targets, weights, (total, J, 3), dev)
     mean_t = _rows(mean, M, F, "mean").to(dev).contiguous()
     std_t = _rows(std, M, F, "std").to(dev).contiguous()
     off_d, fr_d = off.to(dev, torch.int32), fr.to(dev, torch.int32)
@@ -858,18 +860,13 @@ def canvas_scene_loss_grad(rows: torch.Tensor, motion_offsets, frame_rows, mean,
             rec.data_ptr() if K else 0, K, jp.data_ptr())
     tail = (M, F, loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), L.stream_ptr())
     with torch.cuda.device(dev):
-        if tracks is None and terrain is None:
-            L.check(L.lib().mdm_canvas_scene_loss_grad(*head, *tail), "mdm_canvas_scene_loss_grad")
-            return loss, grad
-        trk = canvas_tracks([[] for _ in range(M)] if tracks is None else tracks, off)
-        bnd = track_bounds(trk).to(dev).contiguous() if bounds and trk.shape[1] else None
-        trk = trk.to(dev).contiguous()
-        mid = (trk.data_ptr() if trk.shape[1] else 0, trk.shape[1], L.ptr(bnd))
-        if terrain is None:
-            L.check(L.lib().mdm_canvas_tracks_loss_grad(*head, *mid, *tail), "mdm_canvas_tracks_loss_grad")
-        else:
-            keep, ground = _terrain_args(terrain, stand, M, (total, J), dev)
-            L.check(L.lib().mdm_canvas_terrain_loss_grad(*head, *mid, *ground, *tail), "mdm_canvas_terrain_loss_grad")
+        trk = bnd = None
+        if tracks is not None or terrain is not None:
+            trk = canvas_tracks([[] for _ in range(M)] if tracks is None else tracks, off)
+            bnd = track_bounds(trk).to(dev).contiguous() if bounds and trk.shape[1] else None
+            trk = trk.to(dev).contiguous()
+        keep, ground = ((), ()) if terrain is None else _terrain_args(terrain, stand, M, (total, J), dev)
+        _loss_grad("canvas", head, tail, trk, bnd, ground)
     return loss, grad
 
 
