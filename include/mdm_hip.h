@@ -69,7 +69,12 @@ typedef struct MdmOperand {
  *   v = alpha * (acc + bias[n]);  v = act(v);  v *= out_scale * colscale[n] * rowscale[m];
  *   v += r1_scale * R1[m (mod r1_mod), n] + R2[m, n]
  * Replaces every nn.Linear / einsum on the path (transformer.py:319-360, fast_attention.py:59-78,
- * 145-147,165,248-253,305-329, switch_moe.py:104, stylization.py:26-30). */
+ * 145-147,165,248-253,305-329, switch_moe.py:104, stylization.py:26-30).
+ * Alignment: when ldc, ldr1 and ldr2 are all multiples of 4 the MFMA tile kernels move four columns per lane, so C, R1, R2 must then be
+ * 16-byte aligned, C16 / C16_lo 8-byte and C8 4-byte aligned, and with batch > 1 c_bs1 / c_bs2 multiples of 4; a launch that
+ * only those kernels can run (16-bit, pre-split or fp8 rows, plane / Cx2 outputs) returns MDM_ERR_UNSUPPORTED otherwise and writes
+ * nothing, a Linear on fp32 rows runs on the element-wise kernel.  With an odd leading dimension any 4-byte (C16: 2-byte) aligned
+ * base is taken.  A.p of 16-bit, pre-split and fp8 rows is 16-byte aligned with A.ld * element size a multiple of 16. */
 typedef struct MdmGemmDesc {
   MdmOperand A, W;
   int32_t M, N, K;
@@ -131,7 +136,9 @@ int mdm_gemm(const MdmGemmDesc* desc, void* stream);
  * (switch_moe.py:19-25, grouped by goff with per-expert strides w?_gs / b?_gs), the 4x FFN of the text cross-attention
  * block (fast_attention.py:293-299) and the Performer output projection (fast_attention.py:121-126).
  * Supported shapes: Dout == 512, Din % 64 == 0, F % 256 == 0 (LDS-staged kernel); with a weight stream (below) Dout == 512 and
- * Din in {128, 256, 512}, or Dout == Din == 1024; anything else returns MDM_ERR_UNSUPPORTED. */
+ * Din in {128, 256, 512}, or Dout == Din == 1024; anything else returns MDM_ERR_UNSUPPORTED.
+ * Both kernels move 16 bytes per lane: X, C, R1, R2, b1, b2 must be 16-byte aligned (C16 8-byte), ldx a multiple of 8, ldc / ldr1 /
+ * ldr2 and b1_gs / b2_gs multiples of 4; otherwise MDM_ERR_UNSUPPORTED before any launch, and nothing is written. */
 typedef struct MdmMlpDesc {
   const uint16_t* X; /* bf16 rows [*, Din] */
   int64_t ldx;

@@ -49,6 +49,17 @@ inline Operand op_bf16(const uint16_t* hi, const uint16_t* lo, int64_t ld) {
   return o;
 }
 
+// The tile kernels (gemm2 / gemm3 / gemm4 / gemm8.hip) choose their epilogue by the leading dimensions alone: with ldc, ldr1 and ldr2
+// multiples of 4 a lane moves four columns at once -- 16 bytes of C / R1 / R2, 8 of C16 / C16_lo, 4 of C8 -- so the bases (batch
+// strides included) must be aligned alike (include/mdm_hip.h).  With an odd leading dimension the element-wise path takes any base.
+inline bool epilogue_bases_aligned(const GemmArgs& a) {
+  if ((a.ldc & 3) || (a.R1 && (a.ldr1 & 3)) || (a.R2 && (a.ldr2 & 3))) return true;
+  if ((((uintptr_t)a.C) | ((uintptr_t)a.R1) | ((uintptr_t)a.R2)) & 15) return false;
+  if ((((uintptr_t)a.C16) | ((uintptr_t)a.C16_lo)) & 7) return false;
+  if (((uintptr_t)a.C8) & 3) return false;
+  return a.batch <= 1 || ((a.c_bs1 | a.c_bs2) & 3) == 0;
+}
+
 int gemm(const GemmArgs& a, hipStream_t stream);
 bool gemm_bf16_eligible(const GemmArgs& a);
 int gemm_bf16(const GemmArgs& a, hipStream_t stream);  // gemm2.hip: bf16 x bf16 throughput kernel

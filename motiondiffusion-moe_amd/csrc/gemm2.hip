@@ -307,7 +307,7 @@ constexpr int BIG_MIN_TILES = 352;  // 256 x 256 tiles at K >= 2048 from this ma
 bool gemm_bf16_eligible(const GemmArgs& a) {
   return a.precision == 1 && a.A.kind == OP_BF16_ROW && a.W.kind == OP_BF16_ROW && a.K > 0 && (a.K % 64) == 0 &&
          (a.A.ld % 8) == 0 && (a.W.ld % 8) == 0 && (a.A.bs1 % 8) == 0 && (a.A.bs2 % 8) == 0 &&
-         ((((uintptr_t)a.A.p) | ((uintptr_t)a.W.p)) & 15) == 0 && a.A.rpg == 0;
+         ((((uintptr_t)a.A.p) | ((uintptr_t)a.W.p)) & 15) == 0 && a.A.rpg == 0 && epilogue_bases_aligned(a);
 }
 
 template <typename HT, int BM, int BK, int NS, int ACT>

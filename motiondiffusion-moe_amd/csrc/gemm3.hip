@@ -374,7 +374,7 @@ bool gemm_x3_dma_eligible(const GemmArgs& a) {
   const bool base = a.precision == 3 && (a.A.kind == OP_F32_ROW || a.A.kind == OP_X2_ROW) && a.W.kind == OP_BF16_ROW && a.W.p_lo && a.batch == 1 && a.A.rpg == 0 &&
                     a.K >= 32 && (a.K % 32) == 0 && (a.A.ld % 4) == 0 && (a.W.ld % 8) == 0 && (a.W.bs1 % 8) == 0 &&
                     ((((uintptr_t)a.A.p) | ((uintptr_t)a.W.p) | ((uintptr_t)a.W.p_lo)) & 15) == 0 && a.M >= 1;
-  if (!base) return false;
+  if (!base || !epilogue_bases_aligned(a)) return false;
   // hi / lo plane outputs: whole 128-column slices, vector stores, no fp32 copy
   const bool planes_ok = a.C16 && a.C16_lo && !a.C && a.N % 128 == 0 && (a.ldc % 4) == 0 && (!a.R1 || (a.ldr1 & 3) == 0) &&
                          (!a.R2 || (a.ldr2 & 3) == 0) && ((((uintptr_t)a.C16) | ((uintptr_t)a.C16_lo)) & 7) == 0;

@@ -206,7 +206,7 @@ bool gemm_bf16_256_eligible(const GemmArgs& a) {
   if (!(a.precision == 1 && a.A.kind == OP_BF16_ROW && a.W.kind == OP_BF16_ROW)) return false;
   if (a.batch != 1 || a.A.rpg || a.K < BK || (a.K % BK) || (a.N % BN)) return false;
   if ((a.A.ld % 8) || (a.W.ld % 8) || (a.W.bs1 % 8) || ((((uintptr_t)a.A.p) | ((uintptr_t)a.W.p)) & 15)) return false;
-  if ((a.ldc & 3) || (a.R1 && (a.ldr1 & 3)) || (a.R2 && (a.ldr2 & 3))) return false;
+  if ((a.ldc & 3) || (a.R1 && (a.ldr1 & 3)) || (a.R2 && (a.ldr2 & 3)) || !epilogue_bases_aligned(a)) return false;
   if (a.act != ACT_NONE && a.act != ACT_GELU && a.act != ACT_SILU) return false;
   if (a.bias && ((((uintptr_t)a.bias) & 15) || (a.bias_bs & 3))) return false;
   if (a.colscale && (((uintptr_t)a.colscale) & 15)) return false;

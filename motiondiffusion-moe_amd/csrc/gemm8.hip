@@ -225,7 +225,7 @@ int launch8(const GemmArgs& a, hipStream_t stream) {
 bool gemm_fp8_eligible(const GemmArgs& a) {
   return a.A.kind == MDM_OP_FP8_ROW && a.W.kind == MDM_OP_FP8_ROW && a.K >= BKB && (a.K % BKB) == 0 && (a.A.ld % 16) == 0 &&
          (a.W.ld % 16) == 0 && (a.W.bs1 % 16) == 0 && ((((uintptr_t)a.A.p) | ((uintptr_t)a.W.p)) & 15) == 0 && a.batch == 1 &&
-         !a.R1 && !a.R2 && !a.colscale && (a.act == ACT_NONE || a.act == ACT_GELU) && a.alpha == 1.f;
+         !a.R1 && !a.R2 && !a.colscale && (a.act == ACT_NONE || a.act == ACT_GELU) && a.alpha == 1.f && epilogue_bases_aligned(a);
 }
 
 int gemm_fp8(const GemmArgs& a, hipStream_t stream) {

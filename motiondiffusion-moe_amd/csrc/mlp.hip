@@ -261,6 +261,7 @@ bool fused_mlp_supported(const MdmMlpDesc& a) {
   if ((a.ldx % 8) || (a.ldw1 % 8) || (a.ldw2 % 8) || (a.w1_gs % 8) || (a.w2_gs % 8)) return false;
   if (((((uintptr_t)a.X) | ((uintptr_t)a.w1) | ((uintptr_t)a.w2)) & 15)) return false;
   if ((a.ldc & 3) || (a.R1 && (a.ldr1 & 3)) || (a.R2 && (a.ldr2 & 3))) return false;
+  if (((((uintptr_t)a.C) | ((uintptr_t)a.R1) | ((uintptr_t)a.R2)) & 15) || (((uintptr_t)a.C16) & 7)) return false;  // 16- / 8-byte row pieces
   if ((a.b1 && ((((uintptr_t)a.b1) & 15) || (a.b1_gs & 3))) || (a.b2 && ((((uintptr_t)a.b2) & 15) || (a.b2_gs & 3)))) return false;
   return true;
 }
