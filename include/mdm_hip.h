@@ -1038,6 +1038,14 @@ int mdm_route_workspace(const MdmModel* m, int32_t B, int32_t T, int32_t N, int6
  * experts' outputs times their gate probabilities in slab order (fp16 at MDM_PREC_FP8 and MDM_PREC_F16, bf16 at MDM_PREC_BF16,
  * else fp32).  Rows at or past goff[2 E] are never written. */
 int mdm_expert_workspace(const MdmModel* m, int32_t B, int32_t T, int32_t N, int64_t* off);
+/* Test aid: the sub-buffers of a workspace carved for (m, B, T, N), in carve order, from the table that carves it.  Returns
+ * their number (-1: bad model or shape); for the first `cap` of them writes the byte offset (a multiple of 256), the byte size
+ * and the kind: 0 = data (fp32, or a narrower float format in the modes that keep one there), 1 = int32 indices and counters
+ * (top_idx, perm, pos4, hist, goff, cursor, len_low).  The end of the last one, rounded up to 256, is mdm_workspace_bytes.
+ * mdm_workspace_field_name(i): the name of sub-buffer i ("" outside the table). */
+int mdm_workspace_layout(const MdmModel* m, int32_t B, int32_t T, int32_t N, int64_t* off, int64_t* bytes, int32_t* kind,
+                         int32_t cap);
+const char* mdm_workspace_field_name(int32_t i);
 /* Number of passes (of <= 128 folded text columns, whole heads) the fused text cross-attention takes for H heads and N text
  * tokens, 0 when the folded path is not taken (D != 512, or more than two passes: N > 64 at H = 4, where the GEMM chain
  * measures faster).  Sizes the optional MdmTextCache buffers:

@@ -254,6 +254,8 @@ PROTOTYPES = {
     "mdm_route_dump": (_I32, [_P, _I64]),
     "mdm_route_workspace": (_I32, [_P, _I32, _I32, _I32, _P]),
     "mdm_expert_workspace": (_I32, [_P, _I32, _I32, _I32, _P]),
+    "mdm_workspace_layout": (_I32, [_P, _I32, _I32, _I32, _P, _P, _P, _I32]),
+    "mdm_workspace_field_name": (C.c_char_p, [_I32]),
     "mdm_sd_fold_passes": (_I32, [_I32, _I32, _I32]),
     "mdm_probe_read": (_I32, [_P, _P, _I32]),
     "mdm_gru_bidir_workspace_bytes": (_I64, [_I32, _I32]),

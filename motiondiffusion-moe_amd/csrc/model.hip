@@ -1,6 +1,8 @@
 // Host-side orchestration of one denoiser forward: a straight-line sequence of stream-ordered kernel
 // launches (no allocation, no host sync) so that a whole sampling step can be captured into a hipGraph.
 // Reference arithmetic: text2motion/models/transformer.py:291-361 and the blocks it calls (cited inline).
+#include <type_traits>
+
 #include "gemm.h"
 #include "kernels.h"
 
@@ -48,50 +50,59 @@ struct Bump {  // carve the caller's workspace; with base == nullptr it only mea
   }
 };
 
+// The sub-buffers of the workspace, in carve order: X(element type, field, element count).  The counts are expressions over the
+// locals of carve() (M = B * T rows, D, F, Te = 4 D, nblk = 8 L, dh = D / H, NN = max(N, 1), BN = B * NN, smax = max(Te, 2 D)).
+// This one table declares Work, carves it, and describes it to the tests (mdm_workspace_layout / mdm_workspace_field_name).
+//   token-major activations (M rows); x?16 / h016: bf16 shadows of the fp32 residual stream, written by the producing GEMM's
+//   epilogue in the throughput mode so that the next GEMM streams bf16 straight into LDS;  top_idx .. len_low: the router;
+//   s_a .. gvtmp: the stem (B rows);  tn, kb, vb: text cache scratch
+#define MDM_WORK_FIELDS(X)                                                                                              \
+  X(float, xa, M * D) X(float, xb, M * D) X(float, h0, M * D)                                                           \
+  X(uint16_t, xa16, M * D) X(uint16_t, xb16, M * D) X(uint16_t, h016, M * D)                                            \
+  X(float, t1, M * D) X(float, t2, M * D) X(float, t3, M * D) X(float, t4, M * D) X(float, t5, M * D)                   \
+  X(float, qkv, M * 3 * D) X(float, phi, M * 2 * D) X(float, kvt, (int64_t)B * m.H * dh * dh) X(float, scr, M * m.H * NN) \
+  X(float, f1, M * 4 * D) X(float, hn, 2 * M * D) X(float, hid, 4 * M * F) X(float, y2, 4 * M * D)                      \
+  X(int, top_idx, 4 * M) X(float, top_val, 4 * M) X(int, perm, 4 * M) X(float, rowscale, 4 * M) X(int, pos4, 4 * M)    \
+  X(float, hn_scale, 2 * M)                                                                                             \
+  X(int, hist, 1024 * 32) X(float, uimp, 1024 * 64) X(int, goff, 2 * m.E + 1) X(int, cursor, 2 * m.E) X(int, len_low, B) \
+  X(float, s_a, B * smax) X(float, s_b, B * smax) X(float, s_c, B * smax) X(float, emb, B * D)                          \
+  X(float, e1, B * nblk * Te) X(float, sc, nblk * B * 2 * D) X(float, gvtmp, D)                                         \
+  X(float, tn, BN * m.Dt) X(float, kb, BN * D) X(float, vb, BN * D)
+
 struct Work {
-  // token-major activations (M = B*T rows).  x?16 / h016: bf16 shadows of the fp32 residual stream, written by the
-  // producing GEMM's epilogue in the throughput mode so that the next GEMM streams bf16 straight into LDS.
-  float *xa, *xb, *h0, *t1, *t2, *t3, *t4, *t5, *qkv, *phi, *kvt, *scr, *f1, *hn, *hid, *y2;
-  uint16_t *xa16, *xb16, *h016;
-  int *top_idx, *perm, *pos4, *hist, *goff, *cursor, *len_low;
-  float *top_val, *rowscale, *uimp, *hn_scale;
-  // stem (B rows)
-  float *s_a, *s_b, *s_c, *emb, *e1, *sc, *gvtmp;
-  // text cache scratch
-  float *tn, *kb, *vb;
+#define X(T, f, n) T* f;
+  MDM_WORK_FIELDS(X)
+#undef X
   int64_t bytes;
 };
 
-Work carve(const MdmModel& m, int B, int T, int N, void* ws) {
+#define X(T, f, n) #f,
+const char* const kWorkFieldNames[] = {MDM_WORK_FIELDS(X)};
+#undef X
+constexpr int kWorkFields = sizeof(kWorkFieldNames) / sizeof(kWorkFieldNames[0]);
+
+struct WorkLayout {  // what carve() tells mdm_workspace_layout: the first `cap` of the fields it took
+  int64_t* off;
+  int64_t* bytes;
+  int32_t* kind;  // 0 = data (fp32 or a narrower float format, by mode), 1 = int32 indices / counters
+  int cap;
+  int count = 0;
+  void add(int64_t o, int64_t b, bool is_int) {
+    if (count < cap) off[count] = o, bytes[count] = b, kind[count] = is_int ? 1 : 0;
+    ++count;
+  }
+};
+
+Work carve(const MdmModel& m, int B, int T, int N, void* ws, WorkLayout* lay = nullptr) {
   Work w;
   Bump b(ws);
   const int64_t M = (int64_t)B * T, D = m.D, F = m.F, Te = 4 * D, nblk = 8 * m.L;
-  const int dh = m.D / m.H;
-  w.xa = b.take<float>(M * D), w.xb = b.take<float>(M * D), w.h0 = b.take<float>(M * D);
-  w.xa16 = b.take<uint16_t>(M * D), w.xb16 = b.take<uint16_t>(M * D), w.h016 = b.take<uint16_t>(M * D);
-  w.t1 = b.take<float>(M * D), w.t2 = b.take<float>(M * D), w.t3 = b.take<float>(M * D);
-  w.t4 = b.take<float>(M * D), w.t5 = b.take<float>(M * D);
-  w.qkv = b.take<float>(M * 3 * D);
-  w.phi = b.take<float>(M * 2 * D);
-  w.kvt = b.take<float>((int64_t)B * m.H * dh * dh);
-  w.scr = b.take<float>(M * m.H * (N > 0 ? N : 1));
-  w.f1 = b.take<float>(M * 4 * D);
-  w.hn = b.take<float>(2 * M * D);
-  w.hid = b.take<float>(4 * M * F);
-  w.y2 = b.take<float>(4 * M * D);
-  w.top_idx = b.take<int>(4 * M), w.top_val = b.take<float>(4 * M);
-  w.perm = b.take<int>(4 * M), w.rowscale = b.take<float>(4 * M), w.pos4 = b.take<int>(4 * M);
-  w.hn_scale = b.take<float>(2 * M);
-  w.hist = b.take<int>(1024 * 32), w.uimp = b.take<float>(1024 * 64), w.goff = b.take<int>(2 * m.E + 1), w.cursor = b.take<int>(2 * m.E);
-  w.len_low = b.take<int>(B);
-  const int64_t smax = Te > 2 * D ? Te : 2 * D;
-  w.s_a = b.take<float>(B * smax), w.s_b = b.take<float>(B * smax), w.s_c = b.take<float>(B * smax);
-  w.emb = b.take<float>(B * D);
-  w.e1 = b.take<float>(B * nblk * Te);
-  w.sc = b.take<float>(nblk * B * 2 * D);
-  w.gvtmp = b.take<float>(D);
-  const int64_t BN = (int64_t)B * (N > 0 ? N : 1);
-  w.tn = b.take<float>(BN * m.Dt), w.kb = b.take<float>(BN * D), w.vb = b.take<float>(BN * D);
+  const int64_t dh = m.D / m.H, NN = N > 0 ? N : 1, BN = B * NN, smax = Te > 2 * D ? Te : 2 * D;
+#define X(Ty, f, cnt)       \
+  w.f = b.take<Ty>(cnt);    \
+  if (lay) lay->add(b.off - (int64_t)(cnt) * (int64_t)sizeof(Ty), (int64_t)(cnt) * (int64_t)sizeof(Ty), std::is_same<Ty, int>::value);
+  MDM_WORK_FIELDS(X)
+#undef X
   w.bytes = (b.off + 255) & ~(int64_t)255;
   return w;
 }
@@ -1332,6 +1343,16 @@ int mdm_expert_workspace(const MdmModel* m, int32_t B, int32_t T, int32_t N, int
   for (int i = 0; i < 3; ++i) off[i] = (const uint8_t*)p[i] - base;
   return MDM_OK;
 }
+
+int mdm_workspace_layout(const MdmModel* m, int32_t B, int32_t T, int32_t N, int64_t* off, int64_t* bytes, int32_t* kind,
+                         int32_t cap) {
+  if (check_model(m) != MDM_OK || B <= 0 || T <= 0 || cap < 0 || (cap > 0 && (!off || !bytes || !kind))) return -1;
+  WorkLayout lay{off, bytes, kind, cap};
+  carve(*m, B, T, N, nullptr, &lay);  // (measuring mode: nothing is dereferenced)
+  return lay.count;
+}
+
+const char* mdm_workspace_field_name(int32_t i) { return i >= 0 && i < kWorkFields ? kWorkFieldNames[i] : ""; }
 
 int mdm_route_dump(int32_t* buf, int64_t capacity) {
   if (buf && capacity <= 0) return MDM_ERR_ARG;

@@ -401,13 +401,19 @@ class MotionTransformer(nn.Module):
             fr = forced_routing.to(device=dev, dtype=torch.int32).contiguous()
             if fr.numel() and (int(fr.min()) < 0 or int(fr.max()) >= self.moe_num_experts):  # test hook, host-checked
                 raise ValueError("forced_routing holds expert indices outside [0, moe_num_experts)")
-        tr = torch.zeros((2 * self.num_layers, 4, B * T, self.latent_dim), dtype=torch.float32, device=dev) if trace else None
+        tr_shape = (2 * self.num_layers, 4, B * T, self.latent_dim)
+        if torch.is_tensor(trace):  # the caller's own buffer, like `out`
+            if trace.dtype != torch.float32 or trace.device != dev or not trace.is_contiguous() or tuple(trace.shape) != tr_shape:
+                raise ValueError(f"trace must be a contiguous float32 tensor of shape {tr_shape} on {dev}")
+            tr = trace.zero_()
+        else:
+            tr = torch.zeros(tr_shape, dtype=torch.float32, device=dev) if trace else None
         with torch.cuda.device(dev):
             L.check(L.lib().mdm_denoiser_forward(
                 C.byref(pm.model), C.byref(tcache["tc"]), x.data_ptr(), ts.data_ptr(), ln.data_ptr(), xp.data_ptr(), B, T,
                 out.data_ptr(), ws.data_ptr(), ws.numel(), L.ptr(fr), L.ptr(tr),
                 C.byref(stem_cache["sc"]) if stem_cache is not None else None, self.precision, L.stream_ptr()),
                 "mdm_denoiser_forward")
-        if trace:
+        if tr is not None:
             return out, tr
         return out
