@@ -697,6 +697,32 @@ int mdm_world_render(const float* joints, const int32_t* lengths, const MdmSkele
                      const float* camera, const float* style, const float* ground, int32_t mode, const int32_t* frames,
                      int32_t n_frames, uint8_t* out, float* scratch, void* stream);
 
+/* Body view of the motion preview (csrc/motion_mesh_render.hip): the vertices of a mesh -> image frames, a
+ * triangle rasteriser with a depth test per pixel and shading from normals over the floor and trajectory of
+ * mdm_motion_render.  vertices (B, T, V, 3) fp32, as mdm_skin_vertices writes them; normals the same or NULL; faces (F, 3)
+ * int32 on the device, shared by the batch; root (B, T, 3) fp32: the point each frame's x, z are relative to, and the
+ * trajectory; length (B) int32 or NULL (= T).  The image is defined in DESIGN.md §32: MINS / MAXS over the valid frames'
+ * vertices (a NaN or infinite coordinate is no part of them); a face with a non-finite vertex, an index outside [0, V), a vertex in front of the near plane or no area on the
+ * screen is not drawn (no clipping); coverage by edge functions that two faces sharing an edge evaluate to the same bits, so a
+ * closed surface has no cracks; two-sided; the covering face with the largest perspective-correct 1/z wins, ties to the lower
+ * face index; I = ambient + (1 - ambient) max(0, n . l) with n the face's normal (mode bit 1 clear) or the interpolated vertex
+ * normal (mode bit 1 set, needs normals), turned towards the eye.  camera[8], frames / n_frames and out as in
+ * mdm_motion_render; mode bit 0: palette indices.  style[20]: background r, g, b; floor r, g, b, alpha; trajectory r, g, b,
+ * alpha, full width in points; body r, g, b, alpha; ambient; light x, y, z (any length > 0) in the camera's (right, up,
+ * towards the eye).  scratch: mdm_mesh_render_scratch_floats(B, T, n_frames, V, F, with_normals) floats, 16-byte aligned
+ * (n_frames = T without frames; -1 for bad arguments): the extent's slices, and per drawn frame the projected vertices
+ * (8 floats each), the view-space normals (4, with normals) and each face's pixel box (2 dwords).  Three launches,
+ * stream-ordered, no allocation, no host synchronisation, no atomics on global memory; 64-bit offsets.  Every sample equals
+ * its own run alone bit for bit.  MDM_ERR_ARG, before the device is touched: a null pointer (normals, length, frames
+ * excepted), B < 0, T < 1, V or F outside [1, 2^24], H or W outside [4, 8192], W % 4 != 0, a mode outside [0, 3], mode bit 1
+ * without normals, frames with n_frames < 1, out not 4-byte or scratch not 16-byte aligned, a camera mdm_motion_render
+ * refuses, a non-finite style value, a negative width, a light without length.  MDM_ERR_UNSUPPORTED: B or NF above 65535 (grid
+ * dimensions).  B = 0 or NF = 0: nothing is launched. */
+int64_t mdm_mesh_render_scratch_floats(int32_t B, int32_t T, int32_t n_frames, int32_t V, int32_t F, int32_t with_normals);
+int mdm_mesh_render(const float* vertices, const float* normals, const int32_t* faces, const float* root, const int32_t* length,
+                    int32_t B, int32_t T, int32_t V, int32_t F, int32_t H, int32_t W, const float* camera, const float* style,
+                    int32_t mode, const int32_t* frames, int32_t n_frames, uint8_t* out, float* scratch, void* stream);
+
 /* Joint-position control (csrc/motion_control.hip).  For sample b, with J = (F + 1) / 12 joints (F must be
  * 12 J - 1: 263 -> 22, 251 -> 21), targets G and weights W dense fp32 (B, T, J, 3), W >= 0 and finite, mean / std fp32
  * (B, F) (one row per sample), and P = recover_from_ric(x0 * std + mean) without temporal filter (as mdm_motion_postprocess

@@ -206,6 +206,8 @@ PROTOTYPES = {
     "mdm_world_render_scratch_floats": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32]),
     "mdm_world_render": (_I32, [_P, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I32, _P,
                                 _P, _P]),
+    "mdm_mesh_render_scratch_floats": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "mdm_mesh_render": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P]),
     "mdm_joint_control_max_frames": (_I32, [_I32]),
     "mdm_joint_loss_grad": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mdm_joint_guidance": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F32, _I32, _P, _I32, _P, _I32, _P]),

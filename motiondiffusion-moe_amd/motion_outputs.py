@@ -10,7 +10,7 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .motion_features import pad_clips, skeleton_for_feats
 from .motion_mesh import capsule_body, glb_bytes, skin_vertices
-from .motion_render import gif_bytes, render_motion, render_world, write_gif
+from .motion_render import gif_bytes, render_mesh, render_motion, render_world, write_gif
 from .motion_rig import DEFAULT_FPS, bvh_text, retarget_to_rig, retime_ratio, rig_of, rotations_to_rig, target_bvh_text
 from .motion_rig import target_rig as make_target_rig
 from .postprocess import fk_max_frames, motion_to_joints, motion_to_joints_fk, pin_limbs, remove_foot_skate
@@ -245,6 +245,19 @@ def to_frames_view(view, joints, cond, size, camera, palette, style):
     if view != "world":
         raise ValueError(f"view must be \"root\" or \"world\", not {view!r}")
     return to_world_frames([[j] for j in joints], cond.get("scene"), cond.get("scene_tracks"), size, camera, palette, style)
+
+
+def to_body_frames(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, mesh, size, camera, palette, style, *, pin=None,
+                   pin_blend=5):
+    """Rows -> the body view, per motion ``(lens[i], H, W, 3)`` uint8 frames or ``(lens[i], H, W)`` palette
+    indices: ``skinned_batch`` and ``motion_mesh.skin_vertices`` with normals, as ``to_meshes`` runs them, so that the body in
+    the picture is the body in the ``.glb``, and one ``motion_render.render_mesh`` over the padded batch with the joints of
+    the forward kinematics as root."""
+    j, r, o, lens, skel, mesh = skinned_batch(motions, lens, dim_pose, mean, std, offsets, fix_feet, blend, mesh, pin, pin_blend)
+    j, r = j[:, :max(lens)], r[:, :max(lens)]
+    v, n = skin_vertices(mesh, j, r, torch.tensor(lens), return_normals=True)
+    frames = render_mesh(v, mesh.faces, lens, root=j, normals=n, size=size, camera=camera, palette=palette, **(style or {}))
+    return [frames[i, :k] for i, k in enumerate(lens)]
 
 
 def to_gifs(frames, dim_pose, paths, fps):

@@ -10,6 +10,9 @@ fallback.
 ``render_world`` (``mdm_world_render`` in csrc/motion_world_render.hip) is the world view under the same
 definition: up to four characters and the primitives and tracks of a ``motion_scene`` scene in world coordinates, composited
 far to near per item; ``world_extent`` / ``fit_camera`` give the camera that shows all of it.
+
+``render_mesh`` (``mdm_mesh_render`` in csrc/motion_mesh_render.hip) is the body view: the vertices of a skinned
+mesh (``motion_mesh.skin_vertices``) as shaded triangles with a depth test per pixel, over §21's floor and trajectory.
 """
 from __future__ import annotations
 
@@ -499,4 +502,124 @@ def render_world(characters, lengths=None, scene=None, tracks=None, skeleton=Non
         L.check(lib.mdm_world_render(a["x"].data_ptr(), a["ln_dev"].data_ptr(), C.byref(s), L.ptr(rec), K, L.ptr(trk), Km, B, Cn, T,
                                      J, H, W, cam, st, gr.data_ptr(), 1 if palette else 0, L.ptr(fr), NF, out.data_ptr(),
                                      scratch.data_ptr(), L.stream_ptr()), "mdm_world_render")
+    return out
+
+
+# ---- the body view: a mesh as shaded triangles with a depth test per pixel ----------------------------------
+MESH_STYLE = dict(background=(1.0, 1.0, 1.0),
+                  floor_color=(0.5, 0.5, 0.5), floor_alpha=0.5,
+                  trajectory_color=BLUE, trajectory_alpha=1.0, trajectory_width=1.0,
+                  body_color=(0.72, 0.76, 0.85), body_alpha=1.0, ambient=0.35,
+                  light=(-0.4, 0.6, 0.7))  # the light: (right, up, towards the eye) of the camera; a look, not a measurement
+MAX_SIDE = 8192  # of mdm_mesh_render: a face's pixel box is packed
+
+
+def mesh_style_block(**style):
+    """The 20 floats of ``mdm_mesh_render``'s style argument from the keyword arguments of ``render_mesh`` (``MESH_STYLE`` holds
+    the names and defaults): background; floor colour and alpha; trajectory colour, alpha and width in points; ``body_color``
+    and ``body_alpha``; ``ambient`` in [0, 1]; ``light``, a direction of any length > 0 fixed to the camera in its (right,
+    up, towards the eye) coordinates."""
+    unknown = set(style) - set(MESH_STYLE)
+    if unknown:
+        raise ValueError(f"unknown style arguments {sorted(unknown)}: the style is {sorted(MESH_STYLE)}")
+    st = dict(MESH_STYLE, **style)
+
+    def rgb(v, what):
+        v = [float(x) for x in v]
+        if len(v) != 3 or not all(0.0 <= x <= 1.0 for x in v):
+            raise ValueError(f"{what} must be three values in [0, 1]")
+        return v
+
+    for name in ("floor_alpha", "trajectory_alpha", "body_alpha", "ambient"):
+        if not (np.isfinite(st[name]) and 0 <= st[name] <= 1):
+            raise ValueError(f"{name} must lie in [0, 1]")
+    if not (np.isfinite(st["trajectory_width"]) and st["trajectory_width"] >= 0):
+        raise ValueError("trajectory_width must be finite and >= 0")
+    light = [float(x) for x in st["light"]]
+    if len(light) != 3 or not all(np.isfinite(light)) or not sum(x * x for x in light) > 0:
+        raise ValueError("light must be three finite values, not all zero")
+    v = rgb(st["background"], "background")
+    v += rgb(st["floor_color"], "floor_color") + [float(st["floor_alpha"])]
+    v += rgb(st["trajectory_color"], "trajectory_color") + [float(st["trajectory_alpha"]), float(st["trajectory_width"])]
+    v += rgb(st["body_color"], "body_color") + [float(st["body_alpha"]), float(st["ambient"])] + light
+    return (C.c_float * len(v))(*v)
+
+
+def check_mesh(vertices, faces, lengths, root, normals, size):
+    """Argument checks of ``render_mesh`` that need no device: -> (vertices (B, T, V, 3), faces (F, 3) int32 on the CPU, lengths
+    (B,) int64 on the CPU or None, root (B, T, 3), normals or None, (H, W)).  Raises ValueError."""
+    x = torch.as_tensor(vertices)
+    one = x.dim() == 3
+    if one:
+        x = x[None]
+    if x.dim() != 4 or x.shape[-1] != 3 or not x.dtype.is_floating_point:
+        raise ValueError(f"vertices of shape {tuple(x.shape)} must be floating point (B, T, V, 3)")
+    B, T, V = x.shape[:3]
+    if T < 1 or V < 1 or V > 1 << 24:
+        raise ValueError("a mesh motion needs at least one frame, and 1 to 2^24 vertices")
+    f = torch.as_tensor(faces)
+    if f.dim() != 2 or f.shape[1] != 3 or f.dtype.is_floating_point or f.dtype == torch.bool or not 1 <= f.shape[0] <= 1 << 24:
+        raise ValueError(f"faces of shape {tuple(f.shape)} and dtype {f.dtype} must be integer (F, 3), F in [1, 2^24]")
+    r = torch.as_tensor(root)
+    if one and r.dim() in (2, 3) and r.shape[0] == T:
+        r = r[None]
+    if r.dim() == 4:
+        r = r[:, :, 0]  # joints: joint 0 is the root
+    if tuple(r.shape) != (B, T, 3):
+        raise ValueError(f"root of shape {tuple(torch.as_tensor(root).shape)} must be ({B}, {T}, 3), or joints ({B}, {T}, J, 3)")
+    n = None
+    if normals is not None:
+        n = torch.as_tensor(normals)
+        if one and n.dim() == 3:
+            n = n[None]
+        if tuple(n.shape) != tuple(x.shape):
+            raise ValueError(f"normals of shape {tuple(n.shape)} must have the vertices' shape {tuple(x.shape)}")
+    H, W = (int(v) for v in size)
+    if H < 4 or W < 4 or W % 4 or H > MAX_SIDE or W > MAX_SIDE:
+        raise ValueError(f"size (H, W) = {(H, W)}: both in [4, {MAX_SIDE}] and W a multiple of 4 (a thread stores 4 pixels)")
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).flatten().to(torch.int64).cpu()
+        if lengths.numel() != B or (B and (int(lengths.min()) < 1 or int(lengths.max()) > T)):
+            raise ValueError(f"lengths must hold {B} entries in [1, {T}]")
+    return x, f, lengths, r, n, (H, W)
+
+
+@torch.no_grad()
+def render_mesh(vertices, faces, lengths=None, *, root, normals=None, size=(480, 480), camera=None, palette=False, frames=None,
+                **style):
+    """The body view: vertices (B, T, V, 3) on a GPU (or one clip (T, V, 3)), as ``motion_mesh.skin_vertices``
+    returns them, and ``faces`` (F, 3) integers shared by the batch -> frames (B, T, H, W, 3) uint8 on the device, or
+    (B, T, H, W) palette indices: the mesh as triangles with a depth test per pixel, over §21's floor and trajectory.  ``root``
+    (B, T, 3), or joints (B, T, J, 3) of which joint 0 is taken: every frame's x, z are relative to it, and it draws the
+    trajectory.  ``normals`` (B, T, V, 3): smooth shading from the interpolated vertex normals; None: flat shading from each
+    face's own normal.  A face is drawn from both sides; a face with a non-finite vertex, an index outside [0, V) or a vertex
+    in front of the near plane is not drawn (it is dropped, not clipped).  ``lengths`` / ``size`` / ``camera`` / ``palette`` /
+    ``frames`` as in ``render_motion``: frames at or past a length are zero and are never read.  ``**style``: see
+    ``MESH_STYLE``.  All pixels are made in the kernel; no eager fallback."""
+    x, f, lengths, r, n, (H, W) = check_mesh(vertices, faces, lengths, root, normals, size)
+    B, T, V = x.shape[:3]
+    cam = as_camera(camera).block()
+    st = mesh_style_block(**style)
+    idx = frame_indices(frames, T)
+    L.require_cuda(x, r, n)
+    dev = x.device
+    if r.device != dev or (n is not None and n.device != dev):
+        raise ValueError("root and normals must be on the vertices' device")
+    x = x.detach().to(torch.float32).contiguous()
+    r = r.detach().to(torch.float32).contiguous()
+    n = None if n is None else n.detach().to(torch.float32).contiguous()
+    f = f.detach().to(dev, torch.int32).contiguous()
+    ln = None if lengths is None else lengths.to(dev, torch.int32).contiguous()
+    fr = None if idx is None else torch.tensor(idx, dtype=torch.int32, device=dev)
+    NF = T if idx is None else len(idx)
+    if B > 65535 or NF > 65535:
+        raise ValueError("at most 65535 samples and 65535 frames per call")
+    out = torch.empty((B, NF, H, W) + (() if palette else (3,)), dtype=torch.uint8, device=dev)
+    lib = L.lib()
+    words = int(lib.mdm_mesh_render_scratch_floats(B, T, NF, V, f.shape[0], int(n is not None)))
+    scratch = torch.empty(max(4, words), dtype=torch.float32, device=dev)
+    mode = (1 if palette else 0) | (2 if n is not None else 0)
+    with torch.cuda.device(dev):
+        L.check(lib.mdm_mesh_render(x.data_ptr(), L.ptr(n), f.data_ptr(), r.data_ptr(), L.ptr(ln), B, T, V, f.shape[0], H, W, cam, st,
+                                    mode, L.ptr(fr), NF, out.data_ptr(), scratch.data_ptr(), L.stream_ptr()), "mdm_mesh_render")
     return out

@@ -656,38 +656,72 @@ class DDPMTrainer(object):
         return MO.to_glb(motions, MO.valid_lengths(motions), dim_pose, mean, std, offsets, fix_feet, feet_blend, paths, fps,
                          fps_out, scale, mesh, **MO.pin_kw(pin, pin_blend))
 
+    def _body_frames(self, motions, lens, dim_pose, mean, std, size, camera, palette, style, mesh, body):
+        """The body view of generated rows, ``body`` holding ``generate_mesh``'s output arguments."""
+        return MO.to_body_frames(motions, lens, dim_pose, mean, std, body["offsets"], body["fix_feet"], body["blend"], mesh, size,
+                                 camera, palette, style, **MO.pin_kw(body["pin"], body["pin_blend"]))
+
+    @staticmethod
+    def _body_args(view, mesh, kw, blend_name="blend"):
+        """``view`` / ``mesh`` of the preview methods: None for the joint views (``mesh`` must then be None), else the output
+        arguments of ``generate_mesh`` taken out of ``kw``; any view but "root", "world" and "body" is a ValueError."""
+        if view != "body":
+            if view not in ("root", "world"):
+                raise ValueError(f"view must be \"root\", \"world\" or \"body\", not {view!r}")
+            if mesh is not None:
+                raise ValueError("mesh= belongs to view=\"body\"")
+            return None
+        pin = MO.pin_of(kw.pop("pin_targets", False), kw)
+        return dict(pin=pin, offsets=kw.pop("offsets", None), fix_feet=kw.pop("fix_feet", False),
+                    blend=kw.pop(blend_name, 5), pin_blend=kw.pop("pin_blend", 5))
+
     @torch.no_grad()
     def generate_frames(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, size=(480, 480), camera=None,
-                        palette=False, style=None, view="root", **kw):
+                        palette=False, style=None, view="root", mesh=None, **kw):
         """``generate_joints`` followed by the motion preview (``motion_render.render_motion``) on the device:
         a list of ``(m_len, H, W, 3)`` uint8 frames, ``size`` = (H, W); with ``palette`` ``(m_len, H, W)`` indices into
         ``motion_render.PALETTE``.  ``camera``: a ``motion_render.Camera`` or a dict of its fields; ``style``: a dict of
         ``render_motion``'s colour and width arguments.  ``**kw`` goes to ``generate_joints`` untouched: ``from_rotations``,
         ``fix_feet``, ``pin_targets``, the sampler, edit and control arguments.  ``view="world"``: the world view instead
         (``motion_render.render_world``): each character in world coordinates with the ``scene`` /
-        ``scene_tracks`` that steered it; ``camera`` None then fits one camera to the batch, ``style`` is ``render_world``'s."""
+        ``scene_tracks`` that steered it; ``camera`` None then fits one camera to the batch, ``style`` is ``render_world``'s.
+        ``view="body"``: the body view (``motion_render.render_mesh``) of the skinned mesh that ``generate_mesh``
+        returns for the same arguments (forward kinematics of the rotations, no temporal filter, ``offsets`` / ``fix_feet`` /
+        ``blend`` / ``pin_targets`` / ``pin_blend`` as there, ``**kw`` as for ``generate``): ``mesh`` a ``motion_mesh.Mesh``, None
+        ``motion_mesh.capsule_body`` of the offsets used; ``style`` is ``render_mesh``'s."""
+        body = self._body_args(view, mesh, kw)
+        if body is not None:
+            motions = self.generate(caption, m_lens, dim_pose, batch_size, mean=mean, std=std, **kw)
+            return self._body_frames(motions, MO.valid_lengths(motions, m_lens), dim_pose, mean, std, size, camera, palette, style,
+                                     mesh, body)
         joints = self.generate_joints(caption, m_lens, dim_pose, mean, std, batch_size, **kw)
         return MO.to_frames_view(view, joints, kw, size, camera, palette, style)
 
     @torch.no_grad()
     def generate_gif(self, caption, m_lens, dim_pose, mean, std, batch_size=8, *, paths=None, fps=None, size=(480, 480),
-                     camera=None, style=None, view="root", **kw):
+                     camera=None, style=None, view="root", mesh=None, **kw):
         """``generate_frames`` in palette mode followed by ``motion_render.write_gif``: one animated GIF per caption, as
         bytes, or written to ``paths[i]`` where given (the path is then returned in its place).  ``fps`` defaults to
-        ``motion_rig.DEFAULT_FPS`` (20 at dim_pose 263, 12.5 at 251); a GIF's frame delay is whole centiseconds.  ``view`` as in
-        ``generate_frames``."""
+        ``motion_rig.DEFAULT_FPS`` (20 at dim_pose 263, 12.5 at 251); a GIF's frame delay is whole centiseconds.  ``view`` /
+        ``mesh`` as in ``generate_frames``."""
         MO.check_paths(paths, len(caption), "caption")
         frames = self.generate_frames(caption, m_lens, dim_pose, mean, std, batch_size, size=size, camera=camera, palette=True,
-                                      style=style, view=view, **kw)
+                                      style=style, view=view, mesh=mesh, **kw)
         return MO.to_gifs(frames, dim_pose, paths, fps)
 
     @torch.no_grad()
     def generate_long_gif(self, scripts, dim_pose, mean, std, *, paths=None, fps=None, size=(480, 480), camera=None,
-                          style=None, view="root", **kw):
+                          style=None, view="root", mesh=None, **kw):
         """``generate_long_joints`` followed by the motion preview and ``write_gif``, as ``generate_gif``: one GIF per long
         motion.  ``**kw`` goes to ``generate_long_joints`` untouched.  ``view="world"``: the world view with each motion's
-        ``scene`` and its canvas ``scene_tracks`` (targets are not drawn)."""
+        ``scene`` and its canvas ``scene_tracks`` (targets are not drawn).  ``view="body"`` / ``mesh``: the body view of the
+        skinned mesh that ``generate_long_mesh`` returns for the same arguments (``feet_blend`` is its ``blend``)."""
         MO.check_paths(paths, len(scripts), "motion")
+        body = self._body_args(view, mesh, kw, "feet_blend")
+        if body is not None:
+            motions = self._long_motions(scripts, dim_pose, mean, std, MO.canvas_frame_limit(True), "forward kinematics", kw)
+            frames = self._body_frames(motions, MO.valid_lengths(motions), dim_pose, mean, std, size, camera, True, style, mesh, body)
+            return MO.to_gifs(frames, dim_pose, paths, fps)
         joints = self.generate_long_joints(scripts, dim_pose, mean, std, **kw)
         return MO.to_gifs(MO.to_frames_view(view, joints, kw, size, camera, True, style), dim_pose, paths, fps)
 
