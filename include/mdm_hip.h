@@ -940,6 +940,37 @@ int mdm_partner_tracks(const float* x0, const int32_t* length, const float* mean
                        const int32_t* contacts_host, int32_t Nc, int32_t B, int32_t T, int32_t F, float* world, float* scratch,
                        float* tracks, float* track_bounds, float* targets, void* stream);
 
+/* Self-collision avoidance (csrc/motion_self.hip): keep a character's joints out of the capsules of its own
+ * bones, as per-step targets of the guidance calls above.  bones int32 (nb, 2) in host memory, read before the call returns:
+ * bone i is the segment P[t, bones[i, 0]] ... P[t, bones[i, 1]] of the same frame, with radius bone_radius[i] (nb, device);
+ * joint_params (J, 2) on the device: the joint's radius r_j and weight u_j; pair_mask int32 (J) on the device: bit i of
+ * pair_mask[j] says that bone i acts on joint j.  For t < length[b], with d_i the distance of P[t, j] to the segment of bone i,
+ * c_i the closest point on it, pen_i = max(0, margin + r_j + bone_radius[i] - d_i) and n_i = (P[t, j] - c_i) / d_i (0 where
+ * d_i < 1e-12):
+ *   push[b, t, j] = sum_i pen_i n_i,  depth[b, t, j] = sum_i pen_i   over the allowed bones in ascending i (a fixed order:
+ *   the same bits run after run); both are zero at t >= length[b].  Bones are data: nothing is differentiated.
+ * mdm_self_push: joints (B, T, J, 3) -> push_out (B, T, J, 3) and depth_out (B, T, J) or NULL.  One launch.
+ * mdm_self_targets: P = recover_from_ric(x0 * std + mean) unfiltered, bit for bit, by the two launches mdm_partner_tracks starts
+ * with (mean / std rows (B, F); `scratch`, the caller's, holds mdm_self_targets_scratch_floats(B, T, F) floats, 0 for a bad
+ * size), written to joints_out (B, T, J, 3); then the push launch with the merge fused, writing targets_out and weights_out,
+ * both (B, T, J, 3) as the guidance calls read them: where one of static_weights[b, t, j, :] is not zero, and in every frame at
+ * or past length[b], the static target and weights bit for bit (zeros without a static pair); elsewhere
+ * targets = P + push and all three weights = depth > 0 ? weight * u_j : 0.  The gradient of sum w |P - g|^2 at these targets
+ * is the gradient of weight * sum_j u_j sum_i pen_i^2 with the bones held fixed.  static_targets / static_weights (B, T, J, 3):
+ * both or neither.  Stream-ordered, allocation free, no atomics, graph-capturable.  MDM_ERR_ARG, before any launch: a null
+ * required pointer (depth_out and the static pair excepted), J outside [2, 32], nb outside [1, 31], a bone end outside [0, J),
+ * F + 1 no multiple of 12, one of the static pair without the other, a non-finite margin or weight, weight < 0.
+ * MDM_ERR_UNSUPPORTED: T > mdm_self_max_frames() (the recovery's LDS limit).  B == 0 or T == 0 is a no-op. */
+int mdm_self_max_frames(void);
+int64_t mdm_self_targets_scratch_floats(int32_t B, int32_t T, int32_t F);
+int mdm_self_push(const float* joints, const int32_t* length, const int32_t* bones, int32_t nb, const float* bone_radius,
+                  const float* joint_params, const int32_t* pair_mask, float margin, int32_t B, int32_t T, int32_t J,
+                  float* push_out, float* depth_out, void* stream);
+int mdm_self_targets(const float* x0, const int32_t* length, const float* mean, const float* std, const int32_t* bones, int32_t nb,
+                     const float* bone_radius, const float* joint_params, const int32_t* pair_mask, float margin, float weight,
+                     const float* static_targets, const float* static_weights, int32_t B, int32_t T, int32_t F,
+                     float* joints_out, float* scratch, float* targets_out, float* weights_out, void* stream);
+
 /* ---- long-motion handshakes ---------------------------------------------------------------------
  * In place over the shared canvas frames only.  For every group g < groups, shared frame c < nshared and feature j < F:
  *   v = sum over entries e in [offsets[c], offsets[c+1]) of weights[e] * x[g*group_stride + rows[e]*F + j]

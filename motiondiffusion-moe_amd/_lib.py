@@ -240,6 +240,10 @@ PROTOTYPES = {
     "mdm_partner_tracks_scratch_floats": (_I64, [_I32, _I32, _I32]),
     "mdm_partner_tracks": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _F32, _F32, _F32, _I32, _I32, _P, _P, _I32, _I32, _I32,
                                   _I32, _P, _P, _P, _P, _P, _P]),
+    "mdm_self_max_frames": (_I32, []),
+    "mdm_self_targets_scratch_floats": (_I64, [_I32, _I32, _I32]),
+    "mdm_self_push": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _F32, _I32, _I32, _I32, _P, _P, _P]),
+    "mdm_self_targets": (_I32, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _F32, _F32, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "mdm_handshake_blend": (_I32, [_P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
     "mdm_moe_train_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32]),
     "mdm_moe_ffn_train_forward": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _F32, _U64, _P, _P, _P, _P,

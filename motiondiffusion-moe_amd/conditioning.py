@@ -147,9 +147,16 @@ def check_control_kwargs(kw, shape):
     and a terrain, come back as ``partners``, the ``motion_scene.PartnerTables`` (made with ``model_kwargs["length"]``); the
     returned ``weights`` are then the tables' (the static weights plus the contacts') and ``targets`` zeros where none are
     given.  Raises ValueError for the other partner / contact keys without the scenes and placements and for everything
-    ``motion_scene.partner_tables`` refuses.  Host logic."""
+    ``motion_scene.partner_tables`` refuses.
+    Self-collision avoidance: ``control_self``, a dict of ``body`` (a ``motion_scene.SelfBody``) and ``weight``
+    >= 0, with ``control_mean`` / ``control_std`` and with or without targets, a scene, tracks and a terrain, comes back as
+    ``self`` (the body and the weight); a weight of 0 or a body whose mask allows no pair is the call without the key.  Raises
+    ValueError for another type, a body of another joint count, a weight that is negative or not finite and a T over
+    ``motion_scene.SELF_MAX_FRAMES``; NotImplementedError together with the partner / contact keys (both rewrite the targets),
+    handshake tables and ``canvas_control_*``.  Host logic."""
     from .motion_control import joints_for_feats, max_frames
     names = ("control_joints", "control_weights", "control_mean", "control_std")
+    own = _check_control_self(kw, shape)
     partner = {k: kw.get(k) for k in PARTNER_KEYS}
     if any(v is not None for v in partner.values()):
         if partner["control_partner_scenes"] is None or partner["control_partner_placements"] is None:
@@ -173,11 +180,13 @@ def check_control_kwargs(kw, shape):
     extra = [k for k in ("control_scale", "control_iters") if kw.get(k) is not None]
     if jp is not None and scene is None:
         raise ValueError("control_joint_params given without control_scene")
-    if not given and scene is None:
+    if not given and scene is None and own is None:
         if extra and not any(kw.get(k) is not None for k in CANVAS_CONTROL_KEYS + CANVAS_SCENE_KEYS + (CANVAS_TRACKS_KEY,) + CANVAS_TERRAIN_KEYS):  # canvas control's
             raise ValueError(f"{' / '.join(extra)} given without control_joints / control_weights / control_mean / control_std")
         return None
-    need = names[2:] if scene is not None and g is None and w is None else names
+    if own is None and kw.get("control_self") is not None and scene is None and g is None and w is None:
+        return None  # an inactive body and nothing else to steer by: the plain call, whatever mean / std say
+    need = names[2:] if (scene is not None or own is not None) and g is None and w is None else names
     if any(k not in given for k in need):
         raise ValueError(f"joint control needs all of {', '.join(need)}; missing "
                          f"{', '.join(k for k in need if k not in given)}")
@@ -252,7 +261,40 @@ def check_control_kwargs(kw, shape):
         out["partners"] = tables
         if len(tables.contacts) or g is not None:
             g, w = torch.zeros((B, T, J, 3)) if g is None else g, tables.weights
+    if own is not None:
+        out["self"] = own
     return {"targets": g, "weights": w, "mean": mean, "std": std, "scale": scale, "iters": int(iters), **out}
+
+
+def _check_control_self(kw, shape):
+    """``control_self`` of ``model_kwargs`` checked: None without the key or when it changes nothing (weight 0, or a mask that
+    allows no pair), else ``{"body": SelfBody, "weight": float}``."""
+    own = kw.get("control_self")
+    if own is None:
+        return None
+    from .motion_control import joints_for_feats
+    from .motion_scene import SELF_MAX_FRAMES, SelfBody
+    if not isinstance(own, dict) or set(own) != {"body", "weight"} or not isinstance(own["body"], SelfBody):
+        raise ValueError("control_self must be a dict of body (a motion_scene.SelfBody, see motion_scene.self_body) and weight")
+    body, weight = own["body"], float(own["weight"])
+    if not (math.isfinite(weight) and weight >= 0):
+        raise ValueError(f"control_self: weight must be finite and >= 0, not {weight}")
+    B, T, F_ = (int(v) for v in shape)
+    if body.J != joints_for_feats(F_):
+        raise ValueError(f"control_self: a body of {body.J} joints for feature rows of {joints_for_feats(F_)} joints (F = {F_})")
+    both = [k for k in PARTNER_KEYS if kw.get(k) is not None]
+    if both:
+        raise NotImplementedError(f"self-collision avoidance (DESIGN.md §33) cannot be combined with {', '.join(both)}: both "
+                                  "rewrite the targets on every step")
+    long = [k for k, v in kw.items() if v is not None and (k.startswith("handshake_") or k.startswith("canvas_control_"))]
+    if long:
+        raise NotImplementedError(f"self-collision avoidance (DESIGN.md §33) cannot be combined with {', '.join(sorted(long))}: "
+                                  "long motions are out of its scope")
+    if T > SELF_MAX_FRAMES:
+        raise ValueError(f"T = {T}: self-collision avoidance takes at most {SELF_MAX_FRAMES} frames")
+    if weight == 0 or not bool(body.allowed.any()):
+        return None
+    return {"body": body, "weight": weight}
 
 
 PARTNER_KEYS = ("control_partner_scenes", "control_partner_placements", "control_partner_bones", "control_partner_radius",
@@ -650,6 +692,11 @@ class Conditioning:
     ``edit_bvh``: N BVH texts, paths or parsed files in place of ``edit_joints``, read into clips first (``joint_clips_from_bvh``)
     at the model's frame rate by ``motion_rig.bvh_to_joints`` under ``bvh_options`` (a dict of its ``joint_map`` /
     ``scale`` / ``up`` / ``basis`` / ``fps_out``), from there on treated as ``edit_joints``; exclusive with it and ``edit_motion``.
+    ``self_collision``: keep every joint out of the capsules of the character's own bones: None, True (the
+    defaults) or a dict of ``weight`` (default 5; 0 leaves it out), ``radius_scale``, ``margin``, ``hops``, ``radii``, ``pairs``,
+    ``joint_radius``, ``joint_weights`` (``motion_scene.self_body``'s) and ``offsets`` (J, 3), the skeleton's bone offsets (default
+    ``motion_scene.default_offsets`` of the skeleton dim_pose names, at ``height``); it needs ``mean`` / ``std`` and acts through
+    the same guidance (``control_scale`` / ``control_iters``), with or without targets, ``scene``, ``scene_tracks`` and ``terrain``.
     ``init_motion`` (N, T_max, dim_pose), normalised, with ``strength`` in [0, 1]: motion-to-motion (DESIGN.md §22;
     ``init_rows_from``, ``strength_steps``).  The motion is noised to an intermediate level of the chosen sampler's schedule and
     ``round(strength * steps)`` steps run from there under the caption: 1 is the plain call (the motion is ignored), 0 returns
@@ -665,8 +712,10 @@ class Conditioning:
                  control_weights=None, control_scale=1.0, control_iters=1, mean=None, std=None, edit_joints=None,
                  device=None, to_motion=None, edit_bvh=None, bvh_options=None, init_motion=None, init_joints=None,
                  init_bvh=None, strength=None, latents=None, latent_step=None, scene=None, scene_joint_radius=None,
-                 scene_joint_weights=None, scene_tracks=None, terrain=None, terrain_stand=None, terrain_stand_threshold=0.5):
+                 scene_joint_weights=None, scene_tracks=None, terrain=None, terrain_stand=None, terrain_stand_threshold=0.5,
+                 self_collision=None):
         self.captions, self.dim_pose = captions, dim_pose
+        self.self_collision = self._self_collision(self_collision, dim_pose)
         self.init, self.strength, self.latents, self.latent_step = None, None, None, None
         if init_motion is not None or init_joints is not None or init_bvh is not None:
             if latents is not None:
@@ -712,7 +761,8 @@ class Conditioning:
             if rows is not None:
                 check_joint_edit_mask(self.edit[1], rows)
         self.control = self._control(control_joints, control_weights, mean, std, dim_pose,
-                                     scene is not None or scene_tracks is not None or terrain is not None)
+                                     scene is not None or scene_tracks is not None or terrain is not None
+                                     or self.self_collision is not None)
         self.scene_records = self.scene_joint_params = self.track_records = None
         self.terrain_grids = self.terrain_records = self.terrain_stand = self.terrain_stand_threshold = None
         if scene is not None or scene_tracks is not None or terrain is not None:
@@ -739,6 +789,35 @@ class Conditioning:
         if terrain is None and terrain_stand is not None:
             raise ValueError("terrain_stand goes with terrain")
         self.control_scale, self.control_iters = control_scale, control_iters
+
+    @staticmethod
+    def _self_collision(opts, dim_pose):
+        """``self_collision`` checked: None when it is not given or changes nothing (weight 0, no allowed pair), else the
+        ``control_self`` entry of every batch's ``model_kwargs``."""
+        if opts is None or opts is False:
+            return None
+        from .motion_features import skeleton_for_feats
+        from .motion_scene import default_offsets, self_body
+        opts = {} if opts is True else opts
+        known = {"weight", "radius_scale", "margin", "hops", "radii", "pairs", "offsets", "height", "joint_radius", "joint_weights"}
+        if not isinstance(opts, dict) or set(opts) - known:
+            raise ValueError(f"self_collision must be None, True or a dict of {sorted(known)}")
+        skeleton = skeleton_for_feats(dim_pose)
+        if skeleton is None:
+            raise ValueError(f"self_collision needs dim_pose 263 (HumanML3D) or 251 (KIT), not {dim_pose}")
+        opts = dict(opts)
+        weight = float(opts.pop("weight", 5.0))
+        if not (math.isfinite(weight) and weight >= 0):
+            raise ValueError(f"self_collision: weight must be finite and >= 0, not {weight}")
+        height, offsets = opts.pop("height", None), opts.pop("offsets", None)
+        if offsets is None:
+            offsets = default_offsets(skeleton, **({} if height is None else {"height": height}))
+        elif height is not None:
+            raise ValueError("self_collision: height scales the default skeleton; with offsets= it has no meaning")
+        body = self_body(offsets, skeleton, **opts)
+        if weight == 0 or not bool(body.allowed.any()):
+            return None
+        return {"body": body, "weight": weight}
 
     @staticmethod
     def _track_frames(tracks):
@@ -843,6 +922,8 @@ class Conditioning:
                 if st.shape[1] < T:
                     raise ValueError(f"terrain_stand has {st.shape[1]} frames, the batch {T}")
                 out.update(control_stand=st[:, :T].contiguous().to(device))
+        if self.self_collision is not None:
+            out.update(control_self=self.self_collision)
         n = len(self.captions_of(rows))
         return {**out, "control_mean": c["mean"].to(device).expand(n, -1), "control_std": c["std"].to(device).expand(n, -1),
                 "control_scale": self.control_scale, "control_iters": self.control_iters}

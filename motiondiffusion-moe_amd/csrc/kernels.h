@@ -102,6 +102,12 @@ int text_assemble(const float* pp, const float* ph, int B, int N0, int P, int Dt
 // motion_post.hip: 263-d HumanML3D rows -> (T, J, 3) joints, optional temporal gaussian filter (wts[0..radius])
 int motion_post(const float* x, const int* len, const float* mean, const float* sd, int B, int T, int feats, int J,
                 int radius, const double* wts, float* raw, float* out, hipStream_t s);
+// motion_partners.hip: P = recover_from_ric(x0 * std + mean) unfiltered, bit for bit (the de-normalisation as two roundings, then
+// motion_post's own kernel with a one-tap filter), zero at and past a row's length; mean / sd rows (B, feats); scratch:
+// step_joints_scratch_floats(B, T, J) floats.  Two launches, shared by mdm_partner_tracks and mdm_self_targets
+int64_t step_joints_scratch_floats(int64_t B, int64_t T, int64_t J);
+int step_joints(const float* x0, const int* len, const float* mean, const float* sd, int B, int T, int feats, int J, float* scratch,
+                float* joints, hipStream_t s);
 // motion_features.hip: parent-ordered chains over J joints: every joint but the root is the child of exactly one link, a chain
 // starts at the root or at a joint an earlier link reached; parent[] (MDM_SKEL_MAX_JOINTS) filled.  Host side
 bool skeleton_ok(const MdmSkeleton& s, int* parent);

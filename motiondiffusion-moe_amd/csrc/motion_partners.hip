@@ -170,14 +170,34 @@ __global__ __launch_bounds__(CONTACT_THREADS) void partner_contacts_kernel(const
 }
 
 }  // namespace
+
+int64_t step_joints_scratch_floats(int64_t B, int64_t T, int64_t J) {
+  const int64_t D = 3 * J + 1;
+  return B * T * (D + 3 * J) + 2 * D;
+}
+
+// launches 1 and 2 of the head comment: the joints of this step's x0, as postprocess.recover_from_ric gives them
+int step_joints(const float* x0, const int* len, const float* mean, const float* sd, int B, int T, int feats, int J, float* scratch,
+                float* joints, hipStream_t s) {
+  const int D = 3 * J + 1;
+  const int64_t nd = (int64_t)B * T * D, nj = (int64_t)B * T * J;
+  float* rows = scratch;       // (B, T, D) de-normalised steerable columns
+  float* raw = rows + nd;      // (B, T, J, 3): the recovery's unfiltered copy
+  float* unit = raw + nj * 3;  // D zeros, D ones
+  hipLaunchKernelGGL(partner_denorm_kernel, dim3((unsigned)(((nd > 2 * D ? nd : 2 * D) + WORLD_THREADS - 1) / WORLD_THREADS)),
+                     dim3(WORLD_THREADS), 0, s, x0, mean, sd, nd, T, feats, D, rows, unit);
+  MDM_RETURN_IF_LAUNCH_FAILED();
+  return motion_post(rows, len, unit, unit + D, B, T, D, J, 0, nullptr, raw, joints, s);
+}
+
 }  // namespace mdm
 
 extern "C" int mdm_partner_tracks_max_frames(void) { return 64 * 1024 / (5 * (int)sizeof(float)); }
 
 extern "C" int64_t mdm_partner_tracks_scratch_floats(int32_t B, int32_t T, int32_t F) {
-  const int64_t J = mdm::control::control_joints(F), D = 3 * J + 1;
+  const int64_t J = mdm::control::control_joints(F);
   if (B < 0 || T < 0 || J == 0) return 0;
-  return (int64_t)B * T * (D + 3 * J) + 2 * D;
+  return mdm::step_joints_scratch_floats(B, T, J);
 }
 
 extern "C" int mdm_partner_tracks(const float* x0, const int32_t* length, const float* mean, const float* std,
@@ -221,15 +241,8 @@ extern "C" int mdm_partner_tracks(const float* x0, const int32_t* length, const 
   if (T > mdm_partner_tracks_max_frames()) return MDM_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const float4* place = (const float4*)placements;
-  const int D = 3 * J + 1;
-  const int64_t nd = (int64_t)B * T * D, nj = (int64_t)B * T * J;
-  float* rows = scratch;            // (B, T, D) de-normalised steerable columns
-  float* raw = rows + nd;           // (B, T, J, 3): the recovery's unfiltered copy
-  float* unit = raw + nj * 3;       // D zeros, D ones
-  hipLaunchKernelGGL(mdm::partner_denorm_kernel, dim3((unsigned)(((nd > 2 * D ? nd : 2 * D) + mdm::WORLD_THREADS - 1) / mdm::WORLD_THREADS)),
-                     dim3(mdm::WORLD_THREADS), 0, s, x0, mean, std, nd, T, F, D, rows, unit);
-  MDM_RETURN_IF_LAUNCH_FAILED();
-  const int st = mdm::motion_post(rows, length, unit, unit + D, B, T, D, J, 0, nullptr, raw, world, s);
+  const int64_t nj = (int64_t)B * T * J;
+  const int st = mdm::step_joints(x0, length, mean, std, B, T, F, J, scratch, world, s);
   if (st != MDM_OK) return st;
   hipLaunchKernelGGL(mdm::partner_world_kernel, dim3((unsigned)((nj + mdm::WORLD_THREADS - 1) / mdm::WORLD_THREADS)),
                      dim3(mdm::WORLD_THREADS), 0, s, length, place, nj, T, J, world);

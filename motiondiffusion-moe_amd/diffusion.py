@@ -757,6 +757,15 @@ class _StepRunner:
                                             world=torch.empty((B, T, J, 3), dtype=torch.float32, device=dev),
                                             scratch=torch.empty(max(partner_scratch_floats(B, T, Fe), 1), dtype=torch.float32,
                                                                 device=dev))
+            if "self" in ctl:
+                # self-collision avoidance: targets and weights are rewritten on every step from that step's
+                # x0, in front of the guidance, which reads the rewritten pair; the user's pair is kept as the static one
+                from .motion_scene import self_scratch_floats
+                sb, c = ctl["self"], self.ctl
+                new = lambda *shp: torch.zeros(shp, dtype=torch.float32, device=dev)  # noqa: E731
+                c["self"] = dict(body=sb["body"], dev=sb["body"].on(dev), weight=sb["weight"], static=(c["targets"], c["weights"]),
+                                 joints=new(B, T, J, 3), scratch=new(max(self_scratch_floats(B, T, Fe), 1)))
+                c.update(targets=new(B, T, J, 3), weights=new(B, T, J, 3))
             if "terrain" in ctl:  # terrain: the height grids, their records and the stand weights
                 Gz, Gx = (int(v) for v in ctl["terrain"].shape[1:])
                 self.ctl.update(Gx=Gx, Gz=Gz, terrain=f32(ctl["terrain"], (B, Gz, Gx)), stand=None,
@@ -955,6 +964,11 @@ class _StepRunner:
             c, q = self.ctl, self.ctl["partners"]
             partner_launch(self.x0, c["len"], c["mean"], c["std"], q["tables"], q["dev"], q["world"], q["scratch"], c.get("tracks"),
                            c.get("track_bounds"), c["targets"])
+        if self.ctl is not None and "self" in self.ctl:  # this step's self-collision targets and weights, merged with the user's
+            from .motion_scene import self_launch
+            c, q = self.ctl, self.ctl["self"]
+            self_launch(self.x0, c["len"], c["mean"], c["std"], q["body"], q["dev"], q["weight"], q["static"][0], q["static"][1],
+                        q["joints"], q["scratch"], c["targets"], c["weights"])
         if self._guide is not None:  # x0 and x_{t-1} moved down the joint-position loss, before the counter moves
             L.check(getattr(lib, self._guide[0])(*self._guide[1], s), self._guide[0])
         if self._guide_canvas is not None:  # once per long motion over its canvas, then the owner's bits into every overlap

@@ -41,7 +41,18 @@ Characters sampled together: the characters of a scene are rows
 row avoids are the capsules of its partners' current estimate and the targets it reaches for the meeting points of its
 contacts.  ``contact`` makes a contact, ``partner_tables`` the host tables (partner rows, bones, placements, the contact table
 and the constant target weights) and ``partner_tracks`` runs the device call (``mdm_partner_tracks``) on its own:
-``(tracks, track_bounds, targets)`` as the tracks guidance takes them."""
+``(tracks, track_bounds, targets)`` as the tracks guidance takes them.
+
+Self-collision avoidance: every joint keeps out of the capsules of the character's own bones.  With the bones
+held fixed,
+
+    L_self,b = a sum_{t < len_b} sum_j u_j sum_{i allowed for j} max(0, m + r_j + rho_i - d_i(t, j))^2
+
+with d_i(t, j) the distance of P[t, j] to the segment of bone i in the same frame.  Its gradient is that of the target term at
+the targets P + sum_i pen_i n_i under the weights a u_j, so a producer launch writes those in front of the unchanged guidance on
+every step.  ``self_body`` makes the body (``default_offsets`` a plain skeleton for it), ``self_push`` runs the push and the
+depth on the device (``mdm_self_push``), ``self_targets`` the whole producer (``mdm_self_targets``) and ``self_penetration``
+checks a result in plain torch."""
 from __future__ import annotations
 
 import math
@@ -1071,3 +1082,253 @@ def partner_tracks(x0, lengths, mean, std, tables: PartnerTables, static_tracks=
         bounds.fill_(-math.inf)
         bounds[..., :3] = 0.0
     return (tracks, bounds, targets, world) if return_world else (tracks, bounds, targets)
+
+
+# ---- self-collision avoidance: every joint keeps out of the capsules of the character's own bones ----------
+MAX_SELF_JOINTS, MAX_SELF_BONES = 32, 31
+SELF_MAX_FRAMES = 64 * 1024 // 20  # mdm_self_max_frames(): the recovery's LDS holds five floats a frame
+
+
+# Bone lengths as fractions of the body height, along the rest axes of ``motion_features.SKELETONS``: a look, not a measurement,
+# like ``motion_mesh.BODY_RADII``.  t2m by joint name (the bone that ends in the joint), KIT by joint index.
+_T2M_LENGTHS = {"pelvis": 0.0, "hip": 0.06, "knee": 0.235, "ankle": 0.24, "foot": 0.08, "spine1": 0.07, "spine2": 0.08, "spine3": 0.035,
+                "neck": 0.125, "head": 0.06, "collar": 0.075, "shoulder": 0.07, "elbow": 0.155, "wrist": 0.15}
+_KIT_LENGTHS = (0.0, 0.08, 0.08, 0.12, 0.12, 0.10, 0.155, 0.15, 0.10, 0.155, 0.15, 0.06, 0.235, 0.24, 0.05, 0.05, 0.06, 0.235, 0.24,
+                0.05, 0.05)
+
+
+def default_offsets(skeleton="t2m", height=1.7) -> np.ndarray:
+    """Bone offsets (J, 3) float64 of a plain body of ``height`` (in the data's units: metres in HumanML3D) on the rest axes
+    of ``skeleton`` ("t2m" or "kit"): what ``self_body`` and ``motion_mesh.capsule_body`` take when the user brings no
+    skeleton of their own.  ValueError for another skeleton and a height that is not finite and > 0."""
+    from .motion_features import SKELETONS
+    height = _positive(height, "height")
+    if skeleton == "t2m":
+        from .motion_edit import SMPL_JOINTS
+        lengths = [_T2M_LENGTHS[n.split("_")[-1]] for n in SMPL_JOINTS]
+    elif skeleton == "kit":
+        lengths = list(_KIT_LENGTHS)
+    else:
+        raise ValueError(f"default_offsets knows the skeletons 't2m' and 'kit', not {skeleton!r}")
+    return SKELETONS[skeleton].raw_offsets.astype(np.float64) * (height * np.asarray(lengths))[:, None]
+
+
+class SelfBody:
+    """The body a character keeps out of, made by ``self_body``: ``bones`` (nb, 2) int32 (parent, child), ``bone_radius`` (nb,)
+    float32, ``joint_params`` (J, 2) float32 = (r_j, u_j), ``allowed`` (J, nb) bool (bone i acts on joint j), ``pair_mask`` (J,)
+    int32 (bit i of entry j = ``allowed[j, i]``), ``margin``, ``J`` and ``nb``.  All on the CPU."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def on(self, device):
+        """(bone_radius, joint_params, pair_mask) on ``device``, contiguous: the device tables of the launches."""
+        return tuple(v.to(device).contiguous() for v in (self.bone_radius, self.joint_params, self.pair_mask))
+
+
+def _tree_hops(parents):
+    """(J, J) hop counts between the joints of a tree given by its parents."""
+    J = len(parents)
+    hop = np.full((J, J), J, dtype=np.int64)
+    np.fill_diagonal(hop, 0)
+    for c, p in enumerate(parents):
+        if p >= 0:
+            hop[c, p] = hop[p, c] = 1
+    for k in range(J):  # Floyd-Warshall: J <= 32
+        hop = np.minimum(hop, hop[:, k:k + 1] + hop[k:k + 1, :])
+    return hop
+
+
+def segment_distances(p: torch.Tensor, bones) -> torch.Tensor:
+    """The distance of every joint of ``p`` (..., J, 3) to the segment of every bone (u, v) of the same frame: (..., J, nb).  A
+    bone without length is its point.  Plain torch ops."""
+    bones = torch.as_tensor(bones).reshape(-1, 2).tolist()
+    out = []
+    for u, v in bones:
+        a = p[..., u, :].unsqueeze(-2)
+        e, w = p[..., v, :].unsqueeze(-2) - a, p - a
+        den = (e * e).sum(-1)
+        h = torch.where(den > 0, (w * e).sum(-1) / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den)).clamp(0, 1)
+        out.append((w - h[..., None] * e).norm(dim=-1))
+    return torch.stack(out, -1)
+
+
+def self_body(offsets, skeleton="t2m", radii=None, radius_scale=1.0, joint_radius=None, joint_weights=None, margin=0.02, hops=2,
+              pairs=None, rest_joints=False) -> SelfBody:
+    """The capsules a character keeps its own joints out of.  ``offsets`` (J, 3): the bone offsets of the skeleton, as
+    ``motion_mesh.capsule_body`` takes them, or with ``rest_joints=True`` the joints of its rest pose.  Bone c >= 1 is the segment
+    parent(c) -> c (bone index c - 1).  ``radii`` (J,), per bone as ``capsule_body``'s (entry 0, the pelvis sphere, only serves as
+    the pelvis joint's default radius), in the offsets' units; default ``motion_mesh.BODY_RADII[skeleton]`` times the height of
+    the rest pose; both times ``radius_scale``: the capsules are then those of ``capsule_body``.  ``joint_radius`` (J,): r_j,
+    default the radius of joint j's own bone; ``joint_weights`` (J,): u_j, default 1.  ``margin``: m.  Which bone acts on which
+    joint: ``pairs`` (J, J - 1) bool, or by default every pair (j, i) whose joint is more than ``hops`` tree edges from both
+    ends of bone i and that does not penetrate in the rest pose at this margin (shoulder against neck, hip against the other
+    hip).  ValueError for offsets of another shape or not finite, non-finite or non-positive radii or scale, a wrong shape,
+    more than 32 joints, a skeleton without listed radii when ``radii`` is None, a non-finite margin and negative ``hops``."""
+    from .motion_features import get_skeleton
+    from .motion_mesh import BODY_RADII, rest_pose
+    sk = get_skeleton(skeleton)
+    J = int(sk.joints)
+    if J > MAX_SELF_JOINTS:
+        raise ValueError(f"a skeleton of {J} joints: self-collision takes at most {MAX_SELF_JOINTS}")
+    off = np.asarray(offsets.detach().cpu().numpy() if torch.is_tensor(offsets) else offsets, dtype=np.float64)
+    if off.shape != (J, 3) or not np.isfinite(off).all():
+        raise ValueError(f"offsets of shape {off.shape} must be finite ({J}, 3)")
+    rest = off - off[0] if rest_joints else rest_pose(off, sk)
+    radius_scale = _positive(radius_scale, "radius_scale")
+    if radii is None:
+        name = skeleton if isinstance(skeleton, str) else next((k for k in BODY_RADII if get_skeleton(k) is sk), None)
+        if name not in BODY_RADII:
+            raise ValueError("radii are required for a skeleton that BODY_RADII does not list")
+        radii = np.asarray(BODY_RADII[name], np.float64) * (rest[:, 1].max() - rest[:, 1].min())
+    else:
+        radii = np.asarray(radii.detach().cpu().numpy() if torch.is_tensor(radii) else radii, dtype=np.float64)
+        if radii.shape != (J,):
+            raise ValueError(f"radii of shape {radii.shape} must be ({J},)")
+    radii = radii * radius_scale
+    if not (np.isfinite(radii).all() and (radii > 0).all()):
+        raise ValueError(f"radii must be {J} finite positive numbers")
+    margin = float(margin)
+    if not math.isfinite(margin):
+        raise ValueError("margin must be finite")
+    parents = [int(p) for p in sk.parents]
+    bones = [(parents[c], c) for c in range(1, J)]
+    nb = len(bones)
+    jp = joint_params(J, radii if joint_radius is None else joint_radius, joint_weights)
+    rho = torch.tensor(radii[1:], dtype=torch.float32)
+    if pairs is not None:
+        allowed = np.asarray(pairs.detach().cpu().numpy() if torch.is_tensor(pairs) else pairs)
+        if allowed.shape != (J, nb) or allowed.dtype != np.bool_:
+            raise ValueError(f"pairs of shape {allowed.shape} and dtype {allowed.dtype} must be bool ({J}, {nb})")
+        allowed = allowed.copy()
+    else:
+        if isinstance(hops, bool) or int(hops) != hops or int(hops) < 0:
+            raise ValueError(f"hops must be an integer >= 0, not {hops!r}")
+        hop = _tree_hops(parents)
+        ends = np.asarray(bones)
+        far = (hop[:, ends[:, 0]] > int(hops)) & (hop[:, ends[:, 1]] > int(hops))  # (J, nb)
+        d = segment_distances(torch.from_numpy(rest), bones).numpy()
+        clear = margin + jp[:, 0].double().numpy()[:, None] + rho.double().numpy()[None] - d <= 0
+        allowed = far & clear
+    mask = (allowed.astype(np.int64) << np.arange(nb)[None]).sum(1).astype(np.int32)
+    return SelfBody(bones=torch.tensor(bones, dtype=torch.int32).reshape(nb, 2), bone_radius=rho, joint_params=jp,
+                    allowed=torch.from_numpy(allowed), pair_mask=torch.from_numpy(mask), margin=margin, J=J, nb=nb)
+
+
+def _self_joints(joints, lengths, body):
+    P = torch.as_tensor(joints)
+    if P.dim() != 4 or tuple(P.shape[2:]) != (body.J, 3):
+        raise ValueError(f"joints of shape {tuple(P.shape)} must be (B, T, {body.J}, 3)")
+    ln = torch.as_tensor(lengths).flatten().to(torch.int32)
+    if ln.numel() != P.shape[0]:
+        raise ValueError(f"lengths must hold {P.shape[0]} entries")
+    return P, ln
+
+
+@torch.no_grad()
+def self_push(joints, lengths, body: SelfBody):
+    """``(push (B, T, J, 3), depth (B, T, J))`` of ``joints`` (B, T, J, 3) on a GPU against their own ``body``
+    (``mdm_self_push``): push = sum_i pen_i n_i and depth = sum_i pen_i over the allowed bones, zero at and past a length."""
+    P, ln = _self_joints(joints, lengths, body)
+    L.require_cuda(P)
+    dev = P.device
+    P = P.detach().to(torch.float32).contiguous()
+    B, T = P.shape[:2]
+    push, depth = torch.zeros((B, T, body.J, 3), device=dev), torch.zeros((B, T, body.J), device=dev)
+    rho, jp, mask = body.on(dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().mdm_self_push(P.data_ptr(), ln.to(dev).contiguous().data_ptr(), body.bones.data_ptr(), body.nb, rho.data_ptr(),
+                                      jp.data_ptr(), mask.data_ptr(), body.margin, B, T, body.J, push.data_ptr(), depth.data_ptr(),
+                                      L.stream_ptr()), "mdm_self_push")
+    return push, depth
+
+
+@torch.no_grad()
+def self_penetration(joints, lengths, body: SelfBody):
+    """How far a result violates its own body, per sample: ``(depth (B,), share (B,))``.  ``depth``: the deepest penetration
+    of one joint's sphere into one allowed bone's capsule in metres, max(0, r_j + rho_i - d_i), the margin not counted;
+    ``share``: the share of the sample's valid (t, j) inside some allowed capsule's margin.  Joints of weight 0 are ignored.
+    Plain torch ops on the device the joints are on: the check for a result, like ``penetration``."""
+    P, ln = _self_joints(joints, lengths, body)
+    B, T = P.shape[:2]
+    r = body.joint_params[:, 0].to(P.device, P.dtype)
+    rho = body.bone_radius.to(P.device, P.dtype)
+    on = (body.allowed & (body.joint_params[:, 1] > 0)[:, None]).to(P.device)
+    depth, share = P.new_zeros(B), P.new_zeros(B)
+    for b in range(B):
+        n = min(max(int(ln[b]), 0), T)
+        if n == 0:
+            continue
+        over = r[None, :, None] + rho[None, None] - segment_distances(P[b, :n], body.bones)  # (n, J, nb)
+        depth[b] = torch.where(on[None], over.clamp(min=0), torch.zeros_like(over)).max()
+        share[b] = (on[None] & (over + body.margin > 0)).any(-1).to(P.dtype).mean()
+    return depth, share
+
+
+def self_scratch_floats(B: int, T: int, F: int) -> int:
+    """Floats of the scratch ``mdm_self_targets`` needs."""
+    return int(L.lib().mdm_self_targets_scratch_floats(B, T, F))
+
+
+def self_max_frames() -> int:
+    """The longest T ``mdm_self_targets`` takes (the recovery's LDS limit)."""
+    return int(L.lib().mdm_self_max_frames())
+
+
+def self_launch(x0, lengths, mean_rows, std_rows, body: SelfBody, dev_tables, weight, static_targets, static_weights, joints,
+                scratch, targets, weights):
+    """One ``mdm_self_targets`` call on the current stream: every tensor is the caller's, on the device, float32 (int32 lengths)
+    and contiguous; ``dev_tables`` = ``body.on(device)``, ``scratch`` ``self_scratch_floats`` floats, the static pair both or
+    None.  Allocation free: the sampling runner calls it inside graph capture."""
+    rho, jp, mask = dev_tables
+    B, T, F = x0.shape
+    L.check(L.lib().mdm_self_targets(
+        x0.data_ptr(), lengths.data_ptr(), mean_rows.data_ptr(), std_rows.data_ptr(), body.bones.data_ptr(), body.nb, rho.data_ptr(),
+        jp.data_ptr(), mask.data_ptr(), body.margin, float(weight), L.ptr(static_targets), L.ptr(static_weights), B, T, F,
+        joints.data_ptr(), scratch.data_ptr(), targets.data_ptr(), weights.data_ptr(), L.stream_ptr()), "mdm_self_targets")
+
+
+@torch.no_grad()
+def self_targets(x0, lengths, mean, std, body: SelfBody, weight, static_targets=None, static_weights=None, return_joints=False):
+    """The device call of self-collision avoidance on its own: from ``x0`` (B, T, F) on a GPU and ``mean`` / ``std`` (F,) or
+    (B, F), ``(targets, weights)``, both (B, T, J, 3), as the guidance calls take them: P + push under weight * u_j where a
+    joint penetrates, weight 0 elsewhere, and the static pair (B, T, J, 3), both or neither, wherever it carries a weight.
+    ``return_joints``: also P (B, T, J, 3)."""
+    L.require_cuda(x0)
+    dev = x0.device
+    x = x0.detach().to(torch.float32).contiguous()
+    if x.dim() != 3 or joints_for_feats(x.shape[2]) != body.J:
+        raise ValueError(f"x0 of shape {tuple(x.shape)} must be (B, T, F) with {body.J} joints")
+    B, T, F = x.shape
+    ln = torch.as_tensor(lengths).flatten().to(torch.int32)
+    if ln.numel() != B:
+        raise ValueError(f"lengths must hold {B} entries")
+    if (static_targets is None) != (static_weights is None):
+        raise ValueError("static_targets and static_weights go together: give both or neither")
+    weight = float(weight)
+    if not (math.isfinite(weight) and weight >= 0):
+        raise ValueError(f"weight must be finite and >= 0, not {weight}")
+    if T > self_max_frames():
+        raise ValueError(f"T = {T}: self-collision takes at most {self_max_frames()} frames")
+    sg = sw = None
+    if static_targets is not None:
+        sg, sw = (torch.as_tensor(v).detach().to(dev, torch.float32) for v in (static_targets, static_weights))
+        if tuple(sg.shape) != (B, T, body.J, 3):
+            raise ValueError(f"static_targets of shape {tuple(sg.shape)} must be {(B, T, body.J, 3)}")
+        sw = expand_to_static(sw, sg.shape)
+        sg = sg.contiguous()
+    shape = (B, T, body.J, 3)
+    joints, targets, weights = (torch.zeros(shape, device=dev) for _ in range(3))
+    scratch = torch.empty(max(self_scratch_floats(B, T, F), 1), device=dev)
+    mean_t = _rows(mean, B, F, "mean").to(dev).contiguous()
+    std_t = _rows(std, B, F, "std").to(dev).contiguous()
+    with torch.cuda.device(dev):
+        self_launch(x, ln.to(dev).contiguous(), mean_t, std_t, body, body.on(dev), weight, sg, sw, joints, scratch, targets, weights)
+    return (targets, weights, joints) if return_joints else (targets, weights)
+
+
+def expand_to_static(w, shape):
+    """Static target weights aligned on their leading dims to ``shape`` (B, T, J, 3), dense."""
+    if w.dim() > 4 or tuple(w.shape) != tuple(shape)[:w.dim()]:
+        raise ValueError(f"static_weights of shape {tuple(w.shape)} must lead {tuple(shape)}")
+    return w.reshape(tuple(w.shape) + (1,) * (4 - w.dim())).expand(shape).contiguous()

@@ -321,11 +321,15 @@ class DDPMTrainer(object):
         out.  With ``pin_targets=True`` every contact's meeting point, computed from the final joints, joins both characters'
         pin targets (``postprocess.pin_limbs`` decides what it can pin).  ValueError for ``contacts`` without ``mutual``, a
         scene of more characters than ``batch_size`` and one whose (C - 1) x len(bones) partner capsules do not fit the
-        ``motion_scene.MAX_TRACKS`` tracks of a frame (give a ``bones=`` subset)."""
+        ``motion_scene.MAX_TRACKS`` tracks of a frame (give a ``bones=`` subset).  ``self_collision`` goes to
+        every stage of the sequential mode with the rest of ``**kw``; with ``mutual=True`` it is a NotImplementedError."""
         from . import motion_scene as MS
         J = (dim_pose + 1) // 12
         if contacts is not None and not mutual:
             raise ValueError("contacts join characters that are sampled together: pass mutual=True")
+        if mutual and kw.get("self_collision") is not None:
+            raise NotImplementedError("self-collision avoidance for characters sampled together is out of scope (DESIGN.md §33): "
+                                      "both rewrite the guidance's targets on every step; use mutual=False")
         if mutual:
             return self._generate_mutual(scenes, dim_pose, mean, std, radius, margin, weight, bones, seed, contacts, kw)
         pin = bool(kw.pop("pin_targets", False))
@@ -506,7 +510,7 @@ class DDPMTrainer(object):
     def generate_long(self, scripts, dim_pose, *, overlap=20, blend="linear", batch_size=32, seed=None, sampler="ddpm",
                       sample_steps=None, eta=0.0, progress=False, control_joints=None, control_weights=None, control_scale=None,
                       control_iters=None, scene=None, scene_joint_radius=None, scene_joint_weights=None, scene_tracks=None,
-                      terrain=None, terrain_stand=None, terrain_stand_threshold=0.5, **conditioning):
+                      terrain=None, terrain_stand=None, terrain_stand_threshold=0.5, self_collision=None, **conditioning):
         """Long motions: ``scripts`` is a list of long motions, each a list of ``(caption, length)``
         segments of at most ``num_frames`` frames; neighbouring segments share ``overlap`` canvas frames, whose eps is
         blended on every step (``blend`` "linear" crossfade or "uniform") while x_T and the step noise come from the left
@@ -534,7 +538,10 @@ class DDPMTrainer(object):
         canvas frame, with ``terrain_stand`` None, ``"contacts"`` (over ``terrain_stand_threshold``) or one
         (canvas_len, J) array of stand weights per motion, under the same.
         The other per-motion inputs are ``**conditioning``, checked by
-        ``motion_long.canvas_conditioning``."""
+        ``motion_long.canvas_conditioning``.  ``self_collision`` is not supported on a canvas (NotImplementedError)."""
+        if self_collision is not None:
+            raise NotImplementedError("self-collision avoidance over a long motion's canvas is out of scope (DESIGN.md §33): "
+                                      "generate the motion in one window, or leave self_collision out")
         m = self._model()
         self.eval_mode()
         plans = ML.script_plans(scripts, overlap, m.num_frames)

@@ -46,6 +46,9 @@ G x G height field and ``terrain_stand="contacts"``:
 ``--partners`` measures characters sampled together: 16 scenes of two characters against the same rows
 with 21 static tracks and against the sequential two-stage ``generate_together``, DDIM-50 and DPM-Solver++(2M)-20:
     timeout -k 10 900 python tools/sample_time.py --partners --reps 5 --precisions 1 > profiles/partners_sample_time.txt
+``--self`` measures self-collision avoidance: a controlled generation (every joint's height, ``control_iters``
+1) without and with ``self_collision``, DDIM-50 and DPM-Solver++(2M)-20, alternating, as for ``--edit``:
+    timeout -k 10 900 python tools/sample_time.py --self --reps 5 --precisions 1 > profiles/self_sample_time.txt
 ``--control I --scene K --tracks far,near,near_nobounds`` measures tracks: the controlled generation with
 a scene of K primitives without and with the 21 capsule tracks of a character (``motion_scene.character_tracks``): far from the
 motion (every joint outside the frames' balls), around it, and around it without the broad phase.
@@ -88,6 +91,8 @@ def main():
                     "against control with the scene alone")
     ap.add_argument("--partners", action="store_true", help="time characters sampled together (16 scenes of two, 21 bones) "
                     "against 21 static character tracks and against the two-stage sequential generate_together")
+    ap.add_argument("--self", dest="self_", action="store_true", help="time self-collision avoidance against the same controlled "
+                    "generation without it")
     ap.add_argument("--terrain", type=int, default=None, help="G (with --control): time a G x G terrain with "
                     'terrain_stand="contacts" against joint control alone')
     ap.add_argument("--long", type=int, default=None, help="H: time long motions (4 windows each, H shared frames) "
@@ -109,6 +114,8 @@ def main():
     caps = [f"caption {i}" for i in range(B)]
     if a.partners:
         return partners_main(a, tr, m, caps, B, T)
+    if a.self_:
+        return self_main(a, tr, m, caps, B, T)
     if a.edit:
         return edit_main(a, tr, m, caps, length, B, T)
     if a.compose:
@@ -551,6 +558,54 @@ def partners_main(a, tr, m, caps, B, T):
         spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
         print(f"{r['precision']:>9} {r['against']:>11} {r['sampler']:>22} {r['other_ms']:>9.1f} {r['mutual_ms']:>10.1f} {spread:>22} "
               f"{r['diff_us_per_step']:>8.1f}")
+
+
+def self_main(a, tr, m, caps, B, T):
+    # The same controlled generation (every joint's height as a target, as partners_main: both modes run the guidance with
+    # targets) without and with self_collision, in alternating pairs: what the producer (the two launches of
+    # the joints and the push launch, every step) costs on top of the guidance it feeds.  The de-normalisation, the step and the
+    # small weight are partners_main's, for the same reason: the unclipped random-weight samples are clouds, and the warm-up
+    # asserts finite results; the cost does not depend on the weight.
+    mean, std = torch.zeros(263), torch.full((263,), 0.002)
+    std[0], std[4:67] = 1e-4, 0.0005
+    tg, w = torch.zeros(B, T, 22, 3), torch.zeros(B, T, 22)
+    tg[..., 1], w[:] = 1.0, 1.0
+    rows = []
+    for prec in [int(p) for p in a.precisions.split(",")]:
+        m.precision = prec
+        m.invalidate()
+        for sampler, steps, n in (("ddim", 50, 50), ("dpmpp2m", 20, 20)):
+            opts = dict(seed=0, sampler=sampler, sample_steps=steps, control_scale=5.0, control_iters=1, sigma=0.0, batch_size=B,
+                        control_joints=tg, control_weights=w)
+
+            def gen(own):
+                return tr.generate_joints(caps, torch.full((B,), T), 263, mean, std,
+                                          self_collision=dict(weight=0.01) if own else None, **opts)
+            for own in (False, True):  # warm-up
+                assert all(torch.isfinite(j).all() for j in gen(own)), own
+            ts = {False: [], True: []}
+            for _ in range(a.reps):
+                for own in (False, True):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    gen(own)
+                    torch.cuda.synchronize()
+                    ts[own].append((time.perf_counter() - t0) * 1e3)
+            med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+            diff = sorted(c - p for p, c in zip(ts[False], ts[True]))
+            name = {"ddim": "DDIM", "dpmpp2m": "DPM-Solver++(2M)"}[sampler] + f"-{n}"
+            line = dict(precision=prec, sampler=name, steps=n, B=B, T=T, plain_ms=round(med[False], 2), self_ms=round(med[True], 2),
+                        diff_ms_median=round(diff[len(diff) // 2], 2), diff_ms_min=round(diff[0], 2), diff_ms_max=round(diff[-1], 2),
+                        diff_us_per_step=round(diff[len(diff) // 2] / n * 1e3, 1), plain_reps_ms=[round(t, 2) for t in ts[False]],
+                        self_reps_ms=[round(t, 2) for t in ts[True]])
+            rows.append(line)
+            print(json.dumps(line), flush=True)
+    print(f"\nconfigs[1] shape B={B} T={T}: joint control (every joint's height, control_iters 1) without and with self_collision "
+          f"(22 joints x 21 bones, default mask); {torch.cuda.get_device_name(0)}")
+    print(f"{'precision':>9} {'sampler':>22} {'plain ms':>9} {'self ms':>9} {'diff ms (min..max)':>22} {'us/step':>8}")
+    for r in rows:
+        spread = f"{r['diff_ms_median']:+.2f} ({r['diff_ms_min']:+.2f}..{r['diff_ms_max']:+.2f})"
+        print(f"{r['precision']:>9} {r['sampler']:>22} {r['plain_ms']:>9.1f} {r['self_ms']:>9.1f} {spread:>22} {r['diff_us_per_step']:>8.1f}")
 
 
 def long_main(a, tr, m, caps, B, T):
